@@ -7,7 +7,9 @@ Workload of the headline line = C4 of BASELINE.json as written: 600 frames of 38
 every rank takes a contiguous block of 600/N frames (sharding.shard_frames), i.e. STRONG scaling -- the total work is fixed.  A step = one
 pass of the whole hot path (hevcdl_encode_frames_dev: CNN + RD search) over the rank's frames, which are already resident in HBM.  Frames
 are independent, so there is no data-path collective; RCCL only gathers the per-frame rate records.
-Prints ONE JSON line on rank 0 (metric of BASELINE.json + roofline + cpu_baseline); on the single-GPU run it additionally carries
+Prints ONE JSON line on rank 0: the metric of BASELINE.json and the roofline of the timed steps.  A plain run does nothing else: set-up, warm-up, the
+timed steps, the outputs of the last step when --dump-outputs DIR is given, the line.  With --full the line also carries the latency floor, the scale
+projection, cpu_baseline, and on N > 1 the weak / wavefront legs; on the single-GPU --full run it additionally carries
   "saturated"    the same step over 2048 frames per GPU (every wave of the chip owns a frame: the throughput ceiling of the kernel),
   "c2"           C2 of BASELINE.json (10 frames of 1920x1080) next to the reference encoder on 10 host cores in the same run,
   "parity_check" the reference encoder's own CTU records / reconstruction against the GPU's: whole frames of the timed job (every CTU row, the ragged
@@ -440,11 +442,83 @@ def alloc(torch, hevcdl_amd, dev, n, frame_bytes, ctus):
             torch.zeros((n, frame_bytes), dtype=torch.uint8, device=dev), torch.zeros((n, hevcdl_amd.STATS_DTYPE.itemsize), dtype=torch.uint8, device=dev))
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SEED = 20261016
+DUMP_ALL_CTUS_MAX = 1250000       # bits / dist / cost of every CTU up to this many (24 bytes each), a seeded sample of this many beyond
+DUMP_RECORD_CTUS = 512            # CTUs whose whole record (and labels) is written: 35 904 bytes each as float32
+DUMP_RECON_SAMPLES = 1 << 20      # reconstruction samples (float32)
+
+
+def dump_outputs(torch, hevcdl_amd, out_dir, tensors, n_frames, frame_ids, prefix="", budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: what hevcdl_encode_frames_dev handed back in the last timed step, as float32 / float64 .npy files (at most `budget` bytes in all).
+    Every index sample below is drawn from a fixed seed and depends only on the job's shape, so two builds run with the same arguments write the same
+    positions:
+      frame_ids        [F]          the job's frame indices this rank encoded (float64)
+      stats            [F, 5]       per frame: SSE Y / Cb / Cr before the in-loop filters, estimated bits, CTUs (float64)
+      ctu_bits / ctu_dist / ctu_cost   [F, ctus] (float64) for every CTU, or [n] over the seeded flat CTU indices in ctu_all_index when there are more
+      ctu_sample_index [k]          flat CTU indices (frame * ctus + ctu) of the CTUs whose whole record is written
+      labels           [k, 16]      the CNN's depth labels of those CTUs (float32)
+      rec_<field>      [k, ...]     every field of hevcdl_ctu_record of those CTUs (float32; bits / dist / cost float64)
+      recon_sample     [m]          reconstruction samples (before the in-loop filters) at seeded flat positions of the [F, frame_bytes] buffer (float32)"""
+    yuv, labels, records, recon, stats = tensors
+    if n_frames <= 0:
+        return 0
+    os.makedirs(out_dir, exist_ok=True)
+    rec_dt, st_dt = hevcdl_amd.REC_DTYPE, hevcdl_amd.STATS_DTYPE
+    ctus = records.shape[1]
+    n_ctus = n_frames * ctus
+    scale = budget / DUMP_BUDGET_BYTES          # (a rank of an N-rank run writes its own shard within 1 / N of the budget)
+    all_max, rec_ctus, recon_samples = int(DUMP_ALL_CTUS_MAX * scale), max(1, int(DUMP_RECORD_CTUS * scale)), max(1, int(DUMP_RECON_SAMPLES * scale))
+    rng = np.random.default_rng(DUMP_SEED)
+    out = {"frame_ids": np.asarray(frame_ids, np.float64)}
+    st = np.frombuffer(stats[:n_frames].contiguous().cpu().numpy().tobytes(), dtype=st_dt)
+    out["stats"] = np.concatenate([st["sse"].astype(np.float64), st["est_bits"].astype(np.float64)[:, None], st["ctus"].astype(np.float64)[:, None]], axis=1)
+    # bits / dist / cost: 16 contiguous bytes of every record, sliced on the device (the whole records buffer is ~15 KB a CTU)
+    off = rec_dt.fields["bits"][1]
+    assert rec_dt.fields["dist"][1] == off + 4 and rec_dt.fields["cost"][1] == off + 8
+    flat = records[:n_frames].reshape(n_ctus, rec_dt.itemsize)
+    if n_ctus <= all_max:
+        tail = flat[:, off:off + 16].contiguous().cpu().numpy()
+        shape = (n_frames, ctus)
+    else:
+        all_idx = np.sort(rng.choice(n_ctus, all_max, replace=False))
+        tail = flat[torch.from_numpy(all_idx).to(flat.device), off:off + 16].contiguous().cpu().numpy()
+        shape = (all_max,)
+        out["ctu_all_index"] = all_idx.astype(np.float64)
+    out["ctu_bits"] = tail[:, 0:4].copy().view("<u4").astype(np.float64).reshape(shape)
+    out["ctu_dist"] = tail[:, 4:8].copy().view("<u4").astype(np.float64).reshape(shape)
+    out["ctu_cost"] = tail[:, 8:16].copy().view("<f8").reshape(shape)
+    # whole records and labels of a seeded sample of CTUs
+    k = min(n_ctus, rec_ctus)
+    idx = np.sort(rng.choice(n_ctus, k, replace=False))
+    idx_t = torch.from_numpy(idx).to(flat.device)
+    out["ctu_sample_index"] = idx.astype(np.float64)
+    out["labels"] = labels[:n_frames].reshape(n_ctus, 16)[idx_t].cpu().numpy().astype(np.float32)
+    recs = np.frombuffer(flat[idx_t].contiguous().cpu().numpy().tobytes(), dtype=rec_dt)
+    for name in rec_dt.names:
+        out["rec_" + name] = recs[name].astype(np.float64 if name in ("bits", "dist", "cost") else np.float32)
+    # reconstruction samples at seeded positions
+    rflat = recon[:n_frames].reshape(-1)
+    m = min(rflat.numel(), recon_samples)
+    ridx = np.sort(rng.choice(rflat.numel(), m, replace=False)) if m < rflat.numel() else np.arange(m)
+    out["recon_sample"] = rflat[torch.from_numpy(ridx).to(rflat.device)].cpu().numpy().astype(np.float32)
+    total = sum(v.nbytes for v in out.values())
+    if total > budget:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte budget" % (total, budget))
+    for name, v in out.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), v)
+    return total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=3, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true", help="also run every measurement and check beside the headline (latency floor, scale projection, weak / wavefront "
+                                                         "legs, CPU baseline + parity, CNN label check, e2e, saturated, C2); the --no-* switches below apply to these")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step computed to DIR/<name>.npy (float32 / float64, "
+                                                                         "at most 64 MB in all: seeded samples of the larger outputs)")
     ap.add_argument("--width", type=int, default=3840)
     ap.add_argument("--height", type=int, default=2160)
     ap.add_argument("--qp", type=int, default=32)
@@ -461,6 +535,8 @@ def main():
     ap.add_argument("--cpu-procs", type=int, default=0)
     ap.add_argument("--cpu-baseline", default="reference", choices=["reference", "port"], help="reference: oracle/_ref/TAppEncoder_ref when present; port: the plain-C oracle")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import hevcdl_amd
@@ -499,9 +575,12 @@ def main():
     labels, records, recon, stats = alloc(torch, hevcdl_amd, dev, max(1, Fr), enc.frame_bytes, ctus)
     elapsed, prof = timed_steps(torch, enc, (yuv, labels, records, recon, stats), Fr, a.steps, a.warmup, barrier)
     rd_launch = enc.last_rd_launch()
+    if a.dump_outputs:        # before anything else writes the buffers: what the last timed step handed back
+        dump_outputs(torch, hevcdl_amd, a.dump_outputs, (yuv, labels, records, recon, stats), Fr, list(mine), "" if world == 1 else "rank%d_" % rank,
+                     DUMP_BUDGET_BYTES // max(1, world))
     # one frame alone (outside the timed steps): the serial CTU chain of a frame bounds what any sharding of the job can reach
     floor_s = None
-    if Fr > 0 and not a.no_latency_floor:
+    if a.full and Fr > 0 and not a.no_latency_floor:
         torch.cuda.synchronize(dev)
         t1 = time.perf_counter()
         enc.encode_frames_dev(yuv.data_ptr(), 1, labels.data_ptr(), records.data_ptr(), recon.data_ptr(), stats.data_ptr(), torch.cuda.current_stream().cuda_stream)
@@ -532,7 +611,7 @@ def main():
     # frame's latency rather than the machine -- so every rank also runs the WHOLE 600-frame shape on frames of its own (1 warm-up + 1 timed step between barriers,
     # max over ranks): value = N x 600 frames' CTUs / that time.
     weak = None
-    if world > 1 and a.weak_frames > 0:
+    if a.full and world > 1 and a.weak_frames > 0:
         Fw = a.weak_frames
         ew = hevcdl_amd.Encoder(W, H, qp, max_frames=Fw, device=local)
         yw = synth_frames_torch(torch, dev, W, H, [rank * Fw + i for i in range(Fw)], seed=1000)
@@ -548,7 +627,7 @@ def main():
         torch.cuda.empty_cache()
     # ... and the job itself once more with WaveFrontSynchro 1 (extra key, not the headline: DESIGN.md section 5e): the rank's share of the job's frames, rows as units
     wave_n = None
-    if world > 1 and not a.no_wavefront:
+    if a.full and world > 1 and not a.no_wavefront:
         ewf = hevcdl_amd.Encoder(W, H, qp, max_frames=max(1, per_rank), device=local, wavefront=True)
         elf, prf = timed_steps(torch, ewf, (yuv, labels, records, recon, stats), Fr, 1, 1, barrier)
         tmax = torch.tensor([elf], dtype=torch.float64, device=cdev)
@@ -591,7 +670,7 @@ def main():
                                    "executed_mflop_per_ctu": 2e-6 * CNN_CONV_MACS_EXECUTED, "useful_mflop_per_ctu": 2e-6 * CNN_CONV_MACS,
                                    "head_kernel_ms": prof["cnn_ms"] / max(1, prof["cnn_launches"]) - 1e3 * cnn_s,
                                    "note": "useful_frac = the graph's own multiply-accumulates (95.2 MFLOP per CTU) against the dense f16 peak: the distance from the roof.  frac prices the MFMA products ISSUED: three per multiply-accumulate in conv2 / conv3 (f16 hi/lo split operands for f32-like accuracy; the f32 MFMA runs at 1/16 of the f16 rate), 320 per output of the 5x5 layers (75 taps as 5 k-steps of 16 raw split words, two MFMAs a step): how busy the matrix pipes are; measured with HIP events on the launch stream over the timed steps"}
-        if world == 1 and is_c4 and not a.no_projection:
+        if a.full and world == 1 and is_c4 and not a.no_projection:
             # What the frame-sharded job will take on N GPUs, from this GPU alone: a rank's share of the job is a launch of 600 / N frames (frames are independent, the
             # only collective gathers 8 bytes per frame), timed here as one whole step (label CNN + decisions) each.  The driver's SCALE run can be checked against it.
             proj = {1: elapsed / a.steps}
@@ -630,7 +709,7 @@ def main():
             out["latency_floor_s"] = floor_s
             out["strong_scaling_ceiling"] = {"value": F * ctus / floor_s, "unit": "CTUs/s",
                                              "note": "the whole job in the time one frame takes alone on a GPU (rank 0: %.3f s): more GPUs than frames-per-CU can use do not help" % floor_s}
-        if world == 1:
+        if a.full and world == 1:
             if not a.no_cpu_baseline:       # the CPU baseline is timed on rank 0 of the single-GPU run only
                 nb = min(Fr, 256)                      # frames sampled for the parity check
                 cx = (W + 63) // 64
@@ -702,8 +781,7 @@ def main():
                     out["wavefront"]["c2"]["gpu_over_cpu_reference_default_cfg"] = out["wavefront"]["c2"]["value"] / c2["cpu_reference"]["value"]
                 e3.close()
         print(json.dumps(out), flush=True)
-    if world > 1 or rank != 0:
-        enc.close()
+    enc.close()
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -16,7 +16,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 REF_ENC = os.path.join(HERE, "_ref", "TAppEncoder_ref")
 REF_DEC = os.path.join(HERE, "_ref", "TAppDecoder_ref")
-REF_CFG = "/root/reference/encoder_intra_main.cfg"
+REF_CFG = os.path.join(os.path.dirname(HERE), "tests", "golden", "encoder_intra_main.cfg")      # the reference's own encoder_intra_main.cfg, kept as a fixture
 ORACLE_SO = os.path.join(HERE, "_build", "libhm_oracle.so")
 
 # hevcdl_ctu_record (include/hevcdl.h) as a numpy dtype: 15120 bytes

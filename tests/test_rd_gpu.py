@@ -312,7 +312,8 @@ def test_bench_two_ranks_on_one_gpu_give_the_single_rank_line(tmp_path):
     import subprocess
     import sys
     root = os.path.join(os.path.dirname(GOLD), "..")
-    common = ["--steps", "1", "--warmup", "0", "--width", "256", "--height", "192", "--frames", "6", "--no-cpu-baseline", "--no-c2", "--no-e2e", "--saturated-frames", "0", "--weak-frames", "4"]
+    common = ["--full", "--steps", "1", "--warmup", "0", "--width", "256", "--height", "192", "--frames", "6", "--no-cpu-baseline", "--no-c2", "--no-e2e", "--saturated-frames", "0",
+              "--weak-frames", "4"]
     env = dict(os.environ, HEVCDL_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r1 = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1"] + common, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r1.returncode == 0, r1.stdout[-1500:] + r1.stderr[-1500:]
@@ -334,6 +335,54 @@ def test_bench_two_ranks_on_one_gpu_give_the_single_rank_line(tmp_path):
     assert "issue" in one["roofline"]                            # the instruction-issue bound (None unless a counter pass of this kernel source and launch shape is committed)
     for line in (one, two):
         assert line["value"] > 0 and line["latency_floor_s"] > 0 and line["strong_scaling_ceiling"]["value"] > 0 and "roofline" in line
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain bench.py run (no --full) prints the headline line alone, timed over --steps steps, and --dump-outputs writes what the last step computed:
+    float32 / float64 arrays within 64 MB, the same from run to run, equal to a direct hevcdl_encode_frames_dev call on the same synthetic frames."""
+    import json
+    import subprocess
+    import sys
+    import torch
+    import hevcdl_amd
+    root = os.path.join(os.path.dirname(GOLD), "..")
+    sys.path.insert(0, root)
+    import bench
+    W, H, F = 256, 192, 6
+    args = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--width", str(W), "--height", str(H), "--frames", str(F)]
+    lines = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + args + ["--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    one = lines[0]
+    assert one["steps"] == 2 and one["warmup"] == 1 and one["unit"] == "CTUs/s" and one["higher_is_better"] is True and one["value"] > 0 and one["ms_per_step"] > 0
+    assert abs(one["value"] - F * one["config"]["ctus_per_frame"] * 1e3 / one["ms_per_step"]) < 1e-6 * one["value"]
+    for key in ("latency_floor_s", "strong_scaling_ceiling", "scale_projection", "cpu_baseline", "parity_check", "cnn_label_check", "e2e", "wavefront", "saturated", "c2"):
+        assert key not in one, key
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names and names == sorted(os.listdir(tmp_path / "b"))
+    got = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values()) and sum(v.nbytes for v in got.values()) <= 64 << 20
+    for n in names:
+        assert np.array_equal(got[n[:-4]], np.load(tmp_path / "b" / n)), n
+    # the same step, called directly
+    dev = torch.device("cuda", 0)
+    enc = hevcdl_amd.Encoder(W, H, 32, max_frames=F)
+    yuv = bench.synth_frames_torch(torch, dev, W, H, list(range(F)), seed=1000)
+    labels, records, recon, stats = bench.alloc(torch, hevcdl_amd, dev, F, enc.frame_bytes, enc.ctus)
+    enc.encode_frames_dev(yuv.data_ptr(), F, labels.data_ptr(), records.data_ptr(), recon.data_ptr(), stats.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize(dev)
+    enc.close()
+    recs = np.frombuffer(records.cpu().numpy().tobytes(), hevcdl_amd.REC_DTYPE).reshape(F, -1)
+    st = np.frombuffer(stats.cpu().numpy().tobytes(), hevcdl_amd.STATS_DTYPE)
+    idx = got["ctu_sample_index"].astype(np.int64)
+    assert np.array_equal(got["frame_ids"], np.arange(F)) and np.array_equal(got["stats"][:, :3], st["sse"]) and np.array_equal(got["stats"][:, 3], st["est_bits"])
+    assert np.array_equal(got["ctu_bits"], recs["bits"]) and np.array_equal(got["ctu_dist"], recs["dist"]) and np.array_equal(got["ctu_cost"], recs["cost"])
+    assert np.array_equal(got["labels"], labels.cpu().numpy().reshape(-1, 16)[idx])
+    for k in FIELDS:
+        assert np.array_equal(got["rec_" + k], recs.reshape(-1)[k][idx]), k
+    assert np.array_equal(got["recon_sample"], recon.cpu().numpy().reshape(-1))      # (a buffer this small is written whole)
 
 
 @pytest.mark.skipif(not os.path.exists(os.path.join(os.path.dirname(GOLD), "..", "oracle", "_ref", "TAppEncoder_ref")), reason="reference build (oracle/_ref) not present")
