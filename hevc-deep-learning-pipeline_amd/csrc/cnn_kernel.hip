@@ -91,8 +91,12 @@ __device__ __forceinline__ void bn_fold(double s, double ss, double n, float gam
 // v -> one word: low half f16(v) (rounded toward zero), high half f16(v - low half).
 // Accuracy of the pair, stated exactly: hi carries 11 significant bits, lo the next 11 WHILE v - hi is a normal f16, i.e. for |v| >= 2^-3 (22 bits, 4.8e-7
 // relative); below that lo is an f16 subnormal and the pair's error is bounded absolutely instead, by 2^-25 (lo's last place), and a |v| < 2^-25 remainder is
-// lost.  The operands here are activations in [0, ~8] and weights of magnitude 1e-3 .. 1: the absolute floor (3e-8 per operand) is what the 4.2e-5 logit error
+// lost.  The operands of the shipped checkpoint are activations in [0, ~8] and weights of magnitude 1e-3 .. 1: the absolute floor (3e-8 per operand) is what the 4.2e-5 logit error
 // measured against the fp32 graph consists of (tests/test_cnn_gpu.py bounds it at 1e-3; bench.py cnn_label_check counts the labels that differ: 0 of 32 640).
+// Outside that range tests/test_cnn_numerics_gpu.py holds the kernel to 16 x the f32 graph's own distance from an f64 graph (about 3e-4 with the shipped weights): flat,
+// single-impulse, 1-pixel-pattern, full-range-noise and strongly coloured CTUs (flat maps: variance 0, gain 1 / sqrt(eps)), and weight blobs with negative and zero gamma
+// (the min-pool branch below), a layer's weights times 2^-12 (the weight scale on its 2^24 cap) and 2^+10, one weight of 100 among weights of 1e-4 (the others then lie
+// on the pair's absolute floor), zero biases and biases of +-4 on a flat input (beta' = beta - mean * alpha against x * alpha).  profiles/cnn_numerics.txt has the figures.
 // This relies on the MFMA NOT flushing f16 subnormal inputs, which holds on gfx950 (CDNA3 / 4) and not on gfx90a: hence the guard.
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
 #error "cnn_kernel.hip: the split-f16 operand form is validated for gfx950 only (f16 subnormal MFMA inputs must not be flushed)"

@@ -394,6 +394,35 @@ def gen_cnn(model, src):
     print("cnn fixtures:", n, "CTUs,", m, "label tuples; label histogram", np.bincount(labels.ravel(), minlength=4))
 
 
+def gen_cnn_cases():
+    """F-cnn-4: the adversarial corpus of oracle/cnn_cases.py (flat, single impulses, 1-pixel patterns, full-range noise, strongly coloured CTUs) through the reference
+    model as cnn_f1 goes through it (training-mode BatchNorm, the way the reference runs), and through a freshly loaded one after model.eval().  Only logits, labels and
+    the corpus' seed / version are stored: the CTUs are regenerated from the seed (tests/test_cnn_numerics.py)."""
+    import torch
+    import cnn_cases
+    import cnn_oracle
+    ctus, spans = cnn_cases.stacked()
+    out = {}
+    for key, ev in (("logits", False), ("logits_eval", True)):
+        model, _, src = load_ref_model()
+        if ev:
+            model.eval()
+        lg = np.zeros((len(ctus), 4, 16), np.float32)
+        with torch.no_grad():
+            for i in range(len(ctus)):
+                x = torch.from_numpy(ctus[i].astype(np.float32) / 255.0).permute(2, 0, 1)   # ToTensor: HWC u8 -> CHW /255
+                for q in range(4):
+                    ox, oy = (q % 2) * 32, (q // 2) * 32
+                    lg[i, q] = model(x[:, oy:oy + 32, ox:ox + 32].unsqueeze(0).contiguous(), x.unsqueeze(0))[0].numpy()
+        out[key] = lg
+    ref_labels = ref_label_fn(src)
+    labels = np.array([ref_labels(out["logits"][i]) for i in range(len(ctus))], np.uint8)
+    labels_eval = cnn_oracle.labels_from_logits(out["logits_eval"])          # post-processing pinned by cnn_f1 / cnn_f2
+    np.savez_compressed(os.path.join(GOLD, "cnn_f4.npz"), seed=cnn_cases.SEED, version=cnn_cases.VERSION, groups=np.array(cnn_cases.GROUPS),
+                        sizes=np.array([spans[g].stop - spans[g].start for g in cnn_cases.GROUPS]), labels=labels, labels_eval=labels_eval, **out)
+    print("cnn corpus fixture:", len(ctus), "CTUs; label histogram", np.bincount(labels.ravel(), minlength=4))
+
+
 def gen_cnn_pictures(model, src):
     """F-cnn-3: whole pictures through the reference's OWN frame loop -- use_model.py from `total_frames = ...` to the end of
     the file (lines 72-125: CTU count :80, raster order :86-87, quadrant origin :89-90, img.crop beyond the picture :91-92, ToTensor :93-94, the four
@@ -550,7 +579,7 @@ def gen_bd():
 
 if __name__ == "__main__":
     os.makedirs(GOLD, exist_ok=True)
-    what = sys.argv[1:] or ["rd", "rdtiles", "rd10", "rdx", "rdtools", "rdlf", "rdwpp", "cnn", "weights", "bd", "full", "bdanchor", "stage", "cnneval", "cnnpic", "cnnchain"]
+    what = sys.argv[1:] or ["rd", "rdtiles", "rd10", "rdx", "rdtools", "rdlf", "rdwpp", "cnn", "weights", "bd", "full", "bdanchor", "stage", "cnneval", "cnnpic", "cnnchain", "cnncases"]
     if "stage" in what:
         gen_stage_traces()
     if "rd" in what:
@@ -580,6 +609,8 @@ if __name__ == "__main__":
         gen_cnn_pictures(model, src)
     if "cnnchain" in what:
         gen_cnn_label_chain(load_ref_model()[2])
+    if "cnncases" in what:
+        gen_cnn_cases()
     if "bd" in what:
         gen_bd()
     if "full" in what:
