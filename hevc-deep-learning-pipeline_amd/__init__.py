@@ -21,7 +21,7 @@ LIB_PATH = os.environ.get("HEVCDL_LIB") or os.path.join(PKG_DIR, "lib", "libhevc
 TRACE_LIB_PATH = os.path.join(PKG_DIR, "lib", "libhevcdl_hip_trace.so")      # -DHEVCDL_STAGE_TRACE build, loaded by tests/test_rd_gpu.py only
 WEIGHTS_PATH = os.path.join(PKG_DIR, "weights", "hevc_encoder_model.f32")
 WEIGHT_FLOATS = 637712
-SOURCES = ["cnn_kernel.hip", "fc_kernel.hip", "rd_kernel.hip", "rd_kernel_bd10.hip", "rd_kernel_wide.hip", "rd_kernel_tools.hip", "deblock_kernel.hip", "sao_kernel.hip", "hevcdl_api.hip", "hevcdl_bitstream.cpp"]
+SOURCES = ["cnn_kernel.hip", "fc_kernel.hip", "rd_kernel.hip", "rd_kernel_bd10.hip", "rd_kernel_wide.hip", "rd_kernel_tools.hip", "deblock_kernel.hip", "sao_kernel.hip", "quality_kernel.hip", "hevcdl_api.hip", "hevcdl_bitstream.cpp"]
 
 STATUS = {0: "OK", 1: "INVALID_ARG", 2: "UNSUPPORTED", 3: "NO_DEVICE", 4: "HIP", 5: "OOM"}
 
@@ -33,6 +33,7 @@ REC_DTYPE = np.dtype([
 STATS_DTYPE = np.dtype([("sse", "<u8", 3), ("est_bits", "<u8"), ("ctus", "<u4"), ("pad", "<u4")])
 SAO_DTYPE = np.dtype([("mode", "<i4"), ("type", "<i4"), ("aux", "<i4"), ("offset", "<i4", 32)])       # hevcdl_sao_offset; a CTU has 3 (Y, Cb, Cr)
 CABAC_DTYPE = np.dtype([("ctx", "u1", 160), ("frac", "<u8")])      # hevcdl_cabac_state
+QUALITY_DTYPE = np.dtype([("sse", "<u8", 3), ("msssim", "<f8", 3)])      # hevcdl_quality
 assert REC_DTYPE.itemsize == 15120 and STATS_DTYPE.itemsize == 40 and CABAC_DTYPE.itemsize == 168
 
 
@@ -228,6 +229,11 @@ def load_library():
     lib.hevcdl_frame_bytes_bd.argtypes = [ci, ci, ci]
     lib.hevcdl_frame_bytes_bd.restype = ctypes.c_size_t
     lib.hevcdl_config_default_bd.argtypes = [ctypes.POINTER(Config), ci, ci, ci, ci]
+    lib.hevcdl_picture_quality.argtypes = [vp, vp, vp, ci, vp]
+    lib.hevcdl_picture_quality_dev.argtypes = [vp, vp, vp, ci, vp, vp]
+    lib.hevcdl_plane_quality.argtypes = [ci, vp, vp, ci, ci, ci, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double)]
+    lib.hevcdl_enable_quality.argtypes = [vp, ci]
+    lib.hevcdl_get_quality.argtypes = [vp, ci, ci, vp]
     _lib = lib
     return lib
 
@@ -236,7 +242,8 @@ EXPORTS = ["hevcdl_config_default", "hevcdl_create", "hevcdl_destroy", "hevcdl_l
            "hevcdl_predict_depth_rgb", "hevcdl_labels_from_logits", "hevcdl_compress_frames", "hevcdl_predict_depth_planes", "hevcdl_compress_frames_planes", "hevcdl_predict_depth_dev", "hevcdl_compress_frames_dev",
            "hevcdl_encode_frames_dev", "hevcdl_compress_tiles_dev", "hevcdl_clamp_labels_dev", "hevcdl_device_memory", "hevcdl_host_alloc", "hevcdl_host_free", "hevcdl_encode_pictures", "hevcdl_encode_pictures_chunked", "hevcdl_profile_enable", "hevcdl_profile_get", "hevcdl_last_rd_launch", "hevcdl_reserve_workspace", "hevcdl_ctus_per_frame", "hevcdl_frame_bytes", "hevcdl_frame_bytes_bd", "hevcdl_config_default_bd",
            "hevcdl_begin_frames", "hevcdl_compress_ctu", "hevcdl_get_recon", "hevcdl_deblock_frames", "hevcdl_deblock_frames_dev",
-           "hevcdl_sao_frames", "hevcdl_sao_frames_dev", "hevcdl_stream_config_default", "hevcdl_access_unit_bound", "hevcdl_write_access_unit", "hevcdl_write_picture_hash_sei", "hevcdl_picture_md5", "hevcdl_write_digest_sei", "hevcdl_picture_hash", "hevcdl_write_hash_sei"]
+           "hevcdl_sao_frames", "hevcdl_sao_frames_dev", "hevcdl_stream_config_default", "hevcdl_access_unit_bound", "hevcdl_write_access_unit", "hevcdl_write_picture_hash_sei", "hevcdl_picture_md5", "hevcdl_write_digest_sei", "hevcdl_picture_hash", "hevcdl_write_hash_sei",
+           "hevcdl_picture_quality", "hevcdl_picture_quality_dev", "hevcdl_plane_quality", "hevcdl_enable_quality", "hevcdl_get_quality"]
 
 
 def picture_hash_sei(width, height, picture, bit_depth=8, method=1):
@@ -279,6 +286,20 @@ def load_weights(path=WEIGHTS_PATH):
     if w.size != WEIGHT_FLOATS:
         raise ValueError("weight blob must hold %d floats, got %d" % (WEIGHT_FLOATS, w.size))
     return w
+
+
+def plane_quality(org, pic, bit_depth=8, device=0):
+    """One plane of any size ([rows][cols], uint8 or uint16 samples) -> (exact SSE, MS-SSIM as the reference's xCalculateMSSSIM defines it), computed on the device."""
+    lib = load_library()
+    dt = np.uint8 if bit_depth == 8 else np.dtype("<u2")
+    org, pic = np.ascontiguousarray(org, dt), np.ascontiguousarray(pic, dt)
+    if org.ndim != 2 or org.shape != pic.shape:
+        raise ValueError("two planes [rows][cols] of the same shape")
+    sse, ms = ctypes.c_uint64(0), ctypes.c_double(0.0)
+    st = lib.hevcdl_plane_quality(device, org.ctypes.data, pic.ctypes.data, org.shape[1], org.shape[0], bit_depth, ctypes.byref(sse), ctypes.byref(ms))
+    if st:
+        raise HevcdlError(st, "hevcdl_plane_quality")
+    return int(sse.value), float(ms.value)
 
 
 EXEC_NO_UNIT_HANDOVER, EXEC_RD_WIDE, EXEC_RD_NARROW = 1, 2, 4      # HEVCDL_EXEC_* (hevcdl_config.exec_flags)
@@ -547,6 +568,29 @@ class Encoder:
 
     def encode_frames_dev(self, d_yuv, n, d_labels, d_records, d_recon, d_stats=None, stream=None):
         self._check(self.lib.hevcdl_encode_frames_dev(self._h, d_yuv, n, d_labels, d_records, d_recon, d_stats, stream))
+
+    # ---- picture quality: exact SSE + the reference's MS-SSIM (TEncGOP::xCalculateMSSSIM) ----
+    def picture_quality(self, org, pic):
+        """originals + pictures [n, samples] -> [n] QUALITY_DTYPE (sse[3], msssim[3])."""
+        org, n = self._frames(org)
+        pic, m = self._frames(pic)
+        if n != m:
+            raise ValueError("as many pictures as originals")
+        out = np.zeros(n, QUALITY_DTYPE)
+        self._check(self.lib.hevcdl_picture_quality(self._h, org.ctypes.data, pic.ctypes.data, n, out.ctypes.data))
+        return out
+
+    def picture_quality_dev(self, d_org, d_pic, n, d_out, stream=None):
+        self._check(self.lib.hevcdl_picture_quality_dev(self._h, d_org, d_pic, n, d_out, stream))
+
+    def enable_quality(self, on=True):
+        """The picture pipeline (encode_pictures*) also measures its output pictures; read them with get_quality."""
+        self._check(self.lib.hevcdl_enable_quality(self._h, int(bool(on))))
+
+    def get_quality(self, first, count):
+        out = np.zeros(count, QUALITY_DTYPE)
+        self._check(self.lib.hevcdl_get_quality(self._h, int(first), int(count), out.ctypes.data))
+        return out
 
     def profile_enable(self, on=True):
         self._check(self.lib.hevcdl_profile_enable(self._h, int(on)))

@@ -71,6 +71,11 @@ struct hevcdl_ctx {
   int wpp_ring; size_t wpp_state_bytes;
   unsigned char *d_wpp;          // WaveFrontSynchro: [max_frames][ctus_y] 256 bytes (the contexts behind a row's second CTU, the row's finished-CTU count: rd_kernel.hip)
   unsigned char *d_sched;        // decision kernel: hand-over of units between workgroups (finished counter, per-workgroup unit counts, mailboxes)
+  // picture quality (quality_kernel.hip): the workspace is allocated by hevcdl_enable_quality(ctx, 1), or by the first hevcdl_picture_quality* call of a context
+  // with the switch off, and freed by hevcdl_enable_quality(ctx, 0); d_q_out by the switch or by hevcdl_picture_quality (host buffers).  A context that uses neither allocates none of it
+  bool quality_on = false;                 // hevcdl_enable_quality: the picture pipeline also measures its output pictures
+  unsigned char *d_q_pyr = nullptr, *d_q_partial = nullptr, *d_q_weights = nullptr, *d_q_out = nullptr; int q_group = 0;      // workspace of q_group pictures; d_q_out: [max_frames] hevcdl_quality of the pipeline
+  std::vector<hevcdl_quality> h_quality;   // the pipeline's last batch (hevcdl_get_quality)
   bool profile;
   std::vector<hipEvent_t> ev_cnn, ev_rd, ev_conv;       // start/stop pairs (ev_conv: the convolution kernel alone, one pair per chunk of CTUs)
   char err[256];
@@ -332,6 +337,7 @@ extern "C" void hevcdl_destroy(hevcdl_ctx *ctx)
   if (ctx->copy_stream) hipStreamDestroy(ctx->copy_stream);
   hipFree(ctx->d_weights); hipFree(ctx->d_scratch); hipFree(ctx->d_yuv); hipFree(ctx->d_labels); hipFree(ctx->d_recon);
   hipFree(ctx->d_wpp); hipFree(ctx->d_records); hipFree(ctx->d_stats); hipFree(ctx->d_logits); hipFree(ctx->d_yuv8); hipFree(ctx->d_a3); hipFree(ctx->d_picture); hipFree(ctx->d_rgb); hipFree(ctx->d_cabac); hipFree(ctx->d_sao_stats); hipFree(ctx->d_sao_recon); hipFree(ctx->d_sao_params); hipFree(ctx->d_sao_cand); hipFree(ctx->d_wide); hipFree(ctx->d_flag); hipFree(ctx->d_sched);
+  hipFree(ctx->d_q_pyr); hipFree(ctx->d_q_partial); hipFree(ctx->d_q_weights); hipFree(ctx->d_q_out);
   delete ctx;
 }
 
@@ -884,6 +890,157 @@ extern "C" hevcdl_status hevcdl_sao_frames(hevcdl_ctx *ctx, const uint8_t *org, 
   return HEVCDL_OK;
 }
 
+// ---- picture quality (row f-3): SSE and MS-SSIM of TEncGOP::xCalculateAddPSNR / xCalculateMSSSIM (TEncGOP.cpp:2380-2420, 2559-2727) on the device ----
+// the normalised 11 x 11 Gaussian window, computed by the host's libm in the reference's loop order (TEncGOP.cpp:2591-2611)
+static void quality_weights(double *w)
+{
+  double sum = 0.0;
+  for (int y = 0; y < 11; y++) for (int x = 0; x < 11; x++) { w[y * 11 + x] = exp(-((y - 5) * (y - 5) + (x - 5) * (x - 5)) / (5 - 0.5)); sum += w[y * 11 + x]; }
+  for (int y = 0; y < 11; y++) for (int x = 0; x < 11; x++) w[y * 11 + x] /= sum;
+}
+static void quality_constants(hevcdl_quality_params *p, int bit_depth)
+{
+  const unsigned max_value = (1u << bit_depth) - 1;                   // :2664-2666
+  p->c1 = (0.01 * max_value) * (0.01 * max_value); p->c2 = (0.03 * max_value) * (0.03 * max_value);
+}
+
+static void quality_picture_params(const hevcdl_ctx *ctx, hevcdl_quality_params *p)
+{
+  memset(p, 0, sizeof *p);
+  const int w = ctx->cfg.width, h = ctx->cfg.height;
+  p->n_planes = 3; p->plane_w[0] = w; p->plane_h[0] = h; p->plane_w[1] = p->plane_w[2] = w >> 1; p->plane_h[1] = p->plane_h[2] = h >> 1;
+  p->plane_off[0] = 0; p->plane_off[1] = (size_t)w * h; p->plane_off[2] = (size_t)w * h + (size_t)(w >> 1) * (h >> 1);
+  p->frame_samples = (size_t)w * h * 3 / 2; p->sample_bytes = ctx->cfg.bit_depth > 8 ? 2 : 1;
+  quality_constants(p, ctx->cfg.bit_depth);
+  hevcdl_quality_layout(p);
+}
+
+// The pass's workspace: pyramid levels and tile sums of q_group pictures, the window.  Allocated by hevcdl_enable_quality(ctx, 1) -- so that a lack of memory shows up there,
+// where a front end sizes its batch, and not in the middle of an encode -- or by the first hevcdl_picture_quality* call of a context that never enabled the switch.
+static hevcdl_status ensure_quality_workspace(hevcdl_ctx *ctx)
+{
+  if (ctx->d_q_weights) return HEVCDL_OK;
+  hevcdl_quality_params p; quality_picture_params(ctx, &p);
+  double wt[121]; quality_weights(wt);
+  const int group = std::min(ctx->cfg.max_frames, 16);                // pictures per pass: bounds the pyramid workspace (33 MB a picture at 2160p)
+  unsigned char *pyr = nullptr, *part = nullptr, *dw = nullptr;
+  hipError_t e = hipMalloc(&pyr, std::max<size_t>(p.pyr_pic_words, 1) * 4 * group);
+  if (e == hipSuccess) e = hipMalloc(&part, std::max<size_t>(p.part_pic, 1) * sizeof(double) * group);
+  if (e == hipSuccess) e = hipMalloc(&dw, sizeof wt);
+  if (e == hipSuccess) e = hipMemcpy(dw, wt, sizeof wt, hipMemcpyHostToDevice);
+  if (e != hipSuccess) { hipFree(pyr); hipFree(part); hipFree(dw); (void)hipGetLastError(); return fail(ctx, e == hipErrorOutOfMemory ? HEVCDL_ERR_OOM : HEVCDL_ERR_HIP, "picture quality workspace", e); }
+  ctx->d_q_pyr = pyr; ctx->d_q_partial = part; ctx->d_q_weights = dw; ctx->q_group = group;
+  return HEVCDL_OK;
+}
+
+extern "C" hevcdl_status hevcdl_picture_quality_dev(hevcdl_ctx *ctx, const void *d_org, const void *d_pic, int n_frames, void *d_out, void *stream)
+{
+  hevcdl_status st = check_frames(ctx, n_frames); if (st) return st;
+  if (n_frames == 0) return HEVCDL_OK;
+  if (!d_org || !d_pic || !d_out) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null device pointer");
+  { // the results must not lie inside the pictures they are computed from (every other overlap is the caller's business: d_org == d_pic is a picture compared with itself)
+    const uintptr_t o = (uintptr_t)d_out, oe = o + sizeof(hevcdl_quality) * (size_t)n_frames, span = ctx->frame_bytes * (size_t)n_frames;
+    const uintptr_t a = (uintptr_t)d_org, b = (uintptr_t)d_pic;
+    if ((o < a + span && a < oe) || (o < b + span && b < oe)) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "picture quality: the output overlaps an input");
+  }
+  hipStream_t s = (hipStream_t)stream;
+  st = ensure_quality_workspace(ctx); if (st) return st;
+  hevcdl_quality_params p; quality_picture_params(ctx, &p);
+  p.pyr = ctx->d_q_pyr; p.partial = ctx->d_q_partial; p.weights = ctx->d_q_weights; p.out = d_out;
+  HIPCHK(hipMemsetAsync(d_out, 0, sizeof(hevcdl_quality) * (size_t)n_frames, s));
+  for (int first = 0; first < n_frames; first += ctx->q_group) {        // a picture's result does not depend on the pass it falls into: every picture has its own workspace slot
+    p.n_pics = std::min(ctx->q_group, n_frames - first); p.out_first = first;
+    p.org = (const unsigned char *)d_org + ctx->frame_bytes * (size_t)first; p.pic = (const unsigned char *)d_pic + ctx->frame_bytes * (size_t)first;
+    hevcdl_launch_quality(&p, s);
+  }
+  HIPCHK(hipGetLastError());
+  return HEVCDL_OK;
+}
+
+extern "C" hevcdl_status hevcdl_picture_quality(hevcdl_ctx *ctx, const void *org, const void *pic, int n_frames, hevcdl_quality *out)
+{
+  hevcdl_status st = check_frames(ctx, n_frames); if (st) return st;
+  if (n_frames == 0) return HEVCDL_OK;
+  if (!org || !pic || !out) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null pointer");
+  st = ensure_staging(ctx); if (st) return st;
+  if (!ctx->d_q_out) HIPCHK(hipMalloc(&ctx->d_q_out, sizeof(hevcdl_quality) * (size_t)ctx->cfg.max_frames));
+  HIPCHK(hipMemcpy(ctx->d_yuv, org, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(ctx->d_recon, pic, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
+  st = hevcdl_picture_quality_dev(ctx, ctx->d_yuv, ctx->d_recon, n_frames, ctx->d_q_out, nullptr); if (st) return st;
+  hipError_t e = hipDeviceSynchronize();
+  if (e != hipSuccess) return fail(ctx, HEVCDL_ERR_HIP, "quality kernels", e);
+  HIPCHK(hipMemcpy(out, ctx->d_q_out, sizeof(hevcdl_quality) * (size_t)n_frames, hipMemcpyDeviceToHost));
+  return HEVCDL_OK;
+}
+
+// One plane of any size (host buffers, no context): what the picture entry points do per plane, for callers whose planes are not a context's 4:2:0 picture.
+extern "C" hevcdl_status hevcdl_plane_quality(int device, const void *org, const void *pic, int width, int height, int bit_depth, uint64_t *sse, double *msssim)
+{
+  if (!org || !pic || !sse || !msssim || width < 1 || height < 1 || width > 16384 || height > 16384) return HEVCDL_ERR_INVALID_ARG;
+  if (bit_depth < 8 || bit_depth > 16) return HEVCDL_ERR_UNSUPPORTED;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) { (void)hipGetLastError(); return HEVCDL_ERR_NO_DEVICE; }
+  if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return HEVCDL_ERR_HIP; }
+  hevcdl_quality_params p;
+  memset(&p, 0, sizeof p);
+  p.n_planes = 1; p.plane_w[0] = width; p.plane_h[0] = height; p.frame_samples = (size_t)width * height; p.sample_bytes = bit_depth > 8 ? 2 : 1; p.n_pics = 1;
+  quality_constants(&p, bit_depth);
+  hevcdl_quality_layout(&p);
+  double wt[121]; quality_weights(wt);
+  const size_t bytes = p.frame_samples * p.sample_bytes;
+  unsigned char *d[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+  const size_t sz[6] = { bytes, bytes, std::max<size_t>(p.pyr_pic_words, 1) * 4, std::max<size_t>(p.part_pic, 1) * sizeof(double), sizeof wt, sizeof(hevcdl_quality) };
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < 6 && e == hipSuccess; i++) e = hipMalloc(&d[i], sz[i]);
+  hevcdl_quality q; memset(&q, 0, sizeof q);
+  if (e == hipSuccess) e = hipMemcpy(d[0], org, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d[1], pic, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d[4], wt, sizeof wt, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(d[5], 0, sizeof q);
+  if (e == hipSuccess) {
+    p.org = d[0]; p.pic = d[1]; p.pyr = d[2]; p.partial = d[3]; p.weights = d[4]; p.out = d[5];
+    hevcdl_launch_quality(&p, nullptr);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(&q, d[5], sizeof q, hipMemcpyDeviceToHost);
+  }
+  for (int i = 0; i < 6; i++) hipFree(d[i]);
+  if (e != hipSuccess) { (void)hipGetLastError(); return e == hipErrorOutOfMemory ? HEVCDL_ERR_OOM : HEVCDL_ERR_HIP; }
+  *sse = q.sse[0]; *msssim = q.msssim[0];
+  return HEVCDL_OK;
+}
+
+extern "C" hevcdl_status hevcdl_enable_quality(hevcdl_ctx *ctx, int on)
+{
+  if (!ctx) return HEVCDL_ERR_INVALID_ARG;
+  if (on) { // the whole of what the switch costs is reserved here: a refused allocation is this call's HEVCDL_ERR_OOM, not a later encode's
+    hevcdl_status st = check_frames(ctx, 0); if (st) return st;
+    st = ensure_quality_workspace(ctx); if (st) return st;
+    if (!ctx->d_q_out) { hipError_t e = hipMalloc(&ctx->d_q_out, sizeof(hevcdl_quality) * (size_t)ctx->cfg.max_frames);
+      if (e != hipSuccess) { (void)hipGetLastError(); return fail(ctx, e == hipErrorOutOfMemory ? HEVCDL_ERR_OOM : HEVCDL_ERR_HIP, "picture quality results", e); } }
+    ctx->quality_on = true;
+    return HEVCDL_OK;
+  }
+  ctx->quality_on = false; ctx->h_quality.clear();
+  { // off: the workspace goes back (a later hevcdl_picture_quality* call allocates its own again)
+    hipError_t e = hipSetDevice(ctx->cfg.device); if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return fail(ctx, HEVCDL_ERR_HIP, "hevcdl_enable_quality", e);
+    hipFree(ctx->d_q_pyr); hipFree(ctx->d_q_partial); hipFree(ctx->d_q_weights); hipFree(ctx->d_q_out);
+    ctx->d_q_pyr = ctx->d_q_partial = ctx->d_q_weights = ctx->d_q_out = nullptr; ctx->q_group = 0;
+  }
+  return HEVCDL_OK;
+}
+
+extern "C" hevcdl_status hevcdl_get_quality(hevcdl_ctx *ctx, int first, int count, hevcdl_quality *out)
+{
+  if (!ctx) return HEVCDL_ERR_INVALID_ARG;
+  if (!out || first < 0 || count < 0) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_get_quality: bad range");
+  if (!ctx->quality_on) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_get_quality: hevcdl_enable_quality was not called");
+  if ((size_t)first + (size_t)count > ctx->h_quality.size()) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_get_quality: pictures outside the last batch");
+  if (count) memcpy(out, ctx->h_quality.data() + first, sizeof(hevcdl_quality) * (size_t)count);
+  return HEVCDL_OK;
+}
+
 // ---- whole picture pipeline for host buffers: the stages of TEncGOP::compressGOP between reading a picture and writing its NAL units, with
 // the picture staying in HBM in between (one upload of the originals, one download of records / final picture / SAO parameters) ----------
 // device side of hevcdl_encode_pictures*: upload, labels, decisions, in-loop filters; the results stay in HBM (*d_final: the output pictures)
@@ -899,8 +1056,17 @@ static hevcdl_status encode_pictures_device(hevcdl_ctx *ctx, const void *yuv, in
   *d_final = ctx->d_recon;
   if (deblock) { st = hevcdl_deblock_frames_dev(ctx, ctx->d_recon, n_frames, ctx->d_records, ctx->d_recon, nullptr); if (st) return st; }      // in place
   if (want_sao) { st = hevcdl_sao_frames_dev(ctx, ctx->d_yuv, ctx->d_recon, n_frames, ctx->d_sao_params, ctx->d_picture, nullptr); if (st) return st; *d_final = ctx->d_picture; }
+  ctx->h_quality.clear();
+  if (ctx->quality_on) { // the output pictures against the originals, both still in HBM
+    if (!ctx->d_q_out) HIPCHK(hipMalloc(&ctx->d_q_out, sizeof(hevcdl_quality) * (size_t)ctx->cfg.max_frames));
+    st = hevcdl_picture_quality_dev(ctx, ctx->d_yuv, *d_final, n_frames, ctx->d_q_out, nullptr); if (st) return st;
+  }
   hipError_t e = hipDeviceSynchronize();
   if (e != hipSuccess) return fail(ctx, HEVCDL_ERR_HIP, "picture pipeline", e);
+  if (ctx->quality_on) {
+    ctx->h_quality.resize(n_frames);
+    HIPCHK(hipMemcpy(ctx->h_quality.data(), ctx->d_q_out, sizeof(hevcdl_quality) * (size_t)n_frames, hipMemcpyDeviceToHost));
+  }
   return HEVCDL_OK;
 }
 

@@ -58,6 +58,8 @@ const Key KEYS[] = {
   { "LoopFilterBetaOffset_div2", 0, USED, 0 }, { "LoopFilterTcOffset_div2", 0, USED, 0 },
   { "DeblockingFilterMetric", 0, PATH, "0" }, { "SAO", 0, USED, 0 }, { "SAOLcuBoundary", 0, PATH, "0" }, { "LFCrossSliceBoundaryFlag", 0, NOEFFECT, 0 },      // (without slices the reference sets it to 1 whatever the cfg says: TAppEncTop.cpp:278-281)
   { "LFCrossTileBoundaryFlag", 0, USED, 0 }, { "SEIDecodedPictureHash", 0, USED, 0 },
+  // quality report (TAppEncCfg.cpp:759-762): MS-SSIM per picture and in the summary, MSE per picture, MSE in the summary; default 0
+  { "PrintMSSSIM", 0, USED, 0 }, { "PrintFrameMSE", 0, USED, 0 }, { "PrintSequenceMSE", 0, USED, 0 },
   // no effect on an all-intra slice with the settings above
   { "QuadtreeTUMaxDepthInter", 0, NOEFFECT, 0 }, { "FastSearch", 0, NOEFFECT, 0 }, { "SearchRange", 0, NOEFFECT, 0 }, { "HadamardME", 0, NOEFFECT, 0 },
   { "FEN", 0, NOEFFECT, 0 }, { "FDM", 0, NOEFFECT, 0 }, { "AMP", 0, NOEFFECT, 0 }, { "MaxCuDQPDepth", 0, NOEFFECT, 0 }, { "SliceArgument", 0, NOEFFECT, 0 },
@@ -238,6 +240,8 @@ int main(int argc, char **argv)
     if (prof != (bit_depth == 8 ? "main" : "main10")) opt.errors.push_back("Profile = " + prof + " is not implemented by this path (main at 8 bits, main10 at 10 bits)"); }
   // decoded picture hash SEI (TAppEncCfg.cpp:1093): 0 none, 1 MD5 of the output picture behind every access unit
   const int hash_sei = (int)opt.geti("SEIDecodedPictureHash", 0);
+  // PrintMSSSIM: computed on the device from the pictures the pipeline still holds there (hevcdl_enable_quality); the two MSE keys only print what the PSNR is made of
+  const bool print_msssim = opt.geti("PrintMSSSIM", 0) != 0, print_frame_mse = opt.geti("PrintFrameMSE", 0) != 0, print_seq_mse = opt.geti("PrintSequenceMSE", 0) != 0;
   for (const char *key : { "LoopFilterBetaOffset_div2", "LoopFilterTcOffset_div2" }) {      // the reference's own range check (TAppEncCfg.cpp xConfirmPara: -6 .. 6)
     const long v = opt.geti(key, 0);
     if (v < -6 || v > 6) opt.errors.push_back(std::string(key) + " = " + std::to_string(v) + " is out of range (-6 .. 6)");
@@ -356,11 +360,11 @@ int main(int argc, char **argv)
   struct Shard {
     int dev = 0; long f_lo = 0, f_hi = 0; hevcdl_ctx *ctx = nullptr; int batch = 1; int rc = 0;
     double t_read = 0, t_dev = 0, t_host = 0, t_write = 0;
-    std::vector<unsigned long long> rows;       // per coded picture: { poc, bits, sse Y, sse U, sse V, ctus, encode ns, device }  (what the devices gather)
+    std::vector<unsigned long long> rows;       // per coded picture: { poc, bits, sse Y, sse U, sse V, ctus, encode ns, device }  (what the devices gather); PrintMSSSIM: + the three MS-SSIM doubles' bit patterns
     std::vector<std::vector<uint8_t>> aus;      // multi-device runs: the access units (+ hash SEI) of the block, written out in POC order at the end
     std::vector<std::string> md5;
   };
-  enum { ROW = 8 };
+  const int ROW = print_msssim ? 11 : 8;
   std::vector<Shard> shards(n_shards);
   for (int i = 0; i < n_shards; i++) { shards[i].dev = devices[i]; shards[i].f_lo = (long)i * n_frames / n_shards; shards[i].f_hi = (long)(i + 1) * n_frames / n_shards; }
   for (int i = 0; i < n_shards; i++) { // contexts: created one after the other (a refused allocation halves the batch of every shard)
@@ -370,6 +374,8 @@ int main(int argc, char **argv)
       // the decision kernel's workspace (up to 4.3 GB) is otherwise allocated by the first launch: reserved here, a lack of memory is met by the retry below
       bool ws_oom = false;
       if (st == HEVCDL_OK && (st = hevcdl_reserve_workspace(shards[i].ctx)) != HEVCDL_OK) { ws_oom = st == HEVCDL_ERR_OOM; hevcdl_destroy(shards[i].ctx); shards[i].ctx = nullptr; }
+      // PrintMSSSIM: the quality pass's workspace (pyramids of up to 16 pictures) is reserved by the switch; a refusal halves the batch like any other
+      if (st == HEVCDL_OK && print_msssim && (st = hevcdl_enable_quality(shards[i].ctx, 1)) != HEVCDL_OK) { hevcdl_destroy(shards[i].ctx); shards[i].ctx = nullptr; }
       if (st == HEVCDL_ERR_OOM && ws_oom) {
         // the workspace is sized by the device's CUs, not by the batch: a smaller batch does not shrink it.  What does: the independent launch form (a block per wave of
         // the context's own frames instead of every CU's workgroup), then the eight-wave build
@@ -416,7 +422,7 @@ int main(int argc, char **argv)
   scfg.tools = cfg.tools; scfg.lf_beta_offset_div2 = cfg.lf_beta_offset_div2; scfg.lf_tc_offset_div2 = cfg.lf_tc_offset_div2; scfg.loop_filter_disable = deblock ? 0 : 1;
   scfg.lf_across_tiles = cfg.lf_across_tiles; scfg.tile_uniform_spacing = cfg.tile_uniform_spacing; memcpy(scfg.tile_column_width, cfg.tile_column_width, sizeof scfg.tile_column_width); memcpy(scfg.tile_row_height, cfg.tile_row_height, sizeof scfg.tile_row_height);
   const double ny = (double)width * height, nc = ny / 4;
-  double sum_bits = 0, sum_psnr[3] = { 0, 0, 0 }, sum_mse[3] = { 0, 0, 0 }; long done = 0;
+  double sum_bits = 0, sum_psnr[3] = { 0, 0, 0 }, sum_mse[3] = { 0, 0, 0 }, sum_msssim[3] = { 0, 0, 0 }; long done = 0;
   auto now = [] { return std::chrono::steady_clock::now(); };
   auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
   // host threads for the per-picture work: the CPUs this process may really use (a container's CPU quota is often far below the node's thread count)
@@ -426,9 +432,21 @@ int main(int argc, char **argv)
   const int max_threads = (int)std::max(1u, std::min(cpus, 64u) / (unsigned)n_shards);
   const double maxval = (double)(255 << (bit_depth - 8));
   // one picture's log line and its share of the summary (TEncGOP.cpp:2500-2541; PSNR from the squared error as TEncGOP.cpp:2391-2394)
-  auto log_picture = [&](long poc, unsigned long long bits, const unsigned long long *sse, double et, const char *md5_text) {
+  // msssim_bits: the picture's three MS-SSIM values as bit patterns (PrintMSSSIM), or null
+  auto log_picture = [&](long poc, unsigned long long bits, const unsigned long long *sse, double et, const char *md5_text, const unsigned long long *msssim_bits) {
     const double p[3] = { psnr_of(sse[0], ny, maxval), psnr_of(sse[1], nc, maxval), psnr_of(sse[2], nc, maxval) };
-    printf("POC %4ld TId: %1d ( %c-SLICE, QP %d ) %10llu bits [Y %6.4lf dB    U %6.4lf dB    V %6.4lf dB] [ET %5.0f ]%s\n", poc, 0, 'I', qp, bits, p[0], p[1], p[2], et, md5_text);
+    if (!print_msssim && !print_frame_mse)
+      printf("POC %4ld TId: %1d ( %c-SLICE, QP %d ) %10llu bits [Y %6.4lf dB    U %6.4lf dB    V %6.4lf dB] [ET %5.0f ]%s\n", poc, 0, 'I', qp, bits, p[0], p[1], p[2], et, md5_text);
+    else { // the groups of TEncGOP.cpp:2522-2537 between the PSNR group and [ET
+      printf("POC %4ld TId: %1d ( %c-SLICE, QP %d ) %10llu bits [Y %6.4lf dB    U %6.4lf dB    V %6.4lf dB]", poc, 0, 'I', qp, bits, p[0], p[1], p[2]);
+      if (print_msssim) {
+        double m[3]; memcpy(m, msssim_bits, sizeof m);
+        printf(" [MS-SSIM Y %1.6lf    U %1.6lf    V %1.6lf]", m[0], m[1], m[2]);
+        for (int c = 0; c < 3; c++) sum_msssim[c] += m[c];
+      }
+      if (print_frame_mse) printf(" [Y MSE %6.4lf  U MSE %6.4lf  V MSE %6.4lf]", (double)sse[0] / ny, (double)sse[1] / nc, (double)sse[2] / nc);
+      printf(" [ET %5.0f ]%s\n", et, md5_text);
+    }
     sum_bits += (double)bits;
     for (int c = 0; c < 3; c++) { sum_psnr[c] += p[c]; sum_mse[c] += (double)sse[c] / (c ? nc : ny); }
     done++;
@@ -451,6 +469,8 @@ int main(int argc, char **argv)
       if (first == 0) cc.et = secs(cc.t0, th0) / cc.nb;                // device seconds per picture of this call (the log line's ET)
       const uint8_t *recon = (const uint8_t *)pictures;
       std::vector<PicOut> pics(count);
+      std::vector<hevcdl_quality> quality(print_msssim ? count : 0);          // measured by the device call that made the pictures
+      if (print_msssim) { const hevcdl_status qst = hevcdl_get_quality(S.ctx, first, count, quality.data()); if (qst != HEVCDL_OK) { fprintf(stderr, "Error: %s (status %d)\n", hevcdl_last_error(S.ctx), (int)qst); S.rc = 3; return 1; } }
       {
         std::atomic<int> next(0);
         auto work = [&]() {
@@ -502,12 +522,13 @@ int main(int argc, char **argv)
         PicOut &po = pics[i];
         if (po.st != HEVCDL_OK) { fprintf(stderr, "Error: bitstream writer failed (status %d)\n", (int)po.st); S.rc = 3; return 1; }
         const long poc = cc.f0 + first + i;
-        const unsigned long long row[ROW] = { (unsigned long long)poc, (unsigned long long)po.au_len * 8, po.sse[0], po.sse[1], po.sse[2], (unsigned long long)ctus, (unsigned long long)(cc.et * 1e9), (unsigned long long)S.dev };
+        unsigned long long row[11] = { (unsigned long long)poc, (unsigned long long)po.au_len * 8, po.sse[0], po.sse[1], po.sse[2], (unsigned long long)ctus, (unsigned long long)(cc.et * 1e9), (unsigned long long)S.dev, 0, 0, 0 };
+        if (print_msssim) memcpy(row + 8, quality[i].msssim, 3 * sizeof(double));
         S.rows.insert(S.rows.end(), row, row + ROW);
         if (multi) { S.aus.push_back(std::move(po.bytes)); S.md5.push_back(po.md5_text); }
         else {
           if (fbits) fwrite(po.bytes.data(), 1, po.bytes.size(), fbits);
-          log_picture(poc, (unsigned long long)po.au_len * 8, po.sse, cc.et, po.md5_text);
+          log_picture(poc, (unsigned long long)po.au_len * 8, po.sse, cc.et, po.md5_text, print_msssim ? row + 8 : nullptr);
         }
       }
       if (frec || frecords) {
@@ -567,7 +588,7 @@ int main(int argc, char **argv)
     } else {
       fprintf(stderr, "Picture rows gathered: %s\n", info.c_str());
       std::vector<const unsigned long long *> rows;
-      for (size_t o = 0; o + ROW <= table.size(); o += ROW) if (table[o] != ~0ull) rows.push_back(&table[o]);
+      for (size_t o = 0; o + (size_t)ROW <= table.size(); o += (size_t)ROW) if (table[o] != ~0ull) rows.push_back(&table[o]);
       std::sort(rows.begin(), rows.end(), [](const unsigned long long *a, const unsigned long long *b) { return a[0] < b[0]; });
       if ((long)rows.size() != n_frames) { fprintf(stderr, "Error: %zu rows gathered for %ld pictures\n", rows.size(), n_frames); rc = 3; }
       for (size_t r = 0; r < rows.size() && rc == 0; r++) { // POC order: blocks are contiguous, so this is the blocks one after the other
@@ -576,7 +597,7 @@ int main(int argc, char **argv)
         const Shard &S = shards[si];
         const size_t li = (size_t)(poc - S.f_lo);
         if (fbits) fwrite(S.aus[li].data(), 1, S.aus[li].size(), fbits);
-        log_picture(poc, rows[r][1], rows[r] + 2, (double)rows[r][6] * 1e-9, S.md5[li].c_str());
+        log_picture(poc, rows[r][1], rows[r] + 2, (double)rows[r][6] * 1e-9, S.md5[li].c_str(), print_msssim ? rows[r] + 8 : nullptr);
       }
     }
   }
@@ -587,9 +608,21 @@ int main(int argc, char **argv)
   if (rc == 0 && done > 0) { // TEncAnalyze::printOut, 4:2:0 layout
     const double mse_yuv = (4 * sum_mse[0] + sum_mse[1] + sum_mse[2]) / done / 6.0;
     printf("\n\nSUMMARY --------------------------------------------------------\n");
-    printf("\tTotal Frames |   Bitrate     Y-PSNR    U-PSNR    V-PSNR    YUV-PSNR  \n");
-    printf("\t %8ld    %c %12.4lf  %8.4lf  %8.4lf  %8.4lf  %8.4lf  \n", done, 'a', sum_bits * (fps / 1000.0 / done), sum_psnr[0] / done, sum_psnr[1] / done,
-           sum_psnr[2] / done, mse_yuv == 0 ? 999.99 : 10.0 * log10((double)(255 << (bit_depth - 8)) * (double)(255 << (bit_depth - 8)) / mse_yuv));
+    const double psnr_yuv = mse_yuv == 0 ? 999.99 : 10.0 * log10((double)(255 << (bit_depth - 8)) * (double)(255 << (bit_depth - 8)) / mse_yuv);
+    if (!print_msssim && !print_seq_mse) {
+      printf("\tTotal Frames |   Bitrate     Y-PSNR    U-PSNR    V-PSNR    YUV-PSNR  \n");
+      printf("\t %8ld    %c %12.4lf  %8.4lf  %8.4lf  %8.4lf  %8.4lf  \n", done, 'a', sum_bits * (fps / 1000.0 / done), sum_psnr[0] / done, sum_psnr[1] / done, sum_psnr[2] / done, psnr_yuv);
+    } else { // the extra columns of TEncAnalyze.h:315-388
+      printf("\tTotal Frames |   Bitrate     Y-PSNR    U-PSNR    V-PSNR    YUV-PSNR  ");
+      if (print_msssim) printf("  Y-MS-SSIM    U-MS-SSIM    V-MS-SSIM  ");
+      printf(print_seq_mse ? "  Y-MSE     U-MSE     V-MSE     YUV-MSE  \n" : "\n");
+      printf("\t %8ld    %c %12.4lf  %8.4lf  %8.4lf  %8.4lf  %8.4lf  ", done, 'a', sum_bits * (fps / 1000.0 / done), sum_psnr[0] / done, sum_psnr[1] / done, sum_psnr[2] / done, psnr_yuv);
+      if (print_msssim) printf("   %8.6lf     %8.6lf     %8.6lf  ", sum_msssim[0] / (double)done, sum_msssim[1] / (double)done, sum_msssim[2] / (double)done);
+      if (print_seq_mse) { // MSEyuv as calculateCombinedValues adds it up (TEncAnalyze.h:180-194)
+        double acc = 0; acc += 4 * (sum_mse[0] / (double)done); acc += 1 * (sum_mse[1] / (double)done); acc += 1 * (sum_mse[2] / (double)done);
+        printf(" %8.4lf  %8.4lf  %8.4lf  %8.4lf  \n", sum_mse[0] / (double)done, sum_mse[1] / (double)done, sum_mse[2] / (double)done, acc / 6.0);
+      } else printf("\n");
+    }
   }
   if (frec) fclose(frec);
   if (frecords) fclose(frecords);

@@ -146,6 +146,21 @@ struct hevcdl_sao_params {
   double lambda, lambda_chroma;
 };
 
+// picture quality metrics (quality_kernel.hip): exact SSE and the reference's MS-SSIM for n_pics pictures of up to three planes
+struct hevcdl_quality_params {
+  const void *org, *pic;           // [picture] planes of sample_bytes-wide samples, plane c at sample plane_off[c] of a picture of frame_samples samples
+  void *out;                       // hevcdl_quality[]: picture i of the launch writes entry out_first + i (sse zeroed by the caller)
+  void *pyr;                       // [picture] levels 1 .. 4 of both pictures as uint32 numerators: org at pyr_off[c][s], the other picture pyr_half words behind
+  void *partial;                   // [picture][part_pic] doubles: block sums of every 64 x 16 tile of every (plane, scale), at part_off[c][s]
+  const void *weights;             // 121 doubles: the normalised 11 x 11 window, row-major
+  size_t frame_samples, plane_off[3];
+  size_t pyr_off[3][5], pyr_half, pyr_pic_words;
+  int plane_w[3], plane_h[3], n_planes, scales[3];
+  int part_off[3][5], part_pic;
+  int n_pics, out_first, sample_bytes;
+  double c1, c2;                   // (0.01 max)^2, (0.03 max)^2, max = (1 << bit depth) - 1 (TEncGOP.cpp:2664-2666)
+};
+
 // Tile boundaries in CTUs: bd[0] = 0 < bd[1] < ... < bd[n_tiles] = n_ctus.  Uniform spacing as TComPicSym.cpp xInitTiles; explicit sizes
 // name every tile but the last (which takes the rest).  min_size: smallest tile the reference accepts (4 CTU columns, 1 CTU row,
 // TComPicSym.cpp:380-392) when there is more than one tile in that direction.  Returns 0 when the layout is valid.
@@ -198,6 +213,9 @@ extern "C" {
 #endif
 void hevcdl_launch_sao(const struct hevcdl_sao_params *p, void *stream);
 void hevcdl_launch_deblock(const struct hevcdl_dbk_params *p, void *stream);
+int hevcdl_quality_scales(int w, int h);
+void hevcdl_quality_layout(struct hevcdl_quality_params *p);      // fills scales / *_off / pyr_* / part_pic from the planes' sizes
+void hevcdl_launch_quality(const struct hevcdl_quality_params *p, void *stream);
 size_t hevcdl_cnn_smem_bytes(void);
 size_t hevcdl_fc_smem_bytes(void);
 size_t hevcdl_rd_smem_bytes(void);

@@ -27,24 +27,44 @@ def frame_psnr(sse_yuv, width, height, maxval=MAXVAL_8BIT):
     return tuple(psnr_from_sse(int(s), n, maxval) for s, n in zip(sse_yuv, (ny, nc, nc)))
 
 
-def frame_line(poc, qp, bits, psnr, enc_time_s=0.0):
-    """The picture line of the encoder log (TEncGOP.cpp:2500-2541), intra slices only."""
-    return ("POC %4d TId: %1d ( %c-SLICE, QP %d ) %10d bits [Y %6.4f dB    U %6.4f dB    V %6.4f dB] [ET %5.0f ]"
-            % (poc, 0, "I", qp, bits, psnr[0], psnr[1], psnr[2], enc_time_s))
+def frame_mse(sse_yuv, width, height):
+    """(Y, U, V) MSE of one 4:2:0 picture from its three SSE sums (TEncGOP.cpp:2394)."""
+    ny, nc = width * height, (width // 2) * (height // 2)
+    return tuple(float(int(s)) / n for s, n in zip(sse_yuv, (ny, nc, nc)))
+
+
+def frame_line(poc, qp, bits, psnr, enc_time_s=0.0, msssim=None, mse=None):
+    """The picture line of the encoder log (TEncGOP.cpp:2500-2541), intra slices only.  msssim = (Y, U, V): the group PrintMSSSIM adds
+    (:2522-2527); mse = (Y, U, V): the group PrintFrameMSE adds (:2534-2537); both stand between the PSNR group and [ET."""
+    line = ("POC %4d TId: %1d ( %c-SLICE, QP %d ) %10d bits [Y %6.4f dB    U %6.4f dB    V %6.4f dB]"
+            % (poc, 0, "I", qp, bits, psnr[0], psnr[1], psnr[2]))
+    if msssim is not None:
+        line += " [MS-SSIM Y %1.6f    U %1.6f    V %1.6f]" % tuple(msssim)
+    if mse is not None:
+        line += " [Y MSE %6.4f  U MSE %6.4f  V MSE %6.4f]" % tuple(mse)
+    return line + " [ET %5.0f ]" % enc_time_s
 
 
 class Summary:
     """Running totals of TEncAnalyze (addResult) and its 4:2:0 printOut."""
 
-    def __init__(self, width, height, frame_rate=30.0, bit_depth=8):
+    def __init__(self, width, height, frame_rate=30.0, bit_depth=8, msssim=False, mse=False):
+        """msssim: the three averaged MS-SSIM columns of PrintMSSSIM (feed add() a picture's values); mse: the four MSE columns of PrintSequenceMSE."""
         self.w, self.h, self.fps = width, height, float(frame_rate)
+        self.want_msssim, self.want_mse = bool(msssim), bool(mse)
+        self.msssim = [0.0, 0.0, 0.0]
         self.maxval = 255 << (bit_depth - 8)
         self.n = 0
         self.bits = 0.0
         self.psnr = [0.0, 0.0, 0.0]
         self.mse = [0.0, 0.0, 0.0]
 
-    def add(self, bits, sse_yuv):
+    def add(self, bits, sse_yuv, msssim=None):
+        if self.want_msssim:
+            if msssim is None:
+                raise ValueError("Summary(msssim=True) needs every picture's MS-SSIM")
+            for c in range(3):
+                self.msssim[c] += float(msssim[c])
         ny, nc = self.w * self.h, (self.w // 2) * (self.h // 2)
         p = frame_psnr(sse_yuv, self.w, self.h, self.maxval)
         for c, n in enumerate((ny, nc, nc)):
@@ -65,10 +85,26 @@ class Summary:
     def averages(self):
         return [p / self.n for p in self.psnr]
 
+    def yuv_mse(self):
+        """MSEyuv of calculateCombinedValues (TEncAnalyze.h:163-194)."""
+        scale, acc = 0, 0.0
+        for c, sc in enumerate((4, 1, 1)):
+            scale += sc
+            acc += sc * (self.mse[c] / float(self.n))
+        return acc / float(scale)
+
     def text(self, delim="a"):
+        """TEncAnalyze::printOut, 4:2:0 (TEncAnalyze.h:301-388)."""
         a = self.averages()
-        head = "\tTotal Frames |   Bitrate     Y-PSNR    U-PSNR    V-PSNR    YUV-PSNR  \n"
-        return head + "\t %8d    %c %12.4f  %8.4f  %8.4f  %8.4f  %8.4f  " % (self.n, delim, self.bitrate_kbps(), a[0], a[1], a[2], self.yuv_psnr())
+        head = "\tTotal Frames |   Bitrate     Y-PSNR    U-PSNR    V-PSNR    YUV-PSNR  "
+        line = "\t %8d    %c %12.4f  %8.4f  %8.4f  %8.4f  %8.4f  " % (self.n, delim, self.bitrate_kbps(), a[0], a[1], a[2], self.yuv_psnr())
+        if self.want_msssim:
+            head += "  Y-MS-SSIM    U-MS-SSIM    V-MS-SSIM  "
+            line += "   %8.6f     %8.6f     %8.6f  " % tuple(m / float(self.n) for m in self.msssim)
+        if self.want_mse:
+            head += "  Y-MSE     U-MSE     V-MSE     YUV-MSE  "
+            line += " %8.4f  %8.4f  %8.4f  %8.4f  " % (self.mse[0] / float(self.n), self.mse[1] / float(self.n), self.mse[2] / float(self.n), self.yuv_mse())
+        return head + "\n" + line
 
 
 def _fit_integral(x, y, lo, hi):

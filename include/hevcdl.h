@@ -225,6 +225,34 @@ typedef int (*hevcdl_chunk_fn)(void *user, int first, int count, const hevcdl_ct
 hevcdl_status hevcdl_encode_pictures_chunked(hevcdl_ctx *ctx, const void *yuv, int n_frames, const uint8_t *labels_opt, int deblock, int want_sao,
                                              int chunk_frames, hevcdl_chunk_fn fn, void *user);
 
+/* ---- picture quality: the reference's PrintMSSSIM / PrintFrameMSE / PrintSequenceMSE numbers, computed on the device --------------
+ * Replaces TEncGOP::xCalculateMSSSIM (TEncGOP.cpp:2559-2727: 11 x 11 Gaussian window in f64 at every sample position of up to five scales) and the SSD
+ * loop of xCalculateAddPSNR (:2380-2390).  org / pic: n_frames packed planar 4:2:0 pictures of the context's size and bit depth (uint16 samples at 10 bits).
+ * sse is exact.  Every block SSIM value is computed by the reference's operations in the reference's order and is bit-identical to it; the mean over a
+ * scale's blocks is a fixed reduction tree instead of the reference's serial sum, so msssim may differ from the reference by a few units of the last
+ * place (it is the same bits on every run, for every batch size and position in the batch).  A plane smaller than the window (8 x 8 chroma of a
+ * 16 x 16 picture) gives what the reference's expression gives: 0 / totalBlocks.
+ * The device variant is asynchronous on `stream`; d_out must not overlap the pictures (HEVCDL_ERR_INVALID_ARG); d_org == d_pic is allowed. */
+typedef struct hevcdl_quality {
+  uint64_t sse[3];               /* sum of squared sample differences per plane (Y, Cb, Cr) */
+  double   msssim[3];            /* MS-SSIM per plane */
+} hevcdl_quality;
+hevcdl_status hevcdl_picture_quality(hevcdl_ctx *ctx, const void *org, const void *pic, int n_frames, hevcdl_quality *out);
+hevcdl_status hevcdl_picture_quality_dev(hevcdl_ctx *ctx, const void *d_org, const void *d_pic, int n_frames, void *d_out, void *stream);
+/* TEST AND DIAGNOSTIC entry point, not for a hot path (it allocates and frees its device buffers on every call): the same for ONE plane of any size from
+ * 1 x 1 to 16384 x 16384 and any bit depth from 8 to 16 (host buffers; uint16 samples above 8 bits), without a context.  A context's picture sizes are
+ * multiples of 8, so its planes never have the odd sizes and the sizes next to the scale cut-offs (21, 43, 87, 175) that the kernels' tests need; this runs the
+ * same kernels on them. */
+hevcdl_status hevcdl_plane_quality(int device, const void *org, const void *pic, int width, int height, int bit_depth, uint64_t *sse, double *msssim);
+/* The picture pipeline can measure its own output while original and output picture are still in HBM: after hevcdl_enable_quality(ctx, 1) every
+ * hevcdl_encode_pictures / hevcdl_encode_pictures_chunked call also computes the hevcdl_quality of its output pictures (after the enabled in-loop
+ * filters) against the originals, and hevcdl_get_quality returns those of pictures [first, first + count) of the LAST such call -- valid inside the chunk
+ * callback and after the call returns.  Off (the default): nothing is launched or allocated, hevcdl_get_quality returns HEVCDL_ERR_INVALID_ARG.
+ * hevcdl_enable_quality(ctx, 1) allocates everything the pass needs (pyramids of up to 16 pictures: 33 MB a picture at 2160p) and returns HEVCDL_ERR_OOM when
+ * the device refuses -- call it where the batch is sized, beside hevcdl_reserve_workspace; hevcdl_enable_quality(ctx, 0) synchronises the device and frees it. */
+hevcdl_status hevcdl_enable_quality(hevcdl_ctx *ctx, int on);
+hevcdl_status hevcdl_get_quality(hevcdl_ctx *ctx, int first, int count, hevcdl_quality *out);
+
 /* ---- bitstream writer (host side; no GPU needed) ---------------------------------------------------
  * One access unit per picture exactly as the reference emits it for its all-intra configuration: VPS, SPS, PPS
  * (ReWriteParamSetsFlag 1), then one slice NAL (IDR_W_RADL for POC 0, CRA afterwards), Annex B start codes.
