@@ -21,7 +21,7 @@ LIB_PATH = os.environ.get("HEVCDL_LIB") or os.path.join(PKG_DIR, "lib", "libhevc
 TRACE_LIB_PATH = os.path.join(PKG_DIR, "lib", "libhevcdl_hip_trace.so")      # -DHEVCDL_STAGE_TRACE build, loaded by tests/test_rd_gpu.py only
 WEIGHTS_PATH = os.path.join(PKG_DIR, "weights", "hevc_encoder_model.f32")
 WEIGHT_FLOATS = 637712
-SOURCES = ["cnn_kernel.hip", "fc_kernel.hip", "rd_kernel.hip", "rd_kernel_bd10.hip", "rd_kernel_wide.hip", "rd_kernel_tools.hip", "deblock_kernel.hip", "sao_kernel.hip", "quality_kernel.hip", "hevcdl_api.hip", "hevcdl_bitstream.cpp"]
+SOURCES = ["cnn_kernel.hip", "fc_kernel.hip", "rd_kernel.hip", "rd_kernel_bd10.hip", "rd_kernel_wide.hip", "rd_kernel_tools.hip", "deblock_kernel.hip", "sao_kernel.hip", "quality_kernel.hip", "entropy_kernel.hip", "hevcdl_api.hip", "hevcdl_bitstream.cpp"]
 
 STATUS = {0: "OK", 1: "INVALID_ARG", 2: "UNSUPPORTED", 3: "NO_DEVICE", 4: "HIP", 5: "OOM"}
 
@@ -234,6 +234,15 @@ def load_library():
     lib.hevcdl_plane_quality.argtypes = [ci, vp, vp, ci, ci, ci, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double)]
     lib.hevcdl_enable_quality.argtypes = [vp, ci]
     lib.hevcdl_get_quality.argtypes = [vp, ci, ci, vp]
+    szp, u32p = ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_uint32)
+    lib.hevcdl_write_access_unit_from_slice_data.argtypes = [ctypes.POINTER(StreamConfig), ci, vp, vp, ci, vp, ctypes.c_size_t, szp]
+    lib.hevcdl_slice_data_layout.argtypes = [ctypes.POINTER(StreamConfig), ci, ctypes.POINTER(ci), szp, vp, vp]
+    lib.hevcdl_code_slice_data_host.argtypes = [ctypes.POINTER(StreamConfig), vp, vp, ci, ci, vp, ctypes.c_size_t, vp, vp]
+    lib.hevcdl_code_slice_data.argtypes = [ci, ctypes.POINTER(StreamConfig), vp, vp, ci, ci, vp, ctypes.c_size_t, vp, vp]
+    lib.hevcdl_enable_device_entropy.argtypes = [vp, ci]
+    lib.hevcdl_get_slice_data.argtypes = [vp, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(u32p), ctypes.POINTER(ci)]
+    lib.hevcdl_set_entropy_capacity.argtypes = [vp, ci]
+    lib.hevcdl_get_entropy_info.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double)]
     _lib = lib
     return lib
 
@@ -243,7 +252,9 @@ EXPORTS = ["hevcdl_config_default", "hevcdl_create", "hevcdl_destroy", "hevcdl_l
            "hevcdl_encode_frames_dev", "hevcdl_compress_tiles_dev", "hevcdl_clamp_labels_dev", "hevcdl_device_memory", "hevcdl_host_alloc", "hevcdl_host_free", "hevcdl_encode_pictures", "hevcdl_encode_pictures_chunked", "hevcdl_profile_enable", "hevcdl_profile_get", "hevcdl_last_rd_launch", "hevcdl_reserve_workspace", "hevcdl_ctus_per_frame", "hevcdl_frame_bytes", "hevcdl_frame_bytes_bd", "hevcdl_config_default_bd",
            "hevcdl_begin_frames", "hevcdl_compress_ctu", "hevcdl_get_recon", "hevcdl_deblock_frames", "hevcdl_deblock_frames_dev",
            "hevcdl_sao_frames", "hevcdl_sao_frames_dev", "hevcdl_stream_config_default", "hevcdl_access_unit_bound", "hevcdl_write_access_unit", "hevcdl_write_picture_hash_sei", "hevcdl_picture_md5", "hevcdl_write_digest_sei", "hevcdl_picture_hash", "hevcdl_write_hash_sei",
-           "hevcdl_picture_quality", "hevcdl_picture_quality_dev", "hevcdl_plane_quality", "hevcdl_enable_quality", "hevcdl_get_quality"]
+           "hevcdl_picture_quality", "hevcdl_picture_quality_dev", "hevcdl_plane_quality", "hevcdl_enable_quality", "hevcdl_get_quality",
+           "hevcdl_write_access_unit_from_slice_data", "hevcdl_slice_data_layout", "hevcdl_code_slice_data_host", "hevcdl_code_slice_data",
+           "hevcdl_enable_device_entropy", "hevcdl_get_slice_data", "hevcdl_encode_pictures_stream", "hevcdl_set_entropy_capacity", "hevcdl_get_entropy_info"]
 
 
 def picture_hash_sei(width, height, picture, bit_depth=8, method=1):
@@ -323,9 +334,9 @@ def default_config(width, height, qp, max_frames=1, device=0, cnn_input=0, tiles
     return cfg
 
 
-def write_access_unit(width, height, qp, poc, records, level_idc=186, sao=None, tiles=(1, 1), bit_depth=8, lf_across_tiles=True, tools=TOOLS_REFERENCE, lf_offsets=(0, 0), lf_disable=False,
-                      rewrite_param_sets=True, wavefront=False):
-    """Host-side bitstream writer (no GPU): VPS+SPS+PPS+slice NAL of one picture from its CTU records -> bytes."""
+def stream_config(width, height, qp, level_idc=186, sao=False, tiles=(1, 1), bit_depth=8, lf_across_tiles=True, tools=TOOLS_REFERENCE, lf_offsets=(0, 0), lf_disable=False,
+                  rewrite_param_sets=True, wavefront=False):
+    """hevcdl_stream_config of include/hevcdl.h from keyword arguments."""
     lib = load_library()
     cfg = StreamConfig()
     st = lib.hevcdl_stream_config_default(ctypes.byref(cfg), width, height, qp)
@@ -340,6 +351,73 @@ def write_access_unit(width, height, qp, poc, records, level_idc=186, sao=None, 
     cfg.loop_filter_disable = 1 if lf_disable else 0
     cfg.rewrite_param_sets = 1 if rewrite_param_sets else 0
     cfg.wavefront = 1 if wavefront else 0      # a sub-stream per CTU row, entry points in the slice header
+    cfg.sao_enabled = 1 if sao else 0
+    return cfg
+
+
+CANARY = 0xA5      # what code_slice_data fills its buffer with before the coder runs: the gaps between the sub-stream regions must still hold it afterwards
+
+
+def slice_data_layout(cfg, capacity_per_ctu=0):
+    """-> (sub-streams of a picture, bytes of a picture's regions, offsets [n], capacities [n]) of a slice-data buffer (hevcdl_slice_data_layout)."""
+    lib = load_library()
+    n, nbytes = ctypes.c_int(0), ctypes.c_size_t(0)
+    st = lib.hevcdl_slice_data_layout(ctypes.byref(cfg), int(capacity_per_ctu), ctypes.byref(n), ctypes.byref(nbytes), None, None)
+    if st:
+        raise HevcdlError(st, "hevcdl_slice_data_layout")
+    off, cap = np.zeros(n.value, np.uint32), np.zeros(n.value, np.uint32)
+    lib.hevcdl_slice_data_layout(ctypes.byref(cfg), int(capacity_per_ctu), ctypes.byref(n), ctypes.byref(nbytes), off.ctypes.data, cap.ctypes.data)
+    return n.value, nbytes.value, off, cap
+
+
+def code_slice_data(cfg, records, sao=None, capacity_per_ctu=0, device=None):
+    """TEST AND DIAGNOSTIC: the slice data of records [n_frames, ctus] by the shared coder -- device None: on the CPU (hevcdl_code_slice_data_host, no GPU needed),
+    otherwise by the kernels on that device (hevcdl_code_slice_data).  cfg: stream_config(...) with sao=True when SAO parameters [n_frames, ctus, 3] are passed.
+    -> (buffer [n_frames, picture bytes] pre-filled with CANARY, sizes [n_frames, n], overflow [n_frames, n], offsets [n], capacities [n])."""
+    lib = load_library()
+    records = np.ascontiguousarray(records, REC_DTYPE)
+    records = records.reshape(1, -1) if records.ndim == 1 else records
+    nf = records.shape[0]
+    n, nbytes, off, cap = slice_data_layout(cfg, capacity_per_ctu)
+    buf = np.full((nf, nbytes), CANARY, np.uint8)
+    sizes, ovf = np.zeros((nf, n), np.uint32), np.zeros((nf, n), np.uint32)
+    sao_ptr = None
+    if sao is not None:
+        sao = np.ascontiguousarray(sao, SAO_DTYPE)
+        sao_ptr = sao.ctypes.data
+    if device is None:
+        st = lib.hevcdl_code_slice_data_host(ctypes.byref(cfg), records.ctypes.data, sao_ptr, nf, int(capacity_per_ctu), buf.ctypes.data, buf.size, sizes.ctypes.data, ovf.ctypes.data)
+    else:
+        st = lib.hevcdl_code_slice_data(int(device), ctypes.byref(cfg), records.ctypes.data, sao_ptr, nf, int(capacity_per_ctu), buf.ctypes.data, buf.size, sizes.ctypes.data, ovf.ctypes.data)
+    if st:
+        raise HevcdlError(st, "hevcdl_code_slice_data")
+    return buf, sizes, ovf, off, cap
+
+
+def pack_slice_data(buf, sizes, off):
+    """One picture's row of a code_slice_data buffer -> its sub-streams back to back (bytes)."""
+    return b"".join(buf[int(o):int(o) + int(n)].tobytes() for o, n in zip(off, sizes))
+
+
+def write_access_unit_from_slice_data(cfg, poc, data, sizes):
+    """Everything of picture poc's access unit around slice data that exists already (hevcdl_write_access_unit_from_slice_data) -> bytes."""
+    lib = load_library()
+    data = np.frombuffer(bytes(data) + b"\0", np.uint8)
+    sizes = np.ascontiguousarray(sizes, np.uint32)
+    cap = lib.hevcdl_access_unit_bound(cfg.width, cfg.height) + data.size
+    buf = np.zeros(cap, np.uint8)
+    n = ctypes.c_size_t(0)
+    st = lib.hevcdl_write_access_unit_from_slice_data(ctypes.byref(cfg), int(poc), data.ctypes.data, sizes.ctypes.data, int(sizes.size), buf.ctypes.data, cap, ctypes.byref(n))
+    if st:
+        raise HevcdlError(st, "hevcdl_write_access_unit_from_slice_data")
+    return buf[:n.value].tobytes()
+
+
+def write_access_unit(width, height, qp, poc, records, level_idc=186, sao=None, tiles=(1, 1), bit_depth=8, lf_across_tiles=True, tools=TOOLS_REFERENCE, lf_offsets=(0, 0), lf_disable=False,
+                      rewrite_param_sets=True, wavefront=False):
+    """Host-side bitstream writer (no GPU): VPS+SPS+PPS+slice NAL of one picture from its CTU records -> bytes."""
+    lib = load_library()
+    cfg = stream_config(width, height, qp, level_idc, False, tiles, bit_depth, lf_across_tiles, tools, lf_offsets, lf_disable, rewrite_param_sets, wavefront)
     sao_ptr = None
     if sao is not None:
         sao = np.ascontiguousarray(sao, SAO_DTYPE)
@@ -476,9 +554,11 @@ class Encoder:
                                                     params.ctypes.data if sao else None, stats.ctypes.data))
         return recs, out, params, stats
 
-    def encode_pictures_chunked(self, yuv, labels=None, deblock=True, sao=True, chunk_frames=0):
+    def encode_pictures_chunked(self, yuv, labels=None, deblock=True, sao=True, chunk_frames=0, on_chunk_hook=None):
         """The same pipeline with the results handed over chunk by chunk (hevcdl_encode_pictures_chunked): a generator-like list of
-        (first, records [count, ctus], pictures [count, samples], SAO parameters or None, stats [count]) copies, one per chunk."""
+        (first, records [count, ctus], pictures [count, samples], SAO parameters or None, stats [count]) copies, one per chunk.
+        on_chunk_hook(first, count) is called inside the library's chunk callback, after the chunk has been copied: what is valid there (get_slice_data with the
+        device entropy switch on, get_quality) can be read from it."""
         yuv, n = self._frames(yuv)
         lab_ptr = None
         if labels is not None:
@@ -494,10 +574,20 @@ class Encoder:
         def on_chunk(_user, first, count, recs, pics, sao_p, stats):
             chunks.append((first, view(recs, REC_DTYPE, (count, self.ctus)), view(pics, yuv.dtype, (count, yuv.shape[1])),
                            view(sao_p, SAO_DTYPE, (count, self.ctus, 3)) if sao_p else None, view(stats, STATS_DTYPE, (count,))))
+            if on_chunk_hook is not None:
+                try:
+                    on_chunk_hook(first, count)
+                except BaseException as exc:      # an exception cannot cross the C frames: stop the call and raise it afterwards
+                    hook_error.append(exc)
+                    return 1
             return 0
         cb = fn_t(on_chunk)
+        hook_error = []
         self.lib.hevcdl_encode_pictures_chunked.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, fn_t, ctypes.c_void_p]
-        self._check(self.lib.hevcdl_encode_pictures_chunked(self._h, yuv.ctypes.data, n, lab_ptr, int(bool(deblock)), int(bool(sao)), int(chunk_frames), cb, None))
+        st = self.lib.hevcdl_encode_pictures_chunked(self._h, yuv.ctypes.data, n, lab_ptr, int(bool(deblock)), int(bool(sao)), int(chunk_frames), cb, None)
+        if hook_error:
+            raise hook_error[0]
+        self._check(st)
         return chunks
 
     # ---- deblocking filter (TComLoopFilter::loopFilterPic) ----
@@ -591,6 +681,56 @@ class Encoder:
         out = np.zeros(count, QUALITY_DTYPE)
         self._check(self.lib.hevcdl_get_quality(self._h, int(first), int(count), out.ctypes.data))
         return out
+
+    # ---- slice data coded on the device (hevcdl_enable_device_entropy) ----
+    def enable_device_entropy(self, on=True):
+        """encode_pictures* also code the slice data of their pictures on the device; read it with get_slice_data or take it from encode_pictures_stream."""
+        self._check(self.lib.hevcdl_enable_device_entropy(self._h, int(bool(on))))
+
+    def set_entropy_capacity(self, capacity_per_ctu):
+        """Test entry point (hevcdl_set_entropy_capacity): the capacity per CTU of the next enable_device_entropy(True); a small value makes the host writer code the pictures."""
+        self._check(self.lib.hevcdl_set_entropy_capacity(self._h, int(capacity_per_ctu)))
+
+    def entropy_info(self):
+        """-> (pictures of the last batch the host writer coded, HIP-event ms of [wavefront phase 1, coding, pack] -- zeros without profile_enable)."""
+        n, ms = ctypes.c_int(0), (ctypes.c_double * 3)()
+        self._check(self.lib.hevcdl_get_entropy_info(self._h, ctypes.byref(n), ms))
+        return n.value, list(ms)
+
+    def get_slice_data(self, first, count):
+        """-> (list of `count` byte strings: the packed sub-streams of each picture, sizes [count, n]) of the last encode_pictures* call."""
+        data, sizes, n = ctypes.c_void_p(), ctypes.POINTER(ctypes.c_uint32)(), ctypes.c_int(0)
+        self._check(self.lib.hevcdl_get_slice_data(self._h, int(first), int(count), ctypes.byref(data), ctypes.byref(sizes), ctypes.byref(n)))
+        sz = np.ctypeslib.as_array(sizes, shape=(count, n.value)).copy() if count else np.zeros((0, n.value), np.uint32)
+        blob = ctypes.string_at(data, int(sz.sum())) if count and sz.sum() else b""
+        ends = np.cumsum(sz.sum(axis=1))
+        return [blob[int(e - t):int(e)] for e, t in zip(ends, sz.sum(axis=1))], sz
+
+    def encode_pictures_stream(self, yuv, labels=None, deblock=True, sao=True, want_pictures=False, want_records=False, chunk_frames=0):
+        """hevcdl_encode_pictures_stream: a list of (first, slice data per picture [count] bytes, sizes [count, n], stats [count], pictures or None, records or None), one per chunk."""
+        yuv, n = self._frames(yuv)
+        lab_ptr = None
+        if labels is not None:
+            labels = np.ascontiguousarray(labels, np.uint8).reshape(n, self.ctus, 16)
+            lab_ptr = labels.ctypes.data
+        chunks = []
+        fn_t = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p)
+
+        def view(ptr, dtype, shape):
+            return np.frombuffer(ctypes.string_at(ptr, int(np.prod(shape)) * np.dtype(dtype).itemsize), dtype).reshape(shape).copy()
+
+        def on_chunk(_user, first, count, data, sizes, n_sub, stats, pics, recs):
+            sz = np.ctypeslib.as_array(sizes, shape=(count, n_sub)).copy()
+            per = sz.sum(axis=1)
+            blob = ctypes.string_at(data, int(per.sum())) if per.sum() else b""
+            ends = np.cumsum(per)
+            chunks.append((first, [blob[int(e - t):int(e)] for e, t in zip(ends, per)], sz, view(stats, STATS_DTYPE, (count,)),
+                           view(pics, yuv.dtype, (count, yuv.shape[1])) if pics else None, view(recs, REC_DTYPE, (count, self.ctus)) if recs else None))
+            return 0
+        cb = fn_t(on_chunk)
+        self.lib.hevcdl_encode_pictures_stream.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, fn_t, ctypes.c_void_p]
+        self._check(self.lib.hevcdl_encode_pictures_stream(self._h, yuv.ctypes.data, n, lab_ptr, int(bool(deblock)), int(bool(sao)), int(bool(want_pictures)), int(bool(want_records)), int(chunk_frames), cb, None))
+        return chunks
 
     def profile_enable(self, on=True):
         self._check(self.lib.hevcdl_profile_enable(self._h, int(on)))

@@ -8,6 +8,7 @@
 #include <vector>
 #include "hevcdl.h"
 #include "hevcdl_dev.h"
+#include "entropy_coder.h"
 
 extern "C" __global__ void hevcdl_cnn_ctu_kernel(hevcdl_cnn_params p);
 extern "C" __global__ void hevcdl_fc_kernel(hevcdl_fc_params p);          // fc_kernel.hip: fully connected head + labels, 16 CTUs per workgroup
@@ -76,6 +77,17 @@ struct hevcdl_ctx {
   bool quality_on = false;                 // hevcdl_enable_quality: the picture pipeline also measures its output pictures
   unsigned char *d_q_pyr = nullptr, *d_q_partial = nullptr, *d_q_weights = nullptr, *d_q_out = nullptr; int q_group = 0;      // workspace of q_group pictures; d_q_out: [max_frames] hevcdl_quality of the pipeline
   std::vector<hevcdl_quality> h_quality;   // the pipeline's last batch (hevcdl_get_quality)
+  // slice data on the device (entropy_kernel.hip): everything below is allocated by hevcdl_enable_device_entropy(ctx, 1) and freed by (ctx, 0); a context that never
+  // turns the switch on allocates and launches none of it
+  bool entropy_on = false;
+  int ec_units = 0, ec_pass_frames = 0; size_t ec_frame_stride = 0;        // sub-streams of a picture, pictures the workspace holds, bytes of a picture's regions
+  unsigned char *d_ec_tables = nullptr, *d_ec_ws = nullptr, *d_ec_packed = nullptr, *d_ec_sync = nullptr;
+  uint32_t *d_ec_off = nullptr, *d_ec_cap = nullptr, *d_ec_sizes = nullptr, *d_ec_ovf = nullptr; unsigned long long *d_ec_dst = nullptr;
+  std::vector<uint32_t> ec_off, ec_cap;
+  std::vector<uint8_t> h_slice; std::vector<uint32_t> h_slice_sizes; std::vector<size_t> h_slice_at;      // the last batch: packed sub-streams, [picture][unit] lengths, start of every picture (+ the end)
+  int ec_fallbacks = 0;                    // pictures of the last batch the host writer coded (a sub-stream overflowed its region)
+  int ec_capacity_per_ctu = 0;             // hevcdl_set_entropy_capacity (tests): 0 = the default
+  double ec_ms[3] = { 0, 0, 0 };           // with `profile`: HIP-event times of the last batch (phase 1, coding, pack)
   bool profile;
   std::vector<hipEvent_t> ev_cnn, ev_rd, ev_conv;       // start/stop pairs (ev_conv: the convolution kernel alone, one pair per chunk of CTUs)
   char err[256];
@@ -338,6 +350,7 @@ extern "C" void hevcdl_destroy(hevcdl_ctx *ctx)
   hipFree(ctx->d_weights); hipFree(ctx->d_scratch); hipFree(ctx->d_yuv); hipFree(ctx->d_labels); hipFree(ctx->d_recon);
   hipFree(ctx->d_wpp); hipFree(ctx->d_records); hipFree(ctx->d_stats); hipFree(ctx->d_logits); hipFree(ctx->d_yuv8); hipFree(ctx->d_a3); hipFree(ctx->d_picture); hipFree(ctx->d_rgb); hipFree(ctx->d_cabac); hipFree(ctx->d_sao_stats); hipFree(ctx->d_sao_recon); hipFree(ctx->d_sao_params); hipFree(ctx->d_sao_cand); hipFree(ctx->d_wide); hipFree(ctx->d_flag); hipFree(ctx->d_sched);
   hipFree(ctx->d_q_pyr); hipFree(ctx->d_q_partial); hipFree(ctx->d_q_weights); hipFree(ctx->d_q_out);
+  hipFree(ctx->d_ec_tables); hipFree(ctx->d_ec_ws); hipFree(ctx->d_ec_packed); hipFree(ctx->d_ec_sync); hipFree(ctx->d_ec_off); hipFree(ctx->d_ec_cap); hipFree(ctx->d_ec_sizes); hipFree(ctx->d_ec_ovf); hipFree(ctx->d_ec_dst);
   delete ctx;
 }
 
@@ -1044,6 +1057,7 @@ extern "C" hevcdl_status hevcdl_get_quality(hevcdl_ctx *ctx, int first, int coun
 // ---- whole picture pipeline for host buffers: the stages of TEncGOP::compressGOP between reading a picture and writing its NAL units, with
 // the picture staying in HBM in between (one upload of the originals, one download of records / final picture / SAO parameters) ----------
 // device side of hevcdl_encode_pictures*: upload, labels, decisions, in-loop filters; the results stay in HBM (*d_final: the output pictures)
+static hevcdl_status entropy_pipeline(hevcdl_ctx *ctx, int n_frames, int want_sao);
 static hevcdl_status encode_pictures_device(hevcdl_ctx *ctx, const void *yuv, int n_frames, const uint8_t *labels_opt, int deblock, int want_sao, uint8_t **d_final)
 {
   hevcdl_status st = ensure_staging(ctx); if (st) return st;
@@ -1067,6 +1081,7 @@ static hevcdl_status encode_pictures_device(hevcdl_ctx *ctx, const void *yuv, in
     ctx->h_quality.resize(n_frames);
     HIPCHK(hipMemcpy(ctx->h_quality.data(), ctx->d_q_out, sizeof(hevcdl_quality) * (size_t)n_frames, hipMemcpyDeviceToHost));
   }
+  if (ctx->entropy_on) { st = entropy_pipeline(ctx, n_frames, want_sao); if (st) return st; }      // hevcdl_enable_device_entropy: the slice data too, from the records still in HBM
   return HEVCDL_OK;
 }
 
@@ -1126,6 +1141,264 @@ extern "C" hevcdl_status hevcdl_encode_pictures_chunked(hevcdl_ctx *ctx, const v
       hipStreamSynchronize(ctx->copy_stream);
       return fail(ctx, HEVCDL_ERR_INVALID_ARG, "the chunk callback asked to stop");
     }
+  }
+  return HEVCDL_OK;
+}
+
+// ---- slice data on the device (entropy_kernel.hip) ---------------------------------------------------------------------------------------------------------
+// what the kernels need to know of a stream configuration
+struct EntropyPlan {
+  hevcdl_entropy_params k;             // geometry, QP, tools filled; pointers not
+  std::vector<uint32_t> off, cap; size_t frame_stride; int units;
+};
+static hevcdl_status entropy_plan(const hevcdl_stream_config *cfg, int capacity_per_ctu, EntropyPlan &pl)
+{
+  int n = 0; size_t bytes = 0;
+  hevcdl_status st = hevcdl_slice_data_layout(cfg, capacity_per_ctu, &n, &bytes, nullptr, nullptr); if (st) return st;
+  pl.off.resize((size_t)n); pl.cap.resize((size_t)n);
+  st = hevcdl_slice_data_layout(cfg, capacity_per_ctu, &n, &bytes, pl.off.data(), pl.cap.data()); if (st) return st;
+  pl.units = n; pl.frame_stride = bytes;
+  hevcdl_entropy_params &k = pl.k; memset(&k, 0, sizeof k);
+  k.width = cfg->width; k.height = cfg->height; k.ctus_x = (cfg->width + 63) >> 6; k.ctus_y = (cfg->height + 63) >> 6; k.qp = cfg->qp; k.tools = (int)cfg->tools;
+  k.max_sao_offset = (1 << ((cfg->bit_depth < 10 ? cfg->bit_depth : 10) - 5)) - 1; k.wpp = cfg->wavefront != 0; k.tile_cols = cfg->tile_columns; k.units = n; k.frame_stride = bytes;
+  const int tiled = cfg->tile_columns * cfg->tile_rows > 1, uniform = cfg->tile_uniform_spacing != 0;
+  if (hevcdl_tile_bounds(k.ctus_x, cfg->tile_columns, uniform, cfg->tile_column_width, tiled ? 4 : 1, k.col_bd) || hevcdl_tile_bounds(k.ctus_y, cfg->tile_rows, uniform, cfg->tile_row_height, 1, k.row_bd))
+    return HEVCDL_ERR_INVALID_ARG;
+  return HEVCDL_OK;
+}
+
+extern "C" hevcdl_status hevcdl_code_slice_data(int device, const hevcdl_stream_config *cfg, const hevcdl_ctu_record *records, const hevcdl_sao_blk *sao_opt, int n_frames,
+                                                int capacity_per_ctu, uint8_t *out, size_t out_capacity, uint32_t *sizes, uint32_t *overflow)
+{
+  if (!cfg || !records || !out || !sizes || !overflow || n_frames < 0) return HEVCDL_ERR_INVALID_ARG;
+  EntropyPlan pl;
+  hevcdl_status st = entropy_plan(cfg, capacity_per_ctu, pl); if (st) return st;
+  if ((cfg->sao_enabled != 0) != (sao_opt != nullptr)) return HEVCDL_ERR_INVALID_ARG;
+  if (out_capacity / (pl.frame_stride ? pl.frame_stride : 1) < (size_t)n_frames) return HEVCDL_ERR_INVALID_ARG;
+  if (n_frames == 0) return HEVCDL_OK;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) { (void)hipGetLastError(); return HEVCDL_ERR_NO_DEVICE; }
+  if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return HEVCDL_ERR_HIP; }
+  const size_t ctus = (size_t)pl.k.ctus_x * pl.k.ctus_y, n_sub = (size_t)n_frames * pl.units;
+  const size_t sz[8] = { ctus * sizeof(hevcdl_ctu_record) * n_frames, sao_opt ? ctus * sizeof(hevcdl_sao_blk) * n_frames : 4, sizeof(hevcdl_ec::EcTables), pl.frame_stride * n_frames,
+                         4 * (size_t)pl.units, 4 * (size_t)pl.units, 8 * n_sub, (size_t)n_frames * pl.k.ctus_y * hevcdl_ec::EC_SYNC_BYTES };
+  unsigned char *d[8] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < 8 && e == hipSuccess; i++) e = hipMalloc(&d[i], sz[i]);
+  if (e == hipSuccess) e = hipMemcpy(d[0], records, sz[0], hipMemcpyHostToDevice);
+  if (e == hipSuccess && sao_opt) e = hipMemcpy(d[1], sao_opt, sz[1], hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d[2], &hevcdl_ec::ec_tables(), sz[2], hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d[3], out, sz[3], hipMemcpyHostToDevice);      // what the kernels do not write comes back as the caller left it
+  if (e == hipSuccess) e = hipMemcpy(d[4], pl.off.data(), sz[4], hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d[5], pl.cap.data(), sz[5], hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(d[6], 0, sz[6]);
+  if (e == hipSuccess) e = hipMemset(d[7], 0, sz[7]);
+  if (e == hipSuccess) {
+    hevcdl_entropy_params k = pl.k;
+    k.records = d[0]; k.sao = sao_opt ? d[1] : nullptr; k.tables = d[2]; k.out = d[3]; k.unit_off = (const uint32_t *)d[4]; k.unit_cap = (const uint32_t *)d[5];
+    k.sizes = (uint32_t *)d[6]; k.overflow = (uint32_t *)d[6] + n_sub; k.sync = d[7]; k.n_frames = n_frames;
+    hevcdl_launch_entropy(&k, nullptr, nullptr);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out, d[3], sz[3], hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(sizes, d[6], 4 * n_sub, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(overflow, d[6] + 4 * n_sub, 4 * n_sub, hipMemcpyDeviceToHost);
+  }
+  for (int i = 0; i < 8; i++) hipFree(d[i]);
+  if (e != hipSuccess) { (void)hipGetLastError(); return e == hipErrorOutOfMemory ? HEVCDL_ERR_OOM : HEVCDL_ERR_HIP; }
+  return HEVCDL_OK;
+}
+
+// the stream configuration a context's pictures are written with, as far as the slice data depends on it
+static void entropy_stream_config(const hevcdl_ctx *ctx, int want_sao, hevcdl_stream_config *sc)
+{
+  const hevcdl_config &c = ctx->cfg;
+  hevcdl_stream_config_default(sc, c.width, c.height, c.qp);
+  sc->sao_enabled = want_sao != 0; sc->tile_columns = c.tile_columns; sc->tile_rows = c.tile_rows; sc->bit_depth = c.bit_depth; sc->tile_uniform_spacing = c.tile_uniform_spacing;
+  memcpy(sc->tile_column_width, c.tile_column_width, sizeof sc->tile_column_width); memcpy(sc->tile_row_height, c.tile_row_height, sizeof sc->tile_row_height);
+  sc->lf_across_tiles = c.lf_across_tiles; sc->tools = c.tools; sc->wavefront = c.wavefront;
+}
+
+static void entropy_release(hevcdl_ctx *ctx)
+{
+  hipFree(ctx->d_ec_tables); hipFree(ctx->d_ec_ws); hipFree(ctx->d_ec_packed); hipFree(ctx->d_ec_sync); hipFree(ctx->d_ec_off); hipFree(ctx->d_ec_cap); hipFree(ctx->d_ec_sizes); hipFree(ctx->d_ec_ovf); hipFree(ctx->d_ec_dst);
+  ctx->d_ec_tables = ctx->d_ec_ws = ctx->d_ec_packed = ctx->d_ec_sync = nullptr; ctx->d_ec_off = ctx->d_ec_cap = ctx->d_ec_sizes = ctx->d_ec_ovf = nullptr; ctx->d_ec_dst = nullptr;
+  ctx->entropy_on = false; ctx->ec_units = ctx->ec_pass_frames = 0; ctx->ec_frame_stride = 0;
+  ctx->h_slice.clear(); ctx->h_slice_sizes.clear(); ctx->h_slice_at.clear(); ctx->ec_fallbacks = 0;
+}
+
+extern "C" hevcdl_status hevcdl_enable_device_entropy(hevcdl_ctx *ctx, int on)
+{
+  if (!ctx) return HEVCDL_ERR_INVALID_ARG;
+  hevcdl_status st = check_frames(ctx, 0); if (st) return st;
+  if (!on) {
+    if (!ctx->entropy_on) return HEVCDL_OK;
+    hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) return fail(ctx, HEVCDL_ERR_HIP, "hevcdl_enable_device_entropy", e);
+    entropy_release(ctx);
+    return HEVCDL_OK;
+  }
+  if (ctx->entropy_on) return HEVCDL_OK;
+  hevcdl_stream_config sc; entropy_stream_config(ctx, 0, &sc);
+  EntropyPlan pl;
+  st = entropy_plan(&sc, ctx->ec_capacity_per_ctu, pl); if (st) return fail(ctx, st, "device entropy: stream configuration");
+  // the workspace holds the regions of at most ENTROPY_WS_BYTES worth of pictures (84 MB a picture at 2160p: 2040 CTUs x 40 KB); larger batches go through it in passes
+  const size_t ENTROPY_WS_BYTES = (size_t)512 << 20;
+  const int pass = (int)std::max<size_t>(1, std::min<size_t>((size_t)ctx->cfg.max_frames, ENTROPY_WS_BYTES / pl.frame_stride));
+  const size_t n_sub = (size_t)pass * pl.units;
+  hipError_t e = hipMalloc(&ctx->d_ec_tables, sizeof(hevcdl_ec::EcTables));
+  if (e == hipSuccess) e = hipMalloc(&ctx->d_ec_ws, pl.frame_stride * pass);
+  if (e == hipSuccess) e = hipMalloc(&ctx->d_ec_packed, pl.frame_stride * pass);
+  if (e == hipSuccess) e = hipMalloc(&ctx->d_ec_sync, (size_t)pass * ctx->ctus_y * hevcdl_ec::EC_SYNC_BYTES);
+  if (e == hipSuccess) e = hipMalloc(&ctx->d_ec_off, 4 * (size_t)pl.units);
+  if (e == hipSuccess) e = hipMalloc(&ctx->d_ec_cap, 4 * (size_t)pl.units);
+  if (e == hipSuccess) e = hipMalloc(&ctx->d_ec_sizes, 4 * n_sub);
+  if (e == hipSuccess) e = hipMalloc(&ctx->d_ec_ovf, 4 * n_sub);
+  if (e == hipSuccess) e = hipMalloc(&ctx->d_ec_dst, 8 * n_sub);
+  if (e == hipSuccess) e = hipMemcpy(ctx->d_ec_tables, &hevcdl_ec::ec_tables(), sizeof(hevcdl_ec::EcTables), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(ctx->d_ec_off, pl.off.data(), 4 * (size_t)pl.units, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(ctx->d_ec_cap, pl.cap.data(), 4 * (size_t)pl.units, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(ctx->d_ec_sync, 0, (size_t)pass * ctx->ctus_y * hevcdl_ec::EC_SYNC_BYTES);
+  if (e != hipSuccess) { entropy_release(ctx); (void)hipGetLastError(); return fail(ctx, e == hipErrorOutOfMemory ? HEVCDL_ERR_OOM : HEVCDL_ERR_HIP, "device entropy workspace", e); }
+  ctx->ec_off = pl.off; ctx->ec_cap = pl.cap; ctx->ec_units = pl.units; ctx->ec_pass_frames = pass; ctx->ec_frame_stride = pl.frame_stride; ctx->entropy_on = true;
+  return HEVCDL_OK;
+}
+
+// The slice data of the n_frames pictures whose records (and SAO parameters) the picture pipeline has just left in HBM -> ctx->h_slice*.  Passes of ec_pass_frames
+// pictures: the two kernels, the lengths to the host, an exclusive scan, the pack kernel, one copy of the used bytes.
+static hevcdl_status entropy_pipeline(hevcdl_ctx *ctx, int n_frames, int want_sao)
+{
+  hevcdl_stream_config sc; entropy_stream_config(ctx, want_sao, &sc);
+  EntropyPlan pl;
+  hevcdl_status st = entropy_plan(&sc, ctx->ec_capacity_per_ctu, pl); if (st) return fail(ctx, st, "device entropy: stream configuration");
+  const int units = ctx->ec_units;
+  ctx->ec_ms[0] = ctx->ec_ms[1] = ctx->ec_ms[2] = 0;
+  hipEvent_t ev[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };      // with the profile switch: start, between the two launches, end of the coding, around the pack launch
+  if (ctx->profile) for (int i = 0; i < 5; i++) HIPCHK(hipEventCreate(&ev[i]));
+  struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 5; i++) if (e[i]) hipEventDestroy(e[i]); } } ev_guard{ ev };
+  const size_t rec_b = (size_t)ctx->ctus * sizeof(hevcdl_ctu_record), sao_b = (size_t)ctx->ctus * sizeof(hevcdl_sao_blk);
+  ctx->h_slice.clear(); ctx->h_slice_sizes.assign((size_t)n_frames * units, 0); ctx->h_slice_at.assign((size_t)n_frames + 1, 0); ctx->ec_fallbacks = 0;
+  std::vector<uint32_t> ovf; std::vector<unsigned long long> dst; std::vector<int> fallback;
+  for (int first = 0; first < n_frames; first += ctx->ec_pass_frames) {
+    const int cnt = std::min(ctx->ec_pass_frames, n_frames - first); const size_t n_sub = (size_t)cnt * units;
+    hevcdl_entropy_params k = pl.k;
+    k.records = ctx->d_records + rec_b * first; k.sao = want_sao ? ctx->d_sao_params + sao_b * first : nullptr; k.tables = ctx->d_ec_tables; k.out = ctx->d_ec_ws;
+    k.unit_off = ctx->d_ec_off; k.unit_cap = ctx->d_ec_cap; k.sizes = ctx->d_ec_sizes; k.overflow = ctx->d_ec_ovf; k.sync = ctx->d_ec_sync; k.n_frames = cnt;
+    if (ev[0]) HIPCHK(hipEventRecord(ev[0], nullptr));
+    hevcdl_launch_entropy(&k, nullptr, ev[1]);
+    if (ev[2]) HIPCHK(hipEventRecord(ev[2], nullptr));
+    HIPCHK(hipGetLastError());
+    uint32_t *sz = ctx->h_slice_sizes.data() + (size_t)first * units;
+    ovf.resize(n_sub); dst.resize(n_sub);
+    HIPCHK(hipMemcpy(sz, ctx->d_ec_sizes, 4 * n_sub, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ovf.data(), ctx->d_ec_ovf, 4 * n_sub, hipMemcpyDeviceToHost));
+    unsigned long long at = 0; bool pass_fallback = false;
+    for (int f = 0; f < cnt; f++) {
+      bool bad = false;
+      for (int u = 0; u < units; u++) bad = bad || ovf[(size_t)f * units + u] != 0 || sz[(size_t)f * units + u] > ctx->ec_cap[(size_t)u];
+      if (bad) { pass_fallback = true; fallback.push_back(first + f); for (int u = 0; u < units; u++) sz[(size_t)f * units + u] = 0; }
+      ctx->h_slice_at[(size_t)first + f] = ctx->h_slice.size() + (size_t)at;
+      for (int u = 0; u < units; u++) { dst[(size_t)f * units + u] = at; at += sz[(size_t)f * units + u]; }
+    }
+    HIPCHK(hipMemcpy(ctx->d_ec_dst, dst.data(), 8 * n_sub, hipMemcpyHostToDevice));
+    hevcdl_entropy_pack_params pk; memset(&pk, 0, sizeof pk);
+    pk.src = ctx->d_ec_ws; pk.dst = ctx->d_ec_packed; pk.unit_off = ctx->d_ec_off; pk.unit_cap = ctx->d_ec_cap; pk.sizes = ctx->d_ec_sizes; pk.dst_off = ctx->d_ec_dst;
+    pk.frame_stride = ctx->ec_frame_stride; pk.dst_cap = ctx->ec_frame_stride * (size_t)cnt; pk.n_frames = cnt; pk.units = units;
+    if (pass_fallback) HIPCHK(hipMemcpy(ctx->d_ec_sizes, sz, 4 * n_sub, hipMemcpyHostToDevice));      // the lengths the offsets were made from (0 for a picture the host codes)
+    if (ev[3]) HIPCHK(hipEventRecord(ev[3], nullptr));
+    hevcdl_launch_entropy_pack(&pk, nullptr);
+    if (ev[4]) HIPCHK(hipEventRecord(ev[4], nullptr));
+    HIPCHK(hipGetLastError());
+    const size_t old = ctx->h_slice.size();
+    ctx->h_slice.resize(old + (size_t)at);
+    if (at) HIPCHK(hipMemcpy(ctx->h_slice.data() + old, ctx->d_ec_packed, (size_t)at, hipMemcpyDeviceToHost));
+    if (ev[0]) {
+      HIPCHK(hipEventSynchronize(ev[4]));
+      float ms = 0;
+      HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1])); ctx->ec_ms[0] += ms;
+      HIPCHK(hipEventElapsedTime(&ms, ev[1], ev[2])); ctx->ec_ms[1] += ms;
+      HIPCHK(hipEventElapsedTime(&ms, ev[3], ev[4])); ctx->ec_ms[2] += ms;
+    }
+  }
+  ctx->h_slice_at[(size_t)n_frames] = ctx->h_slice.size();
+  if (!fallback.empty()) { // a sub-stream did not fit its region: the host writer codes those pictures (their records only), and the batch is put together again in picture order
+    std::vector<uint8_t> all; std::vector<size_t> at((size_t)n_frames + 1, 0);
+    std::vector<hevcdl_ctu_record> rec((size_t)ctx->ctus); std::vector<hevcdl_sao_blk> sao(want_sao ? (size_t)ctx->ctus : 0);
+    size_t fb = 0;
+    for (int f = 0; f < n_frames; f++) {
+      at[(size_t)f] = all.size();
+      if (fb < fallback.size() && fallback[fb] == f) {
+        fb++;
+        HIPCHK(hipMemcpy(rec.data(), ctx->d_records + rec_b * f, rec_b, hipMemcpyDeviceToHost));
+        if (want_sao) HIPCHK(hipMemcpy(sao.data(), ctx->d_sao_params + sao_b * f, sao_b, hipMemcpyDeviceToHost));
+        size_t total = 0; uint32_t *sz = ctx->h_slice_sizes.data() + (size_t)f * units;
+        hevcdl_host_writer_slice_data(&sc, rec.data(), want_sao ? sao.data() : nullptr, nullptr, 0, sz, &total);
+        all.resize(at[(size_t)f] + total);
+        if (hevcdl_host_writer_slice_data(&sc, rec.data(), want_sao ? sao.data() : nullptr, all.data() + at[(size_t)f], total, sz, &total) != 0) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "device entropy: host fallback");
+      } else all.insert(all.end(), ctx->h_slice.begin() + (ptrdiff_t)ctx->h_slice_at[(size_t)f], ctx->h_slice.begin() + (ptrdiff_t)ctx->h_slice_at[(size_t)f + 1]);
+    }
+    at[(size_t)n_frames] = all.size();
+    ctx->h_slice.swap(all); ctx->h_slice_at.swap(at); ctx->ec_fallbacks = (int)fallback.size();
+  }
+  return HEVCDL_OK;
+}
+
+extern "C" hevcdl_status hevcdl_set_entropy_capacity(hevcdl_ctx *ctx, int capacity_per_ctu)
+{
+  if (!ctx) return HEVCDL_ERR_INVALID_ARG;
+  if (ctx->entropy_on) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_set_entropy_capacity: the switch is on");
+  if (capacity_per_ctu > 0 && (capacity_per_ctu & 3)) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_set_entropy_capacity: not a multiple of 4");
+  ctx->ec_capacity_per_ctu = capacity_per_ctu > 0 ? capacity_per_ctu : 0;
+  return HEVCDL_OK;
+}
+
+extern "C" hevcdl_status hevcdl_get_entropy_info(hevcdl_ctx *ctx, int *fallbacks_opt, double *kernel_ms_opt)
+{
+  if (!ctx) return HEVCDL_ERR_INVALID_ARG;
+  if (!ctx->entropy_on) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_get_entropy_info: hevcdl_enable_device_entropy was not called");
+  if (fallbacks_opt) *fallbacks_opt = ctx->ec_fallbacks;
+  if (kernel_ms_opt) for (int i = 0; i < 3; i++) kernel_ms_opt[i] = ctx->ec_ms[i];
+  return HEVCDL_OK;
+}
+
+extern "C" hevcdl_status hevcdl_get_slice_data(hevcdl_ctx *ctx, int first, int count, const uint8_t **data, const uint32_t **sizes, int *n_substreams_per_picture)
+{
+  if (!ctx) return HEVCDL_ERR_INVALID_ARG;
+  if (!data || !sizes || !n_substreams_per_picture || first < 0 || count < 0) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_get_slice_data: bad range");
+  if (!ctx->entropy_on) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_get_slice_data: hevcdl_enable_device_entropy was not called");
+  if ((size_t)first + (size_t)count + 1 > ctx->h_slice_at.size()) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_get_slice_data: pictures outside the last batch");
+  *data = ctx->h_slice.data() + ctx->h_slice_at[(size_t)first]; *sizes = ctx->h_slice_sizes.data() + (size_t)first * ctx->ec_units; *n_substreams_per_picture = ctx->ec_units;
+  return HEVCDL_OK;
+}
+
+extern "C" hevcdl_status hevcdl_encode_pictures_stream(hevcdl_ctx *ctx, const void *yuv, int n_frames, const uint8_t *labels_opt, int deblock, int want_sao,
+                                                       int want_pictures, int want_records, int chunk_frames, hevcdl_stream_fn fn, void *user)
+{
+  hevcdl_status st = check_frames(ctx, n_frames); if (st) return st;
+  if (!ctx->entropy_on) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_encode_pictures_stream: hevcdl_enable_device_entropy was not called");
+  if (n_frames == 0) return HEVCDL_OK;
+  if (!yuv || !fn) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null pointer");
+  const int chunk = std::min(n_frames, chunk_frames > 0 ? chunk_frames : 64);
+  const size_t rec_b = want_records ? (size_t)ctx->ctus * sizeof(hevcdl_ctu_record) : 0, pic_b = want_pictures ? ctx->frame_bytes : 0, stat_b = sizeof(hevcdl_frame_stats);
+  auto up64 = [](size_t v) { return (v + 63) & ~(size_t)63; };
+  const size_t o_pic = up64(rec_b * chunk), o_stat = up64(o_pic + pic_b * chunk), need = o_stat + stat_b * chunk;
+  if (ctx->h_chunk_bytes < need) {
+    for (int i = 0; i < 2; i++) { if (ctx->h_chunk[i]) hipHostFree(ctx->h_chunk[i]); ctx->h_chunk[i] = nullptr; }
+    ctx->h_chunk_bytes = 0;
+    for (int i = 0; i < 2; i++) HIPCHK(hipHostMalloc((void **)&ctx->h_chunk[i], need, hipHostMallocDefault));
+    ctx->h_chunk_bytes = need;
+  }
+  uint8_t *d_final = nullptr;
+  st = encode_pictures_device(ctx, yuv, n_frames, labels_opt, deblock, want_sao, &d_final); if (st) return st;      // runs the entropy kernels too (the switch is on)
+  unsigned char *h = ctx->h_chunk[0];
+  for (int first = 0; first < n_frames; first += chunk) { // records and pictures leave HBM only when asked for; the statistics are 40 bytes a picture
+    const int cnt = std::min(chunk, n_frames - first);
+    if (want_records) HIPCHK(hipMemcpy(h, ctx->d_records + rec_b * first, rec_b * cnt, hipMemcpyDeviceToHost));
+    if (want_pictures) HIPCHK(hipMemcpy(h + o_pic, d_final + pic_b * first, pic_b * cnt, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h + o_stat, ctx->d_stats + stat_b * first, stat_b * cnt, hipMemcpyDeviceToHost));
+    if (fn(user, first, cnt, ctx->h_slice.data() + ctx->h_slice_at[(size_t)first], ctx->h_slice_sizes.data() + (size_t)first * ctx->ec_units, ctx->ec_units,
+           (const hevcdl_frame_stats *)(h + o_stat), want_pictures ? h + o_pic : nullptr, want_records ? (const hevcdl_ctu_record *)h : nullptr) != 0)
+      return fail(ctx, HEVCDL_ERR_INVALID_ARG, "the stream callback asked to stop");
   }
   return HEVCDL_OK;
 }

@@ -41,7 +41,7 @@ const Key KEYS[] = {
   { "SourceHeight", "hgt", USED, 0 }, { "FrameRate", "fr", USED, 0 }, { "FrameSkip", "fs", USED, 0 }, { "FramesToBeEncoded", "f", USED, 0 },
   { "QP", "q", USED, 0 },
   // extensions of this front end
-  { "LabelDir", 0, USED, 0 }, { "BatchFrames", 0, USED, 0 }, { "ChunkFrames", 0, USED, 0 }, { "Device", 0, USED, 0 }, { "Devices", 0, USED, 0 }, { "NumDevices", 0, USED, 0 }, { "Weights", 0, USED, 0 }, { "RecordFile", 0, USED, 0 },
+  { "LabelDir", 0, USED, 0 }, { "BatchFrames", 0, USED, 0 }, { "ChunkFrames", 0, USED, 0 }, { "Device", 0, USED, 0 }, { "Devices", 0, USED, 0 }, { "NumDevices", 0, USED, 0 }, { "Weights", 0, USED, 0 }, { "RecordFile", 0, USED, 0 }, { "DeviceEntropy", 0, USED, 0 },
   { "CnnInput", 0, USED, 0 }, { "BnMode", 0, USED, 0 }, { "PrintConfig", 0, USED, 0 }, { "LoopFilterDisable", 0, USED, 0 },
   // keys that define the path: only the implemented value is accepted
   { "InputBitDepth", 0, USED, 0 }, { "InternalBitDepth", 0, USED, 0 }, { "InputChromaFormat", 0, PATH, "420" }, { "Profile", 0, USED, 0 },
@@ -241,6 +241,9 @@ int main(int argc, char **argv)
   // decoded picture hash SEI (TAppEncCfg.cpp:1093): 0 none, 1 MD5 of the output picture behind every access unit
   const int hash_sei = (int)opt.geti("SEIDecodedPictureHash", 0);
   // PrintMSSSIM: computed on the device from the pictures the pipeline still holds there (hevcdl_enable_quality); the two MSE keys only print what the PSNR is made of
+  // DeviceEntropy 1: the slice data is coded on the device (hevcdl_enable_device_entropy) and the run goes through hevcdl_encode_pictures_stream: records leave HBM only for
+  // a record file, pictures only for a reconstruction file, a picture hash or the PSNR of the filtered picture.  Every output is byte for byte that of the run without the key.
+  const bool device_entropy = opt.geti("DeviceEntropy", 0) != 0;
   const bool print_msssim = opt.geti("PrintMSSSIM", 0) != 0, print_frame_mse = opt.geti("PrintFrameMSE", 0) != 0, print_seq_mse = opt.geti("PrintSequenceMSE", 0) != 0;
   for (const char *key : { "LoopFilterBetaOffset_div2", "LoopFilterTcOffset_div2" }) {      // the reference's own range check (TAppEncCfg.cpp xConfirmPara: -6 .. 6)
     const long v = opt.geti(key, 0);
@@ -376,6 +379,8 @@ int main(int argc, char **argv)
       if (st == HEVCDL_OK && (st = hevcdl_reserve_workspace(shards[i].ctx)) != HEVCDL_OK) { ws_oom = st == HEVCDL_ERR_OOM; hevcdl_destroy(shards[i].ctx); shards[i].ctx = nullptr; }
       // PrintMSSSIM: the quality pass's workspace (pyramids of up to 16 pictures) is reserved by the switch; a refusal halves the batch like any other
       if (st == HEVCDL_OK && print_msssim && (st = hevcdl_enable_quality(shards[i].ctx, 1)) != HEVCDL_OK) { hevcdl_destroy(shards[i].ctx); shards[i].ctx = nullptr; }
+      // DeviceEntropy: the sub-stream regions and the packed buffer are reserved by the switch as well
+      if (st == HEVCDL_OK && device_entropy && (st = hevcdl_enable_device_entropy(shards[i].ctx, 1)) != HEVCDL_OK) { hevcdl_destroy(shards[i].ctx); shards[i].ctx = nullptr; }
       if (st == HEVCDL_ERR_OOM && ws_oom) {
         // the workspace is sized by the device's CUs, not by the batch: a smaller batch does not shrink it.  What does: the independent launch form (a block per wave of
         // the context's own frames instead of every CU's workgroup), then the eight-wave build
@@ -464,8 +469,13 @@ int main(int argc, char **argv)
     if (!yuv_mem.data()) { fprintf(stderr, "Error: cannot allocate %zu bytes of page-locked memory for the originals\n", (size_t)frame_bytes * sb); S.rc = 3; fclose(fi); return; }
     std::vector<uint8_t> labels_mem(label_dir.empty() ? 0 : (size_t)ctus * 16 * sb);
     struct ChunkCtx { long f0; double et; const uint8_t *yuv; std::chrono::steady_clock::time_point t0; int nb; } cc = { 0, 0.0, nullptr, now(), 1 };
-    auto on_chunk = [&](int first, int count, const hevcdl_ctu_record *recs, const void *pictures, const hevcdl_sao_blk *sao_params, const hevcdl_frame_stats *stats) -> int {
+    const bool want_pictures = frec || hash_sei || deblock, want_records = frecords != nullptr;      // what a DeviceEntropy run still fetches from HBM
+    // slice_data / slice_sizes / n_sub: the packed sub-streams of the chunk's pictures (DeviceEntropy), or null: the host writer codes the records
+    auto on_chunk = [&](int first, int count, const hevcdl_ctu_record *recs, const void *pictures, const hevcdl_sao_blk *sao_params, const hevcdl_frame_stats *stats,
+                        const uint8_t *slice_data, const uint32_t *slice_sizes, int n_sub) -> int {
       const auto th0 = now();
+      std::vector<size_t> slice_at(slice_data ? (size_t)count + 1 : 0, 0);
+      for (int i = 0; slice_data && i < count; i++) { size_t n = 0; for (int k = 0; k < n_sub; k++) n += slice_sizes[(size_t)i * n_sub + k]; slice_at[(size_t)i + 1] = slice_at[(size_t)i] + n; }
       if (first == 0) cc.et = secs(cc.t0, th0) / cc.nb;                // device seconds per picture of this call (the log line's ET)
       const uint8_t *recon = (const uint8_t *)pictures;
       std::vector<PicOut> pics(count);
@@ -476,9 +486,10 @@ int main(int argc, char **argv)
         auto work = [&]() {
           std::vector<uint8_t> buf(hevcdl_access_unit_bound(width, height));
           for (int i = next++; i < count; i = next++) {
+            if (slice_data && buf.size() < slice_at[(size_t)i + 1] - slice_at[(size_t)i] + 4096) buf.resize(2 * (slice_at[(size_t)i + 1] - slice_at[(size_t)i]) + 4096);
             PicOut &po = pics[i]; po.md5_text[0] = 0;
             for (int c = 0; c < 3; c++) po.sse[c] = stats[i].sse[c];
-            if (deblock) { // the picture statistics follow the filtered picture: recomputed here
+            if (deblock && recon) { // the picture statistics follow the filtered picture: recomputed here
               const uint8_t *o = cc.yuv + frame_bytes * (size_t)(first + i), *r = recon + frame_bytes * (size_t)i;
               const size_t n[3] = { (size_t)width * height, (size_t)width * height / 4, (size_t)width * height / 4 };
               size_t off = 0;
@@ -495,7 +506,8 @@ int main(int argc, char **argv)
               }
             }
             // the access unit: VPS+SPS+PPS+slice, written to -b; its size is the picture's bit count (TEncGOP.cpp:2420-2447)
-            po.st = hevcdl_write_access_unit(&scfg, (int)(cc.f0 + first + i), recs + (size_t)ctus * i, sao ? sao_params + (size_t)ctus * i : nullptr, buf.data(), buf.size(), &po.au_len);
+            if (slice_data) po.st = hevcdl_write_access_unit_from_slice_data(&scfg, (int)(cc.f0 + first + i), slice_data + slice_at[(size_t)i], slice_sizes + (size_t)i * n_sub, n_sub, buf.data(), buf.size(), &po.au_len);
+            else po.st = hevcdl_write_access_unit(&scfg, (int)(cc.f0 + first + i), recs + (size_t)ctus * i, sao ? sao_params + (size_t)ctus * i : nullptr, buf.data(), buf.size(), &po.au_len);
             if (po.st != HEVCDL_OK) continue;
             po.bytes.assign(buf.begin(), buf.begin() + po.au_len);
             if (hash_sei) { // suffix SEI after the slice; not part of the picture's bit count (as in the reference)
@@ -540,7 +552,9 @@ int main(int argc, char **argv)
       return 0;
     };
     struct Tramp { static int call(void *u, int first, int count, const hevcdl_ctu_record *recs, const void *pics, const hevcdl_sao_blk *sp, const hevcdl_frame_stats *st)
-                   { return (*(decltype(on_chunk) *)u)(first, count, recs, pics, sp, st); } };
+                   { return (*(decltype(on_chunk) *)u)(first, count, recs, pics, sp, st, nullptr, nullptr, 0); }
+                   static int stream(void *u, int first, int count, const uint8_t *data, const uint32_t *sizes, int n_sub, const hevcdl_frame_stats *st, const void *pics, const hevcdl_ctu_record *recs)
+                   { return (*(decltype(on_chunk) *)u)(first, count, recs, pics, nullptr, st, data, sizes, n_sub); } };
     const long total = S.f_hi - S.f_lo, n_batches = (total + sb - 1) / sb;
     for (long bi = 0; bi < n_batches && S.rc == 0; bi++) {
       const long f0 = S.f_lo + bi * (long)sb; const int nb = (int)std::min<long>(sb, S.f_hi - f0);
@@ -562,7 +576,8 @@ int main(int argc, char **argv)
       S.t_read += secs(tr0, t0);
       cc.f0 = f0; cc.yuv = yuv_mem.data(); cc.et = 0.0; cc.t0 = t0; cc.nb = nb;
       const double host_before = S.t_host + S.t_write;
-      const hevcdl_status est = hevcdl_encode_pictures_chunked(S.ctx, yuv_mem.data(), nb, lab, deblock ? 1 : 0, sao ? 1 : 0, chunk, &Tramp::call, &on_chunk);
+      const hevcdl_status est = device_entropy ? hevcdl_encode_pictures_stream(S.ctx, yuv_mem.data(), nb, lab, deblock ? 1 : 0, sao ? 1 : 0, want_pictures ? 1 : 0, want_records ? 1 : 0, chunk, &Tramp::stream, &on_chunk)
+                                               : hevcdl_encode_pictures_chunked(S.ctx, yuv_mem.data(), nb, lab, deblock ? 1 : 0, sao ? 1 : 0, chunk, &Tramp::call, &on_chunk);
       S.t_dev += secs(t0, now()) - ((S.t_host + S.t_write) - host_before);
       if (est != HEVCDL_OK && S.rc == 0) { fprintf(stderr, "Error: %s (status %d)\n", hevcdl_last_error(S.ctx), (int)est); S.rc = 3; }
     }

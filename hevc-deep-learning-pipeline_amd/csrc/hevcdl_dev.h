@@ -161,6 +161,29 @@ struct hevcdl_quality_params {
   double c1, c2;                   // (0.01 max)^2, (0.03 max)^2, max = (1 << bit depth) - 1 (TEncGOP.cpp:2664-2666)
 };
 
+// slice data on the device (entropy_kernel.hip): one wave per sub-stream
+struct hevcdl_entropy_params {
+  const unsigned char *records;    // [frame][ctu] hevcdl_ctu_record
+  const unsigned char *sao;        // [frame][ctu] hevcdl_sao_blk, or NULL: SAO is off
+  const void *tables;              // hevcdl_ec::EcTables
+  unsigned char *out;              // sub-stream k of frame f: out + f * frame_stride + unit_off[k], unit_cap[k] bytes (dword aligned, a multiple of 4)
+  const uint32_t *unit_off, *unit_cap;     // [units]
+  uint32_t *sizes, *overflow;      // [frame][unit]: bytes produced (the true length, also past the capacity), sticky overflow word
+  unsigned char *sync;             // wavefront: [frame][ctus_y] 192 bytes, the contexts behind every row's second CTU (phase 1 writes, phase 2 reads); otherwise NULL
+  size_t frame_stride;
+  int n_frames, units;             // units of a frame: tiles, CTU rows (wavefront), or 1
+  int phase;                       // set by hevcdl_launch_entropy: 0 tiles / frames, 1 and 2 the two wavefront launches
+  int width, height, ctus_x, ctus_y, qp, tools, max_sao_offset, wpp, tile_cols;
+  int col_bd[21], row_bd[23];
+};
+struct hevcdl_entropy_pack_params {
+  const unsigned char *src; unsigned char *dst;
+  const uint32_t *unit_off, *unit_cap, *sizes;
+  const unsigned long long *dst_off;       // [frame][unit]
+  size_t frame_stride, dst_cap;
+  int n_frames, units;
+};
+
 // Tile boundaries in CTUs: bd[0] = 0 < bd[1] < ... < bd[n_tiles] = n_ctus.  Uniform spacing as TComPicSym.cpp xInitTiles; explicit sizes
 // name every tile but the last (which takes the rest).  min_size: smallest tile the reference accepts (4 CTU columns, 1 CTU row,
 // TComPicSym.cpp:380-392) when there is more than one tile in that direction.  Returns 0 when the layout is valid.
@@ -216,6 +239,11 @@ void hevcdl_launch_deblock(const struct hevcdl_dbk_params *p, void *stream);
 int hevcdl_quality_scales(int w, int h);
 void hevcdl_quality_layout(struct hevcdl_quality_params *p);      // fills scales / *_off / pyr_* / part_pic from the planes' sizes
 void hevcdl_launch_quality(const struct hevcdl_quality_params *p, void *stream);
+// hevcdl_bitstream.cpp: the packed sub-streams of one picture by the host writer (fallback of the device entropy coder); 0, or -1 when `capacity` is too small
+int hevcdl_host_writer_slice_data(const struct hevcdl_stream_config *cfg, const struct hevcdl_ctu_record *records, const struct hevcdl_sao_blk *sao, uint8_t *out, size_t capacity,
+                                  uint32_t *sizes, size_t *total);
+void hevcdl_launch_entropy(const struct hevcdl_entropy_params *p, void *stream, void *mid_event_opt);      // one launch, or the two of the wavefront scheme; mid_event_opt (a hipEvent_t) is recorded between the two
+void hevcdl_launch_entropy_pack(const struct hevcdl_entropy_pack_params *p, void *stream);
 size_t hevcdl_cnn_smem_bytes(void);
 size_t hevcdl_fc_smem_bytes(void);
 size_t hevcdl_rd_smem_bytes(void);

@@ -12,7 +12,7 @@ import time
 
 import numpy as np
 
-from . import Encoder, write_access_unit, picture_hash_sei
+from . import Encoder, write_access_unit, picture_hash_sei, stream_config, write_access_unit_from_slice_data
 from . import metrics, sharding
 
 
@@ -40,11 +40,14 @@ def read_frames(path, width, height, first, count, bit_depth=8):
 
 
 def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None, recon_path=None, frame_skip=0, batch=256, tiles=(1, 1),
-                    lf_across_tiles=True, bit_depth=8, level_idc=186, frame_rate=30.0, hash_sei=False, labels_fn=None, device=None, log=print, tools=0x7f, wavefront=False):
+                    lf_across_tiles=True, bit_depth=8, level_idc=186, frame_rate=30.0, hash_sei=False, labels_fn=None, device=None, log=print, tools=0x7f, wavefront=False, device_entropy=False):
     """Encode frames [frame_skip, frame_skip + n_frames) of a planar YUV file.  Works stand-alone and under torch.distributed
     (initialised by the caller): rank r takes a contiguous share of the frames.  Returns, on rank 0, the summary (metrics.Summary)
     and the list of per-picture rows [poc, bits, sseY, sseU, sseV]; other ranks return (None, None).
-    labels_fn(first_poc, count) -> uint8 [count, ctus, 16] replaces the on-device CNN (the reference's label files)."""
+    labels_fn(first_poc, count) -> uint8 [count, ctus, 16] replaces the on-device CNN (the reference's label files).
+    device_entropy: the slice data is coded on the device (Encoder.enable_device_entropy) and the host only writes what surrounds it; the stream is the same bytes.
+    This takes the arithmetic coder off the host threads; it saves no copies here, since this function also needs the pictures (reconstruction file, hash, SSE) and fetches
+    records and SAO parameters with them through encode_pictures.  A caller that needs neither uses Encoder.encode_pictures_stream."""
     import torch
     import torch.distributed as dist
     multi = dist.is_available() and dist.is_initialized()
@@ -60,6 +63,10 @@ def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None
     if len(mine):
         enc = Encoder(width, height, qp, max_frames=min(batch, len(mine)), device=device, tiles=tiles, bit_depth=bit_depth, lf_across_tiles=lf_across_tiles, tools=tools, wavefront=wavefront)      # tools: HEVCDL_TOOL_*; wavefront: WaveFrontSynchro mask (the cfg's tool switches)
         ysz = width * height
+        scfg = None
+        if device_entropy:
+            enc.enable_device_entropy(True)
+            scfg = stream_config(width, height, qp, level_idc, True, tiles, bit_depth, lf_across_tiles, tools, wavefront=wavefront)
         for b0 in range(mine.start, mine.stop, batch):
             nb = min(batch, mine.stop - b0)
             yuv = read_frames(input_path, width, height, frame_skip + b0, nb, bit_depth)
@@ -67,8 +74,12 @@ def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None
             labels = labels_fn(b0, nb) if labels_fn else None
             recs, final, sao, _ = enc.encode_pictures(yuv, labels)          # CNN -> decisions -> deblocking -> SAO, pictures stay in HBM
             et = (time.time() - t0) / nb
+            slices, slice_sizes = enc.get_slice_data(0, nb) if device_entropy else (None, None)
             def one_picture(i):          # host work of a picture (arithmetic coder, hash, SSE): independent -> thread pool (ctypes drops the GIL)
-                au = write_access_unit(width, height, qp, b0 + i, recs[i], level_idc=level_idc, sao=sao[i], tiles=tiles, bit_depth=bit_depth, lf_across_tiles=lf_across_tiles, tools=tools, wavefront=wavefront)
+                if device_entropy:
+                    au = write_access_unit_from_slice_data(scfg, b0 + i, slices[i], slice_sizes[i])
+                else:
+                    au = write_access_unit(width, height, qp, b0 + i, recs[i], level_idc=level_idc, sao=sao[i], tiles=tiles, bit_depth=bit_depth, lf_across_tiles=lf_across_tiles, tools=tools, wavefront=wavefront)
                 sei = picture_hash_sei(width, height, final[i], bit_depth) if hash_sei else b""
                 d = (yuv[i].astype(np.int64) - final[i].astype(np.int64)) ** 2
                 return au, sei, [int(d[:ysz].sum()), int(d[ysz:ysz + ysz // 4].sum()), int(d[ysz + ysz // 4:].sum())]

@@ -225,6 +225,35 @@ typedef int (*hevcdl_chunk_fn)(void *user, int first, int count, const hevcdl_ct
 hevcdl_status hevcdl_encode_pictures_chunked(hevcdl_ctx *ctx, const void *yuv, int n_frames, const uint8_t *labels_opt, int deblock, int want_sao,
                                              int chunk_frames, hevcdl_chunk_fn fn, void *user);
 
+/* ---- slice data coded on the device (opt-in; csrc/entropy_kernel.hip) ----------------------------------------------------------------------------
+ * hevcdl_enable_device_entropy(ctx, 1): every hevcdl_encode_pictures / _chunked / _stream call also codes the slice data of its pictures on the device, from the records
+ * and SAO parameters still in HBM (one wave per sub-stream; wavefront rows in two launches, nothing waits).  The call reserves the whole workspace -- sub-stream regions
+ * of up to 512 MB worth of pictures (larger batches go through it in passes), as much again for the packed bytes -- and returns HEVCDL_ERR_OOM when the device refuses;
+ * (ctx, 0) synchronises the device and frees it.  Off (the default): nothing is launched or allocated, hevcdl_get_slice_data and hevcdl_encode_pictures_stream return
+ * HEVCDL_ERR_INVALID_ARG.
+ * hevcdl_get_slice_data: the packed sub-streams of pictures [first, first + count) of the LAST such call (valid inside the chunk callback and until the next call):
+ * *data, the lengths (*sizes)[count][*n_substreams_per_picture]; picture by picture they feed hevcdl_write_access_unit_from_slice_data.  A picture with a sub-stream that
+ * did not fit its region (capacity: 40 960 bytes per CTU + 64) is coded by the host writer from its records instead; the caller sees no difference. */
+hevcdl_status hevcdl_enable_device_entropy(hevcdl_ctx *ctx, int on);
+hevcdl_status hevcdl_get_slice_data(hevcdl_ctx *ctx, int first, int count, const uint8_t **data, const uint32_t **sizes, int *n_substreams_per_picture);
+/* The picture pipeline for a caller that writes the stream from slice data: as hevcdl_encode_pictures_chunked, but the callback gets the slice data of the chunk (as
+ * hevcdl_get_slice_data) and the statistics; the output pictures only with want_pictures, the records only with want_records (NULL otherwise) -- without the two
+ * flags neither leaves HBM (43 MB a 2160p picture; its slice data is about 0.1 MB).  Needs hevcdl_enable_device_entropy(ctx, 1).  SAO parameters are in the slice
+ * data already. */
+typedef int (*hevcdl_stream_fn)(void *user, int first, int count, const uint8_t *slice_data, const uint32_t *sizes, int n_substreams_per_picture,
+                                const hevcdl_frame_stats *stats, const void *pictures_opt, const hevcdl_ctu_record *records_opt);
+hevcdl_status hevcdl_encode_pictures_stream(hevcdl_ctx *ctx, const void *yuv, int n_frames, const uint8_t *labels_opt, int deblock, int want_sao,
+                                            int want_pictures, int want_records, int chunk_frames, hevcdl_stream_fn fn, void *user);
+/* TEST AND DIAGNOSTIC entry points of the switch.
+ * hevcdl_set_entropy_capacity: the capacity per CTU the NEXT hevcdl_enable_device_entropy(ctx, 1) lays its sub-stream regions out with (<= 0: the default; otherwise a
+ * multiple of 4).  A small value makes sub-streams overflow, so that the host writer codes those pictures: that is what it is for.  HEVCDL_ERR_INVALID_ARG while the
+ * switch is on.
+ * hevcdl_get_entropy_info: about the last hevcdl_encode_pictures* call with the switch on -- *fallbacks_opt: pictures the host writer coded; kernel_ms_opt[3]: HIP-event
+ * times of the wavefront phase-1 launch (0 without wavefront), the coding launch and the pack launch, summed over the passes; measured only with
+ * hevcdl_profile_enable(ctx, 1), zeros otherwise. */
+hevcdl_status hevcdl_set_entropy_capacity(hevcdl_ctx *ctx, int capacity_per_ctu);
+hevcdl_status hevcdl_get_entropy_info(hevcdl_ctx *ctx, int *fallbacks_opt, double *kernel_ms_opt);
+
 /* ---- picture quality: the reference's PrintMSSSIM / PrintFrameMSE / PrintSequenceMSE numbers, computed on the device --------------
  * Replaces TEncGOP::xCalculateMSSSIM (TEncGOP.cpp:2559-2727: 11 x 11 Gaussian window in f64 at every sample position of up to five scales) and the SSD
  * loop of xCalculateAddPSNR (:2380-2390).  org / pic: n_frames packed planar 4:2:0 pictures of the context's size and bit depth (uint16 samples at 10 bits).
@@ -291,6 +320,30 @@ size_t        hevcdl_access_unit_bound(int width, int height);
  * buffer is too small (HEVCDL_ERR_INVALID_ARG), so the call can be repeated. */
 hevcdl_status hevcdl_write_access_unit(const hevcdl_stream_config *cfg, int poc, const hevcdl_ctu_record *records, const hevcdl_sao_blk *sao,
                                        uint8_t *out, size_t capacity, size_t *out_len);
+
+/* ---- slice data coded apart from the access unit (csrc/entropy_coder.h: one coder source for the host and the device) -------------------
+ * The slice data of a picture is its sub-streams back to back: one per tile in raster order of the tile grid, one per CTU row with wavefront, otherwise one; each
+ * is the arithmetic coder's bytes of its CTUs followed by byte_alignment().  hevcdl_write_access_unit_from_slice_data writes everything around that payload exactly as
+ * hevcdl_write_access_unit does -- parameter sets, slice segment header with the entry points (counted with their emulation prevention bytes), NAL packing -- so
+ * that for the same decisions the two give the same bytes.  data: the n_substreams sub-streams of picture `poc`, packed; sizes: their lengths. */
+hevcdl_status hevcdl_write_access_unit_from_slice_data(const hevcdl_stream_config *cfg, int poc, const uint8_t *data, const uint32_t *sizes, int n_substreams,
+                                                       uint8_t *out, size_t capacity, size_t *out_len);
+/* TEST AND DIAGNOSTIC entry points (host buffers in and out; the picture pipeline's form is hevcdl_enable_device_entropy above).
+ * hevcdl_slice_data_layout: where the coder puts the sub-streams of ONE picture in a slice-data buffer.  Sub-stream k owns the region [offsets[k], offsets[k] +
+ * capacities[k]), capacities[k] = (its CTUs) x capacity_per_ctu + 64, and the regions lie 64 bytes apart: the coder writes nothing but the regions, so a caller may keep a
+ * pattern in the gaps (the tests do).  Picture i of a call starts at i x picture_bytes.  capacity_per_ctu <= 0: the default, 40 960: above the derived worst case of a CTU, 38 582 bytes (csrc/entropy_coder.h);
+ * otherwise a multiple of 4 (a small value makes sub-streams overflow: that is what it is for).  offsets_opt / capacities_opt: [n_substreams], may be NULL.
+ * hevcdl_code_slice_data_host: the shared coder on the CPU (no GPU needed) for n_frames pictures: records [n_frames][ctus], sao_opt [n_frames][ctus] or NULL as
+ * cfg->sao_enabled says, out as laid out above, sizes / overflow [n_frames][n_substreams].  A sub-stream that does not fit its region sets its overflow word; its size is
+ * still the true length, and nothing outside the region is written.
+ * hevcdl_code_slice_data: the same by the device kernels (csrc/entropy_kernel.hip) on `device`: uploads (the out buffer too, so that what the kernels leave untouched comes
+ * back as it went), runs them and downloads. */
+hevcdl_status hevcdl_slice_data_layout(const hevcdl_stream_config *cfg, int capacity_per_ctu, int *n_substreams, size_t *picture_bytes,
+                                       uint32_t *offsets_opt, uint32_t *capacities_opt);
+hevcdl_status hevcdl_code_slice_data_host(const hevcdl_stream_config *cfg, const hevcdl_ctu_record *records, const hevcdl_sao_blk *sao_opt, int n_frames,
+                                          int capacity_per_ctu, uint8_t *out, size_t out_capacity, uint32_t *sizes, uint32_t *overflow);
+hevcdl_status hevcdl_code_slice_data(int device, const hevcdl_stream_config *cfg, const hevcdl_ctu_record *records, const hevcdl_sao_blk *sao_opt, int n_frames,
+                                     int capacity_per_ctu, uint8_t *out, size_t out_capacity, uint32_t *sizes, uint32_t *overflow);
 
 /* Decoded picture hash (cfg key SEIDecodedPictureHash 1 = MD5): the suffix SEI NAL the reference appends to the access unit
  * (TEncGOP.cpp:1938-1960), computed from `picture` = the final reconstruction (planar 4:2:0; uint16 samples at 10 bits).  At most
