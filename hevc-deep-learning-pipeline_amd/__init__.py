@@ -19,8 +19,10 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG_DIR)
 LIB_PATH = os.environ.get("HEVCDL_LIB") or os.path.join(PKG_DIR, "lib", "libhevcdl_hip.so")
 TRACE_LIB_PATH = os.path.join(PKG_DIR, "lib", "libhevcdl_hip_trace.so")      # -DHEVCDL_STAGE_TRACE build, loaded by tests/test_rd_gpu.py only
+LEAF_LIB_PATH = os.path.join(PKG_DIR, "lib", "libhevcdl_hip_leaf.so")        # -DHEVCDL_LEAF_TEST build of the decision kernel's four builds alone (csrc/rd_leaf*.hip), loaded by tests/test_rd_leaf_gpu.py only (in a process of its own)
 WEIGHTS_PATH = os.path.join(PKG_DIR, "weights", "hevc_encoder_model.f32")
 WEIGHT_FLOATS = 637712
+LEAF_SOURCES = ["rd_leaf.hip", "rd_leaf_bd10.hip", "rd_leaf_wide.hip", "rd_leaf_tools.hip"]      # the decision kernel's four builds, each with csrc/rd_leaf_harness.h behind it
 SOURCES = ["cnn_kernel.hip", "fc_kernel.hip", "rd_kernel.hip", "rd_kernel_bd10.hip", "rd_kernel_wide.hip", "rd_kernel_tools.hip", "deblock_kernel.hip", "sao_kernel.hip", "quality_kernel.hip", "entropy_kernel.hip", "hevcdl_api.hip", "hevcdl_bitstream.cpp"]
 
 STATUS = {0: "OK", 1: "INVALID_ARG", 2: "UNSUPPORTED", 3: "NO_DEVICE", 4: "HIP", 5: "OOM"}
@@ -114,11 +116,12 @@ def _includes(path, seen):
     return seen
 
 
-def build_ext(force=False, verbose=False, defines=(), out=None, extra_flags=(), jobs=None):
-    """Compile every HIP source for gfx950 into lib/libhevcdl_hip.so (hipcc cross-compiles without a GPU).  One object per source under build/<variant>/,
-    recompiled only when the source or a header it includes is newer, the stale ones in parallel (the decision kernel is three translation units of ~80 s each)."""
+def build_ext(force=False, verbose=False, defines=(), out=None, extra_flags=(), jobs=None, sources=None):
+    """Compile every HIP source (or `sources`, names under csrc/) for gfx950 into lib/libhevcdl_hip.so (hipcc cross-compiles without a GPU).  One object per source
+    under build/<variant>/, recompiled only when the source or a header it includes is newer, the stale ones in parallel (the decision kernel is four translation
+    units of ~80 s each)."""
     from concurrent.futures import ThreadPoolExecutor
-    srcs = [os.path.join(PKG_DIR, "csrc", s) for s in SOURCES]
+    srcs = [os.path.join(PKG_DIR, "csrc", s) for s in (sources or SOURCES)]
     out = out or os.path.join(PKG_DIR, "lib", "libhevcdl_hip.so")
     os.makedirs(os.path.dirname(out), exist_ok=True)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -158,6 +161,11 @@ def build_ext(force=False, verbose=False, defines=(), out=None, extra_flags=(), 
     with open(out + ".flags", "w") as f:       # which flag set built `out` (the fast path above must not take a library of other -D's for this one)
         f.write(variant)
     return out
+
+
+def build_leaf_lib(out=None):
+    """lib/libhevcdl_hip_leaf.so: the decision kernel's four builds with the leaf harness csrc/rd_leaf_harness.h behind each (-DHEVCDL_LEAF_TEST; test infrastructure)."""
+    return build_ext(defines=("HEVCDL_LEAF_TEST",), out=out or LEAF_LIB_PATH, sources=LEAF_SOURCES)
 
 
 APP_PATH = os.path.join(PKG_DIR, "bin", "TAppEncoderHevcdl")

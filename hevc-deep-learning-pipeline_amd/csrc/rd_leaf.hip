@@ -1,0 +1,3 @@
+// Leaf-test build of rd_kernel.hip (lib/libhevcdl_hip_leaf.so, -DHEVCDL_LEAF_TEST; test infrastructure): the kernel's translation unit with the leaf harness behind it.
+#include "rd_kernel.hip"
+#include "rd_leaf_harness.h"

@@ -431,12 +431,13 @@ static uint32_t sse(const pel *a, int as, const pel *b, int bs, int n)
 /* =====================================================================================
  * transforms (TComTrQuant.cpp:388-987, 2011-2117)
  * ===================================================================================== */
+static int32_t g_fwd_tmp[32 * 32];               /* fwd_transform's first-stage intermediate [frequency][row] of its last call (read by hm_oracle_tu_leaf) */
 static void fwd_transform(const pel *resi, int rs, int32_t *coef, int n, int use_dst)
 {
   const int log2n = (n == 4) ? 2 : (n == 8) ? 3 : (n == 16) ? 4 : 5;
   const int s1 = log2n + g_bd - 9, s2 = log2n + 6;
   const int a1 = s1 > 0 ? 1 << (s1 - 1) : 0, a2 = 1 << (s2 - 1);
-  static int32_t tmp[32 * 32];
+  int32_t *tmp = g_fwd_tmp;
   for (int j = 0; j < n; j++)
     for (int k = 0; k < n; k++) {
       int32_t acc = 0;
@@ -468,6 +469,16 @@ static void inv_transform(const int32_t *coef, pel *resi, int rs, int n, int use
       for (int k = 0; k < n; k++) acc += (use_dst ? g_dst4[k][x] : g_dct[log2n - 2][k][x]) * tmp[k * n + j];
       resi[j * rs + x] = (pel)clip16((acc + (1 << (s2 - 1))) >> s2);
     }
+}
+
+/* transform skip (xTransformSkip / xITransformSkip TComTrQuant.cpp:1919-2009, 4x4 only): the transform's scaling alone, shift 15 - bitDepth - 2 */
+static void tskip_scale(const pel *resi, int rs, int32_t *coef, int n)
+{
+  for (int j = 0; j < n; j++) for (int i = 0; i < n; i++) coef[j * n + i] = (int32_t)resi[j * rs + i] << (13 - g_bd);
+}
+static void tskip_unscale(const int32_t *coef, pel *resi, int rs, int n)
+{
+  for (int j = 0; j < n; j++) for (int i = 0; i < n; i++) resi[j * rs + i] = (pel)((coef[j * n + i] + (1 << (12 - g_bd))) >> (13 - g_bd));
 }
 
 /* =====================================================================================
@@ -1162,7 +1173,7 @@ static void code_tu_block(enc_t *e, const cu_t *cu, const tu_t *tu, int comp, in
   /* transform + RDOQ (transformNxN TComTrQuant.cpp:1450-1534) */
   int32_t *coef = e->coef_l[5 - tu->log2][comp] + (comp ? (zabs * 16) >> 2 : zabs * 16);
   static int32_t tc[1024];
-  if (tskip) { for (int j = 0; j < n; j++) for (int i = 0; i < n; i++) tc[j * n + i] = (int32_t)resi[j * s + i] << (13 - g_bd); }   /* transform shift 15 - bitDepth - 2 */
+  if (tskip) tskip_scale(resi, s, tc, n);
   else fwd_transform(resi, s, tc, n, !comp && n == 4);
   const int cbf_ctx = comp ? tu->trd : (tu->trd == 0 ? 1 : 0);
   if (g_stage) { fprintf(g_stage, "F %d %d\n", n, comp); stage_block_pel(resi, s, n); stage_block32(tc, n); }      /* TComTrQuant.cpp:1496-1516 */
@@ -1173,7 +1184,7 @@ static void code_tu_block(enc_t *e, const cu_t *cu, const tu_t *tu, int comp, in
     if (g_stage) { fprintf(g_stage, "I %d %d\n", n, comp); stage_block32(coef, n); }                                 /* :1603-1606 */
     dequant(e, comp, n, coef, tc);
     if (g_stage) stage_block32(tc, n);                                                                               /* :1610-1613 */
-    if (tskip) { for (int j = 0; j < n; j++) for (int i = 0; i < n; i++) resi[j * s + i] = (pel)((tc[j * n + i] + (1 << (12 - g_bd))) >> (13 - g_bd)); }
+    if (tskip) tskip_unscale(tc, resi, s, n);
     else inv_transform(tc, resi, s, n, !comp && n == 4);
     if (g_stage) stage_block_pel(resi, s, n);                                                                        /* :1658-1662 */
   } else {
@@ -1626,6 +1637,27 @@ static void compress_ctu(enc_t *e, cabac_t *truec, int last_ctu)
   e->est_bits += get_bits(truec);
 }
 
+/* What a run fixes before the first CTU, for the frame path and for the leaf entries alike: the sample bit depth and tool switches (globals), the tables, the QPs
+ * and the lambda family of the slice.  qp in 0..51, bit_depth 8 or 10 (checked by the callers). */
+static void enc_setup(enc_t *e, int qp, int bit_depth, unsigned tools)
+{
+  g_bd = bit_depth; g_tools = tools;
+  init_tables();
+  e->qp = qp;
+  /* lambda: TEncSlice.cpp:433-527 (all-intra GOP 1) and setUpLambda :112-140 */
+  e->lambda = 0.57 * 1.0 * pow(2.0, (qp - 12) / 3.0);
+  e->sqrt_lambda = sqrt(e->lambda);
+  e->qp_c = g_chroma_scale_420[qp < 0 ? 0 : (qp > 57 ? 57 : qp)];
+  e->cweight = pow(2.0, (qp - e->qp_c) / 3.0);
+  e->lambda_c = e->lambda / e->cweight;
+  for (int ch = 0; ch < 2; ch++) for (int l = 0; l < 4; l++) {
+    int tshift = 15 - g_bd - (l + 2), rem = (ch ? e->qp_c : qp) % 6;      /* (qp + 6k) % 6 == qp % 6 */
+    double s = (double)(1 << 15);
+    s = s * pow(2.0, -2.0 * tshift);
+    e->err_scale[ch][l] = s / g_quant_scales[rem] / g_quant_scales[rem] / (1 << DIST_ADJ(2 * (g_bd - 8)));
+  }
+}
+
 int hm_oracle_encode_frames(const uint8_t *yuv, int width, int height, int n_frames, int qp,
                             const uint8_t *labels, hm_ctu_record *out_recs, uint8_t *recon,
                             hm_frame_stats *stats)
@@ -1659,27 +1691,14 @@ int hm_oracle_encode_frames_tb(const void *yuv_, int width, int height, int n_fr
   const uint8_t *yuv = (const uint8_t *)yuv_; uint8_t *recon = (uint8_t *)recon_;
   const int wide = bit_depth > 8;                /* samples are uint16 (little endian) */
   if (bit_depth != 8 && bit_depth != 10) return -1;
-  g_bd = bit_depth;
   if (tile_cols < 1 || tile_rows < 1 || tile_cols > (width + 63) >> 6 || tile_rows > (height + 63) >> 6) return -1;
   if (width <= 0 || height <= 0 || (width & 7) || (height & 7) || qp < 0 || qp > 51) return -1;
-  init_tables();
   enc_t *e = (enc_t *)calloc(1, sizeof *e);
   if (!e) return -2;
-  e->W = width; e->H = height; e->cw = width >> 1; e->qp = qp;
+  enc_setup(e, qp, bit_depth, g_tools);
+  e->W = width; e->H = height; e->cw = width >> 1;
   e->ctus_x = (width + 63) >> 6; e->ctus_y = (height + 63) >> 6;
   const int nctu = e->ctus_x * e->ctus_y;
-  /* lambda: TEncSlice.cpp:433-527 (all-intra GOP 1) and setUpLambda :112-140 */
-  e->lambda = 0.57 * 1.0 * pow(2.0, (qp - 12) / 3.0);
-  e->sqrt_lambda = sqrt(e->lambda);
-  e->qp_c = g_chroma_scale_420[qp < 0 ? 0 : (qp > 57 ? 57 : qp)];
-  e->cweight = pow(2.0, (qp - e->qp_c) / 3.0);
-  e->lambda_c = e->lambda / e->cweight;
-  for (int ch = 0; ch < 2; ch++) for (int l = 0; l < 4; l++) {
-    int tshift = 15 - g_bd - (l + 2), rem = (ch ? e->qp_c : qp) % 6;      /* (qp + 6k) % 6 == qp % 6 */
-    double s = (double)(1 << 15);
-    s = s * pow(2.0, -2.0 * tshift);
-    e->err_scale[ch][l] = s / g_quant_scales[rem] / g_quant_scales[rem] / (1 << DIST_ADJ(2 * (g_bd - 8)));
-  }
   const size_t ysz = (size_t)width * height, csz = ysz >> 2, fsz = ysz + 2 * csz;
   for (int c = 0; c < 3; c++) {
     e->org[c] = (pel *)malloc(sizeof(pel) * (c ? csz : ysz));
@@ -1740,5 +1759,90 @@ int hm_oracle_encode_frames_tb(const void *yuv_, int width, int height, int n_fr
   }
   for (int c = 0; c < 3; c++) { free(e->org[c]); free(e->rec[c]); }
   free(e->recs); free(e);
+  return 0;
+}
+
+/* =====================================================================================
+ * leaf entries (tests/test_rd_leaf*.py): the static functions above on blocks of the caller's, outside any CTU walk
+ * ===================================================================================== */
+int hm_oracle_tu_leaf(int qp, int bit_depth, unsigned tools, int comp, int n, int dir_mode, int tskip, int cbf_ctx, int entry, int n_blocks,
+                      const int32_t *in, const uint8_t *ctx_in, int32_t *coef, int32_t *lvl, uint32_t *abs_sum, uint64_t *frac, uint8_t *ctx_out,
+                      int32_t *deq, int32_t *resi, int32_t *stage1)
+{
+  if ((bit_depth != 8 && bit_depth != 10) || qp < 0 || qp > 51 || comp < 0 || comp > 2) return -1;
+  if ((n != 4 && n != 8 && n != 16 && n != 32) || (comp && n > 16)) return -1;                  /* a chroma TU of 4:2:0 is at most 16 wide (luma TU 32) */
+  if (dir_mode < 0 || dir_mode > 34 || (tskip != 0 && tskip != 1) || (tskip && n != 4)) return -1;
+  if (cbf_ctx < 0 || cbf_ctx > 4 || entry < 0 || entry > 2 || n_blocks < 1) return -1;
+  if (!in || !ctx_in || !coef || !lvl || !abs_sum || !frac || !ctx_out || !deq || !resi) return -1;
+  enc_t *e = (enc_t *)calloc(1, sizeof *e);
+  if (!e) return -2;
+  const int keep_bd = g_bd; const unsigned keep_tools = g_tools;
+  enc_setup(e, qp, bit_depth, tools);
+  const int nn = n * n, use_dst = !comp && n == 4;
+  for (int b = 0; b < n_blocks; b++) {
+    const int32_t *src = in + (size_t)b * nn;
+    int32_t *tc = coef + (size_t)b * nn, *lv = lvl + (size_t)b * nn, *dq = deq + (size_t)b * nn, *rr = resi + (size_t)b * nn;
+    pel blk[32 * 32];
+    cabac_t cab;
+    memcpy(cab.ctx, ctx_in + (size_t)b * 160, NUM_CTX); cab.ctx[NUM_CTX] = 0; cab.frac = 0;
+    memset(tc, 0, sizeof(int32_t) * nn);
+    if (entry == 0) {
+      for (int i = 0; i < nn; i++) blk[i] = (pel)src[i];
+      if (tskip) tskip_scale(blk, n, tc, n);
+      else {
+        fwd_transform(blk, n, tc, n, use_dst);
+        if (stage1) memcpy(stage1 + (size_t)b * nn, g_fwd_tmp, sizeof(int32_t) * nn);
+      }
+    } else if (entry == 1) memcpy(tc, src, sizeof(int32_t) * nn);
+    uint32_t as = 0;
+    if (entry <= 1) {
+      as = rdoq(e, &cab, comp, n, dir_mode, tskip, cbf_ctx, tc, lv);
+      if (as > 0) code_coeff_nxn(&cab, lv, comp, n, dir_mode, tskip);
+      else memset(lv, 0, sizeof(int32_t) * nn);
+    } else {
+      memcpy(lv, src, sizeof(int32_t) * nn);
+      for (int i = 0; i < nn; i++) as += (uint32_t)abs(lv[i]);
+    }
+    abs_sum[b] = as; frac[b] = cab.frac;
+    memcpy(ctx_out + (size_t)b * 160, cab.ctx, 160);
+    if (entry == 2 || as > 0) {
+      dequant(e, comp, n, lv, dq);
+      if (tskip) tskip_unscale(dq, blk, n, n);
+      else inv_transform(dq, blk, n, n, use_dst);
+      for (int i = 0; i < nn; i++) rr[i] = blk[i];
+    } else { memset(dq, 0, sizeof(int32_t) * nn); memset(rr, 0, sizeof(int32_t) * nn); }
+  }
+  g_bd = keep_bd; g_tools = keep_tools;
+  free(e);
+  return 0;
+}
+
+int hm_oracle_pred_leaf(int bit_depth, unsigned tools, int comp, int n, int n_cases, const int16_t *lines, const int16_t *org,
+                        int16_t *fline, int16_t *pred, uint32_t *satd_out)
+{
+  if ((bit_depth != 8 && bit_depth != 10) || comp < 0 || comp > 2 || n_cases < 1 || !lines) return -1;
+  if (n != 4 && n != 8 && n != 16 && n != 32 && !(n == 64 && !comp)) return -1;
+  if (comp && n > 16) return -1;
+  enc_t *e = (enc_t *)calloc(1, sizeof *e);
+  if (!e) return -2;
+  const int keep_bd = g_bd; const unsigned keep_tools = g_tools;
+  enc_setup(e, 32, bit_depth, tools);
+  const int len = 4 * n + 1, nn = n * n;
+  pel *blk = (pel *)malloc(sizeof(pel) * 64 * 64);
+  for (int cs = 0; cs < n_cases; cs++) {
+    const pel *line = lines + (size_t)cs * len;
+    pel fl[4 * 64 + 1];
+    if (!comp) {
+      filter_refs(line, fl, n);
+      if (fline) memcpy(fline + (size_t)cs * len, fl, sizeof(pel) * len);
+    }
+    for (int mode = 0; mode < 35; mode++) {
+      pel *dst = (pred && n <= 32) ? pred + ((size_t)cs * 35 + mode) * nn : blk;
+      predict_intra(comp, mode, use_filtered_refs(comp, mode, n) ? fl : line, n, dst, n);
+      if (!comp && satd_out && org) satd_out[(size_t)cs * 35 + mode] = satd(org + (size_t)cs * nn, n, dst, n, n);
+    }
+  }
+  g_bd = keep_bd; g_tools = keep_tools;
+  free(blk); free(e);
   return 0;
 }

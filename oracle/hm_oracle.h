@@ -69,6 +69,27 @@ int hm_oracle_sao_frame16_tb(const uint16_t *org, const uint16_t *deblocked, int
 void hm_oracle_sao_set_lf_across_tiles(int flag);   /* LFCrossTileBoundaryFlag for the next hm_oracle_sao_* calls (default 1) */
 int hm_oracle_sao_frame_tiles(const uint8_t *org, const uint8_t *deblocked, int width, int height, int qp, hm_sao_blk *params, uint8_t *out, int tile_cols, int tile_rows);
 
+/* Leaf entries (tests/test_rd_leaf.py, tests/test_rd_leaf_gpu.py): the routines of a TU coding and of the intra prediction on blocks of the caller's, the same
+ * static functions the frame path runs.  Both return 0, or -1 for arguments outside what the frame path can reach.
+ *
+ * hm_oracle_tu_leaf: n_blocks blocks of n x n (4..32; chroma up to 16) values, raster, through the chain of code_tu_block from `entry`:
+ *   0 `in` = residual: forward transform (DST for 4x4 luma) or, with tskip (4x4 only), the transform-skip scaling
+ *   1 `in` = coefficients: the quantiser -- rdoq() or plain_quant(), chosen by tools and tskip as code_tu_block does -- from the coder state ctx_in[b][160]
+ *     (context bytes, [159] = 0; fractional bit counter 0), then, when abs_sum > 0, code_coeff_nxn on that state
+ *   2 `in` = levels: dequantiser and inverse transform only (abs_sum = sum of |level|; the coder does not run)
+ * Outputs per block: coef (behind the transform; zeros for entry 2), lvl, abs_sum, frac and ctx_out (the coder behind code_coeff_nxn, or as it came in), deq
+ * (dequantised), resi (reconstructed residual); with abs_sum == 0 (entries 0, 1) lvl, deq and resi are zeros, as code_tu_block leaves them.
+ * stage1 (may be NULL; entry 0 without tskip): the forward transform's first-stage intermediate [frequency][row]. */
+int hm_oracle_tu_leaf(int qp, int bit_depth, unsigned tools, int comp, int n, int dir_mode, int tskip, int cbf_ctx, int entry, int n_blocks,
+                      const int32_t *in, const uint8_t *ctx_in, int32_t *coef, int32_t *lvl, uint32_t *abs_sum, uint64_t *frac, uint8_t *ctx_out,
+                      int32_t *deq, int32_t *resi, int32_t *stage1);
+/* hm_oracle_pred_leaf: n_cases reference lines of 4n+1 samples (bottom-left ... corner ... top-right) and, for luma, original blocks of n x n.
+ * Luma n 4..64, chroma 4..16.  fline (luma): filter_refs of the line (strong smoothing at n >= 32 under tool bit 0x20); pred [case][35][n * n] (n <= 32):
+ * predict_intra of every mode from the line use_filtered_refs selects; satd [case][35] (luma): the rough mode decision's SATD against the original block
+ * (Hadamard 8x8, 4x4 for a 4x4 block, with the distortion shift of bit_depth 10).  fline / pred / satd may be NULL. */
+int hm_oracle_pred_leaf(int bit_depth, unsigned tools, int comp, int n, int n_cases, const int16_t *lines, const int16_t *org,
+                        int16_t *fline, int16_t *pred, uint32_t *satd_out);
+
 /* Debug: if non-NULL, every RD cost evaluation appends (bits, dist) to this FILE (text). */
 void hm_oracle_set_trace(const char *path);
 

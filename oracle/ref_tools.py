@@ -446,3 +446,49 @@ def run_oracle_stage_trace(yuv, width, height, qp, labels):
     finally:
         lib.hm_oracle_set_stage_trace(None)
         os.remove(path)
+
+
+# ---- leaf entries of the oracle (tests/test_rd_leaf.py, tests/test_rd_leaf_gpu.py; case lists: oracle/leaf_cases.py) ------------------------------------
+def oracle_tu_leaf(qp, bit_depth, tools, comp, n, dir_mode, tskip, cbf_ctx, entry, blocks, ctx, want_stage1=False):
+    """hm_oracle_tu_leaf on blocks int32 [count][n * n] with context bytes uint8 [count][160] -> dict of coef, lvl, deq, resi (int32 [count][n * n]), abs_sum (uint32),
+    frac (uint64), ctx (uint8 [count][160]) and, on request, stage1 (the forward transform's first-stage intermediate, [frequency][row])."""
+    lib = oracle_lib()
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    lib.hm_oracle_tu_leaf.restype = ci
+    lib.hm_oracle_tu_leaf.argtypes = [ci, ci, ctypes.c_uint, ci, ci, ci, ci, ci, ci, ci] + [vp] * 10
+    blocks = np.ascontiguousarray(blocks, np.int32).reshape(-1, n * n)
+    ctx = np.ascontiguousarray(ctx, np.uint8).reshape(-1, 160)
+    nb = blocks.shape[0]
+    assert ctx.shape[0] == nb
+    out = {k: np.zeros((nb, n * n), np.int32) for k in ("coef", "lvl", "deq", "resi")}
+    out.update(abs_sum=np.zeros(nb, np.uint32), frac=np.zeros(nb, np.uint64), ctx=np.zeros((nb, 160), np.uint8))
+    if want_stage1:
+        out["stage1"] = np.zeros((nb, n * n), np.int32)
+    rc = lib.hm_oracle_tu_leaf(qp, bit_depth, tools, comp, n, dir_mode, tskip, cbf_ctx, entry, nb, blocks.ctypes.data, ctx.ctypes.data, out["coef"].ctypes.data,
+                               out["lvl"].ctypes.data, out["abs_sum"].ctypes.data, out["frac"].ctypes.data, out["ctx"].ctypes.data, out["deq"].ctypes.data,
+                               out["resi"].ctypes.data, out["stage1"].ctypes.data if want_stage1 else None)
+    if rc != 0:
+        raise RuntimeError("hm_oracle_tu_leaf failed rc=%d" % rc)
+    return out
+
+
+def oracle_pred_leaf(bit_depth, tools, comp, n, lines, org=None):
+    """hm_oracle_pred_leaf on lines int16 [count][4 n + 1] (and original blocks uint16 [count][n * n] for luma) -> dict of fline (luma), pred ([count][35][n * n],
+    n <= 32), satd ([count][35], luma)."""
+    lib = oracle_lib()
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    lib.hm_oracle_pred_leaf.restype = ci
+    lib.hm_oracle_pred_leaf.argtypes = [ci, ctypes.c_uint, ci, ci, ci] + [vp] * 5
+    lines = np.ascontiguousarray(lines, np.int16).reshape(-1, 4 * n + 1)
+    nc = lines.shape[0]
+    out = {}
+    if not comp:
+        org = np.ascontiguousarray(org, np.int16).reshape(nc, n * n)
+        out["fline"], out["satd"] = np.zeros((nc, 4 * n + 1), np.int16), np.zeros((nc, 35), np.uint32)
+    if n <= 32:
+        out["pred"] = np.zeros((nc, 35, n * n), np.int16)
+    rc = lib.hm_oracle_pred_leaf(bit_depth, tools, comp, n, nc, lines.ctypes.data, None if comp else org.ctypes.data, out["fline"].ctypes.data if not comp else None,
+                                 out["pred"].ctypes.data if n <= 32 else None, out["satd"].ctypes.data if not comp else None)
+    if rc != 0:
+        raise RuntimeError("hm_oracle_pred_leaf failed rc=%d" % rc)
+    return out
