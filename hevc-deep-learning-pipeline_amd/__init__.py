@@ -23,7 +23,7 @@ LEAF_LIB_PATH = os.path.join(PKG_DIR, "lib", "libhevcdl_hip_leaf.so")        # -
 WEIGHTS_PATH = os.path.join(PKG_DIR, "weights", "hevc_encoder_model.f32")
 WEIGHT_FLOATS = 637712
 LEAF_SOURCES = ["rd_leaf.hip", "rd_leaf_bd10.hip", "rd_leaf_wide.hip", "rd_leaf_tools.hip"]      # the decision kernel's four builds, each with csrc/rd_leaf_harness.h behind it
-SOURCES = ["cnn_kernel.hip", "fc_kernel.hip", "rd_kernel.hip", "rd_kernel_bd10.hip", "rd_kernel_wide.hip", "rd_kernel_tools.hip", "deblock_kernel.hip", "sao_kernel.hip", "quality_kernel.hip", "entropy_kernel.hip", "hevcdl_api.hip", "hevcdl_bitstream.cpp"]
+SOURCES = ["cnn_kernel.hip", "fc_kernel.hip", "rd_kernel.hip", "rd_kernel_bd10.hip", "rd_kernel_wide.hip", "rd_kernel_tools.hip", "deblock_kernel.hip", "sao_kernel.hip", "quality_kernel.hip", "report_kernel.hip", "entropy_kernel.hip", "hevcdl_api.hip", "hevcdl_bitstream.cpp"]
 
 STATUS = {0: "OK", 1: "INVALID_ARG", 2: "UNSUPPORTED", 3: "NO_DEVICE", 4: "HIP", 5: "OOM"}
 
@@ -36,7 +36,8 @@ STATS_DTYPE = np.dtype([("sse", "<u8", 3), ("est_bits", "<u8"), ("ctus", "<u4"),
 SAO_DTYPE = np.dtype([("mode", "<i4"), ("type", "<i4"), ("aux", "<i4"), ("offset", "<i4", 32)])       # hevcdl_sao_offset; a CTU has 3 (Y, Cb, Cr)
 CABAC_DTYPE = np.dtype([("ctx", "u1", 160), ("frac", "<u8")])      # hevcdl_cabac_state
 QUALITY_DTYPE = np.dtype([("sse", "<u8", 3), ("msssim", "<f8", 3)])      # hevcdl_quality
-assert REC_DTYPE.itemsize == 15120 and STATS_DTYPE.itemsize == 40 and CABAC_DTYPE.itemsize == 168
+REPORT_DTYPE = np.dtype([("sse", "<u8", 3), ("digest", "u1", 48), ("method", "<i4"), ("plane_bytes", "<i4")])      # hevcdl_picture_report_t
+assert REC_DTYPE.itemsize == 15120 and STATS_DTYPE.itemsize == 40 and CABAC_DTYPE.itemsize == 168 and REPORT_DTYPE.itemsize == 80
 
 
 class HevcdlError(RuntimeError):
@@ -251,6 +252,16 @@ def load_library():
     lib.hevcdl_get_slice_data.argtypes = [vp, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(u32p), ctypes.POINTER(ci)]
     lib.hevcdl_set_entropy_capacity.argtypes = [vp, ci]
     lib.hevcdl_get_entropy_info.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double)]
+    lib.hevcdl_picture_report.argtypes = [vp, vp, vp, ci, ci, vp]
+    lib.hevcdl_picture_report_dev.argtypes = [vp, vp, vp, ci, ci, vp, vp]
+    lib.hevcdl_enable_picture_report.argtypes = [vp, ci, ci]
+    lib.hevcdl_get_picture_report.argtypes = [vp, ci, ci, vp]
+    lib.hevcdl_plane_hash.argtypes = [ci, vp, ci, ci, ci, ci, vp]
+    lib.hevcdl_plane_hash_host.argtypes = [vp, ci, ci, ci, ci, ci, vp]
+    lib.hevcdl_report_chunk_bytes.argtypes = []
+    lib.hevcdl_get_report_info.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
+    lib.hevcdl_picture_hash.argtypes = [ctypes.POINTER(StreamConfig), vp, ci, vp, ctypes.POINTER(ci)]
+    lib.hevcdl_write_hash_sei.argtypes = [ci, vp, vp, ctypes.c_size_t, szp]
     _lib = lib
     return lib
 
@@ -262,7 +273,9 @@ EXPORTS = ["hevcdl_config_default", "hevcdl_create", "hevcdl_destroy", "hevcdl_l
            "hevcdl_sao_frames", "hevcdl_sao_frames_dev", "hevcdl_stream_config_default", "hevcdl_access_unit_bound", "hevcdl_write_access_unit", "hevcdl_write_picture_hash_sei", "hevcdl_picture_md5", "hevcdl_write_digest_sei", "hevcdl_picture_hash", "hevcdl_write_hash_sei",
            "hevcdl_picture_quality", "hevcdl_picture_quality_dev", "hevcdl_plane_quality", "hevcdl_enable_quality", "hevcdl_get_quality",
            "hevcdl_write_access_unit_from_slice_data", "hevcdl_slice_data_layout", "hevcdl_code_slice_data_host", "hevcdl_code_slice_data",
-           "hevcdl_enable_device_entropy", "hevcdl_get_slice_data", "hevcdl_encode_pictures_stream", "hevcdl_set_entropy_capacity", "hevcdl_get_entropy_info"]
+           "hevcdl_enable_device_entropy", "hevcdl_get_slice_data", "hevcdl_encode_pictures_stream", "hevcdl_set_entropy_capacity", "hevcdl_get_entropy_info",
+           "hevcdl_picture_report", "hevcdl_picture_report_dev", "hevcdl_enable_picture_report", "hevcdl_get_picture_report", "hevcdl_plane_hash", "hevcdl_plane_hash_host",
+           "hevcdl_report_chunk_bytes", "hevcdl_get_report_info"]
 
 
 def picture_hash_sei(width, height, picture, bit_depth=8, method=1):
@@ -319,6 +332,71 @@ def plane_quality(org, pic, bit_depth=8, device=0):
     if st:
         raise HevcdlError(st, "hevcdl_plane_quality")
     return int(sse.value), float(ms.value)
+
+
+HASH_BYTES = {1: 16, 2: 2, 3: 4}      # digest bytes a plane of SEIDecodedPictureHash 1 (MD5), 2 (CRC), 3 (checksum)
+
+
+def _hash_plane(plane, bit_depth):
+    plane = np.ascontiguousarray(plane, np.uint8 if bit_depth == 8 else np.dtype("<u2"))
+    if plane.ndim != 2 or plane.size == 0:
+        raise ValueError("a plane [rows][cols]")
+    return plane
+
+
+def plane_hash_host(plane, bit_depth=8, method=1, chunk_bytes=0):
+    """TEST AND DIAGNOSTIC: the digest (bytes: 16 / 2 / 4 for method 1 MD5 / 2 CRC / 3 checksum) of one plane [rows][cols] of any size by the shared hash source
+    (csrc/picture_hash_core.h) on the CPU; chunk_bytes: the chunk of the CRC / checksum partials (0: the default).  No GPU needed."""
+    lib = load_library()
+    plane = _hash_plane(plane, bit_depth)
+    dg = np.zeros(16, np.uint8)
+    st = lib.hevcdl_plane_hash_host(plane.ctypes.data, plane.shape[1], plane.shape[0], bit_depth, method, int(chunk_bytes), dg.ctypes.data)
+    if st:
+        raise HevcdlError(st, "hevcdl_plane_hash_host")
+    return dg[:HASH_BYTES[method]].tobytes()
+
+
+def plane_hash(plane, bit_depth=8, method=1, device=0):
+    """TEST AND DIAGNOSTIC: the same digest by the device kernels (csrc/report_kernel.hip)."""
+    lib = load_library()
+    plane = _hash_plane(plane, bit_depth)
+    dg = np.zeros(16, np.uint8)
+    st = lib.hevcdl_plane_hash(device, plane.ctypes.data, plane.shape[1], plane.shape[0], bit_depth, method, dg.ctypes.data)
+    if st:
+        raise HevcdlError(st, "hevcdl_plane_hash")
+    return dg[:HASH_BYTES[method]].tobytes()
+
+
+def picture_hash(width, height, picture, bit_depth=8, method=1):
+    """The host's digests of one picture (hevcdl_picture_hash) -> bytes, 3 x (16 / 2 / 4)."""
+    lib = load_library()
+    cfg = stream_config(width, height, 32, bit_depth=bit_depth)
+    pic = np.ascontiguousarray(picture, np.uint8 if bit_depth == 8 else np.dtype("<u2")).reshape(-1)
+    if pic.size != width * height * 3 // 2:
+        raise ValueError("picture must hold width * height * 3 / 2 samples")
+    dg, pb = np.zeros(48, np.uint8), ctypes.c_int(0)
+    st = lib.hevcdl_picture_hash(ctypes.byref(cfg), pic.ctypes.data, method, dg.ctypes.data, ctypes.byref(pb))
+    if st:
+        raise HevcdlError(st, "hevcdl_picture_hash")
+    return dg[:3 * pb.value].tobytes()
+
+
+def hash_sei(method, digest):
+    """The suffix SEI NAL of digests that exist already (hevcdl_write_hash_sei: 3 x 16 / 2 / 4 bytes for method 1 / 2 / 3) -> bytes."""
+    lib = load_library()
+    dg = np.zeros(48, np.uint8)
+    d = np.frombuffer(bytes(digest), np.uint8)
+    dg[:d.size] = d
+    buf, n = np.zeros(128, np.uint8), ctypes.c_size_t(0)
+    st = lib.hevcdl_write_hash_sei(int(method), dg.ctypes.data, buf.ctypes.data, 128, ctypes.byref(n))
+    if st:
+        raise HevcdlError(st, "hevcdl_write_hash_sei")
+    return buf[:n.value].tobytes()
+
+
+def report_digest(rec):
+    """The digest bytes of one REPORT_DTYPE record: 3 x plane_bytes."""
+    return rec["digest"][:3 * int(rec["plane_bytes"])].tobytes()
 
 
 EXEC_NO_UNIT_HANDOVER, EXEC_RD_WIDE, EXEC_RD_NARROW = 1, 2, 4      # HEVCDL_EXEC_* (hevcdl_config.exec_flags)
@@ -690,6 +768,38 @@ class Encoder:
         self._check(self.lib.hevcdl_get_quality(self._h, int(first), int(count), out.ctypes.data))
         return out
 
+    # ---- picture report: SSE of the output picture and the digests of SEIDecodedPictureHash, on the device ----
+    def picture_report(self, org, pic, method=1):
+        """originals (or None: sse stays 0) + pictures [n, samples] -> [n] REPORT_DTYPE (hevcdl_picture_report)."""
+        pic, n = self._frames(pic)
+        org_ptr = None
+        if org is not None:
+            org, m = self._frames(org)
+            if n != m:
+                raise ValueError("as many pictures as originals")
+            org_ptr = org.ctypes.data
+        out = np.zeros(n, REPORT_DTYPE)
+        self._check(self.lib.hevcdl_picture_report(self._h, org_ptr, pic.ctypes.data, n, int(method), out.ctypes.data))
+        return out
+
+    def picture_report_dev(self, d_org, d_pic, n, method, d_out, stream=None):
+        self._check(self.lib.hevcdl_picture_report_dev(self._h, d_org, d_pic, n, int(method), d_out, stream))
+
+    def enable_picture_report(self, on=True, method=0):
+        """The picture pipeline (encode_pictures*) also reports on its output pictures (SSE against the original, plane digests of `method`); read with get_picture_report."""
+        self._check(self.lib.hevcdl_enable_picture_report(self._h, int(bool(on)), int(method) if on else 0))
+
+    def get_picture_report(self, first, count):
+        out = np.zeros(count, REPORT_DTYPE)
+        self._check(self.lib.hevcdl_get_picture_report(self._h, int(first), int(count), out.ctypes.data))
+        return out
+
+    def report_info(self):
+        """HIP-event ms of the last report launches [SSE, partial or MD5, finish] -- zeros without profile_enable."""
+        ms = (ctypes.c_double * 3)()
+        self._check(self.lib.hevcdl_get_report_info(self._h, ms))
+        return list(ms)
+
     # ---- slice data coded on the device (hevcdl_enable_device_entropy) ----
     def enable_device_entropy(self, on=True):
         """encode_pictures* also code the slice data of their pictures on the device; read it with get_slice_data or take it from encode_pictures_stream."""
@@ -714,8 +824,9 @@ class Encoder:
         ends = np.cumsum(sz.sum(axis=1))
         return [blob[int(e - t):int(e)] for e, t in zip(ends, sz.sum(axis=1))], sz
 
-    def encode_pictures_stream(self, yuv, labels=None, deblock=True, sao=True, want_pictures=False, want_records=False, chunk_frames=0):
-        """hevcdl_encode_pictures_stream: a list of (first, slice data per picture [count] bytes, sizes [count, n], stats [count], pictures or None, records or None), one per chunk."""
+    def encode_pictures_stream(self, yuv, labels=None, deblock=True, sao=True, want_pictures=False, want_records=False, chunk_frames=0, on_chunk_hook=None):
+        """hevcdl_encode_pictures_stream: a list of (first, slice data per picture [count] bytes, sizes [count, n], stats [count], pictures or None, records or None), one per chunk.
+        on_chunk_hook(first, count): called inside the library's callback (get_picture_report is valid there)."""
         yuv, n = self._frames(yuv)
         lab_ptr = None
         if labels is not None:
@@ -734,10 +845,20 @@ class Encoder:
             ends = np.cumsum(per)
             chunks.append((first, [blob[int(e - t):int(e)] for e, t in zip(ends, per)], sz, view(stats, STATS_DTYPE, (count,)),
                            view(pics, yuv.dtype, (count, yuv.shape[1])) if pics else None, view(recs, REC_DTYPE, (count, self.ctus)) if recs else None))
+            if on_chunk_hook is not None:
+                try:
+                    on_chunk_hook(first, count)
+                except BaseException as exc:      # an exception cannot cross the C frames: stop the call and raise it afterwards
+                    hook_error.append(exc)
+                    return 1
             return 0
         cb = fn_t(on_chunk)
+        hook_error = []
         self.lib.hevcdl_encode_pictures_stream.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, fn_t, ctypes.c_void_p]
-        self._check(self.lib.hevcdl_encode_pictures_stream(self._h, yuv.ctypes.data, n, lab_ptr, int(bool(deblock)), int(bool(sao)), int(bool(want_pictures)), int(bool(want_records)), int(chunk_frames), cb, None))
+        st = self.lib.hevcdl_encode_pictures_stream(self._h, yuv.ctypes.data, n, lab_ptr, int(bool(deblock)), int(bool(sao)), int(bool(want_pictures)), int(bool(want_records)), int(chunk_frames), cb, None)
+        if hook_error:
+            raise hook_error[0]
+        self._check(st)
         return chunks
 
     def profile_enable(self, on=True):

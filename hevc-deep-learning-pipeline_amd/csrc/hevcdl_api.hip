@@ -9,6 +9,7 @@
 #include "hevcdl.h"
 #include "hevcdl_dev.h"
 #include "entropy_coder.h"
+#include "picture_hash_core.h"
 
 extern "C" __global__ void hevcdl_cnn_ctu_kernel(hevcdl_cnn_params p);
 extern "C" __global__ void hevcdl_fc_kernel(hevcdl_fc_params p);          // fc_kernel.hip: fully connected head + labels, 16 CTUs per workgroup
@@ -77,6 +78,12 @@ struct hevcdl_ctx {
   bool quality_on = false;                 // hevcdl_enable_quality: the picture pipeline also measures its output pictures
   unsigned char *d_q_pyr = nullptr, *d_q_partial = nullptr, *d_q_weights = nullptr, *d_q_out = nullptr; int q_group = 0;      // workspace of q_group pictures; d_q_out: [max_frames] hevcdl_quality of the pipeline
   std::vector<hevcdl_quality> h_quality;   // the pipeline's last batch (hevcdl_get_quality)
+  // picture report (report_kernel.hip): the workspace -- records, CRC / checksum partials and the SSE launch's output for max_frames pictures, a few KB a picture -- is
+  // allocated by hevcdl_enable_picture_report(ctx, 1, method), or by the first hevcdl_picture_report* call of a context with the switch off, and freed by (ctx, 0, 0)
+  bool report_on = false; int report_method = 0;
+  unsigned char *d_rp_out = nullptr, *d_rp_sse = nullptr; uint32_t *d_rp_partials = nullptr;
+  std::vector<hevcdl_picture_report_t> h_report;      // the pipeline's last batch (hevcdl_get_picture_report)
+  hipEvent_t rp_ev[4] = { nullptr, nullptr, nullptr, nullptr }; double rp_ms[3] = { 0, 0, 0 };      // with `profile`: HIP-event times of the last report launches (SSE, partial or MD5, finish)
   // slice data on the device (entropy_kernel.hip): everything below is allocated by hevcdl_enable_device_entropy(ctx, 1) and freed by (ctx, 0); a context that never
   // turns the switch on allocates and launches none of it
   bool entropy_on = false;
@@ -350,6 +357,8 @@ extern "C" void hevcdl_destroy(hevcdl_ctx *ctx)
   hipFree(ctx->d_weights); hipFree(ctx->d_scratch); hipFree(ctx->d_yuv); hipFree(ctx->d_labels); hipFree(ctx->d_recon);
   hipFree(ctx->d_wpp); hipFree(ctx->d_records); hipFree(ctx->d_stats); hipFree(ctx->d_logits); hipFree(ctx->d_yuv8); hipFree(ctx->d_a3); hipFree(ctx->d_picture); hipFree(ctx->d_rgb); hipFree(ctx->d_cabac); hipFree(ctx->d_sao_stats); hipFree(ctx->d_sao_recon); hipFree(ctx->d_sao_params); hipFree(ctx->d_sao_cand); hipFree(ctx->d_wide); hipFree(ctx->d_flag); hipFree(ctx->d_sched);
   hipFree(ctx->d_q_pyr); hipFree(ctx->d_q_partial); hipFree(ctx->d_q_weights); hipFree(ctx->d_q_out);
+  hipFree(ctx->d_rp_out); hipFree(ctx->d_rp_sse); hipFree(ctx->d_rp_partials);
+  for (hipEvent_t e : ctx->rp_ev) if (e) hipEventDestroy(e);
   hipFree(ctx->d_ec_tables); hipFree(ctx->d_ec_ws); hipFree(ctx->d_ec_packed); hipFree(ctx->d_ec_sync); hipFree(ctx->d_ec_off); hipFree(ctx->d_ec_cap); hipFree(ctx->d_ec_sizes); hipFree(ctx->d_ec_ovf); hipFree(ctx->d_ec_dst);
   delete ctx;
 }
@@ -1054,6 +1063,156 @@ extern "C" hevcdl_status hevcdl_get_quality(hevcdl_ctx *ctx, int first, int coun
   return HEVCDL_OK;
 }
 
+// ---- picture report: SSE of the output picture and the digests of SEIDecodedPictureHash on the device (report_kernel.hip; the SSE kernel is quality_kernel.hip's) ----
+static void report_plane_params(hevcdl_report_params *p, int n_planes, const int *pw, const int *ph, int sample_bytes)
+{
+  memset(p, 0, sizeof *p);
+  size_t off = 0, max_n = 1;
+  for (int c = 0; c < n_planes; c++) {
+    p->plane_w[c] = pw[c]; p->plane_h[c] = ph[c]; p->plane_off[c] = off;
+    const size_t n = (size_t)pw[c] * ph[c] * sample_bytes;
+    off += n; max_n = std::max(max_n, n);
+  }
+  p->frame_bytes = off; p->n_planes = n_planes; p->sample_bytes = sample_bytes;
+  p->chunk_bytes = HEVCDL_REPORT_CHUNK_BYTES; p->chunk_stride = (int)hevcdl_ph::report_chunks(max_n, HEVCDL_REPORT_CHUNK_BYTES);
+}
+static void report_picture_params(const hevcdl_ctx *ctx, hevcdl_report_params *p)
+{
+  const int w = ctx->cfg.width, h = ctx->cfg.height, pw[3] = { w, w >> 1, w >> 1 }, ph[3] = { h, h >> 1, h >> 1 };
+  report_plane_params(p, 3, pw, ph, ctx->cfg.bit_depth > 8 ? 2 : 1);
+}
+
+static hevcdl_status ensure_report_workspace(hevcdl_ctx *ctx)
+{
+  if (ctx->d_rp_partials) return HEVCDL_OK;
+  hevcdl_report_params p; report_picture_params(ctx, &p);
+  const size_t nf = (size_t)ctx->cfg.max_frames;
+  unsigned char *out = nullptr, *sse = nullptr; uint32_t *part = nullptr;
+  hipError_t e = hipMalloc(&out, sizeof(hevcdl_picture_report_t) * nf);
+  if (e == hipSuccess) e = hipMalloc(&sse, sizeof(hevcdl_quality) * nf);
+  if (e == hipSuccess) e = hipMalloc(&part, sizeof(uint32_t) * 3 * (size_t)p.chunk_stride * nf);
+  if (e != hipSuccess) { hipFree(out); hipFree(sse); hipFree(part); (void)hipGetLastError(); return fail(ctx, e == hipErrorOutOfMemory ? HEVCDL_ERR_OOM : HEVCDL_ERR_HIP, "picture report workspace", e); }
+  ctx->d_rp_out = out; ctx->d_rp_sse = sse; ctx->d_rp_partials = part;
+  return HEVCDL_OK;
+}
+
+extern "C" hevcdl_status hevcdl_picture_report_dev(hevcdl_ctx *ctx, const void *d_org_opt, const void *d_pic, int n_frames, int method, void *d_out, void *stream)
+{
+  hevcdl_status st = check_frames(ctx, n_frames); if (st) return st;
+  if (method < 0 || method > 3) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "picture report: method must be 0 (none), 1 (MD5), 2 (CRC) or 3 (checksum)");
+  if (n_frames == 0) return HEVCDL_OK;
+  if (!d_pic || !d_out || ((uintptr_t)d_out & 7)) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "picture report: null or misaligned device pointer");
+  { // the records must not lie inside the pictures they are computed from
+    const uintptr_t o = (uintptr_t)d_out, oe = o + sizeof(hevcdl_picture_report_t) * (size_t)n_frames, span = ctx->frame_bytes * (size_t)n_frames;
+    const uintptr_t a = (uintptr_t)d_org_opt, b = (uintptr_t)d_pic;
+    if ((d_org_opt && o < a + span && a < oe) || (o < b + span && b < oe)) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "picture report: the output overlaps an input");
+  }
+  hipStream_t s = (hipStream_t)stream;
+  st = ensure_report_workspace(ctx); if (st) return st;
+  if (ctx->profile) for (hipEvent_t &e : ctx->rp_ev) if (!e) HIPCHK(hipEventCreate(&e));
+  HIPCHK(hipMemsetAsync(d_out, 0, sizeof(hevcdl_picture_report_t) * (size_t)n_frames, s));
+  if (ctx->profile) HIPCHK(hipEventRecord(ctx->rp_ev[0], s));
+  if (d_org_opt) { // the exact SSE: quality_kernel.hip's kernel alone, into hevcdl_quality-shaped words the finish kernel copies from
+    hevcdl_quality_params q; quality_picture_params(ctx, &q);
+    q.org = d_org_opt; q.pic = d_pic; q.out = ctx->d_rp_sse; q.n_pics = n_frames; q.out_first = 0;
+    HIPCHK(hipMemsetAsync(ctx->d_rp_sse, 0, sizeof(hevcdl_quality) * (size_t)n_frames, s));
+    hevcdl_launch_quality_sse(&q, s);
+  }
+  hevcdl_report_params p; report_picture_params(ctx, &p);
+  p.pic = d_pic; p.out = d_out; p.partials = ctx->d_rp_partials; p.sse = d_org_opt ? ctx->d_rp_sse : nullptr; p.n_pics = n_frames; p.out_first = 0; p.method = method;
+  hevcdl_launch_report(&p, s, ctx->profile ? (void **)(ctx->rp_ev + 1) : nullptr);
+  HIPCHK(hipGetLastError());
+  if (ctx->profile) { // timing is a diagnostic: the call then waits for its launches
+    HIPCHK(hipEventSynchronize(ctx->rp_ev[3]));
+    for (int i = 0; i < 3; i++) { float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, ctx->rp_ev[i], ctx->rp_ev[i + 1])); ctx->rp_ms[i] = ms; }
+  }
+  return HEVCDL_OK;
+}
+
+extern "C" hevcdl_status hevcdl_picture_report(hevcdl_ctx *ctx, const void *org_opt, const void *pic, int n_frames, int method, hevcdl_picture_report_t *out)
+{
+  hevcdl_status st = check_frames(ctx, n_frames); if (st) return st;
+  if (method < 0 || method > 3) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "picture report: method must be 0 (none), 1 (MD5), 2 (CRC) or 3 (checksum)");
+  if (n_frames == 0) return HEVCDL_OK;
+  if (!pic || !out) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null pointer");
+  st = ensure_staging(ctx); if (st) return st;
+  st = ensure_report_workspace(ctx); if (st) return st;
+  if (org_opt) HIPCHK(hipMemcpy(ctx->d_yuv, org_opt, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(ctx->d_recon, pic, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
+  st = hevcdl_picture_report_dev(ctx, org_opt ? ctx->d_yuv : nullptr, ctx->d_recon, n_frames, method, ctx->d_rp_out, nullptr); if (st) return st;
+  hipError_t e = hipDeviceSynchronize();
+  if (e != hipSuccess) return fail(ctx, HEVCDL_ERR_HIP, "report kernels", e);
+  HIPCHK(hipMemcpy(out, ctx->d_rp_out, sizeof(hevcdl_picture_report_t) * (size_t)n_frames, hipMemcpyDeviceToHost));
+  return HEVCDL_OK;
+}
+
+// One plane of any size (host buffers, no context) through the same kernels: for callers (the tests) whose planes are not a context's 4:2:0 picture.
+extern "C" hevcdl_status hevcdl_plane_hash(int device, const void *plane, int width, int height, int bit_depth, int method, uint8_t *digest16)
+{
+  if (!plane || !digest16 || width < 1 || height < 1 || width > (1 << 20) || height > (1 << 20) || (long long)width * height > (1ll << 28) || method < 1 || method > 3) return HEVCDL_ERR_INVALID_ARG;
+  if (bit_depth < 8 || bit_depth > 16) return HEVCDL_ERR_UNSUPPORTED;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) { (void)hipGetLastError(); return HEVCDL_ERR_NO_DEVICE; }
+  if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return HEVCDL_ERR_HIP; }
+  hevcdl_report_params p; report_plane_params(&p, 1, &width, &height, bit_depth > 8 ? 2 : 1);
+  p.n_pics = 1; p.method = method;
+  unsigned char *d[3] = { nullptr, nullptr, nullptr };
+  const size_t sz[3] = { p.frame_bytes, sizeof(uint32_t) * 3 * (size_t)p.chunk_stride, sizeof(hevcdl_picture_report_t) };
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < 3 && e == hipSuccess; i++) e = hipMalloc(&d[i], sz[i]);
+  hevcdl_picture_report_t r; memset(&r, 0, sizeof r);
+  if (e == hipSuccess) e = hipMemcpy(d[0], plane, p.frame_bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(d[2], 0, sizeof r);
+  if (e == hipSuccess) {
+    p.pic = d[0]; p.partials = (uint32_t *)d[1]; p.out = d[2];
+    hevcdl_launch_report(&p, nullptr, nullptr);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(&r, d[2], sizeof r, hipMemcpyDeviceToHost);
+  }
+  for (int i = 0; i < 3; i++) hipFree(d[i]);
+  if (e != hipSuccess) { (void)hipGetLastError(); return e == hipErrorOutOfMemory ? HEVCDL_ERR_OOM : HEVCDL_ERR_HIP; }
+  memset(digest16, 0, 16); memcpy(digest16, r.digest, (size_t)r.plane_bytes);
+  return HEVCDL_OK;
+}
+
+extern "C" hevcdl_status hevcdl_enable_picture_report(hevcdl_ctx *ctx, int on, int method)
+{
+  if (!ctx) return HEVCDL_ERR_INVALID_ARG;
+  if (on) { // the whole of what the switch costs is reserved here
+    if (method < 0 || method > 3) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_enable_picture_report: method must be 0 (none), 1 (MD5), 2 (CRC) or 3 (checksum)");
+    hevcdl_status st = check_frames(ctx, 0); if (st) return st;
+    st = ensure_report_workspace(ctx); if (st) return st;
+    ctx->report_on = true; ctx->report_method = method;
+    return HEVCDL_OK;
+  }
+  ctx->report_on = false; ctx->report_method = 0; ctx->h_report.clear();
+  { // off: the workspace goes back (a later hevcdl_picture_report* call allocates its own again)
+    hipError_t e = hipSetDevice(ctx->cfg.device); if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return fail(ctx, HEVCDL_ERR_HIP, "hevcdl_enable_picture_report", e);
+    hipFree(ctx->d_rp_out); hipFree(ctx->d_rp_sse); hipFree(ctx->d_rp_partials);
+    ctx->d_rp_out = ctx->d_rp_sse = nullptr; ctx->d_rp_partials = nullptr;
+  }
+  return HEVCDL_OK;
+}
+
+extern "C" hevcdl_status hevcdl_get_picture_report(hevcdl_ctx *ctx, int first, int count, hevcdl_picture_report_t *out)
+{
+  if (!ctx) return HEVCDL_ERR_INVALID_ARG;
+  if (!out || first < 0 || count < 0) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_get_picture_report: bad range");
+  if (!ctx->report_on) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_get_picture_report: hevcdl_enable_picture_report was not called");
+  if ((size_t)first + (size_t)count > ctx->h_report.size()) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_get_picture_report: pictures outside the last batch");
+  if (count) memcpy(out, ctx->h_report.data() + first, sizeof(hevcdl_picture_report_t) * (size_t)count);
+  return HEVCDL_OK;
+}
+
+extern "C" hevcdl_status hevcdl_get_report_info(hevcdl_ctx *ctx, double *kernel_ms)
+{
+  if (!ctx || !kernel_ms) return HEVCDL_ERR_INVALID_ARG;
+  for (int i = 0; i < 3; i++) kernel_ms[i] = ctx->rp_ms[i];
+  return HEVCDL_OK;
+}
+
 // ---- whole picture pipeline for host buffers: the stages of TEncGOP::compressGOP between reading a picture and writing its NAL units, with
 // the picture staying in HBM in between (one upload of the originals, one download of records / final picture / SAO parameters) ----------
 // device side of hevcdl_encode_pictures*: upload, labels, decisions, in-loop filters; the results stay in HBM (*d_final: the output pictures)
@@ -1075,8 +1234,16 @@ static hevcdl_status encode_pictures_device(hevcdl_ctx *ctx, const void *yuv, in
     if (!ctx->d_q_out) HIPCHK(hipMalloc(&ctx->d_q_out, sizeof(hevcdl_quality) * (size_t)ctx->cfg.max_frames));
     st = hevcdl_picture_quality_dev(ctx, ctx->d_yuv, *d_final, n_frames, ctx->d_q_out, nullptr); if (st) return st;
   }
+  ctx->h_report.clear();
+  if (ctx->report_on) { // hevcdl_enable_picture_report: SSE and digests of the output pictures, where they are
+    st = hevcdl_picture_report_dev(ctx, ctx->d_yuv, *d_final, n_frames, ctx->report_method, ctx->d_rp_out, nullptr); if (st) return st;
+  }
   hipError_t e = hipDeviceSynchronize();
   if (e != hipSuccess) return fail(ctx, HEVCDL_ERR_HIP, "picture pipeline", e);
+  if (ctx->report_on) {
+    ctx->h_report.resize(n_frames);
+    HIPCHK(hipMemcpy(ctx->h_report.data(), ctx->d_rp_out, sizeof(hevcdl_picture_report_t) * (size_t)n_frames, hipMemcpyDeviceToHost));
+  }
   if (ctx->quality_on) {
     ctx->h_quality.resize(n_frames);
     HIPCHK(hipMemcpy(ctx->h_quality.data(), ctx->d_q_out, sizeof(hevcdl_quality) * (size_t)n_frames, hipMemcpyDeviceToHost));

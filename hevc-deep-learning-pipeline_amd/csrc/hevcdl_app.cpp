@@ -41,7 +41,7 @@ const Key KEYS[] = {
   { "SourceHeight", "hgt", USED, 0 }, { "FrameRate", "fr", USED, 0 }, { "FrameSkip", "fs", USED, 0 }, { "FramesToBeEncoded", "f", USED, 0 },
   { "QP", "q", USED, 0 },
   // extensions of this front end
-  { "LabelDir", 0, USED, 0 }, { "BatchFrames", 0, USED, 0 }, { "ChunkFrames", 0, USED, 0 }, { "Device", 0, USED, 0 }, { "Devices", 0, USED, 0 }, { "NumDevices", 0, USED, 0 }, { "Weights", 0, USED, 0 }, { "RecordFile", 0, USED, 0 }, { "DeviceEntropy", 0, USED, 0 },
+  { "LabelDir", 0, USED, 0 }, { "BatchFrames", 0, USED, 0 }, { "ChunkFrames", 0, USED, 0 }, { "Device", 0, USED, 0 }, { "Devices", 0, USED, 0 }, { "NumDevices", 0, USED, 0 }, { "Weights", 0, USED, 0 }, { "RecordFile", 0, USED, 0 }, { "DeviceEntropy", 0, USED, 0 }, { "DeviceReport", 0, USED, 0 },
   { "CnnInput", 0, USED, 0 }, { "BnMode", 0, USED, 0 }, { "PrintConfig", 0, USED, 0 }, { "LoopFilterDisable", 0, USED, 0 },
   // keys that define the path: only the implemented value is accepted
   { "InputBitDepth", 0, USED, 0 }, { "InternalBitDepth", 0, USED, 0 }, { "InputChromaFormat", 0, PATH, "420" }, { "Profile", 0, USED, 0 },
@@ -244,6 +244,11 @@ int main(int argc, char **argv)
   // DeviceEntropy 1: the slice data is coded on the device (hevcdl_enable_device_entropy) and the run goes through hevcdl_encode_pictures_stream: records leave HBM only for
   // a record file, pictures only for a reconstruction file, a picture hash or the PSNR of the filtered picture.  Every output is byte for byte that of the run without the key.
   const bool device_entropy = opt.geti("DeviceEntropy", 0) != 0;
+  // DeviceReport 1: the squared errors behind the PSNR columns and the digests of SEIDecodedPictureHash come from the device (hevcdl_enable_picture_report), computed where the
+  // output picture is; a DeviceEntropy run then fetches pictures for a reconstruction file only.  Stream, reconstruction file and log are those of the run without the key.
+  const long device_report_v = opt.geti("DeviceReport", 0);
+  if (device_report_v != 0 && device_report_v != 1) opt.errors.push_back("DeviceReport = " + std::to_string(device_report_v) + " is not a value of the key (0 or 1)");
+  const bool device_report = device_report_v == 1;
   const bool print_msssim = opt.geti("PrintMSSSIM", 0) != 0, print_frame_mse = opt.geti("PrintFrameMSE", 0) != 0, print_seq_mse = opt.geti("PrintSequenceMSE", 0) != 0;
   for (const char *key : { "LoopFilterBetaOffset_div2", "LoopFilterTcOffset_div2" }) {      // the reference's own range check (TAppEncCfg.cpp xConfirmPara: -6 .. 6)
     const long v = opt.geti(key, 0);
@@ -381,6 +386,8 @@ int main(int argc, char **argv)
       if (st == HEVCDL_OK && print_msssim && (st = hevcdl_enable_quality(shards[i].ctx, 1)) != HEVCDL_OK) { hevcdl_destroy(shards[i].ctx); shards[i].ctx = nullptr; }
       // DeviceEntropy: the sub-stream regions and the packed buffer are reserved by the switch as well
       if (st == HEVCDL_OK && device_entropy && (st = hevcdl_enable_device_entropy(shards[i].ctx, 1)) != HEVCDL_OK) { hevcdl_destroy(shards[i].ctx); shards[i].ctx = nullptr; }
+      // DeviceReport: records and partials of a batch (a few KB a picture)
+      if (st == HEVCDL_OK && device_report && (st = hevcdl_enable_picture_report(shards[i].ctx, 1, hash_sei)) != HEVCDL_OK) { hevcdl_destroy(shards[i].ctx); shards[i].ctx = nullptr; }
       if (st == HEVCDL_ERR_OOM && ws_oom) {
         // the workspace is sized by the device's CUs, not by the batch: a smaller batch does not shrink it.  What does: the independent launch form (a block per wave of
         // the context's own frames instead of every CU's workgroup), then the eight-wave build
@@ -469,7 +476,7 @@ int main(int argc, char **argv)
     if (!yuv_mem.data()) { fprintf(stderr, "Error: cannot allocate %zu bytes of page-locked memory for the originals\n", (size_t)frame_bytes * sb); S.rc = 3; fclose(fi); return; }
     std::vector<uint8_t> labels_mem(label_dir.empty() ? 0 : (size_t)ctus * 16 * sb);
     struct ChunkCtx { long f0; double et; const uint8_t *yuv; std::chrono::steady_clock::time_point t0; int nb; } cc = { 0, 0.0, nullptr, now(), 1 };
-    const bool want_pictures = frec || hash_sei || deblock, want_records = frecords != nullptr;      // what a DeviceEntropy run still fetches from HBM
+    const bool want_pictures = device_report ? frec != nullptr : (frec || hash_sei || deblock), want_records = frecords != nullptr;      // what a DeviceEntropy run still fetches from HBM
     // slice_data / slice_sizes / n_sub: the packed sub-streams of the chunk's pictures (DeviceEntropy), or null: the host writer codes the records
     auto on_chunk = [&](int first, int count, const hevcdl_ctu_record *recs, const void *pictures, const hevcdl_sao_blk *sao_params, const hevcdl_frame_stats *stats,
                         const uint8_t *slice_data, const uint32_t *slice_sizes, int n_sub) -> int {
@@ -481,6 +488,8 @@ int main(int argc, char **argv)
       std::vector<PicOut> pics(count);
       std::vector<hevcdl_quality> quality(print_msssim ? count : 0);          // measured by the device call that made the pictures
       if (print_msssim) { const hevcdl_status qst = hevcdl_get_quality(S.ctx, first, count, quality.data()); if (qst != HEVCDL_OK) { fprintf(stderr, "Error: %s (status %d)\n", hevcdl_last_error(S.ctx), (int)qst); S.rc = 3; return 1; } }
+      std::vector<hevcdl_picture_report_t> reports(device_report ? count : 0);      // DeviceReport: squared errors and digests of the chunk's output pictures, made by the device call
+      if (device_report) { const hevcdl_status rst = hevcdl_get_picture_report(S.ctx, first, count, reports.data()); if (rst != HEVCDL_OK) { fprintf(stderr, "Error: %s (status %d)\n", hevcdl_last_error(S.ctx), (int)rst); S.rc = 3; return 1; } }
       {
         std::atomic<int> next(0);
         auto work = [&]() {
@@ -489,7 +498,8 @@ int main(int argc, char **argv)
             if (slice_data && buf.size() < slice_at[(size_t)i + 1] - slice_at[(size_t)i] + 4096) buf.resize(2 * (slice_at[(size_t)i + 1] - slice_at[(size_t)i]) + 4096);
             PicOut &po = pics[i]; po.md5_text[0] = 0;
             for (int c = 0; c < 3; c++) po.sse[c] = stats[i].sse[c];
-            if (deblock && recon) { // the picture statistics follow the filtered picture: recomputed here
+            if (deblock && device_report) { for (int c = 0; c < 3; c++) po.sse[c] = reports[i].sse[c]; }      // of the filtered picture, from the device
+            else if (deblock && recon) { // the picture statistics follow the filtered picture: recomputed here
               const uint8_t *o = cc.yuv + frame_bytes * (size_t)(first + i), *r = recon + frame_bytes * (size_t)i;
               const size_t n[3] = { (size_t)width * height, (size_t)width * height / 4, (size_t)width * height / 4 };
               size_t off = 0;
@@ -512,7 +522,8 @@ int main(int argc, char **argv)
             po.bytes.assign(buf.begin(), buf.begin() + po.au_len);
             if (hash_sei) { // suffix SEI after the slice; not part of the picture's bit count (as in the reference)
               uint8_t sei[128], dg[48]; size_t sei_len = 0; int pb = 16;
-              po.st = hevcdl_picture_hash(&scfg, recon + frame_bytes * (size_t)i, hash_sei, dg, &pb);
+              if (device_report) { memcpy(dg, reports[i].digest, sizeof dg); pb = reports[i].plane_bytes; po.st = pb > 0 && reports[i].method == hash_sei ? HEVCDL_OK : HEVCDL_ERR_INVALID_ARG; }
+              else po.st = hevcdl_picture_hash(&scfg, recon + frame_bytes * (size_t)i, hash_sei, dg, &pb);
               if (po.st == HEVCDL_OK) po.st = hevcdl_write_hash_sei(hash_sei, dg, sei, sizeof sei, &sei_len);
               if (po.st != HEVCDL_OK) continue;
               po.bytes.insert(po.bytes.end(), sei, sei + sei_len);

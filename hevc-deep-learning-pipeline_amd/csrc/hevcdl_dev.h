@@ -161,6 +161,18 @@ struct hevcdl_quality_params {
   double c1, c2;                   // (0.01 max)^2, (0.03 max)^2, max = (1 << bit depth) - 1 (TEncGOP.cpp:2664-2666)
 };
 
+// picture report (report_kernel.hip): the decoded-picture hash of n_pics pictures of up to three planes; the SSE comes from hevcdl_launch_quality_sse
+struct hevcdl_report_params {
+  const void *pic;                 // [picture] planes of sample_bytes-wide samples, plane c at BYTE plane_off[c] of a picture of frame_bytes bytes
+  void *out;                       // hevcdl_picture_report_t[]: picture i of the launch writes entry out_first + i (zeroed by the caller)
+  uint32_t *partials;              // [picture][3][chunk_stride]: CRC / checksum partial of every chunk of chunk_bytes bytes of a plane
+  const void *sse;                 // hevcdl_quality[n_pics] the SSE launch filled (the finish kernel copies sse[] into the records), or NULL: sse stays 0
+  size_t frame_bytes, plane_off[3];
+  int plane_w[3], plane_h[3], n_planes, sample_bytes;
+  int n_pics, out_first, method;   // method: 0 none, 1 MD5, 2 CRC, 3 checksum
+  int chunk_bytes, chunk_stride;   // chunk_bytes: a multiple of 16; chunk_stride >= the chunks of the largest plane
+};
+
 // slice data on the device (entropy_kernel.hip): one wave per sub-stream
 struct hevcdl_entropy_params {
   const unsigned char *records;    // [frame][ctu] hevcdl_ctu_record
@@ -239,6 +251,10 @@ void hevcdl_launch_deblock(const struct hevcdl_dbk_params *p, void *stream);
 int hevcdl_quality_scales(int w, int h);
 void hevcdl_quality_layout(struct hevcdl_quality_params *p);      // fills scales / *_off / pyr_* / part_pic from the planes' sizes
 void hevcdl_launch_quality(const struct hevcdl_quality_params *p, void *stream);
+void hevcdl_launch_quality_sse(const struct hevcdl_quality_params *p, void *stream);      // hevcdl_quality_sse_kernel alone: needs org / pic / out and the plane fields, no pyramid workspace
+// report_kernel.hip: partial (methods 2, 3) or MD5 (method 1) launch, then the finish launch, in order on `stream`.  events_opt: three hipEvent_t recorded in front of the
+// first launch, between the two and behind the second (timing), or NULL
+void hevcdl_launch_report(const struct hevcdl_report_params *p, void *stream, void **events_opt);
 // hevcdl_bitstream.cpp: the packed sub-streams of one picture by the host writer (fallback of the device entropy coder); 0, or -1 when `capacity` is too small
 int hevcdl_host_writer_slice_data(const struct hevcdl_stream_config *cfg, const struct hevcdl_ctu_record *records, const struct hevcdl_sao_blk *sao, uint8_t *out, size_t capacity,
                                   uint32_t *sizes, size_t *total);

@@ -194,12 +194,20 @@ __global__ __launch_bounds__(256) void hevcdl_quality_finish_kernel(hevcdl_quali
   }
 }
 
+// workgroups of the SSE kernel per (picture, plane): 4096 samples each, at most 1024
+int sse_blocks_of(const hevcdl_quality_params &p)
+{
+  int max_n = 0;
+  for (int c = 0; c < p.n_planes; c++) max_n = max_n > p.plane_w[c] * p.plane_h[c] ? max_n : p.plane_w[c] * p.plane_h[c];
+  const int b = (max_n + 256 * 16 - 1) / (256 * 16);
+  return b > 1024 ? 1024 : b;
+}
+
 template <typename PEL> void launch(const hevcdl_quality_params &p, hipStream_t st)
 {
   int max_n = 0, max_scales = 0, n_planes = p.n_planes;
   for (int c = 0; c < n_planes; c++) { max_n = max_n > p.plane_w[c] * p.plane_h[c] ? max_n : p.plane_w[c] * p.plane_h[c]; max_scales = max_scales > p.scales[c] ? max_scales : p.scales[c]; }
-  int sse_blocks = (max_n + 256 * 16 - 1) / (256 * 16); if (sse_blocks > 1024) sse_blocks = 1024;
-  hipLaunchKernelGGL(hevcdl_quality_sse_kernel<PEL>, dim3(sse_blocks, n_planes, p.n_pics), dim3(256), 0, st, p);
+  hipLaunchKernelGGL(hevcdl_quality_sse_kernel<PEL>, dim3(sse_blocks_of(p), n_planes, p.n_pics), dim3(256), 0, st, p);
   for (int s = 1; s < max_scales; s++)
     hipLaunchKernelGGL(hevcdl_quality_pyramid_kernel<PEL>, dim3(((max_n >> (2 * s)) + 255) / 256 + 1, 2 * n_planes, p.n_pics), dim3(256), 0, st, p, s);
   for (int s = 0; s < max_scales; s++) {
@@ -242,4 +250,11 @@ extern "C" void hevcdl_launch_quality(const hevcdl_quality_params *pp, void *str
 {
   if (pp->sample_bytes == 1) launch<uint8_t>(*pp, (hipStream_t)stream);
   else launch<uint16_t>(*pp, (hipStream_t)stream);
+}
+
+// The SSE kernel alone (the picture report, report_kernel.hip): the same launch as the first one of hevcdl_launch_quality; nothing of the pyramid workspace is read.
+extern "C" void hevcdl_launch_quality_sse(const hevcdl_quality_params *pp, void *stream)
+{
+  if (pp->sample_bytes == 1) hipLaunchKernelGGL(hevcdl_quality_sse_kernel<uint8_t>, dim3(sse_blocks_of(*pp), pp->n_planes, pp->n_pics), dim3(256), 0, (hipStream_t)stream, *pp);
+  else hipLaunchKernelGGL(hevcdl_quality_sse_kernel<uint16_t>, dim3(sse_blocks_of(*pp), pp->n_planes, pp->n_pics), dim3(256), 0, (hipStream_t)stream, *pp);
 }

@@ -12,7 +12,7 @@ import time
 
 import numpy as np
 
-from . import Encoder, write_access_unit, picture_hash_sei, stream_config, write_access_unit_from_slice_data
+from . import Encoder, write_access_unit, picture_hash_sei, stream_config, write_access_unit_from_slice_data, hash_sei as digest_sei, report_digest
 from . import metrics, sharding
 
 
@@ -40,14 +40,17 @@ def read_frames(path, width, height, first, count, bit_depth=8):
 
 
 def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None, recon_path=None, frame_skip=0, batch=256, tiles=(1, 1),
-                    lf_across_tiles=True, bit_depth=8, level_idc=186, frame_rate=30.0, hash_sei=False, labels_fn=None, device=None, log=print, tools=0x7f, wavefront=False, device_entropy=False):
+                    lf_across_tiles=True, bit_depth=8, level_idc=186, frame_rate=30.0, hash_sei=False, labels_fn=None, device=None, log=print, tools=0x7f, wavefront=False, device_entropy=False, device_report=False):
     """Encode frames [frame_skip, frame_skip + n_frames) of a planar YUV file.  Works stand-alone and under torch.distributed
     (initialised by the caller): rank r takes a contiguous share of the frames.  Returns, on rank 0, the summary (metrics.Summary)
     and the list of per-picture rows [poc, bits, sseY, sseU, sseV]; other ranks return (None, None).
     labels_fn(first_poc, count) -> uint8 [count, ctus, 16] replaces the on-device CNN (the reference's label files).
     device_entropy: the slice data is coded on the device (Encoder.enable_device_entropy) and the host only writes what surrounds it; the stream is the same bytes.
-    This takes the arithmetic coder off the host threads; it saves no copies here, since this function also needs the pictures (reconstruction file, hash, SSE) and fetches
-    records and SAO parameters with them through encode_pictures.  A caller that needs neither uses Encoder.encode_pictures_stream."""
+    This takes the arithmetic coder off the host threads; alone it saves no copies, since this function then still needs the pictures (hash, SSE) and fetches records and
+    SAO parameters with them through encode_pictures.
+    device_report: the squared errors and the hash SEI's digests come from the device too (Encoder.enable_picture_report), computed where the output picture is.  Together
+    with device_entropy and without a recon_path nothing but slice data, statistics and the 80-byte reports leaves HBM: the batch goes through
+    Encoder.encode_pictures_stream(want_pictures=False).  Stream, reconstruction file and rows are the same either way."""
     import torch
     import torch.distributed as dist
     multi = dist.is_available() and dist.is_initialized()
@@ -67,19 +70,29 @@ def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None
         if device_entropy:
             enc.enable_device_entropy(True)
             scfg = stream_config(width, height, qp, level_idc, True, tiles, bit_depth, lf_across_tiles, tools, wavefront=wavefront)
+        if device_report:
+            enc.enable_picture_report(True, 1 if hash_sei else 0)
+        stream_only = device_report and device_entropy and not recon_path      # no picture, record or SAO parameter is copied to the host
         for b0 in range(mine.start, mine.stop, batch):
             nb = min(batch, mine.stop - b0)
             yuv = read_frames(input_path, width, height, frame_skip + b0, nb, bit_depth)
             t0 = time.time()
             labels = labels_fn(b0, nb) if labels_fn else None
-            recs, final, sao, _ = enc.encode_pictures(yuv, labels)          # CNN -> decisions -> deblocking -> SAO, pictures stay in HBM
+            if stream_only:
+                recs = final = sao = None
+                enc.encode_pictures_stream(yuv, labels, want_pictures=False, want_records=False)
+            else:
+                recs, final, sao, _ = enc.encode_pictures(yuv, labels)          # CNN -> decisions -> deblocking -> SAO, pictures stay in HBM
             et = (time.time() - t0) / nb
             slices, slice_sizes = enc.get_slice_data(0, nb) if device_entropy else (None, None)
+            reports = enc.get_picture_report(0, nb) if device_report else None
             def one_picture(i):          # host work of a picture (arithmetic coder, hash, SSE): independent -> thread pool (ctypes drops the GIL)
                 if device_entropy:
                     au = write_access_unit_from_slice_data(scfg, b0 + i, slices[i], slice_sizes[i])
                 else:
                     au = write_access_unit(width, height, qp, b0 + i, recs[i], level_idc=level_idc, sao=sao[i], tiles=tiles, bit_depth=bit_depth, lf_across_tiles=lf_across_tiles, tools=tools, wavefront=wavefront)
+                if device_report:
+                    return au, digest_sei(1, report_digest(reports[i])) if hash_sei else b"", [int(v) for v in reports[i]["sse"]]
                 sei = picture_hash_sei(width, height, final[i], bit_depth) if hash_sei else b""
                 d = (yuv[i].astype(np.int64) - final[i].astype(np.int64)) ** 2
                 return au, sei, [int(d[:ysz].sum()), int(d[ysz:ysz + ysz // 4].sum()), int(d[ysz + ysz // 4:].sum())]

@@ -282,6 +282,45 @@ hevcdl_status hevcdl_plane_quality(int device, const void *org, const void *pic,
 hevcdl_status hevcdl_enable_quality(hevcdl_ctx *ctx, int on);
 hevcdl_status hevcdl_get_quality(hevcdl_ctx *ctx, int first, int count, hevcdl_quality *out);
 
+/* ---- picture report: what the log line and the hash SEI of a picture are made of, computed on the device (opt-in; csrc/report_kernel.hip) ----------
+ * Replaces, for pictures that are in HBM, the SSD loop of xCalculateAddPSNR (TEncGOP.cpp:2380-2390) and calcMD5 / calcCRC / calcChecksum (TComPicYuvMD5.cpp:88-180;
+ * on the host: hevcdl_picture_hash below).  org / pic: n_frames packed planar 4:2:0 pictures of the context's size and bit depth (uint16 samples at 10 bits).
+ * sse: the output picture against the original, exact; org == NULL leaves it 0.  digest: the plane digests of `method` (SEIDecodedPictureHash: 0 none -- the digest
+ * stays zero --, 1 MD5, 2 CRC, 3 checksum; anything else is HEVCDL_ERR_INVALID_ARG) side by side, plane_bytes each (16 / 2 / 4), exactly as hevcdl_picture_hash leaves
+ * them: they feed hevcdl_write_hash_sei.  Everything is integer arithmetic: the same bits as the host's, for every batch size and position in the batch.
+ * The device variant is asynchronous on `stream`; d_out (8-byte aligned) must not overlap the pictures (HEVCDL_ERR_INVALID_ARG).
+ * Cost at 2160p (profiles/report_time.txt): SSE, CRC and checksum take well under a millisecond a picture at any batch size; an MD5 chain is serial, one lane per plane:
+ * a batch costs about 0.14 s whatever it holds, which beats one host core from 5 pictures and 16 host threads from about 75. */
+typedef struct hevcdl_picture_report {
+  uint64_t sse[3];               /* output picture against the original, per plane; exact */
+  uint8_t  digest[48];           /* plane digests side by side, plane_bytes each (16 / 2 / 4), as hevcdl_picture_hash leaves them */
+  int32_t  method;               /* 0 none, 1 MD5, 2 CRC, 3 checksum */
+  int32_t  plane_bytes;
+} hevcdl_picture_report_t;       /* 80 bytes (C gives a function and a typedef one name space: the type's name carries _t, the struct tag is the plain name) */
+hevcdl_status hevcdl_picture_report(hevcdl_ctx *ctx, const void *org_opt, const void *pic, int n_frames, int method, hevcdl_picture_report_t *out);
+hevcdl_status hevcdl_picture_report_dev(hevcdl_ctx *ctx, const void *d_org_opt, const void *d_pic, int n_frames, int method, void *d_out, void *stream);
+/* The picture pipeline can report on its own output while original and output picture are still in HBM: after hevcdl_enable_picture_report(ctx, 1, method) every
+ * hevcdl_encode_pictures / _chunked / _stream call also computes the report of its output pictures (after the enabled in-loop filters) against the originals, and
+ * hevcdl_get_picture_report returns those of pictures [first, first + count) of the LAST such call -- valid inside the chunk callback and after the call returns.  A
+ * hevcdl_encode_pictures_stream call without want_pictures then yields stream, PSNR and hash SEI while only the slice data leaves HBM.  Off (the default): nothing is
+ * launched or allocated, hevcdl_get_picture_report returns HEVCDL_ERR_INVALID_ARG.  Enabling allocates the whole workspace for the context's max_frames (records, partials
+ * and the SSE words: a few KB a picture) and returns HEVCDL_ERR_OOM when the device refuses; (ctx, 0, 0) synchronises the device and frees it. */
+hevcdl_status hevcdl_enable_picture_report(hevcdl_ctx *ctx, int on, int method);
+hevcdl_status hevcdl_get_picture_report(hevcdl_ctx *ctx, int first, int count, hevcdl_picture_report_t *out);
+/* TEST AND DIAGNOSTIC entry points, not for a hot path.
+ * hevcdl_plane_hash: the digest of ONE plane of any size from 1 x 1 (at most 2^20 samples a side and 2^28 in all: a w x 1 plane reaches any byte length) and any bit depth from 8 to 16 (host buffers; uint16 samples above 8 bits), without a
+ * context, by the same kernels (it allocates and frees its device buffers on every call): a context's planes never have the odd sizes and the tails the kernels' tests need.
+ * digest16 receives 16 / 2 / 4 bytes (method 1 / 2 / 3), the rest is zeroed.
+ * hevcdl_plane_hash_host: the shared source (csrc/picture_hash_core.h) on the CPU, no GPU needed, with an explicit chunk size for the CRC / checksum partials
+ * (chunk_bytes <= 0: the default).
+ * hevcdl_report_chunk_bytes: the default chunk size.
+ * hevcdl_get_report_info: HIP-event times of the last report launches of the context -- kernel_ms[3]: the SSE launch (0 without originals), the partial or MD5 launch, the
+ * finish launch; measured only with hevcdl_profile_enable(ctx, 1) (the call then synchronises), zeros otherwise. */
+hevcdl_status hevcdl_plane_hash(int device, const void *plane, int width, int height, int bit_depth, int method, uint8_t *digest16);
+hevcdl_status hevcdl_plane_hash_host(const void *plane, int width, int height, int bit_depth, int method, int chunk_bytes, uint8_t *digest16);
+int           hevcdl_report_chunk_bytes(void);
+hevcdl_status hevcdl_get_report_info(hevcdl_ctx *ctx, double *kernel_ms);
+
 /* ---- bitstream writer (host side; no GPU needed) ---------------------------------------------------
  * One access unit per picture exactly as the reference emits it for its all-intra configuration: VPS, SPS, PPS
  * (ReWriteParamSetsFlag 1), then one slice NAL (IDR_W_RADL for POC 0, CRA afterwards), Annex B start codes.
