@@ -117,6 +117,12 @@ def _includes(path, seen):
     return seen
 
 
+def compile_flags(defines=(), extra_flags=(), root=ROOT):
+    """The hipcc flags of one object of the library, for the sources of the tree at `root` (tools/same_device_code.py compiles another tree's with them)."""
+    return ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-unused-value", "-mllvm", "-amdgpu-spill-vgpr-to-agpr=0",
+            "-I" + os.path.join(root, "include"), "-I" + os.path.join(root, os.path.basename(PKG_DIR), "csrc")] + ["-D" + d for d in defines] + list(extra_flags)
+
+
 def build_ext(force=False, verbose=False, defines=(), out=None, extra_flags=(), jobs=None, sources=None):
     """Compile every HIP source (or `sources`, names under csrc/) for gfx950 into lib/libhevcdl_hip.so (hipcc cross-compiles without a GPU).  One object per source
     under build/<variant>/, recompiled only when the source or a header it includes is newer, the stale ones in parallel (the decision kernel is four translation
@@ -126,8 +132,7 @@ def build_ext(force=False, verbose=False, defines=(), out=None, extra_flags=(), 
     out = out or os.path.join(PKG_DIR, "lib", "libhevcdl_hip.so")
     os.makedirs(os.path.dirname(out), exist_ok=True)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-unused-value", "-mllvm", "-amdgpu-spill-vgpr-to-agpr=0",
-             "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(PKG_DIR, "csrc")] + ["-D" + d for d in defines] + list(extra_flags)
+    flags = compile_flags(defines, extra_flags)
     import hashlib
     variant = os.path.splitext(os.path.basename(out))[0] + "-" + hashlib.sha1(" ".join(flags).encode()).hexdigest()[:10]
     odir = os.path.join(PKG_DIR, "build", variant)

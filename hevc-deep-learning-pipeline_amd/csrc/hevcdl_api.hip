@@ -2,7 +2,6 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
 #include <algorithm>
 #include <vector>
@@ -13,11 +12,11 @@
 
 extern "C" __global__ void hevcdl_cnn_ctu_kernel(hevcdl_cnn_params p);
 extern "C" __global__ void hevcdl_fc_kernel(hevcdl_fc_params p);          // fc_kernel.hip: fully connected head + labels, 16 CTUs per workgroup
-extern "C" __global__ void hevcdl_rd_frame_kernel(hevcdl_rd_params p);
+extern "C" __global__ void hevcdl_rd_frame_kernel(hevcdl_rd_params p);            // (its hevcdl_rd_smem_bytes / _scratch_bytes / _waves_per_group: hevcdl_dev.h)
 extern "C" __global__ void hevcdl_rd_frame_kernel_bd10(hevcdl_rd_params p);       // rd_kernel_bd10.hip: the same kernel for uint16 samples
 extern "C" size_t hevcdl_rd_smem_bytes_bd10(void);
 extern "C" size_t hevcdl_rd_scratch_bytes_bd10(void);
-extern "C" int hevcdl_rd_waves_per_group(void);
+extern "C" int hevcdl_rd_waves_per_group_bd10(void);
 extern "C" __global__ void hevcdl_rd_frame_kernel_wide(hevcdl_rd_params p);       // rd_kernel_wide.hip: the 8-bit kernel with more wavefronts per workgroup
 extern "C" size_t hevcdl_rd_smem_bytes_wide(void);
 extern "C" size_t hevcdl_rd_scratch_bytes_wide(void);
@@ -25,6 +24,17 @@ extern "C" int hevcdl_rd_waves_per_group_wide(void);
 extern "C" __global__ void hevcdl_rd_frame_kernel_tools(hevcdl_rd_params p);      // rd_kernel_tools.hip: the 8-bit kernel with the cfg's tool switches read at run time
 extern "C" size_t hevcdl_rd_smem_bytes_tools(void);
 extern "C" size_t hevcdl_rd_scratch_bytes_tools(void);
+extern "C" int hevcdl_rd_waves_per_group_tools(void);
+
+// The decision kernel's four builds.  Whatever depends on which of them a launch runs is read from its row (rd_build_of picks the row).
+struct RdBuild { const char *name; const void *kernel; size_t (*smem_bytes)(void); size_t (*scratch_bytes)(void); int (*waves_per_group)(void); };      // name: as hevcdl_last_rd_launch reports it; scratch_bytes: per wave
+enum { RD_NARROW, RD_WIDE, RD_TOOLS, RD_BD10, RD_BUILDS };
+static const RdBuild rd_builds[RD_BUILDS] = {
+  { "hevcdl_rd_frame_kernel", (const void *)hevcdl_rd_frame_kernel, hevcdl_rd_smem_bytes, hevcdl_rd_scratch_bytes, hevcdl_rd_waves_per_group },
+  { "hevcdl_rd_frame_kernel_wide", (const void *)hevcdl_rd_frame_kernel_wide, hevcdl_rd_smem_bytes_wide, hevcdl_rd_scratch_bytes_wide, hevcdl_rd_waves_per_group_wide },
+  { "hevcdl_rd_frame_kernel_tools", (const void *)hevcdl_rd_frame_kernel_tools, hevcdl_rd_smem_bytes_tools, hevcdl_rd_scratch_bytes_tools, hevcdl_rd_waves_per_group_tools },
+  { "hevcdl_rd_frame_kernel_bd10", (const void *)hevcdl_rd_frame_kernel_bd10, hevcdl_rd_smem_bytes_bd10, hevcdl_rd_scratch_bytes_bd10, hevcdl_rd_waves_per_group_bd10 },
+};
 
 // 10-bit samples -> the 8-bit planes the CNN stage reads (the reference's label producer works on 8-bit frames: gen_frames.py)
 __global__ void hevcdl_narrow_samples_kernel(const uint16_t *src, uint8_t *dst, size_t n, int shift)
@@ -323,7 +333,8 @@ extern "C" hevcdl_status hevcdl_create(const hevcdl_config *cfg, const float *we
   if (cfg->bit_depth > 8) CK(hipMalloc(&ctx->d_yuv8, hevcdl_frame_bytes(cfg->width, cfg->height) * (size_t)cfg->max_frames));    // the CNN stage's 8-bit copy
   CK(hipMalloc(&ctx->d_weights, sizeof(float) * HEVCDL_W_TOTAL));
   CK(hipMemcpy(ctx->d_weights, pk.data(), sizeof(float) * HEVCDL_W_TOTAL, hipMemcpyHostToDevice));
-  ctx->scratch_per_wave = cfg->bit_depth == 8 ? std::max(std::max(hevcdl_rd_scratch_bytes(), hevcdl_rd_scratch_bytes_wide()), hevcdl_rd_scratch_bytes_tools()) : hevcdl_rd_scratch_bytes_bd10();
+  for (int b = 0; b < RD_BUILDS; b++)       // the largest of the builds this context can run: the three 8-bit ones, or the 10-bit one
+    if ((b == RD_BD10) == (cfg->bit_depth != 8)) ctx->scratch_per_wave = std::max(ctx->scratch_per_wave, rd_builds[b].scratch_bytes());
   ctx->rd_groups = (int)std::min<long long>(ctx->n_cus, (long long)cfg->max_frames * (cfg->wavefront ? ctx->ctus_y : cfg->tile_columns * cfg->tile_rows));
   // (launches of few units run on every CU: the workgroups without a unit take second luma passes from the others, launch_rd -- they need a workspace too)
   ctx->remote_groups = (cfg->bit_depth == 8 && !(cfg->exec_flags & HEVCDL_EXEC_NO_UNIT_HANDOVER) && ctx->n_cus >= 8 && ctx->n_cus <= 1024) ? ctx->n_cus : 0;
@@ -335,10 +346,7 @@ extern "C" hevcdl_status hevcdl_create(const hevcdl_config *cfg, const float *we
     const size_t chunk = (size_t)std::min<long long>((long long)cfg->max_frames * ctx->ctus, 131072);
     CK(hipMalloc(&ctx->d_a3, chunk * 4 * 2048 * sizeof(float))); ctx->a3_ctus = chunk;
   }
-  CK(hipFuncSetAttribute((const void *)hevcdl_rd_frame_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hevcdl_rd_smem_bytes()));
-  CK(hipFuncSetAttribute((const void *)hevcdl_rd_frame_kernel_bd10, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hevcdl_rd_smem_bytes_bd10()));
-  CK(hipFuncSetAttribute((const void *)hevcdl_rd_frame_kernel_wide, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hevcdl_rd_smem_bytes_wide()));
-  CK(hipFuncSetAttribute((const void *)hevcdl_rd_frame_kernel_tools, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hevcdl_rd_smem_bytes_tools()));
+  for (const RdBuild &b : rd_builds) CK(hipFuncSetAttribute(b.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b.smem_bytes()));
 #undef CK
   *out = ctx;
   return HEVCDL_OK;
@@ -453,6 +461,27 @@ extern "C" size_t hevcdl_stage_trace_fetch(unsigned int *dst, size_t cap_words)
 }
 #endif
 
+// Which build of the decision kernel (row of rd_builds) a launch runs: `walkers` units under way on `groups` workgroups, few_units = the few-units form (hevcdl_rd_params.remote).
+// Measured at 2160p on 256 CUs, eight- / ten-wave build (rd_kernel_wide.hip: 168 registers per lane instead of 256, no look-ahead
+// region): 200 frames 3.53 / 4.21 s, 300 frames 4.16 / 4.59 s, 450 frames 5.17 / 5.21 s, 600 frames 6.24 / 6.11 s, 1024 frames 10.33 / 9.50 s, 2048 frames
+// 16.08 / 15.66 s, 2560 frames 21.47 / 18.14 s -- but the ten-wave build moves three times the bytes (600 frames: 5.8 MB per CTU through the L2s against 1.85 MB:
+// register spills at 168 registers, the CU walk's snapshots in HBM).  It is chosen where it clearly pays: from three units per workgroup on (round 5; four before).  Launches in the
+// few-units form keep the eight-wave build.
+static int rd_build_of(const hevcdl_ctx *ctx, bool few_units, long long walkers, int groups)
+{
+  if (ctx->cfg.bit_depth != 8) return RD_BD10;
+  if (ctx->cfg.tools != HEVCDL_TOOLS_REFERENCE) return RD_TOOLS;      // a context with other tool switches than the reference cfg's runs the build that reads them: rd_kernel_tools.hip, eight waves
+  if (ctx->cfg.exec_flags & HEVCDL_EXEC_RD_NARROW) return RD_NARROW;
+  if (ctx->cfg.exec_flags & HEVCDL_EXEC_RD_WIDE) return RD_WIDE;
+  return (!few_units && walkers >= 3LL * groups) ? RD_WIDE : RD_NARROW;      // round 5, eight- / ten-wave build on 256 CUs: 450 frames 4.80 / 4.87 s, 600 frames 5.76 / 5.70 s, 768 frames 7.00 / 6.87 s, 1024 frames 9.44 / 8.78 s
+}
+// Can a launch of this context ever run the ten-wave build?  Its largest one decides: every unit the context can hold on every workgroup it can have.
+static bool rd_can_go_wide(const hevcdl_ctx *ctx)
+{
+  const long long max_units = (long long)ctx->cfg.max_frames * (ctx->cfg.wavefront ? ctx->ctus_y : ctx->cfg.tile_columns * ctx->cfg.tile_rows);
+  return rd_build_of(ctx, false, max_units, ctx->rd_groups) == RD_WIDE;
+}
+
 static hevcdl_status launch_rd(hevcdl_ctx *ctx, const void *d_yuv, int n_frames, const void *d_labels, void *d_records, void *d_recon, void *d_stats, hipStream_t s,
                                int ctu_begin = 0, int ctu_end = -1, const void *d_cabac_in = nullptr, void *d_cabac_out = nullptr,
                                int tile_begin = 0, int tile_count = -1, int session_frame = -1)
@@ -528,21 +557,12 @@ static hevcdl_status launch_rd(hevcdl_ctx *ctx, const void *d_yuv, int n_frames,
   if (p.remote && 22 * walkers <= ctx->remote_groups) p.remote = 2;
   // the ring of posted jobs has 2048 entries (rd_kernel.hip RQ_SIZE): a unit has at most two passes and the ten component jobs of its chroma modes posted
   if (p.remote && 12 * walkers > 2048) p.remote = 0;
-  if (p.remote && p.wpp == 1) { const char *e = getenv("HEVCDL_WPP_REMOTE"); if (e && atoi(e) >= 1 && atoi(e) <= 3) p.remote = atoi(e); }      // (measurement knob)
   if (p.remote) HIPCHK(hipMemsetAsync(ctx->d_sched, 0, 4096 + 2048 * 8, s));      // finished counter, queue head / tail, the ring (2048 pointers behind byte 4096)
-  // Which build of the 8-bit kernel.  Measured at 2160p on 256 CUs, eight- / ten-wave build (rd_kernel_wide.hip: 168 registers per lane instead of 256, no look-ahead
-  // region): 200 frames 3.53 / 4.21 s, 300 frames 4.16 / 4.59 s, 450 frames 5.17 / 5.21 s, 600 frames 6.24 / 6.11 s, 1024 frames 10.33 / 9.50 s, 2048 frames
-  // 16.08 / 15.66 s, 2560 frames 21.47 / 18.14 s -- but the ten-wave build moves three times the bytes (600 frames: 5.8 MB per CTU through the L2s against 1.85 MB:
-  // register spills at 168 registers, the CU walk's snapshots in HBM).  It is chosen where it clearly pays: from three units per workgroup on (round 5; four before).  Launches in the
-  // few-units form keep the eight-wave build.
-  // (a context with other tool switches than the reference cfg's runs the build that reads them: rd_kernel_tools.hip, eight waves)
-  const bool rt_tools = ctx->cfg.bit_depth == 8 && ctx->cfg.tools != HEVCDL_TOOLS_REFERENCE;
-  bool wide = false;
-  if (ctx->cfg.bit_depth == 8 && !rt_tools && !(ctx->cfg.exec_flags & HEVCDL_EXEC_RD_NARROW))
-    wide = (ctx->cfg.exec_flags & HEVCDL_EXEC_RD_WIDE) || (!p.remote && walkers >= 3LL * groups);      // round 5, eight- / ten-wave build on 256 CUs: 450 frames 4.80 / 4.87 s, 600 frames 5.76 / 5.70 s, 768 frames 7.00 / 6.87 s, 1024 frames 9.44 / 8.78 s
-  if (wide) p.remote = 0;      // (the ten-wave build together with the hand-over of units: launches of more than three and fewer than four units per workgroup, or exec_flags; tests/test_rd_gpu.py::test_units_handed_over_between_workgroups_give_the_same_result runs the pair)
-  const int waves = ctx->cfg.bit_depth != 8 ? hevcdl_rd_waves_per_group() : (wide ? hevcdl_rd_waves_per_group_wide() : hevcdl_rd_waves_per_group());
-  const int threads = 64 * waves;
+  const int build = rd_build_of(ctx, p.remote != 0, walkers, groups);
+  const RdBuild &rd = rd_builds[build];
+  if (build == RD_WIDE) p.remote = 0;      // (the ten-wave build together with the hand-over of units: launches of more than three and fewer than four units per workgroup, or exec_flags; tests/test_rd_gpu.py::test_units_handed_over_between_workgroups_give_the_same_result runs the pair)
+  const int waves = rd.waves_per_group(), threads = 64 * waves;
+  const size_t smem = rd.smem_bytes();
   // Waves of a workgroup that claim rows (the rest help them).  A frame's rows form a chain of ctus_x + 2 (ctus_y - 1) CTU steps; a step takes a claimer ~1.5 ms with seven
   // helpers and ~8 ms without any (t(m) ~ 0.75 + 0.75 m ms at m claimers per workgroup, measured on 600-frame launches: profiles/r06d_wavefront_masters.txt), while the
   // chip's rate grows with m (216 k CTU/s at 2 ... 313 k at 10).  A launch is bound by that chain until the work per claimer exceeds it: m = 0.7 x (CTUs of the launch) /
@@ -550,9 +570,6 @@ static hevcdl_status launch_rd(hevcdl_ctx *ctx, const void *d_yuv, int n_frames,
   // m = 10 3.91 s, m = 6 4.54 s, m = 3 5.06 s.
   if (p.wpp == 1) { const long long chain = ctx->ctus_x + 2LL * (ctx->ctus_y - 1);
                     p.wpp_masters = p.remote ? 1 : (int)std::max<long long>(1, std::min<long long>(waves, (7LL * n_frames * ctx->ctus) / (10LL * groups * chain))); }
-  if (p.wpp == 1 && !p.remote) { const char *e = getenv("HEVCDL_WPP_MASTERS"); if (e && atoi(e) > 0) p.wpp_masters = std::min(waves, atoi(e)); }      // (measurement knob: tools/time_rd.py sweeps)
-  const void *kern = ctx->cfg.bit_depth == 8 ? (wide ? (const void *)hevcdl_rd_frame_kernel_wide : (rt_tools ? (const void *)hevcdl_rd_frame_kernel_tools : (const void *)hevcdl_rd_frame_kernel)) : (const void *)hevcdl_rd_frame_kernel_bd10;
-  const size_t smem = ctx->cfg.bit_depth == 8 ? (wide ? hevcdl_rd_smem_bytes_wide() : (rt_tools ? hevcdl_rd_smem_bytes_tools() : hevcdl_rd_smem_bytes())) : hevcdl_rd_smem_bytes_bd10();
   { // the workspace: one block per wave of every workgroup of this launch
     const size_t need = ctx->scratch_per_wave * (size_t)(p.remote ? ctx->remote_groups : groups) * (size_t)waves;
     if (need > ctx->scratch_bytes) {
@@ -565,24 +582,19 @@ static hevcdl_status launch_rd(hevcdl_ctx *ctx, const void *d_yuv, int n_frames,
   }
   prof_begin(ctx, ctx->ev_rd, s);
   bool launched = false;
+  void *args[] = { &p };
   if (p.migrate || p.remote || p.wpp == 1) { // workgroups that wait for each other: a cooperative launch, which the runtime only accepts when the whole grid can be resident at once
-    void *args[] = { &p };
-    if (hipLaunchCooperativeKernel(kern, dim3(p.remote ? ctx->remote_groups : groups), dim3(threads), args, smem, s) == hipSuccess) launched = true;
+    if (hipLaunchCooperativeKernel(rd.kernel, dim3(p.remote ? ctx->remote_groups : groups), dim3(threads), args, smem, s) == hipSuccess) launched = true;
     else {
       (void)hipGetLastError(); p.migrate = 0; p.remote = 0;
       if (p.wpp == 1) { prof_end(ctx, ctx->ev_rd, s); ctx->cfg.exec_flags |= HEVCDL_EXEC_NO_UNIT_HANDOVER;      // rows on waves of their own need co-residency: this context walks a frame's rows on one wave from now on
                         return launch_rd(ctx, d_yuv, n_frames, d_labels, d_records, d_recon, d_stats, s, ctu_begin, ctu_end, d_cabac_in, d_cabac_out, tile_begin, tile_count); }
     }
   }
-  if (!launched) {
-    if (ctx->cfg.bit_depth != 8) hipLaunchKernelGGL(hevcdl_rd_frame_kernel_bd10, dim3(groups), dim3(threads), smem, s, p);
-    else if (wide) hipLaunchKernelGGL(hevcdl_rd_frame_kernel_wide, dim3(groups), dim3(threads), smem, s, p);
-    else if (rt_tools) hipLaunchKernelGGL(hevcdl_rd_frame_kernel_tools, dim3(groups), dim3(threads), smem, s, p);
-    else hipLaunchKernelGGL(hevcdl_rd_frame_kernel, dim3(groups), dim3(threads), smem, s, p);
-  }
+  if (!launched) (void)hipLaunchKernel(rd.kernel, dim3(groups), dim3(threads), args, smem, s);      // (an error is picked up below, as after every launch)
   prof_end(ctx, ctx->ev_rd, s);
   HIPCHK(hipGetLastError());
-  snprintf(ctx->last_rd, sizeof ctx->last_rd, "%s form=%s workgroups=%d waves=%d units=%d", ctx->cfg.bit_depth != 8 ? "hevcdl_rd_frame_kernel_bd10" : (wide ? "hevcdl_rd_frame_kernel_wide" : (rt_tools ? "hevcdl_rd_frame_kernel_tools" : "hevcdl_rd_frame_kernel")),
+  snprintf(ctx->last_rd, sizeof ctx->last_rd, "%s form=%s workgroups=%d waves=%d units=%d", rd.name,
            p.wpp == 1 ? (p.remote ? "wavefront-rows+few-units" : "wavefront-rows") : p.wpp == 2 ? "wavefront(one wave per frame)" : p.migrate ? "unit-handover" : (p.remote == 1 ? "few-units(passes)" : (p.remote == 2 ? "few-units(passes+chroma)" : (p.remote == 3 ? "few-units(passes while takers idle)" : "independent"))),
            p.remote ? ctx->remote_groups : groups, waves, n_units);
 #if defined(HEVCDL_KERNEL_PROF) || defined(HEVCDL_KERNEL_DEBUG)
@@ -758,12 +770,9 @@ extern "C" hevcdl_status hevcdl_reserve_workspace(hevcdl_ctx *ctx)
 {
   if (!ctx) return HEVCDL_ERR_INVALID_ARG;
   HIPCHK(hipSetDevice(ctx->cfg.device));
-  const long long max_units = (long long)ctx->cfg.max_frames * (ctx->cfg.wavefront ? ctx->ctus_y : ctx->cfg.tile_columns * ctx->cfg.tile_rows);
   const int groups = std::max(ctx->rd_groups, ctx->remote_groups);
-  int waves = ctx->cfg.bit_depth != 8 ? hevcdl_rd_waves_per_group() : hevcdl_rd_waves_per_group();
-  const bool rt_tools = ctx->cfg.bit_depth == 8 && ctx->cfg.tools != HEVCDL_TOOLS_REFERENCE;      // launch_rd's rule: such a context never runs the ten-wave build
-  if (ctx->cfg.bit_depth == 8 && !rt_tools && !(ctx->cfg.exec_flags & HEVCDL_EXEC_RD_NARROW) && ((ctx->cfg.exec_flags & HEVCDL_EXEC_RD_WIDE) || max_units >= 3LL * ctx->rd_groups))
-    waves = std::max(waves, hevcdl_rd_waves_per_group_wide());
+  int waves = rd_builds[rd_build_of(ctx, true, 0, 0)].waves_per_group();      // the build of a launch in the few-units form
+  if (rd_can_go_wide(ctx)) waves = std::max(waves, rd_builds[RD_WIDE].waves_per_group());
   const size_t need = ctx->scratch_per_wave * (size_t)groups * (size_t)waves;
   if (need <= ctx->scratch_bytes) return HEVCDL_OK;
   HIPCHK(hipDeviceSynchronize());

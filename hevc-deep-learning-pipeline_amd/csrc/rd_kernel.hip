@@ -71,6 +71,14 @@ constexpr int NPEND = BD == 8 ? HEVCDL_NPEND : 1;                         // sec
 #define HEVCDL_AHEAD 1
 #endif
 constexpr int AHEAD = (BD == 8 && HEVCDL_AHEAD) ? 1 : 0;       // first-pass candidates of the NEXT CU coded during this CU's chroma search (est_intra_chroma); needs one more region per wave
+// tuned thresholds, each with the measurement behind its value
+constexpr int RMD_SLICE_ROUNDS = 3;   // rough mode decisions of this many rounds of 64 (mode, block) tasks or more are dealt to the workgroup's waves
+constexpr int CARRY_MAX = 2;          // second passes are left pending behind a master only in workgroups with this many masters at most (with waves scarcer the work thrown away at a restart
+                                      // costs more than the waiting saved); measured on the 600-frame job (2-3 masters per workgroup): 1 -> 7.00 s, 2 -> 6.52 s, 3 -> 6.63 s
+constexpr int FG_FIRST_MAX = CARRY_MAX;   // helpers serve the masters' own regions before the pending passes up to this many masters (helper_step)
+constexpr int PREFETCH_MAX = 3;       // the master computes the next CU's rough-mode SATD during the chroma search up to this many masters (est_intra_chroma)
+constexpr int HOP = 4;                // a master offers its unit to the next workgroup of the ring every this many CTUs (unit hand-over, see Mbox); a power of two
+constexpr int AHEAD_MAX = 1;          // measured: with two or three masters per workgroup the candidates coded ahead only take waves from work that is needed now (600 frames: 6.45 -> 6.70 s at 3)
 #ifdef HEVCDL_MICRO_SMALL
 // -DHEVCDL_MICRO -DHEVCDL_MICRO_SMALL -DHEVCDL_NW=12|16: the occupancy experiment of tools/micro_rd.py.  Only hevcdl_micro_kernel of such a library may be launched: the
 // LDS block of a wave is cut down to what the leaf routines of a TU coding touch (so that 12 / 16 waves fit a CU) and the search functions index beyond it.
@@ -333,12 +341,9 @@ DEV int tools_of(KR k) { return HEVCDL_TOOLS_RT ? __builtin_amdgcn_readfirstlane
 #else
 #define TL(ev, arg) do { } while (0)
 #endif
-// -DHEVCDL_DBG_EXEC: trap (s99 = site) when a function that needs the whole wave is entered with lanes masked off; run under rocgdb
-#ifdef HEVCDL_DBG_EXEC
-#define CHECK_EXEC(id) do { if (__builtin_amdgcn_read_exec() != ~0ull) { asm volatile("s_mov_b32 s99, %0\n s_trap 2" :: "i"(id) : "s99"); } } while (0)
-#else
+// CHECK_EXEC: the empty left-over of a retired debugging build (HISTORY.md).  Its three call sites (recur_luma, est_intra_luma, compress_cu) stay for now: the compiler numbers a
+// function's branch targets in source order, empty loops included, and those numbers end up as constants in the code -- the sites go with the next change to those functions
 #define CHECK_EXEC(id) do { } while (0)
-#endif
 // ---- regions: alternatives of the search handed to the waves of the workgroup (see the header comment) ----
 enum { T_LUMA_P1 = 1, T_CHROMA = 2, T_LUMA_SPLIT = 3, T_LUMA_P2 = 4, T_RMD = 5, T_LUMA_AHEAD = 6, T_REMOTE = 7 };   // T_REMOTE: a second pass run by another workgroup (no ticket here; answered through HBM)
 enum { SLOT_CHROMA = 5, SLOT_SPLIT = 10, SLOT_P2 = 14, SLOT_PSET = 5 };   // result slots: 0..9 the first pass, 5..9 the chroma modes (after it); per second pass (set p = its region - 1, slots + 5 p): 10..13 its split tasks (by child), 14 its verdict + start state
@@ -364,42 +369,17 @@ struct Tables {                        // read-only after kernel start, one copy
 };
 struct __attribute__((aligned(16))) WgShared {
   Region reg[NW][NREG];               // see NREG
-  int masters_active, quit, remote, bell;       // waves that currently walk a unit; quit: a workgroup without units has seen the last unit finish; remote: hevcdl_rd_params.remote; bell: counts the times tasks were put up in any region of the workgroup (ring_bell)
+  int masters_active, quit, remote, bell;       // waves that currently walk a unit; quit: a workgroup without units has seen the last unit finish; remote: hevcdl_rd_params.remote; bell: see the idle loops of hevcdl_rd_frame_kernel
   GLB unsigned char *sched; unsigned long long pad2_;
   Tables tab;
 };
 DEV LDS WgShared &wg_shared() { return *(LDS WgShared *)(lds_base() + (size_t)NW * sizeof(RdSmem)); }
 DEV LRegion &my_region(int which = 0) { return wg_shared().reg[wave_id()][which]; }
 DEV LDS Tables &tb() { return wg_shared().tab; }
-#ifndef HEVCDL_RMD_SLICE_ROUNDS
-#define HEVCDL_RMD_SLICE_ROUNDS 3      // rough mode decisions of this many rounds of 64 (mode, block) tasks or more are dealt to the workgroup's waves
-#endif
-#ifndef HEVCDL_SPEC_MARGIN
-#define HEVCDL_SPEC_MARGIN 0
-#endif
-#ifndef HEVCDL_PREFETCH
-#define HEVCDL_PREFETCH 1
-#endif
-#ifndef HEVCDL_CARRY_MAX
-#define HEVCDL_CARRY_MAX 2      // second passes are left pending behind a master only in workgroups with this many masters at most (with waves scarcer the work thrown away at a restart
-                                // costs more than the waiting saved); measured on the 600-frame job (2-3 masters per workgroup): 1 -> 7.00 s, 2 -> 6.52 s, 3 -> 6.63 s
-#endif
-#ifndef HEVCDL_FG_FIRST_MAX
-#define HEVCDL_FG_FIRST_MAX HEVCDL_CARRY_MAX   // helpers serve the masters' own regions before the pending passes up to this many masters (helper_step)
-#endif
-#ifndef HEVCDL_OWNER_LENDS
-#define HEVCDL_OWNER_LENDS 0                  // 1: the owner of a split chain runs other masters' tasks while it waits for its split tasks (spec_children).  Measured on the 600-frame job: 6.23 -> 6.28 s (it returns late to its own chain, and the join of its pass waits), so off
-#endif
-#ifndef HEVCDL_CHROMA_ROOM
-#define HEVCDL_CHROMA_ROOM 0                 // launches of 17..170 units: > 0 posts a CU's chroma modes to other workgroups when at least this many of them are idle beyond the jobs already queued.  Measured (16 / 48): 20 frames 3.16 -> 3.9 s, 40 frames 3.17 -> 4.2 / 3.9 s, 75 frames 3.21 -> 3.66 / 3.46 s -- the takers are needed for the second passes; 0 = never
-#endif
-#ifndef HEVCDL_PREFETCH_MAX
-#define HEVCDL_PREFETCH_MAX 3                 // the master computes the next CU's rough-mode SATD during the chroma search up to this many masters (est_intra_chroma)
-#endif
 DEV int lds_load(LDS int *p);
 // spare waves for the second-pass tasks: at least as many waves without a unit as with one (chain owners serve their own split tasks, so no
 // wave ever waits on an unserved region)
-DEV int spare_waves() { return 2 * lds_load(&wg_shared().masters_active) <= NW - HEVCDL_SPEC_MARGIN; }
+DEV int spare_waves() { return 2 * lds_load(&wg_shared().masters_active) <= NW; }
 DEV int lds_load(LDS int *p) { return uni(__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)); }
 DEVN int lds_add(LDS int *p, int v)
 { // one atomic per wave (lane 0), result to every lane.  NOT inlined: inlined into a loop whose exit depends on the result, the lane-0
@@ -408,24 +388,6 @@ DEVN int lds_add(LDS int *p, int v)
   if (lane_id() == 0) r = __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   return uni(r);
 }
-// -DHEVCDL_BELL (round 5, measured and NOT kept): a doorbell.  A wave without work walks the NREG * NW tickets again and again (40 dependent LDS round trips a
-// scan, ~4 k cycles, then s_sleep 32).  With the bell it sleeps on ONE word that region_open / region_publish count up, and walks the tickets when it has moved.
-// On 256-frame launches (one master, seven helpers per workgroup) that takes 7 % off the kernel's vector + scalar instructions (3.00 -> 2.79 M per CTU,
-// profiles/r05b_bell_counters.txt) -- and costs time: one frame 2.82 -> 2.85 s, 600 frames 6.25 -> 6.31 s, 2048 frames 15.68 -> 15.75 s (two runs each, one
-// box): the poll every 512 cycles and the call behind every ticket take more issue slots from the busy waves than the scans did, and a helper that finds its task
-// 2 k cycles sooner shortens nothing (the tasks are 100 k cycles long).  s_wakeup behind the bell ends the other waves' s_sleep at once (tools/wakeup_probe.hip:
-// a wave in s_sleep 32 notices a flag after 370 instead of 1 280 cycles) -- with it the kernel died with GPU memory faults in every launch of the independent
-// form (three builds with it against three without), so it is not even an option.
-#ifdef HEVCDL_BELL
-constexpr int HELPER_BELL = 1;
-DEVN void ring_bell() { if (lane_id() == 0) __hip_atomic_fetch_add(&wg_shared().bell, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-#else
-constexpr int HELPER_BELL = 0;
-DEV void ring_bell() { }
-#endif
-#ifndef HEVCDL_IDLE_SLEEP
-#define HEVCDL_IDLE_SLEEP 8          // x 64 cycles between two looks at the bell
-#endif
 // hand-over points between waves of the workgroup (same CU: LDS and the vector L1 are shared, workgroup scope is enough)
 DEV void wg_release() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); }
 DEV void wg_acquire() { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); }
@@ -550,7 +512,7 @@ DEV int part_attr(KR k, int field, int x4, int y4)
 // ---------------------------------------------------------------------------------------------------
 DEV LDS int16_t *ref_line(int c) { return c ? lds().cline[c - 1] : lds().line; }
 DEV void build_refs_i(KR k, int c_, int x_, int y_, int n_, int force_)
-{ // _i: the body, inlined into code_tu_block (HEVCDL_REFS_INLINE); build_refs: the call form
+{ // _i: the body, inlined into the copies of code_tu_block with the block size as a constant; build_refs: the call form
   PROF_T0();
   const int c = uni(c_), x = uni(x_), y = uni(y_), n = uni(n_);
   const int key = (ilog2(n) << 24) | (y << 12) | x;
@@ -635,9 +597,6 @@ DEV void build_refs_i(KR k, int c_, int x_, int y_, int n_, int force_)
 }
 
 DEVN void build_refs(KR k, int c_, int x_, int y_, int n_, int force_) { build_refs_i(k, c_, x_, y_, n_, force_); }
-#ifndef HEVCDL_REFS_INLINE
-#define HEVCDL_REFS_INLINE 1
-#endif
 
 DEV void filter_refs(KR k, int n_)
 {
@@ -998,18 +957,6 @@ constexpr int mt_slot(int id) { return id == 18 ? 0 : id == 19 ? 1 : id == 4 ? 2
 #else
 #define RDOQ_MARK(id) do { } while (0)
 #endif
-#ifdef HEVCDL_RDOQ_STOP
-#define RDOQ_STOP(id) do { if (HEVCDL_RDOQ_STOP == (id)) return 0; } while (0)
-#define RDOQ_SKIP(id) if (HEVCDL_RDOQ_STOP == (id)) { cgpos -= R; continue; }
-#else
-#define RDOQ_STOP(id) do { } while (0)
-#define RDOQ_SKIP(id)
-#endif
-#ifdef HEVCDL_RDOQ_STOP
-#define HEVCDL_RDOQ_STOPV HEVCDL_RDOQ_STOP
-#else
-#define HEVCDL_RDOQ_STOPV 0
-#endif
 // RDOQ, whole wave, coefficient groups in batches.  s->tc -> s->lvl ; returns uiAbsSum.  Same arithmetic, same order of every fp64 sum as the reference
 // (TComTrQuant.cpp:2119-2661); what changes is how the work inside phase B is laid out:
 //   * What a group's level decisions depend on: its own positions (the c1 / c2 / Rice state machine runs inside a group and starts afresh in
@@ -1026,12 +973,9 @@ constexpr int mt_slot(int id) { return id == 18 ? 0 : id == 19 ? 1 : id == 4 ? 2
 //     the number of decisions that differ from the guess (typically 2 passes for the whole batch instead of one serial visit per level).
 //   * The ordered sums and the group-level tests (zero-out of a group, TComTrQuant.cpp:2385-2440) then run group by group in scan order,
 //     addends transposed through LDS once per batch.
-// NFIX != 0: the TU size as a compile-time constant (the 4x4 / 8x8 copies: group counts, loop bounds and the masks over the groups fold).  HEVCDL_RDOQ_FIX: the
-// largest size that gets a copy of its own.  Measured (round 5): per call 4x4 8 175 -> 6 795 cycles, 8x8 20 035 -> 17 970; whole kernel, none / 4 / 8 / 16:
+// NFIX != 0: the TU size as a compile-time constant (the 4x4 / 8x8 copies: group counts, loop bounds and the masks over the groups fold).
+// Measured (round 5): per call 4x4 8 175 -> 6 795 cycles, 8x8 20 035 -> 17 970; whole kernel, none / 4 / 8 / 16:
 // one frame 2.62 / 2.60 / 2.59 / 2.59 s, 600 frames 5.77 / 5.72 / 5.70 / 5.71 s, 2048 frames 14.55 / 14.67 / 14.56 / 14.64 s (every copy is 26 KB more code)
-#ifndef HEVCDL_RDOQ_FIX
-#define HEVCDL_RDOQ_FIX 8
-#endif
 template <int NFIX = 0> DEV uint32_t rdoq_wave(KR k, const LCabac *cab, int c_, int n_, int dir_mode_, int cbf_ctx_)
 {
   const int c = uni(c_), n = NFIX ? NFIX : uni(n_), dir_mode = uni(dir_mode_), cbf_ctx = uni(cbf_ctx_);
@@ -1101,7 +1045,6 @@ template <int NFIX = 0> DEV uint32_t rdoq_wave(KR k, const LCabac *cab, int c_, 
   if (last_pos < 0) return 0;
   __builtin_assume(last_pos < ncoef);                       // (with NFIX == 4: one group -- the batch logic, the group test and the walk over the groups fold)
   RDOQ_MARK(18);
-  RDOQ_STOP(18);
   const int sig_off = CTX_SIG + (ch ? 28 : 0), cg_off = CTX_SIG_CG + (ch ? 2 : 0);
   int cg_b00, cg_b01, cg_b10, cg_b11, cbf_bits0, cbf_bits1;  // rates of the significant-group flag [context][value] and of the cbf flag [value]
   { // rate tables: ONE pair of dependent LDS reads for everything the call prices with the (frozen) contexts -- significance, greater-1 / greater-2, the
@@ -1163,7 +1106,6 @@ template <int NFIX = 0> DEV uint32_t rdoq_wave(KR k, const LCabac *cab, int c_, 
   }
   double acc = lane < 2 ? block_uncoded : 0.0;          // lanes 0 / 1 / 2: block_uncoded, base_cost, the current group's significance cost (phase B)
   RDOQ_MARK(19);
-  RDOQ_STOP(19);
   const int cg_last = last_pos >> 4, wg = cp.wg, lwg = log2n - 2;
   // rates of the significant-group flag, by context (0 / 1) and value
   const double cgr00 = lambda * (double)cg_b00, cgr01 = lambda * (double)cg_b01;
@@ -1207,7 +1149,6 @@ template <int NFIX = 0> DEV uint32_t rdoq_wave(KR k, const LCabac *cab, int c_, 
     const int b0_j = is_last ? 0 : s.rq_sig[sc_j][0], b1_j = is_last ? 0 : s.rq_sig[sc_j][1];
     const double cs0_j = lambda * (double)b0_j, cs1_j = lambda * (double)b1_j;
     RDOQ_MARK(4);
-    RDOQ_SKIP(4)
     int lvl_j = 0, ru_j = 0, rd_j = 0;
     double cc_j = c0_j + cs0_j, cs_j = cs0_j;
     unsigned long long g1m = 0;
@@ -1307,7 +1248,6 @@ template <int NFIX = 0> DEV uint32_t rdoq_wave(KR k, const LCabac *cab, int c_, 
         }
       }
     }
-    RDOQ_SKIP(5)
     // --- the ordered sums, group by group (each in scan order, pin = 15..0, as the reference accumulates them).  Three of them ride in ONE chain of 16 additions on
     // lanes 0..2 of `acc` (addends transposed through LDS):   0 block_uncoded += c0      1 base_cost += cost_c      2 sig_cost += cost_s (from zero, per group)
     // and stay in their lanes from group to group and from batch to batch: the group's test runs on lane 1 (lane 2's sum comes over the DPP crossbar), nothing is
@@ -1377,7 +1317,6 @@ template <int NFIX = 0> DEV uint32_t rdoq_wave(KR k, const LCabac *cab, int c_, 
   block_uncoded = rl_d(acc, 0);
   double base_cost = rl_d(acc, 1);
   RDOQ_MARK(20);
-  RDOQ_STOP(20);
   // ---- phase C: last position, TComTrQuant.cpp:2440-2528.  Per CG the 16 positions' costs are fetched
   // lane-parallel, the walk itself is wave-uniform (readlane) and usually ends inside the first group ----
   int best_last_p1 = 0;
@@ -1449,7 +1388,6 @@ template <int NFIX = 0> DEV uint32_t rdoq_wave(KR k, const LCabac *cab, int c_, 
     }
   }
   RDOQ_MARK(21);
-  RDOQ_STOP(21);
   // signs, absolute sum, uncoded tail (lane-parallel; integer sum is exact) -- and, in the same walk, which groups sign data hiding (TComTrQuant.cpp:2530-2660) has to
   // visit at all: a group whose first and last level are four positions or more apart and whose level parity disagrees with the sign of its first level.  A visit only
   // changes levels of its own group, so the tests of all groups can be made beforehand, four groups (one per row of 16 lanes) at a time.
@@ -1779,21 +1717,13 @@ template <int NFIX> DEV uint32_t code_coeff_wave_i(KR k, LCabac *c, int comp_, i
 }
 template <int NFIX> DEVN uint32_t code_coeff_wave_n(KR k, LCabac *c, int comp_, int n_, int dir_mode_, int tskip_flag_, int pre_, int luma_cfrac_)
 { return code_coeff_wave_i<NFIX>(k, c, comp_, n_, dir_mode_, tskip_flag_, pre_, luma_cfrac_); }
-#ifndef HEVCDL_BITS_FIX
-#define HEVCDL_BITS_FIX 16        // per call (tools/micro_rd.py), one copy / own copies: 4x4 4 082 -> 3 495 cycles, 8x8 7 335 -> 6 749
-#endif
+// blocks up to 16x16 get a copy of their own.  Per call (tools/micro_rd.py), one copy / own copies: 4x4 4 082 -> 3 495 cycles, 8x8 7 335 -> 6 749
 DEV uint32_t code_coeff_wave(KR k, LCabac *c, int comp, int n_, int dir_mode, int tskip_flag, int pre = PRE_COEF | PRE_NONE, int luma_cfrac = 0)
 {
   const int n = uni(n_);
-#if HEVCDL_BITS_FIX >= 4
   if (n == 4) return code_coeff_wave_n<4>(k, c, comp, n, dir_mode, tskip_flag, pre, luma_cfrac);
-#endif
-#if HEVCDL_BITS_FIX >= 8
   if (n == 8) return code_coeff_wave_n<8>(k, c, comp, n, dir_mode, tskip_flag, pre, luma_cfrac);
-#endif
-#if HEVCDL_BITS_FIX >= 16
   if (n == 16) return code_coeff_wave_n<16>(k, c, comp, n, dir_mode, tskip_flag, pre, luma_cfrac);
-#endif
   return code_coeff_wave_n<0>(k, c, comp, n, dir_mode, tskip_flag, pre, luma_cfrac);
 }
 
@@ -1937,12 +1867,10 @@ DEV void enc_intra_header(KR k, LCabac *c, const Cu &cu, const Tu &tu, int luma,
 // register-resident coder: the header flags (xEncIntraHeader :1018-1087, xEncSubdivCbfQT :907-972) are bins in front of the coefficients (code_coeff_wave) instead of
 // three dependent LDS round trips each on lane 0, and the levels are read where code_tu_block left them (lvl_in_lds: TUs up to 16x16, see inv_transform_n) instead of
 // coming back from the layer buffer.  Same bins, same contexts, same order per context; leaves `go` and s.cfrac_last as intra_bits_qt does.
-#ifndef HEVCDL_BITS_INLINE
-#define HEVCDL_BITS_INLINE 1     // the count behind a TU coding runs the bit counter inside code_tu_block's frame (the copies with the block size as a constant): no call frame
-#endif                           // (37 scalar registers saved and restored through scratch) and no s_waitcnt vmcnt(0) at a function entry right behind the coding's stores
+// The count behind a TU coding runs the bit counter inside code_tu_block's frame (the copies with the block size as a constant): no call frame
+// (37 scalar registers saved and restored through scratch) and no s_waitcnt vmcnt(0) at a function entry right behind the coding's stores
 template <int NFIX = 0> DEV uint32_t luma_tu_bits_body(KR k, const Cu cu_, const Tu tu_, int lvl_in_lds_)
 {
-  CHECK_EXEC(11);
   PROF_T0();
   const Cu cu = ucu(cu_); const Tu tu = utu(tu_); const int lvl_in_lds = uni(lvl_in_lds_);
   LSmem &s = lds();
@@ -1971,7 +1899,7 @@ template <int NFIX = 0> DEV uint32_t luma_tu_bits_body(KR k, const Cu cu_, const
   if (cbf && !lvl_in_lds) load_tu_coef(k, 0, 0, tu.log2, z, n);
   const int pre_all = pre | (nep << PRE_EP_SHIFT) | PRE_RESET | (cbf ? PRE_COEF : 0);
   uint32_t bits;
-  if constexpr (NFIX != 0 && HEVCDL_BITS_INLINE && NFIX <= HEVCDL_BITS_FIX) bits = code_coeff_wave_i<NFIX>(k, &s.go, 0, NFIX, mode, tskip, pre_all, 1);
+  if constexpr (NFIX != 0) bits = code_coeff_wave_i<NFIX>(k, &s.go, 0, NFIX, mode, tskip, pre_all, 1);
   else bits = code_coeff_wave(k, &s.go, 0, n, mode, tskip, pre_all, 1);
   wsync();
   PROF_ADD_T(k, 10, 49);
@@ -1982,7 +1910,6 @@ template <int NFIX = 0> DEV uint32_t luma_tu_bits_body(KR k, const Cu cu_, const
 // register-resident coder (the flags were three dependent LDS round trips each on lane 0).  Leaves `go` and s.cfrac_last_c as intra_bits_qt does.
 DEVN uint32_t chroma_cu_bits_1tu(KR k, const Cu cu_, const Tu tu_)
 {
-  CHECK_EXEC(11);
   PROF_T0();
   const Cu cu = ucu(cu_); const Tu tu = utu(tu_);
   LSmem &s = lds();
@@ -2002,7 +1929,6 @@ DEVN uint32_t chroma_cu_bits_1tu(KR k, const Cu cu_, const Tu tu_)
 DEVN uint32_t luma_tu_bits(KR k, const Cu cu_, const Tu tu_, int lvl_in_lds_) { return luma_tu_bits_body(k, cu_, tu_, lvl_in_lds_); }     // (the call form: the transform-skip trial of a 4x4 TU; everywhere else the count rides inside code_tu_block)
 template <int LOG2> DEVN uint32_t intra_bits_qt(KR k, const Cu cu_, const Tu tu_, int luma_, int chroma_)
 {
-  CHECK_EXEC(11);
   PROF_T0();
   const Cu cu = ucu(cu_); const Tu tu = utu(tu_); const int luma = uni(luma_), chroma = uni(chroma_); // xGetIntraBitsQT TEncSearch.cpp:1093-1117
   LCabac *c = &lds().go;
@@ -2105,7 +2031,6 @@ DEVN void enc_cu_syntax(KR k, LCabac *c, const Cu cu_)
 template <int NFIX> DEVN TuRes code_tu_block_n(KR k, const Cu cu_, const Tu tu_, int comp_, int mode012_, int count_)
 { // count_ (luma, the TU coded as one transform block): the bit count that follows every such coding (luma_tu_bits) is made before the function returns -- one
   // call frame (37 scalar registers saved and restored, two scratch round trips) per TU coding instead of two
-  CHECK_EXEC(1);
   PROF_T0();
   PROF_MARK0();
   const Cu cu = ucu(cu_); const Tu tu = utu(tu_); const int comp = uni(comp_), mode012 = uni(mode012_), count = uni(count_);
@@ -2118,7 +2043,7 @@ template <int NFIX> DEVN TuRes code_tu_block_n(KR k, const Cu cu_, const Tu tu_,
   const int tskip = uni(s.a[A_TSKIP + comp][zabs]);
   const int use_rdoq = tools_of(k) & (int)(tskip ? HEVCDL_TOOL_RDOQTS : HEVCDL_TOOL_RDOQ);        // useRDOQ = transform skip ? RDOQTS : RDOQ (TComTrQuant.cpp:1152)
   if (mode012 != 2) {
-    if (HEVCDL_REFS_INLINE && NFIX) build_refs_i(k, comp, x, y, n, 0); else build_refs(k, comp, x, y, n, 0);
+    if (NFIX) build_refs_i(k, comp, x, y, n, 0); else build_refs(k, comp, x, y, n, 0);
     if (ub(use_filtered_refs(comp, mode, n))) filter_refs(k, n);
     predict_block(k, comp, mode, n);
     if (mode012 == 1 && lane_id() < 16) s.ts_pred[comp][lane_id()] = s.pred[lane_id()];
@@ -2205,22 +2130,13 @@ template <int NFIX> DEVN TuRes code_tu_block_n(KR k, const Cu cu_, const Tu tu_,
   if (count) res.bits = luma_tu_bits_body<NFIX>(k, cu, tu, log2n <= 4);
   return res;
 }
-#ifndef HEVCDL_TU_FIX
-#define HEVCDL_TU_FIX 16         // 0: one copy of code_tu_block for every size; 4 / 8 / 16: blocks up to that size get their own.  Measured (round 5), 0 / 4 / 8 / 16:
-                                 // one frame 2.62 / 2.60 / 2.55 / 2.54 s, 600 frames 5.755 / 5.74 / 5.65 / 5.61 s, 2048 frames 14.64 / 14.48 / 14.43 / 14.47 s
-#endif
+// blocks up to 16x16 get a copy of their own, with the block size as a constant (measured in round 5 against one copy for every size: HISTORY.md)
 DEV TuRes code_tu_block(KR k, const Cu &cu, const Tu &tu, int comp, int mode012, int count = 0)
 {
   const int n = uni(comp) ? tu_csize(utu(tu)) : (1 << uni(tu.log2));
-#if HEVCDL_TU_FIX >= 4
   if (n == 4) return code_tu_block_n<4>(k, cu, tu, comp, mode012, count);
-#endif
-#if HEVCDL_TU_FIX >= 8
   if (n == 8) return code_tu_block_n<8>(k, cu, tu, comp, mode012, count);
-#endif
-#if HEVCDL_TU_FIX >= 16
   if (n == 16) return code_tu_block_n<16>(k, cu, tu, comp, mode012, count);
-#endif
   return code_tu_block_n<0>(k, cu, tu, comp, mode012, count);
 }
 
@@ -2253,7 +2169,7 @@ DEV void chroma_mode_list(int luma_mode, uint32_t (&mode_list)[5])
 DEVN void region_open(LRegion &r, int kind_, int n_, const Cu cu_, const Tu tu_);
 DEVN void region_run(KR k, LRegion &r);
 DEV void region_close(LRegion &r) { }
-DEV void region_publish(LRegion &r) { wg_release(); lds_add(&r.ticket, 1 << 16); ring_bell(); }         // one more task (parameters written before)
+DEV void region_publish(LRegion &r) { wg_release(); lds_add(&r.ticket, 1 << 16); }         // one more task (parameters written before)
 DEVN int remote_poll(LRegion &r);
 DEVN int remote_room(int need = 1);
 DEVN void chroma_post(KR k, const Cu cu_, const Tu tu_, int m0, int m1, int m2, int m3, int m4, int prepare_only);
@@ -2430,7 +2346,6 @@ template <int LOG2> DEV void set_result(KR k, const Cu &cu, const Tu &tu, int co
 DEVN void set_result_cu(KR k, const Cu cu_, const Tu tu_, int comp_, GLB const int16_t *src_coef, GLB const pel_t *src_rec, int slz_, int slx_, int sly_)
 {
   const int slz = uni(slz_), slx = uni(slx_), sly = uni(sly_);
-  CHECK_EXEC(10);
   PROF_T0();
   const Cu cu = ucu(cu_); const Tu tu = utu(tu_); const int comp = uni(comp_);
   wsync();
@@ -2475,7 +2390,7 @@ template <int LOG2> DEVN DistCbf spec_children(KR k, const Cu cu_, const Tu tu_)
   while (j < 4) {
     wsync();
     if (lane_id() < 4) { r.modes[lane_id()] = j + lane_id(); r.modes[8 + lane_id()] = 0; }          // task i: the split alternative of child j + i; [8 + c]: the chain's answer for child c is there
-    if (lane_id() == 0) r.dist[11] = 0;                                 // context copies made by the waves that took split tasks (helper_step)
+    if (lane_id() == 0) r.dist[11] = 0;                                 // context copies made by the waves that took split tasks (helper_step): left over from a retired experiment (HISTORY.md: owner lends), nothing reads it; goes with the next change to the region's words
     if (lane_id() == 0) s.ref_key[0] = -1;                          // a restarted chain meets the same block again with new neighbours
     region_open(r, T_LUMA_SPLIT, 0, cu, tu);
     for (int c = j; c < 4; c++) {
@@ -2499,48 +2414,11 @@ template <int LOG2> DEVN DistCbf spec_children(KR k, const Cu cu_, const Tu tu_)
       PROF_MARK0();
       constexpr int SAVE_WORDS = (int)(offsetof(RdSmem, line) / 8);
       static_assert(offsetof(RdSmem, line) % 8 == 0 && offsetof(RdSmem, line) <= SAVE_BYTES, "state save area");
-      int mine = 0;                                                   // split tasks of this chain run by this wave itself
       while (lds_load(&r.done) < 4 - j) {
         const int idx = region_claim(r);
         if (idx < 0) {
-#if HEVCDL_OWNER_LENDS
-          // Every split task is taken and this wave would only wait (8.9 % of all wave time on the 600-frame job): it lends itself to the workgroup's masters -- one task
-          // of a first-pass / chroma / rough-mode region at a time, its own state parked in its workspace meanwhile, exactly as for a split task of its own.  Not before
-          // the waves that took its split tasks have copied its context (helper_step counts the copies in dist[11] of the region).
-          const int taken = (int)(lds_load(&r.ticket) & 0xffff) - mine;
-          if (lds_load((LDS int *)&r.dist[11]) >= taken) {
-            LDS WgShared &sh = wg_shared();
-            const int me = wave_id();
-            int ran = 0;
-            for (int q = 1; q < NW && !ran; q++) {
-              LRegion &fr = sh.reg[(me + q) % NW][0];
-              const int t = lds_load(&fr.ticket);
-              if ((t & 0xffff) >= (int)((unsigned)t >> 16)) continue;
-              const int fk = uni(fr.kind);
-              if (fk != T_LUMA_P1 && fk != T_CHROMA && fk != T_RMD) continue;
-              const int fi = region_claim(fr);
-              if (fi < 0) continue;
-              wsync();
-              for (int i = lane_id(); i < SAVE_WORDS; i += 64) s.my_save[i] = ((LDS const unsigned long long *)&s)[i];
-              wg_acquire();
-              import_owner(uni(fr.owner));
-              run_task<true>(fr, fi);
-              wg_release();
-              lds_add(&fr.done, 1);
-              wsync();
-              for (int i = lane_id(); i < SAVE_WORDS; i += 64) ((LDS unsigned long long *)&s)[i] = s.my_save[i];
-              wsync();
-              if (lane_id() < 3) s.ref_key[lane_id()] = -1;
-              if (lane_id() == 0) s.fline_key = -1;
-              wsync();
-              ran = 1;
-            }
-            if (ran) continue;
-          }
-#endif
           __builtin_amdgcn_s_sleep(2); continue;
         }
-        mine++;
         wsync();
         { PROF_GLUE_T0(); for (int i = lane_id(); i < SAVE_WORDS; i += 64) s.my_save[i] = ((LDS const unsigned long long *)&s)[i]; wsync(); PROF_GLUE(4); }
         run_task<true>(r, idx);
@@ -2726,7 +2604,7 @@ DEVN void rmd_satd(KR k, const Cu cu_, const Tu ptu_)
   if (lane_id() < 36) s.satd[lane_id()] = 0;
   const int dcv = dc_value(k, s.line, pn);
   wsync();
-  if (nrounds >= HEVCDL_RMD_SLICE_ROUNDS && lds_load(&wg_shared().masters_active) < NW) {
+  if (nrounds >= RMD_SLICE_ROUNDS && lds_load(&wg_shared().masters_active) < NW) {
     // 16x16 PUs and larger (3 / 9 / 35 rounds) with waves without a unit in the workgroup: the rounds are dealt to them in up to NW slices
     LRegion &r = my_region();
     const int ntasks = nrounds < NW ? nrounds : NW;
@@ -2777,7 +2655,7 @@ DEVN void rmd_prefetch(KR k, int x_, int y_, int log2_, int sliced_ = 0)
   const int x = uni(x_), y = uni(y_), log2 = uni(log2_), pn = 1 << log2, sliced = uni(sliced_);
   LSmem &s = lds();
   const int nbx = pn / 8, nrounds = (35 * nbx * nbx + 63) >> 6;
-  if (sliced == 2 && nrounds >= HEVCDL_RMD_SLICE_ROUNDS) { // open only: every slice gathers the PU's reference lines itself (rmd_prefetch_end gathers this wave's)
+  if (sliced == 2 && nrounds >= RMD_SLICE_ROUNDS) { // open only: every slice gathers the PU's reference lines itself (rmd_prefetch_end gathers this wave's)
     LRegion &r = my_region();
     const int ntasks = nrounds < NW ? nrounds : NW;
     const Cu ncu = { x, y, log2, 6 - log2, 0, 1 << (2 * (log2 - 2)), SIZE_2Nx2N }; const Tu ptu = { x, y, log2, 0, 0, 1 << (2 * (log2 - 2)) };
@@ -2792,7 +2670,7 @@ DEVN void rmd_prefetch(KR k, int x_, int y_, int log2_, int sliced_ = 0)
   if (lane_id() < 36) s.satd_pre[NPEND >= 2 ? lane_id() : 0] = 0;
   const int dcv = dc_value(k, s.line, pn);
   wsync();
-  if (sliced && nrounds >= HEVCDL_RMD_SLICE_ROUNDS) { // the workgroup's other waves are free (the caller's ticket region too): the rounds in slices, as rmd_satd deals them
+  if (sliced && nrounds >= RMD_SLICE_ROUNDS) { // the workgroup's other waves are free (the caller's ticket region too): the rounds in slices, as rmd_satd deals them
     LRegion &r = my_region();
     const int ntasks = nrounds < NW ? nrounds : NW;
     const Cu ncu = { x, y, log2, 6 - log2, 0, 1 << (2 * (log2 - 2)), SIZE_2Nx2N }; const Tu ptu = { x, y, log2, 0, 0, 1 << (2 * (log2 - 2)) };
@@ -2904,9 +2782,6 @@ template <bool TRACE> DEV int rmd_candidates(KR k, int x, int y, int pu_log2, un
 // coded ahead of time starts from a guess, and its bit count is corrected when the real value is known (est_intra_luma): bits = (f0 + S) >> 15 with S the candidate's
 // own sum, which is in the end state it stored.  Candidate LIST: rough-mode costs with the guessed f0; if the real f0 gives another list, or any luma-side context
 // differs after all, the work is dropped.  Claims end when the chroma search does (the master's context is quiet only while it sits in region_run).
-#ifndef HEVCDL_AHEAD_MAX
-#define HEVCDL_AHEAD_MAX 1                      // measured: with two or three masters per workgroup the candidates coded ahead only take waves from work that is needed now (600 frames: 6.45 -> 6.70 s at 3)
-#endif
 // xaddr >= 0: the PU is the first CU of the NEXT CTU (address xaddr, column / row xcx / xcy), opened while this CTU is finished (process_unit): the candidates then take
 // over a context that names that CTU and attribute arrays as initCtu leaves them (this wave's own stay untouched: the CTU may still be walked again).
 DEVN void ahead_open(KR k, const Cu cu_, int nx_, int ny_, int nl_, int xaddr_ = -1, int xcx_ = 0, int xcy_ = 0)
@@ -3055,7 +2930,6 @@ DEVN uint32_t est_intra_luma(KR k, const Cu cu_)
         wsync();
         wg_release();
         if (lane_id() == 0) __hip_atomic_store(&r.ticket, (nfull << 16) | c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (nfull > c) ring_bell();
         region_run(k, r);
         // the bit counts of the candidates coded ahead, from the fractional bits the CU really starts with
         const unsigned long long f0t = s.curr[cu.depth].frac & 32767ull, f0s = (unsigned long long)s.ahead_f0;
@@ -3085,8 +2959,8 @@ DEVN uint32_t est_intra_luma(KR k, const Cu cu_)
         // Launches of few units: the chain that bounds a frame is luma only -- this CU's winner -> rough modes of the next PU -> its candidates.  The winner's samples
         // sit in its result slot: the SATD rounds of the next PU are handed to the idle waves NOW, reading them there (srect / ssrc), while this wave copies the
         // winner's levels, samples and arrays (the slot is not written again before the rounds are collected: est_intra_chroma, ahead_open)
-        if (win < SLOT_CHROMA && npu == 1 && pu_log2 <= 5 && pu_log2 > min_tu_log2(cu) && lds_load(&wg_shared().remote) && HEVCDL_PREFETCH && NPEND >= 2 && cu.depth < 3      // (slots from SLOT_CHROMA on take this CU's chroma modes)
-            && lds_load(&wg_shared().masters_active) <= HEVCDL_PREFETCH_MAX) {
+        if (win < SLOT_CHROMA && npu == 1 && pu_log2 <= 5 && pu_log2 > min_tu_log2(cu) && lds_load(&wg_shared().remote) && NPEND >= 2 && cu.depth < 3      // (slots from SLOT_CHROMA on take this CU's chroma modes)
+            && lds_load(&wg_shared().masters_active) <= PREFETCH_MAX) {
           int nx, ny, nl;
           if (next_leaf(k, cu, nx, ny, nl) && nl >= 4 && nl <= 5) {
             if (uni(s.pend_n) == NPEND) { pend_join_oldest(k, 0); if (uni(s.restart)) return 0; }   // the ticket region (= slot set, = srect entry) the second pass below will take
@@ -3144,7 +3018,7 @@ DEVN uint32_t est_intra_luma(KR k, const Cu cu_)
         LRegion &r2 = my_region(reg);
         wsync();
         if (lane_id() == 0) { r2.modes[0] = (int)best_mode; r2.modes[1] = reg - 1; r2.cost[4] = best_cost; r2.dist[4] = best_dist; s.p2_pending = reg; }
-        if (lds_load(&wg_shared().remote) && HEVCDL_PREFETCH && NPEND >= 2 && cu.depth < 3 && lds_load(&wg_shared().masters_active) <= HEVCDL_PREFETCH_MAX) {
+        if (lds_load(&wg_shared().remote) && NPEND >= 2 && cu.depth < 3 && lds_load(&wg_shared().masters_active) <= PREFETCH_MAX) {
           // The chain that bounds a frame in this form is luma only: this CU's winner -> rough modes of the next PU -> its candidates.  The winner's samples
           // are in best_rec now: mark the CU as the pending pass's (readers take best_rec; check_rd_cost_intra writes the same word again) and hand the SATD
           // rounds of the next PU to the idle waves BEFORE the pass and the chroma modes are posted (est_intra_chroma collects them)
@@ -3164,7 +3038,7 @@ DEVN uint32_t est_intra_luma(KR k, const Cu cu_)
         const int rm = lds_load(&wg_shared().remote);
         // (very few units: the CU's five chroma modes are posted in the same breath -- everything a chroma mode reads is settled once the luma winner is imported, and
         //  posting here instead of in est_intra_chroma brings their answers, which the walk waits for, ~15 k cycles forward and saves a release of its own)
-        if (rm && (rm != 3 || remote_room())) remote_post(k, cu, ptu, reg, (int)best_mode, best_cost, best_dist, cu.part == SIZE_2Nx2N && (rm == 2 || (rm == 1 && HEVCDL_CHROMA_ROOM > 0 && remote_room(HEVCDL_CHROMA_ROOM))));    // a workgroup without a unit runs it (few units in the launch)
+        if (rm && (rm != 3 || remote_room())) remote_post(k, cu, ptu, reg, (int)best_mode, best_cost, best_dist, cu.part == SIZE_2Nx2N && rm == 2);    // a workgroup without a unit runs it (few units in the launch)
         else region_open(r2, T_LUMA_P2, 1, cu, ptu);
         TL(35, 0);
         break;
@@ -3211,7 +3085,6 @@ DEVN uint32_t est_intra_luma(KR k, const Cu cu_)
 // TS3: the copy for 8x8 luma TUs that tries transform skip on their 4x4 chroma blocks (TransformSkipFast 0 only: the usual copy stays without that code)
 template <int LOG2, bool TS3 = false> DEVN uint32_t recur_chroma(KR k, const Cu cu_, const Tu tu_)
 {
-  CHECK_EXEC(7);
   if constexpr (LOG2 == 3 && !TS3) { if ((tools_of(k) & (int)(HEVCDL_TOOL_TSKIP | HEVCDL_TOOL_TSKIP_FAST)) == (int)HEVCDL_TOOL_TSKIP) return recur_chroma<3, true>(k, cu_, tu_); }
   uint32_t dist_sum = 0;
   const Cu cu = ucu(cu_); const Tu tu = utu(tu_);
@@ -3278,7 +3151,7 @@ template <int LOG2, bool TS3 = false> DEVN uint32_t recur_chroma(KR k, const Cu 
 // regions: open / claim / run / answer
 // ---------------------------------------------------------------------------------------------------
 DEVN void region_open(LRegion &r, int kind_, int n_, const Cu cu_, const Tu tu_)
-{ CHECK_EXEC(12); // r.modes[] already written by the caller
+{ // r.modes[] already written by the caller
   const Cu cu = ucu(cu_); const Tu tu = utu(tu_); const int kind = uni(kind_), n = uni(n_);
   wsync();
   if (lane_id() == 0) {
@@ -3289,7 +3162,6 @@ DEVN void region_open(LRegion &r, int kind_, int n_, const Cu cu_, const Tu tu_)
   wsync();
   wg_release();                                              // the master's arrays, snapshots and picture writes before the ticket
   if (lane_id() == 0) __hip_atomic_store(&r.ticket, n << 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  if (n > 0) ring_bell();
 }
 
 // a helper takes over the master's view of the CTU: kernel context + attribute arrays (the coder snapshot a task starts from is
@@ -3329,7 +3201,6 @@ DEV void import_ahead(int owner)
 // one alternative, on the executing wave's private state; levels / reconstruction go to the result slot, trial samples to the overlay
 template <bool LEAF> DEV void run_task_body(LRegion &r, int idx_)
 { // LEAF: the instance a chain owner uses for its own split tasks (spec_children): every kind but the second-pass task, no nested regions
-  CHECK_EXEC(3);
   const int idx = uni(idx_);
   PROF_T0();
   LSmem &s = lds(); LDS K &kk = s.k; KR k = s.k;
@@ -3392,11 +3263,7 @@ template <bool LEAF> DEV void run_task_body(LRegion &r, int idx_)
     wsync();
     state_from_global(&s.go, slot_state(kk.slots, slot, 0));    // the master's [depth][CI_CURR_BEST] snapshot as it was when the pass was handed over
     DistCost dc = { 0, 0.0, 0 };
-#ifdef HEVCDL_XP2
-    dc.cost = MAX_DOUBLE;                                       // timing experiment: the second pass costs nothing (as if another workgroup ran it)
-#else
     if constexpr (!LEAF) dc = recur_luma_any<true>(k, cu, tu, 0, 1, memo_dist, memo_cost);
-#endif
     dist = memo_dist; cost = memo_cost;
     if (ub(dc.cost < memo_cost)) { // the split wins: levels -> record, reconstruction -> the master's best, arrays -> the verdict slot
       dist = dc.dist; cost = dc.cost;
@@ -3555,16 +3422,12 @@ DEVN int region_claim(LRegion &r)
   return uni(res);
 }
 DEVN void region_run(KR k, LRegion &r)
-{ CHECK_EXEC(4); // the master works on its own region, then waits for the helpers' last tasks
+{ // the master works on its own region, then waits for the helpers' last tasks
   const int n = (int)((unsigned)lds_load(&r.ticket) >> 16);
   for (;;) {
     const int idx = region_claim(r);
     if (idx < 0) break;
-#ifdef HEVCDL_RR_INLINE
-    run_task_body<false>(r, idx);          // inside this function's frame: its registers are saved once per region, not once per task
-#else
     run_task<false>(r, idx);
-#endif
     wg_release();
     lds_add(&r.done, 1);
   }
@@ -3580,14 +3443,10 @@ DEV int helper_step()
     int did = 0;
     // the second-pass regions first when they sit on the masters' critical paths; behind the masters' own regions when the passes are left pending
     // (compress_cu): then it is the first pass and the chroma search the master waits for
-    const int p2_first = lds_load(&sh.masters_active) > HEVCDL_FG_FIRST_MAX;
+    const int p2_first = lds_load(&sh.masters_active) > FG_FIRST_MAX;
     for (int j = 0; j < NREG * NW && !did; j++) {
       const int b = j / NW;             // block of the scan: one region index of every wave; the look-ahead comes right behind the masters' own regions, or last
-      #ifdef HEVCDL_AHEAD_LAST
-      const int ri = p2_first ? (b < NPEND ? 1 + b : (b == NPEND ? 0 : REG_AHEAD)) : b;
-#else
       const int ri = p2_first ? (b < NPEND ? 1 + b : (b == NPEND ? 0 : REG_AHEAD)) : (b == 0 ? 0 : (AHEAD ? (b == 1 ? REG_AHEAD : b - 1) : b));
-#endif
       LRegion &r = sh.reg[(me + 1 + (j % NW)) % NW][ri];
       const int t = lds_load(&r.ticket);
       if ((t & 0xffff) >= (int)((unsigned)t >> 16)) continue;
@@ -3595,7 +3454,7 @@ DEV int helper_step()
       if (idx < 0) continue;
       wg_acquire();
       { PROF_T0(); if (AHEAD && uni(r.kind) == T_LUMA_AHEAD && idx < uni(r.pad_)) import_ahead(uni(r.owner)); else import_owner(uni(r.owner)); PROF_ADD(0, 53); }
-      if (uni(r.kind) == T_LUMA_SPLIT) lds_add((LDS int *)&r.dist[11], 1);          // the chain owner's context has been copied: it may lend its wave to other masters now (spec_children)
+      if (uni(r.kind) == T_LUMA_SPLIT) lds_add((LDS int *)&r.dist[11], 1);          // the chain owner's context has been copied (nothing reads the count: see spec_children)
       run_task_body<false>(r, idx);
       wg_release();
       lds_add(&r.done, 1);
@@ -3608,7 +3467,6 @@ DEV int helper_step()
 // estIntraPredChromaQT TEncSearch.cpp:2588-2737 (4:2:0: one chroma PU per CU)
 DEVN uint32_t est_intra_chroma(KR k, const Cu cu_)
 {
-  CHECK_EXEC(6);
   PROF_T0();
   const Cu cu = ucu(cu_);
   LSmem &s = lds();
@@ -3627,7 +3485,7 @@ DEVN uint32_t est_intra_chroma(KR k, const Cu cu_)
     wsync();
     const bool rich = lds_load(&wg_shared().remote) != 0;    // waves to spare: the second passes run on other CUs
     auto look_ahead = [&](int sliced) {
-      if (HEVCDL_PREFETCH && NPEND >= 2 && cu.depth < 3 && lds_load(&wg_shared().masters_active) <= HEVCDL_PREFETCH_MAX) { // the other waves have the chroma modes: the master looks ahead
+      if (NPEND >= 2 && cu.depth < 3 && lds_load(&wg_shared().masters_active) <= PREFETCH_MAX) { // the other waves have the chroma modes: the master looks ahead
         // (not from an 8x8 CU: its 2Nx2N / NxN choice is still open, so is the reconstruction the next CU will see)
         int nx, ny, nl;
         if (next_leaf(k, cu, nx, ny, nl) && nl >= 4 && nl <= 5) {
@@ -3637,7 +3495,7 @@ DEVN uint32_t est_intra_chroma(KR k, const Cu cu_)
           if (lane_id() == 0) PROF_ACC_(18, (unsigned long long)((uni(s.lw_valid) ? 0 : 1) + (uni(s.a[A_TRIDX][cu.zbase]) == 0 ? 0 : 2) + (uni(s.ahead_open) ? 4 : 0) + (spare_waves() ? 0 : 8)) << 10);
 #endif
           if (AHEAD && uni(s.lw_valid) && cu.part == SIZE_2Nx2N && uni(s.a[A_TRIDX][cu.zbase]) == 0 && !uni(s.ahead_open) && spare_waves()
-              && lds_load(&wg_shared().masters_active) <= HEVCDL_AHEAD_MAX) ahead_open(k, cu, nx, ny, nl);
+              && lds_load(&wg_shared().masters_active) <= AHEAD_MAX) ahead_open(k, cu, nx, ny, nl);
         }
       }
     };
@@ -3648,7 +3506,7 @@ DEVN uint32_t est_intra_chroma(KR k, const Cu cu_)
     // (with more units the chroma modes go to other workgroups only while enough of them have nothing to do: est_intra_luma decided and posted them already)
     const bool cremote = lds_load(&wg_shared().remote) == 2 || uni(s.chroma_key) == ((cu.log2 << 24) | (cu.y << 12) | cu.x);
     int anx = 0, any = 0, anl = 0;
-    const bool la = rich && HEVCDL_PREFETCH && NPEND >= 2 && cu.depth < 3 && lds_load(&wg_shared().masters_active) <= HEVCDL_PREFETCH_MAX && next_leaf(k, cu, anx, any, anl) && anl >= 4 && anl <= 5;
+    const bool la = rich && NPEND >= 2 && cu.depth < 3 && lds_load(&wg_shared().masters_active) <= PREFETCH_MAX && next_leaf(k, cu, anx, any, anl) && anl >= 4 && anl <= 5;
     if (uni(s.pre_open) && (!la || uni(s.pre_open) != ((anl << 24) | (any << 12) | anx))) { region_run(k, r); if (lane_id() == 0) s.pre_open = 0; wsync(); }   // (slices opened for another PU: cannot happen by construction)
     if (la && !uni(s.pre_open)) rmd_prefetch(k, anx, any, anl, 2);               // reference lines of the next PU, its SATD rounds handed to the idle waves (est_intra_luma may have done it already) ...
     const bool posted = cremote && uni(s.chroma_key) == ((cu.log2 << 24) | (cu.y << 12) | cu.x);     // together with the second pass (remote_post)
@@ -3661,7 +3519,7 @@ DEVN uint32_t est_intra_chroma(KR k, const Cu cu_)
       if (lane_id() == 0) s.pre_open = 0;
       TL(7, 0);
       if (AHEAD && uni(s.lw_valid) && cu.part == SIZE_2Nx2N && uni(s.a[A_TRIDX][cu.zbase]) == 0 && !uni(s.ahead_open) && spare_waves()
-          && lds_load(&wg_shared().masters_active) <= HEVCDL_AHEAD_MAX) ahead_open(k, cu, anx, any, anl);
+          && lds_load(&wg_shared().masters_active) <= AHEAD_MAX) ahead_open(k, cu, anx, any, anl);
     }
     TL(8, uni(s.ahead_open));
     // with waves to spare the two components of a mode are tasks of their own
@@ -3756,7 +3614,6 @@ DEVN void enc_cu_syntax_fast(KR k, LCabac *c, const Cu cu_, GLB const unsigned l
 // xCheckRDCostIntra TEncCu.cpp:1600-1665; the end state of the CU syntax is left in s->temp[depth]
 DEVN Rd check_rd_cost_intra(KR k, const Cu cu_, int part_, int known_reg_ = 0)
 { // known_reg: the CU's luma search has been done -- by the second pass that was left pending in that ticket region and chose the split (compress_cu)
-  CHECK_EXEC(8);
   LSmem &s = lds();
   const int part = uni(part_);
   Cu cu = ucu(cu_); cu.part = part;
@@ -3909,7 +3766,7 @@ template <int DEPTH> DEVN Rd compress_cu(KR k, int x_, int y_)
           if (lds_load(&rp0.done) < 1) break;
           pend_join_oldest(k, 2); if (uni(s.restart)) return best;
         }
-        const int carry_ok = NPEND > 0 && DEPTH >= 1 && DEPTH <= 2 && li != uni(s.nocarry_leaf) && lds_load(&wg_shared().masters_active) <= HEVCDL_CARRY_MAX;
+        const int carry_ok = NPEND > 0 && DEPTH >= 1 && DEPTH <= 2 && li != uni(s.nocarry_leaf) && lds_load(&wg_shared().masters_active) <= CARRY_MAX;
         wsync();
         if (lane_id() == 0) s.carry_ok = carry_ok;
         wsync();
@@ -4049,9 +3906,6 @@ DEVN void advance_state(KR k, LCabac *truec, int x0_, int y0_)
 // master therefore offers its unit to the next workgroup of the ring at a CTU boundary whenever that one currently walks fewer units: the
 // whole state of a unit between two CTUs is its position and the coder state (168 B) -- records and reconstruction are in HBM.  The surplus
 // units keep travelling round the ring, every workgroup is crowded for the same share of the time, and so is every frame.
-#ifndef HEVCDL_HOP
-#define HEVCDL_HOP 4
-#endif
 struct Mbox { int state, unit, next_i, pad_; unsigned long long cabac[21]; };     // state: 0 empty, 2 being filled, 1 full, 3 being taken
 DEV GLB int *sched_finished(const hevcdl_rd_params &p) { return (GLB int *)p.sched; }
 DEV GLB int *sched_count(const hevcdl_rd_params &p, int g) { return (GLB int *)p.sched + 16 + g; }
@@ -4369,7 +4223,7 @@ DEV int process_unit(const hevcdl_rd_params &p, int unit, int i_resume)
   const int i_begin = wpp ? (wrow0 * tw > p.ctu_begin ? wrow0 * tw : p.ctu_begin) : (i_resume >= 0 ? i_resume : (ntiles == 1 ? p.ctu_begin : 0));
   const int i_end = wpp ? ((wrow0 + wrows) * tw < p.ctu_end ? (wrow0 + wrows) * tw : p.ctu_end) : (ntiles == 1 ? p.ctu_end : tw * (cy1 - cy0));
   for (int i = i_begin; i < i_end; i++) {
-    if (p.migrate && i > i_begin && ((i - i_begin) & (HEVCDL_HOP - 1)) == 0) { // every HEVCDL_HOP CTUs: does the next workgroup of the ring walk fewer units than this one?
+    if (p.migrate && i > i_begin && ((i - i_begin) & (HOP - 1)) == 0) { // every HOP CTUs: does the next workgroup of the ring walk fewer units than this one?
       const int g = (int)blockIdx.x, ng = (g + 1) % (int)gridDim.x;
       if (lds_load(&wg_shared().masters_active) > glb_load(sched_count(p, ng)) && glb_cas(&sched_mbox(p, ng)->state, 0, 2)) {
         GLB Mbox *mb = sched_mbox(p, ng);
@@ -4436,9 +4290,9 @@ DEV int process_unit(const hevcdl_rd_params &p, int unit, int i_resume)
       // rough-mode sums, then its first-pass candidates.  Nothing of this CTU is touched (the candidates get a context of their own naming the next CTU, ahead_open);
       // what they assume is checked when the CU is reached (est_intra_luma), and a restart of this CTU drops them like any other look-ahead.
       // (WaveFrontSynchro: the next CTU's first CU reads the row above one CTU further to the right -- only when that is known to be finished already, never into a row start)
-      if (AHEAD && HEVCDL_PREFETCH && NPEND >= 2 && !p.migrate && !uni(s.restart) && uni(s.pend_n) && i + 1 < i_end && uni(s.lw_valid) && !uni(s.ahead_open) && !uni(s.pre_open) &&
+      if (AHEAD && NPEND >= 2 && !p.migrate && !uni(s.restart) && uni(s.pend_n) && i + 1 < i_end && uni(s.lw_valid) && !uni(s.ahead_open) && !uni(s.pre_open) &&
           (!wpp || (cx + 1 < tw && (cy == 0 || wpp == 2 || wpp_seen >= (cx + 3 < tw ? cx + 3 : tw)))) &&
-          lds_load(&wg_shared().masters_active) <= HEVCDL_AHEAD_MAX && spare_waves()) {
+          lds_load(&wg_shared().masters_active) <= AHEAD_MAX && spare_waves()) {
         const int ni = i + 1, ncx = cx0 + ni % tw, ncy = cy0 + ni / tw, na = ncy * p.ctus_x + ncx;
         int nx = 0, ny = 0, nl = 0;
         if (ctu_first_leaf(k, na, ncx, ncy, nx, ny, nl) && nl >= 4 && nl <= 5) {
@@ -4598,7 +4452,6 @@ void RD_SYM(hevcdl_rd_frame_kernel)(hevcdl_rd_params p)
   __syncthreads();
   if (p.remote && (int)blockIdx.x >= p.master_groups) { // a workgroup without units: wave 0 takes second passes other workgroups post, the other waves serve its regions
     if (wave == 0 && lane == 0) __hip_atomic_fetch_add(rq_idle((GLB unsigned char *)p.sched), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    int seen = -1;
     for (;;) {
       if (wave == 0) {
         if (glb_load(sched_finished(p)) >= n_units) { wsync(); if (lane == 0) __hip_atomic_store(&sh.quit, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); break; }
@@ -4607,16 +4460,14 @@ void RD_SYM(hevcdl_rd_frame_kernel)(hevcdl_rd_params p)
         if (!remote_serve((GLB unsigned char *)p.sched)) { __builtin_amdgcn_s_sleep(127); __builtin_amdgcn_s_sleep(127); }
       } else {
         if (lds_load(&sh.quit)) break;
-        const int b = lds_load(&sh.bell);                       // (see ring_bell: the tickets are walked only when tasks were put up since the last walk that found none)
-        if (HELPER_BELL && b == seen) { __builtin_amdgcn_s_sleep(HEVCDL_IDLE_SLEEP); continue; }
-        if (!helper_step()) { seen = b; __builtin_amdgcn_s_sleep(HELPER_BELL ? HEVCDL_IDLE_SLEEP : 32); }
+        lds_load(&sh.bell);                       // left over from the retired doorbell (HISTORY.md); nothing writes the word after kernel start.  Goes with the next change to the idle loops
+        if (!helper_step()) __builtin_amdgcn_s_sleep(32);
       }
     }
     return;
   }
   // a wave walks a unit (master) or serves the workgroup's regions (helper); with p.migrate units arrive and leave through the mailboxes
   int unit = first < n_units ? first : -1, i_resume = -1;
-  int seen = -1, since_check = 0;          // seen: the doorbell's count when this wave last walked the tickets and found no task (ring_bell)
   bool can_claim = dyn && (int)blockIdx.x < p.master_groups && wave < p.wpp_masters;
   for (;;) {
     if (can_claim && unit < 0) {
@@ -4626,13 +4477,7 @@ void RD_SYM(hevcdl_rd_frame_kernel)(hevcdl_rd_params p)
     }
     if (unit >= 0) {
       PROF_T0();
-#ifdef HEVCDL_MASTER_PRIO
-      __builtin_amdgcn_s_setprio(HEVCDL_MASTER_PRIO);          // experiment: the wave that walks a unit wins the issue arbitration of its SIMD against the wave it shares it with
-#endif
       const int moved = process_unit(p, unit, i_resume);
-#ifdef HEVCDL_MASTER_PRIO
-      __builtin_amdgcn_s_setprio(0);
-#endif
       PROF_ADD(0, 31);
       int next = -1;
       if (dyn) { if (p.remote) glb_add(sched_finished(p), 1); unit = -1; i_resume = -1; continue; }      // (the wave stays a claimer: masters_active counts it until every row has an owner)
@@ -4645,19 +4490,15 @@ void RD_SYM(hevcdl_rd_frame_kernel)(hevcdl_rd_params p)
       if (unit < 0) { wg_release(); lds_add(&sh.masters_active, -1); }
       continue;
     }
-    if (p.migrate) { // (two round trips to HBM: behind every task, and every fourth look of a wave that has none)
-      if (!HELPER_BELL || since_check <= 0) {
-        since_check = 4;
-        if (glb_load(sched_finished(p)) >= n_units) break;
-        GLB Mbox *mb = sched_mbox(p, (int)blockIdx.x);
-        if (glb_load(&mb->state) == 1 && glb_cas(&mb->state, 1, 3)) { // a unit handed over by the previous workgroup of the ring
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-          unit = uni(mb->unit); i_resume = uni(mb->next_i);
-          lds_add(&sh.masters_active, 1);
-          continue;
-        }
+    if (p.migrate) { // (two round trips to HBM at every look of a wave without a unit)
+      if (glb_load(sched_finished(p)) >= n_units) break;
+      GLB Mbox *mb = sched_mbox(p, (int)blockIdx.x);
+      if (glb_load(&mb->state) == 1 && glb_cas(&mb->state, 1, 3)) { // a unit handed over by the previous workgroup of the ring
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        unit = uni(mb->unit); i_resume = uni(mb->next_i);
+        lds_add(&sh.masters_active, 1);
+        continue;
       }
-      since_check--;
     } else if (lds_load(&sh.masters_active) <= 0) break;
     if (can_claim) { // nothing can start right now: serve the workgroup's regions if there are tasks, look again in a few microseconds (the ring's words are shared by every idle wave of the chip)
       PROF_T0();
@@ -4665,10 +4506,8 @@ void RD_SYM(hevcdl_rd_frame_kernel)(hevcdl_rd_params p)
       continue;
     }
     { PROF_T0();
-      const int b = lds_load(&sh.bell);
-      if (HELPER_BELL && b == seen) { __builtin_amdgcn_s_sleep(HEVCDL_IDLE_SLEEP); PROF_ADD(0, 23); }
-      else if (helper_step()) since_check = 0;
-      else { seen = b; __builtin_amdgcn_s_sleep(HELPER_BELL ? HEVCDL_IDLE_SLEEP : 32); PROF_ADD(0, 23); } }
+      lds_load(&sh.bell);                         // (the doorbell's left-over, as above)
+      if (!helper_step()) { __builtin_amdgcn_s_sleep(32); PROF_ADD(0, 23); } }
   }
 #ifdef HEVCDL_KERNEL_PROF
   // in-kernel timers of workgroup 0, summed over its waves (masters and helpers): the host decodes the accumulators (tools/phase_profile.py)
@@ -4732,11 +4571,7 @@ void hevcdl_micro_kernel(hevcdl_rd_params p, const int16_t *resi_, int n_blocks,
     unsigned long long t0 = __builtin_readcyclecounter();
     fwd_transform(k, n, !comp && n == 4);
     if (what != 2) t0 = __builtin_readcyclecounter();
-#if HEVCDL_RDOQ_FIX
-    const uint32_t as = n == 4 ? rdoq_wave<4>(k, &s.go, comp, n, mode, 1) : (n == 8 && HEVCDL_RDOQ_FIX >= 8 ? rdoq_wave<HEVCDL_RDOQ_FIX >= 8 ? 8 : 0>(k, &s.go, comp, n, mode, 1) : rdoq_wave<0>(k, &s.go, comp, n, mode, 1));
-#else
-    const uint32_t as = rdoq_wave(k, &s.go, comp, n, mode, 1);
-#endif
+    const uint32_t as = n == 4 ? rdoq_wave<4>(k, &s.go, comp, n, mode, 1) : (n == 8 ? rdoq_wave<8>(k, &s.go, comp, n, mode, 1) : rdoq_wave<0>(k, &s.go, comp, n, mode, 1));
     wsync();
     unsigned long long t1 = __builtin_readcyclecounter();
     if (what != 0) {

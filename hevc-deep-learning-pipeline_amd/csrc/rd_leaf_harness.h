@@ -46,18 +46,12 @@ DEV void leaf_setup(const hevcdl_rd_params &p)
   k.qp = p.k.qp; k.qp_c = p.k.qp_chroma; k.dbg = 0; k.dbgbuf = nullptr; k.tools = p.k.tools;
   wsync();
 }
-// the copy of rdoq_wave code_tu_block picks for the size (code_tu_block_n<NFIX> calls rdoq_wave<NFIX>, NFIX by HEVCDL_TU_FIX)
+// the copy of rdoq_wave code_tu_block picks for the size (code_tu_block_n<NFIX> calls rdoq_wave<NFIX>, NFIX = the size up to 16x16, 0 above)
 DEV uint32_t leaf_rdoq(KR k, const LCabac *cab, int comp, int n, int mode, int cbf_ctx)
 {
-#if HEVCDL_TU_FIX >= 4
   if (n == 4) return rdoq_wave<4>(k, cab, comp, n, mode, cbf_ctx);
-#endif
-#if HEVCDL_TU_FIX >= 8
   if (n == 8) return rdoq_wave<8>(k, cab, comp, n, mode, cbf_ctx);
-#endif
-#if HEVCDL_TU_FIX >= 16
   if (n == 16) return rdoq_wave<16>(k, cab, comp, n, mode, cbf_ctx);
-#endif
   return rdoq_wave<0>(k, cab, comp, n, mode, cbf_ctx);
 }
 } // namespace
