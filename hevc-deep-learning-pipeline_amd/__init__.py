@@ -23,7 +23,7 @@ LEAF_LIB_PATH = os.path.join(PKG_DIR, "lib", "libhevcdl_hip_leaf.so")        # -
 WEIGHTS_PATH = os.path.join(PKG_DIR, "weights", "hevc_encoder_model.f32")
 WEIGHT_FLOATS = 637712
 LEAF_SOURCES = ["rd_leaf.hip", "rd_leaf_bd10.hip", "rd_leaf_wide.hip", "rd_leaf_tools.hip"]      # the decision kernel's four builds, each with csrc/rd_leaf_harness.h behind it
-SOURCES = ["cnn_kernel.hip", "fc_kernel.hip", "rd_kernel.hip", "rd_kernel_bd10.hip", "rd_kernel_wide.hip", "rd_kernel_tools.hip", "deblock_kernel.hip", "sao_kernel.hip", "quality_kernel.hip", "report_kernel.hip", "entropy_kernel.hip", "hevcdl_api.hip", "hevcdl_bitstream.cpp"]
+SOURCES = ["cnn_kernel.hip", "fc_kernel.hip", "rd_kernel.hip", "rd_kernel_bd10.hip", "rd_kernel_wide.hip", "rd_kernel_tools.hip", "deblock_kernel.hip", "sao_kernel.hip", "quality_kernel.hip", "report_kernel.hip", "entropy_kernel.hip", "source_kernel.hip", "hevcdl_api.hip", "hevcdl_bitstream.cpp"]
 
 STATUS = {0: "OK", 1: "INVALID_ARG", 2: "UNSUPPORTED", 3: "NO_DEVICE", 4: "HIP", 5: "OOM"}
 
@@ -94,7 +94,13 @@ class StreamConfig(ctypes.Structure):
                 ("tile_columns", ctypes.c_int32), ("tile_rows", ctypes.c_int32), ("bit_depth", ctypes.c_int32),
                 ("tile_uniform_spacing", ctypes.c_int32), ("tile_column_width", ctypes.c_int32 * 19), ("tile_row_height", ctypes.c_int32 * 21),
                 ("lf_across_tiles", ctypes.c_int32), ("tools", ctypes.c_uint32), ("lf_beta_offset_div2", ctypes.c_int32), ("lf_tc_offset_div2", ctypes.c_int32),
-                ("rewrite_param_sets", ctypes.c_int32), ("wavefront", ctypes.c_int32)]
+                ("rewrite_param_sets", ctypes.c_int32), ("wavefront", ctypes.c_int32), ("conf_win_right", ctypes.c_int32), ("conf_win_bottom", ctypes.c_int32)]
+
+
+class SourceFormat(ctypes.Structure):
+    """hevcdl_source_format of include/hevcdl.h: what the caller's pictures look like when they are not in the context's own format."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("source_width", ctypes.c_int32), ("source_height", ctypes.c_int32),
+                ("input_bit_depth", ctypes.c_int32), ("output_bit_depth", ctypes.c_int32)]
 
 
 class Profile(ctypes.Structure):
@@ -267,6 +273,21 @@ def load_library():
     lib.hevcdl_get_report_info.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
     lib.hevcdl_picture_hash.argtypes = [ctypes.POINTER(StreamConfig), vp, ci, vp, ctypes.POINTER(ci)]
     lib.hevcdl_write_hash_sei.argtypes = [ci, vp, vp, ctypes.c_size_t, szp]
+    sfp = ctypes.POINTER(SourceFormat)
+    lib.hevcdl_source_format_default.argtypes = [sfp, ctypes.POINTER(Config)]
+    lib.hevcdl_padded_size.argtypes = [ci, ci, ci, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ci)]
+    lib.hevcdl_source_frame_bytes.argtypes = [sfp]
+    lib.hevcdl_source_frame_bytes.restype = ctypes.c_size_t
+    lib.hevcdl_output_frame_bytes.argtypes = [sfp]
+    lib.hevcdl_output_frame_bytes.restype = ctypes.c_size_t
+    lib.hevcdl_set_source_format.argtypes = [vp, sfp]
+    lib.hevcdl_load_source.argtypes = [vp, vp, ci, vp]
+    lib.hevcdl_load_source_dev.argtypes = [vp, vp, ci, vp, vp]
+    lib.hevcdl_store_output.argtypes = [vp, vp, ci, vp]
+    lib.hevcdl_store_output_dev.argtypes = [vp, vp, ci, vp, vp]
+    lib.hevcdl_get_output_frames.argtypes = [vp, ci, ci, vp]
+    lib.hevcdl_load_source_host.argtypes = [sfp, ci, ci, ci, vp, ci, vp]
+    lib.hevcdl_store_output_host.argtypes = [sfp, ci, ci, ci, vp, ci, vp]
     _lib = lib
     return lib
 
@@ -280,7 +301,9 @@ EXPORTS = ["hevcdl_config_default", "hevcdl_create", "hevcdl_destroy", "hevcdl_l
            "hevcdl_write_access_unit_from_slice_data", "hevcdl_slice_data_layout", "hevcdl_code_slice_data_host", "hevcdl_code_slice_data",
            "hevcdl_enable_device_entropy", "hevcdl_get_slice_data", "hevcdl_encode_pictures_stream", "hevcdl_set_entropy_capacity", "hevcdl_get_entropy_info",
            "hevcdl_picture_report", "hevcdl_picture_report_dev", "hevcdl_enable_picture_report", "hevcdl_get_picture_report", "hevcdl_plane_hash", "hevcdl_plane_hash_host",
-           "hevcdl_report_chunk_bytes", "hevcdl_get_report_info"]
+           "hevcdl_report_chunk_bytes", "hevcdl_get_report_info",
+           "hevcdl_source_format_default", "hevcdl_padded_size", "hevcdl_source_frame_bytes", "hevcdl_output_frame_bytes", "hevcdl_set_source_format",
+           "hevcdl_load_source", "hevcdl_load_source_dev", "hevcdl_store_output", "hevcdl_store_output_dev", "hevcdl_load_source_host", "hevcdl_store_output_host", "hevcdl_get_output_frames"]
 
 
 def picture_hash_sei(width, height, picture, bit_depth=8, method=1):
@@ -426,8 +449,8 @@ def default_config(width, height, qp, max_frames=1, device=0, cnn_input=0, tiles
 
 
 def stream_config(width, height, qp, level_idc=186, sao=False, tiles=(1, 1), bit_depth=8, lf_across_tiles=True, tools=TOOLS_REFERENCE, lf_offsets=(0, 0), lf_disable=False,
-                  rewrite_param_sets=True, wavefront=False):
-    """hevcdl_stream_config of include/hevcdl.h from keyword arguments."""
+                  rewrite_param_sets=True, wavefront=False, conf_win=(0, 0)):
+    """hevcdl_stream_config of include/hevcdl.h from keyword arguments.  conf_win: (right, bottom) padding in luma samples, the SPS's conformance window."""
     lib = load_library()
     cfg = StreamConfig()
     st = lib.hevcdl_stream_config_default(ctypes.byref(cfg), width, height, qp)
@@ -443,6 +466,7 @@ def stream_config(width, height, qp, level_idc=186, sao=False, tiles=(1, 1), bit
     cfg.rewrite_param_sets = 1 if rewrite_param_sets else 0
     cfg.wavefront = 1 if wavefront else 0      # a sub-stream per CTU row, entry points in the slice header
     cfg.sao_enabled = 1 if sao else 0
+    cfg.conf_win_right, cfg.conf_win_bottom = int(conf_win[0]), int(conf_win[1])
     return cfg
 
 
@@ -505,10 +529,10 @@ def write_access_unit_from_slice_data(cfg, poc, data, sizes):
 
 
 def write_access_unit(width, height, qp, poc, records, level_idc=186, sao=None, tiles=(1, 1), bit_depth=8, lf_across_tiles=True, tools=TOOLS_REFERENCE, lf_offsets=(0, 0), lf_disable=False,
-                      rewrite_param_sets=True, wavefront=False):
+                      rewrite_param_sets=True, wavefront=False, conf_win=(0, 0)):
     """Host-side bitstream writer (no GPU): VPS+SPS+PPS+slice NAL of one picture from its CTU records -> bytes."""
     lib = load_library()
-    cfg = stream_config(width, height, qp, level_idc, False, tiles, bit_depth, lf_across_tiles, tools, lf_offsets, lf_disable, rewrite_param_sets, wavefront)
+    cfg = stream_config(width, height, qp, level_idc, False, tiles, bit_depth, lf_across_tiles, tools, lf_offsets, lf_disable, rewrite_param_sets, wavefront, conf_win)
     sao_ptr = None
     if sao is not None:
         sao = np.ascontiguousarray(sao, SAO_DTYPE)
@@ -522,6 +546,53 @@ def write_access_unit(width, height, qp, poc, records, level_idc=186, sao=None, 
     if st != 0:
         raise HevcdlError(st, "write_access_unit")
     return buf[:n.value].tobytes()
+
+
+def _sample_dtype(bit_depth):
+    return np.uint8 if bit_depth <= 8 else np.dtype("<u2")
+
+
+def source_format(source_width, source_height, input_bit_depth=8, output_bit_depth=None):
+    """hevcdl_source_format: pictures of source_width x source_height at input_bit_depth; output frames at output_bit_depth (default: the input's)."""
+    fmt = SourceFormat()
+    fmt.struct_size = ctypes.sizeof(SourceFormat)
+    fmt.source_width, fmt.source_height, fmt.input_bit_depth = int(source_width), int(source_height), int(input_bit_depth)
+    fmt.output_bit_depth = int(input_bit_depth if output_bit_depth is None else output_bit_depth)
+    return fmt
+
+
+def padded_size(source_width, source_height, mode=1, pad_x=0, pad_y=0):
+    """The coded size of a source size under ConformanceWindowMode `mode` (hevcdl_padded_size, TAppEncCfg.cpp:1569-1617) -> (width, height)."""
+    lib = load_library()
+    w, h = ctypes.c_int(0), ctypes.c_int(0)
+    st = lib.hevcdl_padded_size(int(source_width), int(source_height), int(mode), int(pad_x), int(pad_y), ctypes.byref(w), ctypes.byref(h))
+    if st:
+        raise HevcdlError(st, "hevcdl_padded_size")
+    return w.value, h.value
+
+
+def load_source_host(fmt, coded_width, coded_height, internal_bit_depth, src):
+    """Source-format frames [n, source samples] -> coded-format frames [n, coded samples] on the CPU (hevcdl_load_source_host; no GPU needed)."""
+    lib = load_library()
+    ss = fmt.source_width * fmt.source_height * 3 // 2
+    src = np.ascontiguousarray(src, _sample_dtype(fmt.input_bit_depth)).reshape(-1, ss)
+    out = np.zeros((src.shape[0], coded_width * coded_height * 3 // 2), _sample_dtype(internal_bit_depth))
+    st = lib.hevcdl_load_source_host(ctypes.byref(fmt), int(coded_width), int(coded_height), int(internal_bit_depth), src.ctypes.data, src.shape[0], out.ctypes.data)
+    if st:
+        raise HevcdlError(st, "hevcdl_load_source_host")
+    return out
+
+
+def store_output_host(fmt, coded_width, coded_height, internal_bit_depth, pictures):
+    """Coded-format pictures [n, coded samples] -> output-format frames [n, window samples] on the CPU (hevcdl_store_output_host; no GPU needed)."""
+    lib = load_library()
+    cs = coded_width * coded_height * 3 // 2
+    pictures = np.ascontiguousarray(pictures, _sample_dtype(internal_bit_depth)).reshape(-1, cs)
+    out = np.zeros((pictures.shape[0], fmt.source_width * fmt.source_height * 3 // 2), _sample_dtype(fmt.output_bit_depth))
+    st = lib.hevcdl_store_output_host(ctypes.byref(fmt), int(coded_width), int(coded_height), int(internal_bit_depth), pictures.ctypes.data, pictures.shape[0], out.ctypes.data)
+    if st:
+        raise HevcdlError(st, "hevcdl_store_output_host")
+    return out
 
 
 class Encoder:
@@ -538,6 +609,7 @@ class Encoder:
         self.ctus = self.lib.hevcdl_ctus_per_frame(self.width, self.height)
         self.frame_bytes = self.lib.hevcdl_frame_bytes_bd(self.width, self.height, self.bit_depth)
         self.frame_samples = self.width * self.height * 3 // 2
+        self.source_format = None
         w = np.ascontiguousarray(load_weights() if weights is None else weights, dtype="<f4")
         self._h = ctypes.c_void_p()
         st = self.lib.hevcdl_create(ctypes.byref(self.cfg), w.ctypes.data, w.size, ctypes.byref(self._h))
@@ -559,6 +631,49 @@ class Encoder:
     def _frames(self, yuv):
         yuv = np.ascontiguousarray(yuv, self.sample_dtype).reshape(-1, self.frame_samples)
         return yuv, yuv.shape[0]
+
+    # ---- source pictures that are not in the context's own format (hevcdl_set_source_format) ----
+    def set_source_format(self, fmt):
+        """fmt: source_format(...) or None.  With a format set encode_pictures* take source-format frames ([n, source samples] at the input depth); what they return stays
+        coded format, and get_quality / get_picture_report / the stats' sse are taken over the window."""
+        self._check(self.lib.hevcdl_set_source_format(self._h, ctypes.byref(fmt) if fmt is not None else None))
+        self.source_format = fmt
+
+    def _input_frames(self, yuv):
+        """The picture pipeline's input: source-format frames with a source format set, the context's own otherwise."""
+        if self.source_format is None:
+            return self._frames(yuv)
+        f = self.source_format
+        yuv = np.ascontiguousarray(yuv, _sample_dtype(f.input_bit_depth)).reshape(-1, f.source_width * f.source_height * 3 // 2)
+        return yuv, yuv.shape[0]
+
+    def load_source(self, src):
+        """Source-format frames -> coded-format frames by the device kernel (hevcdl_load_source)."""
+        src, n = self._input_frames(src)
+        out = np.zeros((n, self.frame_samples), self.sample_dtype)
+        self._check(self.lib.hevcdl_load_source(self._h, src.ctypes.data, n, out.ctypes.data))
+        return out
+
+    def store_output(self, pictures):
+        """Coded-format pictures -> output-format frames (window size, output depth) by the device kernel (hevcdl_store_output)."""
+        pictures, n = self._frames(pictures)
+        f = self.source_format
+        out = np.zeros((n, f.source_width * f.source_height * 3 // 2), _sample_dtype(f.output_bit_depth))
+        self._check(self.lib.hevcdl_store_output(self._h, pictures.ctypes.data, n, out.ctypes.data))
+        return out
+
+    def get_output_frames(self, first, count):
+        """Output-format frames of pictures [first, first + count) of the last encode_pictures* call, cropped and scaled on the device (hevcdl_get_output_frames)."""
+        f = self.source_format
+        out = np.zeros((count, f.source_width * f.source_height * 3 // 2), _sample_dtype(f.output_bit_depth))
+        self._check(self.lib.hevcdl_get_output_frames(self._h, int(first), int(count), out.ctypes.data))
+        return out
+
+    def load_source_dev(self, d_src, n, d_coded, stream=None):
+        self._check(self.lib.hevcdl_load_source_dev(self._h, d_src, n, d_coded, stream))
+
+    def store_output_dev(self, d_pictures, n, d_out, stream=None):
+        self._check(self.lib.hevcdl_store_output_dev(self._h, d_pictures, n, d_out, stream))
 
     def predict_depth(self, yuv, want_logits=False):
         yuv, n = self._frames(yuv)
@@ -632,9 +747,9 @@ class Encoder:
     def encode_pictures(self, yuv, labels=None, deblock=True, sao=True):
         """Whole picture pipeline in one call (the pictures stay in HBM between the stages) -> (records [n, ctus], output pictures [n, samples],
         SAO parameters [n, ctus, 3] or None, stats [n])."""
-        yuv, n = self._frames(yuv)
+        yuv, n = self._input_frames(yuv)
         recs = np.zeros((n, self.ctus), REC_DTYPE)
-        out = np.zeros_like(yuv)
+        out = np.zeros((n, self.frame_samples), self.sample_dtype)
         stats = np.zeros(n, STATS_DTYPE)
         params = np.zeros((n, self.ctus, 3), SAO_DTYPE) if sao else None
         lab_ptr = None
@@ -650,7 +765,7 @@ class Encoder:
         (first, records [count, ctus], pictures [count, samples], SAO parameters or None, stats [count]) copies, one per chunk.
         on_chunk_hook(first, count) is called inside the library's chunk callback, after the chunk has been copied: what is valid there (get_slice_data with the
         device entropy switch on, get_quality) can be read from it."""
-        yuv, n = self._frames(yuv)
+        yuv, n = self._input_frames(yuv)
         lab_ptr = None
         if labels is not None:
             labels = np.ascontiguousarray(labels, np.uint8).reshape(n, self.ctus, 16)
@@ -663,7 +778,7 @@ class Encoder:
             return np.frombuffer(ctypes.string_at(ptr, nbytes), dtype).reshape(shape).copy()
 
         def on_chunk(_user, first, count, recs, pics, sao_p, stats):
-            chunks.append((first, view(recs, REC_DTYPE, (count, self.ctus)), view(pics, yuv.dtype, (count, yuv.shape[1])),
+            chunks.append((first, view(recs, REC_DTYPE, (count, self.ctus)), view(pics, self.sample_dtype, (count, self.frame_samples)),
                            view(sao_p, SAO_DTYPE, (count, self.ctus, 3)) if sao_p else None, view(stats, STATS_DTYPE, (count,))))
             if on_chunk_hook is not None:
                 try:
@@ -832,7 +947,7 @@ class Encoder:
     def encode_pictures_stream(self, yuv, labels=None, deblock=True, sao=True, want_pictures=False, want_records=False, chunk_frames=0, on_chunk_hook=None):
         """hevcdl_encode_pictures_stream: a list of (first, slice data per picture [count] bytes, sizes [count, n], stats [count], pictures or None, records or None), one per chunk.
         on_chunk_hook(first, count): called inside the library's callback (get_picture_report is valid there)."""
-        yuv, n = self._frames(yuv)
+        yuv, n = self._input_frames(yuv)
         lab_ptr = None
         if labels is not None:
             labels = np.ascontiguousarray(labels, np.uint8).reshape(n, self.ctus, 16)
@@ -849,7 +964,7 @@ class Encoder:
             blob = ctypes.string_at(data, int(per.sum())) if per.sum() else b""
             ends = np.cumsum(per)
             chunks.append((first, [blob[int(e - t):int(e)] for e, t in zip(ends, per)], sz, view(stats, STATS_DTYPE, (count,)),
-                           view(pics, yuv.dtype, (count, yuv.shape[1])) if pics else None, view(recs, REC_DTYPE, (count, self.ctus)) if recs else None))
+                           view(pics, self.sample_dtype, (count, self.frame_samples)) if pics else None, view(recs, REC_DTYPE, (count, self.ctus)) if recs else None))
             if on_chunk_hook is not None:
                 try:
                     on_chunk_hook(first, count)

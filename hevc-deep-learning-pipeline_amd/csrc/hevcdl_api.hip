@@ -9,6 +9,7 @@
 #include "hevcdl_dev.h"
 #include "entropy_coder.h"
 #include "picture_hash_core.h"
+#include "source_core.h"
 
 extern "C" __global__ void hevcdl_cnn_ctu_kernel(hevcdl_cnn_params p);
 extern "C" __global__ void hevcdl_fc_kernel(hevcdl_fc_params p);          // fc_kernel.hip: fully connected head + labels, 16 CTUs per workgroup
@@ -58,6 +59,13 @@ __global__ void hevcdl_clamp_labels_kernel(uint8_t *labels, int n_ctus, int ctus
   for (int c = 0; c < 16; c++) lab[c] = (uint8_t)l[c];
 }
 
+// the window's SSE of the reconstruction before the in-loop filters into the statistics of a padded picture (hevcdl_set_source_format): one thread per (picture, plane)
+__global__ void hevcdl_stats_sse_kernel(const hevcdl_quality *q, hevcdl_frame_stats *stats, int n_frames)
+{
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < 3 * n_frames) stats[t / 3].sse[t % 3] = q[t / 3].sse[t % 3];
+}
+
 struct hevcdl_ctx {
   char last_rd[160] = { 0 };           // which build and launch form the last decision launch took (hevcdl_last_rd_launch)
   hevcdl_config cfg;
@@ -105,6 +113,12 @@ struct hevcdl_ctx {
   int ec_fallbacks = 0;                    // pictures of the last batch the host writer coded (a sub-stream overflowed its region)
   int ec_capacity_per_ctu = 0;             // hevcdl_set_entropy_capacity (tests): 0 = the default
   double ec_ms[3] = { 0, 0, 0 };           // with `profile`: HIP-event times of the last batch (phase 1, coding, pack)
+  // source format (source_kernel.hip): everything below is allocated by hevcdl_set_source_format(ctx, fmt) and freed by (ctx, NULL); a context without one allocates
+  // and launches none of it.  d_src: max_frames frames of the larger of the source and the output format (the picture pipeline's upload; staging of the host entry
+  // points).  With padding (source_windowed) also the window crops at the internal depth of originals and pictures, and the SSE words of the statistics.
+  bool source_on = false, source_windowed = false; hevcdl_source_format src_fmt;
+  unsigned char *d_src = nullptr, *d_win_org = nullptr, *d_win_pic = nullptr, *d_win_sse = nullptr;
+  const uint8_t *d_last_final = nullptr; int last_frames = 0;      // output pictures of the last picture pipeline call, still in HBM (hevcdl_get_output_frames)
   bool profile;
   std::vector<hipEvent_t> ev_cnn, ev_rd, ev_conv;       // start/stop pairs (ev_conv: the convolution kernel alone, one pair per chunk of CTUs)
   char err[256];
@@ -366,6 +380,7 @@ extern "C" void hevcdl_destroy(hevcdl_ctx *ctx)
   hipFree(ctx->d_wpp); hipFree(ctx->d_records); hipFree(ctx->d_stats); hipFree(ctx->d_logits); hipFree(ctx->d_yuv8); hipFree(ctx->d_a3); hipFree(ctx->d_picture); hipFree(ctx->d_rgb); hipFree(ctx->d_cabac); hipFree(ctx->d_sao_stats); hipFree(ctx->d_sao_recon); hipFree(ctx->d_sao_params); hipFree(ctx->d_sao_cand); hipFree(ctx->d_wide); hipFree(ctx->d_flag); hipFree(ctx->d_sched);
   hipFree(ctx->d_q_pyr); hipFree(ctx->d_q_partial); hipFree(ctx->d_q_weights); hipFree(ctx->d_q_out);
   hipFree(ctx->d_rp_out); hipFree(ctx->d_rp_sse); hipFree(ctx->d_rp_partials);
+  hipFree(ctx->d_src); hipFree(ctx->d_win_org); hipFree(ctx->d_win_pic); hipFree(ctx->d_win_sse);
   for (hipEvent_t e : ctx->rp_ev) if (e) hipEventDestroy(e);
   hipFree(ctx->d_ec_tables); hipFree(ctx->d_ec_ws); hipFree(ctx->d_ec_packed); hipFree(ctx->d_ec_sync); hipFree(ctx->d_ec_off); hipFree(ctx->d_ec_cap); hipFree(ctx->d_ec_sizes); hipFree(ctx->d_ec_ovf); hipFree(ctx->d_ec_dst);
   delete ctx;
@@ -935,16 +950,17 @@ static void quality_constants(hevcdl_quality_params *p, int bit_depth)
   p->c1 = (0.01 * max_value) * (0.01 * max_value); p->c2 = (0.03 * max_value) * (0.03 * max_value);
 }
 
-static void quality_picture_params(const hevcdl_ctx *ctx, hevcdl_quality_params *p)
+// packed 4:2:0 pictures of w x h luma samples at the context's bit depth: the context's own pictures, or the window crops of a padded source format
+static void quality_sized_params(const hevcdl_ctx *ctx, hevcdl_quality_params *p, int w, int h)
 {
   memset(p, 0, sizeof *p);
-  const int w = ctx->cfg.width, h = ctx->cfg.height;
   p->n_planes = 3; p->plane_w[0] = w; p->plane_h[0] = h; p->plane_w[1] = p->plane_w[2] = w >> 1; p->plane_h[1] = p->plane_h[2] = h >> 1;
   p->plane_off[0] = 0; p->plane_off[1] = (size_t)w * h; p->plane_off[2] = (size_t)w * h + (size_t)(w >> 1) * (h >> 1);
   p->frame_samples = (size_t)w * h * 3 / 2; p->sample_bytes = ctx->cfg.bit_depth > 8 ? 2 : 1;
   quality_constants(p, ctx->cfg.bit_depth);
   hevcdl_quality_layout(p);
 }
+static void quality_picture_params(const hevcdl_ctx *ctx, hevcdl_quality_params *p) { quality_sized_params(ctx, p, ctx->cfg.width, ctx->cfg.height); }
 
 // The pass's workspace: pyramid levels and tile sums of q_group pictures, the window.  Allocated by hevcdl_enable_quality(ctx, 1) -- so that a lack of memory shows up there,
 // where a front end sizes its batch, and not in the middle of an encode -- or by the first hevcdl_picture_quality* call of a context that never enabled the switch.
@@ -964,6 +980,27 @@ static hevcdl_status ensure_quality_workspace(hevcdl_ctx *ctx)
   return HEVCDL_OK;
 }
 
+// the quality launches for packed pictures of w x h luma samples (at most the context's size: the workspace is the context's)
+static hevcdl_status quality_sized_dev(hevcdl_ctx *ctx, const void *d_org, const void *d_pic, int n_frames, void *d_out, hipStream_t s, int w, int h)
+{
+  hevcdl_status st = ensure_quality_workspace(ctx); if (st) return st;
+  hevcdl_quality_params p; quality_sized_params(ctx, &p, w, h);
+  if (w != ctx->cfg.width || h != ctx->cfg.height) { // a window: its levels and tile sums must fit the slots laid out for the whole picture
+    hevcdl_quality_params full; quality_picture_params(ctx, &full);
+    if (p.pyr_pic_words > full.pyr_pic_words || p.part_pic > full.part_pic) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "picture quality: the window needs more workspace than the picture");
+  }
+  const size_t frame_bytes = p.frame_samples * p.sample_bytes;
+  p.pyr = ctx->d_q_pyr; p.partial = ctx->d_q_partial; p.weights = ctx->d_q_weights; p.out = d_out;
+  HIPCHK(hipMemsetAsync(d_out, 0, sizeof(hevcdl_quality) * (size_t)n_frames, s));
+  for (int first = 0; first < n_frames; first += ctx->q_group) {        // a picture's result does not depend on the pass it falls into: every picture has its own workspace slot
+    p.n_pics = std::min(ctx->q_group, n_frames - first); p.out_first = first;
+    p.org = (const unsigned char *)d_org + frame_bytes * (size_t)first; p.pic = (const unsigned char *)d_pic + frame_bytes * (size_t)first;
+    hevcdl_launch_quality(&p, s);
+  }
+  HIPCHK(hipGetLastError());
+  return HEVCDL_OK;
+}
+
 extern "C" hevcdl_status hevcdl_picture_quality_dev(hevcdl_ctx *ctx, const void *d_org, const void *d_pic, int n_frames, void *d_out, void *stream)
 {
   hevcdl_status st = check_frames(ctx, n_frames); if (st) return st;
@@ -974,18 +1011,7 @@ extern "C" hevcdl_status hevcdl_picture_quality_dev(hevcdl_ctx *ctx, const void 
     const uintptr_t a = (uintptr_t)d_org, b = (uintptr_t)d_pic;
     if ((o < a + span && a < oe) || (o < b + span && b < oe)) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "picture quality: the output overlaps an input");
   }
-  hipStream_t s = (hipStream_t)stream;
-  st = ensure_quality_workspace(ctx); if (st) return st;
-  hevcdl_quality_params p; quality_picture_params(ctx, &p);
-  p.pyr = ctx->d_q_pyr; p.partial = ctx->d_q_partial; p.weights = ctx->d_q_weights; p.out = d_out;
-  HIPCHK(hipMemsetAsync(d_out, 0, sizeof(hevcdl_quality) * (size_t)n_frames, s));
-  for (int first = 0; first < n_frames; first += ctx->q_group) {        // a picture's result does not depend on the pass it falls into: every picture has its own workspace slot
-    p.n_pics = std::min(ctx->q_group, n_frames - first); p.out_first = first;
-    p.org = (const unsigned char *)d_org + ctx->frame_bytes * (size_t)first; p.pic = (const unsigned char *)d_pic + ctx->frame_bytes * (size_t)first;
-    hevcdl_launch_quality(&p, s);
-  }
-  HIPCHK(hipGetLastError());
-  return HEVCDL_OK;
+  return quality_sized_dev(ctx, d_org, d_pic, n_frames, d_out, (hipStream_t)stream, ctx->cfg.width, ctx->cfg.height);
 }
 
 extern "C" hevcdl_status hevcdl_picture_quality(hevcdl_ctx *ctx, const void *org, const void *pic, int n_frames, hevcdl_quality *out)
@@ -1105,7 +1131,10 @@ static hevcdl_status ensure_report_workspace(hevcdl_ctx *ctx)
   return HEVCDL_OK;
 }
 
-extern "C" hevcdl_status hevcdl_picture_report_dev(hevcdl_ctx *ctx, const void *d_org_opt, const void *d_pic, int n_frames, int method, void *d_out, void *stream)
+// sse_org / sse_pic: the pictures the SSE is taken over, packed at sse_w x sse_h luma samples -- the originals and d_pic themselves, or the window crops of a padded
+// source format (the digests always cover the whole coded picture d_pic)
+static hevcdl_status report_dev(hevcdl_ctx *ctx, const void *d_org_opt, const void *d_pic, int n_frames, int method, void *d_out, void *stream,
+                                const void *sse_org, const void *sse_pic, int sse_w, int sse_h)
 {
   hevcdl_status st = check_frames(ctx, n_frames); if (st) return st;
   if (method < 0 || method > 3) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "picture report: method must be 0 (none), 1 (MD5), 2 (CRC) or 3 (checksum)");
@@ -1122,8 +1151,8 @@ extern "C" hevcdl_status hevcdl_picture_report_dev(hevcdl_ctx *ctx, const void *
   HIPCHK(hipMemsetAsync(d_out, 0, sizeof(hevcdl_picture_report_t) * (size_t)n_frames, s));
   if (ctx->profile) HIPCHK(hipEventRecord(ctx->rp_ev[0], s));
   if (d_org_opt) { // the exact SSE: quality_kernel.hip's kernel alone, into hevcdl_quality-shaped words the finish kernel copies from
-    hevcdl_quality_params q; quality_picture_params(ctx, &q);
-    q.org = d_org_opt; q.pic = d_pic; q.out = ctx->d_rp_sse; q.n_pics = n_frames; q.out_first = 0;
+    hevcdl_quality_params q; quality_sized_params(ctx, &q, sse_w, sse_h);
+    q.org = sse_org; q.pic = sse_pic; q.out = ctx->d_rp_sse; q.n_pics = n_frames; q.out_first = 0;
     HIPCHK(hipMemsetAsync(ctx->d_rp_sse, 0, sizeof(hevcdl_quality) * (size_t)n_frames, s));
     hevcdl_launch_quality_sse(&q, s);
   }
@@ -1136,6 +1165,12 @@ extern "C" hevcdl_status hevcdl_picture_report_dev(hevcdl_ctx *ctx, const void *
     for (int i = 0; i < 3; i++) { float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, ctx->rp_ev[i], ctx->rp_ev[i + 1])); ctx->rp_ms[i] = ms; }
   }
   return HEVCDL_OK;
+}
+
+extern "C" hevcdl_status hevcdl_picture_report_dev(hevcdl_ctx *ctx, const void *d_org_opt, const void *d_pic, int n_frames, int method, void *d_out, void *stream)
+{
+  if (!ctx) return HEVCDL_ERR_INVALID_ARG;
+  return report_dev(ctx, d_org_opt, d_pic, n_frames, method, d_out, stream, d_org_opt, d_pic, ctx->cfg.width, ctx->cfg.height);
 }
 
 extern "C" hevcdl_status hevcdl_picture_report(hevcdl_ctx *ctx, const void *org_opt, const void *pic, int n_frames, int method, hevcdl_picture_report_t *out)
@@ -1222,6 +1257,117 @@ extern "C" hevcdl_status hevcdl_get_report_info(hevcdl_ctx *ctx, double *kernel_
   return HEVCDL_OK;
 }
 
+// ---- source and output formats (source_kernel.hip; the arithmetic and the host mirrors: source_core.h, hevcdl_bitstream.cpp) ---------------------------------------
+static void source_release(hevcdl_ctx *ctx)
+{
+  hipFree(ctx->d_src); hipFree(ctx->d_win_org); hipFree(ctx->d_win_pic); hipFree(ctx->d_win_sse);
+  ctx->d_src = ctx->d_win_org = ctx->d_win_pic = ctx->d_win_sse = nullptr; ctx->source_on = ctx->source_windowed = false;
+  ctx->d_last_final = nullptr; ctx->last_frames = 0;
+}
+
+extern "C" hevcdl_status hevcdl_set_source_format(hevcdl_ctx *ctx, const hevcdl_source_format *fmt)
+{
+  hevcdl_status st = check_frames(ctx, 0); if (st) return st;
+  if (fmt && (fmt->struct_size != sizeof *fmt || !hevcdl_src::format_fits(fmt->source_width, fmt->source_height, fmt->input_bit_depth, fmt->output_bit_depth, ctx->cfg.width, ctx->cfg.height)))
+    return fail(ctx, HEVCDL_ERR_INVALID_ARG, "source format: even source size of at least 2 x 2 and at most the context's, even padding, bit depths 8 .. 16");
+  { hipError_t e = hipDeviceSynchronize(); if (e != hipSuccess) return fail(ctx, HEVCDL_ERR_HIP, "hevcdl_set_source_format", e); }
+  source_release(ctx);
+  if (!fmt) return HEVCDL_OK;
+  ctx->src_fmt = *fmt;
+  const bool windowed = fmt->source_width != ctx->cfg.width || fmt->source_height != ctx->cfg.height;
+  const size_t nf = (size_t)ctx->cfg.max_frames, win_b = hevcdl_src::picture_samples(fmt->source_width, fmt->source_height) * (ctx->cfg.bit_depth > 8 ? 2 : 1);
+  hipError_t e = hipMalloc(&ctx->d_src, std::max(hevcdl_source_frame_bytes(fmt), hevcdl_output_frame_bytes(fmt)) * nf);      // the whole of what the format costs is reserved here
+  if (e == hipSuccess && windowed) e = hipMalloc(&ctx->d_win_org, win_b * nf);
+  if (e == hipSuccess && windowed) e = hipMalloc(&ctx->d_win_pic, win_b * nf);
+  if (e == hipSuccess && windowed) e = hipMalloc(&ctx->d_win_sse, sizeof(hevcdl_quality) * nf);
+  if (e != hipSuccess) { source_release(ctx); (void)hipGetLastError(); return fail(ctx, e == hipErrorOutOfMemory ? HEVCDL_ERR_OOM : HEVCDL_ERR_HIP, "source format buffers (cfg.max_frames)", e); }
+  ctx->source_on = true; ctx->source_windowed = windowed;
+  return HEVCDL_OK;
+}
+
+static hevcdl_status source_check(hevcdl_ctx *ctx, int n_frames, const void *a, const void *b, int a_bytes, int b_bytes)
+{
+  hevcdl_status st = check_frames(ctx, n_frames); if (st) return st;
+  if (!ctx->source_on) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_set_source_format was not called");
+  if (n_frames && (!a || !b || ((uintptr_t)a & (a_bytes - 1)) || ((uintptr_t)b & (b_bytes - 1)))) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "source format: null or misaligned device pointer");
+  return HEVCDL_OK;
+}
+
+extern "C" hevcdl_status hevcdl_load_source_dev(hevcdl_ctx *ctx, const void *d_src, int n_frames, void *d_coded, void *stream)
+{
+  if (!ctx) return HEVCDL_ERR_INVALID_ARG;
+  hevcdl_source_params p; memset(&p, 0, sizeof p);
+  p.src_bytes = ctx->src_fmt.input_bit_depth > 8 ? 2 : 1; p.dst_bytes = ctx->cfg.bit_depth > 8 ? 2 : 1;
+  hevcdl_status st = source_check(ctx, n_frames, d_src, d_coded, p.src_bytes, p.dst_bytes); if (st) return st;
+  if (n_frames == 0) return HEVCDL_OK;
+  p.src = d_src; p.dst = d_coded; p.src_w = ctx->src_fmt.source_width; p.src_h = ctx->src_fmt.source_height; p.dst_w = ctx->cfg.width; p.dst_h = ctx->cfg.height;
+  p.from_depth = ctx->src_fmt.input_bit_depth; p.to_depth = ctx->cfg.bit_depth; p.n_pics = n_frames;
+  hevcdl_launch_source_load(&p, stream);
+  HIPCHK(hipGetLastError());
+  return HEVCDL_OK;
+}
+
+// coded pictures -> pictures of the window's size at to_depth
+static hevcdl_status store_window_dev(hevcdl_ctx *ctx, const void *d_pictures, int n_frames, void *d_out, void *stream, int to_depth)
+{
+  hevcdl_source_params p; memset(&p, 0, sizeof p);
+  p.src_bytes = ctx->cfg.bit_depth > 8 ? 2 : 1; p.dst_bytes = to_depth > 8 ? 2 : 1;
+  hevcdl_status st = source_check(ctx, n_frames, d_pictures, d_out, p.src_bytes, p.dst_bytes); if (st) return st;
+  if (n_frames == 0) return HEVCDL_OK;
+  p.src = d_pictures; p.dst = d_out; p.src_w = ctx->cfg.width; p.src_h = ctx->cfg.height; p.dst_w = ctx->src_fmt.source_width; p.dst_h = ctx->src_fmt.source_height;
+  p.from_depth = ctx->cfg.bit_depth; p.to_depth = to_depth; p.n_pics = n_frames;
+  hevcdl_launch_source_store(&p, stream);
+  HIPCHK(hipGetLastError());
+  return HEVCDL_OK;
+}
+extern "C" hevcdl_status hevcdl_store_output_dev(hevcdl_ctx *ctx, const void *d_pictures, int n_frames, void *d_out, void *stream)
+{
+  if (!ctx) return HEVCDL_ERR_INVALID_ARG;
+  return store_window_dev(ctx, d_pictures, n_frames, d_out, stream, ctx->src_fmt.output_bit_depth);
+}
+// the window at the internal depth, contiguous: what the quality kernels measure a padded picture by (the store kernel with OUT = PEL, no scaling)
+static hevcdl_status crop_window_dev(hevcdl_ctx *ctx, const void *d_pictures, int n_frames, void *d_out, void *stream) { return store_window_dev(ctx, d_pictures, n_frames, d_out, stream, ctx->cfg.bit_depth); }
+
+extern "C" hevcdl_status hevcdl_load_source(hevcdl_ctx *ctx, const void *src, int n_frames, void *coded_out)
+{
+  hevcdl_status st = source_check(ctx, n_frames, src, coded_out, 1, 1); if (st) return st;
+  if (n_frames == 0) return HEVCDL_OK;
+  st = ensure_staging(ctx); if (st) return st;
+  HIPCHK(hipMemcpy(ctx->d_src, src, hevcdl_source_frame_bytes(&ctx->src_fmt) * n_frames, hipMemcpyHostToDevice));
+  st = hevcdl_load_source_dev(ctx, ctx->d_src, n_frames, ctx->d_yuv, nullptr); if (st) return st;
+  hipError_t e = hipDeviceSynchronize();
+  if (e != hipSuccess) return fail(ctx, HEVCDL_ERR_HIP, "source load kernel", e);
+  HIPCHK(hipMemcpy(coded_out, ctx->d_yuv, ctx->frame_bytes * n_frames, hipMemcpyDeviceToHost));
+  return HEVCDL_OK;
+}
+
+extern "C" hevcdl_status hevcdl_store_output(hevcdl_ctx *ctx, const void *pictures, int n_frames, void *out)
+{
+  hevcdl_status st = source_check(ctx, n_frames, pictures, out, 1, 1); if (st) return st;
+  if (n_frames == 0) return HEVCDL_OK;
+  st = ensure_staging(ctx); if (st) return st;
+  HIPCHK(hipMemcpy(ctx->d_recon, pictures, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
+  st = hevcdl_store_output_dev(ctx, ctx->d_recon, n_frames, ctx->d_src, nullptr); if (st) return st;
+  hipError_t e = hipDeviceSynchronize();
+  if (e != hipSuccess) return fail(ctx, HEVCDL_ERR_HIP, "source store kernel", e);
+  HIPCHK(hipMemcpy(out, ctx->d_src, hevcdl_output_frame_bytes(&ctx->src_fmt) * n_frames, hipMemcpyDeviceToHost));
+  return HEVCDL_OK;
+}
+
+// output-format frames of pictures of the last picture pipeline call, cropped and scaled where the pictures are: a run that needs its pictures only for the reconstruction
+// file fetches the window at the output depth instead of the coded pictures (the upload buffer is free again once the load kernel has run: it is the staging)
+extern "C" hevcdl_status hevcdl_get_output_frames(hevcdl_ctx *ctx, int first, int count, void *out)
+{
+  if (!ctx) return HEVCDL_ERR_INVALID_ARG;
+  if (!ctx->source_on) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_get_output_frames: hevcdl_set_source_format was not called");
+  if (!out || first < 0 || count < 0 || !ctx->d_last_final || (long long)first + count > ctx->last_frames) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_get_output_frames: pictures outside the last batch");
+  if (count == 0) return HEVCDL_OK;
+  hevcdl_status st = hevcdl_store_output_dev(ctx, ctx->d_last_final + ctx->frame_bytes * (size_t)first, count, ctx->d_src, nullptr); if (st) return st;
+  HIPCHK(hipStreamSynchronize(nullptr));
+  HIPCHK(hipMemcpy(out, ctx->d_src, hevcdl_output_frame_bytes(&ctx->src_fmt) * (size_t)count, hipMemcpyDeviceToHost));
+  return HEVCDL_OK;
+}
+
 // ---- whole picture pipeline for host buffers: the stages of TEncGOP::compressGOP between reading a picture and writing its NAL units, with
 // the picture staying in HBM in between (one upload of the originals, one download of records / final picture / SAO parameters) ----------
 // device side of hevcdl_encode_pictures*: upload, labels, decisions, in-loop filters; the results stay in HBM (*d_final: the output pictures)
@@ -1231,21 +1377,43 @@ static hevcdl_status encode_pictures_device(hevcdl_ctx *ctx, const void *yuv, in
   hevcdl_status st = ensure_staging(ctx); if (st) return st;
   if (want_sao && !ctx->d_sao_params) HIPCHK(hipMalloc(&ctx->d_sao_params, (size_t)ctx->ctus * sizeof(hevcdl_sao_blk) * ctx->cfg.max_frames));
   if (want_sao && !ctx->d_picture) HIPCHK(hipMalloc(&ctx->d_picture, ctx->frame_bytes * (size_t)ctx->cfg.max_frames));
+  ctx->d_last_final = nullptr; ctx->last_frames = 0;
+  const bool windowed = ctx->source_on && ctx->source_windowed;
+  const int ww = windowed ? ctx->src_fmt.source_width : ctx->cfg.width, wh = windowed ? ctx->src_fmt.source_height : ctx->cfg.height;      // what SSE and MS-SSIM are taken over
+  if (ctx->source_on) { // hevcdl_set_source_format: the source's own bytes go up; the load kernel pads and converts them in front of everything else
+    HIPCHK(hipMemcpy(ctx->d_src, yuv, hevcdl_source_frame_bytes(&ctx->src_fmt) * n_frames, hipMemcpyHostToDevice));
+    st = hevcdl_load_source_dev(ctx, ctx->d_src, n_frames, ctx->d_yuv, nullptr); if (st) return st;
+    if (windowed) { st = crop_window_dev(ctx, ctx->d_yuv, n_frames, ctx->d_win_org, nullptr); if (st) return st; }
+  } else
   HIPCHK(hipMemcpy(ctx->d_yuv, yuv, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
   if (labels_opt) { HIPCHK(hipMemcpy(ctx->d_labels, labels_opt, (size_t)ctx->ctus * 16 * n_frames, hipMemcpyHostToDevice)); st = hevcdl_clamp_labels_dev(ctx, ctx->d_labels, n_frames, nullptr); if (st) return st; }
   else { st = hevcdl_predict_depth_dev(ctx, ctx->d_yuv, n_frames, ctx->d_labels, nullptr, nullptr); if (st) return st; }
   st = hevcdl_compress_frames_dev(ctx, ctx->d_yuv, n_frames, ctx->d_labels, ctx->d_records, ctx->d_recon, ctx->d_stats, nullptr); if (st) return st;
+  if (windowed) { // the statistics' SSE (the reconstruction before the in-loop filters) over the window: the decision kernel summed over the padding too
+    st = crop_window_dev(ctx, ctx->d_recon, n_frames, ctx->d_win_pic, nullptr); if (st) return st;
+    hevcdl_quality_params q; quality_sized_params(ctx, &q, ww, wh);
+    q.org = ctx->d_win_org; q.pic = ctx->d_win_pic; q.out = ctx->d_win_sse; q.n_pics = n_frames; q.out_first = 0;
+    HIPCHK(hipMemsetAsync(ctx->d_win_sse, 0, sizeof(hevcdl_quality) * (size_t)n_frames, nullptr));
+    hevcdl_launch_quality_sse(&q, nullptr);
+    hipLaunchKernelGGL(hevcdl_stats_sse_kernel, dim3((3 * n_frames + 255) / 256), dim3(256), 0, nullptr, (const hevcdl_quality *)ctx->d_win_sse, (hevcdl_frame_stats *)ctx->d_stats, n_frames);
+    HIPCHK(hipGetLastError());
+  }
   *d_final = ctx->d_recon;
   if (deblock) { st = hevcdl_deblock_frames_dev(ctx, ctx->d_recon, n_frames, ctx->d_records, ctx->d_recon, nullptr); if (st) return st; }      // in place
   if (want_sao) { st = hevcdl_sao_frames_dev(ctx, ctx->d_yuv, ctx->d_recon, n_frames, ctx->d_sao_params, ctx->d_picture, nullptr); if (st) return st; *d_final = ctx->d_picture; }
   ctx->h_quality.clear();
+  ctx->h_report.clear();
+  if (windowed && (ctx->quality_on || ctx->report_on)) { st = crop_window_dev(ctx, *d_final, n_frames, ctx->d_win_pic, nullptr); if (st) return st; }      // the output pictures' window (TEncGOP.cpp:2302-2303, 2375-2376, 2413-2414)
   if (ctx->quality_on) { // the output pictures against the originals, both still in HBM
     if (!ctx->d_q_out) HIPCHK(hipMalloc(&ctx->d_q_out, sizeof(hevcdl_quality) * (size_t)ctx->cfg.max_frames));
-    st = hevcdl_picture_quality_dev(ctx, ctx->d_yuv, *d_final, n_frames, ctx->d_q_out, nullptr); if (st) return st;
+    if (windowed) st = quality_sized_dev(ctx, ctx->d_win_org, ctx->d_win_pic, n_frames, ctx->d_q_out, nullptr, ww, wh);
+    else st = hevcdl_picture_quality_dev(ctx, ctx->d_yuv, *d_final, n_frames, ctx->d_q_out, nullptr);
+    if (st) return st;
   }
-  ctx->h_report.clear();
-  if (ctx->report_on) { // hevcdl_enable_picture_report: SSE and digests of the output pictures, where they are
-    st = hevcdl_picture_report_dev(ctx, ctx->d_yuv, *d_final, n_frames, ctx->report_method, ctx->d_rp_out, nullptr); if (st) return st;
+  if (ctx->report_on) { // hevcdl_enable_picture_report: SSE and digests of the output pictures, where they are (the digests over the whole coded picture, as the hash SEI)
+    if (windowed) st = report_dev(ctx, ctx->d_yuv, *d_final, n_frames, ctx->report_method, ctx->d_rp_out, nullptr, ctx->d_win_org, ctx->d_win_pic, ww, wh);
+    else st = hevcdl_picture_report_dev(ctx, ctx->d_yuv, *d_final, n_frames, ctx->report_method, ctx->d_rp_out, nullptr);
+    if (st) return st;
   }
   hipError_t e = hipDeviceSynchronize();
   if (e != hipSuccess) return fail(ctx, HEVCDL_ERR_HIP, "picture pipeline", e);
@@ -1258,6 +1426,7 @@ static hevcdl_status encode_pictures_device(hevcdl_ctx *ctx, const void *yuv, in
     HIPCHK(hipMemcpy(ctx->h_quality.data(), ctx->d_q_out, sizeof(hevcdl_quality) * (size_t)n_frames, hipMemcpyDeviceToHost));
   }
   if (ctx->entropy_on) { st = entropy_pipeline(ctx, n_frames, want_sao); if (st) return st; }      // hevcdl_enable_device_entropy: the slice data too, from the records still in HBM
+  ctx->d_last_final = *d_final; ctx->last_frames = n_frames;
   return HEVCDL_OK;
 }
 

@@ -5,6 +5,8 @@
 //                                "--Key=value" / "--Key value", short options)
 //   option names / short forms   HM_dl/source/App/TAppEncoder/TAppEncCfg.cpp:730-1290
 //   planar YUV reader            HM_dl/source/Lib/TLibVideoIO/TVideoIOYuv.cpp:249,675 (8-bit 4:2:0 file, FrameSkip)
+//   padding / window / depths    TAppEncCfg.cpp:1569-1632 (ConformanceWindowMode 0 / 1 / 2), TVideoIOYuv.cpp:70-95, 363-381, 755-830: the file holds source-format frames, the
+//                                library pads and converts them on the device (hevcdl_set_source_format), the reconstruction file holds the window at OutputBitDepth
 //   picture log line / summary   TEncGOP.cpp:2500-2541, TEncAnalyze.h:163-370
 // and drives the GPU path through the C ABI of include/hevcdl.h only.  Keys that would change the path are checked
 // against what the path implements (rejected, not ignored).  Labels come from the on-device CNN, or -- the reference's own
@@ -44,6 +46,8 @@ const Key KEYS[] = {
   { "LabelDir", 0, USED, 0 }, { "BatchFrames", 0, USED, 0 }, { "ChunkFrames", 0, USED, 0 }, { "Device", 0, USED, 0 }, { "Devices", 0, USED, 0 }, { "NumDevices", 0, USED, 0 }, { "Weights", 0, USED, 0 }, { "RecordFile", 0, USED, 0 }, { "DeviceEntropy", 0, USED, 0 }, { "DeviceReport", 0, USED, 0 },
   { "CnnInput", 0, USED, 0 }, { "BnMode", 0, USED, 0 }, { "PrintConfig", 0, USED, 0 }, { "LoopFilterDisable", 0, USED, 0 },
   // keys that define the path: only the implemented value is accepted
+  { "ConformanceWindowMode", 0, USED, 0 }, { "HorizontalPadding", "pdx", USED, 0 }, { "VerticalPadding", "pdy", USED, 0 }, { "OutputBitDepth", 0, USED, 0 }, { "OutputBitDepthC", 0, USED, 0 },
+  { "ConfWinLeft", 0, USED, 0 }, { "ConfWinRight", 0, USED, 0 }, { "ConfWinTop", 0, USED, 0 }, { "ConfWinBottom", 0, USED, 0 },      // (rejected: they belong to ConformanceWindowMode 3)
   { "InputBitDepth", 0, USED, 0 }, { "InternalBitDepth", 0, USED, 0 }, { "InputChromaFormat", 0, PATH, "420" }, { "Profile", 0, USED, 0 },
   { "MaxCUWidth", 0, PATH, "64" }, { "MaxCUHeight", 0, PATH, "64" }, { "MaxPartitionDepth", 0, PATH, "4" },
   { "QuadtreeTULog2MaxSize", 0, PATH, "5" }, { "QuadtreeTULog2MinSize", 0, PATH, "2" }, { "QuadtreeTUMaxDepthIntra", 0, PATH, "3" },
@@ -222,7 +226,17 @@ int main(int argc, char **argv)
       opt.errors.push_back(std::string(k->name) + " = " + kv.second + " is not implemented by this path (only " + k->required + ")");
     if (k->kind == STAGE) stage_keys.push_back(k->name);
   }
-  const int width = (int)opt.geti("SourceWidth", 0), height = (int)opt.geti("SourceHeight", 0), qp = (int)opt.geti("QP", 30);
+  // SourceWidth / SourceHeight are the FILE's size; the context is created with the padded (coded) size of ConformanceWindowMode (TAppEncCfg.cpp:1569-1617): 0 none,
+  // 1 up to the next multiple of the minimum CU (8), 2 by HorizontalPadding / VerticalPadding; 3 (explicit ConfWin* offsets) is another path
+  const int src_w = (int)opt.geti("SourceWidth", 0), src_h = (int)opt.geti("SourceHeight", 0), qp = (int)opt.geti("QP", 30);
+  const int conf_mode = (int)opt.geti("ConformanceWindowMode", 0), pad_x = (int)opt.geti("HorizontalPadding", 0), pad_y = (int)opt.geti("VerticalPadding", 0);
+  int width = src_w, height = src_h;
+  if (conf_mode == 3) opt.errors.push_back("ConformanceWindowMode = 3 is not implemented by this path (only 0, 1 and 2)");
+  else if (conf_mode < 0 || conf_mode > 3) opt.errors.push_back("ConformanceWindowMode = " + std::to_string(conf_mode) + " is not a value of the key (0, 1 or 2)");
+  else if (src_w > 0 && src_h > 0 && hevcdl_padded_size(src_w, src_h, conf_mode, pad_x, pad_y, &width, &height) != HEVCDL_OK)
+    opt.errors.push_back("SourceWidth x SourceHeight with ConformanceWindowMode " + std::to_string(conf_mode) + ": the size must be even and the padded size a multiple of 8, the padding even and not negative");
+  for (const char *key : { "ConfWinLeft", "ConfWinRight", "ConfWinTop", "ConfWinBottom" })
+    if (opt.v.count(key)) opt.errors.push_back(std::string(key) + " belongs to ConformanceWindowMode 3, which is not implemented by this path");
   const long frame_skip = opt.geti("FrameSkip", 0); long n_frames = opt.geti("FramesToBeEncoded", 0);
   const double fps = atof(opt.get("FrameRate", "30").c_str());
   const std::string input = native_path(opt.get("InputFile")), recon_path = native_path(opt.get("ReconFile")), label_dir = native_path(opt.get("LabelDir"));
@@ -232,12 +246,21 @@ int main(int argc, char **argv)
   const bool deblock = opt.geti("LoopFilterDisable", 0) == 0;
   const bool sao = opt.geti("SAO", 1) != 0;                                    // TAppEncCfg.cpp: SAO defaults to on
   // sample bit depth (TAppEncCfg.cpp:770-780): 8 (Profile main) or 10 (Profile main10; the file then holds 16-bit little-endian samples).
-  // InternalBitDepth 0 = the input's; bit-depth conversion between file and codec is not implemented.
+  // InternalBitDepth 0 = the input's; OutputBitDepth 0 = the internal one (the reconstruction file's).  The file's samples are scaled to the internal depth on the device and
+  // the output back as TVideoIOYuv.cpp:70-95 does: up by a shift, down by a rounding shift and a clip.
   const int in_bd = (int)opt.geti("InputBitDepth", 8), bit_depth = opt.geti("InternalBitDepth", 0) == 0 ? in_bd : (int)opt.geti("InternalBitDepth", 0);
-  if (bit_depth != in_bd) opt.errors.push_back("InternalBitDepth must equal InputBitDepth on this path (no bit-depth conversion)");
+  const int out_bd = opt.geti("OutputBitDepth", 0) == 0 ? bit_depth : (int)opt.geti("OutputBitDepth", 0);
+  // (the reference's OutputBitDepthC defaults to the INTERNAL depth, not to OutputBitDepth: an output depth of its own has to be named for both channels, as chroma-specific
+  // depths are not implemented)
+  if ((opt.geti("OutputBitDepthC", 0) == 0 ? bit_depth : (int)opt.geti("OutputBitDepthC", 0)) != out_bd)
+    opt.errors.push_back("OutputBitDepthC must equal OutputBitDepth on this path (it defaults to the internal depth, as in the reference; chroma-specific depths are not implemented)");
+  if (in_bd < 8 || in_bd > 16) opt.errors.push_back("InputBitDepth = " + std::to_string(in_bd) + " is not implemented by this path (8 .. 16)");
+  if (out_bd < 8 || out_bd > 16) opt.errors.push_back("OutputBitDepth = " + std::to_string(out_bd) + " is not implemented by this path (8 .. 16)");
   if (bit_depth != 8 && bit_depth != 10) opt.errors.push_back("InternalBitDepth = " + std::to_string(bit_depth) + " is not implemented by this path (only 8 and 10)");
   { const std::string prof = opt.get("Profile", bit_depth == 8 ? "main" : "main10");
-    if (prof != (bit_depth == 8 ? "main" : "main10")) opt.errors.push_back("Profile = " + prof + " is not implemented by this path (main at 8 bits, main10 at 10 bits)"); }
+    if (prof != (bit_depth == 8 ? "main" : "main10")) opt.errors.push_back("Profile = " + prof + " does not go with InternalBitDepth = " + std::to_string(bit_depth) + " on this path (main at 8 bits, main10 at 10 bits)"); }
+  // the source format goes to the library only when the file is not in the codec's own format already: every other run is the run it was
+  const bool use_fmt = src_w != width || src_h != height || in_bd != bit_depth || out_bd != bit_depth;
   // decoded picture hash SEI (TAppEncCfg.cpp:1093): 0 none, 1 MD5 of the output picture behind every access unit
   const int hash_sei = (int)opt.geti("SEIDecodedPictureHash", 0);
   // PrintMSSSIM: computed on the device from the pictures the pipeline still holds there (hevcdl_enable_quality); the two MSE keys only print what the PSNR is made of
@@ -274,8 +297,10 @@ int main(int argc, char **argv)
   }
   if (opt.v.count("PrintConfig")) {
     printf("{\"InputFile\": \"%s\", \"ReconFile\": \"%s\", \"SourceWidth\": %d, \"SourceHeight\": %d, \"QP\": %d, \"FrameSkip\": %ld, \"FramesToBeEncoded\": %ld, "
-           "\"FrameRate\": %g, \"LabelDir\": \"%s\", \"CnnInput\": \"%s\", \"BitstreamFile\": \"%s\", \"level_idc\": %d, \"tiles\": [%d, %d], \"bit_depth\": %d, \"stage_keys\": [", json_escape(input).c_str(), json_escape(recon_path).c_str(), width, height, qp,
-           frame_skip, n_frames, fps, json_escape(label_dir).c_str(), cnn_input.c_str(), json_escape(bitstream_path).c_str(), level_idc, tile_cols, tile_rows, bit_depth);
+           "\"FrameRate\": %g, \"LabelDir\": \"%s\", \"CnnInput\": \"%s\", \"BitstreamFile\": \"%s\", \"level_idc\": %d, \"tiles\": [%d, %d], \"bit_depth\": %d, "
+           "\"ConformanceWindowMode\": %d, \"HorizontalPadding\": %d, \"VerticalPadding\": %d, \"InputBitDepth\": %d, \"InternalBitDepth\": %d, \"OutputBitDepth\": %d, \"coded_size\": [%d, %d], \"stage_keys\": [", json_escape(input).c_str(), json_escape(recon_path).c_str(), src_w, src_h, qp,
+           frame_skip, n_frames, fps, json_escape(label_dir).c_str(), cnn_input.c_str(), json_escape(bitstream_path).c_str(), level_idc, tile_cols, tile_rows, bit_depth,
+           conf_mode, pad_x, pad_y, in_bd, bit_depth, out_bd, width, height);
     for (size_t i = 0; i < stage_keys.size(); i++) printf("%s\"%s\"", i ? ", " : "", stage_keys[i].c_str());
     printf("], \"errors\": [");
     for (size_t i = 0; i < opt.errors.size(); i++) printf("%s\"%s\"", i ? ", " : "", json_escape(opt.errors[i]).c_str());
@@ -289,12 +314,16 @@ int main(int argc, char **argv)
   if (bn_mode != "reference" && bn_mode != "eval") opt.errors.push_back("BnMode must be reference or eval");
   if (!opt.errors.empty()) { for (const auto &e : opt.errors) fprintf(stderr, "Error: %s\n", e.c_str()); return 2; }
 
-  const size_t frame_bytes = hevcdl_frame_bytes_bd(width, height, bit_depth);
+  const size_t frame_bytes = hevcdl_frame_bytes_bd(width, height, bit_depth);      // a coded picture
+  hevcdl_source_format fmt; memset(&fmt, 0, sizeof fmt);
+  fmt.struct_size = sizeof fmt; fmt.source_width = src_w; fmt.source_height = src_h; fmt.input_bit_depth = in_bd; fmt.output_bit_depth = out_bd;
+  const size_t src_frame_bytes = use_fmt ? hevcdl_source_frame_bytes(&fmt) : frame_bytes, out_frame_bytes = use_fmt ? hevcdl_output_frame_bytes(&fmt) : frame_bytes;      // a frame of the input file / of the reconstruction file
+  if (src_frame_bytes == 0) { fprintf(stderr, "Error: unsupported source size / bit depths\n"); return 2; }
   FILE *fin = fopen(input.c_str(), "rb");
   if (!fin) { fprintf(stderr, "Error: cannot open input file '%s'\n", input.c_str()); return 2; }
   fseek(fin, 0, SEEK_END); const long long fsize = ftell(fin);
   fclose(fin);
-  const long avail = (long)(fsize / (long long)frame_bytes) - frame_skip;
+  const long avail = (long)(fsize / (long long)src_frame_bytes) - frame_skip;
   if (avail <= 0) { fprintf(stderr, "Error: input holds no frame after FrameSkip\n"); return 2; }
   if (n_frames <= 0 || n_frames > avail) n_frames = avail;                    // TAppEncTop: stops at end of file
   // Devices.  --Device d (default 0): one device.  --Devices 0-7 | 0,2,5 | --NumDevices N: the frames of the job in contiguous blocks, one block, one host thread and
@@ -388,6 +417,8 @@ int main(int argc, char **argv)
       if (st == HEVCDL_OK && device_entropy && (st = hevcdl_enable_device_entropy(shards[i].ctx, 1)) != HEVCDL_OK) { hevcdl_destroy(shards[i].ctx); shards[i].ctx = nullptr; }
       // DeviceReport: records and partials of a batch (a few KB a picture)
       if (st == HEVCDL_OK && device_report && (st = hevcdl_enable_picture_report(shards[i].ctx, 1, hash_sei)) != HEVCDL_OK) { hevcdl_destroy(shards[i].ctx); shards[i].ctx = nullptr; }
+      // a file that is not in the codec's format: the upload buffer of source-format frames and the window crops of a padded picture
+      if (st == HEVCDL_OK && use_fmt && (st = hevcdl_set_source_format(shards[i].ctx, &fmt)) != HEVCDL_OK) { hevcdl_destroy(shards[i].ctx); shards[i].ctx = nullptr; }
       if (st == HEVCDL_ERR_OOM && ws_oom) {
         // the workspace is sized by the device's CUs, not by the batch: a smaller batch does not shrink it.  What does: the independent launch form (a block per wave of
         // the context's own frames instead of every CU's workgroup), then the eight-wave build
@@ -411,6 +442,7 @@ int main(int argc, char **argv)
   const double t_setup = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_main0).count();      // options, weights, contexts, the decision kernel's workspace
   const int chunk = (int)std::max<long>(1, std::min<long>(batch, opt.geti("ChunkFrames", 48)));
 
+  if (use_fmt) printf("Source %dx%d at %d bits -> coded %dx%d at %d bits (conformance window right %d, bottom %d), output at %d bits\n", src_w, src_h, in_bd, width, height, bit_depth, width - src_w, height - src_h, out_bd);
   printf("HEVC-DL MI355X path: %dx%d  QP %d  frames %ld (skip %ld)  batch %d  labels: %s\n", width, height, qp, n_frames, frame_skip, batch,
          label_dir.empty() ? (cnn_input == "luma" ? "on-device CNN (luma input)" : "on-device CNN (BT.601 RGB input)") : ("files under " + label_dir).c_str());
   if (multi) {
@@ -433,7 +465,8 @@ int main(int argc, char **argv)
   scfg.rewrite_param_sets = opt.geti("ReWriteParamSetsFlag", 1) != 0;
   scfg.tools = cfg.tools; scfg.lf_beta_offset_div2 = cfg.lf_beta_offset_div2; scfg.lf_tc_offset_div2 = cfg.lf_tc_offset_div2; scfg.loop_filter_disable = deblock ? 0 : 1;
   scfg.lf_across_tiles = cfg.lf_across_tiles; scfg.tile_uniform_spacing = cfg.tile_uniform_spacing; memcpy(scfg.tile_column_width, cfg.tile_column_width, sizeof scfg.tile_column_width); memcpy(scfg.tile_row_height, cfg.tile_row_height, sizeof scfg.tile_row_height);
-  const double ny = (double)width * height, nc = ny / 4;
+  scfg.conf_win_right = width - src_w; scfg.conf_win_bottom = height - src_h;
+  const double ny = (double)src_w * src_h, nc = ny / 4;      // PSNR, MSE and MS-SSIM are taken over the picture without the padding (TEncGOP.cpp:2302-2303, 2375-2376)
   double sum_bits = 0, sum_psnr[3] = { 0, 0, 0 }, sum_mse[3] = { 0, 0, 0 }, sum_msssim[3] = { 0, 0, 0 }; long done = 0;
   auto now = [] { return std::chrono::steady_clock::now(); };
   auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
@@ -472,11 +505,12 @@ int main(int argc, char **argv)
     if (!fi) { S.rc = 2; return; }
     const int sb = (int)std::min<long>(batch, S.f_hi - S.f_lo);
     // originals of one device call in page-locked memory (the upload then runs at the link's rate and does not go through a bounce buffer); label files beside them
-    struct Pinned { uint8_t *p; explicit Pinned(size_t n) : p((uint8_t *)hevcdl_host_alloc(n)) {} ~Pinned() { hevcdl_host_free(p); } uint8_t *data() { return p; } } yuv_mem((size_t)frame_bytes * sb);
-    if (!yuv_mem.data()) { fprintf(stderr, "Error: cannot allocate %zu bytes of page-locked memory for the originals\n", (size_t)frame_bytes * sb); S.rc = 3; fclose(fi); return; }
+    struct Pinned { uint8_t *p; explicit Pinned(size_t n) : p((uint8_t *)hevcdl_host_alloc(n)) {} ~Pinned() { hevcdl_host_free(p); } uint8_t *data() { return p; } } yuv_mem((size_t)src_frame_bytes * sb);
+    if (!yuv_mem.data()) { fprintf(stderr, "Error: cannot allocate %zu bytes of page-locked memory for the originals\n", (size_t)src_frame_bytes * sb); S.rc = 3; fclose(fi); return; }
     std::vector<uint8_t> labels_mem(label_dir.empty() ? 0 : (size_t)ctus * 16 * sb);
     struct ChunkCtx { long f0; double et; const uint8_t *yuv; std::chrono::steady_clock::time_point t0; int nb; } cc = { 0, 0.0, nullptr, now(), 1 };
-    const bool want_pictures = device_report ? frec != nullptr : (frec || hash_sei || deblock), want_records = frecords != nullptr;      // what a DeviceEntropy run still fetches from HBM
+    // (with a source format the reconstruction file's frames are made on the device from the pictures in HBM: hevcdl_get_output_frames)
+    const bool want_pictures = device_report ? (frec != nullptr && !use_fmt) : (frec || hash_sei || deblock), want_records = frecords != nullptr;      // what a DeviceEntropy run still fetches from HBM
     // slice_data / slice_sizes / n_sub: the packed sub-streams of the chunk's pictures (DeviceEntropy), or null: the host writer codes the records
     auto on_chunk = [&](int first, int count, const hevcdl_ctu_record *recs, const void *pictures, const hevcdl_sao_blk *sao_params, const hevcdl_frame_stats *stats,
                         const uint8_t *slice_data, const uint32_t *slice_sizes, int n_sub) -> int {
@@ -499,6 +533,19 @@ int main(int argc, char **argv)
             PicOut &po = pics[i]; po.md5_text[0] = 0;
             for (int c = 0; c < 3; c++) po.sse[c] = stats[i].sse[c];
             if (deblock && device_report) { for (int c = 0; c < 3; c++) po.sse[c] = reports[i].sse[c]; }      // of the filtered picture, from the device
+            else if (deblock && recon && use_fmt) { // the same over the window: original and output picture at the internal depth, by the library's host functions
+              hevcdl_source_format wf = fmt; wf.output_bit_depth = bit_depth;
+              const size_t wn[3] = { (size_t)src_w * src_h, (size_t)src_w * src_h / 4, (size_t)src_w * src_h / 4 }, wtot = wn[0] + wn[1] + wn[2], ws = bit_depth > 8 ? 2 : 1;
+              std::vector<uint8_t> ow(wtot * ws), rw(wtot * ws);
+              if (hevcdl_load_source_host(&wf, src_w, src_h, bit_depth, cc.yuv + src_frame_bytes * (size_t)(first + i), 1, ow.data()) != HEVCDL_OK ||
+                  hevcdl_store_output_host(&wf, width, height, bit_depth, recon + frame_bytes * (size_t)i, 1, rw.data()) != HEVCDL_OK) { po.st = HEVCDL_ERR_INVALID_ARG; continue; }
+              size_t off = 0;
+              for (int c = 0; c < 3; c++) {
+                unsigned long long sse = 0;
+                for (size_t k = 0; k < wn[c]; k++) { const int d = ws == 1 ? (int)ow[off + k] - (int)rw[off + k] : (int)((const uint16_t *)ow.data())[off + k] - (int)((const uint16_t *)rw.data())[off + k]; sse += (unsigned long long)(d * d); }
+                po.sse[c] = sse; off += wn[c];
+              }
+            }
             else if (deblock && recon) { // the picture statistics follow the filtered picture: recomputed here
               const uint8_t *o = cc.yuv + frame_bytes * (size_t)(first + i), *r = recon + frame_bytes * (size_t)i;
               const size_t n[3] = { (size_t)width * height, (size_t)width * height / 4, (size_t)width * height / 4 };
@@ -556,6 +603,12 @@ int main(int argc, char **argv)
       }
       if (frec || frecords) {
         std::lock_guard<std::mutex> lock(file_mutex);
+        if (frec && use_fmt) { // the window at OutputBitDepth (TVideoIOYuv.cpp:755-830)
+          std::vector<uint8_t> outf(out_frame_bytes * (size_t)count);
+          if ((recon ? hevcdl_store_output_host(&fmt, width, height, bit_depth, recon, count, outf.data()) : hevcdl_get_output_frames(S.ctx, first, count, outf.data())) != HEVCDL_OK) { fprintf(stderr, "Error: cannot convert the output pictures\n"); S.rc = 3; return 1; }
+          if (multi) fseeko(frec, (off_t)((cc.f0 + first) * (long long)out_frame_bytes), SEEK_SET);
+          fwrite(outf.data(), out_frame_bytes, count, frec);
+        } else
         if (frec) { if (multi) fseeko(frec, (off_t)((cc.f0 + first) * (long long)frame_bytes), SEEK_SET); fwrite(recon, frame_bytes, count, frec); }
         if (frecords) { if (multi) fseeko(frecords, (off_t)((cc.f0 + first) * (long long)ctus * (long long)sizeof(hevcdl_ctu_record)), SEEK_SET); fwrite(recs, sizeof(hevcdl_ctu_record), (size_t)ctus * count, frecords); }
       }
@@ -570,8 +623,8 @@ int main(int argc, char **argv)
     for (long bi = 0; bi < n_batches && S.rc == 0; bi++) {
       const long f0 = S.f_lo + bi * (long)sb; const int nb = (int)std::min<long>(sb, S.f_hi - f0);
       const auto tr0 = now();
-      fseeko(fi, (off_t)((frame_skip + f0) * (long long)frame_bytes), SEEK_SET);
-      if (fread(yuv_mem.data(), frame_bytes, nb, fi) != (size_t)nb) { fprintf(stderr, "Error: short read of '%s'\n", input.c_str()); S.rc = 2; break; }
+      fseeko(fi, (off_t)((frame_skip + f0) * (long long)src_frame_bytes), SEEK_SET);
+      if (fread(yuv_mem.data(), src_frame_bytes, nb, fi) != (size_t)nb) { fprintf(stderr, "Error: short read of '%s'\n", input.c_str()); S.rc = 2; break; }
       const uint8_t *lab = nullptr;
       if (!label_dir.empty()) {
         for (int i = 0; i < nb && S.rc == 0; i++) for (int a = 0; a < ctus; a++) {

@@ -173,6 +173,17 @@ struct hevcdl_report_params {
   int chunk_bytes, chunk_stride;   // chunk_bytes: a multiple of 16; chunk_stride >= the chunks of the largest plane
 };
 
+// source and output formats (source_kernel.hip): n_pics packed 4:2:0 pictures of src_w x src_h luma samples become pictures of dst_w x dst_h; destination sample
+// (x, y) of a plane is the source sample (min(x, plane width - 1), min(y, plane height - 1)) scaled from from_depth to to_depth (csrc/source_core.h)
+struct hevcdl_source_params {
+  const void *src; void *dst;      // sample aligned; every plane follows the one before without a gap
+  int src_w, src_h, dst_w, dst_h;  // luma sizes, all even; chroma planes are halved
+  int from_depth, to_depth;
+  int src_bytes, dst_bytes;        // 1 or 2 bytes a sample
+  int n_pics;
+  int rows_per_group;              // set by the launcher
+};
+
 // slice data on the device (entropy_kernel.hip): one wave per sub-stream
 struct hevcdl_entropy_params {
   const unsigned char *records;    // [frame][ctu] hevcdl_ctu_record
@@ -255,6 +266,8 @@ void hevcdl_launch_quality_sse(const struct hevcdl_quality_params *p, void *stre
 // report_kernel.hip: partial (methods 2, 3) or MD5 (method 1) launch, then the finish launch, in order on `stream`.  events_opt: three hipEvent_t recorded in front of the
 // first launch, between the two and behind the second (timing), or NULL
 void hevcdl_launch_report(const struct hevcdl_report_params *p, void *stream, void **events_opt);
+void hevcdl_launch_source_load(const struct hevcdl_source_params *p, void *stream);       // source_kernel.hip: hevcdl_source_load_kernel<IN, PEL> by src_bytes / dst_bytes
+void hevcdl_launch_source_store(const struct hevcdl_source_params *p, void *stream);      // hevcdl_source_store_kernel<PEL, OUT>
 // hevcdl_bitstream.cpp: the packed sub-streams of one picture by the host writer (fallback of the device entropy coder); 0, or -1 when `capacity` is too small
 int hevcdl_host_writer_slice_data(const struct hevcdl_stream_config *cfg, const struct hevcdl_ctu_record *records, const struct hevcdl_sao_blk *sao, uint8_t *out, size_t capacity,
                                   uint32_t *sizes, size_t *total);

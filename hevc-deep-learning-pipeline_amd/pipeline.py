@@ -13,6 +13,7 @@ import time
 import numpy as np
 
 from . import Encoder, write_access_unit, picture_hash_sei, stream_config, write_access_unit_from_slice_data, hash_sei as digest_sei, report_digest
+from . import load_source_host, store_output_host, source_format as make_source_format
 from . import metrics, sharding
 
 
@@ -40,7 +41,7 @@ def read_frames(path, width, height, first, count, bit_depth=8):
 
 
 def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None, recon_path=None, frame_skip=0, batch=256, tiles=(1, 1),
-                    lf_across_tiles=True, bit_depth=8, level_idc=186, frame_rate=30.0, hash_sei=False, labels_fn=None, device=None, log=print, tools=0x7f, wavefront=False, device_entropy=False, device_report=False):
+                    lf_across_tiles=True, bit_depth=8, level_idc=186, frame_rate=30.0, hash_sei=False, labels_fn=None, device=None, log=print, tools=0x7f, wavefront=False, device_entropy=False, device_report=False, source_format=None):
     """Encode frames [frame_skip, frame_skip + n_frames) of a planar YUV file.  Works stand-alone and under torch.distributed
     (initialised by the caller): rank r takes a contiguous share of the frames.  Returns, on rank 0, the summary (metrics.Summary)
     and the list of per-picture rows [poc, bits, sseY, sseU, sseV]; other ranks return (None, None).
@@ -50,7 +51,10 @@ def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None
     SAO parameters with them through encode_pictures.
     device_report: the squared errors and the hash SEI's digests come from the device too (Encoder.enable_picture_report), computed where the output picture is.  Together
     with device_entropy and without a recon_path nothing but slice data, statistics and the 80-byte reports leaves HBM: the batch goes through
-    Encoder.encode_pictures_stream(want_pictures=False).  Stream, reconstruction file and rows are the same either way."""
+    Encoder.encode_pictures_stream(want_pictures=False).  Stream, reconstruction file and rows are the same either way.
+    source_format (hevcdl_amd.source_format(...)): the file holds frames of that size and input depth, not of the codec's format; width / height / bit_depth stay the
+    CODED size (hevcdl_amd.padded_size) and the internal depth.  The frames go to the device as they are (Encoder.set_source_format), the SPS carries the window, the
+    rows' squared errors are the window's and the reconstruction file holds window-sized frames at the format's output depth."""
     import torch
     import torch.distributed as dist
     multi = dist.is_available() and dist.is_initialized()
@@ -65,17 +69,23 @@ def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None
     fb, fr = open(part_bits, "wb") if part_bits else None, open(part_rec, "wb") if part_rec else None
     if len(mine):
         enc = Encoder(width, height, qp, max_frames=min(batch, len(mine)), device=device, tiles=tiles, bit_depth=bit_depth, lf_across_tiles=lf_across_tiles, tools=tools, wavefront=wavefront)      # tools: HEVCDL_TOOL_*; wavefront: WaveFrontSynchro mask (the cfg's tool switches)
-        ysz = width * height
+        sf = source_format
+        sw, sh = (sf.source_width, sf.source_height) if sf is not None else (width, height)
+        conf_win = (width - sw, height - sh)
+        if sf is not None:
+            enc.set_source_format(sf)
+            wf = make_source_format(sw, sh, sf.input_bit_depth, bit_depth)      # the window at the internal depth: what the squared errors are taken over
+        ysz = sw * sh
         scfg = None
         if device_entropy:
             enc.enable_device_entropy(True)
-            scfg = stream_config(width, height, qp, level_idc, True, tiles, bit_depth, lf_across_tiles, tools, wavefront=wavefront)
+            scfg = stream_config(width, height, qp, level_idc, True, tiles, bit_depth, lf_across_tiles, tools, wavefront=wavefront, conf_win=conf_win)
         if device_report:
             enc.enable_picture_report(True, 1 if hash_sei else 0)
         stream_only = device_report and device_entropy and not recon_path      # no picture, record or SAO parameter is copied to the host
         for b0 in range(mine.start, mine.stop, batch):
             nb = min(batch, mine.stop - b0)
-            yuv = read_frames(input_path, width, height, frame_skip + b0, nb, bit_depth)
+            yuv = read_frames(input_path, sw, sh, frame_skip + b0, nb, sf.input_bit_depth if sf is not None else bit_depth)
             t0 = time.time()
             labels = labels_fn(b0, nb) if labels_fn else None
             if stream_only:
@@ -90,11 +100,14 @@ def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None
                 if device_entropy:
                     au = write_access_unit_from_slice_data(scfg, b0 + i, slices[i], slice_sizes[i])
                 else:
-                    au = write_access_unit(width, height, qp, b0 + i, recs[i], level_idc=level_idc, sao=sao[i], tiles=tiles, bit_depth=bit_depth, lf_across_tiles=lf_across_tiles, tools=tools, wavefront=wavefront)
+                    au = write_access_unit(width, height, qp, b0 + i, recs[i], level_idc=level_idc, sao=sao[i], tiles=tiles, bit_depth=bit_depth, lf_across_tiles=lf_across_tiles, tools=tools, wavefront=wavefront, conf_win=conf_win)
                 if device_report:
                     return au, digest_sei(1, report_digest(reports[i])) if hash_sei else b"", [int(v) for v in reports[i]["sse"]]
                 sei = picture_hash_sei(width, height, final[i], bit_depth) if hash_sei else b""
-                d = (yuv[i].astype(np.int64) - final[i].astype(np.int64)) ** 2
+                if sf is not None:
+                    d = (load_source_host(wf, sw, sh, bit_depth, yuv[i:i + 1])[0].astype(np.int64) - store_output_host(wf, width, height, bit_depth, final[i:i + 1])[0].astype(np.int64)) ** 2
+                else:
+                    d = (yuv[i].astype(np.int64) - final[i].astype(np.int64)) ** 2
                 return au, sei, [int(d[:ysz].sum()), int(d[ysz:ysz + ysz // 4].sum()), int(d[ysz + ysz // 4:].sum())]
             for i, (au, sei, sse) in enumerate(_pool().map(one_picture, range(nb))):
                 poc = b0 + i
@@ -102,7 +115,7 @@ def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None
                     fb.write(au + sei)
                 rows[poc - mine.start] = [poc, len(au) * 8] + sse
             if fr:
-                final.tofile(fr)
+                (final if sf is None else store_output_host(sf, width, height, bit_depth, final)).tofile(fr)
             log("rank %d: pictures %d..%d encoded (%.2f s per picture)" % (rank, b0, b0 + nb - 1, et))
         enc.close()
     for f in (fb, fr):
@@ -127,7 +140,7 @@ def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None
                                 break
                             out.write(chunk)
                     os.remove(path + ".part%d" % r)
-    summ = metrics.Summary(width, height, frame_rate, bit_depth)
+    summ = metrics.Summary(*((source_format.source_width, source_format.source_height) if source_format is not None else (width, height)), frame_rate, bit_depth)
     for poc, bits, sy, su, sv in allrows:
         p = summ.add(int(bits), (int(sy), int(su), int(sv)))
         log(metrics.frame_line(int(poc), qp, int(bits), p))

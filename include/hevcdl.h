@@ -321,6 +321,47 @@ hevcdl_status hevcdl_plane_hash_host(const void *plane, int width, int height, i
 int           hevcdl_report_chunk_bytes(void);
 hevcdl_status hevcdl_get_report_info(hevcdl_ctx *ctx, double *kernel_ms);
 
+/* ---- source pictures of any size and bit depth: padding, conformance window, bit-depth conversion (csrc/source_core.h, csrc/source_kernel.hip) ----------------
+ * A context is created with the CODED size (multiples of 8) and the internal bit depth, as ever.  A source format describes what the caller's pictures look like
+ * instead: source_width x source_height (even, at most the coded size; the difference is the padding, even as well) at input_bit_depth, and at which depth output
+ * frames are wanted.  Replaces the reference's file boundary: TVideoIOYuv.cpp readPlane :363-381 (a column past the source width takes the row's last source sample, a
+ * row past the source height the row above), scalePlane :70-95 (up: a left shift; down: a rounding right shift clipped to the target depth; no Rec.709 clip), write
+ * :755-830 (the window = the coded picture minus the right and lower padding, scaled from the internal to the output depth).  Samples above 8 bits are two bytes,
+ * little endian; a picture is its Y, Cb, Cr planes back to back without a pitch.  Input samples must lie inside input_bit_depth. */
+typedef struct hevcdl_source_format {
+  uint32_t struct_size;          /* sizeof(hevcdl_source_format) */
+  int32_t  source_width, source_height;      /* luma samples, even, >= 2 */
+  int32_t  input_bit_depth, output_bit_depth;      /* 8 .. 16 */
+} hevcdl_source_format;
+/* the context's own size and depth: a format that changes nothing */
+hevcdl_status hevcdl_source_format_default(hevcdl_source_format *fmt, const hevcdl_config *cfg);
+/* The coded size of a source size (TAppEncCfg.cpp:1569-1617).  mode = ConformanceWindowMode: 0 no padding (a size that is no multiple of 8 is HEVCDL_ERR_INVALID_ARG),
+ * 1 pad every dimension that is no multiple of the minimum CU (8) up to the next one, 2 pad by pad_x / pad_y (HorizontalPadding / VerticalPadding; the result must be a
+ * multiple of 8), 3 (explicit window offsets) HEVCDL_ERR_UNSUPPORTED.  Odd padding or an odd source size is HEVCDL_ERR_INVALID_ARG (4:2:0). */
+hevcdl_status hevcdl_padded_size(int source_width, int source_height, int mode, int pad_x, int pad_y, int *width, int *height);
+size_t        hevcdl_source_frame_bytes(const hevcdl_source_format *fmt);      /* one source-format frame; 0 for an invalid format */
+size_t        hevcdl_output_frame_bytes(const hevcdl_source_format *fmt);      /* one output-format frame (window size, output depth) */
+/* With a source format set (fmt == NULL clears it; HEVCDL_ERR_INVALID_ARG when it does not fit the context's size), hevcdl_encode_pictures / _chunked / _stream read
+ * `yuv` as source-format frames: those bytes are uploaded (an 8-bit source of a 10-bit context is half the bytes of its coded form) and hevcdl_source_load_kernel
+ * converts and pads them in HBM in front of the CNN and the decisions.  Records, pictures and slice data stay what they are: coded format, so every consumer keeps
+ * working, and the hash SEI / the report's digests cover the whole coded picture.  hevcdl_get_quality and hevcdl_get_picture_report carry SSE and MS-SSIM of the WINDOW
+ * (TEncGOP.cpp:2302-2303, 2375-2376, 2413-2414), and so does hevcdl_frame_stats.sse when the picture is padded.  The per-CTU session and the *_dev entry points take
+ * coded-format input, as before.  With no format set every entry point behaves exactly as before. */
+hevcdl_status hevcdl_set_source_format(hevcdl_ctx *ctx, const hevcdl_source_format *fmt);
+/* source-format frames -> coded-format frames of the context (host buffers: upload, kernel, download; device buffers: asynchronous on `stream`, pointers sample aligned) */
+hevcdl_status hevcdl_load_source(hevcdl_ctx *ctx, const void *src, int n_frames, void *coded_out);
+hevcdl_status hevcdl_load_source_dev(hevcdl_ctx *ctx, const void *d_src, int n_frames, void *d_coded, void *stream);
+/* coded-format pictures -> output-format frames (window size, output depth) */
+hevcdl_status hevcdl_store_output(hevcdl_ctx *ctx, const void *pictures, int n_frames, void *out);
+hevcdl_status hevcdl_store_output_dev(hevcdl_ctx *ctx, const void *d_pictures, int n_frames, void *d_out, void *stream);
+/* Output-format frames of pictures [first, first + count) of the LAST hevcdl_encode_pictures / _chunked / _stream call of a context with a source format, cropped and scaled on
+ * the device from the pictures still in HBM -- valid inside the chunk callback and after the call returns.  A run that needs its pictures for the reconstruction file only
+ * (hevcdl_encode_pictures_stream without want_pictures, the report on) fetches the window at the output depth this way instead of the coded pictures. */
+hevcdl_status hevcdl_get_output_frames(hevcdl_ctx *ctx, int first, int count, void *out);
+/* The same on the CPU, by the same source (csrc/source_core.h), without a context or a GPU: coded_width x coded_height at internal_bit_depth (8 .. 16) is the coded format. */
+hevcdl_status hevcdl_load_source_host(const hevcdl_source_format *fmt, int coded_width, int coded_height, int internal_bit_depth, const void *src, int n_frames, void *coded_out);
+hevcdl_status hevcdl_store_output_host(const hevcdl_source_format *fmt, int coded_width, int coded_height, int internal_bit_depth, const void *pictures, int n_frames, void *out);
+
 /* ---- bitstream writer (host side; no GPU needed) ---------------------------------------------------
  * One access unit per picture exactly as the reference emits it for its all-intra configuration: VPS, SPS, PPS
  * (ReWriteParamSetsFlag 1), then one slice NAL (IDR_W_RADL for POC 0, CRA afterwards), Annex B start codes.
@@ -350,6 +391,9 @@ typedef struct hevcdl_stream_config {
   int32_t  wavefront;            /* WaveFrontSynchro (default 0): 1 = entropy_coding_sync_enabled_flag, one sub-stream per CTU row with entry points in the slice header, every row
                                     starting from the contexts behind the second CTU of the row above (TEncSlice.cpp:1047-1145); the records must come from a context with
                                     hevcdl_config.wavefront 1.  Not together with tiles (the reference refuses the pair in the main profiles) */
+  int32_t  conf_win_right, conf_win_bottom;   /* conformance window in LUMA samples (default 0): the right and lower padding of a picture whose source size is no multiple of
+                                    the minimum CU (hevcdl_source_format); both even.  The SPS carries them in chroma units, conf_win_right_offset = right / 2
+                                    (TEncCavlc.cpp:526-535); a decoder then outputs width - right by height - bottom */
                                  /* (LFCrossSliceBoundaryFlag has no field: without slices -- SliceMode 0, the only mode of this path -- the reference sets it to 1 whatever the cfg
                                     says, TAppEncTop.cpp:278-281; tests/golden/stream_c192_q32.npz pins that) */
 } hevcdl_stream_config;
