@@ -407,8 +407,8 @@ EC_FN void ec_code_transform_tree(EcCoder &s, const EcPic &p, const EcCu &cu)
 EC_FN void ec_code_sao_offset(EcCoder &s, int comp, const hevcdl_sao_offset &p, int max_off)
 {
   const int first = comp != 2;
-  if (first) {
-    if (p.mode == 0) ec_bin(s, CTX_SAO_TYPE, 0);
+  if (first) {   // anything but "new" is written as off: a merge reaches this only where its candidate does not exist (ec_code_sao_blk), and sao() cannot say that
+    if (p.mode != 1) ec_bin(s, CTX_SAO_TYPE, 0);
     else { ec_bin(s, CTX_SAO_TYPE, 1); ec_ep(s, p.type == 4 ? 0 : 1); }
   }
   if (p.mode != 1) return;

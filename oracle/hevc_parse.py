@@ -97,10 +97,11 @@ def parse_pps(n):
     if f["cu_qp_delta"]:
         f["diff_cu_qp_delta_depth"] = r.ue()
     f["cb_off"] = r.se(); f["cr_off"] = r.se(); f["slice_chroma_off"] = r.u(1); f["wp"] = r.u(1); f["wbp"] = r.u(1)
-    f["tq_bypass"] = r.u(1); f["tiles_enabled"] = r.u(1); f["wpp"] = r.u(1); assert not f["wpp"]
+    f["tq_bypass"] = r.u(1); f["tiles_enabled"] = r.u(1); f["wpp"] = r.u(1)
     if f["tiles_enabled"]:
         f["tile_columns"] = r.ue() + 1; f["tile_rows"] = r.ue() + 1; f["uniform_spacing"] = r.u(1)
-        assert f["uniform_spacing"]
+        if not f["uniform_spacing"]:      # sizes in CTBs of every tile column / row but the last
+            f["column_widths"] = [r.ue() + 1 for _ in range(f["tile_columns"] - 1)]; f["row_heights"] = [r.ue() + 1 for _ in range(f["tile_rows"] - 1)]
         f["lf_across_tiles"] = r.u(1)
     f["lf_across_slices"] = r.u(1); f["dbk_control"] = r.u(1)
     if f["dbk_control"]:
@@ -136,7 +137,7 @@ def parse_slice_header(n, sps, pps):
     if pps["lf_across_slices"]:             # deblocking on (and / or SAO): slice_loop_filter_across_slices_enabled_flag
         f["slice_lf_across_slices"] = r.u(1)
     f["entry_points"] = []
-    if pps.get("tiles_enabled"):
+    if pps.get("tiles_enabled") or pps.get("wpp"):
         n_entry = r.ue()
         if n_entry:
             bits = r.ue() + 1

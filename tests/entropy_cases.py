@@ -235,3 +235,203 @@ def garbage_sao(seed, ctus):
     import hevcdl_amd
     rng = np.random.default_rng(seed)
     return np.frombuffer(rng.integers(0, 256, ctus * 3 * hevcdl_amd.SAO_DTYPE.itemsize, dtype=np.uint8).tobytes(), hevcdl_amd.SAO_DTYPE).reshape(ctus, 3).copy()
+
+
+# ---- what a decoder can give back -----------------------------------------------------------------------------------------------------------------------
+def _walk_blocks(r, x0, y0, w, h):
+    """The transform blocks of one CTU record, by its depth map and tr_idx alone: (component, first coefficient, log2 of the block, prediction mode that picks its
+    scan) for every block whose cbf bit is set.  Recursive over both trees, in any order: only the set of blocks matters here."""
+    out = []
+
+    def tu(z, zrel, log2, trd, np_cu, luma0):
+        zz = z + zrel
+        if log2 > 5 or (log2 > 2 and r["tr_idx"][zz] > trd):
+            for i in range(4):
+                tu(z, zrel + i * ((np_cu >> (2 * trd)) >> 2), log2 - 1, trd + 1, np_cu, luma0)
+            return
+        cd = int(r["chroma_dir"][z])
+        mode_c = luma0 if cd == 36 else cd
+        if (r["cbf"][0][zz] >> trd) & 1:
+            out.append((0, zz * 16, log2, int(r["luma_dir"][zz])))
+        for c in (1, 2):
+            if log2 > 2 and (r["cbf"][c][zz] >> trd) & 1:
+                out.append((c, zz * 4, log2 - 1, mode_c))
+            elif log2 == 2 and (zrel & 3) == 3 and (r["cbf"][c][zz] >> trd) & 1:
+                out.append((c, (z + (zrel & ~3)) * 4, 2, mode_c))
+
+    def cu(x, y, d, z):
+        if x >= w or y >= h:
+            return
+        size = 64 >> d
+        if d < 3 and (r["depth"][z] > d or x + size > w or y + size > h):
+            for i in range(4):
+                cu(x + (i & 1) * (size >> 1), y + (i >> 1) * (size >> 1), d + 1, z + i * (256 >> (2 * d + 2)))
+            return
+        tu(z, 0, 6 - d, 0, 256 >> (2 * d), int(r["luma_dir"][z]))
+    cu(x0, y0, 0, 0)
+    return out
+
+
+def canonical(cfg, recs, sao, mask, counts=None):
+    """What a decoder of the slice data can give back of records [ctus] and SAO parameters [ctus, 3] (or None): -> (records, SAO parameters).  mask: the decoder's
+    [ctus, 3, 256] mask of the tskip entries whose flag was in the stream.  counts: an optional dict that receives how many hidden signs differed from the input's.
+    Dropped or changed, each because the bitstream does not carry it:
+      * bits, dist, cost: statistics of the decision, never coded;
+      * tskip outside the mask: transform_skip_flag exists only for 4x4 blocks with a coded coefficient and transform_skip_enabled_flag; the records of a larger
+        block's partitions, of a block without coefficients and of the three further partitions of a 4x4 chroma block hold values no syntax element says;
+      * the sign of the coefficient at the lowest scan position of a coefficient group whose first and last significant scan positions are at least 4 apart, with
+        HEVCDL_TOOL_SIGN_HIDE: 7.3.8.11 sends no coeff_sign_flag for it, a decoder takes the parity of the group's absolute sum (odd: negative).  A level of -32768
+        there that the parity turns positive does not fit 16 bits; as an int16 it reads -32768 again (the decoder counts such levels in level_out_of_range);
+      * SAO: a merge candidate that does not exist cannot be named by the syntax -- the coder writes such a CTU as SAO off (mode 0) for all three components;
+        of a merged CTU only mode 2 and left / above (in component 0) are coded; of a component that is off nothing but mode 0; of an edge offset only the
+        magnitude (classes 0, 1 positive, 3, 4 negative by 7.4.9.3.2, class 2 none); of the 32 band offsets only the four from the band position on (modulo 32);
+        Cr shares mode and edge class with Cb (sao_type_idx_chroma, sao_eo_class_chroma are coded once)."""
+    import slice_spec as ss
+    out = recs.copy()
+    out["bits"], out["dist"], out["cost"] = 0, 0, 0
+    out["tskip"] = np.where(mask, recs["tskip"], 0)
+    w, h = cfg.width, cfg.height
+    cx = (w + 63) // 64
+    differed = 0
+    if cfg.tools & 0x10:
+        for a in range(len(out)):
+            r = out[a]
+            for comp, base, log2, mode in _walk_blocks(recs[a], (a % cx) * 64, (a // cx) * 64, w, h):
+                plane = r[("coeff_y", "coeff_cb", "coeff_cr")[comp]]
+                n = 1 << log2
+                for sub in ss.block_scan(log2, ss.scan_idx_of(log2, comp, mode)):
+                    vals = [int(plane[base + y * n + x]) for x, y in sub]
+                    nz = [k for k, v in enumerate(vals) if v]
+                    if nz and nz[-1] - nz[0] >= 4:
+                        x, y = sub[nz[0]]
+                        mag = abs(vals[nz[0]])
+                        new = -mag if sum(abs(v) for v in vals) & 1 else mag
+                        differed += (new < 0) != (vals[nz[0]] < 0)
+                        plane[base + y * n + x] = np.int64(new).astype(np.int16)
+    if counts is not None:
+        counts["hidden_sign_differed"] = counts.get("hidden_sign_differed", 0) + differed
+    if sao is None:
+        return out, None
+    import hevcdl_amd
+    n_sub, _, _, _ = hevcdl_amd.slice_data_layout(cfg)
+    _, _, _, cb, rb = hevcdl_amd.tile_layout(tiles_of_cfg(cfg), w, h)
+    s = np.zeros_like(sao)
+    for a in range(sao.shape[0]):
+        p = sao[a]
+        if p[0]["mode"] == 2:
+            rx, ry = a % cx, a // cx
+            have = (rx > 0 and rx not in cb) if p[0]["type"] == 0 else (ry > 0 and ry not in rb)
+            if have and p[0]["type"] in (0, 1):
+                s[a, 0]["mode"], s[a, 0]["type"] = 2, p[0]["type"]
+            continue
+        for c in range(3):
+            src = p[c]
+            if (p[1] if c == 2 else src)["mode"] != 1 if c == 2 else src["mode"] != 1:
+                continue
+            s[a, c]["mode"] = 1
+            ty = int(p[1]["type"]) if c == 2 else int(src["type"])
+            if ty == 4:
+                s[a, c]["type"], s[a, c]["aux"] = 4, src["aux"] & 31
+                for i in range(4):
+                    k = (int(src["aux"]) + i) & 31
+                    s[a, c]["offset"][k] = src["offset"][k]
+            else:
+                s[a, c]["type"] = ty
+                for i, cls in enumerate((0, 1, 3, 4)):
+                    s[a, c]["offset"][cls] = abs(int(src["offset"][cls])) * (1 if i < 2 else -1)
+    return out, s
+
+
+def tiles_of_cfg(cfg):
+    """The tiles argument of stream_config back from a configuration: explicit sizes in CTUs of every tile column / row."""
+    cx, cy = (cfg.width + 63) // 64, (cfg.height + 63) // 64
+    if cfg.tile_uniform_spacing:
+        return (cfg.tile_columns, cfg.tile_rows)
+    cw = [cfg.tile_column_width[i] for i in range(cfg.tile_columns - 1)]
+    rh = [cfg.tile_row_height[i] for i in range(cfg.tile_rows - 1)]
+    return (cw + [cx - sum(cw)], rh + [cy - sum(rh)])
+
+
+@functools.lru_cache(maxsize=None)
+def directed_pictures():
+    """Seeded pictures for what fuzz_corpus cannot reach: tile COLUMNS (a tile column is at least four CTUs wide, so the picture is eight: the left neighbour of a
+    CTU, a CU and a prediction block lies in another tile; the reference decoder takes it too), a 3x3-CTU
+    wavefront picture with SAO and a 10-bit picture with two tile rows and SAO (both also decoded from the device coder's output)."""
+    import hevcdl_amd
+    rng = np.random.default_rng(20240907)
+    out = []
+    for name, w, h, bd, kw in (("d0_456x64_t2x1", 456, 64, 8, {"tiles": (2, 1)}), ("d1_136x136_wpp", 136, 136, 8, {"wavefront": True}), ("d2_136x200_t1x2", 136, 200, 10, {"tiles": (1, 2)})):
+        cfg = hevcdl_amd.stream_config(w, h, int(rng.integers(20, 40)), sao=True, bit_depth=bd, **kw)
+        recs = synth_records(rng, w, h)[None]
+        out.append((name, cfg, recs, synth_sao(rng, recs.shape[1], bd)[None]))
+    return out
+
+
+# One-CTU pictures (64x64, QP 30, one sub-stream) whose slice data ends on, one byte behind and one byte before a boundary of the device coder's 256-byte output stage,
+# and with 1, 2 and 3 bytes in the last dword: (seed of synth_records, length in bytes).  Found by a search over the seeds 1, 2, 3, ...; the tests assert the residues.
+STAGE_SEEDS = {"on_boundary": (104, 1792), "one_past": (217, 1793), "one_before": (97, 1535), "tail_1": (3, 1041), "tail_2": (2, 898), "tail_3": (7, 1311)}
+
+
+def stage_picture(kind):
+    import hevcdl_amd
+    seed, length = STAGE_SEEDS[kind]
+    return hevcdl_amd.stream_config(64, 64, 30), synth_records(np.random.default_rng(seed), 64, 64)[None], length
+
+
+def flat_picture():
+    """8x8, every cbf zero, DC prediction: the whole slice data is two or three bytes."""
+    import hevcdl_amd
+    recs = np.zeros((1, 1), hevcdl_amd.REC_DTYPE)
+    recs["depth"][..., 0:4] = 3
+    recs["luma_dir"][..., 0:4] = 1
+    recs["chroma_dir"][..., 0:4] = 36
+    return hevcdl_amd.stream_config(8, 8, 30), recs
+
+
+def substreams_of(coded, poc=0):
+    """code_slice_data's result -> the sub-streams of picture poc as byte strings (none may have overflowed)."""
+    buf, sizes, ovf, off, cap = coded
+    assert not ovf[poc].any()
+    return [buf[poc, int(o):int(o) + int(n)].tobytes() for o, n in zip(off, sizes[poc])]
+
+
+_DECODED = {}
+
+
+def cached_decode_picture(subs, width, height, qp, tools, bit_depth, col_bd, row_bd, wavefront, sao, strict_levels=False, **sps):
+    """slice_spec.decode_picture behind a table of its results: the decoder is deterministic and slow, so the same bytes with the same parameters -- the same picture
+    coming from another writer or through the access-unit entry -- are decoded once.  Callers do not change what they get."""
+    import slice_spec
+    key = (tuple(subs), width, height, qp, tools & 0x14, bit_depth, tuple(col_bd), tuple(row_bd), bool(wavefront), bool(sao), bool(strict_levels), tuple(sorted(sps.items())))
+    if key not in _DECODED:
+        try:
+            _DECODED[key] = slice_spec.decode_picture(subs, width, height, qp, tools, bit_depth, col_bd, row_bd, wavefront, sao, strict_levels=strict_levels, **sps)
+        except slice_spec.SliceError as e:
+            _DECODED[key] = e
+    if isinstance(_DECODED[key], Exception):
+        raise _DECODED[key]
+    return _DECODED[key]
+
+
+SPS_OF_THE_PRODUCT = {"min_cb_log2": 3, "ctb_log2": 6, "min_tb_log2": 2, "max_tb_log2": 5, "max_th_depth_intra": 2}      # what the access-unit entry reads from the SPS
+
+
+def decode_substreams(cfg, subs, strict_levels=False):
+    """The decoder's picture entry for sub-streams coded under cfg -> (records, SAO parameters, tskip mask, tally)."""
+    import hevcdl_amd
+    _, _, _, cb, rb = hevcdl_amd.tile_layout(tiles_of_cfg(cfg), cfg.width, cfg.height)
+    return cached_decode_picture(subs, cfg.width, cfg.height, cfg.qp, cfg.tools, cfg.bit_depth, cb, rb, bool(cfg.wavefront), bool(cfg.sao_enabled), strict_levels=strict_levels, **SPS_OF_THE_PRODUCT)
+
+
+RT_FIELDS = ("depth", "part_size", "luma_dir", "chroma_dir", "tr_idx", "cbf", "tskip", "coeff_y", "coeff_cb", "coeff_cr")
+
+
+def assert_round_trip(name, cfg, recs, sao, decoded, counts=None):
+    """The decoder's result == the canonical form of the coder's input, field by field."""
+    got, gsao, mask, _ = decoded
+    want, wsao = canonical(cfg, recs, sao, mask, counts)
+    for k in RT_FIELDS:
+        assert np.array_equal(got[k], want[k]), "%s: %s differs at %s" % (name, k, np.argwhere(got[k] != want[k])[:4].tolist())
+    assert (gsao is None) == (wsao is None)
+    if wsao is not None:
+        assert np.array_equal(gsao, wsao), "%s: SAO parameters differ at CTU %s" % (name, [a for a in range(len(wsao)) if not np.array_equal(gsao[a], wsao[a])][:4])

@@ -231,3 +231,85 @@ def test_cli_device_entropy_changes_no_output(extra, tmp_path):
         outs.append(((tmp_path / (tag + ".bin")).read_bytes(), b"" if nofiles else (tmp_path / (tag + ".yuv")).read_bytes(), b"" if nofiles else (tmp_path / (tag + ".rec")).read_bytes(), log))
     assert outs[0][0] == outs[1][0] and len(outs[0][0]) > 1000
     assert outs[0][1] == outs[1][1] and outs[0][2] == outs[1][2] and outs[0][3] == outs[1][3]
+
+
+# ---- the device coder's bytes through the decoder (oracle/slice_spec.py), and the edges of its output staging ----------------------------------------------
+def _device_round_trip(name, cfg, recs, sao):
+    import hevcdl_amd
+    dev = hevcdl_amd.code_slice_data(cfg, recs, sao, device=0)
+    ec.check_guard(dev)
+    decoded = ec.decode_substreams(cfg, ec.substreams_of(dev))            # straight from the device's buffer: the host instantiation is not in between
+    ec.assert_round_trip(name, cfg, recs[0], None if sao is None else sao[0], decoded)
+
+
+@pytest.mark.parametrize("size", ["8x8", "64x8", "8x72", "72x72"])
+def test_device_round_trip_of_the_small_corpus_pictures(size):
+    """Every corpus picture of at most 4 CTUs (34 per size): what the decoder reads out of the device coder's sub-streams is the canonical form of the input."""
+    picks = [c for c in ec.fuzz_corpus() if c[0].endswith("_" + size)]
+    assert len(picks) == 34
+    for name, cfg, recs, sao in picks:
+        _device_round_trip(name, cfg, recs, sao)
+
+
+@pytest.mark.parametrize("which", [1, 2], ids=["wavefront_3x3_sao", "two_tile_rows_10bit_sao"])
+def test_device_round_trip_of_the_two_launch_path_and_a_tile_origin(which):
+    name, cfg, recs, sao = ec.directed_pictures()[which]
+    assert (cfg.wavefront == 1 and recs.shape[1] == 9) if which == 1 else (cfg.tile_rows == 2 and (cfg.width, cfg.height) == (136, 200))
+    _device_round_trip(name, cfg, recs, sao)
+
+
+@pytest.mark.parametrize("kind", sorted(ec.STAGE_SEEDS))
+def test_stage_edges(kind):
+    """One sub-stream that ends on, one byte behind and one byte before a 256-byte stage boundary, and with 1, 2, 3 bytes in its last dword: first the host
+    instantiation confirms the residue the committed seed is there for, then the device gives the same bytes and length inside intact canaries."""
+    import hevcdl_amd
+    cfg, recs, length = ec.stage_picture(kind)
+    host = hevcdl_amd.code_slice_data(cfg, recs)
+    assert host[1].shape == (1, 1) and int(host[1][0, 0]) == length > 256
+    want = {"on_boundary": length % 256 == 0, "one_past": length % 256 == 1, "one_before": length % 256 == 255, "tail_1": length % 4 == 1, "tail_2": length % 4 == 2, "tail_3": length % 4 == 3}
+    assert want[kind]
+    dev = hevcdl_amd.code_slice_data(cfg, recs, device=0)
+    ec.check_guard(dev)
+    assert int(dev[1][0, 0]) == length and not dev[2].any() and ec.substreams_of(dev) == ec.substreams_of(host)
+
+
+def test_stage_edges_short_substream_and_a_later_wave():
+    """A sub-stream shorter than one dword (a flat 8x8 picture: 3 bytes), and five stage-edge pictures in one launch: waves 1, 2 and 3 of the first workgroup and
+    wave 0 of a second one code an edge case too, not only the launch's first wave."""
+    import hevcdl_amd
+    cfg, recs = ec.flat_picture()
+    host, dev = hevcdl_amd.code_slice_data(cfg, recs), hevcdl_amd.code_slice_data(cfg, recs, device=0)
+    ec.check_guard(dev)
+    assert 2 <= int(host[1][0, 0]) < 4 and same_coded(dev, host) and ec.substreams_of(dev) == ec.substreams_of(host)
+    cfg, last, length = ec.stage_picture("on_boundary")
+    batch = np.concatenate([ec.stage_picture(k)[1] for k in ("tail_1", "tail_2", "tail_3", "one_before")] + [last])
+    host, dev = hevcdl_amd.code_slice_data(cfg, batch), hevcdl_amd.code_slice_data(cfg, batch, device=0)
+    ec.check_guard(dev)
+    assert int(dev[1][4, 0]) == length and same_coded(dev, host)
+    assert [ec.substreams_of(dev, f) for f in range(5)] == [ec.substreams_of(host, f) for f in range(5)]
+
+
+@pytest.mark.parametrize("kind", ["tail_3", "one_past", "on_boundary"])
+def test_capacity_edges(kind):
+    """The region's capacity c on and beside the true length L rounded down to a dword (L4) and the last stage boundary below L (B): the reported size is L, the overflow
+    word is set exactly when L > c, the stored bytes are the head of the full stream, the canaries (inside the allocation, as in the tests above) are intact, and the
+    device result is the host's."""
+    import hevcdl_amd
+    cfg, recs, length = ec.stage_picture(kind)
+    full = ec.substreams_of(hevcdl_amd.code_slice_data(cfg, recs))[0]
+    assert len(full) == length
+    l4, b = length & ~3, ((length - 1) // 256) * 256
+    seen = set()
+    for c in sorted({l4 - 4, l4, l4 + 4, b - 4, b, b + 4}):
+        cpc = c - 64                                                      # one CTU: its region holds capacity_per_ctu + 64 bytes
+        assert cpc > 0 and cpc % 4 == 0 and int(hevcdl_amd.slice_data_layout(cfg, cpc)[3][0]) == c
+        host, dev = hevcdl_amd.code_slice_data(cfg, recs, capacity_per_ctu=cpc), hevcdl_amd.code_slice_data(cfg, recs, capacity_per_ctu=cpc, device=0)
+        for coded in (host, dev):
+            ec.check_guard(coded)
+            buf, sizes, ovf, off, cap = coded
+            assert int(cap[0]) == c and int(sizes[0, 0]) == length and bool(ovf[0, 0]) == (length > c)
+            n = min(length, c)
+            assert buf[0, int(off[0]):int(off[0]) + n].tobytes() == full[:n]
+        assert same_coded(dev, host)
+        seen.add(length > c)
+    assert seen == {False, True}
