@@ -10,32 +10,23 @@
 #include "entropy_coder.h"
 #include "picture_hash_core.h"
 #include "source_core.h"
+#include "rd_launch_plan.h"
+
+enum { LABELS_PER_CTU = 16, LOGITS_PER_CTU = 64, CTU_RGB_BYTES = 64 * 64 * 3 };      // of a CTU: its 16x16 cells, four logits a cell, the RGB input of hevcdl_predict_depth_rgb
 
 extern "C" __global__ void hevcdl_cnn_ctu_kernel(hevcdl_cnn_params p);
 extern "C" __global__ void hevcdl_fc_kernel(hevcdl_fc_params p);          // fc_kernel.hip: fully connected head + labels, 16 CTUs per workgroup
-extern "C" __global__ void hevcdl_rd_frame_kernel(hevcdl_rd_params p);            // (its hevcdl_rd_smem_bytes / _scratch_bytes / _waves_per_group: hevcdl_dev.h)
-extern "C" __global__ void hevcdl_rd_frame_kernel_bd10(hevcdl_rd_params p);       // rd_kernel_bd10.hip: the same kernel for uint16 samples
-extern "C" size_t hevcdl_rd_smem_bytes_bd10(void);
-extern "C" size_t hevcdl_rd_scratch_bytes_bd10(void);
-extern "C" int hevcdl_rd_waves_per_group_bd10(void);
-extern "C" __global__ void hevcdl_rd_frame_kernel_wide(hevcdl_rd_params p);       // rd_kernel_wide.hip: the 8-bit kernel with more wavefronts per workgroup
-extern "C" size_t hevcdl_rd_smem_bytes_wide(void);
-extern "C" size_t hevcdl_rd_scratch_bytes_wide(void);
-extern "C" int hevcdl_rd_waves_per_group_wide(void);
-extern "C" __global__ void hevcdl_rd_frame_kernel_tools(hevcdl_rd_params p);      // rd_kernel_tools.hip: the 8-bit kernel with the cfg's tool switches read at run time
-extern "C" size_t hevcdl_rd_smem_bytes_tools(void);
-extern "C" size_t hevcdl_rd_scratch_bytes_tools(void);
-extern "C" int hevcdl_rd_waves_per_group_tools(void);
+// the decision kernel's builds: rd_kernel.hip (its hevcdl_rd_smem_bytes / _scratch_bytes / _waves_per_group: hevcdl_dev.h), and the same kernel for uint16 samples
+// (rd_kernel_bd10.hip), with more wavefronts per workgroup (rd_kernel_wide.hip) and with the cfg's tool switches read at run time (rd_kernel_tools.hip)
+extern "C" __global__ void hevcdl_rd_frame_kernel(hevcdl_rd_params p);
+#define RD_BUILD_DECL(sfx) extern "C" __global__ void hevcdl_rd_frame_kernel##sfx(hevcdl_rd_params p); extern "C" size_t hevcdl_rd_smem_bytes##sfx(void); \
+                           extern "C" size_t hevcdl_rd_scratch_bytes##sfx(void); extern "C" int hevcdl_rd_waves_per_group##sfx(void);
+RD_BUILD_DECL(_bd10) RD_BUILD_DECL(_wide) RD_BUILD_DECL(_tools)
 
-// The decision kernel's four builds.  Whatever depends on which of them a launch runs is read from its row (rd_build_of picks the row).
-struct RdBuild { const char *name; const void *kernel; size_t (*smem_bytes)(void); size_t (*scratch_bytes)(void); int (*waves_per_group)(void); };      // name: as hevcdl_last_rd_launch reports it; scratch_bytes: per wave
-enum { RD_NARROW, RD_WIDE, RD_TOOLS, RD_BD10, RD_BUILDS };
-static const RdBuild rd_builds[RD_BUILDS] = {
-  { "hevcdl_rd_frame_kernel", (const void *)hevcdl_rd_frame_kernel, hevcdl_rd_smem_bytes, hevcdl_rd_scratch_bytes, hevcdl_rd_waves_per_group },
-  { "hevcdl_rd_frame_kernel_wide", (const void *)hevcdl_rd_frame_kernel_wide, hevcdl_rd_smem_bytes_wide, hevcdl_rd_scratch_bytes_wide, hevcdl_rd_waves_per_group_wide },
-  { "hevcdl_rd_frame_kernel_tools", (const void *)hevcdl_rd_frame_kernel_tools, hevcdl_rd_smem_bytes_tools, hevcdl_rd_scratch_bytes_tools, hevcdl_rd_waves_per_group_tools },
-  { "hevcdl_rd_frame_kernel_bd10", (const void *)hevcdl_rd_frame_kernel_bd10, hevcdl_rd_smem_bytes_bd10, hevcdl_rd_scratch_bytes_bd10, hevcdl_rd_waves_per_group_bd10 },
-};
+// The decision kernel's four builds.  Whatever depends on which of them a launch runs is read from its row (rd_launch_plan.h picks the row and holds the names).
+struct RdBuild { const void *kernel; size_t (*smem_bytes)(void); size_t (*scratch_bytes)(void); int (*waves_per_group)(void); };      // scratch_bytes: per wave
+#define RD_BUILD_ROW(sfx) { (const void *)hevcdl_rd_frame_kernel##sfx, hevcdl_rd_smem_bytes##sfx, hevcdl_rd_scratch_bytes##sfx, hevcdl_rd_waves_per_group##sfx }
+static const RdBuild rd_builds[RD_BUILDS] = { RD_BUILD_ROW(), RD_BUILD_ROW(_wide), RD_BUILD_ROW(_tools), RD_BUILD_ROW(_bd10) };      // in the order of rd_launch_plan.h's RD_*
 
 // 10-bit samples -> the 8-bit planes the CNN stage reads (the reference's label producer works on 8-bit frames: gen_frames.py)
 __global__ void hevcdl_narrow_samples_kernel(const uint16_t *src, uint8_t *dst, size_t n, int shift)
@@ -66,62 +57,99 @@ __global__ void hevcdl_stats_sse_kernel(const hevcdl_quality *q, hevcdl_frame_st
   if (t < 3 * n_frames) stats[t / 3].sse[t % 3] = q[t / 3].sse[t % 3];
 }
 
-struct hevcdl_ctx {
-  char last_rd[160] = { 0 };           // which build and launch form the last decision launch took (hevcdl_last_rd_launch)
-  hevcdl_config cfg;
-  int ctus_x, ctus_y, ctus, n_cus;
-  int col_bd[21], row_bd[23];    // tile boundaries in CTUs
-  size_t frame_bytes;
-  float *d_weights;
-  unsigned char *d_scratch;      // decision kernel workspace: one block per wave of every workgroup of a launch; allocated by the first launch that needs it, grown when a later one needs more (ensure_scratch)
-  size_t scratch_bytes;
-  size_t scratch_per_wave; int rd_groups, remote_groups;   // workgroups of a launch: one per CU, fewer when the context cannot hold that many units
-  // staging buffers for the host-pointer entry points
-  uint8_t *d_yuv, *d_labels, *d_recon; unsigned char *d_records, *d_stats; float *d_logits; uint8_t *d_rgb; size_t rgb_cap;
-  uint8_t *d_yuv8;               // 8-bit copy of 10-bit input for the CNN stage
-  uint8_t *d_picture;            // final pictures of hevcdl_encode_pictures (SAO output)
-  unsigned char *h_chunk[2]; size_t h_chunk_bytes; hipStream_t copy_stream; hipEvent_t copy_ev[2];   // hevcdl_encode_pictures_chunked: two page-locked chunk buffers
-  float *d_a3; size_t a3_ctus;   // conv3 outputs of one chunk of CTUs (32 KB per CTU): the hand-over from the conv kernel to the head kernel
-  hipStream_t stream;
-  // per-CTU session (hevcdl_begin_frames / hevcdl_compress_ctu): coder state after the last CTU of every frame, next CTU expected
-  unsigned char *d_cabac; std::vector<int> next_ctu; int session_frames;
-  unsigned char *d_sao_stats, *d_sao_recon, *d_sao_params, *d_sao_cand;
-  unsigned char *d_wide;                 // 16-bit staging of hevcdl_*_planes with sample_bytes 2 on an 8-bit context   // SAO workspace
-  int *d_flag;                   // device-side error flag of the label check
-  int wpp_ring; size_t wpp_state_bytes;
-  unsigned char *d_wpp;          // WaveFrontSynchro: [max_frames][ctus_y] 256 bytes (the contexts behind a row's second CTU, the row's finished-CTU count: rd_kernel.hip)
-  unsigned char *d_sched;        // decision kernel: hand-over of units between workgroups (finished counter, per-workgroup unit counts, mailboxes)
-  // picture quality (quality_kernel.hip): the workspace is allocated by hevcdl_enable_quality(ctx, 1), or by the first hevcdl_picture_quality* call of a context
-  // with the switch off, and freed by hevcdl_enable_quality(ctx, 0); d_q_out by the switch or by hevcdl_picture_quality (host buffers).  A context that uses neither allocates none of it
+// Owners: a handle that is released in the destructor and in reset(), moves but does not copy, and converts to the handle.  Everything a context holds on the device
+// is one of these, so releasing a feature is assigning a fresh sub-struct and hevcdl_destroy is `delete`.
+template <class H, class Release> struct Owned {
+  H p = H();
+  Owned() = default;
+  Owned(Owned &&o) noexcept : p(o.p) { o.p = H(); }      // (a move constructor: no copies)
+  Owned &operator=(Owned &&o) noexcept { if (this != &o) { reset(); p = o.p; o.p = H(); } return *this; }
+  ~Owned() { reset(); }
+  void reset() { if (p) Release()(p); p = H(); }
+  operator H() const { return p; }
+};
+struct ReleaseDev { void operator()(void *p) const { hipFree(p); } };
+struct ReleaseHost { void operator()(void *p) const { hipHostFree(p); } };
+struct ReleaseEvent { void operator()(hipEvent_t e) const { hipEventDestroy(e); } };
+struct ReleaseStream { void operator()(hipStream_t s) const { hipStreamDestroy(s); } };
+template <class T> using DevBuf = Owned<T *, ReleaseDev>;      // hipMalloc'ed
+using HostBuf = Owned<unsigned char *, ReleaseHost>;           // page-locked
+using Event = Owned<hipEvent_t, ReleaseEvent>;
+using Stream = Owned<hipStream_t, ReleaseStream>;
+
+// The context's buffers, grouped by who allocates them (and who gives them back).
+struct Staging {      // staging buffers for the host-pointer entry points: the first six by ensure_staging (all or nothing), the rest by the first call that needs them
+  DevBuf<uint8_t> d_yuv, d_labels, d_recon; DevBuf<unsigned char> d_records, d_stats; DevBuf<float> d_logits;
+  DevBuf<uint8_t> d_yuv8;               // 8-bit copy of 10-bit input for the CNN stage
+  DevBuf<unsigned char> d_wide;         // 16-bit staging of hevcdl_*_planes with sample_bytes 2 on an 8-bit context
+  DevBuf<uint8_t> d_picture;            // final pictures of hevcdl_encode_pictures (SAO output)
+  HostBuf h_chunk[2]; size_t h_chunk_bytes = 0; Stream copy_stream; Event copy_ev[2];   // hevcdl_encode_pictures_chunked: two page-locked chunk buffers
+};
+struct SaoWorkspace { DevBuf<unsigned char> d_sao_stats, d_sao_recon, d_sao_params, d_sao_cand; };      // SAO workspace: by the first call that needs each
+// picture quality (quality_kernel.hip): the workspace is allocated by hevcdl_enable_quality(ctx, 1), or by the first hevcdl_picture_quality* call of a context
+// with the switch off, and freed by hevcdl_enable_quality(ctx, 0); d_q_out by the switch or by hevcdl_picture_quality (host buffers).  A context that uses neither allocates none of it
+struct Quality {
   bool quality_on = false;                 // hevcdl_enable_quality: the picture pipeline also measures its output pictures
-  unsigned char *d_q_pyr = nullptr, *d_q_partial = nullptr, *d_q_weights = nullptr, *d_q_out = nullptr; int q_group = 0;      // workspace of q_group pictures; d_q_out: [max_frames] hevcdl_quality of the pipeline
+  DevBuf<unsigned char> d_q_pyr, d_q_partial, d_q_weights, d_q_out; int q_group = 0;      // workspace of q_group pictures; d_q_out: [max_frames] hevcdl_quality of the pipeline
   std::vector<hevcdl_quality> h_quality;   // the pipeline's last batch (hevcdl_get_quality)
-  // picture report (report_kernel.hip): the workspace -- records, CRC / checksum partials and the SSE launch's output for max_frames pictures, a few KB a picture -- is
-  // allocated by hevcdl_enable_picture_report(ctx, 1, method), or by the first hevcdl_picture_report* call of a context with the switch off, and freed by (ctx, 0, 0)
+};
+// picture report (report_kernel.hip): the workspace -- records, CRC / checksum partials and the SSE launch's output for max_frames pictures, a few KB a picture -- is
+// allocated by hevcdl_enable_picture_report(ctx, 1, method), or by the first hevcdl_picture_report* call of a context with the switch off, and freed by (ctx, 0, 0)
+struct Report {
   bool report_on = false; int report_method = 0;
-  unsigned char *d_rp_out = nullptr, *d_rp_sse = nullptr; uint32_t *d_rp_partials = nullptr;
+  DevBuf<unsigned char> d_rp_out, d_rp_sse; DevBuf<uint32_t> d_rp_partials;
   std::vector<hevcdl_picture_report_t> h_report;      // the pipeline's last batch (hevcdl_get_picture_report)
-  hipEvent_t rp_ev[4] = { nullptr, nullptr, nullptr, nullptr }; double rp_ms[3] = { 0, 0, 0 };      // with `profile`: HIP-event times of the last report launches (SSE, partial or MD5, finish)
-  // slice data on the device (entropy_kernel.hip): everything below is allocated by hevcdl_enable_device_entropy(ctx, 1) and freed by (ctx, 0); a context that never
-  // turns the switch on allocates and launches none of it
+};
+// slice data on the device (entropy_kernel.hip): everything below is allocated by hevcdl_enable_device_entropy(ctx, 1) and freed by (ctx, 0); a context that never
+// turns the switch on allocates and launches none of it
+struct Entropy {
   bool entropy_on = false;
   int ec_units = 0, ec_pass_frames = 0; size_t ec_frame_stride = 0;        // sub-streams of a picture, pictures the workspace holds, bytes of a picture's regions
-  unsigned char *d_ec_tables = nullptr, *d_ec_ws = nullptr, *d_ec_packed = nullptr, *d_ec_sync = nullptr;
-  uint32_t *d_ec_off = nullptr, *d_ec_cap = nullptr, *d_ec_sizes = nullptr, *d_ec_ovf = nullptr; unsigned long long *d_ec_dst = nullptr;
+  DevBuf<unsigned char> d_ec_tables, d_ec_ws, d_ec_packed, d_ec_sync;
+  DevBuf<uint32_t> d_ec_off, d_ec_cap, d_ec_sizes, d_ec_ovf; DevBuf<unsigned long long> d_ec_dst;
   std::vector<uint32_t> ec_off, ec_cap;
   std::vector<uint8_t> h_slice; std::vector<uint32_t> h_slice_sizes; std::vector<size_t> h_slice_at;      // the last batch: packed sub-streams, [picture][unit] lengths, start of every picture (+ the end)
   int ec_fallbacks = 0;                    // pictures of the last batch the host writer coded (a sub-stream overflowed its region)
-  int ec_capacity_per_ctu = 0;             // hevcdl_set_entropy_capacity (tests): 0 = the default
-  double ec_ms[3] = { 0, 0, 0 };           // with `profile`: HIP-event times of the last batch (phase 1, coding, pack)
-  // source format (source_kernel.hip): everything below is allocated by hevcdl_set_source_format(ctx, fmt) and freed by (ctx, NULL); a context without one allocates
-  // and launches none of it.  d_src: max_frames frames of the larger of the source and the output format (the picture pipeline's upload; staging of the host entry
-  // points).  With padding (source_windowed) also the window crops at the internal depth of originals and pictures, and the SSE words of the statistics.
-  bool source_on = false, source_windowed = false; hevcdl_source_format src_fmt;
-  unsigned char *d_src = nullptr, *d_win_org = nullptr, *d_win_pic = nullptr, *d_win_sse = nullptr;
+};
+// source format (source_kernel.hip): everything below is allocated by hevcdl_set_source_format(ctx, fmt) and freed by (ctx, NULL); a context without one allocates
+// and launches none of it.  d_src: max_frames frames of the larger of the source and the output format (the picture pipeline's upload; staging of the host entry
+// points).  With padding (source_windowed) also the window crops at the internal depth of originals and pictures, and the SSE words of the statistics.
+struct Source {
+  bool source_on = false, source_windowed = false; hevcdl_source_format src_fmt = {};
+  DevBuf<unsigned char> d_src, d_win_org, d_win_pic, d_win_sse;
   const uint8_t *d_last_final = nullptr; int last_frames = 0;      // output pictures of the last picture pipeline call, still in HBM (hevcdl_get_output_frames)
-  bool profile;
-  std::vector<hipEvent_t> ev_cnn, ev_rd, ev_conv;       // start/stop pairs (ev_conv: the convolution kernel alone, one pair per chunk of CTUs)
-  char err[256];
+};
+// per-CTU session (hevcdl_begin_frames / hevcdl_compress_ctu): coder state after the last CTU of every frame, next CTU expected
+struct Session { DevBuf<unsigned char> d_cabac; std::vector<int> next_ctu; int session_frames = 0; };
+// the decision kernel's workspace and scheduling areas
+struct RdWorkspace {
+  RdPlanContext plan;                    // what rd_launch_plan reads of this context (rd_launch_plan.h)
+  DevBuf<unsigned char> d_scratch;       // one block per wave of every workgroup of a launch; allocated by the first launch that needs it, grown when a later one needs more (ensure_scratch)
+  size_t scratch_bytes = 0, scratch_per_wave = 0;      // scratch_per_wave: the largest of the builds this context can run
+  int wpp_ring = 0; size_t wpp_state_bytes = 0;
+  DevBuf<unsigned char> d_wpp;           // WaveFrontSynchro: [max_frames][ctus_y] 256 bytes (the contexts behind a row's second CTU, the row's finished-CTU count: rd_kernel.hip)
+  DevBuf<unsigned char> d_sched;         // hand-over of units between workgroups (finished counter, per-workgroup unit counts, mailboxes)
+};
+
+struct hevcdl_ctx {
+  char last_rd[160] = { 0 };           // which build and launch form the last decision launch took (hevcdl_last_rd_launch)
+  hevcdl_config cfg = {};
+  int ctus_x = 0, ctus_y = 0, ctus = 0, n_cus = 0; size_t frame_bytes = 0;
+  int col_bd[21] = { 0 }, row_bd[23] = { 0 };    // tile boundaries in CTUs
+  DevBuf<float> d_weights, d_a3; size_t a3_ctus = 0;   // d_a3: conv3 outputs of one chunk of CTUs (32 KB per CTU): the hand-over from the conv kernel to the head kernel
+  DevBuf<int> d_flag;                  // device-side error flag of the label check
+  Staging stage; SaoWorkspace sao; Quality q; Report rp; Entropy ec; Source src; Session ses; RdWorkspace rd;
+  int ec_capacity_per_ctu = 0;         // hevcdl_set_entropy_capacity (tests): 0 = the default; outlives the entropy switch
+  bool profile = false;
+  std::vector<Event> ev_cnn, ev_rd, ev_conv;       // start/stop pairs (ev_conv: the convolution kernel alone, one pair per chunk of CTUs)
+  Event rp_ev[4]; double rp_ms[3] = { 0, 0, 0 };      // with `profile`: HIP-event times of the last report launches (SSE, partial or MD5, finish)
+  double ec_ms[3] = { 0, 0, 0 };       // with `profile`: HIP-event times of the last entropy batch (phase 1, coding, pack)
+  char err[256] = { 0 };
+  // sizes of a batch of n frames
+  size_t records_bytes(size_t n) const { return (size_t)ctus * sizeof(hevcdl_ctu_record) * n; }
+  size_t labels_bytes(size_t n) const { return (size_t)ctus * LABELS_PER_CTU * n; }
+  size_t logits_bytes(size_t n) const { return (size_t)ctus * LOGITS_PER_CTU * sizeof(float) * n; }
+  size_t sao_bytes(size_t n) const { return (size_t)ctus * sizeof(hevcdl_sao_blk) * n; }
 };
 
 static const int CHROMA_SCALE_420[58] = { 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29,
@@ -135,6 +163,48 @@ static hevcdl_status fail(hevcdl_ctx *c, hevcdl_status s, const char *what, hipE
   return s;
 }
 #define HIPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(ctx, HEVCDL_ERR_HIP, #call, e_); } while (0)
+
+// The one mapping of a HIP error to a status, and the one way an allocation (or the upload that fills it) fails: the sticky error is cleared, the message is `what`.
+static hevcdl_status hip_status(hipError_t e) { return e == hipErrorOutOfMemory ? HEVCDL_ERR_OOM : HEVCDL_ERR_HIP; }
+static hevcdl_status hip_fail(hevcdl_ctx *c, const char *what, hipError_t e) { (void)hipGetLastError(); return fail(c, hip_status(e), what, e); }
+struct AllocItem { void **slot; size_t bytes; };
+template <class T> static AllocItem want(DevBuf<T> &b, size_t bytes) { return { (void **)&b.p, bytes }; }
+// A set of (empty) buffers, all or nothing: a partial set would let later calls run on null buffers (records alone are 63 GB at 2048 frames of 2160p)
+static hevcdl_status alloc_all(hevcdl_ctx *c, std::initializer_list<AllocItem> items, const char *what)
+{
+  for (const AllocItem &it : items) {
+    const hipError_t e = hipMalloc(it.slot, it.bytes);
+    if (e == hipSuccess) continue;
+    for (const AllocItem &u : items) { if (&u == &it) break; hipFree(*u.slot); *u.slot = nullptr; }
+    *it.slot = nullptr;
+    return hip_fail(c, what, e);
+  }
+  return HEVCDL_OK;
+}
+// a buffer allocated by the first call that needs it
+template <class T> static hevcdl_status lazy_alloc(hevcdl_ctx *c, DevBuf<T> &b, size_t bytes, const char *what)
+{
+  if (b) return HEVCDL_OK;
+  const hipError_t e = hipMalloc(&b.p, bytes);
+  return e == hipSuccess ? HEVCDL_OK : hip_fail(c, what, e);
+}
+#define TRY(call) do { hevcdl_status st_ = (call); if (st_) return st_; } while (0)
+// the device of the entries that take no context
+static hevcdl_status select_device(int device)
+{
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0 || device < 0 || device >= n) { (void)hipGetLastError(); return HEVCDL_ERR_NO_DEVICE; }
+  if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return HEVCDL_ERR_HIP; }
+  return HEVCDL_OK;
+}
+// the error of the launches just made, if any
+static hevcdl_status launch_status(hevcdl_ctx *ctx) { HIPCHK(hipGetLastError()); return HEVCDL_OK; }
+// the context's device, idle: behind the launches of a host wrapper, in front of giving buffers back
+static hevcdl_status sync_or_fail(hevcdl_ctx *ctx, const char *what)
+{
+  hipError_t e = hipSetDevice(ctx->cfg.device); if (e == hipSuccess) e = hipDeviceSynchronize();
+  return e == hipSuccess ? HEVCDL_OK : fail(ctx, HEVCDL_ERR_HIP, what, e);
+}
 
 extern "C" int hevcdl_ctus_per_frame(int w, int h) { return ((w + 63) >> 6) * ((h + 63) >> 6); }
 extern "C" size_t hevcdl_frame_bytes(int w, int h) { return (size_t)w * h * 3 / 2; }
@@ -307,15 +377,13 @@ extern "C" hevcdl_status hevcdl_create(const hevcdl_config *cfg, const float *we
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device >= ndev) return HEVCDL_ERR_NO_DEVICE;
   hevcdl_ctx *ctx = new (std::nothrow) hevcdl_ctx();
   if (!ctx) return HEVCDL_ERR_OOM;
-  ctx->cfg = *cfg; ctx->err[0] = 0; ctx->profile = false;
+  ctx->cfg = *cfg;
   ctx->ctus_x = (cfg->width + 63) >> 6; ctx->ctus_y = (cfg->height + 63) >> 6; ctx->ctus = ctx->ctus_x * ctx->ctus_y;
   ctx->frame_bytes = hevcdl_frame_bytes_bd(cfg->width, cfg->height, cfg->bit_depth);
   hevcdl_tile_bounds(ctx->ctus_x, cfg->tile_columns, cfg->tile_uniform_spacing, cfg->tile_column_width, 1, ctx->col_bd);
   hevcdl_tile_bounds(ctx->ctus_y, cfg->tile_rows, cfg->tile_uniform_spacing, cfg->tile_row_height, 1, ctx->row_bd);
-  ctx->d_weights = nullptr; ctx->d_scratch = nullptr; ctx->scratch_bytes = 0; ctx->d_yuv = ctx->d_labels = ctx->d_recon = nullptr; ctx->d_records = ctx->d_stats = nullptr;
-  ctx->d_logits = nullptr; ctx->d_yuv8 = nullptr; ctx->d_a3 = nullptr; ctx->a3_ctus = 0; ctx->d_picture = nullptr; ctx->h_chunk[0] = ctx->h_chunk[1] = nullptr; ctx->h_chunk_bytes = 0; ctx->copy_stream = nullptr; ctx->copy_ev[0] = ctx->copy_ev[1] = nullptr; ctx->d_rgb = nullptr; ctx->rgb_cap = 0; ctx->stream = nullptr; ctx->d_cabac = nullptr; ctx->session_frames = 0; ctx->d_sao_stats = ctx->d_sao_recon = ctx->d_sao_params = ctx->d_sao_cand = nullptr; ctx->d_wide = nullptr; ctx->d_flag = nullptr; ctx->d_sched = nullptr;
   hipError_t e;
-#define CK(call) if ((e = (call)) != hipSuccess) { hevcdl_status s_ = (e == hipErrorOutOfMemory) ? HEVCDL_ERR_OOM : HEVCDL_ERR_HIP; hevcdl_destroy(ctx); return s_; }
+#define CK(call) if ((e = (call)) != hipSuccess) { hevcdl_status s_ = hip_status(e); hevcdl_destroy(ctx); return s_; }
   CK(hipSetDevice(cfg->device));
   { hipDeviceProp_t prop; CK(hipGetDeviceProperties(&prop, cfg->device)); ctx->n_cus = prop.multiProcessorCount; }
   std::vector<float> pk(HEVCDL_W_TOTAL);
@@ -336,29 +404,29 @@ extern "C" hevcdl_status hevcdl_create(const hevcdl_config *cfg, const float *we
   pack_fc1(weights + B_F1W, weights + B_F1B, pk.data() + HEVCDL_W_FC1, scf);
   pack_fc(weights + B_F2W, weights + B_F2B, 64, 256, pk.data() + HEVCDL_W_FC2);
   pack_fc(weights + B_F3W, weights + B_F3B, 16, 64, pk.data() + HEVCDL_W_FC3);
-  CK(hipMalloc(&ctx->d_flag, sizeof(int)));
-  CK(hipMalloc(&ctx->d_sched, 8192 + 1024 * 192));
-  ctx->d_wpp = nullptr;
+  CK(hipMalloc(&ctx->d_flag.p, sizeof(int)));
+  CK(hipMalloc(&ctx->rd.d_sched.p, 8192 + 1024 * 192));
   if (cfg->wavefront) { // per (frame, row) 256 bytes, then the queue of claimable rows: 1024 bytes of counters + a ring of one int per frame (rounded up to a power of two)
-    ctx->wpp_ring = 64; while (ctx->wpp_ring < cfg->max_frames) ctx->wpp_ring <<= 1;
-    ctx->wpp_state_bytes = (size_t)256 * ctx->ctus_y * cfg->max_frames;
-    CK(hipMalloc(&ctx->d_wpp, ctx->wpp_state_bytes + 1024 + (size_t)4 * ctx->wpp_ring));
+    ctx->rd.wpp_ring = 64; while (ctx->rd.wpp_ring < cfg->max_frames) ctx->rd.wpp_ring <<= 1;
+    ctx->rd.wpp_state_bytes = (size_t)256 * ctx->ctus_y * cfg->max_frames;
+    CK(hipMalloc(&ctx->rd.d_wpp.p, ctx->rd.wpp_state_bytes + 1024 + (size_t)4 * ctx->rd.wpp_ring));
   }
-  if (cfg->bit_depth > 8) CK(hipMalloc(&ctx->d_yuv8, hevcdl_frame_bytes(cfg->width, cfg->height) * (size_t)cfg->max_frames));    // the CNN stage's 8-bit copy
-  CK(hipMalloc(&ctx->d_weights, sizeof(float) * HEVCDL_W_TOTAL));
+  if (cfg->bit_depth > 8) CK(hipMalloc(&ctx->stage.d_yuv8.p, hevcdl_frame_bytes(cfg->width, cfg->height) * (size_t)cfg->max_frames));    // the CNN stage's 8-bit copy
+  CK(hipMalloc(&ctx->d_weights.p, sizeof(float) * HEVCDL_W_TOTAL));
   CK(hipMemcpy(ctx->d_weights, pk.data(), sizeof(float) * HEVCDL_W_TOTAL, hipMemcpyHostToDevice));
   for (int b = 0; b < RD_BUILDS; b++)       // the largest of the builds this context can run: the three 8-bit ones, or the 10-bit one
-    if ((b == RD_BD10) == (cfg->bit_depth != 8)) ctx->scratch_per_wave = std::max(ctx->scratch_per_wave, rd_builds[b].scratch_bytes());
-  ctx->rd_groups = (int)std::min<long long>(ctx->n_cus, (long long)cfg->max_frames * (cfg->wavefront ? ctx->ctus_y : cfg->tile_columns * cfg->tile_rows));
-  // (launches of few units run on every CU: the workgroups without a unit take second luma passes from the others, launch_rd -- they need a workspace too)
-  ctx->remote_groups = (cfg->bit_depth == 8 && !(cfg->exec_flags & HEVCDL_EXEC_NO_UNIT_HANDOVER) && ctx->n_cus >= 8 && ctx->n_cus <= 1024) ? ctx->n_cus : 0;
+    if ((b == RD_BD10) == (cfg->bit_depth != 8)) ctx->rd.scratch_per_wave = std::max(ctx->rd.scratch_per_wave, rd_builds[b].scratch_bytes());
+  { RdPlanContext &pc = ctx->rd.plan;      // what the launch plan reads (rd_launch_plan.h)
+    pc.n_cus = ctx->n_cus; pc.max_frames = cfg->max_frames; pc.bit_depth = cfg->bit_depth; pc.tools = cfg->tools; pc.exec_flags = cfg->exec_flags; pc.wavefront = cfg->wavefront;
+    pc.tile_columns = cfg->tile_columns; pc.tile_rows = cfg->tile_rows; pc.ctus_x = ctx->ctus_x; pc.ctus_y = ctx->ctus_y;
+    for (int b = 0; b < RD_BUILDS; b++) pc.waves[b] = rd_builds[b].waves_per_group(); }
   // (the workspace itself -- 1.6 MB per wave -- is sized by the launches: a context that only ever codes a frame or two in the independent form holds a few MB, not the
   // several GB a launch on every CU needs)
   CK(hipFuncSetAttribute((const void *)hevcdl_cnn_ctu_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hevcdl_cnn_smem_bytes()));
   CK(hipFuncSetAttribute((const void *)hevcdl_fc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hevcdl_fc_smem_bytes()));
   { // conv -> head hand-over buffer for one chunk of CTUs, allocated up front so that no step pays for it
     const size_t chunk = (size_t)std::min<long long>((long long)cfg->max_frames * ctx->ctus, 131072);
-    CK(hipMalloc(&ctx->d_a3, chunk * 4 * 2048 * sizeof(float))); ctx->a3_ctus = chunk;
+    CK(hipMalloc(&ctx->d_a3.p, chunk * 4 * 2048 * sizeof(float))); ctx->a3_ctus = chunk;
   }
   for (const RdBuild &b : rd_builds) CK(hipFuncSetAttribute(b.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b.smem_bytes()));
 #undef CK
@@ -371,61 +439,38 @@ extern "C" void hevcdl_destroy(hevcdl_ctx *ctx)
   if (!ctx) return;
   hipSetDevice(ctx->cfg.device);
   hipDeviceSynchronize();
-  for (hipEvent_t e : ctx->ev_cnn) hipEventDestroy(e);
-  for (hipEvent_t e : ctx->ev_rd) hipEventDestroy(e);
-  for (hipEvent_t e : ctx->ev_conv) hipEventDestroy(e);
-  for (int i = 0; i < 2; i++) { if (ctx->h_chunk[i]) hipHostFree(ctx->h_chunk[i]); if (ctx->copy_ev[i]) hipEventDestroy(ctx->copy_ev[i]); }
-  if (ctx->copy_stream) hipStreamDestroy(ctx->copy_stream);
-  hipFree(ctx->d_weights); hipFree(ctx->d_scratch); hipFree(ctx->d_yuv); hipFree(ctx->d_labels); hipFree(ctx->d_recon);
-  hipFree(ctx->d_wpp); hipFree(ctx->d_records); hipFree(ctx->d_stats); hipFree(ctx->d_logits); hipFree(ctx->d_yuv8); hipFree(ctx->d_a3); hipFree(ctx->d_picture); hipFree(ctx->d_rgb); hipFree(ctx->d_cabac); hipFree(ctx->d_sao_stats); hipFree(ctx->d_sao_recon); hipFree(ctx->d_sao_params); hipFree(ctx->d_sao_cand); hipFree(ctx->d_wide); hipFree(ctx->d_flag); hipFree(ctx->d_sched);
-  hipFree(ctx->d_q_pyr); hipFree(ctx->d_q_partial); hipFree(ctx->d_q_weights); hipFree(ctx->d_q_out);
-  hipFree(ctx->d_rp_out); hipFree(ctx->d_rp_sse); hipFree(ctx->d_rp_partials);
-  hipFree(ctx->d_src); hipFree(ctx->d_win_org); hipFree(ctx->d_win_pic); hipFree(ctx->d_win_sse);
-  for (hipEvent_t e : ctx->rp_ev) if (e) hipEventDestroy(e);
-  hipFree(ctx->d_ec_tables); hipFree(ctx->d_ec_ws); hipFree(ctx->d_ec_packed); hipFree(ctx->d_ec_sync); hipFree(ctx->d_ec_off); hipFree(ctx->d_ec_cap); hipFree(ctx->d_ec_sizes); hipFree(ctx->d_ec_ovf); hipFree(ctx->d_ec_dst);
   delete ctx;
 }
 
 extern "C" const char *hevcdl_last_error(const hevcdl_ctx *ctx) { return ctx ? ctx->err : "null ctx"; }
 
-// page-locked host memory for the buffers of the host-pointer entry points (optional: any host memory works, pinned memory copies faster)
 extern "C" hevcdl_status hevcdl_device_memory(int device, size_t *free_bytes, size_t *total_bytes)
 {
   if (!free_bytes || !total_bytes) return HEVCDL_ERR_INVALID_ARG;
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) { (void)hipGetLastError(); return HEVCDL_ERR_NO_DEVICE; }
-  if (hipSetDevice(device) != hipSuccess || hipMemGetInfo(free_bytes, total_bytes) != hipSuccess) { (void)hipGetLastError(); return HEVCDL_ERR_HIP; }
+  TRY(select_device(device));
+  if (hipMemGetInfo(free_bytes, total_bytes) != hipSuccess) { (void)hipGetLastError(); return HEVCDL_ERR_HIP; }
   return HEVCDL_OK;
 }
+// page-locked host memory for the buffers of the host-pointer entry points (optional: any host memory works, pinned memory copies faster)
 extern "C" void *hevcdl_host_alloc(size_t bytes) { void *p = nullptr; return hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault) == hipSuccess ? p : nullptr; }
 extern "C" void hevcdl_host_free(void *p) { if (p) hipHostFree(p); }
 
 static hevcdl_status ensure_staging(hevcdl_ctx *ctx)
 {
-  if (ctx->d_yuv) return HEVCDL_OK;
+  if (ctx->stage.d_yuv) return HEVCDL_OK;
   const size_t nf = (size_t)ctx->cfg.max_frames;
-  // all or nothing: a partial set would let later calls run on null buffers (records alone are 63 GB at 2048 frames of 2160p)
-  void **bufs[6] = { (void **)&ctx->d_recon, (void **)&ctx->d_labels, (void **)&ctx->d_logits, (void **)&ctx->d_records, (void **)&ctx->d_stats, (void **)&ctx->d_yuv };
-  const size_t sizes[6] = { ctx->frame_bytes * nf, (size_t)ctx->ctus * 16 * nf, (size_t)ctx->ctus * 64 * sizeof(float) * nf, (size_t)ctx->ctus * sizeof(hevcdl_ctu_record) * nf,
-                            sizeof(hevcdl_frame_stats) * nf, ctx->frame_bytes * nf };
-  for (int i = 0; i < 6; i++) {
-    const hipError_t e = hipMalloc(bufs[i], sizes[i]);
-    if (e != hipSuccess) {
-      for (int j = 0; j <= i; j++) { hipFree(*bufs[j]); *bufs[j] = nullptr; }
-      (void)hipGetLastError();
-      return fail(ctx, e == hipErrorOutOfMemory ? HEVCDL_ERR_OOM : HEVCDL_ERR_HIP, "staging buffers (cfg.max_frames)", e);
-    }
-  }
-  return HEVCDL_OK;
+  Staging &g = ctx->stage;
+  return alloc_all(ctx, { want(g.d_recon, ctx->frame_bytes * nf), want(g.d_labels, ctx->labels_bytes(nf)), want(g.d_logits, ctx->logits_bytes(nf)), want(g.d_records, ctx->records_bytes(nf)),
+                          want(g.d_stats, sizeof(hevcdl_frame_stats) * nf), want(g.d_yuv, ctx->frame_bytes * nf) }, "staging buffers (cfg.max_frames)");
 }
 
-static void prof_begin(hevcdl_ctx *ctx, std::vector<hipEvent_t> &v, hipStream_t s)
+static void prof_begin(hevcdl_ctx *ctx, std::vector<Event> &v, hipStream_t s)
 {
   if (!ctx->profile) return;
-  hipEvent_t a, b; hipEventCreate(&a); hipEventCreate(&b);
-  hipEventRecord(a, s); v.push_back(a); v.push_back(b);
+  Event a, b; hipEventCreate(&a.p); hipEventCreate(&b.p);
+  hipEventRecord(a, s); v.push_back(std::move(a)); v.push_back(std::move(b));
 }
-static void prof_end(hevcdl_ctx *ctx, std::vector<hipEvent_t> &v, hipStream_t s) { if (ctx->profile) hipEventRecord(v.back(), s); }
+static void prof_end(hevcdl_ctx *ctx, std::vector<Event> &v, hipStream_t s) { if (ctx->profile) hipEventRecord(v.back(), s); }
 
 static hevcdl_status launch_cnn(hevcdl_ctx *ctx, const void *d_in, int mode, int n_ctus, int clamp, void *d_labels, void *d_logits, hipStream_t s)
 {
@@ -436,7 +481,7 @@ static hevcdl_status launch_cnn(hevcdl_ctx *ctx, const void *d_in, int mode, int
   // convolutions per CTU (one workgroup each) -> 32 KB of conv3 output per CTU in HBM -> the fully connected head batched over 16 CTUs
   // per workgroup.  The hand-over buffer holds one chunk of CTUs (<= 4 GiB); larger batches go through it chunk by chunk.
   const size_t chunk = (size_t)std::min<long long>(n_ctus, 131072);
-  if (ctx->a3_ctus < chunk) { hipFree(ctx->d_a3); ctx->d_a3 = nullptr; ctx->a3_ctus = 0; HIPCHK(hipMalloc(&ctx->d_a3, chunk * 4 * 2048 * sizeof(float))); ctx->a3_ctus = chunk; }
+  if (ctx->a3_ctus < chunk) { ctx->d_a3.reset(); ctx->a3_ctus = 0; HIPCHK(hipMalloc(&ctx->d_a3.p, chunk * 4 * 2048 * sizeof(float))); ctx->a3_ctus = chunk; }
   p.a3 = ctx->d_a3; p.n_cus = ctx->n_cus; p.bn_eval = ctx->cfg.bn_mode == HEVCDL_BN_EVAL;
   hevcdl_fc_params f;
   f.logits_in = nullptr;
@@ -456,8 +501,7 @@ static hevcdl_status launch_cnn(hevcdl_ctx *ctx, const void *d_in, int mode, int
     hipLaunchKernelGGL(hevcdl_fc_kernel, dim3((n + 15) / 16), dim3(256), hevcdl_fc_smem_bytes(), s, f);
   }
   prof_end(ctx, ctx->ev_cnn, s);
-  HIPCHK(hipGetLastError());
-  return HEVCDL_OK;
+  return launch_status(ctx);
 }
 
 #ifdef HEVCDL_STAGE_TRACE
@@ -476,54 +520,42 @@ extern "C" size_t hevcdl_stage_trace_fetch(unsigned int *dst, size_t cap_words)
 }
 #endif
 
-// Which build of the decision kernel (row of rd_builds) a launch runs: `walkers` units under way on `groups` workgroups, few_units = the few-units form (hevcdl_rd_params.remote).
-// Measured at 2160p on 256 CUs, eight- / ten-wave build (rd_kernel_wide.hip: 168 registers per lane instead of 256, no look-ahead
-// region): 200 frames 3.53 / 4.21 s, 300 frames 4.16 / 4.59 s, 450 frames 5.17 / 5.21 s, 600 frames 6.24 / 6.11 s, 1024 frames 10.33 / 9.50 s, 2048 frames
-// 16.08 / 15.66 s, 2560 frames 21.47 / 18.14 s -- but the ten-wave build moves three times the bytes (600 frames: 5.8 MB per CTU through the L2s against 1.85 MB:
-// register spills at 168 registers, the CU walk's snapshots in HBM).  It is chosen where it clearly pays: from three units per workgroup on (round 5; four before).  Launches in the
-// few-units form keep the eight-wave build.
-static int rd_build_of(const hevcdl_ctx *ctx, bool few_units, long long walkers, int groups)
+// the decision kernel's workspace: grown to `need` bytes (a launch's one block per wave of every workgroup, or hevcdl_reserve_workspace's largest); what: the message of a refusal
+static hevcdl_status ensure_scratch(hevcdl_ctx *ctx, size_t need, hipStream_t s, const char *what)
 {
-  if (ctx->cfg.bit_depth != 8) return RD_BD10;
-  if (ctx->cfg.tools != HEVCDL_TOOLS_REFERENCE) return RD_TOOLS;      // a context with other tool switches than the reference cfg's runs the build that reads them: rd_kernel_tools.hip, eight waves
-  if (ctx->cfg.exec_flags & HEVCDL_EXEC_RD_NARROW) return RD_NARROW;
-  if (ctx->cfg.exec_flags & HEVCDL_EXEC_RD_WIDE) return RD_WIDE;
-  return (!few_units && walkers >= 3LL * groups) ? RD_WIDE : RD_NARROW;      // round 5, eight- / ten-wave build on 256 CUs: 450 frames 4.80 / 4.87 s, 600 frames 5.76 / 5.70 s, 768 frames 7.00 / 6.87 s, 1024 frames 9.44 / 8.78 s
-}
-// Can a launch of this context ever run the ten-wave build?  Its largest one decides: every unit the context can hold on every workgroup it can have.
-static bool rd_can_go_wide(const hevcdl_ctx *ctx)
-{
-  const long long max_units = (long long)ctx->cfg.max_frames * (ctx->cfg.wavefront ? ctx->ctus_y : ctx->cfg.tile_columns * ctx->cfg.tile_rows);
-  return rd_build_of(ctx, false, max_units, ctx->rd_groups) == RD_WIDE;
+  RdWorkspace &w = ctx->rd;
+  if (need <= w.scratch_bytes) return HEVCDL_OK;
+  if (w.d_scratch) { HIPCHK(hipStreamSynchronize(s)); w.d_scratch.reset(); w.scratch_bytes = 0; }
+  const hipError_t e = hipMalloc(&w.d_scratch.p, need);
+  if (e != hipSuccess) { (void)hipGetLastError(); return fail(ctx, HEVCDL_ERR_OOM, what, e); }
+  w.scratch_bytes = need;
+  return HEVCDL_OK;
 }
 
+// One decision launch: the plan (rd_launch_plan.h: build, form, workgroups), the areas it wants cleared and seeded, the workspace, the launch, the report.
 static hevcdl_status launch_rd(hevcdl_ctx *ctx, const void *d_yuv, int n_frames, const void *d_labels, void *d_records, void *d_recon, void *d_stats, hipStream_t s,
                                int ctu_begin = 0, int ctu_end = -1, const void *d_cabac_in = nullptr, void *d_cabac_out = nullptr,
                                int tile_begin = 0, int tile_count = -1, int session_frame = -1)
 {
+  RdWorkspace &w = ctx->rd;
+  const RdLaunchArgs a = { n_frames, ctu_begin, ctu_end, d_cabac_in != nullptr, d_cabac_out != nullptr, tile_begin, tile_count, session_frame };
+  RdLaunchPlan pl = rd_launch_plan(w.plan, a);
+  if (pl.status) return fail(ctx, pl.status, "WaveFrontSynchro: whole-frame launches or the per-CTU session (no tile range, no CTU range of several frames)");
   hevcdl_rd_params p;
   memset(&p, 0, sizeof p);
   p.ctu_begin = ctu_begin; p.ctu_end = ctu_end < 0 ? ctx->ctus : ctu_end; p.cabac_in = (const unsigned char *)d_cabac_in; p.cabac_out = (unsigned char *)d_cabac_out;
   p.yuv = (const uint8_t *)d_yuv; p.labels = (const uint8_t *)d_labels; p.records = (unsigned char *)d_records; p.recon = (uint8_t *)d_recon;
-  p.stats = (unsigned char *)d_stats; p.scratch = ctx->d_scratch; p.scratch_per_wave = ctx->scratch_per_wave;
+  p.stats = (unsigned char *)d_stats; p.scratch_per_wave = w.scratch_per_wave;
   p.width = ctx->cfg.width; p.height = ctx->cfg.height; p.ctus_x = ctx->ctus_x; p.ctus_y = ctx->ctus_y; p.n_frames = n_frames;
   p.tile_cols = ctx->cfg.tile_columns; p.tile_rows = ctx->cfg.tile_rows;
   memcpy(p.col_bd, ctx->col_bd, sizeof p.col_bd); memcpy(p.row_bd, ctx->row_bd, sizeof p.row_bd);
-  p.tile_begin = tile_begin; p.tile_count = tile_count < 0 ? p.tile_cols * p.tile_rows : tile_count;
-  // WaveFrontSynchro: a unit is one CTU row of a frame (rows of a frame run two CTUs apart on different waves, which wait for each other: a cooperative launch), or -- where
-  // the grid cannot be co-resident, or the caller shares the device (HEVCDL_EXEC_NO_UNIT_HANDOVER) -- a whole frame whose rows one wave walks in order
-  const bool whole_launch = !d_cabac_in && !d_cabac_out && ctu_begin == 0 && p.ctu_end == ctx->ctus && tile_begin == 0 && tile_count < 0;
-  if (ctx->cfg.wavefront) {
-    if (session_frame >= 0 && n_frames == 1 && tile_begin == 0 && tile_count < 0) {
-      // the per-CTU session (hevcdl_compress_ctu): one CTU a launch in the one-wave form; the contexts behind the second CTU of every row stay in the session frame's part of
-      // d_wpp from call to call (hevcdl_begin_frames cleared it), so a row's first CTU finds what the row above left -- whatever state the caller hands in for that CTU
-      p.wpp = 2; p.tile_count = 1; p.wpp_state = ctx->d_wpp + (size_t)256 * ctx->ctus_y * session_frame; p.wpp_queue = ctx->d_wpp + ctx->wpp_state_bytes; p.wpp_ring = ctx->wpp_ring;
-    } else {
-      if (!whole_launch) return fail(ctx, HEVCDL_ERR_UNSUPPORTED, "WaveFrontSynchro: whole-frame launches or the per-CTU session (no tile range, no CTU range of several frames)");
-      p.wpp = (ctx->cfg.exec_flags & HEVCDL_EXEC_NO_UNIT_HANDOVER) ? 2 : 1; p.wpp_state = ctx->d_wpp; p.tile_count = p.wpp == 1 ? ctx->ctus_y : 1;
-      p.wpp_queue = ctx->d_wpp + ctx->wpp_state_bytes; p.wpp_ring = ctx->wpp_ring;
-      HIPCHK(hipMemsetAsync(ctx->d_wpp, 0, (size_t)256 * ctx->ctus_y * n_frames, s));
-      HIPCHK(hipMemsetAsync(p.wpp_queue, 0, 1024 + (size_t)4 * ctx->wpp_ring, s));
+  p.tile_begin = tile_begin; p.tile_count = pl.tile_count;
+  p.wpp = pl.wpp; p.wpp_masters = pl.wpp_masters; p.master_groups = pl.master_groups; p.migrate = pl.migrate; p.remote = pl.remote; p.sched = w.d_sched;
+  if (pl.wpp) { // the rows' contexts and the queue of claimable rows: the session's stay from call to call, a whole-frame launch starts from cleared ones
+    p.wpp_state = pl.wpp_session ? w.d_wpp + (size_t)256 * ctx->ctus_y * session_frame : w.d_wpp.p; p.wpp_queue = w.d_wpp + w.wpp_state_bytes; p.wpp_ring = w.wpp_ring;
+    if (!pl.wpp_session) {
+      HIPCHK(hipMemsetAsync(w.d_wpp, 0, (size_t)256 * ctx->ctus_y * n_frames, s));
+      HIPCHK(hipMemsetAsync(p.wpp_queue, 0, 1024 + (size_t)4 * w.wpp_ring, s));
     }
   }
   if (d_stats) HIPCHK(hipMemsetAsync(d_stats, 0, sizeof(hevcdl_frame_stats) * (size_t)n_frames, s));     // the tile waves of a frame add into its entry
@@ -540,78 +572,33 @@ static hevcdl_status launch_rd(hevcdl_ctx *ctx, const void *d_yuv, int n_frames,
   unsigned int *d_dbg = nullptr;               // instrumented builds only (tools/phase_profile.py): in-kernel timers / traces come back through this buffer
   HIPCHK(hipMalloc(&d_dbg, 8004 * 4)); HIPCHK(hipMemset(d_dbg, 0, 8004 * 4)); p.dbgbuf = d_dbg;
 #endif
-  // One workgroup (hevcdl_rd_waves_per_group() wavefronts, the whole LDS) per CU; the units (frame x tile) are dealt round-robin to the
-  // workgroups, a wave per unit; waves left without a unit help the others (rd_kernel.hip).
-  const int n_units = n_frames * p.tile_count;
-  // WaveFrontSynchro, rows on waves of their own: rows are claimed as they become startable, so what sizes the launch is not the number of rows but how many of them can be
-  // under way at once -- a row starts two CTUs behind the row above, i.e. at most (ctus_x + 1) / 2 rows of a frame (+ 1: one being claimed) -- `walkers`
-  const long long walkers = p.wpp == 1 ? (long long)n_frames * std::min(ctx->ctus_y, (ctx->ctus_x + 1) / 2 + 1) : (long long)n_units;
-  const int groups = (int)std::min<long long>(walkers, ctx->rd_groups);
-  p.master_groups = (int)std::min<long long>(walkers, 1 << 30);
-  // Uneven dealing (e.g. 600 frames on 256 workgroups): the surplus units travel round the ring of workgroups so that every workgroup --
-  // and every frame -- is crowded for the same share of the time (rd_kernel.hip, process_unit).  Only for whole-unit launches of a few units
-  // per workgroup.
-  p.sched = ctx->d_sched;
-  p.migrate = (!p.wpp && n_units > groups && n_units % groups != 0 && n_units / groups <= 3 && groups <= 1024 && groups >= 8 && !d_cabac_in && !d_cabac_out &&
-               ctu_begin == 0 && p.ctu_end == ctx->ctus && !(ctx->cfg.exec_flags & HEVCDL_EXEC_NO_UNIT_HANDOVER)) ? 1 : 0;
-  if (p.migrate) {
-    std::vector<int> init(16 + groups, 0);
-    const int base = n_units / groups, extra = n_units % groups;
+  if (pl.sched_clear) HIPCHK(hipMemsetAsync(w.d_sched, 0, pl.sched_clear, s));
+  if (pl.migrate) { // unit hand-over: every workgroup's share of the units behind the counters
+    std::vector<int> init(16 + pl.groups, 0);
+    const int groups = pl.groups, base = pl.n_units / groups, extra = pl.n_units % groups;
     for (int g = 0; g < groups; g++) { const int e = (g * extra + groups - 1) / groups; init[16 + g] = base + ((e < extra && (e * groups) / extra == g) ? 1 : 0); }    // the kernel's dealing
-    HIPCHK(hipMemsetAsync(ctx->d_sched, 0, 8192 + (size_t)groups * 192, s));
-    HIPCHK(hipMemcpyAsync(ctx->d_sched, init.data(), init.size() * sizeof(int), hipMemcpyHostToDevice, s));      // pageable source: the copy is staged before the call returns
+    HIPCHK(hipMemcpyAsync(w.d_sched, init.data(), init.size() * sizeof(int), hipMemcpyHostToDevice, s));      // pageable source: the copy is staged before the call returns
   }
-  // Few units (one frame, ten, a GPU's share of a sharded job): a frame is bound by the work of its CU's eight waves while most CUs have nothing to do -> the
-  // kernel runs on ALL CUs and the workgroups without a unit take the second luma passes the others post (rd_kernel.hip, remote_post / remote_serve)
-  p.remote = (!p.migrate && p.wpp != 2 && ctx->remote_groups && 3 * walkers <= 2 * ctx->remote_groups && !d_cabac_in && !d_cabac_out && ctu_begin == 0 && p.ctu_end == ctx->ctus) ? 1 : 0;
-  // more units than takers (up to two units per taker; measured on 256 CUs: 150 frames 3.89 -> 3.79 s, 200 frames 3.92 -> 4.00 s, hence the limit): a pass is
-  // posted only while a taker is free (rd_kernel.hip, remote_room)
-  if (p.remote && 2 * walkers > ctx->remote_groups) p.remote = 3;
-  // very few units: enough idle workgroups for the chroma modes of every master as well (eleven jobs per unit in flight).  Measured on 256 CUs, chroma jobs posted /
-  // kept in the unit's own workgroup: 1 frame 2.84 / 3.10 s, 10 frames 2.95 / 3.17 s, 16 frames 3.38 / 3.18 s -- hence a twenty-second of the CUs, not a sixteenth
-  if (p.remote && 22 * walkers <= ctx->remote_groups) p.remote = 2;
-  // the ring of posted jobs has 2048 entries (rd_kernel.hip RQ_SIZE): a unit has at most two passes and the ten component jobs of its chroma modes posted
-  if (p.remote && 12 * walkers > 2048) p.remote = 0;
-  if (p.remote) HIPCHK(hipMemsetAsync(ctx->d_sched, 0, 4096 + 2048 * 8, s));      // finished counter, queue head / tail, the ring (2048 pointers behind byte 4096)
-  const int build = rd_build_of(ctx, p.remote != 0, walkers, groups);
-  const RdBuild &rd = rd_builds[build];
-  if (build == RD_WIDE) p.remote = 0;      // (the ten-wave build together with the hand-over of units: launches of more than three and fewer than four units per workgroup, or exec_flags; tests/test_rd_gpu.py::test_units_handed_over_between_workgroups_give_the_same_result runs the pair)
-  const int waves = rd.waves_per_group(), threads = 64 * waves;
+  const RdBuild &rd = rd_builds[pl.build];
+  TRY(ensure_scratch(ctx, w.scratch_per_wave * pl.scratch_blocks(), s, "decision-kernel workspace (1.6 MB per wave of the launch)"));
+  p.scratch = w.d_scratch;
+  const int threads = 64 * pl.waves;
   const size_t smem = rd.smem_bytes();
-  // Waves of a workgroup that claim rows (the rest help them).  A frame's rows form a chain of ctus_x + 2 (ctus_y - 1) CTU steps; a step takes a claimer ~1.5 ms with seven
-  // helpers and ~8 ms without any (t(m) ~ 0.75 + 0.75 m ms at m claimers per workgroup, measured on 600-frame launches: profiles/r06d_wavefront_masters.txt), while the
-  // chip's rate grows with m (216 k CTU/s at 2 ... 313 k at 10).  A launch is bound by that chain until the work per claimer exceeds it: m = 0.7 x (CTUs of the launch) /
-  // (workgroups x chain), at least 1, at most every wave.  Measured at 2160p, 75 frames: m = 3 0.79 s, m = 10 0.98 s; 150 frames: flat from 6 up (1.32 - 1.34 s); 600 frames:
-  // m = 10 3.91 s, m = 6 4.54 s, m = 3 5.06 s.
-  if (p.wpp == 1) { const long long chain = ctx->ctus_x + 2LL * (ctx->ctus_y - 1);
-                    p.wpp_masters = p.remote ? 1 : (int)std::max<long long>(1, std::min<long long>(waves, (7LL * n_frames * ctx->ctus) / (10LL * groups * chain))); }
-  { // the workspace: one block per wave of every workgroup of this launch
-    const size_t need = ctx->scratch_per_wave * (size_t)(p.remote ? ctx->remote_groups : groups) * (size_t)waves;
-    if (need > ctx->scratch_bytes) {
-      if (ctx->d_scratch) { HIPCHK(hipStreamSynchronize(s)); HIPCHK(hipFree(ctx->d_scratch)); ctx->d_scratch = nullptr; ctx->scratch_bytes = 0; }
-      { const hipError_t e_ = hipMalloc(&ctx->d_scratch, need);
-        if (e_ != hipSuccess) { (void)hipGetLastError(); ctx->d_scratch = nullptr; return fail(ctx, HEVCDL_ERR_OOM, "decision-kernel workspace (1.6 MB per wave of the launch)", e_); } }
-      ctx->scratch_bytes = need;
-    }
-    p.scratch = ctx->d_scratch;
-  }
   prof_begin(ctx, ctx->ev_rd, s);
   bool launched = false;
   void *args[] = { &p };
-  if (p.migrate || p.remote || p.wpp == 1) { // workgroups that wait for each other: a cooperative launch, which the runtime only accepts when the whole grid can be resident at once
-    if (hipLaunchCooperativeKernel(rd.kernel, dim3(p.remote ? ctx->remote_groups : groups), dim3(threads), args, smem, s) == hipSuccess) launched = true;
+  if (pl.cooperative()) { // workgroups that wait for each other: a cooperative launch, which the runtime only accepts when the whole grid can be resident at once
+    if (hipLaunchCooperativeKernel(rd.kernel, dim3(pl.grid), dim3(threads), args, smem, s) == hipSuccess) launched = true;
     else {
-      (void)hipGetLastError(); p.migrate = 0; p.remote = 0;
-      if (p.wpp == 1) { prof_end(ctx, ctx->ev_rd, s); ctx->cfg.exec_flags |= HEVCDL_EXEC_NO_UNIT_HANDOVER;      // rows on waves of their own need co-residency: this context walks a frame's rows on one wave from now on
-                        return launch_rd(ctx, d_yuv, n_frames, d_labels, d_records, d_recon, d_stats, s, ctu_begin, ctu_end, d_cabac_in, d_cabac_out, tile_begin, tile_count); }
+      (void)hipGetLastError(); p.migrate = pl.migrate = 0; p.remote = pl.remote = 0; pl.grid = pl.groups;
+      if (pl.wpp == 1) { prof_end(ctx, ctx->ev_rd, s); ctx->cfg.exec_flags |= HEVCDL_EXEC_NO_UNIT_HANDOVER; w.plan.exec_flags = ctx->cfg.exec_flags;      // rows on waves of their own need co-residency: this context walks a frame's rows on one wave from now on
+                         return launch_rd(ctx, d_yuv, n_frames, d_labels, d_records, d_recon, d_stats, s, ctu_begin, ctu_end, d_cabac_in, d_cabac_out, tile_begin, tile_count); }
     }
   }
-  if (!launched) (void)hipLaunchKernel(rd.kernel, dim3(groups), dim3(threads), args, smem, s);      // (an error is picked up below, as after every launch)
+  if (!launched) (void)hipLaunchKernel(rd.kernel, dim3(pl.groups), dim3(threads), args, smem, s);      // (an error is picked up below, as after every launch)
   prof_end(ctx, ctx->ev_rd, s);
   HIPCHK(hipGetLastError());
-  snprintf(ctx->last_rd, sizeof ctx->last_rd, "%s form=%s workgroups=%d waves=%d units=%d", rd.name,
-           p.wpp == 1 ? (p.remote ? "wavefront-rows+few-units" : "wavefront-rows") : p.wpp == 2 ? "wavefront(one wave per frame)" : p.migrate ? "unit-handover" : (p.remote == 1 ? "few-units(passes)" : (p.remote == 2 ? "few-units(passes+chroma)" : (p.remote == 3 ? "few-units(passes while takers idle)" : "independent"))),
-           p.remote ? ctx->remote_groups : groups, waves, n_units);
+  rd_launch_report(pl, ctx->last_rd, sizeof ctx->last_rd);
 #if defined(HEVCDL_KERNEL_PROF) || defined(HEVCDL_KERNEL_DEBUG)
   {
     std::vector<unsigned int> hb(8004); hipDeviceSynchronize(); hipMemcpy(hb.data(), d_dbg, 8004 * 4, hipMemcpyDeviceToHost);
@@ -638,15 +625,17 @@ static hevcdl_status check_frames(hevcdl_ctx *ctx, int n_frames)
   return HEVCDL_OK;
 }
 
+// the opening of an entry that takes n_frames pictures: a bad context or count is its status, no pictures are nothing to do
+#define FRAMES_OR_RETURN(ctx, n) do { TRY(check_frames(ctx, n)); if ((n) == 0) return HEVCDL_OK; } while (0)
+
 // caller-supplied labels (device copy): boundary clamp + quadtree consistency in place; labels above 3 -> HEVCDL_ERR_INVALID_ARG
 extern "C" hevcdl_status hevcdl_clamp_labels_dev(hevcdl_ctx *ctx, void *d_labels, int n_frames, void *stream)
 {
-  hevcdl_status st = check_frames(ctx, n_frames); if (st) return st;
-  if (n_frames == 0) return HEVCDL_OK;
+  FRAMES_OR_RETURN(ctx, n_frames);
   if (!d_labels) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null device pointer");
   const int n = n_frames * ctx->ctus;
   HIPCHK(hipMemsetAsync(ctx->d_flag, 0, sizeof(int), (hipStream_t)stream));
-  hipLaunchKernelGGL(hevcdl_clamp_labels_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, (uint8_t *)d_labels, n, ctx->ctus, ctx->ctus_x, ctx->cfg.width, ctx->cfg.height, ctx->d_flag);
+  hipLaunchKernelGGL(hevcdl_clamp_labels_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, (uint8_t *)d_labels, n, ctx->ctus, ctx->ctus_x, ctx->cfg.width, ctx->cfg.height, ctx->d_flag.p);
   int bad = 0;
   HIPCHK(hipMemcpyAsync(&bad, ctx->d_flag, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
   HIPCHK(hipStreamSynchronize((hipStream_t)stream));
@@ -656,14 +645,13 @@ extern "C" hevcdl_status hevcdl_clamp_labels_dev(hevcdl_ctx *ctx, void *d_labels
 
 extern "C" hevcdl_status hevcdl_predict_depth_dev(hevcdl_ctx *ctx, const void *d_yuv, int n_frames, void *d_labels, void *d_logits_opt, void *stream)
 {
-  hevcdl_status st = check_frames(ctx, n_frames); if (st) return st;
-  if (n_frames == 0) return HEVCDL_OK;
+  FRAMES_OR_RETURN(ctx, n_frames);
   if (!d_yuv || !d_labels) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null device pointer");
   if (ctx->cfg.bit_depth > 8) { // the CNN stage is defined on 8-bit pictures: the top 8 bits of every sample
-    if (!ctx->d_yuv8) HIPCHK(hipMalloc(&ctx->d_yuv8, hevcdl_frame_bytes(ctx->cfg.width, ctx->cfg.height) * (size_t)ctx->cfg.max_frames));
+    TRY(lazy_alloc(ctx, ctx->stage.d_yuv8, hevcdl_frame_bytes(ctx->cfg.width, ctx->cfg.height) * (size_t)ctx->cfg.max_frames, "8-bit pictures of the CNN stage (cfg.max_frames)"));
     const size_t n = hevcdl_frame_bytes(ctx->cfg.width, ctx->cfg.height) * (size_t)n_frames;
-    hipLaunchKernelGGL(hevcdl_narrow_samples_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream, (const uint16_t *)d_yuv, ctx->d_yuv8, n, ctx->cfg.bit_depth - 8);
-    d_yuv = ctx->d_yuv8;
+    hipLaunchKernelGGL(hevcdl_narrow_samples_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream, (const uint16_t *)d_yuv, ctx->stage.d_yuv8.p, n, ctx->cfg.bit_depth - 8);
+    d_yuv = ctx->stage.d_yuv8.p;
   }
   return launch_cnn(ctx, d_yuv, ctx->cfg.cnn_input == HEVCDL_CNN_INPUT_LUMA ? HEVCDL_DEV_INPUT_LUMA : HEVCDL_DEV_INPUT_RGB601,
                     n_frames * ctx->ctus, 1, d_labels, d_logits_opt, (hipStream_t)stream);
@@ -672,8 +660,7 @@ extern "C" hevcdl_status hevcdl_predict_depth_dev(hevcdl_ctx *ctx, const void *d
 extern "C" hevcdl_status hevcdl_compress_frames_dev(hevcdl_ctx *ctx, const void *d_yuv, int n_frames, const void *d_labels,
                                                     void *d_records, void *d_recon, void *d_stats, void *stream)
 {
-  hevcdl_status st = check_frames(ctx, n_frames); if (st) return st;
-  if (n_frames == 0) return HEVCDL_OK;
+  FRAMES_OR_RETURN(ctx, n_frames);
   if (!d_yuv || !d_labels || !d_records || !d_recon) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null device pointer");
   return launch_rd(ctx, d_yuv, n_frames, d_labels, d_records, d_recon, d_stats, (hipStream_t)stream);
 }
@@ -681,7 +668,7 @@ extern "C" hevcdl_status hevcdl_compress_frames_dev(hevcdl_ctx *ctx, const void 
 extern "C" hevcdl_status hevcdl_compress_tiles_dev(hevcdl_ctx *ctx, const void *d_yuv, int n_frames, const void *d_labels, void *d_records, void *d_recon, void *d_stats,
                                                    int tile_begin, int tile_count, void *stream)
 {
-  hevcdl_status st = check_frames(ctx, n_frames); if (st) return st;
+  TRY(check_frames(ctx, n_frames));
   if (tile_begin < 0 || tile_count < 0 || tile_begin + tile_count > ctx->cfg.tile_columns * ctx->cfg.tile_rows) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "tile range outside the tile grid");
   if (n_frames == 0 || tile_count == 0) return HEVCDL_OK;
   if (!d_yuv || !d_labels || !d_records || !d_recon) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null device pointer");
@@ -691,7 +678,7 @@ extern "C" hevcdl_status hevcdl_compress_tiles_dev(hevcdl_ctx *ctx, const void *
 extern "C" hevcdl_status hevcdl_encode_frames_dev(hevcdl_ctx *ctx, const void *d_yuv, int n_frames, void *d_labels,
                                                   void *d_records, void *d_recon, void *d_stats, void *stream)
 {
-  hevcdl_status st = hevcdl_predict_depth_dev(ctx, d_yuv, n_frames, d_labels, nullptr, stream); if (st) return st;
+  TRY(hevcdl_predict_depth_dev(ctx, d_yuv, n_frames, d_labels, nullptr, stream));
   return hevcdl_compress_frames_dev(ctx, d_yuv, n_frames, d_labels, d_records, d_recon, d_stats, stream);
 }
 
@@ -703,10 +690,10 @@ static hevcdl_status upload_planes(hevcdl_ctx *ctx, const hevcdl_planes *src, in
   if (sb != native && !(sb == 2 && native == 1)) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "sample_bytes does not fit the context's bit depth");
   const int w = ctx->cfg.width, h = ctx->cfg.height;
   for (int c = 0; c < 3; c++) if (src->row_stride[c] < (size_t)(c ? w / 2 : w) * sb) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "row stride smaller than a row");
-  unsigned char *dst = (unsigned char *)ctx->d_yuv;
+  unsigned char *dst = (unsigned char *)ctx->stage.d_yuv;
   if (sb != native) {
-    if (!ctx->d_wide) HIPCHK(hipMalloc(&ctx->d_wide, 2 * ctx->frame_bytes * (size_t)ctx->cfg.max_frames));
-    dst = ctx->d_wide;
+    TRY(lazy_alloc(ctx, ctx->stage.d_wide, 2 * ctx->frame_bytes * (size_t)ctx->cfg.max_frames, "16-bit staging of the planes (cfg.max_frames)"));
+    dst = ctx->stage.d_wide;
   }
   const size_t fb = ctx->frame_bytes / native * sb, off[3] = { 0, (size_t)w * h * sb, (size_t)w * h * sb + (size_t)(w / 2) * (h / 2) * sb };
   for (int f = 0; f < n_frames; f++) for (int c = 0; c < 3; c++) {
@@ -714,7 +701,7 @@ static hevcdl_status upload_planes(hevcdl_ctx *ctx, const hevcdl_planes *src, in
     HIPCHK(hipMemcpy2D(dst + (size_t)f * fb + off[c], rw, (const unsigned char *)src->plane[c] + (size_t)f * src->frame_stride[c], src->row_stride[c], rw, rows, hipMemcpyHostToDevice));
   }
   if (sb != native) {
-    hipLaunchKernelGGL(hevcdl_narrow_samples_kernel, dim3(2048), dim3(256), 0, (hipStream_t)nullptr, (const uint16_t *)ctx->d_wide, (uint8_t *)ctx->d_yuv, ctx->frame_bytes * (size_t)n_frames, 0);
+    hipLaunchKernelGGL(hevcdl_narrow_samples_kernel, dim3(2048), dim3(256), 0, (hipStream_t)nullptr, (const uint16_t *)ctx->stage.d_wide.p, ctx->stage.d_yuv.p, ctx->frame_bytes * (size_t)n_frames, 0);
     HIPCHK(hipGetLastError());
   }
   return HEVCDL_OK;
@@ -723,29 +710,26 @@ static hevcdl_status upload_planes(hevcdl_ctx *ctx, const hevcdl_planes *src, in
 static hevcdl_status predict_depth_staged(hevcdl_ctx *ctx, int n_frames, uint8_t *labels, float *logits_opt);
 extern "C" hevcdl_status hevcdl_predict_depth(hevcdl_ctx *ctx, const uint8_t *yuv, int n_frames, uint8_t *labels, float *logits_opt)
 {
-  hevcdl_status st = check_frames(ctx, n_frames); if (st) return st;
-  if (n_frames == 0) return HEVCDL_OK;
+  FRAMES_OR_RETURN(ctx, n_frames);
   if (!yuv || !labels) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null pointer");
-  st = ensure_staging(ctx); if (st) return st;
-  HIPCHK(hipMemcpy(ctx->d_yuv, yuv, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
+  TRY(ensure_staging(ctx));
+  HIPCHK(hipMemcpy(ctx->stage.d_yuv, yuv, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
   return predict_depth_staged(ctx, n_frames, labels, logits_opt);
 }
 extern "C" hevcdl_status hevcdl_predict_depth_planes(hevcdl_ctx *ctx, const hevcdl_planes *src, int n_frames, uint8_t *labels, float *logits_opt)
 {
-  hevcdl_status st = check_frames(ctx, n_frames); if (st) return st;
-  if (n_frames == 0) return HEVCDL_OK;
+  FRAMES_OR_RETURN(ctx, n_frames);
   if (!labels) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null pointer");
-  st = ensure_staging(ctx); if (st) return st;
-  st = upload_planes(ctx, src, n_frames); if (st) return st;
+  TRY(ensure_staging(ctx));
+  TRY(upload_planes(ctx, src, n_frames));
   return predict_depth_staged(ctx, n_frames, labels, logits_opt);
 }
 static hevcdl_status predict_depth_staged(hevcdl_ctx *ctx, int n_frames, uint8_t *labels, float *logits_opt)
 {
-  hevcdl_status st;
-  st = hevcdl_predict_depth_dev(ctx, ctx->d_yuv, n_frames, ctx->d_labels, logits_opt ? ctx->d_logits : nullptr, nullptr); if (st) return st;
+  TRY(hevcdl_predict_depth_dev(ctx, ctx->stage.d_yuv, n_frames, ctx->stage.d_labels, logits_opt ? ctx->stage.d_logits.p : nullptr, nullptr));
   HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(labels, ctx->d_labels, (size_t)ctx->ctus * 16 * n_frames, hipMemcpyDeviceToHost));
-  if (logits_opt) HIPCHK(hipMemcpy(logits_opt, ctx->d_logits, (size_t)ctx->ctus * 64 * sizeof(float) * n_frames, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(labels, ctx->stage.d_labels, ctx->labels_bytes(n_frames), hipMemcpyDeviceToHost));
+  if (logits_opt) HIPCHK(hipMemcpy(logits_opt, ctx->stage.d_logits, ctx->logits_bytes(n_frames), hipMemcpyDeviceToHost));
   return HEVCDL_OK;
 }
 
@@ -756,23 +740,16 @@ extern "C" hevcdl_status hevcdl_predict_depth_rgb(hevcdl_ctx *ctx, const uint8_t
   if (n_ctus == 0) return HEVCDL_OK;
   if (!ctu_rgb || !labels) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null pointer");
   HIPCHK(hipSetDevice(ctx->cfg.device));
-  uint8_t *d_in = nullptr, *d_lab = nullptr; float *d_lg = nullptr;
-  hipError_t e0 = hipMalloc(&d_in, (size_t)n_ctus * 12288);
-  if (e0 == hipSuccess) e0 = hipMalloc(&d_lab, (size_t)n_ctus * 16);
-  if (e0 == hipSuccess) e0 = hipMalloc(&d_lg, (size_t)n_ctus * 64 * sizeof(float));
-  if (e0 == hipSuccess) e0 = hipMemcpy(d_in, ctu_rgb, (size_t)n_ctus * 12288, hipMemcpyHostToDevice);
-  if (e0 != hipSuccess) { hipFree(d_in); hipFree(d_lab); hipFree(d_lg); return fail(ctx, e0 == hipErrorOutOfMemory ? HEVCDL_ERR_OOM : HEVCDL_ERR_HIP, "predict_depth_rgb buffers", e0); }
-  hevcdl_status st = launch_cnn(ctx, d_in, HEVCDL_DEV_INPUT_RGB_CTU, n_ctus, 0, d_lab, d_lg, nullptr);
-  if (st == HEVCDL_OK) {
-    hipError_t e = hipDeviceSynchronize();
-    if (e != hipSuccess) st = fail(ctx, HEVCDL_ERR_HIP, "cnn kernel", e);
-  }
-  if (st == HEVCDL_OK) {
-    hipMemcpy(labels, d_lab, (size_t)n_ctus * 16, hipMemcpyDeviceToHost);
-    if (logits_opt) hipMemcpy(logits_opt, d_lg, (size_t)n_ctus * 64 * sizeof(float), hipMemcpyDeviceToHost);
-  }
-  hipFree(d_in); hipFree(d_lab); hipFree(d_lg);
-  return st;
+  const size_t n = (size_t)n_ctus;
+  DevBuf<uint8_t> d_in, d_lab; DevBuf<float> d_lg;
+  TRY(alloc_all(ctx, { want(d_in, n * CTU_RGB_BYTES), want(d_lab, n * LABELS_PER_CTU), want(d_lg, n * LOGITS_PER_CTU * sizeof(float)) }, "predict_depth_rgb buffers"));
+  const hipError_t e0 = hipMemcpy(d_in, ctu_rgb, n * CTU_RGB_BYTES, hipMemcpyHostToDevice);
+  if (e0 != hipSuccess) return hip_fail(ctx, "predict_depth_rgb buffers", e0);
+  TRY(launch_cnn(ctx, d_in, HEVCDL_DEV_INPUT_RGB_CTU, n_ctus, 0, d_lab, d_lg, nullptr));
+  TRY(sync_or_fail(ctx, "cnn kernel"));
+  hipMemcpy(labels, d_lab, n * LABELS_PER_CTU, hipMemcpyDeviceToHost);
+  if (logits_opt) hipMemcpy(logits_opt, d_lg, n * LOGITS_PER_CTU * sizeof(float), hipMemcpyDeviceToHost);
+  return HEVCDL_OK;
 }
 
 extern "C" const char *hevcdl_last_rd_launch(const hevcdl_ctx *ctx) { return ctx ? ctx->last_rd : ""; }
@@ -780,22 +757,15 @@ extern "C" const char *hevcdl_last_rd_launch(const hevcdl_ctx *ctx) { return ctx
 // The decision kernel's workspace (1.6 MB per wave of a launch) is allocated by the first launch that needs it and grown when a later one needs more: a context that
 // only ever codes a frame in the independent form holds megabytes, a launch on every CU 3.4 GB (4.3 GB for the ten-wave build).  A caller that wants to learn
 // about a lack of device memory BEFORE its first pictures are in flight reserves the largest workspace any launch of this context can ask for -- launches of 1 ..
-// max_frames frames: every CU's workgroup (the few-units form runs on all of them), ten waves where the ten-wave build can be chosen -- and gets HEVCDL_ERR_OOM here.
+// max_frames frames, as the launch plan sizes them (rd_launch_plan.h, rd_largest_scratch_blocks) -- and gets HEVCDL_ERR_OOM here.
 extern "C" hevcdl_status hevcdl_reserve_workspace(hevcdl_ctx *ctx)
 {
   if (!ctx) return HEVCDL_ERR_INVALID_ARG;
   HIPCHK(hipSetDevice(ctx->cfg.device));
-  const int groups = std::max(ctx->rd_groups, ctx->remote_groups);
-  int waves = rd_builds[rd_build_of(ctx, true, 0, 0)].waves_per_group();      // the build of a launch in the few-units form
-  if (rd_can_go_wide(ctx)) waves = std::max(waves, rd_builds[RD_WIDE].waves_per_group());
-  const size_t need = ctx->scratch_per_wave * (size_t)groups * (size_t)waves;
-  if (need <= ctx->scratch_bytes) return HEVCDL_OK;
+  const size_t need = ctx->rd.scratch_per_wave * rd_largest_scratch_blocks(ctx->rd.plan);
+  if (need <= ctx->rd.scratch_bytes) return HEVCDL_OK;
   HIPCHK(hipDeviceSynchronize());
-  if (ctx->d_scratch) { hipFree(ctx->d_scratch); ctx->d_scratch = nullptr; ctx->scratch_bytes = 0; }
-  const hipError_t e = hipMalloc(&ctx->d_scratch, need);
-  if (e != hipSuccess) { (void)hipGetLastError(); ctx->d_scratch = nullptr; return fail(ctx, HEVCDL_ERR_OOM, "decision-kernel workspace (1.6 MB per wave of the largest launch)", e); }
-  ctx->scratch_bytes = need;
-  return HEVCDL_OK;
+  return ensure_scratch(ctx, need, nullptr, "decision-kernel workspace (1.6 MB per wave of the largest launch)");
 }
 
 extern "C" hevcdl_status hevcdl_labels_from_logits(hevcdl_ctx *ctx, const float *logits, int n_ctus, int clamp, uint8_t *labels)
@@ -805,54 +775,55 @@ extern "C" hevcdl_status hevcdl_labels_from_logits(hevcdl_ctx *ctx, const float 
   if (n_ctus == 0) return HEVCDL_OK;
   if (!logits || !labels) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null pointer");
   HIPCHK(hipSetDevice(ctx->cfg.device));
-  uint8_t *d_lab = nullptr; float *d_lg = nullptr;
-  hipError_t e0 = hipMalloc(&d_lab, (size_t)n_ctus * 16);
-  if (e0 == hipSuccess) e0 = hipMalloc(&d_lg, (size_t)n_ctus * 64 * sizeof(float));
-  if (e0 == hipSuccess) e0 = hipMemcpy(d_lg, logits, (size_t)n_ctus * 64 * sizeof(float), hipMemcpyHostToDevice);
-  if (e0 != hipSuccess) { hipFree(d_lab); hipFree(d_lg); return fail(ctx, e0 == hipErrorOutOfMemory ? HEVCDL_ERR_OOM : HEVCDL_ERR_HIP, "labels_from_logits buffers", e0); }
+  const size_t n = (size_t)n_ctus;
+  DevBuf<uint8_t> d_lab; DevBuf<float> d_lg;
+  TRY(alloc_all(ctx, { want(d_lab, n * LABELS_PER_CTU), want(d_lg, n * LOGITS_PER_CTU * sizeof(float)) }, "labels_from_logits buffers"));
+  const hipError_t e0 = hipMemcpy(d_lg, logits, n * LOGITS_PER_CTU * sizeof(float), hipMemcpyHostToDevice);
+  if (e0 != hipSuccess) return hip_fail(ctx, "labels_from_logits buffers", e0);
   hevcdl_fc_params f;
   f.a3 = nullptr; f.weights = ctx->d_weights; f.labels = d_lab; f.logits = nullptr; f.logits_in = d_lg;
   f.n_ctus = n_ctus; f.ctu_base = 0; f.width = ctx->cfg.width; f.height = ctx->cfg.height; f.ctus_x = ctx->ctus_x; f.ctus_per_frame = ctx->ctus; f.clamp = clamp ? 1 : 0;
   hipLaunchKernelGGL(hevcdl_fc_kernel, dim3((n_ctus + 15) / 16), dim3(256), hevcdl_fc_smem_bytes(), nullptr, f);
-  hipError_t e = hipDeviceSynchronize();
-  hevcdl_status st = e == hipSuccess ? HEVCDL_OK : fail(ctx, HEVCDL_ERR_HIP, "label kernel", e);
-  if (st == HEVCDL_OK) hipMemcpy(labels, d_lab, (size_t)n_ctus * 16, hipMemcpyDeviceToHost);
-  hipFree(d_lab); hipFree(d_lg);
-  return st;
+  TRY(sync_or_fail(ctx, "label kernel"));
+  hipMemcpy(labels, d_lab, n * LABELS_PER_CTU, hipMemcpyDeviceToHost);
+  return HEVCDL_OK;
+}
+
+// the labels of n_frames staged pictures into the staging buffer: the caller's (uploaded, boundary policy applied) or the CNN stage's
+static hevcdl_status stage_labels(hevcdl_ctx *ctx, const uint8_t *labels_opt, int n_frames)
+{
+  if (!labels_opt) return hevcdl_predict_depth_dev(ctx, ctx->stage.d_yuv, n_frames, ctx->stage.d_labels, nullptr, nullptr);
+  HIPCHK(hipMemcpy(ctx->stage.d_labels, labels_opt, ctx->labels_bytes(n_frames), hipMemcpyHostToDevice));
+  return hevcdl_clamp_labels_dev(ctx, ctx->stage.d_labels, n_frames, nullptr);
 }
 
 static hevcdl_status compress_frames_staged(hevcdl_ctx *ctx, int n_frames, const uint8_t *labels_opt, hevcdl_ctu_record *records, uint8_t *recon_opt, hevcdl_frame_stats *stats_opt);
 extern "C" hevcdl_status hevcdl_compress_frames(hevcdl_ctx *ctx, const uint8_t *yuv, int n_frames, const uint8_t *labels_opt,
                                                 hevcdl_ctu_record *records, uint8_t *recon_opt, hevcdl_frame_stats *stats_opt)
 {
-  hevcdl_status st = check_frames(ctx, n_frames); if (st) return st;
-  if (n_frames == 0) return HEVCDL_OK;
+  FRAMES_OR_RETURN(ctx, n_frames);
   if (!yuv || !records) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null pointer");
-  st = ensure_staging(ctx); if (st) return st;
-  HIPCHK(hipMemcpy(ctx->d_yuv, yuv, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
+  TRY(ensure_staging(ctx));
+  HIPCHK(hipMemcpy(ctx->stage.d_yuv, yuv, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
   return compress_frames_staged(ctx, n_frames, labels_opt, records, recon_opt, stats_opt);
 }
 extern "C" hevcdl_status hevcdl_compress_frames_planes(hevcdl_ctx *ctx, const hevcdl_planes *src, int n_frames, const uint8_t *labels_opt,
                                                        hevcdl_ctu_record *records, uint8_t *recon_opt, hevcdl_frame_stats *stats_opt)
 {
-  hevcdl_status st = check_frames(ctx, n_frames); if (st) return st;
-  if (n_frames == 0) return HEVCDL_OK;
+  FRAMES_OR_RETURN(ctx, n_frames);
   if (!records) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null pointer");
-  st = ensure_staging(ctx); if (st) return st;
-  st = upload_planes(ctx, src, n_frames); if (st) return st;
+  TRY(ensure_staging(ctx));
+  TRY(upload_planes(ctx, src, n_frames));
   return compress_frames_staged(ctx, n_frames, labels_opt, records, recon_opt, stats_opt);
 }
 static hevcdl_status compress_frames_staged(hevcdl_ctx *ctx, int n_frames, const uint8_t *labels_opt, hevcdl_ctu_record *records, uint8_t *recon_opt, hevcdl_frame_stats *stats_opt)
 {
-  hevcdl_status st;
-  if (labels_opt) { HIPCHK(hipMemcpy(ctx->d_labels, labels_opt, (size_t)ctx->ctus * 16 * n_frames, hipMemcpyHostToDevice)); st = hevcdl_clamp_labels_dev(ctx, ctx->d_labels, n_frames, nullptr); if (st) return st; }
-  else { st = hevcdl_predict_depth_dev(ctx, ctx->d_yuv, n_frames, ctx->d_labels, nullptr, nullptr); if (st) return st; }
-  st = hevcdl_compress_frames_dev(ctx, ctx->d_yuv, n_frames, ctx->d_labels, ctx->d_records, ctx->d_recon, ctx->d_stats, nullptr); if (st) return st;
-  hipError_t e = hipDeviceSynchronize();
-  if (e != hipSuccess) return fail(ctx, HEVCDL_ERR_HIP, "rd kernel", e);
-  HIPCHK(hipMemcpy(records, ctx->d_records, (size_t)ctx->ctus * sizeof(hevcdl_ctu_record) * n_frames, hipMemcpyDeviceToHost));
-  if (recon_opt) HIPCHK(hipMemcpy(recon_opt, ctx->d_recon, ctx->frame_bytes * n_frames, hipMemcpyDeviceToHost));
-  if (stats_opt) HIPCHK(hipMemcpy(stats_opt, ctx->d_stats, sizeof(hevcdl_frame_stats) * n_frames, hipMemcpyDeviceToHost));
+  TRY(stage_labels(ctx, labels_opt, n_frames));
+  TRY(hevcdl_compress_frames_dev(ctx, ctx->stage.d_yuv, n_frames, ctx->stage.d_labels, ctx->stage.d_records, ctx->stage.d_recon, ctx->stage.d_stats, nullptr));
+  TRY(sync_or_fail(ctx, "rd kernel"));
+  HIPCHK(hipMemcpy(records, ctx->stage.d_records, ctx->records_bytes(n_frames), hipMemcpyDeviceToHost));
+  if (recon_opt) HIPCHK(hipMemcpy(recon_opt, ctx->stage.d_recon, ctx->frame_bytes * n_frames, hipMemcpyDeviceToHost));
+  if (stats_opt) HIPCHK(hipMemcpy(stats_opt, ctx->stage.d_stats, sizeof(hevcdl_frame_stats) * n_frames, hipMemcpyDeviceToHost));
   return HEVCDL_OK;
 }
 
@@ -862,8 +833,7 @@ static const unsigned char DBK_BETA[52] = { 0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,6,7,
 
 extern "C" hevcdl_status hevcdl_deblock_frames_dev(hevcdl_ctx *ctx, const void *d_recon, int n_frames, const void *d_records, void *d_out, void *stream)
 {
-  hevcdl_status st = check_frames(ctx, n_frames); if (st) return st;
-  if (n_frames == 0) return HEVCDL_OK;
+  FRAMES_OR_RETURN(ctx, n_frames);
   if (!d_recon || !d_records || !d_out) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null device pointer");
   hevcdl_dbk_params p;
   p.in = (const uint8_t *)d_recon; p.out = (uint8_t *)d_out; p.records = (const unsigned char *)d_records;
@@ -877,62 +847,55 @@ extern "C" hevcdl_status hevcdl_deblock_frames_dev(hevcdl_ctx *ctx, const void *
   p.lf_across_tiles = ctx->cfg.lf_across_tiles != 0; p.tile_cols = ctx->cfg.tile_columns; p.tile_rows = ctx->cfg.tile_rows;
   memcpy(p.col_bd, ctx->col_bd, sizeof p.col_bd); memcpy(p.row_bd, ctx->row_bd, sizeof p.row_bd);
   hevcdl_launch_deblock(&p, stream);
-  HIPCHK(hipGetLastError());
-  return HEVCDL_OK;
+  return launch_status(ctx);
 }
 
 extern "C" hevcdl_status hevcdl_deblock_frames(hevcdl_ctx *ctx, const uint8_t *recon, int n_frames, const hevcdl_ctu_record *records, uint8_t *out)
 {
-  hevcdl_status st = check_frames(ctx, n_frames); if (st) return st;
-  if (n_frames == 0) return HEVCDL_OK;
+  FRAMES_OR_RETURN(ctx, n_frames);
   if (!recon || !records || !out) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null pointer");
-  st = ensure_staging(ctx); if (st) return st;
-  HIPCHK(hipMemcpy(ctx->d_recon, recon, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(ctx->d_records, records, (size_t)ctx->ctus * sizeof(hevcdl_ctu_record) * n_frames, hipMemcpyHostToDevice));
-  st = hevcdl_deblock_frames_dev(ctx, ctx->d_recon, n_frames, ctx->d_records, ctx->d_yuv, nullptr); if (st) return st;   // d_yuv: free staging plane set
-  hipError_t e = hipDeviceSynchronize();
-  if (e != hipSuccess) return fail(ctx, HEVCDL_ERR_HIP, "deblock kernels", e);
-  HIPCHK(hipMemcpy(out, ctx->d_yuv, ctx->frame_bytes * n_frames, hipMemcpyDeviceToHost));
+  TRY(ensure_staging(ctx));
+  HIPCHK(hipMemcpy(ctx->stage.d_recon, recon, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(ctx->stage.d_records, records, ctx->records_bytes(n_frames), hipMemcpyHostToDevice));
+  TRY(hevcdl_deblock_frames_dev(ctx, ctx->stage.d_recon, n_frames, ctx->stage.d_records, ctx->stage.d_yuv, nullptr));   // d_yuv: free staging plane set
+  TRY(sync_or_fail(ctx, "deblock kernels"));
+  HIPCHK(hipMemcpy(out, ctx->stage.d_yuv, ctx->frame_bytes * n_frames, hipMemcpyDeviceToHost));
   return HEVCDL_OK;
 }
 
 // ---- SAO (row f-2, second half): TEncSampleAdaptiveOffset::SAOProcess, TEncSampleAdaptiveOffset.cpp:244, called at TEncGOP.cpp:1797 ----
 extern "C" hevcdl_status hevcdl_sao_frames_dev(hevcdl_ctx *ctx, const void *d_org, const void *d_deblocked, int n_frames, void *d_params, void *d_out, void *stream)
 {
-  hevcdl_status st = check_frames(ctx, n_frames); if (st) return st;
-  if (n_frames == 0) return HEVCDL_OK;
+  FRAMES_OR_RETURN(ctx, n_frames);
   if (!d_org || !d_deblocked || !d_params || !d_out) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null device pointer");
   const size_t nf = (size_t)ctx->cfg.max_frames;
-  if (!ctx->d_sao_stats) HIPCHK(hipMalloc(&ctx->d_sao_stats, (size_t)ctx->ctus * 3 * 5 * 256 * nf));
-  if (!ctx->d_sao_recon) HIPCHK(hipMalloc(&ctx->d_sao_recon, (size_t)ctx->ctus * sizeof(hevcdl_sao_blk) * nf));
-  if (!ctx->d_sao_cand) HIPCHK(hipMalloc(&ctx->d_sao_cand, (size_t)ctx->ctus * (3 * 5 * 16 + 32) * nf));      // candidates, then the chain's records
+  TRY(lazy_alloc(ctx, ctx->sao.d_sao_stats, (size_t)ctx->ctus * 3 * 5 * 256 * nf, "SAO statistics (cfg.max_frames)"));
+  TRY(lazy_alloc(ctx, ctx->sao.d_sao_recon, ctx->sao_bytes(nf), "SAO reconstruction parameters (cfg.max_frames)"));
+  TRY(lazy_alloc(ctx, ctx->sao.d_sao_cand, (size_t)ctx->ctus * (3 * 5 * 16 + 32) * nf, "SAO candidates (cfg.max_frames)"));      // candidates, then the chain's records
   hevcdl_sao_params p;
   p.org = (const uint8_t *)d_org; p.deblocked = (const uint8_t *)d_deblocked; p.out = (uint8_t *)d_out;
-  p.stats = ctx->d_sao_stats; p.params = (unsigned char *)d_params; p.recon_params = ctx->d_sao_recon; p.cand = ctx->d_sao_cand; p.crec = ctx->d_sao_cand + (size_t)ctx->ctus * 3 * 5 * 16 * nf;
+  p.stats = ctx->sao.d_sao_stats; p.params = (unsigned char *)d_params; p.recon_params = ctx->sao.d_sao_recon; p.cand = ctx->sao.d_sao_cand; p.crec = ctx->sao.d_sao_cand + (size_t)ctx->ctus * 3 * 5 * 16 * nf;
   p.width = ctx->cfg.width; p.height = ctx->cfg.height; p.ctus_x = ctx->ctus_x; p.ctus_per_frame = ctx->ctus; p.n_frames = n_frames; p.qp = ctx->cfg.qp;
   p.lambda = ctx->cfg.lambda; p.lambda_chroma = ctx->cfg.lambda_chroma;          // slice lambdas per component, TEncSlice.cpp:112-140
   p.tile_cols = ctx->cfg.tile_columns; p.tile_rows = ctx->cfg.tile_rows; p.bit_depth = ctx->cfg.bit_depth; p.lf_across_tiles = ctx->cfg.lf_across_tiles != 0;
   memcpy(p.col_bd, ctx->col_bd, sizeof p.col_bd); memcpy(p.row_bd, ctx->row_bd, sizeof p.row_bd);
   hevcdl_launch_sao(&p, stream);
-  HIPCHK(hipGetLastError());
-  return HEVCDL_OK;
+  return launch_status(ctx);
 }
 
 extern "C" hevcdl_status hevcdl_sao_frames(hevcdl_ctx *ctx, const uint8_t *org, const uint8_t *deblocked, int n_frames, hevcdl_sao_blk *params, uint8_t *out)
 {
-  hevcdl_status st = check_frames(ctx, n_frames); if (st) return st;
-  if (n_frames == 0) return HEVCDL_OK;
+  FRAMES_OR_RETURN(ctx, n_frames);
   if (!org || !deblocked || !params || !out) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null pointer");
-  st = ensure_staging(ctx); if (st) return st;
-  if (!ctx->d_sao_params) HIPCHK(hipMalloc(&ctx->d_sao_params, (size_t)ctx->ctus * sizeof(hevcdl_sao_blk) * ctx->cfg.max_frames));
-  HIPCHK(hipMemcpy(ctx->d_yuv, org, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(ctx->d_recon, deblocked, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
+  TRY(ensure_staging(ctx));
+  TRY(lazy_alloc(ctx, ctx->sao.d_sao_params, ctx->sao_bytes(ctx->cfg.max_frames), "SAO parameters (cfg.max_frames)"));
+  HIPCHK(hipMemcpy(ctx->stage.d_yuv, org, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(ctx->stage.d_recon, deblocked, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
   // the records staging area is free here and large enough for one more picture set (15120 B per CTU >= 6144)
-  st = hevcdl_sao_frames_dev(ctx, ctx->d_yuv, ctx->d_recon, n_frames, ctx->d_sao_params, ctx->d_records, nullptr); if (st) return st;
-  hipError_t e = hipDeviceSynchronize();
-  if (e != hipSuccess) return fail(ctx, HEVCDL_ERR_HIP, "sao kernels", e);
-  HIPCHK(hipMemcpy(params, ctx->d_sao_params, (size_t)ctx->ctus * sizeof(hevcdl_sao_blk) * n_frames, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(out, ctx->d_records, ctx->frame_bytes * n_frames, hipMemcpyDeviceToHost));
+  TRY(hevcdl_sao_frames_dev(ctx, ctx->stage.d_yuv, ctx->stage.d_recon, n_frames, ctx->sao.d_sao_params, ctx->stage.d_records, nullptr));
+  TRY(sync_or_fail(ctx, "sao kernels"));
+  HIPCHK(hipMemcpy(params, ctx->sao.d_sao_params, ctx->sao_bytes(n_frames), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out, ctx->stage.d_records, ctx->frame_bytes * n_frames, hipMemcpyDeviceToHost));
   return HEVCDL_OK;
 }
 
@@ -966,67 +929,66 @@ static void quality_picture_params(const hevcdl_ctx *ctx, hevcdl_quality_params 
 // where a front end sizes its batch, and not in the middle of an encode -- or by the first hevcdl_picture_quality* call of a context that never enabled the switch.
 static hevcdl_status ensure_quality_workspace(hevcdl_ctx *ctx)
 {
-  if (ctx->d_q_weights) return HEVCDL_OK;
+  if (ctx->q.d_q_weights) return HEVCDL_OK;
   hevcdl_quality_params p; quality_picture_params(ctx, &p);
   double wt[121]; quality_weights(wt);
   const int group = std::min(ctx->cfg.max_frames, 16);                // pictures per pass: bounds the pyramid workspace (33 MB a picture at 2160p)
-  unsigned char *pyr = nullptr, *part = nullptr, *dw = nullptr;
-  hipError_t e = hipMalloc(&pyr, std::max<size_t>(p.pyr_pic_words, 1) * 4 * group);
-  if (e == hipSuccess) e = hipMalloc(&part, std::max<size_t>(p.part_pic, 1) * sizeof(double) * group);
-  if (e == hipSuccess) e = hipMalloc(&dw, sizeof wt);
-  if (e == hipSuccess) e = hipMemcpy(dw, wt, sizeof wt, hipMemcpyHostToDevice);
-  if (e != hipSuccess) { hipFree(pyr); hipFree(part); hipFree(dw); (void)hipGetLastError(); return fail(ctx, e == hipErrorOutOfMemory ? HEVCDL_ERR_OOM : HEVCDL_ERR_HIP, "picture quality workspace", e); }
-  ctx->d_q_pyr = pyr; ctx->d_q_partial = part; ctx->d_q_weights = dw; ctx->q_group = group;
+  Quality &q = ctx->q;
+  TRY(alloc_all(ctx, { want(q.d_q_pyr, std::max<size_t>(p.pyr_pic_words, 1) * 4 * group), want(q.d_q_partial, std::max<size_t>(p.part_pic, 1) * sizeof(double) * group), want(q.d_q_weights, sizeof wt) },
+                "picture quality workspace"));
+  const hipError_t e = hipMemcpy(q.d_q_weights, wt, sizeof wt, hipMemcpyHostToDevice);
+  if (e != hipSuccess) { q.d_q_pyr.reset(); q.d_q_partial.reset(); q.d_q_weights.reset(); return hip_fail(ctx, "picture quality workspace", e); }
+  q.q_group = group;
   return HEVCDL_OK;
+}
+
+// do out_bytes at out reach into in_bytes at in?  (results must not lie inside the pictures they are computed from; every other overlap is the caller's business)
+static bool overlaps(const void *out, size_t out_bytes, const void *in, size_t in_bytes)
+{
+  const uintptr_t o = (uintptr_t)out, a = (uintptr_t)in;
+  return in && o < a + in_bytes && a < o + out_bytes;
 }
 
 // the quality launches for packed pictures of w x h luma samples (at most the context's size: the workspace is the context's)
 static hevcdl_status quality_sized_dev(hevcdl_ctx *ctx, const void *d_org, const void *d_pic, int n_frames, void *d_out, hipStream_t s, int w, int h)
 {
-  hevcdl_status st = ensure_quality_workspace(ctx); if (st) return st;
+  TRY(ensure_quality_workspace(ctx));
   hevcdl_quality_params p; quality_sized_params(ctx, &p, w, h);
   if (w != ctx->cfg.width || h != ctx->cfg.height) { // a window: its levels and tile sums must fit the slots laid out for the whole picture
     hevcdl_quality_params full; quality_picture_params(ctx, &full);
     if (p.pyr_pic_words > full.pyr_pic_words || p.part_pic > full.part_pic) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "picture quality: the window needs more workspace than the picture");
   }
   const size_t frame_bytes = p.frame_samples * p.sample_bytes;
-  p.pyr = ctx->d_q_pyr; p.partial = ctx->d_q_partial; p.weights = ctx->d_q_weights; p.out = d_out;
+  p.pyr = ctx->q.d_q_pyr; p.partial = ctx->q.d_q_partial; p.weights = ctx->q.d_q_weights; p.out = d_out;
   HIPCHK(hipMemsetAsync(d_out, 0, sizeof(hevcdl_quality) * (size_t)n_frames, s));
-  for (int first = 0; first < n_frames; first += ctx->q_group) {        // a picture's result does not depend on the pass it falls into: every picture has its own workspace slot
-    p.n_pics = std::min(ctx->q_group, n_frames - first); p.out_first = first;
+  for (int first = 0; first < n_frames; first += ctx->q.q_group) {        // a picture's result does not depend on the pass it falls into: every picture has its own workspace slot
+    p.n_pics = std::min(ctx->q.q_group, n_frames - first); p.out_first = first;
     p.org = (const unsigned char *)d_org + frame_bytes * (size_t)first; p.pic = (const unsigned char *)d_pic + frame_bytes * (size_t)first;
     hevcdl_launch_quality(&p, s);
   }
-  HIPCHK(hipGetLastError());
-  return HEVCDL_OK;
+  return launch_status(ctx);
 }
 
 extern "C" hevcdl_status hevcdl_picture_quality_dev(hevcdl_ctx *ctx, const void *d_org, const void *d_pic, int n_frames, void *d_out, void *stream)
 {
-  hevcdl_status st = check_frames(ctx, n_frames); if (st) return st;
-  if (n_frames == 0) return HEVCDL_OK;
+  FRAMES_OR_RETURN(ctx, n_frames);
   if (!d_org || !d_pic || !d_out) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null device pointer");
-  { // the results must not lie inside the pictures they are computed from (every other overlap is the caller's business: d_org == d_pic is a picture compared with itself)
-    const uintptr_t o = (uintptr_t)d_out, oe = o + sizeof(hevcdl_quality) * (size_t)n_frames, span = ctx->frame_bytes * (size_t)n_frames;
-    const uintptr_t a = (uintptr_t)d_org, b = (uintptr_t)d_pic;
-    if ((o < a + span && a < oe) || (o < b + span && b < oe)) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "picture quality: the output overlaps an input");
-  }
+  const size_t out_b = sizeof(hevcdl_quality) * (size_t)n_frames, span = ctx->frame_bytes * (size_t)n_frames;      // (d_org == d_pic is a picture compared with itself)
+  if (overlaps(d_out, out_b, d_org, span) || overlaps(d_out, out_b, d_pic, span)) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "picture quality: the output overlaps an input");
   return quality_sized_dev(ctx, d_org, d_pic, n_frames, d_out, (hipStream_t)stream, ctx->cfg.width, ctx->cfg.height);
 }
 
 extern "C" hevcdl_status hevcdl_picture_quality(hevcdl_ctx *ctx, const void *org, const void *pic, int n_frames, hevcdl_quality *out)
 {
-  hevcdl_status st = check_frames(ctx, n_frames); if (st) return st;
-  if (n_frames == 0) return HEVCDL_OK;
+  FRAMES_OR_RETURN(ctx, n_frames);
   if (!org || !pic || !out) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null pointer");
-  st = ensure_staging(ctx); if (st) return st;
-  if (!ctx->d_q_out) HIPCHK(hipMalloc(&ctx->d_q_out, sizeof(hevcdl_quality) * (size_t)ctx->cfg.max_frames));
-  HIPCHK(hipMemcpy(ctx->d_yuv, org, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(ctx->d_recon, pic, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
-  st = hevcdl_picture_quality_dev(ctx, ctx->d_yuv, ctx->d_recon, n_frames, ctx->d_q_out, nullptr); if (st) return st;
-  hipError_t e = hipDeviceSynchronize();
-  if (e != hipSuccess) return fail(ctx, HEVCDL_ERR_HIP, "quality kernels", e);
-  HIPCHK(hipMemcpy(out, ctx->d_q_out, sizeof(hevcdl_quality) * (size_t)n_frames, hipMemcpyDeviceToHost));
+  TRY(ensure_staging(ctx));
+  TRY(lazy_alloc(ctx, ctx->q.d_q_out, sizeof(hevcdl_quality) * (size_t)ctx->cfg.max_frames, "picture quality results"));
+  HIPCHK(hipMemcpy(ctx->stage.d_yuv, org, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(ctx->stage.d_recon, pic, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
+  TRY(hevcdl_picture_quality_dev(ctx, ctx->stage.d_yuv, ctx->stage.d_recon, n_frames, ctx->q.d_q_out, nullptr));
+  TRY(sync_or_fail(ctx, "quality kernels"));
+  HIPCHK(hipMemcpy(out, ctx->q.d_q_out, sizeof(hevcdl_quality) * (size_t)n_frames, hipMemcpyDeviceToHost));
   return HEVCDL_OK;
 }
 
@@ -1035,9 +997,7 @@ extern "C" hevcdl_status hevcdl_plane_quality(int device, const void *org, const
 {
   if (!org || !pic || !sse || !msssim || width < 1 || height < 1 || width > 16384 || height > 16384) return HEVCDL_ERR_INVALID_ARG;
   if (bit_depth < 8 || bit_depth > 16) return HEVCDL_ERR_UNSUPPORTED;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) { (void)hipGetLastError(); return HEVCDL_ERR_NO_DEVICE; }
-  if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return HEVCDL_ERR_HIP; }
+  TRY(select_device(device));
   hevcdl_quality_params p;
   memset(&p, 0, sizeof p);
   p.n_planes = 1; p.plane_w[0] = width; p.plane_h[0] = height; p.frame_samples = (size_t)width * height; p.sample_bytes = bit_depth > 8 ? 2 : 1; p.n_pics = 1;
@@ -1045,24 +1005,22 @@ extern "C" hevcdl_status hevcdl_plane_quality(int device, const void *org, const
   hevcdl_quality_layout(&p);
   double wt[121]; quality_weights(wt);
   const size_t bytes = p.frame_samples * p.sample_bytes;
-  unsigned char *d[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-  const size_t sz[6] = { bytes, bytes, std::max<size_t>(p.pyr_pic_words, 1) * 4, std::max<size_t>(p.part_pic, 1) * sizeof(double), sizeof wt, sizeof(hevcdl_quality) };
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < 6 && e == hipSuccess; i++) e = hipMalloc(&d[i], sz[i]);
+  DevBuf<unsigned char> d_org, d_pic, d_pyr, d_part, d_wt, d_out;
+  TRY(alloc_all(nullptr, { want(d_org, bytes), want(d_pic, bytes), want(d_pyr, std::max<size_t>(p.pyr_pic_words, 1) * 4), want(d_part, std::max<size_t>(p.part_pic, 1) * sizeof(double)),
+                           want(d_wt, sizeof wt), want(d_out, sizeof(hevcdl_quality)) }, ""));
   hevcdl_quality q; memset(&q, 0, sizeof q);
-  if (e == hipSuccess) e = hipMemcpy(d[0], org, bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d[1], pic, bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d[4], wt, sizeof wt, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(d[5], 0, sizeof q);
+  hipError_t e = hipMemcpy(d_org, org, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_pic, pic, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_wt, wt, sizeof wt, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(d_out, 0, sizeof q);
   if (e == hipSuccess) {
-    p.org = d[0]; p.pic = d[1]; p.pyr = d[2]; p.partial = d[3]; p.weights = d[4]; p.out = d[5];
+    p.org = d_org; p.pic = d_pic; p.pyr = d_pyr; p.partial = d_part; p.weights = d_wt; p.out = d_out;
     hevcdl_launch_quality(&p, nullptr);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(&q, d[5], sizeof q, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(&q, d_out, sizeof q, hipMemcpyDeviceToHost);
   }
-  for (int i = 0; i < 6; i++) hipFree(d[i]);
-  if (e != hipSuccess) { (void)hipGetLastError(); return e == hipErrorOutOfMemory ? HEVCDL_ERR_OOM : HEVCDL_ERR_HIP; }
+  if (e != hipSuccess) return hip_fail(nullptr, "", e);
   *sse = q.sse[0]; *msssim = q.msssim[0];
   return HEVCDL_OK;
 }
@@ -1071,30 +1029,34 @@ extern "C" hevcdl_status hevcdl_enable_quality(hevcdl_ctx *ctx, int on)
 {
   if (!ctx) return HEVCDL_ERR_INVALID_ARG;
   if (on) { // the whole of what the switch costs is reserved here: a refused allocation is this call's HEVCDL_ERR_OOM, not a later encode's
-    hevcdl_status st = check_frames(ctx, 0); if (st) return st;
-    st = ensure_quality_workspace(ctx); if (st) return st;
-    if (!ctx->d_q_out) { hipError_t e = hipMalloc(&ctx->d_q_out, sizeof(hevcdl_quality) * (size_t)ctx->cfg.max_frames);
-      if (e != hipSuccess) { (void)hipGetLastError(); return fail(ctx, e == hipErrorOutOfMemory ? HEVCDL_ERR_OOM : HEVCDL_ERR_HIP, "picture quality results", e); } }
-    ctx->quality_on = true;
+    TRY(check_frames(ctx, 0));
+    TRY(ensure_quality_workspace(ctx));
+    TRY(lazy_alloc(ctx, ctx->q.d_q_out, sizeof(hevcdl_quality) * (size_t)ctx->cfg.max_frames, "picture quality results"));
+    ctx->q.quality_on = true;
     return HEVCDL_OK;
   }
-  ctx->quality_on = false; ctx->h_quality.clear();
-  { // off: the workspace goes back (a later hevcdl_picture_quality* call allocates its own again)
-    hipError_t e = hipSetDevice(ctx->cfg.device); if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return fail(ctx, HEVCDL_ERR_HIP, "hevcdl_enable_quality", e);
-    hipFree(ctx->d_q_pyr); hipFree(ctx->d_q_partial); hipFree(ctx->d_q_weights); hipFree(ctx->d_q_out);
-    ctx->d_q_pyr = ctx->d_q_partial = ctx->d_q_weights = ctx->d_q_out = nullptr; ctx->q_group = 0;
-  }
+  ctx->q.quality_on = false; ctx->q.h_quality.clear();
+  TRY(sync_or_fail(ctx, "hevcdl_enable_quality"));
+  ctx->q = Quality();      // off: the workspace goes back (a later hevcdl_picture_quality* call allocates its own again)
   return HEVCDL_OK;
+}
+
+// what the hevcdl_get_* of a switch check in this order: the pointers and signs, the switch (turned on by `enabler`), the range against the `have` pictures of the last batch
+static hevcdl_status check_batch_range(hevcdl_ctx *ctx, const char *who, bool pointers, bool on, const char *enabler, int first, int count, long long have)
+{
+  char msg[160];
+  if (!pointers || first < 0 || count < 0) snprintf(msg, sizeof msg, "%s: bad range", who);
+  else if (!on) snprintf(msg, sizeof msg, "%s: %s was not called", who, enabler);
+  else if ((long long)first + count > have) snprintf(msg, sizeof msg, "%s: pictures outside the last batch", who);
+  else return HEVCDL_OK;
+  return fail(ctx, HEVCDL_ERR_INVALID_ARG, msg);
 }
 
 extern "C" hevcdl_status hevcdl_get_quality(hevcdl_ctx *ctx, int first, int count, hevcdl_quality *out)
 {
   if (!ctx) return HEVCDL_ERR_INVALID_ARG;
-  if (!out || first < 0 || count < 0) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_get_quality: bad range");
-  if (!ctx->quality_on) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_get_quality: hevcdl_enable_quality was not called");
-  if ((size_t)first + (size_t)count > ctx->h_quality.size()) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_get_quality: pictures outside the last batch");
-  if (count) memcpy(out, ctx->h_quality.data() + first, sizeof(hevcdl_quality) * (size_t)count);
+  TRY(check_batch_range(ctx, "hevcdl_get_quality", out != nullptr, ctx->q.quality_on, "hevcdl_enable_quality", first, count, (long long)ctx->q.h_quality.size()));
+  if (count) memcpy(out, ctx->q.h_quality.data() + first, sizeof(hevcdl_quality) * (size_t)count);
   return HEVCDL_OK;
 }
 
@@ -1117,18 +1079,20 @@ static void report_picture_params(const hevcdl_ctx *ctx, hevcdl_report_params *p
   report_plane_params(p, 3, pw, ph, ctx->cfg.bit_depth > 8 ? 2 : 1);
 }
 
+static hevcdl_status check_method(hevcdl_ctx *ctx, int method, const char *who)
+{
+  if (method >= 0 && method <= 3) return HEVCDL_OK;
+  char msg[160]; snprintf(msg, sizeof msg, "%s: method must be 0 (none), 1 (MD5), 2 (CRC) or 3 (checksum)", who);
+  return fail(ctx, HEVCDL_ERR_INVALID_ARG, msg);
+}
+
 static hevcdl_status ensure_report_workspace(hevcdl_ctx *ctx)
 {
-  if (ctx->d_rp_partials) return HEVCDL_OK;
+  if (ctx->rp.d_rp_partials) return HEVCDL_OK;
   hevcdl_report_params p; report_picture_params(ctx, &p);
   const size_t nf = (size_t)ctx->cfg.max_frames;
-  unsigned char *out = nullptr, *sse = nullptr; uint32_t *part = nullptr;
-  hipError_t e = hipMalloc(&out, sizeof(hevcdl_picture_report_t) * nf);
-  if (e == hipSuccess) e = hipMalloc(&sse, sizeof(hevcdl_quality) * nf);
-  if (e == hipSuccess) e = hipMalloc(&part, sizeof(uint32_t) * 3 * (size_t)p.chunk_stride * nf);
-  if (e != hipSuccess) { hipFree(out); hipFree(sse); hipFree(part); (void)hipGetLastError(); return fail(ctx, e == hipErrorOutOfMemory ? HEVCDL_ERR_OOM : HEVCDL_ERR_HIP, "picture report workspace", e); }
-  ctx->d_rp_out = out; ctx->d_rp_sse = sse; ctx->d_rp_partials = part;
-  return HEVCDL_OK;
+  return alloc_all(ctx, { want(ctx->rp.d_rp_out, sizeof(hevcdl_picture_report_t) * nf), want(ctx->rp.d_rp_sse, sizeof(hevcdl_quality) * nf),
+                          want(ctx->rp.d_rp_partials, sizeof(uint32_t) * 3 * (size_t)p.chunk_stride * nf) }, "picture report workspace");
 }
 
 // sse_org / sse_pic: the pictures the SSE is taken over, packed at sse_w x sse_h luma samples -- the originals and d_pic themselves, or the window crops of a padded
@@ -1136,29 +1100,27 @@ static hevcdl_status ensure_report_workspace(hevcdl_ctx *ctx)
 static hevcdl_status report_dev(hevcdl_ctx *ctx, const void *d_org_opt, const void *d_pic, int n_frames, int method, void *d_out, void *stream,
                                 const void *sse_org, const void *sse_pic, int sse_w, int sse_h)
 {
-  hevcdl_status st = check_frames(ctx, n_frames); if (st) return st;
-  if (method < 0 || method > 3) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "picture report: method must be 0 (none), 1 (MD5), 2 (CRC) or 3 (checksum)");
+  TRY(check_frames(ctx, n_frames));
+  TRY(check_method(ctx, method, "picture report"));
   if (n_frames == 0) return HEVCDL_OK;
   if (!d_pic || !d_out || ((uintptr_t)d_out & 7)) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "picture report: null or misaligned device pointer");
-  { // the records must not lie inside the pictures they are computed from
-    const uintptr_t o = (uintptr_t)d_out, oe = o + sizeof(hevcdl_picture_report_t) * (size_t)n_frames, span = ctx->frame_bytes * (size_t)n_frames;
-    const uintptr_t a = (uintptr_t)d_org_opt, b = (uintptr_t)d_pic;
-    if ((d_org_opt && o < a + span && a < oe) || (o < b + span && b < oe)) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "picture report: the output overlaps an input");
-  }
+  const size_t out_b = sizeof(hevcdl_picture_report_t) * (size_t)n_frames, span = ctx->frame_bytes * (size_t)n_frames;
+  if (overlaps(d_out, out_b, d_org_opt, span) || overlaps(d_out, out_b, d_pic, span)) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "picture report: the output overlaps an input");
   hipStream_t s = (hipStream_t)stream;
-  st = ensure_report_workspace(ctx); if (st) return st;
-  if (ctx->profile) for (hipEvent_t &e : ctx->rp_ev) if (!e) HIPCHK(hipEventCreate(&e));
+  TRY(ensure_report_workspace(ctx));
+  if (ctx->profile) for (Event &e : ctx->rp_ev) if (!e) HIPCHK(hipEventCreate(&e.p));
   HIPCHK(hipMemsetAsync(d_out, 0, sizeof(hevcdl_picture_report_t) * (size_t)n_frames, s));
   if (ctx->profile) HIPCHK(hipEventRecord(ctx->rp_ev[0], s));
   if (d_org_opt) { // the exact SSE: quality_kernel.hip's kernel alone, into hevcdl_quality-shaped words the finish kernel copies from
     hevcdl_quality_params q; quality_sized_params(ctx, &q, sse_w, sse_h);
-    q.org = sse_org; q.pic = sse_pic; q.out = ctx->d_rp_sse; q.n_pics = n_frames; q.out_first = 0;
-    HIPCHK(hipMemsetAsync(ctx->d_rp_sse, 0, sizeof(hevcdl_quality) * (size_t)n_frames, s));
+    q.org = sse_org; q.pic = sse_pic; q.out = ctx->rp.d_rp_sse; q.n_pics = n_frames; q.out_first = 0;
+    HIPCHK(hipMemsetAsync(ctx->rp.d_rp_sse, 0, sizeof(hevcdl_quality) * (size_t)n_frames, s));
     hevcdl_launch_quality_sse(&q, s);
   }
   hevcdl_report_params p; report_picture_params(ctx, &p);
-  p.pic = d_pic; p.out = d_out; p.partials = ctx->d_rp_partials; p.sse = d_org_opt ? ctx->d_rp_sse : nullptr; p.n_pics = n_frames; p.out_first = 0; p.method = method;
-  hevcdl_launch_report(&p, s, ctx->profile ? (void **)(ctx->rp_ev + 1) : nullptr);
+  p.pic = d_pic; p.out = d_out; p.partials = ctx->rp.d_rp_partials; p.sse = d_org_opt ? ctx->rp.d_rp_sse.p : nullptr; p.n_pics = n_frames; p.out_first = 0; p.method = method;
+  void *ev[3] = { ctx->rp_ev[1].p, ctx->rp_ev[2].p, ctx->rp_ev[3].p };
+  hevcdl_launch_report(&p, s, ctx->profile ? ev : nullptr);
   HIPCHK(hipGetLastError());
   if (ctx->profile) { // timing is a diagnostic: the call then waits for its launches
     HIPCHK(hipEventSynchronize(ctx->rp_ev[3]));
@@ -1175,18 +1137,17 @@ extern "C" hevcdl_status hevcdl_picture_report_dev(hevcdl_ctx *ctx, const void *
 
 extern "C" hevcdl_status hevcdl_picture_report(hevcdl_ctx *ctx, const void *org_opt, const void *pic, int n_frames, int method, hevcdl_picture_report_t *out)
 {
-  hevcdl_status st = check_frames(ctx, n_frames); if (st) return st;
-  if (method < 0 || method > 3) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "picture report: method must be 0 (none), 1 (MD5), 2 (CRC) or 3 (checksum)");
+  TRY(check_frames(ctx, n_frames));
+  TRY(check_method(ctx, method, "picture report"));
   if (n_frames == 0) return HEVCDL_OK;
   if (!pic || !out) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null pointer");
-  st = ensure_staging(ctx); if (st) return st;
-  st = ensure_report_workspace(ctx); if (st) return st;
-  if (org_opt) HIPCHK(hipMemcpy(ctx->d_yuv, org_opt, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(ctx->d_recon, pic, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
-  st = hevcdl_picture_report_dev(ctx, org_opt ? ctx->d_yuv : nullptr, ctx->d_recon, n_frames, method, ctx->d_rp_out, nullptr); if (st) return st;
-  hipError_t e = hipDeviceSynchronize();
-  if (e != hipSuccess) return fail(ctx, HEVCDL_ERR_HIP, "report kernels", e);
-  HIPCHK(hipMemcpy(out, ctx->d_rp_out, sizeof(hevcdl_picture_report_t) * (size_t)n_frames, hipMemcpyDeviceToHost));
+  TRY(ensure_staging(ctx));
+  TRY(ensure_report_workspace(ctx));
+  if (org_opt) HIPCHK(hipMemcpy(ctx->stage.d_yuv, org_opt, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(ctx->stage.d_recon, pic, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
+  TRY(hevcdl_picture_report_dev(ctx, org_opt ? ctx->stage.d_yuv.p : nullptr, ctx->stage.d_recon, n_frames, method, ctx->rp.d_rp_out, nullptr));
+  TRY(sync_or_fail(ctx, "report kernels"));
+  HIPCHK(hipMemcpy(out, ctx->rp.d_rp_out, sizeof(hevcdl_picture_report_t) * (size_t)n_frames, hipMemcpyDeviceToHost));
   return HEVCDL_OK;
 }
 
@@ -1195,27 +1156,22 @@ extern "C" hevcdl_status hevcdl_plane_hash(int device, const void *plane, int wi
 {
   if (!plane || !digest16 || width < 1 || height < 1 || width > (1 << 20) || height > (1 << 20) || (long long)width * height > (1ll << 28) || method < 1 || method > 3) return HEVCDL_ERR_INVALID_ARG;
   if (bit_depth < 8 || bit_depth > 16) return HEVCDL_ERR_UNSUPPORTED;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) { (void)hipGetLastError(); return HEVCDL_ERR_NO_DEVICE; }
-  if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return HEVCDL_ERR_HIP; }
+  TRY(select_device(device));
   hevcdl_report_params p; report_plane_params(&p, 1, &width, &height, bit_depth > 8 ? 2 : 1);
   p.n_pics = 1; p.method = method;
-  unsigned char *d[3] = { nullptr, nullptr, nullptr };
-  const size_t sz[3] = { p.frame_bytes, sizeof(uint32_t) * 3 * (size_t)p.chunk_stride, sizeof(hevcdl_picture_report_t) };
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < 3 && e == hipSuccess; i++) e = hipMalloc(&d[i], sz[i]);
+  DevBuf<unsigned char> d_pic, d_out; DevBuf<uint32_t> d_part;
+  TRY(alloc_all(nullptr, { want(d_pic, p.frame_bytes), want(d_part, sizeof(uint32_t) * 3 * (size_t)p.chunk_stride), want(d_out, sizeof(hevcdl_picture_report_t)) }, ""));
   hevcdl_picture_report_t r; memset(&r, 0, sizeof r);
-  if (e == hipSuccess) e = hipMemcpy(d[0], plane, p.frame_bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(d[2], 0, sizeof r);
+  hipError_t e = hipMemcpy(d_pic, plane, p.frame_bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(d_out, 0, sizeof r);
   if (e == hipSuccess) {
-    p.pic = d[0]; p.partials = (uint32_t *)d[1]; p.out = d[2];
+    p.pic = d_pic; p.partials = d_part; p.out = d_out;
     hevcdl_launch_report(&p, nullptr, nullptr);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(&r, d[2], sizeof r, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(&r, d_out, sizeof r, hipMemcpyDeviceToHost);
   }
-  for (int i = 0; i < 3; i++) hipFree(d[i]);
-  if (e != hipSuccess) { (void)hipGetLastError(); return e == hipErrorOutOfMemory ? HEVCDL_ERR_OOM : HEVCDL_ERR_HIP; }
+  if (e != hipSuccess) return hip_fail(nullptr, "", e);
   memset(digest16, 0, 16); memcpy(digest16, r.digest, (size_t)r.plane_bytes);
   return HEVCDL_OK;
 }
@@ -1224,29 +1180,23 @@ extern "C" hevcdl_status hevcdl_enable_picture_report(hevcdl_ctx *ctx, int on, i
 {
   if (!ctx) return HEVCDL_ERR_INVALID_ARG;
   if (on) { // the whole of what the switch costs is reserved here
-    if (method < 0 || method > 3) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_enable_picture_report: method must be 0 (none), 1 (MD5), 2 (CRC) or 3 (checksum)");
-    hevcdl_status st = check_frames(ctx, 0); if (st) return st;
-    st = ensure_report_workspace(ctx); if (st) return st;
-    ctx->report_on = true; ctx->report_method = method;
+    TRY(check_method(ctx, method, "hevcdl_enable_picture_report"));
+    TRY(check_frames(ctx, 0));
+    TRY(ensure_report_workspace(ctx));
+    ctx->rp.report_on = true; ctx->rp.report_method = method;
     return HEVCDL_OK;
   }
-  ctx->report_on = false; ctx->report_method = 0; ctx->h_report.clear();
-  { // off: the workspace goes back (a later hevcdl_picture_report* call allocates its own again)
-    hipError_t e = hipSetDevice(ctx->cfg.device); if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return fail(ctx, HEVCDL_ERR_HIP, "hevcdl_enable_picture_report", e);
-    hipFree(ctx->d_rp_out); hipFree(ctx->d_rp_sse); hipFree(ctx->d_rp_partials);
-    ctx->d_rp_out = ctx->d_rp_sse = nullptr; ctx->d_rp_partials = nullptr;
-  }
+  ctx->rp.report_on = false; ctx->rp.report_method = 0; ctx->rp.h_report.clear();
+  TRY(sync_or_fail(ctx, "hevcdl_enable_picture_report"));
+  ctx->rp = Report();      // off: the workspace goes back (a later hevcdl_picture_report* call allocates its own again)
   return HEVCDL_OK;
 }
 
 extern "C" hevcdl_status hevcdl_get_picture_report(hevcdl_ctx *ctx, int first, int count, hevcdl_picture_report_t *out)
 {
   if (!ctx) return HEVCDL_ERR_INVALID_ARG;
-  if (!out || first < 0 || count < 0) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_get_picture_report: bad range");
-  if (!ctx->report_on) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_get_picture_report: hevcdl_enable_picture_report was not called");
-  if ((size_t)first + (size_t)count > ctx->h_report.size()) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_get_picture_report: pictures outside the last batch");
-  if (count) memcpy(out, ctx->h_report.data() + first, sizeof(hevcdl_picture_report_t) * (size_t)count);
+  TRY(check_batch_range(ctx, "hevcdl_get_picture_report", out != nullptr, ctx->rp.report_on, "hevcdl_enable_picture_report", first, count, (long long)ctx->rp.h_report.size()));
+  if (count) memcpy(out, ctx->rp.h_report.data() + first, sizeof(hevcdl_picture_report_t) * (size_t)count);
   return HEVCDL_OK;
 }
 
@@ -1260,35 +1210,33 @@ extern "C" hevcdl_status hevcdl_get_report_info(hevcdl_ctx *ctx, double *kernel_
 // ---- source and output formats (source_kernel.hip; the arithmetic and the host mirrors: source_core.h, hevcdl_bitstream.cpp) ---------------------------------------
 static void source_release(hevcdl_ctx *ctx)
 {
-  hipFree(ctx->d_src); hipFree(ctx->d_win_org); hipFree(ctx->d_win_pic); hipFree(ctx->d_win_sse);
-  ctx->d_src = ctx->d_win_org = ctx->d_win_pic = ctx->d_win_sse = nullptr; ctx->source_on = ctx->source_windowed = false;
-  ctx->d_last_final = nullptr; ctx->last_frames = 0;
+  ctx->src = Source();
 }
 
 extern "C" hevcdl_status hevcdl_set_source_format(hevcdl_ctx *ctx, const hevcdl_source_format *fmt)
 {
-  hevcdl_status st = check_frames(ctx, 0); if (st) return st;
+  TRY(check_frames(ctx, 0));
   if (fmt && (fmt->struct_size != sizeof *fmt || !hevcdl_src::format_fits(fmt->source_width, fmt->source_height, fmt->input_bit_depth, fmt->output_bit_depth, ctx->cfg.width, ctx->cfg.height)))
     return fail(ctx, HEVCDL_ERR_INVALID_ARG, "source format: even source size of at least 2 x 2 and at most the context's, even padding, bit depths 8 .. 16");
-  { hipError_t e = hipDeviceSynchronize(); if (e != hipSuccess) return fail(ctx, HEVCDL_ERR_HIP, "hevcdl_set_source_format", e); }
+  TRY(sync_or_fail(ctx, "hevcdl_set_source_format"));
   source_release(ctx);
   if (!fmt) return HEVCDL_OK;
-  ctx->src_fmt = *fmt;
+  ctx->src.src_fmt = *fmt;
   const bool windowed = fmt->source_width != ctx->cfg.width || fmt->source_height != ctx->cfg.height;
   const size_t nf = (size_t)ctx->cfg.max_frames, win_b = hevcdl_src::picture_samples(fmt->source_width, fmt->source_height) * (ctx->cfg.bit_depth > 8 ? 2 : 1);
-  hipError_t e = hipMalloc(&ctx->d_src, std::max(hevcdl_source_frame_bytes(fmt), hevcdl_output_frame_bytes(fmt)) * nf);      // the whole of what the format costs is reserved here
-  if (e == hipSuccess && windowed) e = hipMalloc(&ctx->d_win_org, win_b * nf);
-  if (e == hipSuccess && windowed) e = hipMalloc(&ctx->d_win_pic, win_b * nf);
-  if (e == hipSuccess && windowed) e = hipMalloc(&ctx->d_win_sse, sizeof(hevcdl_quality) * nf);
-  if (e != hipSuccess) { source_release(ctx); (void)hipGetLastError(); return fail(ctx, e == hipErrorOutOfMemory ? HEVCDL_ERR_OOM : HEVCDL_ERR_HIP, "source format buffers (cfg.max_frames)", e); }
-  ctx->source_on = true; ctx->source_windowed = windowed;
+  Source &g = ctx->src;
+  const char *what = "source format buffers (cfg.max_frames)";
+  hevcdl_status st = alloc_all(ctx, { want(g.d_src, std::max(hevcdl_source_frame_bytes(fmt), hevcdl_output_frame_bytes(fmt)) * nf) }, what);      // the whole of what the format costs is reserved here
+  if (!st && windowed) st = alloc_all(ctx, { want(g.d_win_org, win_b * nf), want(g.d_win_pic, win_b * nf), want(g.d_win_sse, sizeof(hevcdl_quality) * nf) }, what);
+  if (st) { source_release(ctx); return st; }
+  ctx->src.source_on = true; ctx->src.source_windowed = windowed;
   return HEVCDL_OK;
 }
 
 static hevcdl_status source_check(hevcdl_ctx *ctx, int n_frames, const void *a, const void *b, int a_bytes, int b_bytes)
 {
-  hevcdl_status st = check_frames(ctx, n_frames); if (st) return st;
-  if (!ctx->source_on) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_set_source_format was not called");
+  TRY(check_frames(ctx, n_frames));
+  if (!ctx->src.source_on) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_set_source_format was not called");
   if (n_frames && (!a || !b || ((uintptr_t)a & (a_bytes - 1)) || ((uintptr_t)b & (b_bytes - 1)))) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "source format: null or misaligned device pointer");
   return HEVCDL_OK;
 }
@@ -1297,14 +1245,13 @@ extern "C" hevcdl_status hevcdl_load_source_dev(hevcdl_ctx *ctx, const void *d_s
 {
   if (!ctx) return HEVCDL_ERR_INVALID_ARG;
   hevcdl_source_params p; memset(&p, 0, sizeof p);
-  p.src_bytes = ctx->src_fmt.input_bit_depth > 8 ? 2 : 1; p.dst_bytes = ctx->cfg.bit_depth > 8 ? 2 : 1;
-  hevcdl_status st = source_check(ctx, n_frames, d_src, d_coded, p.src_bytes, p.dst_bytes); if (st) return st;
+  p.src_bytes = ctx->src.src_fmt.input_bit_depth > 8 ? 2 : 1; p.dst_bytes = ctx->cfg.bit_depth > 8 ? 2 : 1;
+  TRY(source_check(ctx, n_frames, d_src, d_coded, p.src_bytes, p.dst_bytes));
   if (n_frames == 0) return HEVCDL_OK;
-  p.src = d_src; p.dst = d_coded; p.src_w = ctx->src_fmt.source_width; p.src_h = ctx->src_fmt.source_height; p.dst_w = ctx->cfg.width; p.dst_h = ctx->cfg.height;
-  p.from_depth = ctx->src_fmt.input_bit_depth; p.to_depth = ctx->cfg.bit_depth; p.n_pics = n_frames;
+  p.src = d_src; p.dst = d_coded; p.src_w = ctx->src.src_fmt.source_width; p.src_h = ctx->src.src_fmt.source_height; p.dst_w = ctx->cfg.width; p.dst_h = ctx->cfg.height;
+  p.from_depth = ctx->src.src_fmt.input_bit_depth; p.to_depth = ctx->cfg.bit_depth; p.n_pics = n_frames;
   hevcdl_launch_source_load(&p, stream);
-  HIPCHK(hipGetLastError());
-  return HEVCDL_OK;
+  return launch_status(ctx);
 }
 
 // coded pictures -> pictures of the window's size at to_depth
@@ -1312,45 +1259,42 @@ static hevcdl_status store_window_dev(hevcdl_ctx *ctx, const void *d_pictures, i
 {
   hevcdl_source_params p; memset(&p, 0, sizeof p);
   p.src_bytes = ctx->cfg.bit_depth > 8 ? 2 : 1; p.dst_bytes = to_depth > 8 ? 2 : 1;
-  hevcdl_status st = source_check(ctx, n_frames, d_pictures, d_out, p.src_bytes, p.dst_bytes); if (st) return st;
+  TRY(source_check(ctx, n_frames, d_pictures, d_out, p.src_bytes, p.dst_bytes));
   if (n_frames == 0) return HEVCDL_OK;
-  p.src = d_pictures; p.dst = d_out; p.src_w = ctx->cfg.width; p.src_h = ctx->cfg.height; p.dst_w = ctx->src_fmt.source_width; p.dst_h = ctx->src_fmt.source_height;
+  p.src = d_pictures; p.dst = d_out; p.src_w = ctx->cfg.width; p.src_h = ctx->cfg.height; p.dst_w = ctx->src.src_fmt.source_width; p.dst_h = ctx->src.src_fmt.source_height;
   p.from_depth = ctx->cfg.bit_depth; p.to_depth = to_depth; p.n_pics = n_frames;
   hevcdl_launch_source_store(&p, stream);
-  HIPCHK(hipGetLastError());
-  return HEVCDL_OK;
+  return launch_status(ctx);
 }
 extern "C" hevcdl_status hevcdl_store_output_dev(hevcdl_ctx *ctx, const void *d_pictures, int n_frames, void *d_out, void *stream)
 {
   if (!ctx) return HEVCDL_ERR_INVALID_ARG;
-  return store_window_dev(ctx, d_pictures, n_frames, d_out, stream, ctx->src_fmt.output_bit_depth);
+  return store_window_dev(ctx, d_pictures, n_frames, d_out, stream, ctx->src.src_fmt.output_bit_depth);
 }
 // the window at the internal depth, contiguous: what the quality kernels measure a padded picture by (the store kernel with OUT = PEL, no scaling)
 static hevcdl_status crop_window_dev(hevcdl_ctx *ctx, const void *d_pictures, int n_frames, void *d_out, void *stream) { return store_window_dev(ctx, d_pictures, n_frames, d_out, stream, ctx->cfg.bit_depth); }
 
 extern "C" hevcdl_status hevcdl_load_source(hevcdl_ctx *ctx, const void *src, int n_frames, void *coded_out)
 {
-  hevcdl_status st = source_check(ctx, n_frames, src, coded_out, 1, 1); if (st) return st;
+  TRY(source_check(ctx, n_frames, src, coded_out, 1, 1));
   if (n_frames == 0) return HEVCDL_OK;
-  st = ensure_staging(ctx); if (st) return st;
-  HIPCHK(hipMemcpy(ctx->d_src, src, hevcdl_source_frame_bytes(&ctx->src_fmt) * n_frames, hipMemcpyHostToDevice));
-  st = hevcdl_load_source_dev(ctx, ctx->d_src, n_frames, ctx->d_yuv, nullptr); if (st) return st;
-  hipError_t e = hipDeviceSynchronize();
-  if (e != hipSuccess) return fail(ctx, HEVCDL_ERR_HIP, "source load kernel", e);
-  HIPCHK(hipMemcpy(coded_out, ctx->d_yuv, ctx->frame_bytes * n_frames, hipMemcpyDeviceToHost));
+  TRY(ensure_staging(ctx));
+  HIPCHK(hipMemcpy(ctx->src.d_src, src, hevcdl_source_frame_bytes(&ctx->src.src_fmt) * n_frames, hipMemcpyHostToDevice));
+  TRY(hevcdl_load_source_dev(ctx, ctx->src.d_src, n_frames, ctx->stage.d_yuv, nullptr));
+  TRY(sync_or_fail(ctx, "source load kernel"));
+  HIPCHK(hipMemcpy(coded_out, ctx->stage.d_yuv, ctx->frame_bytes * n_frames, hipMemcpyDeviceToHost));
   return HEVCDL_OK;
 }
 
 extern "C" hevcdl_status hevcdl_store_output(hevcdl_ctx *ctx, const void *pictures, int n_frames, void *out)
 {
-  hevcdl_status st = source_check(ctx, n_frames, pictures, out, 1, 1); if (st) return st;
+  TRY(source_check(ctx, n_frames, pictures, out, 1, 1));
   if (n_frames == 0) return HEVCDL_OK;
-  st = ensure_staging(ctx); if (st) return st;
-  HIPCHK(hipMemcpy(ctx->d_recon, pictures, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
-  st = hevcdl_store_output_dev(ctx, ctx->d_recon, n_frames, ctx->d_src, nullptr); if (st) return st;
-  hipError_t e = hipDeviceSynchronize();
-  if (e != hipSuccess) return fail(ctx, HEVCDL_ERR_HIP, "source store kernel", e);
-  HIPCHK(hipMemcpy(out, ctx->d_src, hevcdl_output_frame_bytes(&ctx->src_fmt) * n_frames, hipMemcpyDeviceToHost));
+  TRY(ensure_staging(ctx));
+  HIPCHK(hipMemcpy(ctx->stage.d_recon, pictures, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
+  TRY(hevcdl_store_output_dev(ctx, ctx->stage.d_recon, n_frames, ctx->src.d_src, nullptr));
+  TRY(sync_or_fail(ctx, "source store kernel"));
+  HIPCHK(hipMemcpy(out, ctx->src.d_src, hevcdl_output_frame_bytes(&ctx->src.src_fmt) * n_frames, hipMemcpyDeviceToHost));
   return HEVCDL_OK;
 }
 
@@ -1359,12 +1303,12 @@ extern "C" hevcdl_status hevcdl_store_output(hevcdl_ctx *ctx, const void *pictur
 extern "C" hevcdl_status hevcdl_get_output_frames(hevcdl_ctx *ctx, int first, int count, void *out)
 {
   if (!ctx) return HEVCDL_ERR_INVALID_ARG;
-  if (!ctx->source_on) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_get_output_frames: hevcdl_set_source_format was not called");
-  if (!out || first < 0 || count < 0 || !ctx->d_last_final || (long long)first + count > ctx->last_frames) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_get_output_frames: pictures outside the last batch");
+  if (!ctx->src.source_on) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_get_output_frames: hevcdl_set_source_format was not called");
+  if (!out || first < 0 || count < 0 || !ctx->src.d_last_final || (long long)first + count > ctx->src.last_frames) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_get_output_frames: pictures outside the last batch");
   if (count == 0) return HEVCDL_OK;
-  hevcdl_status st = hevcdl_store_output_dev(ctx, ctx->d_last_final + ctx->frame_bytes * (size_t)first, count, ctx->d_src, nullptr); if (st) return st;
+  TRY(hevcdl_store_output_dev(ctx, ctx->src.d_last_final + ctx->frame_bytes * (size_t)first, count, ctx->src.d_src, nullptr));
   HIPCHK(hipStreamSynchronize(nullptr));
-  HIPCHK(hipMemcpy(out, ctx->d_src, hevcdl_output_frame_bytes(&ctx->src_fmt) * (size_t)count, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out, ctx->src.d_src, hevcdl_output_frame_bytes(&ctx->src.src_fmt) * (size_t)count, hipMemcpyDeviceToHost));
   return HEVCDL_OK;
 }
 
@@ -1374,116 +1318,117 @@ extern "C" hevcdl_status hevcdl_get_output_frames(hevcdl_ctx *ctx, int first, in
 static hevcdl_status entropy_pipeline(hevcdl_ctx *ctx, int n_frames, int want_sao);
 static hevcdl_status encode_pictures_device(hevcdl_ctx *ctx, const void *yuv, int n_frames, const uint8_t *labels_opt, int deblock, int want_sao, uint8_t **d_final)
 {
-  hevcdl_status st = ensure_staging(ctx); if (st) return st;
-  if (want_sao && !ctx->d_sao_params) HIPCHK(hipMalloc(&ctx->d_sao_params, (size_t)ctx->ctus * sizeof(hevcdl_sao_blk) * ctx->cfg.max_frames));
-  if (want_sao && !ctx->d_picture) HIPCHK(hipMalloc(&ctx->d_picture, ctx->frame_bytes * (size_t)ctx->cfg.max_frames));
-  ctx->d_last_final = nullptr; ctx->last_frames = 0;
-  const bool windowed = ctx->source_on && ctx->source_windowed;
-  const int ww = windowed ? ctx->src_fmt.source_width : ctx->cfg.width, wh = windowed ? ctx->src_fmt.source_height : ctx->cfg.height;      // what SSE and MS-SSIM are taken over
-  if (ctx->source_on) { // hevcdl_set_source_format: the source's own bytes go up; the load kernel pads and converts them in front of everything else
-    HIPCHK(hipMemcpy(ctx->d_src, yuv, hevcdl_source_frame_bytes(&ctx->src_fmt) * n_frames, hipMemcpyHostToDevice));
-    st = hevcdl_load_source_dev(ctx, ctx->d_src, n_frames, ctx->d_yuv, nullptr); if (st) return st;
-    if (windowed) { st = crop_window_dev(ctx, ctx->d_yuv, n_frames, ctx->d_win_org, nullptr); if (st) return st; }
+  TRY(ensure_staging(ctx));
+  if (want_sao) TRY(lazy_alloc(ctx, ctx->sao.d_sao_params, ctx->sao_bytes(ctx->cfg.max_frames), "SAO parameters (cfg.max_frames)"));
+  if (want_sao) TRY(lazy_alloc(ctx, ctx->stage.d_picture, ctx->frame_bytes * (size_t)ctx->cfg.max_frames, "output pictures (cfg.max_frames)"));
+  ctx->src.d_last_final = nullptr; ctx->src.last_frames = 0;
+  const bool windowed = ctx->src.source_on && ctx->src.source_windowed;
+  const int ww = windowed ? ctx->src.src_fmt.source_width : ctx->cfg.width, wh = windowed ? ctx->src.src_fmt.source_height : ctx->cfg.height;      // what SSE and MS-SSIM are taken over
+  if (ctx->src.source_on) { // hevcdl_set_source_format: the source's own bytes go up; the load kernel pads and converts them in front of everything else
+    HIPCHK(hipMemcpy(ctx->src.d_src, yuv, hevcdl_source_frame_bytes(&ctx->src.src_fmt) * n_frames, hipMemcpyHostToDevice));
+    TRY(hevcdl_load_source_dev(ctx, ctx->src.d_src, n_frames, ctx->stage.d_yuv, nullptr));
+    if (windowed) { TRY(crop_window_dev(ctx, ctx->stage.d_yuv, n_frames, ctx->src.d_win_org, nullptr)); }
   } else
-  HIPCHK(hipMemcpy(ctx->d_yuv, yuv, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
-  if (labels_opt) { HIPCHK(hipMemcpy(ctx->d_labels, labels_opt, (size_t)ctx->ctus * 16 * n_frames, hipMemcpyHostToDevice)); st = hevcdl_clamp_labels_dev(ctx, ctx->d_labels, n_frames, nullptr); if (st) return st; }
-  else { st = hevcdl_predict_depth_dev(ctx, ctx->d_yuv, n_frames, ctx->d_labels, nullptr, nullptr); if (st) return st; }
-  st = hevcdl_compress_frames_dev(ctx, ctx->d_yuv, n_frames, ctx->d_labels, ctx->d_records, ctx->d_recon, ctx->d_stats, nullptr); if (st) return st;
+  HIPCHK(hipMemcpy(ctx->stage.d_yuv, yuv, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
+  TRY(stage_labels(ctx, labels_opt, n_frames));
+  TRY(hevcdl_compress_frames_dev(ctx, ctx->stage.d_yuv, n_frames, ctx->stage.d_labels, ctx->stage.d_records, ctx->stage.d_recon, ctx->stage.d_stats, nullptr));
   if (windowed) { // the statistics' SSE (the reconstruction before the in-loop filters) over the window: the decision kernel summed over the padding too
-    st = crop_window_dev(ctx, ctx->d_recon, n_frames, ctx->d_win_pic, nullptr); if (st) return st;
+    TRY(crop_window_dev(ctx, ctx->stage.d_recon, n_frames, ctx->src.d_win_pic, nullptr));
     hevcdl_quality_params q; quality_sized_params(ctx, &q, ww, wh);
-    q.org = ctx->d_win_org; q.pic = ctx->d_win_pic; q.out = ctx->d_win_sse; q.n_pics = n_frames; q.out_first = 0;
-    HIPCHK(hipMemsetAsync(ctx->d_win_sse, 0, sizeof(hevcdl_quality) * (size_t)n_frames, nullptr));
+    q.org = ctx->src.d_win_org; q.pic = ctx->src.d_win_pic; q.out = ctx->src.d_win_sse; q.n_pics = n_frames; q.out_first = 0;
+    HIPCHK(hipMemsetAsync(ctx->src.d_win_sse, 0, sizeof(hevcdl_quality) * (size_t)n_frames, nullptr));
     hevcdl_launch_quality_sse(&q, nullptr);
-    hipLaunchKernelGGL(hevcdl_stats_sse_kernel, dim3((3 * n_frames + 255) / 256), dim3(256), 0, nullptr, (const hevcdl_quality *)ctx->d_win_sse, (hevcdl_frame_stats *)ctx->d_stats, n_frames);
+    hipLaunchKernelGGL(hevcdl_stats_sse_kernel, dim3((3 * n_frames + 255) / 256), dim3(256), 0, nullptr, (const hevcdl_quality *)ctx->src.d_win_sse.p, (hevcdl_frame_stats *)ctx->stage.d_stats.p, n_frames);
     HIPCHK(hipGetLastError());
   }
-  *d_final = ctx->d_recon;
-  if (deblock) { st = hevcdl_deblock_frames_dev(ctx, ctx->d_recon, n_frames, ctx->d_records, ctx->d_recon, nullptr); if (st) return st; }      // in place
-  if (want_sao) { st = hevcdl_sao_frames_dev(ctx, ctx->d_yuv, ctx->d_recon, n_frames, ctx->d_sao_params, ctx->d_picture, nullptr); if (st) return st; *d_final = ctx->d_picture; }
-  ctx->h_quality.clear();
-  ctx->h_report.clear();
-  if (windowed && (ctx->quality_on || ctx->report_on)) { st = crop_window_dev(ctx, *d_final, n_frames, ctx->d_win_pic, nullptr); if (st) return st; }      // the output pictures' window (TEncGOP.cpp:2302-2303, 2375-2376, 2413-2414)
-  if (ctx->quality_on) { // the output pictures against the originals, both still in HBM
-    if (!ctx->d_q_out) HIPCHK(hipMalloc(&ctx->d_q_out, sizeof(hevcdl_quality) * (size_t)ctx->cfg.max_frames));
-    if (windowed) st = quality_sized_dev(ctx, ctx->d_win_org, ctx->d_win_pic, n_frames, ctx->d_q_out, nullptr, ww, wh);
-    else st = hevcdl_picture_quality_dev(ctx, ctx->d_yuv, *d_final, n_frames, ctx->d_q_out, nullptr);
-    if (st) return st;
+  *d_final = ctx->stage.d_recon;
+  if (deblock) { TRY(hevcdl_deblock_frames_dev(ctx, ctx->stage.d_recon, n_frames, ctx->stage.d_records, ctx->stage.d_recon, nullptr)); }      // in place
+  if (want_sao) { TRY(hevcdl_sao_frames_dev(ctx, ctx->stage.d_yuv, ctx->stage.d_recon, n_frames, ctx->sao.d_sao_params, ctx->stage.d_picture, nullptr)); *d_final = ctx->stage.d_picture; }
+  ctx->q.h_quality.clear();
+  ctx->rp.h_report.clear();
+  if (windowed && (ctx->q.quality_on || ctx->rp.report_on)) { TRY(crop_window_dev(ctx, *d_final, n_frames, ctx->src.d_win_pic, nullptr)); }      // the output pictures' window (TEncGOP.cpp:2302-2303, 2375-2376, 2413-2414)
+  if (ctx->q.quality_on) { // the output pictures against the originals, both still in HBM
+    TRY(lazy_alloc(ctx, ctx->q.d_q_out, sizeof(hevcdl_quality) * (size_t)ctx->cfg.max_frames, "picture quality results"));
+    TRY(windowed ? quality_sized_dev(ctx, ctx->src.d_win_org, ctx->src.d_win_pic, n_frames, ctx->q.d_q_out, nullptr, ww, wh)
+                 : hevcdl_picture_quality_dev(ctx, ctx->stage.d_yuv, *d_final, n_frames, ctx->q.d_q_out, nullptr));
   }
-  if (ctx->report_on) { // hevcdl_enable_picture_report: SSE and digests of the output pictures, where they are (the digests over the whole coded picture, as the hash SEI)
-    if (windowed) st = report_dev(ctx, ctx->d_yuv, *d_final, n_frames, ctx->report_method, ctx->d_rp_out, nullptr, ctx->d_win_org, ctx->d_win_pic, ww, wh);
-    else st = hevcdl_picture_report_dev(ctx, ctx->d_yuv, *d_final, n_frames, ctx->report_method, ctx->d_rp_out, nullptr);
-    if (st) return st;
+  if (ctx->rp.report_on) { // hevcdl_enable_picture_report: SSE and digests of the output pictures, where they are (the digests over the whole coded picture, as the hash SEI)
+    TRY(windowed ? report_dev(ctx, ctx->stage.d_yuv, *d_final, n_frames, ctx->rp.report_method, ctx->rp.d_rp_out, nullptr, ctx->src.d_win_org, ctx->src.d_win_pic, ww, wh)
+                 : hevcdl_picture_report_dev(ctx, ctx->stage.d_yuv, *d_final, n_frames, ctx->rp.report_method, ctx->rp.d_rp_out, nullptr));
   }
-  hipError_t e = hipDeviceSynchronize();
-  if (e != hipSuccess) return fail(ctx, HEVCDL_ERR_HIP, "picture pipeline", e);
-  if (ctx->report_on) {
-    ctx->h_report.resize(n_frames);
-    HIPCHK(hipMemcpy(ctx->h_report.data(), ctx->d_rp_out, sizeof(hevcdl_picture_report_t) * (size_t)n_frames, hipMemcpyDeviceToHost));
+  TRY(sync_or_fail(ctx, "picture pipeline"));
+  if (ctx->rp.report_on) {
+    ctx->rp.h_report.resize(n_frames);
+    HIPCHK(hipMemcpy(ctx->rp.h_report.data(), ctx->rp.d_rp_out, sizeof(hevcdl_picture_report_t) * (size_t)n_frames, hipMemcpyDeviceToHost));
   }
-  if (ctx->quality_on) {
-    ctx->h_quality.resize(n_frames);
-    HIPCHK(hipMemcpy(ctx->h_quality.data(), ctx->d_q_out, sizeof(hevcdl_quality) * (size_t)n_frames, hipMemcpyDeviceToHost));
+  if (ctx->q.quality_on) {
+    ctx->q.h_quality.resize(n_frames);
+    HIPCHK(hipMemcpy(ctx->q.h_quality.data(), ctx->q.d_q_out, sizeof(hevcdl_quality) * (size_t)n_frames, hipMemcpyDeviceToHost));
   }
-  if (ctx->entropy_on) { st = entropy_pipeline(ctx, n_frames, want_sao); if (st) return st; }      // hevcdl_enable_device_entropy: the slice data too, from the records still in HBM
-  ctx->d_last_final = *d_final; ctx->last_frames = n_frames;
+  if (ctx->ec.entropy_on) { TRY(entropy_pipeline(ctx, n_frames, want_sao)); }      // hevcdl_enable_device_entropy: the slice data too, from the records still in HBM
+  ctx->src.d_last_final = *d_final; ctx->src.last_frames = n_frames;
   return HEVCDL_OK;
 }
 
 extern "C" hevcdl_status hevcdl_encode_pictures(hevcdl_ctx *ctx, const void *yuv, int n_frames, const uint8_t *labels_opt, int deblock, hevcdl_ctu_record *records,
                                                 void *picture_out, hevcdl_sao_blk *sao_opt, hevcdl_frame_stats *stats_opt)
 {
-  hevcdl_status st = check_frames(ctx, n_frames); if (st) return st;
-  if (n_frames == 0) return HEVCDL_OK;
+  FRAMES_OR_RETURN(ctx, n_frames);
   if (!yuv || !records || !picture_out) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null pointer");
   uint8_t *d_final = nullptr;
-  st = encode_pictures_device(ctx, yuv, n_frames, labels_opt, deblock, sao_opt != nullptr, &d_final); if (st) return st;
-  HIPCHK(hipMemcpy(records, ctx->d_records, (size_t)ctx->ctus * sizeof(hevcdl_ctu_record) * n_frames, hipMemcpyDeviceToHost));
+  TRY(encode_pictures_device(ctx, yuv, n_frames, labels_opt, deblock, sao_opt != nullptr, &d_final));
+  HIPCHK(hipMemcpy(records, ctx->stage.d_records, ctx->records_bytes(n_frames), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(picture_out, d_final, ctx->frame_bytes * n_frames, hipMemcpyDeviceToHost));
-  if (sao_opt) HIPCHK(hipMemcpy(sao_opt, ctx->d_sao_params, (size_t)ctx->ctus * sizeof(hevcdl_sao_blk) * n_frames, hipMemcpyDeviceToHost));
-  if (stats_opt) HIPCHK(hipMemcpy(stats_opt, ctx->d_stats, sizeof(hevcdl_frame_stats) * n_frames, hipMemcpyDeviceToHost));
+  if (sao_opt) HIPCHK(hipMemcpy(sao_opt, ctx->sao.d_sao_params, ctx->sao_bytes(n_frames), hipMemcpyDeviceToHost));
+  if (stats_opt) HIPCHK(hipMemcpy(stats_opt, ctx->stage.d_stats, sizeof(hevcdl_frame_stats) * n_frames, hipMemcpyDeviceToHost));
+  return HEVCDL_OK;
+}
+
+// the two page-locked chunk buffers of hevcdl_encode_pictures_chunked / _stream, grown to `need` bytes each
+static hevcdl_status ensure_chunk_buffers(hevcdl_ctx *ctx, size_t need)
+{
+  Staging &g = ctx->stage;
+  if (g.h_chunk_bytes >= need) return HEVCDL_OK;
+  for (HostBuf &h : g.h_chunk) h.reset();
+  g.h_chunk_bytes = 0;
+  for (HostBuf &h : g.h_chunk) HIPCHK(hipHostMalloc((void **)&h.p, need, hipHostMallocDefault));
+  g.h_chunk_bytes = need;
   return HEVCDL_OK;
 }
 
 extern "C" hevcdl_status hevcdl_encode_pictures_chunked(hevcdl_ctx *ctx, const void *yuv, int n_frames, const uint8_t *labels_opt, int deblock, int want_sao,
                                                         int chunk_frames, hevcdl_chunk_fn fn, void *user)
 {
-  hevcdl_status st = check_frames(ctx, n_frames); if (st) return st;
-  if (n_frames == 0) return HEVCDL_OK;
+  FRAMES_OR_RETURN(ctx, n_frames);
   if (!yuv || !fn) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null pointer");
   const int chunk = std::min(n_frames, chunk_frames > 0 ? chunk_frames : 64);
-  const size_t rec_b = (size_t)ctx->ctus * sizeof(hevcdl_ctu_record), sao_b = (size_t)ctx->ctus * sizeof(hevcdl_sao_blk), pic_b = ctx->frame_bytes, stat_b = sizeof(hevcdl_frame_stats);
+  const size_t rec_b = ctx->records_bytes(1), sao_b = ctx->sao_bytes(1), pic_b = ctx->frame_bytes, stat_b = sizeof(hevcdl_frame_stats);
   auto up64 = [](size_t v) { return (v + 63) & ~(size_t)63; };      // every section of a chunk buffer starts on a 64-byte boundary (the callback gets pointers to structs with 64-bit members)
   const size_t o_pic = up64(rec_b * chunk), o_sao = up64(o_pic + pic_b * chunk), o_stat = up64(o_sao + sao_b * chunk), need = o_stat + stat_b * chunk;      // layout of a chunk buffer
-  if (ctx->h_chunk_bytes < need) {
-    for (int i = 0; i < 2; i++) { if (ctx->h_chunk[i]) hipHostFree(ctx->h_chunk[i]); ctx->h_chunk[i] = nullptr; }
-    ctx->h_chunk_bytes = 0;
-    for (int i = 0; i < 2; i++) HIPCHK(hipHostMalloc((void **)&ctx->h_chunk[i], need, hipHostMallocDefault));
-    ctx->h_chunk_bytes = need;
-  }
-  if (!ctx->copy_stream) { HIPCHK(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking)); for (int i = 0; i < 2; i++) HIPCHK(hipEventCreateWithFlags(&ctx->copy_ev[i], hipEventDisableTiming)); }
+  TRY(ensure_chunk_buffers(ctx, need));
+  if (!ctx->stage.copy_stream) { HIPCHK(hipStreamCreateWithFlags(&ctx->stage.copy_stream.p, hipStreamNonBlocking)); for (Event &e : ctx->stage.copy_ev) HIPCHK(hipEventCreateWithFlags(&e.p, hipEventDisableTiming)); }
   uint8_t *d_final = nullptr;
-  st = encode_pictures_device(ctx, yuv, n_frames, labels_opt, deblock, want_sao, &d_final); if (st) return st;
+  TRY(encode_pictures_device(ctx, yuv, n_frames, labels_opt, deblock, want_sao, &d_final));
   auto fetch = [&](int ci) -> hipError_t { // chunk ci -> buffer ci & 1, asynchronously
     const int first = ci * chunk, cnt = std::min(chunk, n_frames - first);
-    unsigned char *h = ctx->h_chunk[ci & 1];
-    hipError_t e = hipMemcpyAsync(h, ctx->d_records + rec_b * first, rec_b * cnt, hipMemcpyDeviceToHost, ctx->copy_stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(h + o_pic, d_final + pic_b * first, pic_b * cnt, hipMemcpyDeviceToHost, ctx->copy_stream);
-    if (e == hipSuccess && want_sao) e = hipMemcpyAsync(h + o_sao, ctx->d_sao_params + sao_b * first, sao_b * cnt, hipMemcpyDeviceToHost, ctx->copy_stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(h + o_stat, ctx->d_stats + stat_b * first, stat_b * cnt, hipMemcpyDeviceToHost, ctx->copy_stream);
-    if (e == hipSuccess) e = hipEventRecord(ctx->copy_ev[ci & 1], ctx->copy_stream);
+    unsigned char *h = ctx->stage.h_chunk[ci & 1];
+    hipError_t e = hipMemcpyAsync(h, ctx->stage.d_records + rec_b * first, rec_b * cnt, hipMemcpyDeviceToHost, ctx->stage.copy_stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h + o_pic, d_final + pic_b * first, pic_b * cnt, hipMemcpyDeviceToHost, ctx->stage.copy_stream);
+    if (e == hipSuccess && want_sao) e = hipMemcpyAsync(h + o_sao, ctx->sao.d_sao_params + sao_b * first, sao_b * cnt, hipMemcpyDeviceToHost, ctx->stage.copy_stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h + o_stat, ctx->stage.d_stats + stat_b * first, stat_b * cnt, hipMemcpyDeviceToHost, ctx->stage.copy_stream);
+    if (e == hipSuccess) e = hipEventRecord(ctx->stage.copy_ev[ci & 1], ctx->stage.copy_stream);
     return e;
   };
   const int n_chunks = (n_frames + chunk - 1) / chunk;
   HIPCHK(fetch(0));
   for (int ci = 0; ci < n_chunks; ci++) {
-    { hipError_t e_ = hipEventSynchronize(ctx->copy_ev[ci & 1]);
+    { hipError_t e_ = hipEventSynchronize(ctx->stage.copy_ev[ci & 1]);
       if (e_ == hipSuccess && ci + 1 < n_chunks) e_ = fetch(ci + 1);                   // into the other buffer, behind the caller's work on this one
-      if (e_ != hipSuccess) { (void)hipStreamSynchronize(ctx->copy_stream); return fail(ctx, HEVCDL_ERR_HIP, "chunk copy", e_); } }     // no copy into the library's buffers is left in flight
+      if (e_ != hipSuccess) { (void)hipStreamSynchronize(ctx->stage.copy_stream); return fail(ctx, HEVCDL_ERR_HIP, "chunk copy", e_); } }     // no copy into the library's buffers is left in flight
     const int first = ci * chunk, cnt = std::min(chunk, n_frames - first);
-    unsigned char *h = ctx->h_chunk[ci & 1];
+    unsigned char *h = ctx->stage.h_chunk[ci & 1];
     if (fn(user, first, cnt, (const hevcdl_ctu_record *)h, h + o_pic, want_sao ? (const hevcdl_sao_blk *)(h + o_sao) : nullptr, (const hevcdl_frame_stats *)(h + o_stat)) != 0) {
-      hipStreamSynchronize(ctx->copy_stream);
+      hipStreamSynchronize(ctx->stage.copy_stream);
       return fail(ctx, HEVCDL_ERR_INVALID_ARG, "the chunk callback asked to stop");
     }
   }
@@ -1499,9 +1444,9 @@ struct EntropyPlan {
 static hevcdl_status entropy_plan(const hevcdl_stream_config *cfg, int capacity_per_ctu, EntropyPlan &pl)
 {
   int n = 0; size_t bytes = 0;
-  hevcdl_status st = hevcdl_slice_data_layout(cfg, capacity_per_ctu, &n, &bytes, nullptr, nullptr); if (st) return st;
+  TRY(hevcdl_slice_data_layout(cfg, capacity_per_ctu, &n, &bytes, nullptr, nullptr));
   pl.off.resize((size_t)n); pl.cap.resize((size_t)n);
-  st = hevcdl_slice_data_layout(cfg, capacity_per_ctu, &n, &bytes, pl.off.data(), pl.cap.data()); if (st) return st;
+  TRY(hevcdl_slice_data_layout(cfg, capacity_per_ctu, &n, &bytes, pl.off.data(), pl.cap.data()));
   pl.units = n; pl.frame_stride = bytes;
   hevcdl_entropy_params &k = pl.k; memset(&k, 0, sizeof k);
   k.width = cfg->width; k.height = cfg->height; k.ctus_x = (cfg->width + 63) >> 6; k.ctus_y = (cfg->height + 63) >> 6; k.qp = cfg->qp; k.tools = (int)cfg->tools;
@@ -1517,40 +1462,37 @@ extern "C" hevcdl_status hevcdl_code_slice_data(int device, const hevcdl_stream_
 {
   if (!cfg || !records || !out || !sizes || !overflow || n_frames < 0) return HEVCDL_ERR_INVALID_ARG;
   EntropyPlan pl;
-  hevcdl_status st = entropy_plan(cfg, capacity_per_ctu, pl); if (st) return st;
+  TRY(entropy_plan(cfg, capacity_per_ctu, pl));
   if ((cfg->sao_enabled != 0) != (sao_opt != nullptr)) return HEVCDL_ERR_INVALID_ARG;
   if (out_capacity / (pl.frame_stride ? pl.frame_stride : 1) < (size_t)n_frames) return HEVCDL_ERR_INVALID_ARG;
   if (n_frames == 0) return HEVCDL_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) { (void)hipGetLastError(); return HEVCDL_ERR_NO_DEVICE; }
-  if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return HEVCDL_ERR_HIP; }
+  TRY(select_device(device));
   const size_t ctus = (size_t)pl.k.ctus_x * pl.k.ctus_y, n_sub = (size_t)n_frames * pl.units;
-  const size_t sz[8] = { ctus * sizeof(hevcdl_ctu_record) * n_frames, sao_opt ? ctus * sizeof(hevcdl_sao_blk) * n_frames : 4, sizeof(hevcdl_ec::EcTables), pl.frame_stride * n_frames,
-                         4 * (size_t)pl.units, 4 * (size_t)pl.units, 8 * n_sub, (size_t)n_frames * pl.k.ctus_y * hevcdl_ec::EC_SYNC_BYTES };
-  unsigned char *d[8] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < 8 && e == hipSuccess; i++) e = hipMalloc(&d[i], sz[i]);
-  if (e == hipSuccess) e = hipMemcpy(d[0], records, sz[0], hipMemcpyHostToDevice);
-  if (e == hipSuccess && sao_opt) e = hipMemcpy(d[1], sao_opt, sz[1], hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d[2], &hevcdl_ec::ec_tables(), sz[2], hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d[3], out, sz[3], hipMemcpyHostToDevice);      // what the kernels do not write comes back as the caller left it
-  if (e == hipSuccess) e = hipMemcpy(d[4], pl.off.data(), sz[4], hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d[5], pl.cap.data(), sz[5], hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(d[6], 0, sz[6]);
-  if (e == hipSuccess) e = hipMemset(d[7], 0, sz[7]);
+  const size_t rec_b = ctus * sizeof(hevcdl_ctu_record) * n_frames, sao_b = sao_opt ? ctus * sizeof(hevcdl_sao_blk) * n_frames : 4, out_b = pl.frame_stride * n_frames, unit_b = 4 * (size_t)pl.units;
+  const size_t sync_b = (size_t)n_frames * pl.k.ctus_y * hevcdl_ec::EC_SYNC_BYTES;
+  DevBuf<unsigned char> d_rec, d_sao, d_tables, d_out, d_sync; DevBuf<uint32_t> d_off, d_cap, d_sizes;      // d_sizes: the lengths, then the overflow flags
+  TRY(alloc_all(nullptr, { want(d_rec, rec_b), want(d_sao, sao_b), want(d_tables, sizeof(hevcdl_ec::EcTables)), want(d_out, out_b), want(d_off, unit_b), want(d_cap, unit_b),
+                           want(d_sizes, 8 * n_sub), want(d_sync, sync_b) }, ""));
+  hipError_t e = hipMemcpy(d_rec, records, rec_b, hipMemcpyHostToDevice);
+  if (e == hipSuccess && sao_opt) e = hipMemcpy(d_sao, sao_opt, sao_b, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_tables, &hevcdl_ec::ec_tables(), sizeof(hevcdl_ec::EcTables), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_out, out, out_b, hipMemcpyHostToDevice);      // what the kernels do not write comes back as the caller left it
+  if (e == hipSuccess) e = hipMemcpy(d_off, pl.off.data(), unit_b, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_cap, pl.cap.data(), unit_b, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(d_sizes, 0, 8 * n_sub);
+  if (e == hipSuccess) e = hipMemset(d_sync, 0, sync_b);
   if (e == hipSuccess) {
     hevcdl_entropy_params k = pl.k;
-    k.records = d[0]; k.sao = sao_opt ? d[1] : nullptr; k.tables = d[2]; k.out = d[3]; k.unit_off = (const uint32_t *)d[4]; k.unit_cap = (const uint32_t *)d[5];
-    k.sizes = (uint32_t *)d[6]; k.overflow = (uint32_t *)d[6] + n_sub; k.sync = d[7]; k.n_frames = n_frames;
+    k.records = d_rec; k.sao = sao_opt ? d_sao.p : nullptr; k.tables = d_tables; k.out = d_out; k.unit_off = d_off; k.unit_cap = d_cap;
+    k.sizes = d_sizes; k.overflow = d_sizes + n_sub; k.sync = d_sync; k.n_frames = n_frames;
     hevcdl_launch_entropy(&k, nullptr, nullptr);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(out, d[3], sz[3], hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(sizes, d[6], 4 * n_sub, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(overflow, d[6] + 4 * n_sub, 4 * n_sub, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out, d_out, out_b, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(sizes, d_sizes, 4 * n_sub, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(overflow, d_sizes + n_sub, 4 * n_sub, hipMemcpyDeviceToHost);
   }
-  for (int i = 0; i < 8; i++) hipFree(d[i]);
-  if (e != hipSuccess) { (void)hipGetLastError(); return e == hipErrorOutOfMemory ? HEVCDL_ERR_OOM : HEVCDL_ERR_HIP; }
+  if (e != hipSuccess) return hip_fail(nullptr, "", e);
   return HEVCDL_OK;
 }
 
@@ -1566,97 +1508,87 @@ static void entropy_stream_config(const hevcdl_ctx *ctx, int want_sao, hevcdl_st
 
 static void entropy_release(hevcdl_ctx *ctx)
 {
-  hipFree(ctx->d_ec_tables); hipFree(ctx->d_ec_ws); hipFree(ctx->d_ec_packed); hipFree(ctx->d_ec_sync); hipFree(ctx->d_ec_off); hipFree(ctx->d_ec_cap); hipFree(ctx->d_ec_sizes); hipFree(ctx->d_ec_ovf); hipFree(ctx->d_ec_dst);
-  ctx->d_ec_tables = ctx->d_ec_ws = ctx->d_ec_packed = ctx->d_ec_sync = nullptr; ctx->d_ec_off = ctx->d_ec_cap = ctx->d_ec_sizes = ctx->d_ec_ovf = nullptr; ctx->d_ec_dst = nullptr;
-  ctx->entropy_on = false; ctx->ec_units = ctx->ec_pass_frames = 0; ctx->ec_frame_stride = 0;
-  ctx->h_slice.clear(); ctx->h_slice_sizes.clear(); ctx->h_slice_at.clear(); ctx->ec_fallbacks = 0;
+  ctx->ec = Entropy();
 }
 
 extern "C" hevcdl_status hevcdl_enable_device_entropy(hevcdl_ctx *ctx, int on)
 {
   if (!ctx) return HEVCDL_ERR_INVALID_ARG;
-  hevcdl_status st = check_frames(ctx, 0); if (st) return st;
+  TRY(check_frames(ctx, 0));
   if (!on) {
-    if (!ctx->entropy_on) return HEVCDL_OK;
-    hipError_t e = hipDeviceSynchronize();
-    if (e != hipSuccess) return fail(ctx, HEVCDL_ERR_HIP, "hevcdl_enable_device_entropy", e);
+    if (!ctx->ec.entropy_on) return HEVCDL_OK;
+    TRY(sync_or_fail(ctx, "hevcdl_enable_device_entropy"));
     entropy_release(ctx);
     return HEVCDL_OK;
   }
-  if (ctx->entropy_on) return HEVCDL_OK;
+  if (ctx->ec.entropy_on) return HEVCDL_OK;
   hevcdl_stream_config sc; entropy_stream_config(ctx, 0, &sc);
   EntropyPlan pl;
-  st = entropy_plan(&sc, ctx->ec_capacity_per_ctu, pl); if (st) return fail(ctx, st, "device entropy: stream configuration");
+  const hevcdl_status st = entropy_plan(&sc, ctx->ec_capacity_per_ctu, pl); if (st) return fail(ctx, st, "device entropy: stream configuration");
   // the workspace holds the regions of at most ENTROPY_WS_BYTES worth of pictures (84 MB a picture at 2160p: 2040 CTUs x 40 KB); larger batches go through it in passes
   const size_t ENTROPY_WS_BYTES = (size_t)512 << 20;
   const int pass = (int)std::max<size_t>(1, std::min<size_t>((size_t)ctx->cfg.max_frames, ENTROPY_WS_BYTES / pl.frame_stride));
   const size_t n_sub = (size_t)pass * pl.units;
-  hipError_t e = hipMalloc(&ctx->d_ec_tables, sizeof(hevcdl_ec::EcTables));
-  if (e == hipSuccess) e = hipMalloc(&ctx->d_ec_ws, pl.frame_stride * pass);
-  if (e == hipSuccess) e = hipMalloc(&ctx->d_ec_packed, pl.frame_stride * pass);
-  if (e == hipSuccess) e = hipMalloc(&ctx->d_ec_sync, (size_t)pass * ctx->ctus_y * hevcdl_ec::EC_SYNC_BYTES);
-  if (e == hipSuccess) e = hipMalloc(&ctx->d_ec_off, 4 * (size_t)pl.units);
-  if (e == hipSuccess) e = hipMalloc(&ctx->d_ec_cap, 4 * (size_t)pl.units);
-  if (e == hipSuccess) e = hipMalloc(&ctx->d_ec_sizes, 4 * n_sub);
-  if (e == hipSuccess) e = hipMalloc(&ctx->d_ec_ovf, 4 * n_sub);
-  if (e == hipSuccess) e = hipMalloc(&ctx->d_ec_dst, 8 * n_sub);
-  if (e == hipSuccess) e = hipMemcpy(ctx->d_ec_tables, &hevcdl_ec::ec_tables(), sizeof(hevcdl_ec::EcTables), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(ctx->d_ec_off, pl.off.data(), 4 * (size_t)pl.units, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(ctx->d_ec_cap, pl.cap.data(), 4 * (size_t)pl.units, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(ctx->d_ec_sync, 0, (size_t)pass * ctx->ctus_y * hevcdl_ec::EC_SYNC_BYTES);
-  if (e != hipSuccess) { entropy_release(ctx); (void)hipGetLastError(); return fail(ctx, e == hipErrorOutOfMemory ? HEVCDL_ERR_OOM : HEVCDL_ERR_HIP, "device entropy workspace", e); }
-  ctx->ec_off = pl.off; ctx->ec_cap = pl.cap; ctx->ec_units = pl.units; ctx->ec_pass_frames = pass; ctx->ec_frame_stride = pl.frame_stride; ctx->entropy_on = true;
+  Entropy &g = ctx->ec;
+  const size_t unit_b = 4 * (size_t)pl.units, sync_b = (size_t)pass * ctx->ctus_y * hevcdl_ec::EC_SYNC_BYTES;
+  TRY(alloc_all(ctx, { want(g.d_ec_tables, sizeof(hevcdl_ec::EcTables)), want(g.d_ec_ws, pl.frame_stride * pass), want(g.d_ec_packed, pl.frame_stride * pass), want(g.d_ec_sync, sync_b),
+                       want(g.d_ec_off, unit_b), want(g.d_ec_cap, unit_b), want(g.d_ec_sizes, 4 * n_sub), want(g.d_ec_ovf, 4 * n_sub), want(g.d_ec_dst, 8 * n_sub) }, "device entropy workspace"));
+  hipError_t e = hipMemcpy(g.d_ec_tables, &hevcdl_ec::ec_tables(), sizeof(hevcdl_ec::EcTables), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(g.d_ec_off, pl.off.data(), unit_b, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(g.d_ec_cap, pl.cap.data(), unit_b, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(g.d_ec_sync, 0, sync_b);
+  if (e != hipSuccess) { entropy_release(ctx); return hip_fail(ctx, "device entropy workspace", e); }
+  ctx->ec.ec_off = pl.off; ctx->ec.ec_cap = pl.cap; ctx->ec.ec_units = pl.units; ctx->ec.ec_pass_frames = pass; ctx->ec.ec_frame_stride = pl.frame_stride; ctx->ec.entropy_on = true;
   return HEVCDL_OK;
 }
 
-// The slice data of the n_frames pictures whose records (and SAO parameters) the picture pipeline has just left in HBM -> ctx->h_slice*.  Passes of ec_pass_frames
+// The slice data of the n_frames pictures whose records (and SAO parameters) the picture pipeline has just left in HBM -> ctx->ec.h_slice*.  Passes of ec_pass_frames
 // pictures: the two kernels, the lengths to the host, an exclusive scan, the pack kernel, one copy of the used bytes.
 static hevcdl_status entropy_pipeline(hevcdl_ctx *ctx, int n_frames, int want_sao)
 {
   hevcdl_stream_config sc; entropy_stream_config(ctx, want_sao, &sc);
   EntropyPlan pl;
   hevcdl_status st = entropy_plan(&sc, ctx->ec_capacity_per_ctu, pl); if (st) return fail(ctx, st, "device entropy: stream configuration");
-  const int units = ctx->ec_units;
+  const int units = ctx->ec.ec_units;
   ctx->ec_ms[0] = ctx->ec_ms[1] = ctx->ec_ms[2] = 0;
-  hipEvent_t ev[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };      // with the profile switch: start, between the two launches, end of the coding, around the pack launch
-  if (ctx->profile) for (int i = 0; i < 5; i++) HIPCHK(hipEventCreate(&ev[i]));
-  struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 5; i++) if (e[i]) hipEventDestroy(e[i]); } } ev_guard{ ev };
-  const size_t rec_b = (size_t)ctx->ctus * sizeof(hevcdl_ctu_record), sao_b = (size_t)ctx->ctus * sizeof(hevcdl_sao_blk);
-  ctx->h_slice.clear(); ctx->h_slice_sizes.assign((size_t)n_frames * units, 0); ctx->h_slice_at.assign((size_t)n_frames + 1, 0); ctx->ec_fallbacks = 0;
+  Event ev[5];      // with the profile switch: start, between the two launches, end of the coding, around the pack launch
+  if (ctx->profile) for (Event &e : ev) HIPCHK(hipEventCreate(&e.p));
+  const size_t rec_b = ctx->records_bytes(1), sao_b = ctx->sao_bytes(1);
+  ctx->ec.h_slice.clear(); ctx->ec.h_slice_sizes.assign((size_t)n_frames * units, 0); ctx->ec.h_slice_at.assign((size_t)n_frames + 1, 0); ctx->ec.ec_fallbacks = 0;
   std::vector<uint32_t> ovf; std::vector<unsigned long long> dst; std::vector<int> fallback;
-  for (int first = 0; first < n_frames; first += ctx->ec_pass_frames) {
-    const int cnt = std::min(ctx->ec_pass_frames, n_frames - first); const size_t n_sub = (size_t)cnt * units;
+  for (int first = 0; first < n_frames; first += ctx->ec.ec_pass_frames) {
+    const int cnt = std::min(ctx->ec.ec_pass_frames, n_frames - first); const size_t n_sub = (size_t)cnt * units;
     hevcdl_entropy_params k = pl.k;
-    k.records = ctx->d_records + rec_b * first; k.sao = want_sao ? ctx->d_sao_params + sao_b * first : nullptr; k.tables = ctx->d_ec_tables; k.out = ctx->d_ec_ws;
-    k.unit_off = ctx->d_ec_off; k.unit_cap = ctx->d_ec_cap; k.sizes = ctx->d_ec_sizes; k.overflow = ctx->d_ec_ovf; k.sync = ctx->d_ec_sync; k.n_frames = cnt;
+    k.records = ctx->stage.d_records + rec_b * first; k.sao = want_sao ? ctx->sao.d_sao_params + sao_b * first : (unsigned char *)nullptr; k.tables = ctx->ec.d_ec_tables; k.out = ctx->ec.d_ec_ws;
+    k.unit_off = ctx->ec.d_ec_off; k.unit_cap = ctx->ec.d_ec_cap; k.sizes = ctx->ec.d_ec_sizes; k.overflow = ctx->ec.d_ec_ovf; k.sync = ctx->ec.d_ec_sync; k.n_frames = cnt;
     if (ev[0]) HIPCHK(hipEventRecord(ev[0], nullptr));
     hevcdl_launch_entropy(&k, nullptr, ev[1]);
     if (ev[2]) HIPCHK(hipEventRecord(ev[2], nullptr));
     HIPCHK(hipGetLastError());
-    uint32_t *sz = ctx->h_slice_sizes.data() + (size_t)first * units;
+    uint32_t *sz = ctx->ec.h_slice_sizes.data() + (size_t)first * units;
     ovf.resize(n_sub); dst.resize(n_sub);
-    HIPCHK(hipMemcpy(sz, ctx->d_ec_sizes, 4 * n_sub, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(ovf.data(), ctx->d_ec_ovf, 4 * n_sub, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(sz, ctx->ec.d_ec_sizes, 4 * n_sub, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ovf.data(), ctx->ec.d_ec_ovf, 4 * n_sub, hipMemcpyDeviceToHost));
     unsigned long long at = 0; bool pass_fallback = false;
     for (int f = 0; f < cnt; f++) {
       bool bad = false;
-      for (int u = 0; u < units; u++) bad = bad || ovf[(size_t)f * units + u] != 0 || sz[(size_t)f * units + u] > ctx->ec_cap[(size_t)u];
+      for (int u = 0; u < units; u++) bad = bad || ovf[(size_t)f * units + u] != 0 || sz[(size_t)f * units + u] > ctx->ec.ec_cap[(size_t)u];
       if (bad) { pass_fallback = true; fallback.push_back(first + f); for (int u = 0; u < units; u++) sz[(size_t)f * units + u] = 0; }
-      ctx->h_slice_at[(size_t)first + f] = ctx->h_slice.size() + (size_t)at;
+      ctx->ec.h_slice_at[(size_t)first + f] = ctx->ec.h_slice.size() + (size_t)at;
       for (int u = 0; u < units; u++) { dst[(size_t)f * units + u] = at; at += sz[(size_t)f * units + u]; }
     }
-    HIPCHK(hipMemcpy(ctx->d_ec_dst, dst.data(), 8 * n_sub, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ctx->ec.d_ec_dst, dst.data(), 8 * n_sub, hipMemcpyHostToDevice));
     hevcdl_entropy_pack_params pk; memset(&pk, 0, sizeof pk);
-    pk.src = ctx->d_ec_ws; pk.dst = ctx->d_ec_packed; pk.unit_off = ctx->d_ec_off; pk.unit_cap = ctx->d_ec_cap; pk.sizes = ctx->d_ec_sizes; pk.dst_off = ctx->d_ec_dst;
-    pk.frame_stride = ctx->ec_frame_stride; pk.dst_cap = ctx->ec_frame_stride * (size_t)cnt; pk.n_frames = cnt; pk.units = units;
-    if (pass_fallback) HIPCHK(hipMemcpy(ctx->d_ec_sizes, sz, 4 * n_sub, hipMemcpyHostToDevice));      // the lengths the offsets were made from (0 for a picture the host codes)
+    pk.src = ctx->ec.d_ec_ws; pk.dst = ctx->ec.d_ec_packed; pk.unit_off = ctx->ec.d_ec_off; pk.unit_cap = ctx->ec.d_ec_cap; pk.sizes = ctx->ec.d_ec_sizes; pk.dst_off = ctx->ec.d_ec_dst;
+    pk.frame_stride = ctx->ec.ec_frame_stride; pk.dst_cap = ctx->ec.ec_frame_stride * (size_t)cnt; pk.n_frames = cnt; pk.units = units;
+    if (pass_fallback) HIPCHK(hipMemcpy(ctx->ec.d_ec_sizes, sz, 4 * n_sub, hipMemcpyHostToDevice));      // the lengths the offsets were made from (0 for a picture the host codes)
     if (ev[3]) HIPCHK(hipEventRecord(ev[3], nullptr));
     hevcdl_launch_entropy_pack(&pk, nullptr);
     if (ev[4]) HIPCHK(hipEventRecord(ev[4], nullptr));
     HIPCHK(hipGetLastError());
-    const size_t old = ctx->h_slice.size();
-    ctx->h_slice.resize(old + (size_t)at);
-    if (at) HIPCHK(hipMemcpy(ctx->h_slice.data() + old, ctx->d_ec_packed, (size_t)at, hipMemcpyDeviceToHost));
+    const size_t old = ctx->ec.h_slice.size();
+    ctx->ec.h_slice.resize(old + (size_t)at);
+    if (at) HIPCHK(hipMemcpy(ctx->ec.h_slice.data() + old, ctx->ec.d_ec_packed, (size_t)at, hipMemcpyDeviceToHost));
     if (ev[0]) {
       HIPCHK(hipEventSynchronize(ev[4]));
       float ms = 0;
@@ -1665,7 +1597,7 @@ static hevcdl_status entropy_pipeline(hevcdl_ctx *ctx, int n_frames, int want_sa
       HIPCHK(hipEventElapsedTime(&ms, ev[3], ev[4])); ctx->ec_ms[2] += ms;
     }
   }
-  ctx->h_slice_at[(size_t)n_frames] = ctx->h_slice.size();
+  ctx->ec.h_slice_at[(size_t)n_frames] = ctx->ec.h_slice.size();
   if (!fallback.empty()) { // a sub-stream did not fit its region: the host writer codes those pictures (their records only), and the batch is put together again in picture order
     std::vector<uint8_t> all; std::vector<size_t> at((size_t)n_frames + 1, 0);
     std::vector<hevcdl_ctu_record> rec((size_t)ctx->ctus); std::vector<hevcdl_sao_blk> sao(want_sao ? (size_t)ctx->ctus : 0);
@@ -1674,16 +1606,16 @@ static hevcdl_status entropy_pipeline(hevcdl_ctx *ctx, int n_frames, int want_sa
       at[(size_t)f] = all.size();
       if (fb < fallback.size() && fallback[fb] == f) {
         fb++;
-        HIPCHK(hipMemcpy(rec.data(), ctx->d_records + rec_b * f, rec_b, hipMemcpyDeviceToHost));
-        if (want_sao) HIPCHK(hipMemcpy(sao.data(), ctx->d_sao_params + sao_b * f, sao_b, hipMemcpyDeviceToHost));
-        size_t total = 0; uint32_t *sz = ctx->h_slice_sizes.data() + (size_t)f * units;
+        HIPCHK(hipMemcpy(rec.data(), ctx->stage.d_records + rec_b * f, rec_b, hipMemcpyDeviceToHost));
+        if (want_sao) HIPCHK(hipMemcpy(sao.data(), ctx->sao.d_sao_params + sao_b * f, sao_b, hipMemcpyDeviceToHost));
+        size_t total = 0; uint32_t *sz = ctx->ec.h_slice_sizes.data() + (size_t)f * units;
         hevcdl_host_writer_slice_data(&sc, rec.data(), want_sao ? sao.data() : nullptr, nullptr, 0, sz, &total);
         all.resize(at[(size_t)f] + total);
         if (hevcdl_host_writer_slice_data(&sc, rec.data(), want_sao ? sao.data() : nullptr, all.data() + at[(size_t)f], total, sz, &total) != 0) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "device entropy: host fallback");
-      } else all.insert(all.end(), ctx->h_slice.begin() + (ptrdiff_t)ctx->h_slice_at[(size_t)f], ctx->h_slice.begin() + (ptrdiff_t)ctx->h_slice_at[(size_t)f + 1]);
+      } else all.insert(all.end(), ctx->ec.h_slice.begin() + (ptrdiff_t)ctx->ec.h_slice_at[(size_t)f], ctx->ec.h_slice.begin() + (ptrdiff_t)ctx->ec.h_slice_at[(size_t)f + 1]);
     }
     at[(size_t)n_frames] = all.size();
-    ctx->h_slice.swap(all); ctx->h_slice_at.swap(at); ctx->ec_fallbacks = (int)fallback.size();
+    ctx->ec.h_slice.swap(all); ctx->ec.h_slice_at.swap(at); ctx->ec.ec_fallbacks = (int)fallback.size();
   }
   return HEVCDL_OK;
 }
@@ -1691,7 +1623,7 @@ static hevcdl_status entropy_pipeline(hevcdl_ctx *ctx, int n_frames, int want_sa
 extern "C" hevcdl_status hevcdl_set_entropy_capacity(hevcdl_ctx *ctx, int capacity_per_ctu)
 {
   if (!ctx) return HEVCDL_ERR_INVALID_ARG;
-  if (ctx->entropy_on) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_set_entropy_capacity: the switch is on");
+  if (ctx->ec.entropy_on) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_set_entropy_capacity: the switch is on");
   if (capacity_per_ctu > 0 && (capacity_per_ctu & 3)) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_set_entropy_capacity: not a multiple of 4");
   ctx->ec_capacity_per_ctu = capacity_per_ctu > 0 ? capacity_per_ctu : 0;
   return HEVCDL_OK;
@@ -1700,8 +1632,8 @@ extern "C" hevcdl_status hevcdl_set_entropy_capacity(hevcdl_ctx *ctx, int capaci
 extern "C" hevcdl_status hevcdl_get_entropy_info(hevcdl_ctx *ctx, int *fallbacks_opt, double *kernel_ms_opt)
 {
   if (!ctx) return HEVCDL_ERR_INVALID_ARG;
-  if (!ctx->entropy_on) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_get_entropy_info: hevcdl_enable_device_entropy was not called");
-  if (fallbacks_opt) *fallbacks_opt = ctx->ec_fallbacks;
+  if (!ctx->ec.entropy_on) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_get_entropy_info: hevcdl_enable_device_entropy was not called");
+  if (fallbacks_opt) *fallbacks_opt = ctx->ec.ec_fallbacks;
   if (kernel_ms_opt) for (int i = 0; i < 3; i++) kernel_ms_opt[i] = ctx->ec_ms[i];
   return HEVCDL_OK;
 }
@@ -1709,39 +1641,33 @@ extern "C" hevcdl_status hevcdl_get_entropy_info(hevcdl_ctx *ctx, int *fallbacks
 extern "C" hevcdl_status hevcdl_get_slice_data(hevcdl_ctx *ctx, int first, int count, const uint8_t **data, const uint32_t **sizes, int *n_substreams_per_picture)
 {
   if (!ctx) return HEVCDL_ERR_INVALID_ARG;
-  if (!data || !sizes || !n_substreams_per_picture || first < 0 || count < 0) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_get_slice_data: bad range");
-  if (!ctx->entropy_on) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_get_slice_data: hevcdl_enable_device_entropy was not called");
-  if ((size_t)first + (size_t)count + 1 > ctx->h_slice_at.size()) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_get_slice_data: pictures outside the last batch");
-  *data = ctx->h_slice.data() + ctx->h_slice_at[(size_t)first]; *sizes = ctx->h_slice_sizes.data() + (size_t)first * ctx->ec_units; *n_substreams_per_picture = ctx->ec_units;
+  TRY(check_batch_range(ctx, "hevcdl_get_slice_data", data && sizes && n_substreams_per_picture, ctx->ec.entropy_on, "hevcdl_enable_device_entropy", first, count,
+                        (long long)ctx->ec.h_slice_at.size() - 1));      // (h_slice_at holds the start of every picture and the end)
+  *data = ctx->ec.h_slice.data() + ctx->ec.h_slice_at[(size_t)first]; *sizes = ctx->ec.h_slice_sizes.data() + (size_t)first * ctx->ec.ec_units; *n_substreams_per_picture = ctx->ec.ec_units;
   return HEVCDL_OK;
 }
 
 extern "C" hevcdl_status hevcdl_encode_pictures_stream(hevcdl_ctx *ctx, const void *yuv, int n_frames, const uint8_t *labels_opt, int deblock, int want_sao,
                                                        int want_pictures, int want_records, int chunk_frames, hevcdl_stream_fn fn, void *user)
 {
-  hevcdl_status st = check_frames(ctx, n_frames); if (st) return st;
-  if (!ctx->entropy_on) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_encode_pictures_stream: hevcdl_enable_device_entropy was not called");
+  TRY(check_frames(ctx, n_frames));
+  if (!ctx->ec.entropy_on) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_encode_pictures_stream: hevcdl_enable_device_entropy was not called");
   if (n_frames == 0) return HEVCDL_OK;
   if (!yuv || !fn) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null pointer");
   const int chunk = std::min(n_frames, chunk_frames > 0 ? chunk_frames : 64);
-  const size_t rec_b = want_records ? (size_t)ctx->ctus * sizeof(hevcdl_ctu_record) : 0, pic_b = want_pictures ? ctx->frame_bytes : 0, stat_b = sizeof(hevcdl_frame_stats);
+  const size_t rec_b = want_records ? ctx->records_bytes(1) : 0, pic_b = want_pictures ? ctx->frame_bytes : 0, stat_b = sizeof(hevcdl_frame_stats);
   auto up64 = [](size_t v) { return (v + 63) & ~(size_t)63; };
   const size_t o_pic = up64(rec_b * chunk), o_stat = up64(o_pic + pic_b * chunk), need = o_stat + stat_b * chunk;
-  if (ctx->h_chunk_bytes < need) {
-    for (int i = 0; i < 2; i++) { if (ctx->h_chunk[i]) hipHostFree(ctx->h_chunk[i]); ctx->h_chunk[i] = nullptr; }
-    ctx->h_chunk_bytes = 0;
-    for (int i = 0; i < 2; i++) HIPCHK(hipHostMalloc((void **)&ctx->h_chunk[i], need, hipHostMallocDefault));
-    ctx->h_chunk_bytes = need;
-  }
+  TRY(ensure_chunk_buffers(ctx, need));
   uint8_t *d_final = nullptr;
-  st = encode_pictures_device(ctx, yuv, n_frames, labels_opt, deblock, want_sao, &d_final); if (st) return st;      // runs the entropy kernels too (the switch is on)
-  unsigned char *h = ctx->h_chunk[0];
+  TRY(encode_pictures_device(ctx, yuv, n_frames, labels_opt, deblock, want_sao, &d_final));      // runs the entropy kernels too (the switch is on)
+  unsigned char *h = ctx->stage.h_chunk[0];
   for (int first = 0; first < n_frames; first += chunk) { // records and pictures leave HBM only when asked for; the statistics are 40 bytes a picture
     const int cnt = std::min(chunk, n_frames - first);
-    if (want_records) HIPCHK(hipMemcpy(h, ctx->d_records + rec_b * first, rec_b * cnt, hipMemcpyDeviceToHost));
+    if (want_records) HIPCHK(hipMemcpy(h, ctx->stage.d_records + rec_b * first, rec_b * cnt, hipMemcpyDeviceToHost));
     if (want_pictures) HIPCHK(hipMemcpy(h + o_pic, d_final + pic_b * first, pic_b * cnt, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(h + o_stat, ctx->d_stats + stat_b * first, stat_b * cnt, hipMemcpyDeviceToHost));
-    if (fn(user, first, cnt, ctx->h_slice.data() + ctx->h_slice_at[(size_t)first], ctx->h_slice_sizes.data() + (size_t)first * ctx->ec_units, ctx->ec_units,
+    HIPCHK(hipMemcpy(h + o_stat, ctx->stage.d_stats + stat_b * first, stat_b * cnt, hipMemcpyDeviceToHost));
+    if (fn(user, first, cnt, ctx->ec.h_slice.data() + ctx->ec.h_slice_at[(size_t)first], ctx->ec.h_slice_sizes.data() + (size_t)first * ctx->ec.ec_units, ctx->ec.ec_units,
            (const hevcdl_frame_stats *)(h + o_stat), want_pictures ? h + o_pic : nullptr, want_records ? (const hevcdl_ctu_record *)h : nullptr) != 0)
       return fail(ctx, HEVCDL_ERR_INVALID_ARG, "the stream callback asked to stop");
   }
@@ -1751,19 +1677,18 @@ extern "C" hevcdl_status hevcdl_encode_pictures_stream(hevcdl_ctx *ctx, const vo
 // ---- per-CTU session: the semantic drop-in for TEncCu::compressCtu + encodeCtu (TEncSlice.cpp:879,893) ----------------
 extern "C" hevcdl_status hevcdl_begin_frames(hevcdl_ctx *ctx, const uint8_t *yuv, int n_frames, const uint8_t *labels_opt, uint8_t *labels_out_opt)
 {
-  hevcdl_status st = check_frames(ctx, n_frames); if (st) return st;
+  TRY(check_frames(ctx, n_frames));
   if (n_frames == 0 || !yuv) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "begin_frames: no frames");
-  st = ensure_staging(ctx); if (st) return st;
-  if (!ctx->d_cabac) HIPCHK(hipMalloc(&ctx->d_cabac, (size_t)168 * ctx->cfg.max_frames));
-  HIPCHK(hipMemcpy(ctx->d_yuv, yuv, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
-  if (labels_opt) { HIPCHK(hipMemcpy(ctx->d_labels, labels_opt, (size_t)ctx->ctus * 16 * n_frames, hipMemcpyHostToDevice)); st = hevcdl_clamp_labels_dev(ctx, ctx->d_labels, n_frames, nullptr); if (st) return st; }
-  else { st = hevcdl_predict_depth_dev(ctx, ctx->d_yuv, n_frames, ctx->d_labels, nullptr, nullptr); if (st) return st; }
-  HIPCHK(hipMemset(ctx->d_recon, 0, ctx->frame_bytes * n_frames));
-  HIPCHK(hipMemset(ctx->d_records, 0, (size_t)ctx->ctus * sizeof(hevcdl_ctu_record) * n_frames));
-  if (ctx->d_wpp) HIPCHK(hipMemset(ctx->d_wpp, 0, (size_t)256 * ctx->ctus_y * n_frames));      // WaveFrontSynchro: the rows' synchronisation contexts of this session
+  TRY(ensure_staging(ctx));
+  TRY(lazy_alloc(ctx, ctx->ses.d_cabac, sizeof(hevcdl_cabac_state) * (size_t)ctx->cfg.max_frames, "coder states of the per-CTU session (cfg.max_frames)"));
+  HIPCHK(hipMemcpy(ctx->stage.d_yuv, yuv, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
+  TRY(stage_labels(ctx, labels_opt, n_frames));
+  HIPCHK(hipMemset(ctx->stage.d_recon, 0, ctx->frame_bytes * n_frames));
+  HIPCHK(hipMemset(ctx->stage.d_records, 0, ctx->records_bytes(n_frames)));
+  if (ctx->rd.d_wpp) HIPCHK(hipMemset(ctx->rd.d_wpp, 0, (size_t)256 * ctx->ctus_y * n_frames));      // WaveFrontSynchro: the rows' synchronisation contexts of this session
   HIPCHK(hipDeviceSynchronize());
-  if (labels_out_opt) HIPCHK(hipMemcpy(labels_out_opt, ctx->d_labels, (size_t)ctx->ctus * 16 * n_frames, hipMemcpyDeviceToHost));
-  ctx->next_ctu.assign(n_frames, 0); ctx->session_frames = n_frames;
+  if (labels_out_opt) HIPCHK(hipMemcpy(labels_out_opt, ctx->stage.d_labels, ctx->labels_bytes(n_frames), hipMemcpyDeviceToHost));
+  ctx->ses.next_ctu.assign(n_frames, 0); ctx->ses.session_frames = n_frames;
   return HEVCDL_OK;
 }
 
@@ -1772,33 +1697,32 @@ extern "C" hevcdl_status hevcdl_compress_ctu(hevcdl_ctx *ctx, int frame, int ctu
 {
   if (!ctx) return HEVCDL_ERR_INVALID_ARG;
   if (ctx->cfg.tile_columns * ctx->cfg.tile_rows != 1) return fail(ctx, HEVCDL_ERR_UNSUPPORTED, "compress_ctu: the per-CTU session walks the untiled raster scan; with tiles use hevcdl_compress_frames");
-  if (frame < 0 || frame >= ctx->session_frames) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "compress_ctu: frame outside the session (hevcdl_begin_frames)");
+  if (frame < 0 || frame >= ctx->ses.session_frames) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "compress_ctu: frame outside the session (hevcdl_begin_frames)");
   if (ctu_addr < 0 || ctu_addr >= ctx->ctus || !record) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "compress_ctu: bad CTU address / null record");
   // the CTUs of a slice are a chain: neighbours' reconstruction and records must exist
-  if (ctu_addr > ctx->next_ctu[frame]) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "compress_ctu: CTUs must be submitted in coding order");
-  if (ctu_addr < ctx->next_ctu[frame] && !state_in_opt) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "compress_ctu: re-coding an earlier CTU needs its entry state");
+  if (ctu_addr > ctx->ses.next_ctu[frame]) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "compress_ctu: CTUs must be submitted in coding order");
+  if (ctu_addr < ctx->ses.next_ctu[frame] && !state_in_opt) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "compress_ctu: re-coding an earlier CTU needs its entry state");
   HIPCHK(hipSetDevice(ctx->cfg.device));
-  unsigned char *cab = ctx->d_cabac + (size_t)168 * frame;
-  if (state_in_opt) HIPCHK(hipMemcpy(cab, state_in_opt, 168, hipMemcpyHostToDevice));
+  unsigned char *cab = ctx->ses.d_cabac + sizeof(hevcdl_cabac_state) * (size_t)frame;
+  if (state_in_opt) HIPCHK(hipMemcpy(cab, state_in_opt, sizeof(hevcdl_cabac_state), hipMemcpyHostToDevice));
   const void *cab_in = (state_in_opt || ctu_addr > 0) ? cab : nullptr;      // NULL: slice-start contexts from the QP
-  hevcdl_status st = launch_rd(ctx, ctx->d_yuv + ctx->frame_bytes * frame, 1, ctx->d_labels + (size_t)ctx->ctus * 16 * frame,
-                               ctx->d_records + (size_t)ctx->ctus * sizeof(hevcdl_ctu_record) * frame, ctx->d_recon + ctx->frame_bytes * frame, nullptr, nullptr,
+  hevcdl_status st = launch_rd(ctx, ctx->stage.d_yuv + ctx->frame_bytes * frame, 1, ctx->stage.d_labels + ctx->labels_bytes(frame),
+                               ctx->stage.d_records + ctx->records_bytes(frame), ctx->stage.d_recon + ctx->frame_bytes * frame, nullptr, nullptr,
                                ctu_addr, ctu_addr + 1, cab_in, cab, 0, -1, frame);
   if (st) return st;
-  hipError_t e = hipDeviceSynchronize();
-  if (e != hipSuccess) return fail(ctx, HEVCDL_ERR_HIP, "rd kernel", e);
-  HIPCHK(hipMemcpy(record, ctx->d_records + ((size_t)ctx->ctus * frame + ctu_addr) * sizeof(hevcdl_ctu_record), sizeof(hevcdl_ctu_record), hipMemcpyDeviceToHost));
-  if (state_out_opt) HIPCHK(hipMemcpy(state_out_opt, cab, 168, hipMemcpyDeviceToHost));
-  if (ctu_addr == ctx->next_ctu[frame]) ctx->next_ctu[frame] = ctu_addr + 1;
+  TRY(sync_or_fail(ctx, "rd kernel"));
+  HIPCHK(hipMemcpy(record, ctx->stage.d_records + ctx->records_bytes(frame) + sizeof(hevcdl_ctu_record) * (size_t)ctu_addr, sizeof(hevcdl_ctu_record), hipMemcpyDeviceToHost));
+  if (state_out_opt) HIPCHK(hipMemcpy(state_out_opt, cab, sizeof(hevcdl_cabac_state), hipMemcpyDeviceToHost));
+  if (ctu_addr == ctx->ses.next_ctu[frame]) ctx->ses.next_ctu[frame] = ctu_addr + 1;
   return HEVCDL_OK;
 }
 
 extern "C" hevcdl_status hevcdl_get_recon(hevcdl_ctx *ctx, int frame, uint8_t *recon)
 {
   if (!ctx) return HEVCDL_ERR_INVALID_ARG;
-  if (frame < 0 || frame >= ctx->session_frames || !recon) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "get_recon: frame outside the session / null pointer");
+  if (frame < 0 || frame >= ctx->ses.session_frames || !recon) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "get_recon: frame outside the session / null pointer");
   HIPCHK(hipSetDevice(ctx->cfg.device));
-  HIPCHK(hipMemcpy(recon, ctx->d_recon + ctx->frame_bytes * frame, ctx->frame_bytes, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(recon, ctx->stage.d_recon + ctx->frame_bytes * frame, ctx->frame_bytes, hipMemcpyDeviceToHost));
   return HEVCDL_OK;
 }
 
@@ -1809,21 +1733,24 @@ extern "C" hevcdl_status hevcdl_profile_enable(hevcdl_ctx *ctx, int enable)
   return HEVCDL_OK;
 }
 
+// ms between the events of the start/stop pairs in v (and how many pairs were timed); the events are released
+static double sum_event_pairs(std::vector<Event> &v, unsigned *pairs_opt)
+{
+  double ms = 0; unsigned n = 0;
+  for (size_t i = 0; i + 1 < v.size(); i += 2) { float t = 0; if (hipEventElapsedTime(&t, v[i], v[i + 1]) == hipSuccess) { ms += t; n++; } }
+  v.clear();
+  if (pairs_opt) *pairs_opt = n;
+  return ms;
+}
+
 extern "C" hevcdl_status hevcdl_profile_get(hevcdl_ctx *ctx, hevcdl_profile *out)
 {
   if (!ctx || !out) return HEVCDL_ERR_INVALID_ARG;
   HIPCHK(hipSetDevice(ctx->cfg.device));
   HIPCHK(hipDeviceSynchronize());
   memset(out, 0, sizeof *out);
-  for (int which = 0; which < 2; which++) {
-    std::vector<hipEvent_t> &v = which ? ctx->ev_rd : ctx->ev_cnn;
-    double ms = 0; unsigned n = 0;
-    for (size_t i = 0; i + 1 < v.size(); i += 2) { float t = 0; if (hipEventElapsedTime(&t, v[i], v[i + 1]) == hipSuccess) { ms += t; n++; } hipEventDestroy(v[i]); hipEventDestroy(v[i + 1]); }
-    v.clear();
-    if (which) { out->rd_ms = ms; out->rd_launches = n; } else { out->cnn_ms = ms; out->cnn_launches = n; }
-  }
-  { std::vector<hipEvent_t> &v = ctx->ev_conv; double ms = 0;
-    for (size_t i = 0; i + 1 < v.size(); i += 2) { float t = 0; if (hipEventElapsedTime(&t, v[i], v[i + 1]) == hipSuccess) ms += t; hipEventDestroy(v[i]); hipEventDestroy(v[i + 1]); }
-    v.clear(); out->cnn_conv_ms = ms; }
+  out->cnn_ms = sum_event_pairs(ctx->ev_cnn, &out->cnn_launches);
+  out->rd_ms = sum_event_pairs(ctx->ev_rd, &out->rd_launches);
+  out->cnn_conv_ms = sum_event_pairs(ctx->ev_conv, nullptr);
   return HEVCDL_OK;
 }

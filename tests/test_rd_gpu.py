@@ -969,3 +969,19 @@ def test_random_configurations_match_oracle(oracle_built, seed):
     assert sao.tobytes() == o_sao.tobytes() and np.array_equal(final, o_final.reshape(final.shape)), what
     au = hevcdl_amd.write_access_unit(w, h, qp, 0, recs[0], sao=sao[0], tiles=tiles, bit_depth=bd, lf_across_tiles=lf)
     assert len(au) > 60
+
+
+def test_launch_forms_are_the_recorded_ones():
+    """The launches of tests/rd_plan_cases.py, made for real on tiny pictures: hevcdl_last_rd_launch must report, character for character, what
+    tests/golden/rd_launch_forms.json holds -- recorded from the library before the launch plan became a function of its own (tools/record_rd_launch_forms.py)."""
+    import json
+    import rd_plan_cases
+    with open(os.path.join(GOLD, "rd_launch_forms.json")) as f:
+        recorded = json.load(f)
+    cus = rd_plan_cases.device_cus()
+    assert cus == recorded["cus"], ("this device has %d CUs, tests/golden/rd_launch_forms.json was recorded on %d: record it again with the library of the commit "
+                                    "before the launch plan last changed (tools/record_rd_launch_forms.py)" % (cus, recorded["cus"]))
+    assert rd_plan_cases.build_waves() == recorded["waves"]
+    got = rd_plan_cases.run_cases(recorded["cases"])
+    for c in recorded["cases"]:
+        assert got[c["name"]] == c["launch"], c["name"]
