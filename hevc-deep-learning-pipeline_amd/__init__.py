@@ -94,13 +94,32 @@ class StreamConfig(ctypes.Structure):
                 ("tile_columns", ctypes.c_int32), ("tile_rows", ctypes.c_int32), ("bit_depth", ctypes.c_int32),
                 ("tile_uniform_spacing", ctypes.c_int32), ("tile_column_width", ctypes.c_int32 * 19), ("tile_row_height", ctypes.c_int32 * 21),
                 ("lf_across_tiles", ctypes.c_int32), ("tools", ctypes.c_uint32), ("lf_beta_offset_div2", ctypes.c_int32), ("lf_tc_offset_div2", ctypes.c_int32),
-                ("rewrite_param_sets", ctypes.c_int32), ("wavefront", ctypes.c_int32), ("conf_win_right", ctypes.c_int32), ("conf_win_bottom", ctypes.c_int32)]
+                ("rewrite_param_sets", ctypes.c_int32), ("wavefront", ctypes.c_int32), ("conf_win_right", ctypes.c_int32), ("conf_win_bottom", ctypes.c_int32),
+                ("conf_win_left", ctypes.c_int32), ("conf_win_top", ctypes.c_int32)]
 
 
 class SourceFormat(ctypes.Structure):
     """hevcdl_source_format of include/hevcdl.h: what the caller's pictures look like when they are not in the context's own format."""
     _fields_ = [("struct_size", ctypes.c_uint32), ("source_width", ctypes.c_int32), ("source_height", ctypes.c_int32),
-                ("input_bit_depth", ctypes.c_int32), ("output_bit_depth", ctypes.c_int32)]
+                ("input_bit_depth", ctypes.c_int32), ("output_bit_depth", ctypes.c_int32),
+                ("chroma_format", ctypes.c_int32), ("colour_space", ctypes.c_int32), ("output_internal_colour_space", ctypes.c_int32), ("snr_internal_colour_space", ctypes.c_int32),
+                ("conf_win_left", ctypes.c_int32), ("conf_win_right", ctypes.c_int32), ("conf_win_top", ctypes.c_int32), ("conf_win_bottom", ctypes.c_int32)]
+
+    @property
+    def source_samples(self):
+        """Samples of one source-format frame: Y, then both chroma planes at the file's own chroma size (4:0:0: none)."""
+        w, h, f = self.source_width, self.source_height, self.chroma_format or 420
+        return w * h + {400: 0, 420: 2 * (w // 2) * (h // 2), 422: 2 * (w // 2) * h, 444: 2 * w * h}[f]
+
+    @property
+    def window_size(self):
+        """Luma size of one output-format frame: the source size, or the explicit window (conf_win_*)."""
+        return self.source_width - self.conf_win_left - self.conf_win_right, self.source_height - self.conf_win_top - self.conf_win_bottom
+
+    @property
+    def output_samples(self):
+        w, h = self.window_size
+        return w * h * 3 // 2
 
 
 class Profile(ctypes.Structure):
@@ -450,7 +469,8 @@ def default_config(width, height, qp, max_frames=1, device=0, cnn_input=0, tiles
 
 def stream_config(width, height, qp, level_idc=186, sao=False, tiles=(1, 1), bit_depth=8, lf_across_tiles=True, tools=TOOLS_REFERENCE, lf_offsets=(0, 0), lf_disable=False,
                   rewrite_param_sets=True, wavefront=False, conf_win=(0, 0)):
-    """hevcdl_stream_config of include/hevcdl.h from keyword arguments.  conf_win: (right, bottom) padding in luma samples, the SPS's conformance window."""
+    """hevcdl_stream_config of include/hevcdl.h from keyword arguments.  conf_win: (right, bottom) padding in luma samples, the SPS's conformance window; or all four
+    offsets (left, right, top, bottom) of an explicit window (ConformanceWindowMode 3)."""
     lib = load_library()
     cfg = StreamConfig()
     st = lib.hevcdl_stream_config_default(ctypes.byref(cfg), width, height, qp)
@@ -466,7 +486,10 @@ def stream_config(width, height, qp, level_idc=186, sao=False, tiles=(1, 1), bit
     cfg.rewrite_param_sets = 1 if rewrite_param_sets else 0
     cfg.wavefront = 1 if wavefront else 0      # a sub-stream per CTU row, entry points in the slice header
     cfg.sao_enabled = 1 if sao else 0
-    cfg.conf_win_right, cfg.conf_win_bottom = int(conf_win[0]), int(conf_win[1])
+    if len(conf_win) == 4:
+        cfg.conf_win_left, cfg.conf_win_right, cfg.conf_win_top, cfg.conf_win_bottom = (int(v) for v in conf_win)
+    else:
+        cfg.conf_win_right, cfg.conf_win_bottom = int(conf_win[0]), int(conf_win[1])
     return cfg
 
 
@@ -552,12 +575,22 @@ def _sample_dtype(bit_depth):
     return np.uint8 if bit_depth <= 8 else np.dtype("<u2")
 
 
-def source_format(source_width, source_height, input_bit_depth=8, output_bit_depth=None):
-    """hevcdl_source_format: pictures of source_width x source_height at input_bit_depth; output frames at output_bit_depth (default: the input's)."""
+COLOUR_SPACES = {None: 0, "": 0, "UNCHANGED": 0, "YCbCrtoYCrCb": 1}
+
+
+def source_format(source_width, source_height, input_bit_depth=8, output_bit_depth=None, chroma_format=420, colour_space=0, output_internal_colour_space=False,
+                  snr_internal_colour_space=False, conf_win=(0, 0, 0, 0)):
+    """hevcdl_source_format: pictures of source_width x source_height at input_bit_depth; output frames at output_bit_depth (default: the input's).  chroma_format: the
+    file's (400 / 420 / 422 / 444; the coded picture stays 4:2:0); colour_space: 0 / 1 or the reference's names ("YCbCrtoYCrCb": the file stores Cr before Cb);
+    conf_win: (left, right, top, bottom) of an explicit window in luma samples (ConformanceWindowMode 3: no padding)."""
     fmt = SourceFormat()
     fmt.struct_size = ctypes.sizeof(SourceFormat)
     fmt.source_width, fmt.source_height, fmt.input_bit_depth = int(source_width), int(source_height), int(input_bit_depth)
     fmt.output_bit_depth = int(input_bit_depth if output_bit_depth is None else output_bit_depth)
+    fmt.chroma_format = int(chroma_format)
+    fmt.colour_space = COLOUR_SPACES[colour_space] if colour_space in COLOUR_SPACES else int(colour_space)
+    fmt.output_internal_colour_space, fmt.snr_internal_colour_space = int(bool(output_internal_colour_space)), int(bool(snr_internal_colour_space))
+    fmt.conf_win_left, fmt.conf_win_right, fmt.conf_win_top, fmt.conf_win_bottom = (int(v) for v in conf_win)
     return fmt
 
 
@@ -574,8 +607,9 @@ def padded_size(source_width, source_height, mode=1, pad_x=0, pad_y=0):
 def load_source_host(fmt, coded_width, coded_height, internal_bit_depth, src):
     """Source-format frames [n, source samples] -> coded-format frames [n, coded samples] on the CPU (hevcdl_load_source_host; no GPU needed)."""
     lib = load_library()
-    ss = fmt.source_width * fmt.source_height * 3 // 2
-    src = np.ascontiguousarray(src, _sample_dtype(fmt.input_bit_depth)).reshape(-1, ss)
+    if not lib.hevcdl_source_frame_bytes(ctypes.byref(fmt)):
+        raise HevcdlError(1, "hevcdl_load_source_host: the source format")
+    src = np.ascontiguousarray(src, _sample_dtype(fmt.input_bit_depth)).reshape(-1, fmt.source_samples)
     out = np.zeros((src.shape[0], coded_width * coded_height * 3 // 2), _sample_dtype(internal_bit_depth))
     st = lib.hevcdl_load_source_host(ctypes.byref(fmt), int(coded_width), int(coded_height), int(internal_bit_depth), src.ctypes.data, src.shape[0], out.ctypes.data)
     if st:
@@ -588,7 +622,9 @@ def store_output_host(fmt, coded_width, coded_height, internal_bit_depth, pictur
     lib = load_library()
     cs = coded_width * coded_height * 3 // 2
     pictures = np.ascontiguousarray(pictures, _sample_dtype(internal_bit_depth)).reshape(-1, cs)
-    out = np.zeros((pictures.shape[0], fmt.source_width * fmt.source_height * 3 // 2), _sample_dtype(fmt.output_bit_depth))
+    if not lib.hevcdl_output_frame_bytes(ctypes.byref(fmt)):
+        raise HevcdlError(1, "hevcdl_store_output_host: the source format")
+    out = np.zeros((pictures.shape[0], fmt.output_samples), _sample_dtype(fmt.output_bit_depth))
     st = lib.hevcdl_store_output_host(ctypes.byref(fmt), int(coded_width), int(coded_height), int(internal_bit_depth), pictures.ctypes.data, pictures.shape[0], out.ctypes.data)
     if st:
         raise HevcdlError(st, "hevcdl_store_output_host")
@@ -644,7 +680,7 @@ class Encoder:
         if self.source_format is None:
             return self._frames(yuv)
         f = self.source_format
-        yuv = np.ascontiguousarray(yuv, _sample_dtype(f.input_bit_depth)).reshape(-1, f.source_width * f.source_height * 3 // 2)
+        yuv = np.ascontiguousarray(yuv, _sample_dtype(f.input_bit_depth)).reshape(-1, f.source_samples)
         return yuv, yuv.shape[0]
 
     def load_source(self, src):
@@ -658,14 +694,14 @@ class Encoder:
         """Coded-format pictures -> output-format frames (window size, output depth) by the device kernel (hevcdl_store_output)."""
         pictures, n = self._frames(pictures)
         f = self.source_format
-        out = np.zeros((n, f.source_width * f.source_height * 3 // 2), _sample_dtype(f.output_bit_depth))
+        out = np.zeros((n, f.output_samples), _sample_dtype(f.output_bit_depth))
         self._check(self.lib.hevcdl_store_output(self._h, pictures.ctypes.data, n, out.ctypes.data))
         return out
 
     def get_output_frames(self, first, count):
         """Output-format frames of pictures [first, first + count) of the last encode_pictures* call, cropped and scaled on the device (hevcdl_get_output_frames)."""
         f = self.source_format
-        out = np.zeros((count, f.source_width * f.source_height * 3 // 2), _sample_dtype(f.output_bit_depth))
+        out = np.zeros((count, f.output_samples), _sample_dtype(f.output_bit_depth))
         self._check(self.lib.hevcdl_get_output_frames(self._h, int(first), int(count), out.ctypes.data))
         return out
 

@@ -1218,6 +1218,8 @@ extern "C" hevcdl_status hevcdl_set_source_format(hevcdl_ctx *ctx, const hevcdl_
   TRY(check_frames(ctx, 0));
   if (fmt && (fmt->struct_size != sizeof *fmt || !hevcdl_src::format_fits(fmt->source_width, fmt->source_height, fmt->input_bit_depth, fmt->output_bit_depth, ctx->cfg.width, ctx->cfg.height)))
     return fail(ctx, HEVCDL_ERR_INVALID_ARG, "source format: even source size of at least 2 x 2 and at most the context's, even padding, bit depths 8 .. 16");
+  if (fmt && !hevcdl_source_format_fits(fmt, ctx->cfg.width, ctx->cfg.height))
+    return fail(ctx, HEVCDL_ERR_INVALID_ARG, "source format: chroma format 400 / 420 / 422 / 444, colour space 0 / 1 (not with 400), window offsets even, with something left of the picture and without padding");
   TRY(sync_or_fail(ctx, "hevcdl_set_source_format"));
   source_release(ctx);
   if (!fmt) return HEVCDL_OK;
@@ -1250,12 +1252,19 @@ extern "C" hevcdl_status hevcdl_load_source_dev(hevcdl_ctx *ctx, const void *d_s
   if (n_frames == 0) return HEVCDL_OK;
   p.src = d_src; p.dst = d_coded; p.src_w = ctx->src.src_fmt.source_width; p.src_h = ctx->src.src_fmt.source_height; p.dst_w = ctx->cfg.width; p.dst_h = ctx->cfg.height;
   p.from_depth = ctx->src.src_fmt.input_bit_depth; p.to_depth = ctx->cfg.bit_depth; p.n_pics = n_frames;
+  const hevcdl_source_format &f = ctx->src.src_fmt;
+  if (hevcdl_src::chroma_format_id(f.chroma_format) != hevcdl_src::FMT_420 || f.colour_space) { // the file's layout: the kernels of their own (a 4:2:0 file in the coded order runs what it ran)
+    hevcdl_source_fmt_params q; memset(&q, 0, sizeof q);
+    q.b = p; q.chroma_format = hevcdl_src::chroma_format_id(f.chroma_format); q.swap = f.colour_space;
+    hevcdl_launch_source_load_fmt(&q, stream);
+  } else
   hevcdl_launch_source_load(&p, stream);
   return launch_status(ctx);
 }
 
-// coded pictures -> pictures of the window's size at to_depth
-static hevcdl_status store_window_dev(hevcdl_ctx *ctx, const void *d_pictures, int n_frames, void *d_out, void *stream, int to_depth)
+// coded pictures -> pictures of the window's size at to_depth.  output: the output frames (the explicit window, the planes back in the file's order); otherwise the crop
+// the quality kernels measure a padded picture by (the coded picture minus the padding, coded plane order)
+static hevcdl_status store_window_dev(hevcdl_ctx *ctx, const void *d_pictures, int n_frames, void *d_out, void *stream, int to_depth, bool output)
 {
   hevcdl_source_params p; memset(&p, 0, sizeof p);
   p.src_bytes = ctx->cfg.bit_depth > 8 ? 2 : 1; p.dst_bytes = to_depth > 8 ? 2 : 1;
@@ -1263,16 +1272,24 @@ static hevcdl_status store_window_dev(hevcdl_ctx *ctx, const void *d_pictures, i
   if (n_frames == 0) return HEVCDL_OK;
   p.src = d_pictures; p.dst = d_out; p.src_w = ctx->cfg.width; p.src_h = ctx->cfg.height; p.dst_w = ctx->src.src_fmt.source_width; p.dst_h = ctx->src.src_fmt.source_height;
   p.from_depth = ctx->cfg.bit_depth; p.to_depth = to_depth; p.n_pics = n_frames;
+  const hevcdl_source_format &f = ctx->src.src_fmt;
+  const int swap = f.colour_space && !f.output_internal_colour_space;
+  if (output && (swap || (f.conf_win_left | f.conf_win_right | f.conf_win_top | f.conf_win_bottom))) {
+    hevcdl_source_fmt_params q; memset(&q, 0, sizeof q);
+    q.b = p; hevcdl_source_window_size(&f, &q.b.dst_w, &q.b.dst_h);
+    q.chroma_format = hevcdl_src::FMT_420; q.swap = swap; q.win_x = f.conf_win_left; q.win_y = f.conf_win_top;
+    hevcdl_launch_source_store_fmt(&q, stream);
+  } else
   hevcdl_launch_source_store(&p, stream);
   return launch_status(ctx);
 }
 extern "C" hevcdl_status hevcdl_store_output_dev(hevcdl_ctx *ctx, const void *d_pictures, int n_frames, void *d_out, void *stream)
 {
   if (!ctx) return HEVCDL_ERR_INVALID_ARG;
-  return store_window_dev(ctx, d_pictures, n_frames, d_out, stream, ctx->src.src_fmt.output_bit_depth);
+  return store_window_dev(ctx, d_pictures, n_frames, d_out, stream, ctx->src.src_fmt.output_bit_depth, true);
 }
 // the window at the internal depth, contiguous: what the quality kernels measure a padded picture by (the store kernel with OUT = PEL, no scaling)
-static hevcdl_status crop_window_dev(hevcdl_ctx *ctx, const void *d_pictures, int n_frames, void *d_out, void *stream) { return store_window_dev(ctx, d_pictures, n_frames, d_out, stream, ctx->cfg.bit_depth); }
+static hevcdl_status crop_window_dev(hevcdl_ctx *ctx, const void *d_pictures, int n_frames, void *d_out, void *stream) { return store_window_dev(ctx, d_pictures, n_frames, d_out, stream, ctx->cfg.bit_depth, false); }
 
 extern "C" hevcdl_status hevcdl_load_source(hevcdl_ctx *ctx, const void *src, int n_frames, void *coded_out)
 {
@@ -1357,13 +1374,17 @@ static hevcdl_status encode_pictures_device(hevcdl_ctx *ctx, const void *yuv, in
                  : hevcdl_picture_report_dev(ctx, ctx->stage.d_yuv, *d_final, n_frames, ctx->rp.report_method, ctx->rp.d_rp_out, nullptr));
   }
   TRY(sync_or_fail(ctx, "picture pipeline"));
+  // YCbCrtoYCrCb without SNRInternalColourSpace: the reference measures against the file's planes, so its U column is the coded picture's third plane (TEncGOP.cpp xCalculateAddPSNR)
+  const bool file_order = ctx->src.source_on && ctx->src.src_fmt.colour_space && !ctx->src.src_fmt.snr_internal_colour_space;
   if (ctx->rp.report_on) {
     ctx->rp.h_report.resize(n_frames);
     HIPCHK(hipMemcpy(ctx->rp.h_report.data(), ctx->rp.d_rp_out, sizeof(hevcdl_picture_report_t) * (size_t)n_frames, hipMemcpyDeviceToHost));
+    if (file_order) for (hevcdl_picture_report_t &r : ctx->rp.h_report) std::swap(r.sse[1], r.sse[2]);      // (the digests stay the coded picture's)
   }
   if (ctx->q.quality_on) {
     ctx->q.h_quality.resize(n_frames);
     HIPCHK(hipMemcpy(ctx->q.h_quality.data(), ctx->q.d_q_out, sizeof(hevcdl_quality) * (size_t)n_frames, hipMemcpyDeviceToHost));
+    if (file_order) for (hevcdl_quality &r : ctx->q.h_quality) { std::swap(r.sse[1], r.sse[2]); std::swap(r.msssim[1], r.msssim[2]); }
   }
   if (ctx->ec.entropy_on) { TRY(entropy_pipeline(ctx, n_frames, want_sao)); }      // hevcdl_enable_device_entropy: the slice data too, from the records still in HBM
   ctx->src.d_last_final = *d_final; ctx->src.last_frames = n_frames;

@@ -7,6 +7,8 @@
 //   planar YUV reader            HM_dl/source/Lib/TLibVideoIO/TVideoIOYuv.cpp:249,675 (8-bit 4:2:0 file, FrameSkip)
 //   padding / window / depths    TAppEncCfg.cpp:1569-1632 (ConformanceWindowMode 0 / 1 / 2), TVideoIOYuv.cpp:70-95, 363-381, 755-830: the file holds source-format frames, the
 //                                library pads and converts them on the device (hevcdl_set_source_format), the reconstruction file holds the window at OutputBitDepth
+//   file layout                  TVideoIOYuv.cpp:249-384 (InputChromaFormat 400 / 422 / 444 into a 4:2:0 coded picture), :981-1041 (InputColourSpaceConvert YCbCrtoYCrCb),
+//                                TAppEncCfg.cpp:1618-1631 (ConformanceWindowMode 3 with ConfWin*), TAppEncTop.cpp:669 + TAppEncCfg.cpp:1286 (TemporalSubsampleRatio)
 //   picture log line / summary   TEncGOP.cpp:2500-2541, TEncAnalyze.h:163-370
 // and drives the GPU path through the C ABI of include/hevcdl.h only.  Keys that would change the path are checked
 // against what the path implements (rejected, not ignored).  Labels come from the on-device CNN, or -- the reference's own
@@ -47,8 +49,9 @@ const Key KEYS[] = {
   { "CnnInput", 0, USED, 0 }, { "BnMode", 0, USED, 0 }, { "PrintConfig", 0, USED, 0 }, { "LoopFilterDisable", 0, USED, 0 },
   // keys that define the path: only the implemented value is accepted
   { "ConformanceWindowMode", 0, USED, 0 }, { "HorizontalPadding", "pdx", USED, 0 }, { "VerticalPadding", "pdy", USED, 0 }, { "OutputBitDepth", 0, USED, 0 }, { "OutputBitDepthC", 0, USED, 0 },
-  { "ConfWinLeft", 0, USED, 0 }, { "ConfWinRight", 0, USED, 0 }, { "ConfWinTop", 0, USED, 0 }, { "ConfWinBottom", 0, USED, 0 },      // (rejected: they belong to ConformanceWindowMode 3)
-  { "InputBitDepth", 0, USED, 0 }, { "InternalBitDepth", 0, USED, 0 }, { "InputChromaFormat", 0, PATH, "420" }, { "Profile", 0, USED, 0 },
+  { "ConfWinLeft", 0, USED, 0 }, { "ConfWinRight", 0, USED, 0 }, { "ConfWinTop", 0, USED, 0 }, { "ConfWinBottom", 0, USED, 0 },      // (ConformanceWindowMode 3 only)
+  { "InputBitDepth", 0, USED, 0 }, { "InternalBitDepth", 0, USED, 0 }, { "InputChromaFormat", 0, USED, 0 }, { "ChromaFormatIDC", "cf", USED, 0 }, { "Profile", 0, USED, 0 },
+  { "InputColourSpaceConvert", 0, USED, 0 }, { "OutputInternalColourSpace", 0, USED, 0 }, { "SNRInternalColourSpace", 0, USED, 0 }, { "TemporalSubsampleRatio", "ts", USED, 0 },
   { "MaxCUWidth", 0, PATH, "64" }, { "MaxCUHeight", 0, PATH, "64" }, { "MaxPartitionDepth", 0, PATH, "4" },
   { "QuadtreeTULog2MaxSize", 0, PATH, "5" }, { "QuadtreeTULog2MinSize", 0, PATH, "2" }, { "QuadtreeTUMaxDepthIntra", 0, PATH, "3" },
   { "IntraPeriod", 0, PATH, "1" }, { "GOPSize", 0, PATH, "1" }, { "MaxDeltaQP", 0, PATH, "0" }, { "DeltaQpRD", 0, PATH, "0" },
@@ -227,16 +230,22 @@ int main(int argc, char **argv)
     if (k->kind == STAGE) stage_keys.push_back(k->name);
   }
   // SourceWidth / SourceHeight are the FILE's size; the context is created with the padded (coded) size of ConformanceWindowMode (TAppEncCfg.cpp:1569-1617): 0 none,
-  // 1 up to the next multiple of the minimum CU (8), 2 by HorizontalPadding / VerticalPadding; 3 (explicit ConfWin* offsets) is another path
+  // 1 up to the next multiple of the minimum CU (8), 2 by HorizontalPadding / VerticalPadding; 3: no padding, the window is the four ConfWin* offsets
   const int src_w = (int)opt.geti("SourceWidth", 0), src_h = (int)opt.geti("SourceHeight", 0), qp = (int)opt.geti("QP", 30);
   const int conf_mode = (int)opt.geti("ConformanceWindowMode", 0), pad_x = (int)opt.geti("HorizontalPadding", 0), pad_y = (int)opt.geti("VerticalPadding", 0);
   int width = src_w, height = src_h;
-  if (conf_mode == 3) opt.errors.push_back("ConformanceWindowMode = 3 is not implemented by this path (only 0, 1 and 2)");
-  else if (conf_mode < 0 || conf_mode > 3) opt.errors.push_back("ConformanceWindowMode = " + std::to_string(conf_mode) + " is not a value of the key (0, 1 or 2)");
+  const int win_l = conf_mode == 3 ? (int)opt.geti("ConfWinLeft", 0) : 0, win_r = conf_mode == 3 ? (int)opt.geti("ConfWinRight", 0) : 0;
+  const int win_t = conf_mode == 3 ? (int)opt.geti("ConfWinTop", 0) : 0, win_b = conf_mode == 3 ? (int)opt.geti("ConfWinBottom", 0) : 0;
+  if (conf_mode == 3) { // TAppEncCfg.cpp:1618-1631: nothing is padded, so the size must be the coded size already; the offsets are in luma samples and even (4:2:0, :2231-2234)
+    if (src_w > 0 && src_h > 0 && ((src_w & 7) || (src_h & 7))) opt.errors.push_back("ConformanceWindowMode = 3 pads nothing: SourceWidth x SourceHeight must be multiples of the minimum CU (8)");
+    if (win_l < 0 || win_r < 0 || win_t < 0 || win_b < 0 || ((win_l | win_r | win_t | win_b) & 1)) opt.errors.push_back("ConfWinLeft / ConfWinRight / ConfWinTop / ConfWinBottom: a conformance window offset must be an integer multiple of the specified chroma subsampling (2), and not negative");
+    else if (src_w > 0 && src_h > 0 && (win_l + win_r >= src_w || win_t + win_b >= src_h)) opt.errors.push_back("ConfWinLeft / ConfWinRight / ConfWinTop / ConfWinBottom leave nothing of the picture");
+  }
+  else if (conf_mode < 0 || conf_mode > 3) opt.errors.push_back("ConformanceWindowMode = " + std::to_string(conf_mode) + " is not a value of the key (0, 1, 2 or 3)");
   else if (src_w > 0 && src_h > 0 && hevcdl_padded_size(src_w, src_h, conf_mode, pad_x, pad_y, &width, &height) != HEVCDL_OK)
     opt.errors.push_back("SourceWidth x SourceHeight with ConformanceWindowMode " + std::to_string(conf_mode) + ": the size must be even and the padded size a multiple of 8, the padding even and not negative");
   for (const char *key : { "ConfWinLeft", "ConfWinRight", "ConfWinTop", "ConfWinBottom" })
-    if (opt.v.count(key)) opt.errors.push_back(std::string(key) + " belongs to ConformanceWindowMode 3, which is not implemented by this path");
+    if (conf_mode != 3 && opt.v.count(key)) opt.errors.push_back(std::string(key) + " belongs to ConformanceWindowMode 3");
   const long frame_skip = opt.geti("FrameSkip", 0); long n_frames = opt.geti("FramesToBeEncoded", 0);
   const double fps = atof(opt.get("FrameRate", "30").c_str());
   const std::string input = native_path(opt.get("InputFile")), recon_path = native_path(opt.get("ReconFile")), label_dir = native_path(opt.get("LabelDir"));
@@ -259,8 +268,26 @@ int main(int argc, char **argv)
   if (bit_depth != 8 && bit_depth != 10) opt.errors.push_back("InternalBitDepth = " + std::to_string(bit_depth) + " is not implemented by this path (only 8 and 10)");
   { const std::string prof = opt.get("Profile", bit_depth == 8 ? "main" : "main10");
     if (prof != (bit_depth == 8 ? "main" : "main10")) opt.errors.push_back("Profile = " + prof + " does not go with InternalBitDepth = " + std::to_string(bit_depth) + " on this path (main at 8 bits, main10 at 10 bits)"); }
+  // The file's layout.  The coded picture is 4:2:0 (Profile main / main10), so ChromaFormatIDC must say 420 -- and must be named when the file is something else, because
+  // the reference's default (0) means "as the input" and it then refuses the profile with the message below (TAppEncCfg.cpp:1381, 2033).
+  const int in_cf = (int)opt.geti("InputChromaFormat", 420), cf_idc = (int)opt.geti("ChromaFormatIDC", 0);
+  if (in_cf != 400 && in_cf != 420 && in_cf != 422 && in_cf != 444) opt.errors.push_back("InputChromaFormatIDC must be either 400, 420, 422 or 444");
+  else if ((cf_idc == 0 ? in_cf : cf_idc) != 420) {
+    if (cf_idc != 0 && cf_idc != 400 && cf_idc != 422 && cf_idc != 444) opt.errors.push_back("ChromaFormatIDC must be either 400, 420, 422 or 444");
+    else opt.errors.push_back("ChromaFormatConstraint must be 420 for non main-RExt profiles.");
+  }
+  const std::string csc = opt.get("InputColourSpaceConvert", "");
+  if (csc != "" && csc != "UNCHANGED" && csc != "YCbCrtoYCrCb") opt.errors.push_back("InputColourSpaceConvert = " + csc + " is not implemented by this path (only UNCHANGED and YCbCrtoYCrCb: the others need a 4:4:4 coded picture)");
+  const int colour_space = csc == "YCbCrtoYCrCb" ? 1 : 0;
+  if (colour_space && in_cf == 400) opt.errors.push_back("InputColourSpaceConvert = YCbCrtoYCrCb needs a file with chroma planes (InputChromaFormat 400 has none)");
+  const int out_internal_cs = opt.geti("OutputInternalColourSpace", 0) != 0, snr_internal_cs = opt.geti("SNRInternalColourSpace", 0) != 0;
+  // TemporalSubsampleRatio: the file reader skips ratio - 1 frames behind every picture it reads, and FramesToBeEncoded counts SOURCE frames (TAppEncTop.cpp:669, TAppEncCfg.cpp:1286);
+  // the summary's bitrate is taken at FrameRate / ratio (TEncGOP.cpp:2043)
+  const long ts_ratio = opt.geti("TemporalSubsampleRatio", 1);
+  if (ts_ratio < 1) opt.errors.push_back("Temporal subsample rate must be no less than 1");
   // the source format goes to the library only when the file is not in the codec's own format already: every other run is the run it was
-  const bool use_fmt = src_w != width || src_h != height || in_bd != bit_depth || out_bd != bit_depth;
+  const bool use_fmt = src_w != width || src_h != height || in_bd != bit_depth || out_bd != bit_depth || in_cf != 420 || colour_space || (win_l | win_r | win_t | win_b) != 0;
+  const bool file_order = colour_space && !snr_internal_cs;      // the U and V columns are the file's second and third plane (the library's quality and report results come in that order)
   // decoded picture hash SEI (TAppEncCfg.cpp:1093): 0 none, 1 MD5 of the output picture behind every access unit
   const int hash_sei = (int)opt.geti("SEIDecodedPictureHash", 0);
   // PrintMSSSIM: computed on the device from the pictures the pipeline still holds there (hevcdl_enable_quality); the two MSE keys only print what the PSNR is made of
@@ -298,9 +325,13 @@ int main(int argc, char **argv)
   if (opt.v.count("PrintConfig")) {
     printf("{\"InputFile\": \"%s\", \"ReconFile\": \"%s\", \"SourceWidth\": %d, \"SourceHeight\": %d, \"QP\": %d, \"FrameSkip\": %ld, \"FramesToBeEncoded\": %ld, "
            "\"FrameRate\": %g, \"LabelDir\": \"%s\", \"CnnInput\": \"%s\", \"BitstreamFile\": \"%s\", \"level_idc\": %d, \"tiles\": [%d, %d], \"bit_depth\": %d, "
-           "\"ConformanceWindowMode\": %d, \"HorizontalPadding\": %d, \"VerticalPadding\": %d, \"InputBitDepth\": %d, \"InternalBitDepth\": %d, \"OutputBitDepth\": %d, \"coded_size\": [%d, %d], \"stage_keys\": [", json_escape(input).c_str(), json_escape(recon_path).c_str(), src_w, src_h, qp,
+           "\"ConformanceWindowMode\": %d, \"HorizontalPadding\": %d, \"VerticalPadding\": %d, \"InputBitDepth\": %d, \"InternalBitDepth\": %d, \"OutputBitDepth\": %d, \"coded_size\": [%d, %d], "
+           "\"InputChromaFormat\": %d, \"ChromaFormatIDC\": %d, \"Input ChromaFormatIDC\": \"4:%c:%c\", \"Output (internal) ChromaFormatIDC\": \"4:2:0\", \"InputColourSpaceConvert\": \"%s\", "
+           "\"OutputInternalColourSpace\": %d, \"SNRInternalColourSpace\": %d, \"ConfWin\": [%d, %d, %d, %d], \"TemporalSubsampleRatio\": %ld, \"stage_keys\": [", json_escape(input).c_str(), json_escape(recon_path).c_str(), src_w, src_h, qp,
            frame_skip, n_frames, fps, json_escape(label_dir).c_str(), cnn_input.c_str(), json_escape(bitstream_path).c_str(), level_idc, tile_cols, tile_rows, bit_depth,
-           conf_mode, pad_x, pad_y, in_bd, bit_depth, out_bd, width, height);
+           conf_mode, pad_x, pad_y, in_bd, bit_depth, out_bd, width, height,
+           in_cf, cf_idc == 0 ? in_cf : cf_idc, in_cf == 400 ? '0' : (in_cf == 444 ? '4' : '2'), in_cf == 400 ? '0' : (in_cf == 420 ? '0' : (in_cf == 422 ? '2' : '4')), colour_space ? "YCbCrtoYCrCb" : "UNCHANGED",
+           out_internal_cs, snr_internal_cs, win_l, win_r, win_t, win_b, ts_ratio);
     for (size_t i = 0; i < stage_keys.size(); i++) printf("%s\"%s\"", i ? ", " : "", stage_keys[i].c_str());
     printf("], \"errors\": [");
     for (size_t i = 0; i < opt.errors.size(); i++) printf("%s\"%s\"", i ? ", " : "", json_escape(opt.errors[i]).c_str());
@@ -317,6 +348,8 @@ int main(int argc, char **argv)
   const size_t frame_bytes = hevcdl_frame_bytes_bd(width, height, bit_depth);      // a coded picture
   hevcdl_source_format fmt; memset(&fmt, 0, sizeof fmt);
   fmt.struct_size = sizeof fmt; fmt.source_width = src_w; fmt.source_height = src_h; fmt.input_bit_depth = in_bd; fmt.output_bit_depth = out_bd;
+  fmt.chroma_format = in_cf == 420 ? 0 : in_cf; fmt.colour_space = colour_space; fmt.output_internal_colour_space = out_internal_cs; fmt.snr_internal_colour_space = snr_internal_cs;
+  fmt.conf_win_left = win_l; fmt.conf_win_right = win_r; fmt.conf_win_top = win_t; fmt.conf_win_bottom = win_b;
   const size_t src_frame_bytes = use_fmt ? hevcdl_source_frame_bytes(&fmt) : frame_bytes, out_frame_bytes = use_fmt ? hevcdl_output_frame_bytes(&fmt) : frame_bytes;      // a frame of the input file / of the reconstruction file
   if (src_frame_bytes == 0) { fprintf(stderr, "Error: unsupported source size / bit depths\n"); return 2; }
   FILE *fin = fopen(input.c_str(), "rb");
@@ -326,6 +359,7 @@ int main(int argc, char **argv)
   const long avail = (long)(fsize / (long long)src_frame_bytes) - frame_skip;
   if (avail <= 0) { fprintf(stderr, "Error: input holds no frame after FrameSkip\n"); return 2; }
   if (n_frames <= 0 || n_frames > avail) n_frames = avail;                    // TAppEncTop: stops at end of file
+  n_frames = (n_frames + ts_ratio - 1) / ts_ratio;                            // source frames -> pictures: picture k is source frame FrameSkip + k * ratio; POCs are consecutive
   // Devices.  --Device d (default 0): one device.  --Devices 0-7 | 0,2,5 | --NumDevices N: the frames of the job in contiguous blocks, one block, one host thread and
   // one context per entry (the app loop of TAppEncTop.cpp:568-691 once per block; -fs / -f of TAppEncCfg.cpp:786,788 are what a block is); an entry may repeat a
   // device (two contexts share it: the contexts then never wait on each other, HEVCDL_EXEC_NO_UNIT_HANDOVER).
@@ -442,7 +476,13 @@ int main(int argc, char **argv)
   const double t_setup = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_main0).count();      // options, weights, contexts, the decision kernel's workspace
   const int chunk = (int)std::max<long>(1, std::min<long>(batch, opt.geti("ChunkFrames", 48)));
 
-  if (use_fmt) printf("Source %dx%d at %d bits -> coded %dx%d at %d bits (conformance window right %d, bottom %d), output at %d bits\n", src_w, src_h, in_bd, width, height, bit_depth, width - src_w, height - src_h, out_bd);
+  if (conf_mode == 3 && !(win_l | win_r | win_t | win_b)) fprintf(stderr, "Warning: Conformance window enabled, but all conformance window parameters set to zero\n");
+  if (conf_mode == 3 && (pad_x || pad_y)) fprintf(stderr, "Warning: Conformance window enabled, padding parameters will be ignored\n");
+  if (use_fmt) printf("Source %dx%d at %d bits -> coded %dx%d at %d bits (conformance window right %d, bottom %d), output at %d bits\n", src_w, src_h, in_bd, width, height, bit_depth, conf_mode == 3 ? win_r : width - src_w, conf_mode == 3 ? win_b : height - src_h, out_bd);
+  if (in_cf != 420 || colour_space || conf_mode == 3 || ts_ratio > 1) { // TAppEncTop::printChromaFormat, and what else of the file's layout is in force
+    printf("%43s  4:%c:%c\n%43s  4:2:0\n\n", "Input ChromaFormatIDC = ", in_cf == 400 ? '0' : (in_cf == 444 ? '4' : '2'), in_cf == 400 ? '0' : (in_cf == 420 ? '0' : (in_cf == 422 ? '2' : '4')), "Output (internal) ChromaFormatIDC = ");
+    printf("File layout: colour space %s, window left %d right %d top %d bottom %d, every %ld. source frame\n", colour_space ? "YCbCrtoYCrCb" : "UNCHANGED", win_l, win_r, win_t, win_b, ts_ratio);
+  }
   printf("HEVC-DL MI355X path: %dx%d  QP %d  frames %ld (skip %ld)  batch %d  labels: %s\n", width, height, qp, n_frames, frame_skip, batch,
          label_dir.empty() ? (cnn_input == "luma" ? "on-device CNN (luma input)" : "on-device CNN (BT.601 RGB input)") : ("files under " + label_dir).c_str());
   if (multi) {
@@ -466,6 +506,7 @@ int main(int argc, char **argv)
   scfg.tools = cfg.tools; scfg.lf_beta_offset_div2 = cfg.lf_beta_offset_div2; scfg.lf_tc_offset_div2 = cfg.lf_tc_offset_div2; scfg.loop_filter_disable = deblock ? 0 : 1;
   scfg.lf_across_tiles = cfg.lf_across_tiles; scfg.tile_uniform_spacing = cfg.tile_uniform_spacing; memcpy(scfg.tile_column_width, cfg.tile_column_width, sizeof scfg.tile_column_width); memcpy(scfg.tile_row_height, cfg.tile_row_height, sizeof scfg.tile_row_height);
   scfg.conf_win_right = width - src_w; scfg.conf_win_bottom = height - src_h;
+  if (conf_mode == 3) { scfg.conf_win_left = win_l; scfg.conf_win_right = win_r; scfg.conf_win_top = win_t; scfg.conf_win_bottom = win_b; }      // PSNR, the hash and the digests stay over the whole coded picture (no padding: m_aiPad is 0)
   const double ny = (double)src_w * src_h, nc = ny / 4;      // PSNR, MSE and MS-SSIM are taken over the picture without the padding (TEncGOP.cpp:2302-2303, 2375-2376)
   double sum_bits = 0, sum_psnr[3] = { 0, 0, 0 }, sum_mse[3] = { 0, 0, 0 }, sum_msssim[3] = { 0, 0, 0 }; long done = 0;
   auto now = [] { return std::chrono::steady_clock::now(); };
@@ -532,12 +573,15 @@ int main(int argc, char **argv)
             if (slice_data && buf.size() < slice_at[(size_t)i + 1] - slice_at[(size_t)i] + 4096) buf.resize(2 * (slice_at[(size_t)i + 1] - slice_at[(size_t)i]) + 4096);
             PicOut &po = pics[i]; po.md5_text[0] = 0;
             for (int c = 0; c < 3; c++) po.sse[c] = stats[i].sse[c];
-            if (deblock && device_report) { for (int c = 0; c < 3; c++) po.sse[c] = reports[i].sse[c]; }      // of the filtered picture, from the device
+            bool coded_order = true;                                           // which plane order po.sse is in (the log wants the file's with YCbCrtoYCrCb, unless SNRInternalColourSpace)
+            if (deblock && device_report) { for (int c = 0; c < 3; c++) po.sse[c] = reports[i].sse[c]; coded_order = false; }      // of the filtered picture, from the device
             else if (deblock && recon && use_fmt) { // the same over the window: original and output picture at the internal depth, by the library's host functions
-              hevcdl_source_format wf = fmt; wf.output_bit_depth = bit_depth;
+              // (the original through the file's layout, without the explicit window; the output picture minus the padding, in the coded plane order)
+              hevcdl_source_format lf = fmt; lf.output_bit_depth = bit_depth; lf.conf_win_left = lf.conf_win_right = lf.conf_win_top = lf.conf_win_bottom = 0;
+              hevcdl_source_format wf = lf; wf.chroma_format = 0; wf.colour_space = 0;
               const size_t wn[3] = { (size_t)src_w * src_h, (size_t)src_w * src_h / 4, (size_t)src_w * src_h / 4 }, wtot = wn[0] + wn[1] + wn[2], ws = bit_depth > 8 ? 2 : 1;
               std::vector<uint8_t> ow(wtot * ws), rw(wtot * ws);
-              if (hevcdl_load_source_host(&wf, src_w, src_h, bit_depth, cc.yuv + src_frame_bytes * (size_t)(first + i), 1, ow.data()) != HEVCDL_OK ||
+              if (hevcdl_load_source_host(&lf, src_w, src_h, bit_depth, cc.yuv + src_frame_bytes * (size_t)(first + i), 1, ow.data()) != HEVCDL_OK ||
                   hevcdl_store_output_host(&wf, width, height, bit_depth, recon + frame_bytes * (size_t)i, 1, rw.data()) != HEVCDL_OK) { po.st = HEVCDL_ERR_INVALID_ARG; continue; }
               size_t off = 0;
               for (int c = 0; c < 3; c++) {
@@ -562,6 +606,7 @@ int main(int argc, char **argv)
                 po.sse[c] = sse; off += n[c];
               }
             }
+            if (file_order && coded_order) std::swap(po.sse[1], po.sse[2]);
             // the access unit: VPS+SPS+PPS+slice, written to -b; its size is the picture's bit count (TEncGOP.cpp:2420-2447)
             if (slice_data) po.st = hevcdl_write_access_unit_from_slice_data(&scfg, (int)(cc.f0 + first + i), slice_data + slice_at[(size_t)i], slice_sizes + (size_t)i * n_sub, n_sub, buf.data(), buf.size(), &po.au_len);
             else po.st = hevcdl_write_access_unit(&scfg, (int)(cc.f0 + first + i), recs + (size_t)ctus * i, sao ? sao_params + (size_t)ctus * i : nullptr, buf.data(), buf.size(), &po.au_len);
@@ -623,8 +668,13 @@ int main(int argc, char **argv)
     for (long bi = 0; bi < n_batches && S.rc == 0; bi++) {
       const long f0 = S.f_lo + bi * (long)sb; const int nb = (int)std::min<long>(sb, S.f_hi - f0);
       const auto tr0 = now();
-      fseeko(fi, (off_t)((frame_skip + f0) * (long long)src_frame_bytes), SEEK_SET);
-      if (fread(yuv_mem.data(), src_frame_bytes, nb, fi) != (size_t)nb) { fprintf(stderr, "Error: short read of '%s'\n", input.c_str()); S.rc = 2; break; }
+      bool short_read = false;
+      if (ts_ratio == 1) { fseeko(fi, (off_t)((frame_skip + f0) * (long long)src_frame_bytes), SEEK_SET); short_read = fread(yuv_mem.data(), src_frame_bytes, nb, fi) != (size_t)nb; }
+      else for (int i = 0; i < nb && !short_read; i++) { // TemporalSubsampleRatio: picture f0 + i is source frame FrameSkip + (f0 + i) * ratio
+        fseeko(fi, (off_t)((frame_skip + (f0 + i) * ts_ratio) * (long long)src_frame_bytes), SEEK_SET);
+        short_read = fread(yuv_mem.data() + src_frame_bytes * (size_t)i, src_frame_bytes, 1, fi) != 1;
+      }
+      if (short_read) { fprintf(stderr, "Error: short read of '%s'\n", input.c_str()); S.rc = 2; break; }
       const uint8_t *lab = nullptr;
       if (!label_dir.empty()) {
         for (int i = 0; i < nb && S.rc == 0; i++) for (int a = 0; a < ctus; a++) {
@@ -690,12 +740,12 @@ int main(int argc, char **argv)
     const double psnr_yuv = mse_yuv == 0 ? 999.99 : 10.0 * log10((double)(255 << (bit_depth - 8)) * (double)(255 << (bit_depth - 8)) / mse_yuv);
     if (!print_msssim && !print_seq_mse) {
       printf("\tTotal Frames |   Bitrate     Y-PSNR    U-PSNR    V-PSNR    YUV-PSNR  \n");
-      printf("\t %8ld    %c %12.4lf  %8.4lf  %8.4lf  %8.4lf  %8.4lf  \n", done, 'a', sum_bits * (fps / 1000.0 / done), sum_psnr[0] / done, sum_psnr[1] / done, sum_psnr[2] / done, psnr_yuv);
+      printf("\t %8ld    %c %12.4lf  %8.4lf  %8.4lf  %8.4lf  %8.4lf  \n", done, 'a', sum_bits * (fps / (double)ts_ratio / 1000.0 / done), sum_psnr[0] / done, sum_psnr[1] / done, sum_psnr[2] / done, psnr_yuv);
     } else { // the extra columns of TEncAnalyze.h:315-388
       printf("\tTotal Frames |   Bitrate     Y-PSNR    U-PSNR    V-PSNR    YUV-PSNR  ");
       if (print_msssim) printf("  Y-MS-SSIM    U-MS-SSIM    V-MS-SSIM  ");
       printf(print_seq_mse ? "  Y-MSE     U-MSE     V-MSE     YUV-MSE  \n" : "\n");
-      printf("\t %8ld    %c %12.4lf  %8.4lf  %8.4lf  %8.4lf  %8.4lf  ", done, 'a', sum_bits * (fps / 1000.0 / done), sum_psnr[0] / done, sum_psnr[1] / done, sum_psnr[2] / done, psnr_yuv);
+      printf("\t %8ld    %c %12.4lf  %8.4lf  %8.4lf  %8.4lf  %8.4lf  ", done, 'a', sum_bits * (fps / (double)ts_ratio / 1000.0 / done), sum_psnr[0] / done, sum_psnr[1] / done, sum_psnr[2] / done, psnr_yuv);
       if (print_msssim) printf("   %8.6lf     %8.6lf     %8.6lf  ", sum_msssim[0] / (double)done, sum_msssim[1] / (double)done, sum_msssim[2] / (double)done);
       if (print_seq_mse) { // MSEyuv as calculateCombinedValues adds it up (TEncAnalyze.h:180-194)
         double acc = 0; acc += 4 * (sum_mse[0] / (double)done); acc += 1 * (sum_mse[1] / (double)done); acc += 1 * (sum_mse[2] / (double)done);

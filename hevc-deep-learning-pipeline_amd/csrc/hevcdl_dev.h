@@ -183,6 +183,13 @@ struct hevcdl_source_params {
   int n_pics;
   int rows_per_group;              // set by the launcher
 };
+// The same with the file's layout (csrc/source_core.h plane_ref): a block of its own, so that the 4:2:0 kernels above keep the parameters -- and the code -- they had.
+// Load: the SOURCE is chroma_format (400 / 422 / 444 / 420), swap reads file plane 2 into coded plane 1 and the other way round; win_x / win_y are 0.
+// Store: the source is a coded 4:2:0 picture (chroma_format 420); b.dst_w x b.dst_h is the window whose origin is (win_x, win_y) luma samples (even); swap as above.
+struct hevcdl_source_fmt_params {
+  struct hevcdl_source_params b;
+  int chroma_format, swap, win_x, win_y;
+};
 
 // slice data on the device (entropy_kernel.hip): one wave per sub-stream
 struct hevcdl_entropy_params {
@@ -268,6 +275,14 @@ void hevcdl_launch_quality_sse(const struct hevcdl_quality_params *p, void *stre
 void hevcdl_launch_report(const struct hevcdl_report_params *p, void *stream, void **events_opt);
 void hevcdl_launch_source_load(const struct hevcdl_source_params *p, void *stream);       // source_kernel.hip: hevcdl_source_load_kernel<IN, PEL> by src_bytes / dst_bytes
 void hevcdl_launch_source_store(const struct hevcdl_source_params *p, void *stream);      // hevcdl_source_store_kernel<PEL, OUT>
+void hevcdl_launch_source_load_fmt(const struct hevcdl_source_fmt_params *p, void *stream);       // hevcdl_source_load_fmt_kernel<IN, PEL>: 4:0:0 / 4:2:2 / 4:4:4 files, swapped chroma
+void hevcdl_launch_source_store_fmt(const struct hevcdl_source_fmt_params *p, void *stream);      // hevcdl_source_store_fmt_kernel<PEL, OUT>: a window with an origin, swapped chroma
+// hevcdl_bitstream.cpp: the rules of a hevcdl_source_format, once for the host functions and the context -- fits a coded size (1 / 0); no field of the file's layout set (1 / 0);
+// the output frame's luma size
+struct hevcdl_source_format;
+int hevcdl_source_format_fits(const struct hevcdl_source_format *fmt, int coded_width, int coded_height);
+int hevcdl_source_format_plain(const struct hevcdl_source_format *fmt);
+void hevcdl_source_window_size(const struct hevcdl_source_format *fmt, int *ww, int *wh);
 // hevcdl_bitstream.cpp: the packed sub-streams of one picture by the host writer (fallback of the device entropy coder); 0, or -1 when `capacity` is too small
 int hevcdl_host_writer_slice_data(const struct hevcdl_stream_config *cfg, const struct hevcdl_ctu_record *records, const struct hevcdl_sao_blk *sao, uint8_t *out, size_t capacity,
                                   uint32_t *sizes, size_t *total);

@@ -28,10 +28,11 @@ def _pool():
     return _POOL
 
 
-def read_frames(path, width, height, first, count, bit_depth=8):
-    """Planar 4:2:0 frames [count, w*h*3/2] (uint8, or uint16 little endian for bit_depth 10) starting at frame `first`."""
+def read_frames(path, width, height, first, count, bit_depth=8, frame_samples=None):
+    """Planar 4:2:0 frames [count, w*h*3/2] (uint8, or uint16 little endian for bit_depth 10) starting at frame `first`.  frame_samples: the samples of a frame of
+    another file format (SourceFormat.source_samples)."""
     dt = np.uint8 if bit_depth == 8 else np.dtype("<u2")
-    n = width * height * 3 // 2
+    n = frame_samples or width * height * 3 // 2
     with open(path, "rb") as f:
         f.seek(first * n * (1 if bit_depth == 8 else 2))
         a = np.fromfile(f, dt, n * count)
@@ -54,7 +55,8 @@ def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None
     Encoder.encode_pictures_stream(want_pictures=False).  Stream, reconstruction file and rows are the same either way.
     source_format (hevcdl_amd.source_format(...)): the file holds frames of that size and input depth, not of the codec's format; width / height / bit_depth stay the
     CODED size (hevcdl_amd.padded_size) and the internal depth.  The frames go to the device as they are (Encoder.set_source_format), the SPS carries the window, the
-    rows' squared errors are the window's and the reconstruction file holds window-sized frames at the format's output depth."""
+    rows' squared errors are the window's and the reconstruction file holds window-sized frames at the format's output depth.  The format also carries the file's layout:
+    a 4:0:0 / 4:2:2 / 4:4:4 file, Cr stored before Cb, an explicit window (its offsets go into the SPS; the squared errors then stay those of the whole picture)."""
     import torch
     import torch.distributed as dist
     multi = dist.is_available() and dist.is_initialized()
@@ -72,9 +74,15 @@ def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None
         sf = source_format
         sw, sh = (sf.source_width, sf.source_height) if sf is not None else (width, height)
         conf_win = (width - sw, height - sh)
+        file_order = False
         if sf is not None:
             enc.set_source_format(sf)
-            wf = make_source_format(sw, sh, sf.input_bit_depth, bit_depth)      # the window at the internal depth: what the squared errors are taken over
+            if sf.conf_win_left or sf.conf_win_right or sf.conf_win_top or sf.conf_win_bottom:      # an explicit window: no padding, all four offsets in the SPS
+                conf_win = (sf.conf_win_left, sf.conf_win_right, sf.conf_win_top, sf.conf_win_bottom)
+            # what the squared errors are taken over, at the internal depth: the coded picture minus the padding, in the coded plane order
+            lf = make_source_format(sw, sh, sf.input_bit_depth, bit_depth, chroma_format=sf.chroma_format, colour_space=sf.colour_space)
+            wf = make_source_format(sw, sh, bit_depth, bit_depth)
+            file_order = bool(sf.colour_space and not sf.snr_internal_colour_space)      # the U and V columns in the file's order
         ysz = sw * sh
         scfg = None
         if device_entropy:
@@ -85,7 +93,7 @@ def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None
         stream_only = device_report and device_entropy and not recon_path      # no picture, record or SAO parameter is copied to the host
         for b0 in range(mine.start, mine.stop, batch):
             nb = min(batch, mine.stop - b0)
-            yuv = read_frames(input_path, sw, sh, frame_skip + b0, nb, sf.input_bit_depth if sf is not None else bit_depth)
+            yuv = read_frames(input_path, sw, sh, frame_skip + b0, nb, sf.input_bit_depth if sf is not None else bit_depth, sf.source_samples if sf is not None else None)
             t0 = time.time()
             labels = labels_fn(b0, nb) if labels_fn else None
             if stream_only:
@@ -105,10 +113,11 @@ def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None
                     return au, digest_sei(1, report_digest(reports[i])) if hash_sei else b"", [int(v) for v in reports[i]["sse"]]
                 sei = picture_hash_sei(width, height, final[i], bit_depth) if hash_sei else b""
                 if sf is not None:
-                    d = (load_source_host(wf, sw, sh, bit_depth, yuv[i:i + 1])[0].astype(np.int64) - store_output_host(wf, width, height, bit_depth, final[i:i + 1])[0].astype(np.int64)) ** 2
+                    d = (load_source_host(lf, sw, sh, bit_depth, yuv[i:i + 1])[0].astype(np.int64) - store_output_host(wf, width, height, bit_depth, final[i:i + 1])[0].astype(np.int64)) ** 2
                 else:
                     d = (yuv[i].astype(np.int64) - final[i].astype(np.int64)) ** 2
-                return au, sei, [int(d[:ysz].sum()), int(d[ysz:ysz + ysz // 4].sum()), int(d[ysz + ysz // 4:].sum())]
+                sse = [int(d[:ysz].sum()), int(d[ysz:ysz + ysz // 4].sum()), int(d[ysz + ysz // 4:].sum())]
+                return au, sei, [sse[0], sse[2], sse[1]] if file_order else sse
             for i, (au, sei, sse) in enumerate(_pool().map(one_picture, range(nb))):
                 poc = b0 + i
                 if fb:

@@ -332,12 +332,26 @@ typedef struct hevcdl_source_format {
   uint32_t struct_size;          /* sizeof(hevcdl_source_format) */
   int32_t  source_width, source_height;      /* luma samples, even, >= 2 */
   int32_t  input_bit_depth, output_bit_depth;      /* 8 .. 16 */
+  /* The file's layout; zero in every field below is a planar 4:2:0 file with Cb before Cr and no explicit window.  The CODED picture is 4:2:0 whatever the file is. */
+  int32_t  chroma_format;        /* InputChromaFormat: 400 / 420 / 422 / 444 (0 = 420).  A frame is Y, then both chroma planes at the file's own chroma size (4:0:0: none).  A
+                                    coded chroma sample is the nearest (top-left) file sample, no filter: file_c(min(x, sw/2 - 1) << (1 - csx), min(y, sh/2 - 1) << (1 - csy)), the
+                                    clamp in coded coordinates (readPlane, TVideoIOYuv.cpp:249-384); 4:0:0: both coded chroma planes are 1 << (input_bit_depth - 1), scaled
+                                    like any sample.  Output frames are never converted back: they are 4:2:0 */
+  int32_t  colour_space;         /* InputColourSpaceConvert: 0 unchanged, 1 YCbCrtoYCrCb -- file planes 1 and 2 change places on the way in (ColourSpaceConvert, :981-1041);
+                                    not with chroma_format 400 */
+  int32_t  output_internal_colour_space;      /* OutputInternalColourSpace: 0 output frames get the two planes back in the file's order, 1 they keep the coded order */
+  int32_t  snr_internal_colour_space;         /* SNRInternalColourSpace: 0 hevcdl_get_quality / hevcdl_get_picture_report carry U and V (SSE, MS-SSIM) in the file's order,
+                                                 1 in the coded order.  Digests are always those of the coded picture */
+  int32_t  conf_win_left, conf_win_right, conf_win_top, conf_win_bottom;      /* ConformanceWindowMode 3: an explicit window in luma samples, all even, something left
+                                    of the picture.  Only without padding (source size == coded size); output frames are the window (write, :811-826), while quality, the
+                                    report and the digests stay over the WHOLE coded picture.  hevcdl_stream_config carries the same four offsets into the SPS */
 } hevcdl_source_format;
 /* the context's own size and depth: a format that changes nothing */
 hevcdl_status hevcdl_source_format_default(hevcdl_source_format *fmt, const hevcdl_config *cfg);
 /* The coded size of a source size (TAppEncCfg.cpp:1569-1617).  mode = ConformanceWindowMode: 0 no padding (a size that is no multiple of 8 is HEVCDL_ERR_INVALID_ARG),
  * 1 pad every dimension that is no multiple of the minimum CU (8) up to the next one, 2 pad by pad_x / pad_y (HorizontalPadding / VerticalPadding; the result must be a
- * multiple of 8), 3 (explicit window offsets) HEVCDL_ERR_UNSUPPORTED.  Odd padding or an odd source size is HEVCDL_ERR_INVALID_ARG (4:2:0). */
+ * multiple of 8), 3 (explicit window offsets) HEVCDL_ERR_UNSUPPORTED: that mode pads nothing, so there is no size to derive -- the coded size is the source size
+ * (a multiple of 8) and the window goes into hevcdl_source_format.conf_win_*.  Odd padding or an odd source size is HEVCDL_ERR_INVALID_ARG (4:2:0). */
 hevcdl_status hevcdl_padded_size(int source_width, int source_height, int mode, int pad_x, int pad_y, int *width, int *height);
 size_t        hevcdl_source_frame_bytes(const hevcdl_source_format *fmt);      /* one source-format frame; 0 for an invalid format */
 size_t        hevcdl_output_frame_bytes(const hevcdl_source_format *fmt);      /* one output-format frame (window size, output depth) */
@@ -346,7 +360,11 @@ size_t        hevcdl_output_frame_bytes(const hevcdl_source_format *fmt);      /
  * converts and pads them in HBM in front of the CNN and the decisions.  Records, pictures and slice data stay what they are: coded format, so every consumer keeps
  * working, and the hash SEI / the report's digests cover the whole coded picture.  hevcdl_get_quality and hevcdl_get_picture_report carry SSE and MS-SSIM of the WINDOW
  * (TEncGOP.cpp:2302-2303, 2375-2376, 2413-2414), and so does hevcdl_frame_stats.sse when the picture is padded.  The per-CTU session and the *_dev entry points take
- * coded-format input, as before.  With no format set every entry point behaves exactly as before. */
+ * coded-format input, as before.  With no format set every entry point behaves exactly as before.
+ * The file's layout (chroma_format, colour_space, conf_win_*): hevcdl_source_frame_bytes is the file's own frame (Y plus chroma planes at the file's size) and only those
+ * bytes are uploaded; hevcdl_output_frame_bytes is a 4:2:0 frame of the window.  With padding (source size < coded size) quality, report and stats cover the coded picture
+ * minus the padding, as above; with an explicit window they cover the WHOLE coded picture.  HEVCDL_ERR_INVALID_ARG: an unknown chroma_format, colour_space outside 0 / 1 or
+ * together with chroma_format 400, odd or negative window offsets, a window of no samples, window offsets together with padding. */
 hevcdl_status hevcdl_set_source_format(hevcdl_ctx *ctx, const hevcdl_source_format *fmt);
 /* source-format frames -> coded-format frames of the context (host buffers: upload, kernel, download; device buffers: asynchronous on `stream`, pointers sample aligned) */
 hevcdl_status hevcdl_load_source(hevcdl_ctx *ctx, const void *src, int n_frames, void *coded_out);
@@ -394,6 +412,8 @@ typedef struct hevcdl_stream_config {
   int32_t  conf_win_right, conf_win_bottom;   /* conformance window in LUMA samples (default 0): the right and lower padding of a picture whose source size is no multiple of
                                     the minimum CU (hevcdl_source_format); both even.  The SPS carries them in chroma units, conf_win_right_offset = right / 2
                                     (TEncCavlc.cpp:526-535); a decoder then outputs width - right by height - bottom */
+  int32_t  conf_win_left, conf_win_top;       /* the other two offsets (default 0; ConformanceWindowMode 3, hevcdl_source_format.conf_win_*): even, and something must be left
+                                    of the picture */
                                  /* (LFCrossSliceBoundaryFlag has no field: without slices -- SliceMode 0, the only mode of this path -- the reference sets it to 1 whatever the cfg
                                     says, TAppEncTop.cpp:278-281; tests/golden/stream_c192_q32.npz pins that) */
 } hevcdl_stream_config;
