@@ -962,11 +962,11 @@ class Encoder:
         self._check(self.lib.hevcdl_enable_device_entropy(self._h, int(bool(on))))
 
     def set_entropy_capacity(self, capacity_per_ctu):
-        """Test entry point (hevcdl_set_entropy_capacity): the capacity per CTU of the next enable_device_entropy(True); a small value makes the host writer code the pictures."""
+        """Test entry point (hevcdl_set_entropy_capacity): the capacity per CTU of the next enable_device_entropy(True); a small value makes the host code the pictures."""
         self._check(self.lib.hevcdl_set_entropy_capacity(self._h, int(capacity_per_ctu)))
 
     def entropy_info(self):
-        """-> (pictures of the last batch the host writer coded, HIP-event ms of [wavefront phase 1, coding, pack] -- zeros without profile_enable)."""
+        """-> (pictures of the last batch the host coded, HIP-event ms of [wavefront phase 1, coding, pack] -- zeros without profile_enable)."""
         n, ms = ctypes.c_int(0), (ctypes.c_double * 3)()
         self._check(self.lib.hevcdl_get_entropy_info(self._h, ctypes.byref(n), ms))
         return n.value, list(ms)

@@ -1,9 +1,10 @@
 // entropy_coder.h -- the arithmetic coder and the slice-data syntax of an I slice as ONE source for the host and the device.
 //
-// Plain inline functions over raw pointers and a small POD state (EcCoder): what hevcdl_bitstream.cpp's host writer does (Cabac, code_cu_tree, code_transform, code_coeff,
-// code_sao_blk; the reference: TEncBinCoderCABAC.cpp:70-446, TEncSbac.cpp:613-1720, TEncEntropy.cpp:200-398, TEncCu.cpp:1167-1271, TEncSlice.cpp:985-1170), restated so
-// that a GPU wave can run it: hevcdl_entropy_kernel (entropy_kernel.hip) and hevcdl_code_slice_data_host (hevcdl_bitstream.cpp) are the two instantiations.  The host
-// writer stays the independent yardstick: tests/test_entropy.py holds the two byte for byte against each other.
+// Plain inline functions over raw pointers and a small POD state (EcCoder), after the reference's TEncBinCoderCABAC.cpp:70-446, TEncSbac.cpp:613-1720,
+// TEncEntropy.cpp:200-398, TEncCu.cpp:1167-1271 and TEncSlice.cpp:985-1170, stated so that a GPU wave can run it.  Two instantiations: hevcdl_entropy_kernel
+// (entropy_kernel.hip) and the host's SliceCoder (hevcdl_bitstream.cpp), which is behind hevcdl_write_access_unit, hevcdl_code_slice_data_host and the fallback of the
+// device path.  There is no second coder: what this one writes is held to the reference encoder's streams (tests/golden/rd_*.npz), to the test suite's spec-level
+// slice-data decoder and to the streams recorded from the former host writer before it went (tests/golden/entropy_host_writer_digests.json).
 //
 // Construction rules (they are what makes a GPU fault an implausible outcome of garbage input):
 //   * no recursion: the CU quadtree and the transform tree are walked iteratively in z-order; the flags of a node (split flag; subdivision flag and chroma cbf flags) are
@@ -11,8 +12,8 @@
 //   * no dynamic allocation, no std:: containers, no function pointers;
 //   * every loop has a bound that does not depend on record contents (256 partitions, 4 + 5 tree levels, 64 coefficient groups, 16 positions, 32 escape bits, the
 //     sub-stream's capacity);
-//   * every index into a record's arrays is masked (z & 255, coefficient offsets & 4095 / & 1023) and every CTU address range-checked; neighbours are looked up inside the
-//     tile / picture only;
+//   * every index into a record's arrays is masked (z & 255; a transform block is moved to lie inside its coefficient array, a position in it masked to the block) and
+//     every CTU address range-checked; neighbours are looked up inside the tile / picture only;
 //   * every output byte goes through ec_put_byte, which compares the position with the sub-stream's capacity: past it, a sticky flag is set and the bytes are counted,
 //     not stored.
 #ifndef HEVCDL_ENTROPY_CODER_H
@@ -193,9 +194,9 @@ EC_FN void ec_get_cparam(const EcTables *t, EcCParam &cp, int c, int log2n, int 
   else cp.first_sig_ctx = cp.ch ? 12 : 21;
   cp.scan = t->scan[cp.scan_type][cp.log2 - 2]; cp.scan_cg = t->scan_cg[cp.scan_type][cp.log2 - 2];
 }
-EC_FN int ec_sig_ctx_inc(const EcTables *t, const EcCParam &cp, int pat, int scan_pos)
-{ // TComTrQuant.cpp:2707-2803
-  const int raster = cp.scan[scan_pos & 1023], py = raster >> cp.log2, px = raster - (py << cp.log2);
+EC_FN int ec_sig_ctx_inc(const EcTables *t, const EcCParam &cp, int pat, int raster)
+{ // TComTrQuant.cpp:2707-2803; raster: the level's position in the block
+  const int py = raster >> cp.log2, px = raster - (py << cp.log2);
   if (px + py == 0) return 0;
   int offset;
   if (cp.log2 == 2) offset = t->ctx_ind_map_4x4[(4 * py + px) & 15];
@@ -209,8 +210,8 @@ EC_FN int ec_sig_ctx_inc(const EcTables *t, const EcCParam &cp, int pat, int sca
   }
   return cp.first_sig_ctx + offset;
 }
-// plane: the record's coefficient array of the component, base: first coefficient of the block, mask: 4095 (luma) / 1023 (chroma) -- a block of a valid record never
-// wraps, a block of a garbage record stays inside the array
+// plane: the record's coefficient array of the component, base: first coefficient of the block, mask: 4095 (luma) / 1023 (chroma), the array's size - 1 -- a block
+// of a valid record lies inside the array, a block of a garbage record is moved there
 EC_FN void ec_code_coeff(EcCoder &s, uint32_t tools, const int16_t *plane, int base, int mask, int comp, int log2n, int dir_mode, int tskip_flag)
 {
   const EcTables *t = s.t;
@@ -218,13 +219,20 @@ EC_FN void ec_code_coeff(EcCoder &s, uint32_t tools, const int16_t *plane, int b
   EcCParam cp; ec_get_cparam(t, cp, comp, log2n, dir_mode);
   log2n = cp.log2;
   const int n = cp.n, nn = n * n;
-#define EC_COEF(i) ((int)plane[(base + (int)(i)) & mask])
-  // coefficient groups that hold a level, and the last level in scan order (the host writer walks the scan up to the last level; what it marks is the same set)
-  uint64_t cgf = 0; int scan_last = -1;
-  for (int g = 0; g < cp.wg * cp.wg; g++) {
-    const int cgblk = cp.scan_cg[g] & 63;
-    for (int q = 0; q < 16; q++) if (EC_COEF(cp.scan[g * 16 + q] & (nn - 1)) != 0) { cgf |= 1ull << cgblk; scan_last = g * 16 + q; }
+  if (base + nn > mask + 1) base = mask + 1 - nn;
+  const int16_t *coef = plane + base;            // n x n levels inside the array; base is a multiple of 4 levels, so a group's row of four is one aligned 8-byte word
+#define EC_COEF(i) ((int)coef[(i) & (nn - 1)])
+  // coefficient groups that hold a level, and how many levels the block holds: one pass over the block's rows, the four levels of a group's row at a time (bit 15 of
+  // a 16-bit lane of `lanes` is set where the lane is not zero).  Then the last level in scan order: up the scan until all levels are seen -- no further than the
+  // coding loop below comes down again, and a block of content ends early in its scan.
+  uint64_t cgf = 0; int scan_last = -1, num_sig = 0;
+  for (int y = 0; y < n; y++) for (int gx = 0; gx < cp.wg; gx++) {
+    uint64_t four; __builtin_memcpy(&four, coef + y * n + 4 * gx, 8);
+    if (!four) continue;
+    const uint64_t lanes = (((four & 0x7fff7fff7fff7fffull) + 0x7fff7fff7fff7fffull) | four) & 0x8000800080008000ull;
+    cgf |= 1ull << ((y >> 2) * cp.wg + gx); num_sig += __builtin_popcountll(lanes);
   }
+  for (int q = 0; q < nn && num_sig > 0; q++) if (EC_COEF(cp.scan[q]) != 0) { scan_last = q; num_sig--; }
   if (scan_last < 0) return;
   const int pos_last = cp.scan[scan_last] & (nn - 1);
   if (n == 4 && (tools & HEVCDL_TOOL_TSKIP)) ec_bin(s, CTX_TSKIP + ch, tskip_flag != 0);      // transform_skip_flag only with transform_skip_enabled_flag (TEncSbac.cpp:1007)
@@ -249,15 +257,15 @@ EC_FN void ec_code_coeff(EcCoder &s, uint32_t tools, const int16_t *plane, int b
     int num_nz = 0, go_rice = 0; const int sub_pos = subset << 4;
     int last_nz = -1, first_nz = 16; uint32_t signs = 0;
     if (sp == scan_last) { const int v = EC_COEF(pos_last); s.absb[0] = (uint16_t)ec_abs(v); num_nz = 1; last_nz = sp; first_nz = sp; signs = v < 0; sp--; }
-    const int cgblk = cp.scan_cg[subset] & 63, gy = cgblk / cp.wg, gx = cgblk - gy * cp.wg;
+    const int cgblk = cp.scan_cg[subset] & 63, gy = cgblk >> (log2n - 2), gx = cgblk & (cp.wg - 1);
     const int right = (gx < cp.wg - 1) ? (int)((cgf >> (gy * cp.wg + gx + 1)) & 1) : 0, lower = (gy < cp.wg - 1) ? (int)((cgf >> ((gy + 1) * cp.wg + gx)) & 1) : 0;
     if (subset == last_set || subset == 0) cgf |= 1ull << cgblk;
     else ec_bin(s, cg_off + ((right + lower) != 0), (int)((cgf >> cgblk) & 1));
     if ((cgf >> cgblk) & 1) {
       const int pat = cp.wg <= 1 ? 0 : right + (lower << 1);
       for (int q = 0; q < 16 && sp >= sub_pos; q++, sp--) {
-        const int v = EC_COEF(cp.scan[sp] & (nn - 1)), sig = v != 0;
-        if (sp > sub_pos || subset == 0 || num_nz) ec_bin(s, sig_off + ec_sig_ctx_inc(t, cp, pat, sp), sig);
+        const int raster = cp.scan[sp] & (nn - 1), v = EC_COEF(raster), sig = v != 0;
+        if (sp > sub_pos || subset == 0 || num_nz) ec_bin(s, sig_off + ec_sig_ctx_inc(t, cp, pat, raster), sig);
         if (sig) { s.absb[num_nz & 15] = (uint16_t)ec_abs(v); num_nz++; signs = 2 * signs + (v < 0); if (last_nz == -1) last_nz = sp; first_nz = sp; }
       }
     } else sp = sub_pos - 1;

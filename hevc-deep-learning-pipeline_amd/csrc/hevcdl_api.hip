@@ -109,7 +109,7 @@ struct Entropy {
   DevBuf<uint32_t> d_ec_off, d_ec_cap, d_ec_sizes, d_ec_ovf; DevBuf<unsigned long long> d_ec_dst;
   std::vector<uint32_t> ec_off, ec_cap;
   std::vector<uint8_t> h_slice; std::vector<uint32_t> h_slice_sizes; std::vector<size_t> h_slice_at;      // the last batch: packed sub-streams, [picture][unit] lengths, start of every picture (+ the end)
-  int ec_fallbacks = 0;                    // pictures of the last batch the host writer coded (a sub-stream overflowed its region)
+  int ec_fallbacks = 0;                    // pictures of the last batch the host coded (a sub-stream overflowed its region)
 };
 // source format (source_kernel.hip): everything below is allocated by hevcdl_set_source_format(ctx, fmt) and freed by (ctx, NULL); a context without one allocates
 // and launches none of it.  d_src: max_frames frames of the larger of the source and the output format (the picture pipeline's upload; staging of the host entry
@@ -1619,7 +1619,7 @@ static hevcdl_status entropy_pipeline(hevcdl_ctx *ctx, int n_frames, int want_sa
     }
   }
   ctx->ec.h_slice_at[(size_t)n_frames] = ctx->ec.h_slice.size();
-  if (!fallback.empty()) { // a sub-stream did not fit its region: the host writer codes those pictures (their records only), and the batch is put together again in picture order
+  if (!fallback.empty()) { // a sub-stream did not fit its region: the host codes those pictures (their records only; a first call sizes, a second writes), and the batch is put together again in picture order
     std::vector<uint8_t> all; std::vector<size_t> at((size_t)n_frames + 1, 0);
     std::vector<hevcdl_ctu_record> rec((size_t)ctx->ctus); std::vector<hevcdl_sao_blk> sao(want_sao ? (size_t)ctx->ctus : 0);
     size_t fb = 0;

@@ -552,7 +552,7 @@ int main(int argc, char **argv)
     struct ChunkCtx { long f0; double et; const uint8_t *yuv; std::chrono::steady_clock::time_point t0; int nb; } cc = { 0, 0.0, nullptr, now(), 1 };
     // (with a source format the reconstruction file's frames are made on the device from the pictures in HBM: hevcdl_get_output_frames)
     const bool want_pictures = device_report ? (frec != nullptr && !use_fmt) : (frec || hash_sei || deblock), want_records = frecords != nullptr;      // what a DeviceEntropy run still fetches from HBM
-    // slice_data / slice_sizes / n_sub: the packed sub-streams of the chunk's pictures (DeviceEntropy), or null: the host writer codes the records
+    // slice_data / slice_sizes / n_sub: the packed sub-streams of the chunk's pictures (DeviceEntropy), or null: the host codes the records (hevcdl_write_access_unit)
     auto on_chunk = [&](int first, int count, const hevcdl_ctu_record *recs, const void *pictures, const hevcdl_sao_blk *sao_params, const hevcdl_frame_stats *stats,
                         const uint8_t *slice_data, const uint32_t *slice_sizes, int n_sub) -> int {
       const auto th0 = now();

@@ -283,7 +283,8 @@ struct hevcdl_source_format;
 int hevcdl_source_format_fits(const struct hevcdl_source_format *fmt, int coded_width, int coded_height);
 int hevcdl_source_format_plain(const struct hevcdl_source_format *fmt);
 void hevcdl_source_window_size(const struct hevcdl_source_format *fmt, int *ww, int *wh);
-// hevcdl_bitstream.cpp: the packed sub-streams of one picture by the host writer (fallback of the device entropy coder); 0, or -1 when `capacity` is too small
+// hevcdl_bitstream.cpp: the packed sub-streams of one picture, coded on the host by the coder the device runs (entropy_coder.h) with all the room it asks for -- the
+// fallback for a picture whose sub-stream overflowed its region on the device; 0, or -1 when `capacity` is too small or `out` is null (sizes and *total are set either way)
 int hevcdl_host_writer_slice_data(const struct hevcdl_stream_config *cfg, const struct hevcdl_ctu_record *records, const struct hevcdl_sao_blk *sao, uint8_t *out, size_t capacity,
                                   uint32_t *sizes, size_t *total);
 void hevcdl_launch_entropy(const struct hevcdl_entropy_params *p, void *stream, void *mid_event_opt);      // one launch, or the two of the wavefront scheme; mid_event_opt (a hipEvent_t) is recorded between the two

@@ -233,7 +233,7 @@ hevcdl_status hevcdl_encode_pictures_chunked(hevcdl_ctx *ctx, const void *yuv, i
  * HEVCDL_ERR_INVALID_ARG.
  * hevcdl_get_slice_data: the packed sub-streams of pictures [first, first + count) of the LAST such call (valid inside the chunk callback and until the next call):
  * *data, the lengths (*sizes)[count][*n_substreams_per_picture]; picture by picture they feed hevcdl_write_access_unit_from_slice_data.  A picture with a sub-stream that
- * did not fit its region (capacity: 40 960 bytes per CTU + 64) is coded by the host writer from its records instead; the caller sees no difference. */
+ * did not fit its region (capacity: 40 960 bytes per CTU + 64) is coded on the host from its records instead, by the same coder source (csrc/entropy_coder.h); the caller sees no difference. */
 hevcdl_status hevcdl_enable_device_entropy(hevcdl_ctx *ctx, int on);
 hevcdl_status hevcdl_get_slice_data(hevcdl_ctx *ctx, int first, int count, const uint8_t **data, const uint32_t **sizes, int *n_substreams_per_picture);
 /* The picture pipeline for a caller that writes the stream from slice data: as hevcdl_encode_pictures_chunked, but the callback gets the slice data of the chunk (as
@@ -246,9 +246,9 @@ hevcdl_status hevcdl_encode_pictures_stream(hevcdl_ctx *ctx, const void *yuv, in
                                             int want_pictures, int want_records, int chunk_frames, hevcdl_stream_fn fn, void *user);
 /* TEST AND DIAGNOSTIC entry points of the switch.
  * hevcdl_set_entropy_capacity: the capacity per CTU the NEXT hevcdl_enable_device_entropy(ctx, 1) lays its sub-stream regions out with (<= 0: the default; otherwise a
- * multiple of 4).  A small value makes sub-streams overflow, so that the host writer codes those pictures: that is what it is for.  HEVCDL_ERR_INVALID_ARG while the
+ * multiple of 4).  A small value makes sub-streams overflow, so that the host codes those pictures: that is what it is for.  HEVCDL_ERR_INVALID_ARG while the
  * switch is on.
- * hevcdl_get_entropy_info: about the last hevcdl_encode_pictures* call with the switch on -- *fallbacks_opt: pictures the host writer coded; kernel_ms_opt[3]: HIP-event
+ * hevcdl_get_entropy_info: about the last hevcdl_encode_pictures* call with the switch on -- *fallbacks_opt: pictures the host coded; kernel_ms_opt[3]: HIP-event
  * times of the wavefront phase-1 launch (0 without wavefront), the coding launch and the pack launch, summed over the passes; measured only with
  * hevcdl_profile_enable(ctx, 1), zeros otherwise. */
 hevcdl_status hevcdl_set_entropy_capacity(hevcdl_ctx *ctx, int capacity_per_ctu);
@@ -420,7 +420,8 @@ typedef struct hevcdl_stream_config {
 hevcdl_status hevcdl_stream_config_default(hevcdl_stream_config *cfg, int width, int height, int qp);
 size_t        hevcdl_access_unit_bound(int width, int height);
 /* records: the [ctus] records of picture `poc` (= frame index; POC lsb is 8 bits).  out_len is set even when the
- * buffer is too small (HEVCDL_ERR_INVALID_ARG), so the call can be repeated. */
+ * buffer is too small (HEVCDL_ERR_INVALID_ARG), so the call can be repeated.  The slice data is coded by csrc/entropy_coder.h, the source the
+ * device kernel compiles too: garbage records give garbage bytes, never an access outside the records. */
 hevcdl_status hevcdl_write_access_unit(const hevcdl_stream_config *cfg, int poc, const hevcdl_ctu_record *records, const hevcdl_sao_blk *sao,
                                        uint8_t *out, size_t capacity, size_t *out_len);
 
@@ -428,7 +429,7 @@ hevcdl_status hevcdl_write_access_unit(const hevcdl_stream_config *cfg, int poc,
  * The slice data of a picture is its sub-streams back to back: one per tile in raster order of the tile grid, one per CTU row with wavefront, otherwise one; each
  * is the arithmetic coder's bytes of its CTUs followed by byte_alignment().  hevcdl_write_access_unit_from_slice_data writes everything around that payload exactly as
  * hevcdl_write_access_unit does -- parameter sets, slice segment header with the entry points (counted with their emulation prevention bytes), NAL packing -- so
- * that for the same decisions the two give the same bytes.  data: the n_substreams sub-streams of picture `poc`, packed; sizes: their lengths. */
+ * that for the same decisions the two give the same bytes (the slice data of both comes from that one source).  data: the n_substreams sub-streams of picture `poc`, packed; sizes: their lengths. */
 hevcdl_status hevcdl_write_access_unit_from_slice_data(const hevcdl_stream_config *cfg, int poc, const uint8_t *data, const uint32_t *sizes, int n_substreams,
                                                        uint8_t *out, size_t capacity, size_t *out_len);
 /* TEST AND DIAGNOSTIC entry points (host buffers in and out; the picture pipeline's form is hevcdl_enable_device_entropy above).
@@ -436,7 +437,7 @@ hevcdl_status hevcdl_write_access_unit_from_slice_data(const hevcdl_stream_confi
  * capacities[k]), capacities[k] = (its CTUs) x capacity_per_ctu + 64, and the regions lie 64 bytes apart: the coder writes nothing but the regions, so a caller may keep a
  * pattern in the gaps (the tests do).  Picture i of a call starts at i x picture_bytes.  capacity_per_ctu <= 0: the default, 40 960: above the derived worst case of a CTU, 38 582 bytes (csrc/entropy_coder.h);
  * otherwise a multiple of 4 (a small value makes sub-streams overflow: that is what it is for).  offsets_opt / capacities_opt: [n_substreams], may be NULL.
- * hevcdl_code_slice_data_host: the shared coder on the CPU (no GPU needed) for n_frames pictures: records [n_frames][ctus], sao_opt [n_frames][ctus] or NULL as
+ * hevcdl_code_slice_data_host: the coder on the CPU (no GPU needed) for n_frames pictures: records [n_frames][ctus], sao_opt [n_frames][ctus] or NULL as
  * cfg->sao_enabled says, out as laid out above, sizes / overflow [n_frames][n_substreams].  A sub-stream that does not fit its region sets its overflow word; its size is
  * still the true length, and nothing outside the region is written.
  * hevcdl_code_slice_data: the same by the device kernels (csrc/entropy_kernel.hip) on `device`: uploads (the out buffer too, so that what the kernels leave untouched comes

@@ -3,6 +3,8 @@ synthetic records that no encode produces, garbage records, and the helpers that
 import ctypes
 import functools
 import glob
+import hashlib
+import json
 import os
 
 import numpy as np
@@ -42,7 +44,8 @@ def sao_case(name):
 
 
 def host_writer_stream(cfg, recs, sao=None):
-    """The existing host writer (hevcdl_write_access_unit) with a buffer that also holds pictures of maximal levels -> the frames' access units, joined."""
+    """hevcdl_write_access_unit (the host's entry from records to an access unit) with a buffer that also holds pictures of maximal levels -> the frames' access units,
+    joined."""
     import hevcdl_amd
     lib = hevcdl_amd.load_library()
     cap = cfg.width * cfg.height * 12 + (1 << 16)
@@ -56,6 +59,34 @@ def host_writer_stream(cfg, recs, sao=None):
         assert st == 0, st
         out.append(buf[:n.value].tobytes())
     return b"".join(out)
+
+
+def input_digest(cfg, recs, sao):
+    """SHA-256 of what a coder is given: stream configuration, records, SAO parameters."""
+    h = hashlib.sha256(bytes(cfg))
+    h.update(recs.tobytes())
+    if sao is not None:
+        h.update(sao.tobytes())
+    return h.hexdigest()
+
+
+def recorded_pictures():
+    """The pictures of tests/golden/entropy_host_writer_digests.json (tools/record_entropy_host_writer_digests.py): [(name, cfg, records, SAO parameters or None)]."""
+    return fuzz_corpus() + directed_pictures() + [("sao_" + name,) + sao_case(name) for name in SAO_CASES]
+
+
+@functools.lru_cache(maxsize=None)
+def _recorded():
+    with open(os.path.join(GOLD, "entropy_host_writer_digests.json")) as f:
+        return json.load(f)["pictures"]
+
+
+def assert_recorded_stream(name, cfg, recs, sao, stream):
+    """`stream` (the frames' access units, joined) is what the host writer of the recorded commit -- the second coder this project had until then -- produced for
+    the picture.  A picture that is no longer the recorded one fails as that, not as a coder difference."""
+    entry = _recorded()[name]
+    assert entry["input"] == input_digest(cfg, recs, sao), "%s is not the picture that was recorded: the corpus drifted (record again at a commit whose coder is trusted)" % name
+    assert (len(stream), hashlib.sha256(stream).hexdigest()) == (entry["bytes"], entry["stream"]), "%s: the stream differs from the recorded one" % name
 
 
 def assemble(cfg, coded):

@@ -2,11 +2,12 @@
 // compiler and -fsanitize=address,undefined, and runs it on dumped inputs.  The index arithmetic of the device kernel is this source: a wild index shows up here as a
 // sanitizer report.  Sanitizers stay on host code.
 //
-// A dump: hevcdl_stream_config, then int32 { n_frames, has_sao, capacity_per_ctu, mode }, the records, the SAO parameters.  mode 0: the coder's access units must equal the
-// host writer's (fixtures, synthetic corpus); mode 1: guard only (overflow, garbage records) -- lengths within the capacity or the overflow word set, the canaries between
-// the regions intact.  The regions of a dump share one buffer, so a store past a region shows in the canary gap behind it (AddressSanitizer does not see it); the
-// first picture of a dump with a single sub-stream (no tiles, no wavefront) is coded once more into an allocation of exactly its capacity, where such a store is also an
-// AddressSanitizer report.
+// A dump: hevcdl_stream_config, then int32 { n_frames, has_sao, capacity_per_ctu, mode }, the records, the SAO parameters.  Every dump: lengths within the capacity or the
+// overflow word set, the canaries between the regions intact; every picture through hevcdl_write_access_unit (which codes into a first-pass region and, past it, once
+// more) into an allocation of exactly its length, and, where no region overflowed, equal to hevcdl_code_slice_data_host + hevcdl_write_access_unit_from_slice_data.
+// mode 0 (fixtures, synthetic corpus): no region may overflow; mode 1: overflow and garbage records.  The regions of a dump share one buffer, so a store past a region
+// shows in the canary gap behind it (AddressSanitizer does not see it); the first picture of a dump with a single sub-stream (no tiles, no wavefront) is coded once
+// more into an allocation of exactly its capacity, where such a store is also an AddressSanitizer report.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -40,16 +41,25 @@ static int run(const char *path)
     const uint32_t sz = sizes[(size_t)fr * n_sub + k], ov = ovf[(size_t)fr * n_sub + k];
     if ((sz > cap[k]) != (ov != 0)) { printf("%s: length %u capacity %u overflow %u\n", path, sz, cap[k], ov); return 1; }
   }
-  if (mode == 0) {
-    std::vector<uint8_t> a((size_t)cfg.width * cfg.height * 12 + 65536), b(a.size()), packed;
+  { // every picture of every dump through hevcdl_write_access_unit, into an allocation of exactly the access unit's length (learnt from a first call, whose buffer is
+    // too small on purpose); where no region overflowed above, the two ways to an access unit must agree
+    std::vector<uint8_t> b((size_t)ctus * (hevcdl_ec::EC_DEFAULT_CAPACITY_PER_CTU + 128) * 2 + 65536), packed;
     for (int fr = 0; fr < n_frames; fr++) {
-      size_t na = 0, nb = 0;
+      const hevcdl_ctu_record *r = recs.data() + ctus * fr; const hevcdl_sao_blk *sp = has_sao ? sao.data() + ctus * fr : nullptr;
+      size_t na = 0, nb = 0; uint8_t none = 0; bool fits = true;
+      if (hevcdl_write_access_unit(&cfg, fr, r, sp, &none, 0, &na) != HEVCDL_ERR_INVALID_ARG || na == 0) { printf("%s: picture %d: no length from a call without room\n", path, fr); return 1; }
+      std::vector<uint8_t> a(na);
+      if (hevcdl_write_access_unit(&cfg, fr, r, sp, a.data(), a.size(), &nb) != HEVCDL_OK || nb != na) { printf("%s: picture %d: writer status\n", path, fr); return 1; }
       packed.clear();
-      for (int k = 0; k < n_sub; k++) { const uint8_t *p = out.data() + pic_bytes * fr + off[k]; packed.insert(packed.end(), p, p + sizes[(size_t)fr * n_sub + k]); }
+      for (int k = 0; k < n_sub; k++) {
+        const size_t i = (size_t)fr * n_sub + k; const uint8_t *p = out.data() + pic_bytes * fr + off[k];
+        if (ovf[i]) { fits = false; break; }
+        packed.insert(packed.end(), p, p + sizes[i]);
+      }
+      if (!fits) { if (mode == 0) { printf("%s: picture %d overflowed its region\n", path, fr); return 1; } continue; }
       packed.push_back(0);
-      if (hevcdl_write_access_unit(&cfg, fr, recs.data() + ctus * fr, has_sao ? sao.data() + ctus * fr : nullptr, a.data(), a.size(), &na) != HEVCDL_OK ||
-          hevcdl_write_access_unit_from_slice_data(&cfg, fr, packed.data(), sizes.data() + (size_t)fr * n_sub, n_sub, b.data(), b.size(), &nb) != HEVCDL_OK) { printf("%s: writer status\n", path); return 1; }
-      if (na != nb || memcmp(a.data(), b.data(), na) != 0) { printf("%s: picture %d differs from the host writer\n", path, fr); return 1; }
+      if (hevcdl_write_access_unit_from_slice_data(&cfg, fr, packed.data(), sizes.data() + (size_t)fr * n_sub, n_sub, b.data(), b.size(), &nb) != HEVCDL_OK) { printf("%s: picture %d: assembly status\n", path, fr); return 1; }
+      if (na != nb || memcmp(a.data(), b.data(), na) != 0) { printf("%s: picture %d: hevcdl_write_access_unit differs from the assembled slice data\n", path, fr); return 1; }
     }
   }
   // the first picture of a single-sub-stream dump once more, into an allocation of exactly its capacity: a store past the region is a heap-buffer-overflow report

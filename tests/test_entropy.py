@@ -1,6 +1,7 @@
-"""The shared entropy coder (csrc/entropy_coder.h) on the CPU: hevcdl_code_slice_data_host + hevcdl_write_access_unit_from_slice_data against the reference's streams
-(golden fixtures) and against the existing host writer (hevcdl_write_access_unit), byte for byte; the capacity guard; garbage records; the same under
-AddressSanitizer / UndefinedBehaviorSanitizer.  No GPU."""
+"""The entropy coder (csrc/entropy_coder.h) on the CPU: hevcdl_code_slice_data_host + hevcdl_write_access_unit_from_slice_data against the reference's streams
+(golden fixtures), against the streams recorded from the former host writer (tests/golden/entropy_host_writer_digests.json) and against hevcdl_write_access_unit, the
+other way from the same coder to an access unit, byte for byte; the capacity guard; garbage records; the same under AddressSanitizer / UndefinedBehaviorSanitizer.
+No GPU."""
 import ctypes
 import os
 import shutil
@@ -29,12 +30,15 @@ def test_fixture_streams_without_sao(path):
 def test_fixture_streams_with_sao(name, oracle_built):
     import hevcdl_amd
     cfg, recs, sao = ec.sao_case(name)
-    assert ec.assemble(cfg, hevcdl_amd.code_slice_data(cfg, recs, sao)) == ec.host_writer_stream(cfg, recs, sao)
+    stream = ec.assemble(cfg, hevcdl_amd.code_slice_data(cfg, recs, sao))
+    ec.assert_recorded_stream("sao_" + name, cfg, recs, sao, stream)
+    assert stream == ec.host_writer_stream(cfg, recs, sao)
 
 
 def test_pictures_of_maximal_levels_fit_the_default_capacity():
-    """Checked with the existing writer alone: the slice data of the all-+-32767 pictures stays below (CTUs x default capacity per CTU); the old per-CTU figure
-    (hevcdl_access_unit_bound / CTUs = 12 288) does not hold for them, which is why the default is the derived 40 960 (csrc/entropy_coder.h)."""
+    """Checked with hevcdl_write_access_unit, which has no capacity of its own: the slice data of the all-+-32767 pictures stays below (CTUs x default capacity per
+    CTU); the old per-CTU figure (hevcdl_access_unit_bound / CTUs = 12 288) does not hold for them, which is why the default is the derived 40 960
+    (csrc/entropy_coder.h)."""
     import hevcdl_amd
     worst = 0.0
     for name, cfg, recs, sao in ec.fuzz_corpus()[:6]:
@@ -46,14 +50,45 @@ def test_pictures_of_maximal_levels_fit_the_default_capacity():
 
 
 def test_fuzz_against_the_host_writer():
-    """At least 200 seeded synthetic pictures (valid records no encode produces): the shared coder == hevcdl_write_access_unit."""
+    """At least 200 seeded synthetic pictures (valid records no encode produces) and the directed ones: the coder's sub-streams, assembled, are the stream recorded
+    from the host writer, and hevcdl_write_access_unit (its own sub-stream regions, the second pass after an overflow, its own assembly) gives the same bytes."""
     import hevcdl_amd
     corpus = ec.fuzz_corpus()
     assert len(corpus) >= 200
-    for name, cfg, recs, sao in corpus:
+    for name, cfg, recs, sao in corpus + ec.directed_pictures():
         coded = hevcdl_amd.code_slice_data(cfg, recs, sao)
         ec.check_guard(coded)
-        assert ec.assemble(cfg, coded) == ec.host_writer_stream(cfg, recs, sao), name
+        stream = ec.assemble(cfg, coded)
+        ec.assert_recorded_stream(name, cfg, recs, sao, stream)
+        assert stream == ec.host_writer_stream(cfg, recs, sao), name
+
+
+FIRST_PASS_PER_CTU = 4096      # HOST_FIRST_PASS_PER_CTU of csrc/hevcdl_bitstream.cpp: the room hevcdl_write_access_unit gives a picture's slice data before it knows better
+
+
+def test_write_access_unit_codes_a_sub_stream_that_overflowed_once_more():
+    """hevcdl_write_access_unit itself through its second pass.  The all-+-32767 corpus pictures of 72x72, 136x200 and 200x136 (one sub-stream each; 23 KB per whole
+    CTU, 7 to 13 KB per CTU of the picture, against the 4 KB of the first pass) give the recorded streams; pictures of the same kind with two tiles and with three wavefront rows overflow in a sub-stream that has others in front
+    of it (the coded ones move to the larger buffer, a wavefront row starts again from the contexts it started from) and give what the default regions give."""
+    import hevcdl_amd
+    for name, cfg, recs, sao in ec.fuzz_corpus()[3:6]:
+        stream = ec.host_writer_stream(cfg, recs, sao)
+        print(name, len(stream), "bytes,", recs.shape[1], "CTUs")
+        assert len(stream) > recs.shape[1] * FIRST_PASS_PER_CTU + 4096, name      # more than the first pass holds (+ 64 bytes, + parameter sets and slice header)
+        ec.assert_recorded_stream(name, cfg, recs, sao, stream)
+    rng = np.random.default_rng(5)
+    room = 12 * FIRST_PASS_PER_CTU + 64                                 # 136 x 200: 3 x 4 CTUs
+    for kw in ({"tiles": (1, 2)}, {"wavefront": True}):
+        cfg = hevcdl_amd.stream_config(136, 200, 30, **kw)
+        recs = ec.synth_records(rng, 136, 200, 0)[None]
+        coded = hevcdl_amd.code_slice_data(cfg, recs)
+        n = [int(v) for v in coded[1][0]]
+        print(kw, "sub-streams of", n, "bytes; first pass", room)
+        if "tiles" in kw:      # tile 0 does not fit; tile 1 does not fit what its six CTUs are given behind it
+            assert len(n) == 2 and n[0] > room and n[1] > 6 * FIRST_PASS_PER_CTU + 64
+        else:                  # row 0 fits, row 1 does not fit what is left, row 2 does not fit what rows 2 and 3 are given behind row 1, row 3 fits
+            assert len(n) == 4 and n[0] <= room < n[0] + n[1] and n[2] > 6 * FIRST_PASS_PER_CTU + 64 and n[3] <= 3 * FIRST_PASS_PER_CTU + 64
+        assert ec.host_writer_stream(cfg, recs) == ec.assemble(cfg, coded)
 
 
 @pytest.mark.parametrize("name", ["c192_q32_r2", "t576_q27_2x3", "w200_q27_r2"])
@@ -108,7 +143,7 @@ def _dump(path, cfg, recs, sao, cpc, mode):
 
 def test_sanitizer_harness(tmp_path):
     """tests/entropy_harness.cpp + csrc/hevcdl_bitstream.cpp built with the host compiler and -fsanitize=address,undefined -static-libasan: fixtures, the synthetic
-    corpus, overflow and garbage records run without a sanitizer report and with the same checks as above."""
+    corpus, overflow and garbage records run without a sanitizer report and with the same checks as above, each picture also through hevcdl_write_access_unit."""
     import hevcdl_amd
     cxx = shutil.which("g++")
     if not cxx:

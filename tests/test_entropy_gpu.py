@@ -1,5 +1,6 @@
 """The device entropy coder (csrc/entropy_kernel.hip) on the MI355X: byte for byte the reference's streams, the host instantiation of the same source and the
-existing host writer; batches, the two-phase wavefront path, the capacity guard, the picture pipeline.  Inputs: tests/entropy_cases.py."""
+streams recorded from the former host writer (tests/golden/entropy_host_writer_digests.json); batches, the two-phase wavefront path, the capacity guard, the picture
+pipeline.  Inputs: tests/entropy_cases.py."""
 import os
 
 import numpy as np
@@ -23,7 +24,9 @@ def test_fixture_streams_without_sao(path):
 def test_fixture_streams_with_sao(name, oracle_built):
     import hevcdl_amd
     cfg, recs, sao = ec.sao_case(name)
-    assert ec.assemble(cfg, hevcdl_amd.code_slice_data(cfg, recs, sao, device=0)) == ec.host_writer_stream(cfg, recs, sao)
+    dev = hevcdl_amd.code_slice_data(cfg, recs, sao, device=0)
+    assert same_coded(dev, hevcdl_amd.code_slice_data(cfg, recs, sao))
+    ec.assert_recorded_stream("sao_" + name, cfg, recs, sao, ec.assemble(cfg, dev))
 
 
 def same_coded(a, b):
@@ -39,11 +42,13 @@ def same_coded(a, b):
 
 
 def test_fuzz_corpus_equals_the_host_instantiation():
+    """... and, assembled, the stream recorded from the former host writer."""
     import hevcdl_amd
     for name, cfg, recs, sao in ec.fuzz_corpus():
         dev = hevcdl_amd.code_slice_data(cfg, recs, sao, device=0)
         ec.check_guard(dev)
         assert same_coded(dev, hevcdl_amd.code_slice_data(cfg, recs, sao)), name
+        ec.assert_recorded_stream(name, cfg, recs, sao, ec.assemble(cfg, dev))
 
 
 def test_batches():
@@ -143,7 +148,7 @@ def test_pipeline_stream_equals_chunked_plus_host_writer(w, h, n, bd):
             inside.extend((first + i, hevcdl_amd.write_access_unit_from_slice_data(cfg, first + i, data[i], sizes[i])) for i in range(count))
         again = enc.encode_pictures_chunked(yuv, chunk_frames=2, on_chunk_hook=hook)
         assert [poc for poc, _ in inside] == list(range(n)) and [au for _, au in inside] == want
-        assert enc.entropy_info()[0] == 0                                 # no picture went to the host writer
+        assert enc.entropy_info()[0] == 0                                 # no picture went to the host
         data, sizes = enc.get_slice_data(0, n)                            # and it stays valid until the next call
         assert [hevcdl_amd.write_access_unit_from_slice_data(cfg, i, data[i], sizes[i]) for i in range(n)] == want
         assert all(np.array_equal(a[1], b[1]) for a, b in zip(again, plain))
@@ -155,8 +160,8 @@ def test_pipeline_stream_equals_chunked_plus_host_writer(w, h, n, bd):
 
 
 def test_pipeline_overflow_falls_back_to_the_host_writer():
-    """A capacity of 16 bytes per CTU (hevcdl_set_entropy_capacity, a test entry point) makes sub-streams overflow: those pictures are coded by the host writer from
-    their records, the batch is put together in picture order, and the access units are the same bytes.  Picture 1 is flat and fits even 16 bytes per CTU (12 CTUs:
+    """A capacity of 16 bytes per CTU (hevcdl_set_entropy_capacity, a test entry point) makes sub-streams overflow: those pictures are coded on the host from
+    their records (hevcdl_host_writer_slice_data: the same coder with the room it asks for), the batch is put together in picture order, and the access units are the same bytes.  Picture 1 is flat and fits even 16 bytes per CTU (12 CTUs:
     256 bytes), the others do not fit 64 (832 bytes), so kernel-coded and host-coded pictures meet in one batch; a second batch follows one with fallbacks."""
     import hevcdl_amd
     import ref_tools
@@ -179,7 +184,7 @@ def test_pipeline_overflow_falls_back_to_the_host_writer():
                 assert got == want
             seen.append(enc.entropy_info()[0])
             enc.enable_device_entropy(False)
-        print("pictures coded by the host writer at 16 and 64 bytes per CTU:", seen)
+        print("pictures coded on the host at 16 and 64 bytes per CTU:", seen)
         assert seen[0] >= n - 1 and 0 < seen[1] < n
     finally:
         enc.close()

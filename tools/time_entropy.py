@@ -8,11 +8,15 @@
              pictures' records (one core and 16 threads), the wall time of the pipeline calls, and the bytes that reach the callback per picture with and without
              want_records / want_pictures (counted from the arrays handed over, not computed).
   --cli N    tools/bench_cli.py N with and without --DeviceEntropy=1 (an MI355X).
+  --against LIB [--rounds N]   needs no GPU.  How a change of the coder is accepted: hevcdl_write_access_unit of this tree's library and of LIB (the parent commit's
+             build) in alternation, N rounds each (default 7), 3840 x 2176 with wavefront 0 and 1 on the --host records: per round the one-core time per access unit
+             (mean of 5) and the tail of 600 access units on 16 threads; medians, and the other library's interquartile spread as the margin the machine supports.
 Sections that were not run are written as NOT TIMED YET."""
 import argparse
 import os
 import subprocess
 import sys
+import threading
 import time
 from concurrent.futures import ThreadPoolExecutor
 
@@ -55,6 +59,52 @@ def host_section(out):
             for n in (75, 600):
                 line += "; %d access units on %d threads %.3f s" % (n, THREADS, tail(write_one, n))
             out.append(line)
+
+
+def quartiles(v):
+    v = sorted(v)
+    q = lambda p: v[int(round(p * (len(v) - 1)))]
+    return q(0.5), q(0.75) - q(0.25)
+
+
+def against_section(out, other, rounds):
+    import ctypes
+    import hevcdl_amd
+    import entropy_cases as ec
+    libs = (("base", ctypes.CDLL(other)), ("this", hevcdl_amd.load_library()))
+    _, fx, _ = ec.fixture_case(os.path.join(ec.GOLD, "rd_c192_q32_r2.npz"))
+    w, h = 3840, 2176
+    cx, cy = w // 64, h // 64
+    grid = np.arange(cx * cy).reshape(cy, cx)
+    recs = np.ascontiguousarray(fx[0][((grid // cx) % 2) * 3 + (grid % cx) % 3].reshape(-1))
+    cap = w * h * 3 + 4096
+    out.append("== this library against base = %s: hevcdl_write_access_unit, %dx%d, records as in --host; %d rounds each in alternation; %d CPUs here ==" % (other, w, h, rounds, os.cpu_count() or 1))
+    local = threading.local()
+    for wpp in (0, 1):
+        cfg = hevcdl_amd.stream_config(w, h, 32, wavefront=bool(wpp))
+
+        def one(lib):
+            if not hasattr(local, "buf"):
+                local.buf = np.empty(cap, np.uint8)
+            n = ctypes.c_size_t(0)
+            st = lib.hevcdl_write_access_unit(ctypes.byref(cfg), 0, ctypes.c_void_p(recs.ctypes.data), None, ctypes.c_void_p(local.buf.ctypes.data), ctypes.c_size_t(cap), ctypes.byref(n))
+            assert st == 0, st
+            return local.buf[:n.value].tobytes()
+        assert one(libs[0][1]) == one(libs[1][1]), "the two libraries write different access units"
+        core, tails = {"base": [], "this": []}, {"base": [], "this": []}
+        for _ in range(rounds):
+            for name, lib in libs:
+                t0 = time.perf_counter()
+                for _ in range(5):
+                    one(lib)
+                core[name].append((time.perf_counter() - t0) / 5 * 1e3)
+                tails[name].append(tail(lambda i: one(lib), 600))
+        for what, unit, got in (("one core, per access unit", "ms", core), ("600 access units on %d threads" % THREADS, "s", tails)):
+            (mb, iqr), (mt, _) = quartiles(got["base"]), quartiles(got["this"])
+            for name in ("base", "this"):
+                out.append("wavefront %d, %s, %s [%s]: %s" % (wpp, what, name, unit, " ".join("%.3f" % v for v in got[name])))
+            out.append("wavefront %d, %s: median base %.3f, this %.3f (%+.1f %%); interquartile spread of base %.3f: %s" %
+                       (wpp, what, mb, mt, 100 * (mt - mb) / mb, iqr, "within" if mt <= mb + iqr else "SLOWER THAN THE MARGIN"))
 
 
 def device_section(out, batch):
@@ -114,6 +164,8 @@ if __name__ == "__main__":
     ap.add_argument("--device", action="store_true")
     ap.add_argument("--cli", type=int, default=0)
     ap.add_argument("--batch", type=int, default=75)
+    ap.add_argument("--against", default=None, metavar="LIB")
+    ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "entropy_time.txt"))
     a = ap.parse_args()
     lines = ["Entropy coding (csrc/entropy_coder.h, csrc/entropy_kernel.hip).  Sections as tools/time_entropy.py prints them (--host, --device, --cli).", ""]
@@ -122,6 +174,9 @@ if __name__ == "__main__":
     else:
         lines.append("== host ==\nNOT TIMED YET.")
     lines.append("")
+    if a.against:
+        against_section(lines, os.path.abspath(a.against), a.rounds)
+        lines.append("")
     if a.device:
         device_section(lines, a.batch)
     else:
