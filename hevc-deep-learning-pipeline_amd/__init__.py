@@ -23,7 +23,7 @@ LEAF_LIB_PATH = os.path.join(PKG_DIR, "lib", "libhevcdl_hip_leaf.so")        # -
 WEIGHTS_PATH = os.path.join(PKG_DIR, "weights", "hevc_encoder_model.f32")
 WEIGHT_FLOATS = 637712
 LEAF_SOURCES = ["rd_leaf.hip", "rd_leaf_bd10.hip", "rd_leaf_wide.hip", "rd_leaf_tools.hip"]      # the decision kernel's four builds, each with csrc/rd_leaf_harness.h behind it
-SOURCES = ["cnn_kernel.hip", "fc_kernel.hip", "rd_kernel.hip", "rd_kernel_bd10.hip", "rd_kernel_wide.hip", "rd_kernel_tools.hip", "deblock_kernel.hip", "sao_kernel.hip", "quality_kernel.hip", "report_kernel.hip", "entropy_kernel.hip", "source_kernel.hip", "hevcdl_api.hip", "hevcdl_bitstream.cpp"]
+SOURCES = ["cnn_kernel.hip", "fc_kernel.hip", "rd_kernel.hip", "rd_kernel_bd10.hip", "rd_kernel_wide.hip", "rd_kernel_tools.hip", "deblock_kernel.hip", "dbk_select_kernel.hip", "sao_kernel.hip", "quality_kernel.hip", "report_kernel.hip", "entropy_kernel.hip", "source_kernel.hip", "hevcdl_api.hip", "hevcdl_bitstream.cpp"]
 
 STATUS = {0: "OK", 1: "INVALID_ARG", 2: "UNSUPPORTED", 3: "NO_DEVICE", 4: "HIP", 5: "OOM"}
 
@@ -63,7 +63,16 @@ class Config(ctypes.Structure):
                 ("sbh_rd_factor", ctypes.c_int64 * 2), ("qp_chroma", ctypes.c_int32),
                 ("tile_columns", ctypes.c_int32), ("tile_rows", ctypes.c_int32), ("exec_flags", ctypes.c_int32),
                 ("tile_uniform_spacing", ctypes.c_int32), ("tile_column_width", ctypes.c_int32 * 19), ("tile_row_height", ctypes.c_int32 * 21),
-                ("lf_across_tiles", ctypes.c_int32), ("lf_beta_offset_div2", ctypes.c_int32), ("lf_tc_offset_div2", ctypes.c_int32), ("wavefront", ctypes.c_int32)]
+                ("lf_across_tiles", ctypes.c_int32), ("lf_beta_offset_div2", ctypes.c_int32), ("lf_tc_offset_div2", ctypes.c_int32), ("wavefront", ctypes.c_int32),
+                ("deblocking_metric", ctypes.c_int32), ("lf_offset_in_pps", ctypes.c_int32)]
+
+
+class DbkChoice(ctypes.Structure):
+    """hevcdl_dbk_choice of include/hevcdl.h: what one picture's slice header says about the deblocking filter and what the filter ran with."""
+    _fields_ = [("override_enabled", ctypes.c_int32), ("override_flag", ctypes.c_int32), ("disabled", ctypes.c_int32), ("beta_offset_div2", ctypes.c_int32), ("tc_offset_div2", ctypes.c_int32)]
+
+
+DBK_CHOICE_DTYPE = np.dtype([("override_enabled", "<i4"), ("override_flag", "<i4"), ("disabled", "<i4"), ("beta_offset_div2", "<i4"), ("tc_offset_div2", "<i4")])      # the same as a numpy record
 
 
 def tile_layout(tiles, width, height):
@@ -307,6 +316,20 @@ def load_library():
     lib.hevcdl_get_output_frames.argtypes = [vp, ci, ci, vp]
     lib.hevcdl_load_source_host.argtypes = [sfp, ci, ci, ci, vp, ci, vp]
     lib.hevcdl_store_output_host.argtypes = [sfp, ci, ci, ci, vp, ci, vp]
+    lib.hevcdl_create_error.argtypes = []
+    lib.hevcdl_create_error.restype = ctypes.c_char_p
+    lib.hevcdl_dbk_metric_frames.argtypes = [vp, vp, ci, vp]
+    lib.hevcdl_dbk_metric_frames_dev.argtypes = [vp, vp, ci, vp, vp]
+    lib.hevcdl_dbk_metric_choice.argtypes = [ci, ci, ci, ctypes.c_uint64, ctypes.c_uint64, ci, ci, ctypes.POINTER(DbkChoice)]
+    lib.hevcdl_deblock_frames_choice.argtypes = [vp, vp, ci, vp, vp, vp]
+    lib.hevcdl_deblock_frames_choice_dev.argtypes = [vp, vp, ci, vp, vp, vp, vp]
+    lib.hevcdl_get_dbk_choice.argtypes = [vp, ci, ci, vp]
+    lib.hevcdl_dbk_trial_frames.argtypes = [vp, vp, vp, ci, vp, vp]
+    lib.hevcdl_dbk_trial_frames_dev.argtypes = [vp, vp, vp, ci, vp, vp, vp]
+    lib.hevcdl_dbk_walk_table.argtypes = [vp, ci, ci, vp, ctypes.POINTER(DbkChoice)]
+    lib.hevcdl_dbk_select_reset.argtypes = [vp]
+    lib.hevcdl_write_access_unit_dbk.argtypes = [ctypes.POINTER(StreamConfig), ci, vp, vp, vp, vp, ctypes.c_size_t, szp]
+    lib.hevcdl_write_access_unit_from_slice_data_dbk.argtypes = [ctypes.POINTER(StreamConfig), ci, vp, vp, ci, vp, vp, ctypes.c_size_t, szp]
     _lib = lib
     return lib
 
@@ -322,7 +345,9 @@ EXPORTS = ["hevcdl_config_default", "hevcdl_create", "hevcdl_destroy", "hevcdl_l
            "hevcdl_picture_report", "hevcdl_picture_report_dev", "hevcdl_enable_picture_report", "hevcdl_get_picture_report", "hevcdl_plane_hash", "hevcdl_plane_hash_host",
            "hevcdl_report_chunk_bytes", "hevcdl_get_report_info",
            "hevcdl_source_format_default", "hevcdl_padded_size", "hevcdl_source_frame_bytes", "hevcdl_output_frame_bytes", "hevcdl_set_source_format",
-           "hevcdl_load_source", "hevcdl_load_source_dev", "hevcdl_store_output", "hevcdl_store_output_dev", "hevcdl_load_source_host", "hevcdl_store_output_host", "hevcdl_get_output_frames"]
+           "hevcdl_load_source", "hevcdl_load_source_dev", "hevcdl_store_output", "hevcdl_store_output_dev", "hevcdl_load_source_host", "hevcdl_store_output_host", "hevcdl_get_output_frames",
+           "hevcdl_create_error", "hevcdl_dbk_metric_frames", "hevcdl_dbk_metric_frames_dev", "hevcdl_dbk_metric_choice", "hevcdl_deblock_frames_choice", "hevcdl_deblock_frames_choice_dev",
+           "hevcdl_get_dbk_choice", "hevcdl_dbk_trial_frames", "hevcdl_dbk_trial_frames_dev", "hevcdl_dbk_walk_table", "hevcdl_dbk_select_reset", "hevcdl_write_access_unit_dbk", "hevcdl_write_access_unit_from_slice_data_dbk"]
 
 
 def picture_hash_sei(width, height, picture, bit_depth=8, method=1):
@@ -451,7 +476,8 @@ TOOLS_REFERENCE = 0x7f
 TOOL_RDOQ, TOOL_RDOQTS, TOOL_TSKIP, TOOL_TSKIP_FAST, TOOL_SIGN_HIDE, TOOL_STRONG_INTRA, TOOL_FAST_UDI_MPM = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40      # HEVCDL_TOOL_* (include/hevcdl.h): each may be turned off
 
 
-def default_config(width, height, qp, max_frames=1, device=0, cnn_input=0, tiles=(1, 1), bit_depth=8, lf_across_tiles=True, bn_mode=0, tools=TOOLS_REFERENCE, lf_offsets=(0, 0), wavefront=False):
+def default_config(width, height, qp, max_frames=1, device=0, cnn_input=0, tiles=(1, 1), bit_depth=8, lf_across_tiles=True, bn_mode=0, tools=TOOLS_REFERENCE, lf_offsets=(0, 0), wavefront=False,
+                   deblocking_metric=0, lf_offset_in_pps=True):
     lib = load_library()
     cfg = Config()
     st = lib.hevcdl_config_default_bd(ctypes.byref(cfg), width, height, qp, bit_depth)
@@ -464,6 +490,7 @@ def default_config(width, height, qp, max_frames=1, device=0, cnn_input=0, tiles
     cfg.tools = tools                          # cfg keys TransformSkip / SignHideFlag / StrongIntraSmoothing / FastUDIUseMPMEnabled
     cfg.lf_beta_offset_div2, cfg.lf_tc_offset_div2 = lf_offsets      # LoopFilterBetaOffset_div2, LoopFilterTcOffset_div2
     cfg.wavefront = 1 if wavefront else 0      # WaveFrontSynchro: CTU rows start from the contexts behind the second CTU of the row above (and run as units of their own)
+    cfg.deblocking_metric, cfg.lf_offset_in_pps = int(deblocking_metric), 1 if lf_offset_in_pps else 0      # DeblockingFilterMetric, LoopFilterOffsetInPPS
     return cfg
 
 
@@ -537,23 +564,63 @@ def pack_slice_data(buf, sizes, off):
     return b"".join(buf[int(o):int(o) + int(n)].tobytes() for o, n in zip(off, sizes))
 
 
-def write_access_unit_from_slice_data(cfg, poc, data, sizes):
-    """Everything of picture poc's access unit around slice data that exists already (hevcdl_write_access_unit_from_slice_data) -> bytes."""
+def _choice_ptr(choice):
+    """A picture's deblocking choice (a DBK_CHOICE_DTYPE record, a DbkChoice, a 5-tuple or None) -> (pointer or None, keep-alive)."""
+    if choice is None:
+        return None, None
+    if isinstance(choice, DbkChoice):
+        return ctypes.addressof(choice), choice
+    c = np.zeros(1, DBK_CHOICE_DTYPE)
+    c[0] = tuple(int(v) for v in (choice.tolist() if isinstance(choice, np.void) else choice))
+    return c.ctypes.data, c
+
+
+def dbk_metric_choice(width, height, bit_depth, col_sum, row_sum, pps_offsets=(0, 0)):
+    """The two sums of DeblockingFilterMetric 1 -> the picture's choice as a DBK_CHOICE_DTYPE record (hevcdl_dbk_metric_choice; host only)."""
+    lib = load_library()
+    c = DbkChoice()
+    st = lib.hevcdl_dbk_metric_choice(int(width), int(height), int(bit_depth), int(col_sum), int(row_sum), int(pps_offsets[0]), int(pps_offsets[1]), ctypes.byref(c))
+    if st:
+        raise HevcdlError(st, "hevcdl_dbk_metric_choice")
+    return np.array([(c.override_enabled, c.override_flag, c.disabled, c.beta_offset_div2, c.tc_offset_div2)], DBK_CHOICE_DTYPE)[0]
+
+
+def dbk_walk_table(table, state, pps_offsets=(0, 0)):
+    """One 7 x 7 table of trial distortions (49 uint64, entry 7 (b + 3) + (t + 3)) and the carried state [available, disabled, beta, tc] -> (the picture's choice as a
+    DBK_CHOICE_DTYPE record, the new state as a list): hevcdl_dbk_walk_table, host only."""
+    lib = load_library()
+    table = np.ascontiguousarray(table, np.uint64).reshape(49)
+    st = np.array(state, np.int32)
+    c = DbkChoice()
+    rc = lib.hevcdl_dbk_walk_table(table.ctypes.data, int(pps_offsets[0]), int(pps_offsets[1]), st.ctypes.data, ctypes.byref(c))
+    if rc:
+        raise HevcdlError(rc, "hevcdl_dbk_walk_table")
+    return np.array([(c.override_enabled, c.override_flag, c.disabled, c.beta_offset_div2, c.tc_offset_div2)], DBK_CHOICE_DTYPE)[0], st.tolist()
+
+
+def write_access_unit_from_slice_data(cfg, poc, data, sizes, choice=None):
+    """Everything of picture poc's access unit around slice data that exists already (hevcdl_write_access_unit_from_slice_data; with `choice`, the picture's deblocking
+    parameters, hevcdl_write_access_unit_from_slice_data_dbk) -> bytes."""
     lib = load_library()
     data = np.frombuffer(bytes(data) + b"\0", np.uint8)
     sizes = np.ascontiguousarray(sizes, np.uint32)
     cap = lib.hevcdl_access_unit_bound(cfg.width, cfg.height) + data.size
     buf = np.zeros(cap, np.uint8)
     n = ctypes.c_size_t(0)
-    st = lib.hevcdl_write_access_unit_from_slice_data(ctypes.byref(cfg), int(poc), data.ctypes.data, sizes.ctypes.data, int(sizes.size), buf.ctypes.data, cap, ctypes.byref(n))
+    cp, _keep = _choice_ptr(choice)
+    if cp is None:
+        st = lib.hevcdl_write_access_unit_from_slice_data(ctypes.byref(cfg), int(poc), data.ctypes.data, sizes.ctypes.data, int(sizes.size), buf.ctypes.data, cap, ctypes.byref(n))
+    else:
+        st = lib.hevcdl_write_access_unit_from_slice_data_dbk(ctypes.byref(cfg), int(poc), data.ctypes.data, sizes.ctypes.data, int(sizes.size), cp, buf.ctypes.data, cap, ctypes.byref(n))
     if st:
         raise HevcdlError(st, "hevcdl_write_access_unit_from_slice_data")
     return buf[:n.value].tobytes()
 
 
 def write_access_unit(width, height, qp, poc, records, level_idc=186, sao=None, tiles=(1, 1), bit_depth=8, lf_across_tiles=True, tools=TOOLS_REFERENCE, lf_offsets=(0, 0), lf_disable=False,
-                      rewrite_param_sets=True, wavefront=False, conf_win=(0, 0)):
-    """Host-side bitstream writer (no GPU): VPS+SPS+PPS+slice NAL of one picture from its CTU records -> bytes."""
+                      rewrite_param_sets=True, wavefront=False, conf_win=(0, 0), choice=None):
+    """Host-side bitstream writer (no GPU): VPS+SPS+PPS+slice NAL of one picture from its CTU records -> bytes.  choice: the picture's deblocking parameters
+    and whether the PPS lets a slice override (hevcdl_write_access_unit_dbk: DeblockingFilterMetric, LoopFilterOffsetInPPS 0)."""
     lib = load_library()
     cfg = stream_config(width, height, qp, level_idc, False, tiles, bit_depth, lf_across_tiles, tools, lf_offsets, lf_disable, rewrite_param_sets, wavefront, conf_win)
     sao_ptr = None
@@ -565,7 +632,11 @@ def write_access_unit(width, height, qp, poc, records, level_idc=186, sao=None, 
     cap = lib.hevcdl_access_unit_bound(width, height)
     buf = np.zeros(cap, np.uint8)
     n = ctypes.c_size_t(0)
-    st = lib.hevcdl_write_access_unit(ctypes.byref(cfg), int(poc), records.ctypes.data, sao_ptr, buf.ctypes.data, cap, ctypes.byref(n))
+    cp, _keep = _choice_ptr(choice)
+    if cp is None:
+        st = lib.hevcdl_write_access_unit(ctypes.byref(cfg), int(poc), records.ctypes.data, sao_ptr, buf.ctypes.data, cap, ctypes.byref(n))
+    else:
+        st = lib.hevcdl_write_access_unit_dbk(ctypes.byref(cfg), int(poc), records.ctypes.data, sao_ptr, cp, buf.ctypes.data, cap, ctypes.byref(n))
     if st != 0:
         raise HevcdlError(st, "write_access_unit")
     return buf[:n.value].tobytes()
@@ -634,10 +705,12 @@ def store_output_host(fmt, coded_width, coded_height, internal_bit_depth, pictur
 class Encoder:
     """One context per device.  Frames are planar 8-bit 4:2:0, numpy [n_frames, w*h*3/2] uint8."""
 
-    def __init__(self, width, height, qp, max_frames=1, device=0, cnn_input=0, weights=None, cfg=None, tiles=(1, 1), bit_depth=8, lf_across_tiles=True, bn_mode=0, tools=TOOLS_REFERENCE, lf_offsets=(0, 0), wavefront=False):
+    def __init__(self, width, height, qp, max_frames=1, device=0, cnn_input=0, weights=None, cfg=None, tiles=(1, 1), bit_depth=8, lf_across_tiles=True, bn_mode=0, tools=TOOLS_REFERENCE, lf_offsets=(0, 0), wavefront=False,
+                 deblocking_metric=0, lf_offset_in_pps=True):
         """bit_depth 10: every yuv / recon array of the decision path holds uint16 samples (frame_bytes counts bytes)."""
         self.lib = load_library()
-        self.cfg = cfg or default_config(width, height, qp, max_frames, device, cnn_input, tiles, bit_depth, lf_across_tiles, bn_mode, tools, lf_offsets, wavefront)
+        self.cfg = cfg or default_config(width, height, qp, max_frames, device, cnn_input, tiles, bit_depth, lf_across_tiles, bn_mode, tools, lf_offsets, wavefront,
+                                         deblocking_metric, lf_offset_in_pps)
         self.bit_depth = self.cfg.bit_depth
         self.sample_dtype = np.uint8 if self.bit_depth == 8 else np.dtype("<u2")
         self.tiles = (self.cfg.tile_columns, self.cfg.tile_rows)
@@ -651,7 +724,7 @@ class Encoder:
         st = self.lib.hevcdl_create(ctypes.byref(self.cfg), w.ctypes.data, w.size, ctypes.byref(self._h))
         if st:
             self._h = None
-            raise HevcdlError(st, "hevcdl_create")
+            raise HevcdlError(st, "hevcdl_create" + "".join(": " + m for m in [(self.lib.hevcdl_create_error() or b"").decode()] if m))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -839,6 +912,54 @@ class Encoder:
         records = np.ascontiguousarray(records).reshape(n, self.ctus)
         out = np.zeros_like(recon)
         self._check(self.lib.hevcdl_deblock_frames(self._h, recon.ctypes.data, n, records.ctypes.data, out.ctypes.data))
+        return out
+
+    def deblock_frames_choice(self, recon, records, choices):
+        """deblock_frames with the parameters of every picture: choices [n] DBK_CHOICE_DTYPE (hevcdl_deblock_frames_choice)."""
+        recon, n = self._frames(recon)
+        records = np.ascontiguousarray(records).reshape(n, self.ctus)
+        choices = np.ascontiguousarray(choices, DBK_CHOICE_DTYPE).reshape(n)
+        out = np.zeros_like(recon)
+        self._check(self.lib.hevcdl_deblock_frames_choice(self._h, recon.ctypes.data, n, records.ctypes.data, choices.ctypes.data, out.ctypes.data))
+        return out
+
+    def deblock_frames_choice_dev(self, d_recon, n, d_records, choices, d_out, stream=None):
+        """Device buffers, the choices [n] DBK_CHOICE_DTYPE (or None) from host memory; d_out may be d_recon."""
+        if choices is not None:
+            choices = np.ascontiguousarray(choices, DBK_CHOICE_DTYPE).reshape(n)
+        self._check(self.lib.hevcdl_deblock_frames_choice_dev(self._h, d_recon, n, d_records, None if choices is None else choices.ctypes.data, d_out, stream))
+
+    # ---- per-picture deblocking parameters (DeblockingFilterMetric) ----
+    def dbk_metric_frames(self, recon):
+        """Reconstructions before deblocking [n, samples] -> the metric's exact sums [n, 2] uint64: vertical edges, horizontal edges (hevcdl_dbk_metric_frames)."""
+        recon, n = self._frames(recon)
+        sums = np.zeros((n, 2), np.uint64)
+        self._check(self.lib.hevcdl_dbk_metric_frames(self._h, recon.ctypes.data, n, sums.ctypes.data))
+        return sums
+
+    def dbk_metric_frames_dev(self, d_recon, n, d_sums, stream=None):
+        self._check(self.lib.hevcdl_dbk_metric_frames_dev(self._h, d_recon, n, d_sums, stream))
+
+    def dbk_trial_frames(self, org, recon, records):
+        """Originals, reconstructions before deblocking [n, samples] and records [n, ctus] -> the trial tables [n, 7, 7] uint64, [b + 3][t + 3] (hevcdl_dbk_trial_frames)."""
+        org, n = self._frames(org)
+        recon, _ = self._frames(recon)
+        records = np.ascontiguousarray(records).reshape(n, self.ctus)
+        tables = np.zeros((n, 7, 7), np.uint64)
+        self._check(self.lib.hevcdl_dbk_trial_frames(self._h, org.ctypes.data, recon.ctypes.data, n, records.ctypes.data, tables.ctypes.data))
+        return tables
+
+    def dbk_trial_frames_dev(self, d_org, d_recon, n, d_records, d_tables, stream=None):
+        self._check(self.lib.hevcdl_dbk_trial_frames_dev(self._h, d_org, d_recon, n, d_records, d_tables, stream))
+
+    def dbk_select_reset(self):
+        """DeblockingFilterMetric 2: forget the previous picture's choice; the next picture starts a sequence (hevcdl_dbk_select_reset)."""
+        self._check(self.lib.hevcdl_dbk_select_reset(self._h))
+
+    def get_dbk_choice(self, first, count):
+        """The deblocking choices [count] DBK_CHOICE_DTYPE of pictures [first, first + count) of the last encode_pictures* call (hevcdl_get_dbk_choice)."""
+        out = np.zeros(count, DBK_CHOICE_DTYPE)
+        self._check(self.lib.hevcdl_get_dbk_choice(self._h, int(first), int(count), out.ctypes.data))
         return out
 
     def sao_frames(self, org, deblocked):

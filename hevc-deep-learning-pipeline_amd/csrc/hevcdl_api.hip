@@ -7,6 +7,7 @@
 #include <vector>
 #include "hevcdl.h"
 #include "hevcdl_dev.h"
+#include "dbk_select.h"
 #include "entropy_coder.h"
 #include "picture_hash_core.h"
 #include "source_core.h"
@@ -119,6 +120,13 @@ struct Source {
   DevBuf<unsigned char> d_src, d_win_org, d_win_pic, d_win_sse;
   const uint8_t *d_last_final = nullptr; int last_frames = 0;      // output pictures of the last picture pipeline call, still in HBM (hevcdl_get_output_frames)
 };
+// per-picture deblocking parameters: the parameter rows of a batch in HBM and the metric's sums, allocated by the first call that needs them; the choices of the picture
+// pipeline's last batch (hevcdl_get_dbk_choice)
+struct DbkSelect {
+  DevBuf<int> d_frame_params; DevBuf<unsigned long long> d_sums;      // d_sums: [max_frames][49] words (the metric uses two a picture)
+  std::vector<int> h_frame_params; std::vector<unsigned long long> h_sums; std::vector<hevcdl_dbk_choice> h_choice;
+  hevcdl_dbk_walk_state walk = { 0, 0, 0, 0 };      // DeblockingFilterMetric 2: the reference's m_DBParam[0], advanced picture by picture across calls (hevcdl_dbk_select_reset)
+};
 // per-CTU session (hevcdl_begin_frames / hevcdl_compress_ctu): coder state after the last CTU of every frame, next CTU expected
 struct Session { DevBuf<unsigned char> d_cabac; std::vector<int> next_ctu; int session_frames = 0; };
 // the decision kernel's workspace and scheduling areas
@@ -138,7 +146,7 @@ struct hevcdl_ctx {
   int col_bd[21] = { 0 }, row_bd[23] = { 0 };    // tile boundaries in CTUs
   DevBuf<float> d_weights, d_a3; size_t a3_ctus = 0;   // d_a3: conv3 outputs of one chunk of CTUs (32 KB per CTU): the hand-over from the conv kernel to the head kernel
   DevBuf<int> d_flag;                  // device-side error flag of the label check
-  Staging stage; SaoWorkspace sao; Quality q; Report rp; Entropy ec; Source src; Session ses; RdWorkspace rd;
+  Staging stage; SaoWorkspace sao; Quality q; Report rp; Entropy ec; Source src; Session ses; RdWorkspace rd; DbkSelect dbk;
   int ec_capacity_per_ctu = 0;         // hevcdl_set_entropy_capacity (tests): 0 = the default; outlives the entropy switch
   bool profile = false;
   std::vector<Event> ev_cnn, ev_rd, ev_conv;       // start/stop pairs (ev_conv: the convolution kernel alone, one pair per chunk of CTUs)
@@ -224,7 +232,7 @@ extern "C" hevcdl_status hevcdl_config_default_bd(hevcdl_config *cfg, int width,
   cfg->width = width; cfg->height = height; cfg->bit_depth = bit_depth; cfg->chroma_format = 420; cfg->qp = qp;
   cfg->ctu_size = 64; cfg->max_partition_depth = 4; cfg->tu_log2_min = 2; cfg->tu_log2_max = 5; cfg->tu_max_depth_intra = 3;
   cfg->tools = HEVCDL_TOOLS_REFERENCE; cfg->bn_mode = HEVCDL_BN_REFERENCE; cfg->boundary_policy = HEVCDL_BOUNDARY_CLAMP;
-  cfg->cnn_input = HEVCDL_CNN_INPUT_RGB601; cfg->device = 0; cfg->max_frames = 1; cfg->tile_columns = 1; cfg->tile_rows = 1; cfg->tile_uniform_spacing = 1; cfg->lf_across_tiles = 1;
+  cfg->cnn_input = HEVCDL_CNN_INPUT_RGB601; cfg->device = 0; cfg->max_frames = 1; cfg->tile_columns = 1; cfg->tile_rows = 1; cfg->tile_uniform_spacing = 1; cfg->lf_across_tiles = 1; cfg->lf_offset_in_pps = 1;
   // TEncSlice::calculateLambda (TEncSlice.cpp:433-527) for an all-intra GOP of 1, then setUpLambda (:112-140)
   cfg->lambda = 0.57 * 1.0 * pow(2.0, (qp - 12) / 3.0);
   cfg->sqrt_lambda = sqrt(cfg->lambda);                         // TComRdCost::setLambda TComRdCost.cpp:109-122
@@ -351,8 +359,14 @@ static void pack_fc1(const float *w, const float *b, float *dst, float sc)
 static void pack_fc(const float *w, const float *b, int out, int in, float *dst)
 { for (int j = 0; j < out; j++) for (int k = 0; k < in; k++) dst[(size_t)k * out + j] = w[(size_t)j * in + k]; memcpy(dst + (size_t)in * out, b, out * sizeof(float)); }
 
+// hevcdl_create has no context to leave a message in: the calling thread's last refusal
+static thread_local const char *g_create_error = "";
+static hevcdl_status refuse(hevcdl_status s, const char *why) { g_create_error = why; return s; }
+extern "C" const char *hevcdl_create_error(void) { return g_create_error; }
+
 extern "C" hevcdl_status hevcdl_create(const hevcdl_config *cfg, const float *weights, size_t n_floats, hevcdl_ctx **out)
 {
+  g_create_error = "";
   if (!cfg || !out || !weights || cfg->struct_size != sizeof(hevcdl_config)) return HEVCDL_ERR_INVALID_ARG;
   if (n_floats != HEVCDL_WEIGHT_FLOATS) return HEVCDL_ERR_INVALID_ARG;
   if (cfg->width <= 0 || cfg->height <= 0 || (cfg->width & 7) || (cfg->height & 7) || cfg->qp < 0 || cfg->qp > 51 || cfg->max_frames < 1) return HEVCDL_ERR_INVALID_ARG;
@@ -373,6 +387,12 @@ extern "C" hevcdl_status hevcdl_create(const hevcdl_config *cfg, const float *we
   }
   if (cfg->wavefront != 0 && cfg->wavefront != 1) return HEVCDL_ERR_INVALID_ARG;
   if (cfg->wavefront && cfg->tile_columns * cfg->tile_rows > 1) return HEVCDL_ERR_UNSUPPORTED;      // as the reference (TAppEncCfg.cpp xCheckParameter: only the high-throughput profile has both)
+  // per-picture deblocking parameters: the reference's own condition (TAppEncCfg.cpp:2143) -- that the filter is on is the caller's word at every picture pipeline call
+  // (its `deblock` argument), checked there -- and the metric's assert (TEncGOP.cpp:3198-3199)
+  if (cfg->deblocking_metric < 0 || cfg->deblocking_metric > 2 || (cfg->lf_offset_in_pps != 0 && cfg->lf_offset_in_pps != 1)) return refuse(HEVCDL_ERR_INVALID_ARG, "deblocking_metric is 0, 1 or 2 and lf_offset_in_pps 0 or 1");
+  if (cfg->deblocking_metric != 0 && cfg->lf_offset_in_pps != 0) return refuse(HEVCDL_ERR_INVALID_ARG, "If DeblockingFilterMetric is non-zero then both LoopFilterDisable and LoopFilterOffsetInPPS must be 0");
+  if (cfg->deblocking_metric == 1 && (hevcdl_dbk_metric_edges(cfg->width) < 1 || hevcdl_dbk_metric_edges(cfg->height) < 1))
+    return refuse(HEVCDL_ERR_INVALID_ARG, "DeblockingFilterMetric 1 needs a coded picture of at least 64 luma samples in either direction (the reference asserts noCol > 1 && noRows > 1)");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device >= ndev) return HEVCDL_ERR_NO_DEVICE;
   hevcdl_ctx *ctx = new (std::nothrow) hevcdl_ctx();
@@ -828,38 +848,169 @@ static hevcdl_status compress_frames_staged(hevcdl_ctx *ctx, int n_frames, const
 }
 
 // ---- deblocking (row f-2, first half): TComLoopFilter::loopFilterPic, TComLoopFilter.cpp:130, called at TEncGOP.cpp:1742 ----
-static const unsigned char DBK_TC[54] = { 0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,1,1,1,1,1,1,1,1,1,2,2,2,2,3,3,3,3,4,4,4,5,5,6,6,7,8,9,10,11,13,14,16,18,20,22,24 };   // :59-62
-static const unsigned char DBK_BETA[52] = { 0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,6,7,8,9,10,11,12,13,14,15,16,17,18,20,22,24,26,28,30,32,34,36,38,40,42,44,46,48,50,52,54,56,58,60,62,64 };   // :64-67
+// tc / beta / chroma tc of a picture filtered with (beta_offset_div2, tc_offset_div2): TComLoopFilter.cpp:59-67 (the tables: csrc/dbk_select.h), :623-624, 782-804, Bs 2
+static void dbk_triple(const hevcdl_ctx *ctx, int beta_offset_div2, int tc_offset_div2, int *tc, int *beta, int *tc_c)
+{
+  const int qp = ctx->cfg.qp, qpc = CHROMA_SCALE_420[qp < 0 ? 0 : (qp > 57 ? 57 : qp)];      // TComLoopFilter.cpp:782-797, cQpOffset 0
+  const int bd_scale = 1 << (ctx->cfg.bit_depth - 8);                                       // iBitdepthScale, TComLoopFilter.cpp:596, 770
+  const int tco = 2 * tc_offset_div2, bo = 2 * beta_offset_div2;   // slice_tc_offset_div2 / slice_beta_offset_div2 << 1 (TComLoopFilter.cpp:623-624, 804), Bs 2
+  auto clipi = [](int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); };
+  *tc = HEVCDL_DBK_TC[clipi(qp + 2 + tco, 53)] * bd_scale; *beta = HEVCDL_DBK_BETA[clipi(qp + bo, 51)] * bd_scale; *tc_c = HEVCDL_DBK_TC[clipi(qpc + 2 + tco, 53)] * bd_scale;
+}
 
-extern "C" hevcdl_status hevcdl_deblock_frames_dev(hevcdl_ctx *ctx, const void *d_recon, int n_frames, const void *d_records, void *d_out, void *stream)
+extern "C" hevcdl_status hevcdl_deblock_frames_choice_dev(hevcdl_ctx *ctx, const void *d_recon, int n_frames, const void *d_records, const hevcdl_dbk_choice *choices, void *d_out, void *stream)
 {
   FRAMES_OR_RETURN(ctx, n_frames);
   if (!d_recon || !d_records || !d_out) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null device pointer");
   hevcdl_dbk_params p;
   p.in = (const uint8_t *)d_recon; p.out = (uint8_t *)d_out; p.records = (const unsigned char *)d_records;
   p.width = ctx->cfg.width; p.height = ctx->cfg.height; p.ctus_x = ctx->ctus_x; p.ctus_per_frame = ctx->ctus; p.n_frames = n_frames;
-  const int qp = ctx->cfg.qp, qpc = CHROMA_SCALE_420[qp < 0 ? 0 : (qp > 57 ? 57 : qp)];      // TComLoopFilter.cpp:782-797, cQpOffset 0
-  const int bd_scale = 1 << (ctx->cfg.bit_depth - 8);                                       // iBitdepthScale, TComLoopFilter.cpp:596, 770
-  const int tco = 2 * ctx->cfg.lf_tc_offset_div2, bo = 2 * ctx->cfg.lf_beta_offset_div2;   // slice_tc_offset_div2 / slice_beta_offset_div2 << 1 (TComLoopFilter.cpp:623-624, 804), Bs 2
-  auto clipi = [](int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); };
-  p.tc = DBK_TC[clipi(qp + 2 + tco, 53)] * bd_scale; p.beta = DBK_BETA[clipi(qp + bo, 51)] * bd_scale; p.tc_c = DBK_TC[clipi(qpc + 2 + tco, 53)] * bd_scale;
+  dbk_triple(ctx, ctx->cfg.lf_beta_offset_div2, ctx->cfg.lf_tc_offset_div2, &p.tc, &p.beta, &p.tc_c);
   p.pel_max = (1 << ctx->cfg.bit_depth) - 1;
   p.lf_across_tiles = ctx->cfg.lf_across_tiles != 0; p.tile_cols = ctx->cfg.tile_columns; p.tile_rows = ctx->cfg.tile_rows;
   memcpy(p.col_bd, ctx->col_bd, sizeof p.col_bd); memcpy(p.row_bd, ctx->row_bd, sizeof p.row_bd);
+  p.frame_params = nullptr;
+  if (choices) { // a row of (tc, beta, tc_c, disabled) per picture, uploaded in front of the launch on its stream (the host copy lives in the context until the next call)
+    for (int i = 0; i < n_frames; i++)
+      if (choices[i].beta_offset_div2 < -6 || choices[i].beta_offset_div2 > 6 || choices[i].tc_offset_div2 < -6 || choices[i].tc_offset_div2 > 6) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "a picture's deblocking offsets are out of range (-6 .. 6)");
+    TRY(lazy_alloc(ctx, ctx->dbk.d_frame_params, sizeof(int) * 4 * (size_t)ctx->cfg.max_frames, "per-picture deblocking parameters (cfg.max_frames)"));
+    std::vector<int> &h = ctx->dbk.h_frame_params;
+    h.assign((size_t)4 * n_frames, 0);
+    for (int i = 0; i < n_frames; i++) { dbk_triple(ctx, choices[i].beta_offset_div2, choices[i].tc_offset_div2, &h[4 * i], &h[4 * i + 1], &h[4 * i + 2]); h[4 * i + 3] = choices[i].disabled != 0; }
+    HIPCHK(hipMemcpyAsync(ctx->dbk.d_frame_params, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice, (hipStream_t)stream));
+    p.frame_params = ctx->dbk.d_frame_params;
+  }
   hevcdl_launch_deblock(&p, stream);
   return launch_status(ctx);
 }
 
+extern "C" hevcdl_status hevcdl_deblock_frames_dev(hevcdl_ctx *ctx, const void *d_recon, int n_frames, const void *d_records, void *d_out, void *stream)
+{
+  return hevcdl_deblock_frames_choice_dev(ctx, d_recon, n_frames, d_records, nullptr, d_out, stream);
+}
+
 extern "C" hevcdl_status hevcdl_deblock_frames(hevcdl_ctx *ctx, const uint8_t *recon, int n_frames, const hevcdl_ctu_record *records, uint8_t *out)
+{
+  return hevcdl_deblock_frames_choice(ctx, recon, n_frames, records, nullptr, out);
+}
+
+extern "C" hevcdl_status hevcdl_deblock_frames_choice(hevcdl_ctx *ctx, const uint8_t *recon, int n_frames, const hevcdl_ctu_record *records, const hevcdl_dbk_choice *choices, uint8_t *out)
 {
   FRAMES_OR_RETURN(ctx, n_frames);
   if (!recon || !records || !out) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null pointer");
   TRY(ensure_staging(ctx));
   HIPCHK(hipMemcpy(ctx->stage.d_recon, recon, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(ctx->stage.d_records, records, ctx->records_bytes(n_frames), hipMemcpyHostToDevice));
-  TRY(hevcdl_deblock_frames_dev(ctx, ctx->stage.d_recon, n_frames, ctx->stage.d_records, ctx->stage.d_yuv, nullptr));   // d_yuv: free staging plane set
+  TRY(hevcdl_deblock_frames_choice_dev(ctx, ctx->stage.d_recon, n_frames, ctx->stage.d_records, choices, ctx->stage.d_yuv, nullptr));   // d_yuv: free staging plane set
   TRY(sync_or_fail(ctx, "deblock kernels"));
   HIPCHK(hipMemcpy(out, ctx->stage.d_yuv, ctx->frame_bytes * n_frames, hipMemcpyDeviceToHost));
+  return HEVCDL_OK;
+}
+
+// ---- per-picture deblocking parameters: DeblockingFilterMetric 1 (dbk_select_kernel.hip, dbk_select.h), TEncGOP::applyDeblockingFilterMetric, called at TEncGOP.cpp:1739 ----
+extern "C" hevcdl_status hevcdl_dbk_metric_frames_dev(hevcdl_ctx *ctx, const void *d_recon, int n_frames, void *d_sums, void *stream)
+{
+  FRAMES_OR_RETURN(ctx, n_frames);
+  if (!d_recon || !d_sums) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null device pointer");
+  hevcdl_dbk_metric_params p;
+  p.recon = d_recon; p.sums = d_sums; p.width = ctx->cfg.width; p.height = ctx->cfg.height; p.n_frames = n_frames; p.sample_bytes = ctx->cfg.bit_depth > 8 ? 2 : 1;
+  p.edges_x = hevcdl_dbk_metric_edges(p.width); p.edges_y = hevcdl_dbk_metric_edges(p.height);
+  if (p.edges_x < 1 || p.edges_y < 1) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "the deblocking metric needs a picture of at least 64 luma samples in either direction");
+  hevcdl_dbk_metric_thresholds(ctx->cfg.qp, ctx->cfg.bit_depth, &p.thr1, &p.thr2);
+  HIPCHK(hipMemsetAsync(d_sums, 0, sizeof(unsigned long long) * 2 * (size_t)n_frames, (hipStream_t)stream));
+  hevcdl_launch_dbk_metric(&p, stream);
+  return launch_status(ctx);
+}
+
+extern "C" hevcdl_status hevcdl_dbk_metric_frames(hevcdl_ctx *ctx, const void *recon, int n_frames, uint64_t *sums)
+{
+  FRAMES_OR_RETURN(ctx, n_frames);
+  if (!recon || !sums) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null pointer");
+  TRY(ensure_staging(ctx));
+  TRY(lazy_alloc(ctx, ctx->dbk.d_sums, sizeof(unsigned long long) * 49 * (size_t)ctx->cfg.max_frames, "deblocking metric sums (cfg.max_frames)"));
+  HIPCHK(hipMemcpy(ctx->stage.d_recon, recon, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
+  TRY(hevcdl_dbk_metric_frames_dev(ctx, ctx->stage.d_recon, n_frames, ctx->dbk.d_sums, nullptr));
+  TRY(sync_or_fail(ctx, "deblocking metric kernel"));
+  HIPCHK(hipMemcpy(sums, ctx->dbk.d_sums, sizeof(unsigned long long) * 2 * (size_t)n_frames, hipMemcpyDeviceToHost));
+  return HEVCDL_OK;
+}
+
+extern "C" hevcdl_status hevcdl_dbk_metric_choice(int width, int height, int bit_depth, uint64_t col_sum, uint64_t row_sum, int pps_beta_offset_div2, int pps_tc_offset_div2,
+                                                  hevcdl_dbk_choice *out)
+{
+  if (!out || width <= 0 || height <= 0 || hevcdl_dbk_metric_edges(width) < 1 || hevcdl_dbk_metric_edges(height) < 1) return HEVCDL_ERR_INVALID_ARG;
+  if (bit_depth < 8 || bit_depth > 16) return HEVCDL_ERR_UNSUPPORTED;
+  const int offset = hevcdl_dbk_metric_offset(width, height, bit_depth, col_sum, row_sum);
+  out->override_enabled = 1; out->override_flag = offset != 0; out->disabled = 0;                  // TEncGOP.cpp:3284-3300 (the PPS of a run with the metric never disables the filter: TEncTop.cpp:1010)
+  out->beta_offset_div2 = offset ? offset : pps_beta_offset_div2; out->tc_offset_div2 = offset ? offset : pps_tc_offset_div2;
+  return HEVCDL_OK;
+}
+
+// ---- DeblockingFilterMetric 2: TEncGOP::applyDeblockingFilterParameterSelection, called at TEncGOP.cpp:1735 ----
+extern "C" hevcdl_status hevcdl_dbk_trial_frames_dev(hevcdl_ctx *ctx, const void *d_org, const void *d_recon, int n_frames, const void *d_records, void *d_tables, void *stream)
+{
+  FRAMES_OR_RETURN(ctx, n_frames);
+  if (!d_org || !d_recon || !d_records || !d_tables) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null device pointer");
+  hevcdl_dbk_trial_params q;
+  memset(&q, 0, sizeof q);
+  hevcdl_dbk_params &p = q.d;
+  p.in = (const uint8_t *)d_recon; p.records = (const unsigned char *)d_records;
+  p.width = ctx->cfg.width; p.height = ctx->cfg.height; p.ctus_x = ctx->ctus_x; p.ctus_per_frame = ctx->ctus; p.n_frames = n_frames;
+  p.pel_max = (1 << ctx->cfg.bit_depth) - 1;
+  p.lf_across_tiles = ctx->cfg.lf_across_tiles != 0; p.tile_cols = ctx->cfg.tile_columns; p.tile_rows = ctx->cfg.tile_rows;
+  memcpy(p.col_bd, ctx->col_bd, sizeof p.col_bd); memcpy(p.row_bd, ctx->row_bd, sizeof p.row_bd);
+  q.org = (const uint8_t *)d_org; q.table = d_tables; q.shift = 2 * (ctx->cfg.bit_depth - 8);
+  for (int b = -3; b <= 3; b++) for (int t = -3; t <= 3; t++) { // the distinct (tc, beta) pairs of luma and the distinct chroma tc values (a function of t alone)
+    int tc, beta, tc_c;
+    dbk_triple(ctx, b, t, &tc, &beta, &tc_c);
+    const int e = 7 * (b + 3) + (t + 3);
+    int j = 0; while (j < q.n_luma && (q.tc[j] != tc || q.beta[j] != beta)) j++;
+    if (j == q.n_luma) { q.tc[j] = tc; q.beta[j] = beta; q.n_luma++; }
+    q.luma_of[e] = j;
+    if (b == -3) { int k = 0; while (k < q.n_chroma && q.tc_c[k] != tc_c) k++; if (k == q.n_chroma) q.tc_c[q.n_chroma++] = tc_c; q.chroma_of[t + 3] = k; }
+  }
+  HIPCHK(hipMemsetAsync(d_tables, 0, sizeof(unsigned long long) * 49 * (size_t)n_frames, (hipStream_t)stream));
+  hevcdl_launch_dbk_trial(&q, stream);
+  return launch_status(ctx);
+}
+
+extern "C" hevcdl_status hevcdl_dbk_trial_frames(hevcdl_ctx *ctx, const void *org, const void *recon, int n_frames, const hevcdl_ctu_record *records, uint64_t *tables)
+{
+  FRAMES_OR_RETURN(ctx, n_frames);
+  if (!org || !recon || !records || !tables) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null pointer");
+  TRY(ensure_staging(ctx));
+  TRY(lazy_alloc(ctx, ctx->dbk.d_sums, sizeof(unsigned long long) * 49 * (size_t)ctx->cfg.max_frames, "deblocking trial tables (cfg.max_frames)"));
+  HIPCHK(hipMemcpy(ctx->stage.d_yuv, org, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(ctx->stage.d_recon, recon, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(ctx->stage.d_records, records, ctx->records_bytes(n_frames), hipMemcpyHostToDevice));
+  TRY(hevcdl_dbk_trial_frames_dev(ctx, ctx->stage.d_yuv, ctx->stage.d_recon, n_frames, ctx->stage.d_records, ctx->dbk.d_sums, nullptr));
+  TRY(sync_or_fail(ctx, "deblocking trial kernels"));
+  HIPCHK(hipMemcpy(tables, ctx->dbk.d_sums, sizeof(unsigned long long) * 49 * (size_t)n_frames, hipMemcpyDeviceToHost));
+  return HEVCDL_OK;
+}
+
+extern "C" hevcdl_status hevcdl_dbk_walk_table(const uint64_t *table, int pps_beta_offset_div2, int pps_tc_offset_div2, int32_t *state4, hevcdl_dbk_choice *out)
+{
+  if (!table || !state4 || !out) return HEVCDL_ERR_INVALID_ARG;
+  hevcdl_dbk_walk_state st = { state4[0], state4[1], state4[2], state4[3] };
+  const hevcdl_dbk_walk_result r = hevcdl_dbk_walk(table, pps_beta_offset_div2, pps_tc_offset_div2, &st);
+  state4[0] = st.available; state4[1] = st.disabled; state4[2] = st.beta_offset_div2; state4[3] = st.tc_offset_div2;
+  out->override_enabled = 1; out->override_flag = r.override_flag; out->disabled = r.disabled; out->beta_offset_div2 = r.beta_offset_div2; out->tc_offset_div2 = r.tc_offset_div2;
+  return HEVCDL_OK;
+}
+
+extern "C" hevcdl_status hevcdl_dbk_select_reset(hevcdl_ctx *ctx)
+{
+  if (!ctx) return HEVCDL_ERR_INVALID_ARG;
+  ctx->dbk.walk = hevcdl_dbk_walk_state{ 0, 0, 0, 0 };
+  return HEVCDL_OK;
+}
+
+extern "C" hevcdl_status hevcdl_get_dbk_choice(hevcdl_ctx *ctx, int first, int count, hevcdl_dbk_choice *out)
+{
+  if (!ctx) return HEVCDL_ERR_INVALID_ARG;
+  if (!out || first < 0 || count < 0 || (long long)first + count > (long long)ctx->dbk.h_choice.size()) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_get_dbk_choice: pictures outside the last picture pipeline call");
+  std::copy(ctx->dbk.h_choice.begin() + first, ctx->dbk.h_choice.begin() + first + count, out);
   return HEVCDL_OK;
 }
 
@@ -1335,6 +1486,8 @@ extern "C" hevcdl_status hevcdl_get_output_frames(hevcdl_ctx *ctx, int first, in
 static hevcdl_status entropy_pipeline(hevcdl_ctx *ctx, int n_frames, int want_sao);
 static hevcdl_status encode_pictures_device(hevcdl_ctx *ctx, const void *yuv, int n_frames, const uint8_t *labels_opt, int deblock, int want_sao, uint8_t **d_final)
 {
+  ctx->dbk.h_choice.clear();
+  if (ctx->cfg.deblocking_metric != 0 && !deblock) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "If DeblockingFilterMetric is non-zero then both LoopFilterDisable and LoopFilterOffsetInPPS must be 0");
   TRY(ensure_staging(ctx));
   if (want_sao) TRY(lazy_alloc(ctx, ctx->sao.d_sao_params, ctx->sao_bytes(ctx->cfg.max_frames), "SAO parameters (cfg.max_frames)"));
   if (want_sao) TRY(lazy_alloc(ctx, ctx->stage.d_picture, ctx->frame_bytes * (size_t)ctx->cfg.max_frames, "output pictures (cfg.max_frames)"));
@@ -1359,7 +1512,33 @@ static hevcdl_status encode_pictures_device(hevcdl_ctx *ctx, const void *yuv, in
     HIPCHK(hipGetLastError());
   }
   *d_final = ctx->stage.d_recon;
-  if (deblock) { TRY(hevcdl_deblock_frames_dev(ctx, ctx->stage.d_recon, n_frames, ctx->stage.d_records, ctx->stage.d_recon, nullptr)); }      // in place
+  { // what every picture's slice header says and its filter runs with: the cfg's values, or (DeblockingFilterMetric 1) what the picture's blockiness asks for -- the
+    // metric launch, two words a picture to the host, the reference's integer lines there, a row of parameters a picture back
+    std::vector<hevcdl_dbk_choice> &ch = ctx->dbk.h_choice;
+    const int enabled = ctx->cfg.deblocking_metric != 0 || ctx->cfg.lf_offset_in_pps == 0;      // TEncTop.cpp:1007-1016
+    const hevcdl_dbk_choice plain = { enabled, enabled, deblock ? 0 : 1, deblock ? ctx->cfg.lf_beta_offset_div2 : 0, deblock ? ctx->cfg.lf_tc_offset_div2 : 0 };
+    ch.assign((size_t)n_frames, plain);
+    if (ctx->cfg.deblocking_metric == 1) {
+      TRY(lazy_alloc(ctx, ctx->dbk.d_sums, sizeof(unsigned long long) * 49 * (size_t)ctx->cfg.max_frames, "deblocking metric sums (cfg.max_frames)"));
+      TRY(hevcdl_dbk_metric_frames_dev(ctx, ctx->stage.d_recon, n_frames, ctx->dbk.d_sums, nullptr));
+      ctx->dbk.h_sums.resize((size_t)2 * n_frames);
+      HIPCHK(hipMemcpy(ctx->dbk.h_sums.data(), ctx->dbk.d_sums, sizeof(unsigned long long) * 2 * (size_t)n_frames, hipMemcpyDeviceToHost));      // (behind the launches of the null stream)
+      for (int i = 0; i < n_frames; i++)
+        hevcdl_dbk_metric_choice(ctx->cfg.width, ctx->cfg.height, ctx->cfg.bit_depth, ctx->dbk.h_sums[2 * i], ctx->dbk.h_sums[2 * i + 1], ctx->cfg.lf_beta_offset_div2, ctx->cfg.lf_tc_offset_div2, &ch[(size_t)i]);
+      TRY(hevcdl_deblock_frames_choice_dev(ctx, ctx->stage.d_recon, n_frames, ctx->stage.d_records, ch.data(), ctx->stage.d_recon, nullptr));      // in place
+    } else if (ctx->cfg.deblocking_metric == 2) { // one trial launch fills a 7 x 7 table a picture; the walk takes the pictures in order, each from the state the one before left
+      TRY(lazy_alloc(ctx, ctx->dbk.d_sums, sizeof(unsigned long long) * 49 * (size_t)ctx->cfg.max_frames, "deblocking trial tables (cfg.max_frames)"));
+      TRY(hevcdl_dbk_trial_frames_dev(ctx, ctx->stage.d_yuv, ctx->stage.d_recon, n_frames, ctx->stage.d_records, ctx->dbk.d_sums, nullptr));
+      ctx->dbk.h_sums.resize((size_t)49 * n_frames);
+      HIPCHK(hipMemcpy(ctx->dbk.h_sums.data(), ctx->dbk.d_sums, sizeof(unsigned long long) * 49 * (size_t)n_frames, hipMemcpyDeviceToHost));
+      for (int i = 0; i < n_frames; i++) {
+        const hevcdl_dbk_walk_result r = hevcdl_dbk_walk((const uint64_t *)&ctx->dbk.h_sums[(size_t)49 * i], ctx->cfg.lf_beta_offset_div2, ctx->cfg.lf_tc_offset_div2, &ctx->dbk.walk);
+        ch[(size_t)i] = hevcdl_dbk_choice{ 1, r.override_flag, r.disabled, r.beta_offset_div2, r.tc_offset_div2 };
+      }
+      TRY(hevcdl_deblock_frames_choice_dev(ctx, ctx->stage.d_recon, n_frames, ctx->stage.d_records, ch.data(), ctx->stage.d_recon, nullptr));      // in place
+    } else
+    if (deblock) { TRY(hevcdl_deblock_frames_dev(ctx, ctx->stage.d_recon, n_frames, ctx->stage.d_records, ctx->stage.d_recon, nullptr)); }      // in place
+  }
   if (want_sao) { TRY(hevcdl_sao_frames_dev(ctx, ctx->stage.d_yuv, ctx->stage.d_recon, n_frames, ctx->sao.d_sao_params, ctx->stage.d_picture, nullptr)); *d_final = ctx->stage.d_picture; }
   ctx->q.h_quality.clear();
   ctx->rp.h_report.clear();

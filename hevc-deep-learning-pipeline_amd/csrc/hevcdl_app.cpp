@@ -61,9 +61,9 @@ const Key KEYS[] = {
   { "NumTileRowsMinus1", 0, USED, 0 }, { "WaveFrontSynchro", 0, USED, 0 }, { "ScalingList", 0, PATH, "0" },
   { "TransquantBypassEnable", 0, PATH, "0" }, { "CUTransquantBypassFlagForce", 0, PATH, "0" },
   // stream / in-loop filter keys
-  { "Level", 0, USED, 0 }, { "DecodingRefreshType", 0, PATH, "1" }, { "ReWriteParamSetsFlag", 0, USED, 0 }, { "LoopFilterOffsetInPPS", 0, PATH, "1" },
+  { "Level", 0, USED, 0 }, { "DecodingRefreshType", 0, PATH, "1" }, { "ReWriteParamSetsFlag", 0, USED, 0 }, { "LoopFilterOffsetInPPS", 0, USED, 0 },
   { "LoopFilterBetaOffset_div2", 0, USED, 0 }, { "LoopFilterTcOffset_div2", 0, USED, 0 },
-  { "DeblockingFilterMetric", 0, PATH, "0" }, { "SAO", 0, USED, 0 }, { "SAOLcuBoundary", 0, PATH, "0" }, { "LFCrossSliceBoundaryFlag", 0, NOEFFECT, 0 },      // (without slices the reference sets it to 1 whatever the cfg says: TAppEncTop.cpp:278-281)
+  { "DeblockingFilterMetric", 0, USED, 0 }, { "SAO", 0, USED, 0 }, { "SAOLcuBoundary", 0, PATH, "0" }, { "LFCrossSliceBoundaryFlag", 0, NOEFFECT, 0 },      // (without slices the reference sets it to 1 whatever the cfg says: TAppEncTop.cpp:278-281)
   { "LFCrossTileBoundaryFlag", 0, USED, 0 }, { "SEIDecodedPictureHash", 0, USED, 0 },
   // quality report (TAppEncCfg.cpp:759-762): MS-SSIM per picture and in the summary, MSE per picture, MSE in the summary; default 0
   { "PrintMSSSIM", 0, USED, 0 }, { "PrintFrameMSE", 0, USED, 0 }, { "PrintSequenceMSE", 0, USED, 0 },
@@ -254,6 +254,7 @@ int main(int argc, char **argv)
   const int level_idc = (int)(atof(opt.get("Level", "6.2").c_str()) * 30.0 + 0.5);      // general_level_idc
   const bool deblock = opt.geti("LoopFilterDisable", 0) == 0;
   const bool sao = opt.geti("SAO", 1) != 0;                                    // TAppEncCfg.cpp: SAO defaults to on
+  const bool filtered = deblock || sao;      // an in-loop filter is on: the log's PSNR is the output picture's, not the reconstruction's before the filters (LoopFilterDisable 1 leaves SAO on)
   // sample bit depth (TAppEncCfg.cpp:770-780): 8 (Profile main) or 10 (Profile main10; the file then holds 16-bit little-endian samples).
   // InternalBitDepth 0 = the input's; OutputBitDepth 0 = the internal one (the reconstruction file's).  The file's samples are scaled to the internal depth on the device and
   // the output back as TVideoIOYuv.cpp:70-95 does: up by a shift, down by a rounding shift and a clip.
@@ -304,6 +305,12 @@ int main(int argc, char **argv)
     const long v = opt.geti(key, 0);
     if (v < -6 || v > 6) opt.errors.push_back(std::string(key) + " = " + std::to_string(v) + " is out of range (-6 .. 6)");
   }
+  // DeblockingFilterMetric (TAppEncCfg.cpp:910): 1 = one deblocking offset per picture from the blockiness of its reconstruction, in the slice header; LoopFilterOffsetInPPS
+  // (:907) 0 = the slice header repeats the cfg's offsets.  The reference's own condition and text (:2143); mode 2 chains every picture's search to the one before it
+  const long dbk_metric = opt.geti("DeblockingFilterMetric", 0), lf_in_pps = opt.geti("LoopFilterOffsetInPPS", 1) != 0;
+  if (dbk_metric < 0 || dbk_metric > 2) opt.errors.push_back("DeblockingFilterMetric = " + std::to_string(dbk_metric) + " is not a value of the key (0, 1 or 2)");
+  else if (dbk_metric != 0 && (!deblock || lf_in_pps)) opt.errors.push_back("If DeblockingFilterMetric is non-zero then both LoopFilterDisable and LoopFilterOffsetInPPS must be 0");
+  else if (dbk_metric == 1 && width > 0 && height > 0 && (width < 64 || height < 64)) opt.errors.push_back("DeblockingFilterMetric = 1 needs a coded picture of at least 64 luma samples in either direction");
   if (hash_sei < 0 || hash_sei > 3) opt.errors.push_back("SEIDecodedPictureHash = " + std::to_string(hash_sei) + " is not a hash of the reference (0 none, 1 MD5, 2 CRC, 3 checksum)");
   // tiles (TAppEncCfg.cpp:1024-1028): uniformly spaced columns x rows or explicit sizes; LFCrossTileBoundaryFlag (default 1) lets the in-loop filters cross tile borders
   const int tile_cols = (int)opt.geti("NumTileColumnsMinus1", 0) + 1, tile_rows = (int)opt.geti("NumTileRowsMinus1", 0) + 1;
@@ -370,6 +377,7 @@ int main(int argc, char **argv)
     while (is >> tok) { const size_t d = tok.find('-'); if (d != std::string::npos && d > 0) { for (int v = atoi(tok.substr(0, d).c_str()); v <= atoi(tok.substr(d + 1).c_str()); v++) devices.push_back(v); } else devices.push_back(atoi(tok.c_str())); }
   } else if (opt.v.count("NumDevices")) { for (int v = 0; v < (int)opt.geti("NumDevices", 1); v++) devices.push_back(v); }
   else devices.push_back((int)opt.geti("Device", 0));
+  if (dbk_metric == 2 && devices.size() > 1) { fprintf(stderr, "Error: DeblockingFilterMetric = 2 on %zu devices: every picture's search window lies round the choice of the picture before it, so the pictures of a sequence are one chain and cannot be dealt to devices; name one device\n", devices.size()); return 2; }
   if (devices.empty() || devices.size() > 64) { fprintf(stderr, "Error: Devices / NumDevices must name 1..64 devices\n"); return 2; }
   const int n_shards = (int)std::min<long>((long)devices.size(), n_frames);
   const bool multi = devices.size() > 1;
@@ -413,6 +421,7 @@ int main(int argc, char **argv)
   if (opt.geti("FastUDIUseMPMEnabled", 1) == 0) tools &= ~HEVCDL_TOOL_FAST_UDI_MPM;
   cfg.tools = tools;
   cfg.lf_beta_offset_div2 = (int)opt.geti("LoopFilterBetaOffset_div2", 0); cfg.lf_tc_offset_div2 = (int)opt.geti("LoopFilterTcOffset_div2", 0);      // -6 .. 6 (hevcdl_create checks)
+  cfg.deblocking_metric = (int)dbk_metric; cfg.lf_offset_in_pps = (int)lf_in_pps;
   cfg.cnn_input = cnn_input == "luma" ? HEVCDL_CNN_INPUT_LUMA : HEVCDL_CNN_INPUT_RGB601;
   cfg.bn_mode = bn_mode == "eval" ? HEVCDL_BN_EVAL : HEVCDL_BN_REFERENCE;
   if (shared_device) cfg.exec_flags |= HEVCDL_EXEC_NO_UNIT_HANDOVER;
@@ -470,6 +479,7 @@ int main(int argc, char **argv)
       i = -1; break;
     }
     if (i < 0) continue;
+    if (st != HEVCDL_OK && hevcdl_create_error()[0]) { fprintf(stderr, "Error: %s\n", hevcdl_create_error()); return 2; }
     if (st == HEVCDL_ERR_INVALID_ARG) { fprintf(stderr, "Error: hevcdl_create rejected the configuration as invalid (e.g. tiles, which must be at least 4 CTUs wide and 1 CTU high: TComPicSym.cpp:380-392)\n"); return 2; }
     if (st != HEVCDL_OK) { fprintf(stderr, "Error: hevcdl_create failed on device %d with status %d (no GPU / unsupported configuration); there is no CPU path\n", shards[i].dev, (int)st); return 3; }
   }
@@ -551,7 +561,7 @@ int main(int argc, char **argv)
     std::vector<uint8_t> labels_mem(label_dir.empty() ? 0 : (size_t)ctus * 16 * sb);
     struct ChunkCtx { long f0; double et; const uint8_t *yuv; std::chrono::steady_clock::time_point t0; int nb; } cc = { 0, 0.0, nullptr, now(), 1 };
     // (with a source format the reconstruction file's frames are made on the device from the pictures in HBM: hevcdl_get_output_frames)
-    const bool want_pictures = device_report ? (frec != nullptr && !use_fmt) : (frec || hash_sei || deblock), want_records = frecords != nullptr;      // what a DeviceEntropy run still fetches from HBM
+    const bool want_pictures = device_report ? (frec != nullptr && !use_fmt) : (frec || hash_sei || filtered), want_records = frecords != nullptr;      // what a DeviceEntropy run still fetches from HBM
     // slice_data / slice_sizes / n_sub: the packed sub-streams of the chunk's pictures (DeviceEntropy), or null: the host codes the records (hevcdl_write_access_unit)
     auto on_chunk = [&](int first, int count, const hevcdl_ctu_record *recs, const void *pictures, const hevcdl_sao_blk *sao_params, const hevcdl_frame_stats *stats,
                         const uint8_t *slice_data, const uint32_t *slice_sizes, int n_sub) -> int {
@@ -565,6 +575,8 @@ int main(int argc, char **argv)
       if (print_msssim) { const hevcdl_status qst = hevcdl_get_quality(S.ctx, first, count, quality.data()); if (qst != HEVCDL_OK) { fprintf(stderr, "Error: %s (status %d)\n", hevcdl_last_error(S.ctx), (int)qst); S.rc = 3; return 1; } }
       std::vector<hevcdl_picture_report_t> reports(device_report ? count : 0);      // DeviceReport: squared errors and digests of the chunk's output pictures, made by the device call
       if (device_report) { const hevcdl_status rst = hevcdl_get_picture_report(S.ctx, first, count, reports.data()); if (rst != HEVCDL_OK) { fprintf(stderr, "Error: %s (status %d)\n", hevcdl_last_error(S.ctx), (int)rst); S.rc = 3; return 1; } }
+      std::vector<hevcdl_dbk_choice> choices(count);          // what every picture's slice header says about its deblocking filter (the cfg's values, or the metric's)
+      { const hevcdl_status cst = hevcdl_get_dbk_choice(S.ctx, first, count, choices.data()); if (cst != HEVCDL_OK) { fprintf(stderr, "Error: %s (status %d)\n", hevcdl_last_error(S.ctx), (int)cst); S.rc = 3; return 1; } }
       {
         std::atomic<int> next(0);
         auto work = [&]() {
@@ -574,8 +586,8 @@ int main(int argc, char **argv)
             PicOut &po = pics[i]; po.md5_text[0] = 0;
             for (int c = 0; c < 3; c++) po.sse[c] = stats[i].sse[c];
             bool coded_order = true;                                           // which plane order po.sse is in (the log wants the file's with YCbCrtoYCrCb, unless SNRInternalColourSpace)
-            if (deblock && device_report) { for (int c = 0; c < 3; c++) po.sse[c] = reports[i].sse[c]; coded_order = false; }      // of the filtered picture, from the device
-            else if (deblock && recon && use_fmt) { // the same over the window: original and output picture at the internal depth, by the library's host functions
+            if (filtered && device_report) { for (int c = 0; c < 3; c++) po.sse[c] = reports[i].sse[c]; coded_order = false; }      // of the filtered picture, from the device
+            else if (filtered && recon && use_fmt) { // the same over the window: original and output picture at the internal depth, by the library's host functions
               // (the original through the file's layout, without the explicit window; the output picture minus the padding, in the coded plane order)
               hevcdl_source_format lf = fmt; lf.output_bit_depth = bit_depth; lf.conf_win_left = lf.conf_win_right = lf.conf_win_top = lf.conf_win_bottom = 0;
               hevcdl_source_format wf = lf; wf.chroma_format = 0; wf.colour_space = 0;
@@ -590,7 +602,7 @@ int main(int argc, char **argv)
                 po.sse[c] = sse; off += wn[c];
               }
             }
-            else if (deblock && recon) { // the picture statistics follow the filtered picture: recomputed here
+            else if (filtered && recon) { // the picture statistics follow the filtered picture: recomputed here
               const uint8_t *o = cc.yuv + frame_bytes * (size_t)(first + i), *r = recon + frame_bytes * (size_t)i;
               const size_t n[3] = { (size_t)width * height, (size_t)width * height / 4, (size_t)width * height / 4 };
               size_t off = 0;
@@ -608,8 +620,8 @@ int main(int argc, char **argv)
             }
             if (file_order && coded_order) std::swap(po.sse[1], po.sse[2]);
             // the access unit: VPS+SPS+PPS+slice, written to -b; its size is the picture's bit count (TEncGOP.cpp:2420-2447)
-            if (slice_data) po.st = hevcdl_write_access_unit_from_slice_data(&scfg, (int)(cc.f0 + first + i), slice_data + slice_at[(size_t)i], slice_sizes + (size_t)i * n_sub, n_sub, buf.data(), buf.size(), &po.au_len);
-            else po.st = hevcdl_write_access_unit(&scfg, (int)(cc.f0 + first + i), recs + (size_t)ctus * i, sao ? sao_params + (size_t)ctus * i : nullptr, buf.data(), buf.size(), &po.au_len);
+            if (slice_data) po.st = hevcdl_write_access_unit_from_slice_data_dbk(&scfg, (int)(cc.f0 + first + i), slice_data + slice_at[(size_t)i], slice_sizes + (size_t)i * n_sub, n_sub, &choices[i], buf.data(), buf.size(), &po.au_len);
+            else po.st = hevcdl_write_access_unit_dbk(&scfg, (int)(cc.f0 + first + i), recs + (size_t)ctus * i, sao ? sao_params + (size_t)ctus * i : nullptr, &choices[i], buf.data(), buf.size(), &po.au_len);
             if (po.st != HEVCDL_OK) continue;
             po.bytes.assign(buf.begin(), buf.begin() + po.au_len);
             if (hash_sei) { // suffix SEI after the slice; not part of the picture's bit count (as in the reference)

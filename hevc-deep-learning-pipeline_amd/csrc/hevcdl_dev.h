@@ -127,6 +127,26 @@ struct hevcdl_dbk_params {
   int tc, beta, tc_c;              // already scaled by 1 << (bit depth - 8) (TComLoopFilter.cpp:596, 770)
   int pel_max;                     // (1 << bit depth) - 1; 255: planes of uint8, otherwise planes of uint16
   int lf_across_tiles, tile_cols, tile_rows, col_bd[21], row_bd[23];   // LFCrossTileBoundaryFlag 0: no edge on a tile border is filtered
+  const int *frame_params;         // NULL, or [frame][4] in HBM: tc, beta, tc_c (scaled like the three above, which are then not read) and disabled (non-zero: the picture passes unfiltered)
+};
+
+// DeblockingFilterMetric 1 (dbk_select_kernel.hip): the two sums of TEncGOP::applyDeblockingFilterMetric per picture
+struct hevcdl_dbk_metric_params {
+  const void *recon;               // [frame] planar 4:2:0 reconstruction before the in-loop filters; only luma is read
+  void *sums;                      // [frame][2] uint64: vertical edges, horizontal edges; zero before the launch
+  int width, height, n_frames, sample_bytes;
+  int edges_x, edges_y;            // edges at multiples of 32 that count: (size >> 5) - 1, both at least 1
+  int thr1, thr2;                  // a line counts when thr1 < a < thr2 (csrc/dbk_select.h hevcdl_dbk_metric_thresholds)
+};
+
+// DeblockingFilterMetric 2 (dbk_select_kernel.hip): the distortion of every filter trial of a picture against its original
+struct hevcdl_dbk_trial_params {
+  struct hevcdl_dbk_params d;      // in = the reconstruction before deblocking, records, sizes, tiles; out / tc / beta / tc_c / frame_params are not read
+  const uint8_t *org;              // [frame] planar 4:2:0 originals
+  void *table;                     // [frame][49] uint64, entry 7 (b + 3) + (t + 3) for slice_beta_offset_div2 b, slice_tc_offset_div2 t; zero before the launch
+  int shift;                       // 2 (bit depth - 8), applied to every sample's squared error
+  int n_luma, tc[49], beta[49], luma_of[49];      // the distinct (tc, beta) pairs, and for every entry the pair it uses
+  int n_chroma, tc_c[7], chroma_of[7];            // the distinct chroma tc values, and for every t the value it uses
 };
 
 // sample adaptive offset (sao_kernel.hip)
@@ -266,6 +286,8 @@ extern "C" {
 #endif
 void hevcdl_launch_sao(const struct hevcdl_sao_params *p, void *stream);
 void hevcdl_launch_deblock(const struct hevcdl_dbk_params *p, void *stream);
+void hevcdl_launch_dbk_metric(const struct hevcdl_dbk_metric_params *p, void *stream);
+void hevcdl_launch_dbk_trial(const struct hevcdl_dbk_trial_params *p, void *stream);
 int hevcdl_quality_scales(int w, int h);
 void hevcdl_quality_layout(struct hevcdl_quality_params *p);      // fills scales / *_off / pyr_* / part_pic from the planes' sizes
 void hevcdl_launch_quality(const struct hevcdl_quality_params *p, void *stream);

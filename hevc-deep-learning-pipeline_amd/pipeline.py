@@ -42,7 +42,8 @@ def read_frames(path, width, height, first, count, bit_depth=8, frame_samples=No
 
 
 def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None, recon_path=None, frame_skip=0, batch=256, tiles=(1, 1),
-                    lf_across_tiles=True, bit_depth=8, level_idc=186, frame_rate=30.0, hash_sei=False, labels_fn=None, device=None, log=print, tools=0x7f, wavefront=False, device_entropy=False, device_report=False, source_format=None):
+                    lf_across_tiles=True, bit_depth=8, level_idc=186, frame_rate=30.0, hash_sei=False, labels_fn=None, device=None, log=print, tools=0x7f, wavefront=False, device_entropy=False, device_report=False, source_format=None,
+                    deblocking_metric=0, lf_offset_in_pps=True):
     """Encode frames [frame_skip, frame_skip + n_frames) of a planar YUV file.  Works stand-alone and under torch.distributed
     (initialised by the caller): rank r takes a contiguous share of the frames.  Returns, on rank 0, the summary (metrics.Summary)
     and the list of per-picture rows [poc, bits, sseY, sseU, sseV]; other ranks return (None, None).
@@ -56,13 +57,25 @@ def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None
     source_format (hevcdl_amd.source_format(...)): the file holds frames of that size and input depth, not of the codec's format; width / height / bit_depth stay the
     CODED size (hevcdl_amd.padded_size) and the internal depth.  The frames go to the device as they are (Encoder.set_source_format), the SPS carries the window, the
     rows' squared errors are the window's and the reconstruction file holds window-sized frames at the format's output depth.  The format also carries the file's layout:
-    a 4:0:0 / 4:2:2 / 4:4:4 file, Cr stored before Cb, an explicit window (its offsets go into the SPS; the squared errors then stay those of the whole picture)."""
+    a 4:0:0 / 4:2:2 / 4:4:4 file, Cr stored before Cb, an explicit window (its offsets go into the SPS; the squared errors then stay those of the whole picture).
+    deblocking_metric / lf_offset_in_pps: the cfg keys DeblockingFilterMetric and LoopFilterOffsetInPPS.  Metric 1 (one deblocking offset per picture from the blockiness
+    of its reconstruction, signalled in the slice header) keeps no state between pictures, so it shards like everything else; it needs lf_offset_in_pps False, as in the
+    reference.  Metric 2 (a search over up to 49 filter trials a picture) searches round the choice of the picture before, so the pictures form one chain: it is refused
+    with more than one rank."""
+    if deblocking_metric not in (0, 1, 2):
+        raise ValueError("DeblockingFilterMetric %r is not a value of the key (0, 1 or 2)" % (deblocking_metric,))
+    if deblocking_metric and lf_offset_in_pps:
+        raise ValueError("If DeblockingFilterMetric is non-zero then both LoopFilterDisable and LoopFilterOffsetInPPS must be 0")
+    dbk = dict(deblocking_metric=deblocking_metric, lf_offset_in_pps=lf_offset_in_pps)
     import torch
     import torch.distributed as dist
     multi = dist.is_available() and dist.is_initialized()
     rank, world = (dist.get_rank(), dist.get_world_size()) if multi else (0, 1)
     if device is None:
         device = int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count())
+    if deblocking_metric == 2 and world > 1:
+        raise ValueError("DeblockingFilterMetric 2 on %d ranks: every picture's search window lies round the choice of the picture before it, so the pictures of a sequence are one "
+                         "chain and cannot be dealt to ranks; run it on one rank" % world)
     mine = sharding.shard_frames(n_frames, world, rank)
     per_rank = sharding.max_shard(n_frames, world)
     rows = np.full((per_rank + 1, 5), -1, np.int64)
@@ -70,7 +83,7 @@ def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None
     part_rec = (recon_path + ".part%d" % rank) if recon_path else None
     fb, fr = open(part_bits, "wb") if part_bits else None, open(part_rec, "wb") if part_rec else None
     if len(mine):
-        enc = Encoder(width, height, qp, max_frames=min(batch, len(mine)), device=device, tiles=tiles, bit_depth=bit_depth, lf_across_tiles=lf_across_tiles, tools=tools, wavefront=wavefront)      # tools: HEVCDL_TOOL_*; wavefront: WaveFrontSynchro mask (the cfg's tool switches)
+        enc = Encoder(width, height, qp, max_frames=min(batch, len(mine)), device=device, tiles=tiles, bit_depth=bit_depth, lf_across_tiles=lf_across_tiles, tools=tools, wavefront=wavefront, **dbk)      # tools: HEVCDL_TOOL_*; wavefront: WaveFrontSynchro mask (the cfg's tool switches)
         sf = source_format
         sw, sh = (sf.source_width, sf.source_height) if sf is not None else (width, height)
         conf_win = (width - sw, height - sh)
@@ -104,11 +117,12 @@ def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None
             et = (time.time() - t0) / nb
             slices, slice_sizes = enc.get_slice_data(0, nb) if device_entropy else (None, None)
             reports = enc.get_picture_report(0, nb) if device_report else None
+            choices = enc.get_dbk_choice(0, nb)      # what every picture's slice header says about its deblocking filter
             def one_picture(i):          # host work of a picture (arithmetic coder, hash, SSE): independent -> thread pool (ctypes drops the GIL)
                 if device_entropy:
-                    au = write_access_unit_from_slice_data(scfg, b0 + i, slices[i], slice_sizes[i])
+                    au = write_access_unit_from_slice_data(scfg, b0 + i, slices[i], slice_sizes[i], choices[i])
                 else:
-                    au = write_access_unit(width, height, qp, b0 + i, recs[i], level_idc=level_idc, sao=sao[i], tiles=tiles, bit_depth=bit_depth, lf_across_tiles=lf_across_tiles, tools=tools, wavefront=wavefront, conf_win=conf_win)
+                    au = write_access_unit(width, height, qp, b0 + i, recs[i], level_idc=level_idc, sao=sao[i], tiles=tiles, bit_depth=bit_depth, lf_across_tiles=lf_across_tiles, tools=tools, wavefront=wavefront, conf_win=conf_win, choice=choices[i])
                 if device_report:
                     return au, digest_sei(1, report_digest(reports[i])) if hash_sei else b"", [int(v) for v in reports[i]["sse"]]
                 sei = picture_hash_sei(width, height, final[i], bit_depth) if hash_sei else b""

@@ -115,6 +115,12 @@ typedef struct hevcdl_config {
    * session (hevcdl_compress_ctu) works on such a context too: the contexts behind the second CTU of every row are kept per session frame, a row's first CTU starts from them
    * whatever state the caller hands in (that IS the reference's behaviour: resetEntropy + loadContexts in front of compressCtu, TEncSlice.cpp:808-823). */
   int32_t  wavefront;
+  /* Per-picture deblocking parameters (section "deblocking parameters chosen per picture" below).  deblocking_metric = DeblockingFilterMetric (default 0): 1 = the blockiness
+   * metric of TEncGOP::applyDeblockingFilterMetric picks one offset for beta and tc per picture; 2 = the trial search of applyDeblockingFilterParameterSelection:
+   * up to 49 pairs (beta, tc) in -3 .. 3 are tried on every picture and the one with the least distortion is signalled.  lf_offset_in_pps = LoopFilterOffsetInPPS (default 1); 0 = the slice header repeats the offsets (deblocking_filter_override_flag 1), the filter
+   * itself runs as before.  A non-zero metric needs lf_offset_in_pps 0 and the filter on, as in the reference (TAppEncCfg.cpp:2143), and metric 1 a picture of at least
+   * 64 luma samples either way (the reference divides by the number of 32-sample columns and rows minus one).  hevcdl_create_error names what was refused. */
+  int32_t  deblocking_metric, lf_offset_in_pps;
 } hevcdl_config;
 
 /* One CTU of decisions: what compressCtu leaves in the picture's CTU record (TEncCu.cpp:1091 copyToPic).
@@ -152,6 +158,9 @@ hevcdl_status hevcdl_config_default_bd(hevcdl_config *cfg, int width, int height
 
 /* weights: flat fp32 blob, HEVCDL_WEIGHT_FLOATS values (replaces torch.load at use_model.py:62). */
 hevcdl_status hevcdl_create(const hevcdl_config *cfg, const float *weights, size_t n_floats, hevcdl_ctx **out);
+/* Why the calling thread's last hevcdl_create refused its configuration: there is no context to ask yet.  ONLY the refusals of the deblocking keys (deblocking_metric,
+ * lf_offset_in_pps) leave a message so far; every other failure of hevcdl_create, and a success, leave "" -- the status is then all there is. */
+const char   *hevcdl_create_error(void);
 void          hevcdl_destroy(hevcdl_ctx *ctx);
 const char   *hevcdl_last_error(const hevcdl_ctx *ctx);
 
@@ -192,6 +201,57 @@ hevcdl_status hevcdl_compress_frames_planes(hevcdl_ctx *ctx, const hevcdl_planes
  * TU grid), out = the picture the reference hands to SAO (may alias recon in the device variant). */
 hevcdl_status hevcdl_deblock_frames(hevcdl_ctx *ctx, const uint8_t *recon, int n_frames, const hevcdl_ctu_record *records, uint8_t *out);
 hevcdl_status hevcdl_deblock_frames_dev(hevcdl_ctx *ctx, const void *d_recon, int n_frames, const void *d_records, void *d_out, void *stream);
+
+/* ---- deblocking parameters chosen per picture (cfg keys DeblockingFilterMetric, LoopFilterOffsetInPPS; csrc/dbk_select_kernel.hip, csrc/dbk_select.h) -------------
+ * What the slice header says about the deblocking filter of ONE picture and what the filter ran with (TEncCavlc.cpp:1080-1095).  Without override_flag the picture uses the
+ * PPS's values, and the other three fields hold exactly those. */
+typedef struct hevcdl_dbk_choice {
+  int32_t override_enabled;                    /* deblocking_filter_override_enabled_flag of the PPS the picture is coded under: DeblockingFilterMetric != 0 or
+                                                  LoopFilterOffsetInPPS 0 (TEncTop.cpp:1007-1016).  A property of the STREAM carried with every picture: it must be the
+                                                  same for all pictures of a stream (hevcdl_get_dbk_choice gives it so); the writers put it into the PPS in front of the
+                                                  picture they are called for, so with rewrite_param_sets 0 picture 0's value is the one a decoder sees */
+  int32_t override_flag;                       /* deblocking_filter_override_flag */
+  int32_t disabled;                            /* slice_deblocking_filter_disabled_flag */
+  int32_t beta_offset_div2, tc_offset_div2;    /* slice_beta_offset_div2 / slice_tc_offset_div2 */
+} hevcdl_dbk_choice;
+/* DeblockingFilterMetric 1, the measurement: for n_frames reconstructions BEFORE deblocking (coded size, padding included) the two exact sums of
+ * TEncGOP::applyDeblockingFilterMetric (TEncGOP.cpp:3216-3268), sums[i][0] over the vertical edges at multiples of 32 and sums[i][1] over the horizontal ones: |p0 - q0| of
+ * every line whose a = (|p2 - 2 p1 + p0| + |q0 - 2 q1 + q2|) << 1 lies strictly between 2 << (bit depth - 8) and (beta(QP) << (bit depth - 8)) >> 2.  Of the edges only the
+ * first (width >> 5) - 1 and (height >> 5) - 1 count, as in the reference: at a size that is no multiple of 32 the last edge is dropped.  A picture under 64 samples
+ * either way is HEVCDL_ERR_INVALID_ARG.  The device variant is asynchronous on `stream`; d_sums: [n_frames][2] uint64. */
+hevcdl_status hevcdl_dbk_metric_frames(hevcdl_ctx *ctx, const void *recon, int n_frames, uint64_t *sums);
+hevcdl_status hevcdl_dbk_metric_frames_dev(hevcdl_ctx *ctx, const void *d_recon, int n_frames, void *d_sums, void *stream);
+/* ... and the decision (TEncGOP.cpp:3270-3301; host only, no GPU needed): the two sums of a width x height picture -> the picture's choice.  Above the threshold: override
+ * with one offset 2 .. 6 for beta and tc; otherwise no override and the PPS's values (pps_beta_offset_div2, pps_tc_offset_div2).  override_enabled is 1 either way. */
+hevcdl_status hevcdl_dbk_metric_choice(int width, int height, int bit_depth, uint64_t col_sum, uint64_t row_sum, int pps_beta_offset_div2, int pps_tc_offset_div2,
+                                       hevcdl_dbk_choice *out);
+/* hevcdl_deblock_frames with parameters per picture: choices[i] = what picture i is filtered with (disabled: the picture is copied; override_flag is not looked at).
+ * choices == NULL is hevcdl_deblock_frames itself.  The device variant takes the choices from HOST memory too and synchronises nothing; d_out may alias d_recon.  The rows
+ * are staged in the context (one host copy, one device buffer): like every launch of a context, one such call at a time -- a second call must not be issued before the
+ * first has finished on the device, on whatever stream. */
+hevcdl_status hevcdl_deblock_frames_choice(hevcdl_ctx *ctx, const uint8_t *recon, int n_frames, const hevcdl_ctu_record *records, const hevcdl_dbk_choice *choices, uint8_t *out);
+hevcdl_status hevcdl_deblock_frames_choice_dev(hevcdl_ctx *ctx, const void *d_recon, int n_frames, const void *d_records, const hevcdl_dbk_choice *choices, void *d_out, void *stream);
+/* DeblockingFilterMetric 2, the trials: for n_frames pictures one launch fills tables[i][49], entry 7 (b + 3) + (t + 3) = the distortion (xFindDistortionFrame,
+ * TEncGOP.cpp:2172-2200: all three components, (d * d) >> 2 (bit depth - 8) per sample) of the original against the reconstruction deblocked with slice_beta_offset_div2 b
+ * and slice_tc_offset_div2 t, b, t in -3 .. 3 -- every entry, also those the reference's walk would not visit.  No trial picture is written to memory.  The device variant is
+ * asynchronous on `stream`; d_tables: [n_frames][49] uint64. */
+hevcdl_status hevcdl_dbk_trial_frames(hevcdl_ctx *ctx, const void *org, const void *recon, int n_frames, const hevcdl_ctu_record *records, uint64_t *tables);
+hevcdl_status hevcdl_dbk_trial_frames_dev(hevcdl_ctx *ctx, const void *d_org, const void *d_recon, int n_frames, const void *d_records, void *d_tables, void *stream);
+/* ... and the walk (TEncGOP.cpp:3335-3420; host only, no GPU needed; csrc/dbk_select.h): one table and the carried state -- state4 = the reference's m_DBParam[0]:
+ * available, disabled, beta, tc; all zero at the start of a sequence -- -> the picture's choice; state4 is advanced.  The search windows are +-1 (beta) and +-2 (tc) round
+ * the previous picture's best, so the result depends on the ORDER of the pictures. */
+hevcdl_status hevcdl_dbk_walk_table(const uint64_t *table, int pps_beta_offset_div2, int pps_tc_offset_div2, int32_t *state4, hevcdl_dbk_choice *out);
+/* With deblocking_metric 2 the picture pipelines keep that state in the context and advance it picture by picture ACROSS calls: the pictures of a sequence must reach one
+ * context in POC order, call after call.  A caller that deals pictures out of order, or over several contexts, gets other choices than the reference; that is the caller's
+ * problem, the library cannot see it.  hevcdl_dbk_select_reset starts a new sequence (the state of a fresh context). */
+hevcdl_status hevcdl_dbk_select_reset(hevcdl_ctx *ctx);
+/* The choices of pictures [first, first + count) of the LAST hevcdl_encode_pictures / _chunked / _stream call -- valid inside the chunk callback and after the call returns,
+ * like hevcdl_get_slice_data; they feed hevcdl_write_access_unit_dbk / hevcdl_write_access_unit_from_slice_data_dbk.  With deblocking_metric 1 the pipeline measures the
+ * reconstruction behind the decisions, fetches two sums a picture, decides on the host and deblocks every picture with its own parameters; the metric keeps no state, so
+ * pictures may be dealt to contexts, devices and calls in any way; with deblocking_metric 2 it runs the trial launch, fetches 49 words a picture and walks them in
+ * order (see above).  Without the metric every picture carries the cfg's values (override_enabled = override_flag =
+ * !lf_offset_in_pps). */
+hevcdl_status hevcdl_get_dbk_choice(hevcdl_ctx *ctx, int first, int count, hevcdl_dbk_choice *out);
 
 /* ---- sample adaptive offset (second in-loop filter) ---------------------------------------------------
  * Replaces TEncSampleAdaptiveOffset::SAOProcess (TLibEncoder/TEncSampleAdaptiveOffset.cpp:244, called at TEncGOP.cpp:1797):
@@ -387,7 +447,7 @@ hevcdl_status hevcdl_store_output_host(const hevcdl_source_format *fmt, int code
  * codeSPS / codePPS / codeSliceHeader (TEncCavlc.cpp:677, 500, 189, 755), TEncSlice::encodeSlice (TEncSlice.cpp:985) and
  * the arithmetic coder TEncBinCABAC (TEncBinCoderCABAC.cpp:187-446) for the CTU records hevcdl_compress_frames
  * returns.  sao == NULL (cfg.sao_enabled 0): sample_adaptive_offset_enabled_flag 0; otherwise the [ctus] parameters
- * hevcdl_sao_frames returned are coded in front of every CTU.  loop_filter_disable != 0 -> HEVCDL_ERR_UNSUPPORTED. */
+ * hevcdl_sao_frames returned are coded in front of every CTU. */
 typedef struct hevcdl_stream_config {
   uint32_t struct_size;          /* sizeof(hevcdl_stream_config) */
   int32_t  width, height, qp;    /* as in hevcdl_config */
@@ -425,6 +485,15 @@ size_t        hevcdl_access_unit_bound(int width, int height);
 hevcdl_status hevcdl_write_access_unit(const hevcdl_stream_config *cfg, int poc, const hevcdl_ctu_record *records, const hevcdl_sao_blk *sao,
                                        uint8_t *out, size_t capacity, size_t *out_len);
 
+/* The same for a stream whose slice headers carry deblocking parameters (DeblockingFilterMetric, LoopFilterOffsetInPPS 0): choice = what hevcdl_get_dbk_choice returned
+ * for the picture.  The stream configuration has no field for the two keys; everything they change in the stream is in the choice: override_enabled sets
+ * deblocking_filter_override_enabled_flag in the PPS (which keeps cfg's loop_filter_disable and offsets), and the slice header then carries
+ * deblocking_filter_override_flag and, behind a 1, the picture's own values (TEncTop.cpp:1007-1035, TEncCavlc.cpp:1080-1095).  LoopFilterOffsetInPPS 0 alone: every slice
+ * repeats the cfg's values (TEncSlice.cpp:388-404), loop_filter_disable included.  NULL is hevcdl_write_access_unit itself.  A choice the PPS cannot carry --
+ * override_flag without override_enabled, or no override_flag with values that are not the PPS's -- is HEVCDL_ERR_INVALID_ARG. */
+hevcdl_status hevcdl_write_access_unit_dbk(const hevcdl_stream_config *cfg, int poc, const hevcdl_ctu_record *records, const hevcdl_sao_blk *sao,
+                                           const hevcdl_dbk_choice *choice, uint8_t *out, size_t capacity, size_t *out_len);
+
 /* ---- slice data coded apart from the access unit (csrc/entropy_coder.h: one coder source for the host and the device) -------------------
  * The slice data of a picture is its sub-streams back to back: one per tile in raster order of the tile grid, one per CTU row with wavefront, otherwise one; each
  * is the arithmetic coder's bytes of its CTUs followed by byte_alignment().  hevcdl_write_access_unit_from_slice_data writes everything around that payload exactly as
@@ -432,6 +501,8 @@ hevcdl_status hevcdl_write_access_unit(const hevcdl_stream_config *cfg, int poc,
  * that for the same decisions the two give the same bytes (the slice data of both comes from that one source).  data: the n_substreams sub-streams of picture `poc`, packed; sizes: their lengths. */
 hevcdl_status hevcdl_write_access_unit_from_slice_data(const hevcdl_stream_config *cfg, int poc, const uint8_t *data, const uint32_t *sizes, int n_substreams,
                                                        uint8_t *out, size_t capacity, size_t *out_len);
+hevcdl_status hevcdl_write_access_unit_from_slice_data_dbk(const hevcdl_stream_config *cfg, int poc, const uint8_t *data, const uint32_t *sizes, int n_substreams,
+                                                           const hevcdl_dbk_choice *choice, uint8_t *out, size_t capacity, size_t *out_len);      /* choice: as hevcdl_write_access_unit_dbk */
 /* TEST AND DIAGNOSTIC entry points (host buffers in and out; the picture pipeline's form is hevcdl_enable_device_entropy above).
  * hevcdl_slice_data_layout: where the coder puts the sub-streams of ONE picture in a slice-data buffer.  Sub-stream k owns the region [offsets[k], offsets[k] +
  * capacities[k]), capacities[k] = (its CTUs) x capacity_per_ctu + 64, and the regions lie 64 bytes apart: the coder writes nothing but the regions, so a caller may keep a
