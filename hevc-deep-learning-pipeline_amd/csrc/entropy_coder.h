@@ -60,6 +60,8 @@ struct EcPic {
   int W, H, ctus_x, ctus_y, ctus;
   int tx0, ty0;                  // top-left luma sample of the tile being written: nothing left of / above it is a neighbour
   uint32_t tools; int max_sao_offset;
+  int slice_end_ctu = -1;        // raster address of the last CTU of the sub-stream when a slice ends with it; -1: none but the picture's last CTU ends a slice (no slices, or a
+                                 // sub-stream inside a slice).  The one member with a default: code that fills an EcPic field by field and knows no slices needs no change
 };
 struct EcCu { int x, y, log2, depth, zbase, nparts, part; const hevcdl_ctu_record *r; };
 struct EcTu { int log2, trd, zrel; };
@@ -494,14 +496,20 @@ EC_FN void ec_unit_rect(int wpp, int tcols, const int *col_bd, const int *row_bd
   cx0 = col_bd[tc]; cx1 = col_bd[tc + 1]; cy0 = row_bd[tr]; cy1 = row_bd[tr + 1];
 }
 
-// one CTU of a sub-stream: its SAO parameters, its coding quadtree, end_of_slice_segment_flag 0 unless it is the picture's last (TEncSlice.cpp:1075-1136)
+// Does sub-stream k of `units` end a slice?  slice_units: sub-streams (tiles) per slice -- 0: one slice a picture; SliceMode 1 (a grid of one column, a slice per row
+// of it): 1; SliceMode 3: SliceArgument, the last slice taking what is left (TEncSlice::calculateBoundingCtuTsAddrForSlice, FIXED_NUMBER_OF_TILES).
+EC_FN int ec_ends_slice(int slice_units, int k, int units) { return k == units - 1 || (slice_units > 0 && (k + 1) % slice_units == 0); }
+// ... and p.slice_end_ctu of that sub-stream, the CTUs [cx0, cx1) x [cy0, cy1)
+EC_FN int ec_slice_end_ctu(int ends_slice, int ctus_x, int cx1, int cy1) { return ends_slice ? (cy1 - 1) * ctus_x + cx1 - 1 : -1; }
+
+// one CTU of a sub-stream: its SAO parameters, its coding quadtree, end_of_slice_segment_flag 0 unless it is the last of its slice (TEncSlice.cpp:1075-1136)
 EC_FN void ec_code_ctu(EcCoder &s, const EcPic &p, int cx, int cy)
 {
   const int a = cy * p.ctus_x + cx;
   if ((unsigned)a >= (unsigned)p.ctus) return;
   if (p.sao) ec_code_sao_blk(s, p.sao[a], cx * 64 > p.tx0, cy * 64 > p.ty0, p.max_sao_offset);      // merge candidates stay inside the tile (TComPic::getSAOMergeAvailability)
   ec_code_cu_tree(s, p, cx, cy);
-  if (a != p.ctus - 1) ec_terminate(s, 0);
+  if (a != p.ctus - 1 && a != p.slice_end_ctu) ec_terminate(s, 0);
 }
 // the CTUs [cx0, cx1) x [cy0, cy1) in raster order, then the sub-stream's end: terminating 1 bin, coder flush, byte_alignment().  The contexts are the caller's
 // (slice-start contexts, or the stored ones of a WaveFrontSynchro row).

@@ -12,6 +12,7 @@
 #include "picture_hash_core.h"
 #include "source_core.h"
 #include "rd_launch_plan.h"
+#include "slice_grid.h"
 
 enum { LABELS_PER_CTU = 16, LOGITS_PER_CTU = 64, CTU_RGB_BYTES = 64 * 64 * 3 };      // of a CTU: its 16x16 cells, four logits a cell, the RGB input of hevcdl_predict_depth_rgb
 
@@ -141,7 +142,9 @@ struct RdWorkspace {
 
 struct hevcdl_ctx {
   char last_rd[160] = { 0 };           // which build and launch form the last decision launch took (hevcdl_last_rd_launch)
-  hevcdl_config cfg = {};
+  hevcdl_config cfg = {};              // as created -- but with slices its tile fields hold the grid the context RUNS (hevcdl_create): a column of row slices for SliceMode 1
+  hevcdl_slice_layout slices = { 0, 0, 1 };      // what the caller's slice keys say; the stream is written from this, never from the grid
+  int stream_lf_across_tiles = 1;      // the caller's lf_across_tiles (cfg's is the effective one: in SliceMode 3 combined with lf_across_slices)
   int ctus_x = 0, ctus_y = 0, ctus = 0, n_cus = 0; size_t frame_bytes = 0;
   int col_bd[21] = { 0 }, row_bd[23] = { 0 };    // tile boundaries in CTUs
   DevBuf<float> d_weights, d_a3; size_t a3_ctus = 0;   // d_a3: conv3 outputs of one chunk of CTUs (32 KB per CTU): the hand-over from the conv kernel to the head kernel
@@ -232,7 +235,7 @@ extern "C" hevcdl_status hevcdl_config_default_bd(hevcdl_config *cfg, int width,
   cfg->width = width; cfg->height = height; cfg->bit_depth = bit_depth; cfg->chroma_format = 420; cfg->qp = qp;
   cfg->ctu_size = 64; cfg->max_partition_depth = 4; cfg->tu_log2_min = 2; cfg->tu_log2_max = 5; cfg->tu_max_depth_intra = 3;
   cfg->tools = HEVCDL_TOOLS_REFERENCE; cfg->bn_mode = HEVCDL_BN_REFERENCE; cfg->boundary_policy = HEVCDL_BOUNDARY_CLAMP;
-  cfg->cnn_input = HEVCDL_CNN_INPUT_RGB601; cfg->device = 0; cfg->max_frames = 1; cfg->tile_columns = 1; cfg->tile_rows = 1; cfg->tile_uniform_spacing = 1; cfg->lf_across_tiles = 1; cfg->lf_offset_in_pps = 1;
+  cfg->cnn_input = HEVCDL_CNN_INPUT_RGB601; cfg->device = 0; cfg->max_frames = 1; cfg->tile_columns = 1; cfg->tile_rows = 1; cfg->tile_uniform_spacing = 1; cfg->lf_across_tiles = 1; cfg->lf_offset_in_pps = 1; cfg->lf_across_slices = 1;
   // TEncSlice::calculateLambda (TEncSlice.cpp:433-527) for an all-intra GOP of 1, then setUpLambda (:112-140)
   cfg->lambda = 0.57 * 1.0 * pow(2.0, (qp - 12) / 3.0);
   cfg->sqrt_lambda = sqrt(cfg->lambda);                         // TComRdCost::setLambda TComRdCost.cpp:109-122
@@ -393,11 +396,16 @@ extern "C" hevcdl_status hevcdl_create(const hevcdl_config *cfg, const float *we
   if (cfg->deblocking_metric != 0 && cfg->lf_offset_in_pps != 0) return refuse(HEVCDL_ERR_INVALID_ARG, "If DeblockingFilterMetric is non-zero then both LoopFilterDisable and LoopFilterOffsetInPPS must be 0");
   if (cfg->deblocking_metric == 1 && (hevcdl_dbk_metric_edges(cfg->width) < 1 || hevcdl_dbk_metric_edges(cfg->height) < 1))
     return refuse(HEVCDL_ERR_INVALID_ARG, "DeblockingFilterMetric 1 needs a coded picture of at least 64 luma samples in either direction (the reference asserts noCol > 1 && noRows > 1)");
+  // Slices: the grid the context runs (slice_grid.h) -- a column of row slices for SliceMode 1, the cfg's tiles otherwise
+  hevcdl_config grid;
+  { const char *why = ""; const hevcdl_status gs = hevcdl_slice_grid(cfg, &grid, &why); if (gs != HEVCDL_OK) return refuse(gs, why); }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device >= ndev) return HEVCDL_ERR_NO_DEVICE;
   hevcdl_ctx *ctx = new (std::nothrow) hevcdl_ctx();
   if (!ctx) return HEVCDL_ERR_OOM;
-  ctx->cfg = *cfg;
+  ctx->cfg = grid; ctx->stream_lf_across_tiles = cfg->lf_across_tiles;
+  ctx->slices.mode = cfg->slice_mode; ctx->slices.argument = cfg->slice_mode ? cfg->slice_argument : 0; ctx->slices.lf_across_slices = cfg->slice_mode ? cfg->lf_across_slices != 0 : 1;
+  cfg = &ctx->cfg;      // the one place the grid comes from
   ctx->ctus_x = (cfg->width + 63) >> 6; ctx->ctus_y = (cfg->height + 63) >> 6; ctx->ctus = ctx->ctus_x * ctx->ctus_y;
   ctx->frame_bytes = hevcdl_frame_bytes_bd(cfg->width, cfg->height, cfg->bit_depth);
   hevcdl_tile_bounds(ctx->ctus_x, cfg->tile_columns, cfg->tile_uniform_spacing, cfg->tile_column_width, 1, ctx->col_bd);
@@ -436,10 +444,9 @@ extern "C" hevcdl_status hevcdl_create(const hevcdl_config *cfg, const float *we
   CK(hipMemcpy(ctx->d_weights, pk.data(), sizeof(float) * HEVCDL_W_TOTAL, hipMemcpyHostToDevice));
   for (int b = 0; b < RD_BUILDS; b++)       // the largest of the builds this context can run: the three 8-bit ones, or the 10-bit one
     if ((b == RD_BD10) == (cfg->bit_depth != 8)) ctx->rd.scratch_per_wave = std::max(ctx->rd.scratch_per_wave, rd_builds[b].scratch_bytes());
-  { RdPlanContext &pc = ctx->rd.plan;      // what the launch plan reads (rd_launch_plan.h)
-    pc.n_cus = ctx->n_cus; pc.max_frames = cfg->max_frames; pc.bit_depth = cfg->bit_depth; pc.tools = cfg->tools; pc.exec_flags = cfg->exec_flags; pc.wavefront = cfg->wavefront;
-    pc.tile_columns = cfg->tile_columns; pc.tile_rows = cfg->tile_rows; pc.ctus_x = ctx->ctus_x; pc.ctus_y = ctx->ctus_y;
-    for (int b = 0; b < RD_BUILDS; b++) pc.waves[b] = rd_builds[b].waves_per_group(); }
+  { int waves[RD_BUILDS];                  // what the launch plan reads (rd_launch_plan.h)
+    for (int b = 0; b < RD_BUILDS; b++) waves[b] = rd_builds[b].waves_per_group();
+    ctx->rd.plan = rd_plan_context_of(*cfg, ctx->n_cus, waves); }
   // (the workspace itself -- 1.6 MB per wave -- is sized by the launches: a context that only ever codes a frame or two in the independent form holds a few MB, not the
   // several GB a launch on every CU needs)
   CK(hipFuncSetAttribute((const void *)hevcdl_cnn_ctu_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hevcdl_cnn_smem_bytes()));
@@ -1641,28 +1648,32 @@ struct EntropyPlan {
   hevcdl_entropy_params k;             // geometry, QP, tools filled; pointers not
   std::vector<uint32_t> off, cap; size_t frame_stride; int units;
 };
-static hevcdl_status entropy_plan(const hevcdl_stream_config *cfg, int capacity_per_ctu, EntropyPlan &pl)
+static hevcdl_status entropy_plan(const hevcdl_stream_config *cfg, const hevcdl_slice_layout *layout, int capacity_per_ctu, EntropyPlan &pl)
 {
   int n = 0; size_t bytes = 0;
-  TRY(hevcdl_slice_data_layout(cfg, capacity_per_ctu, &n, &bytes, nullptr, nullptr));
+  TRY(hevcdl_slice_data_layout_slices(cfg, layout, capacity_per_ctu, &n, &bytes, nullptr, nullptr));
   pl.off.resize((size_t)n); pl.cap.resize((size_t)n);
-  TRY(hevcdl_slice_data_layout(cfg, capacity_per_ctu, &n, &bytes, pl.off.data(), pl.cap.data()));
+  TRY(hevcdl_slice_data_layout_slices(cfg, layout, capacity_per_ctu, &n, &bytes, pl.off.data(), pl.cap.data()));
   pl.units = n; pl.frame_stride = bytes;
   hevcdl_entropy_params &k = pl.k; memset(&k, 0, sizeof k);
   k.width = cfg->width; k.height = cfg->height; k.ctus_x = (cfg->width + 63) >> 6; k.ctus_y = (cfg->height + 63) >> 6; k.qp = cfg->qp; k.tools = (int)cfg->tools;
-  k.max_sao_offset = (1 << ((cfg->bit_depth < 10 ? cfg->bit_depth : 10) - 5)) - 1; k.wpp = cfg->wavefront != 0; k.tile_cols = cfg->tile_columns; k.units = n; k.frame_stride = bytes;
-  const int tiled = cfg->tile_columns * cfg->tile_rows > 1, uniform = cfg->tile_uniform_spacing != 0;
-  if (hevcdl_tile_bounds(k.ctus_x, cfg->tile_columns, uniform, cfg->tile_column_width, tiled ? 4 : 1, k.col_bd) || hevcdl_tile_bounds(k.ctus_y, cfg->tile_rows, uniform, cfg->tile_row_height, 1, k.row_bd))
-    return HEVCDL_ERR_INVALID_ARG;
-  return HEVCDL_OK;
+  k.max_sao_offset = (1 << ((cfg->bit_depth < 10 ? cfg->bit_depth : 10) - 5)) - 1; k.wpp = cfg->wavefront != 0; k.units = n; k.frame_stride = bytes;
+  int rows = 0;
+  return (hevcdl_status)hevcdl_substream_grid(cfg, layout, &k.tile_cols, &rows, k.col_bd, k.row_bd, &k.slice_units);    // the writer's own grid: the cfg's tiles, or a column of row slices
 }
 
 extern "C" hevcdl_status hevcdl_code_slice_data(int device, const hevcdl_stream_config *cfg, const hevcdl_ctu_record *records, const hevcdl_sao_blk *sao_opt, int n_frames,
                                                 int capacity_per_ctu, uint8_t *out, size_t out_capacity, uint32_t *sizes, uint32_t *overflow)
 {
+  return hevcdl_code_slice_data_slices(device, cfg, nullptr, records, sao_opt, n_frames, capacity_per_ctu, out, out_capacity, sizes, overflow);
+}
+
+extern "C" hevcdl_status hevcdl_code_slice_data_slices(int device, const hevcdl_stream_config *cfg, const hevcdl_slice_layout *layout, const hevcdl_ctu_record *records,
+                                                       const hevcdl_sao_blk *sao_opt, int n_frames, int capacity_per_ctu, uint8_t *out, size_t out_capacity, uint32_t *sizes, uint32_t *overflow)
+{
   if (!cfg || !records || !out || !sizes || !overflow || n_frames < 0) return HEVCDL_ERR_INVALID_ARG;
   EntropyPlan pl;
-  TRY(entropy_plan(cfg, capacity_per_ctu, pl));
+  TRY(entropy_plan(cfg, layout, capacity_per_ctu, pl));
   if ((cfg->sao_enabled != 0) != (sao_opt != nullptr)) return HEVCDL_ERR_INVALID_ARG;
   if (out_capacity / (pl.frame_stride ? pl.frame_stride : 1) < (size_t)n_frames) return HEVCDL_ERR_INVALID_ARG;
   if (n_frames == 0) return HEVCDL_OK;
@@ -1701,9 +1712,18 @@ static void entropy_stream_config(const hevcdl_ctx *ctx, int want_sao, hevcdl_st
 {
   const hevcdl_config &c = ctx->cfg;
   hevcdl_stream_config_default(sc, c.width, c.height, c.qp);
-  sc->sao_enabled = want_sao != 0; sc->tile_columns = c.tile_columns; sc->tile_rows = c.tile_rows; sc->bit_depth = c.bit_depth; sc->tile_uniform_spacing = c.tile_uniform_spacing;
+  sc->sao_enabled = want_sao != 0; sc->bit_depth = c.bit_depth; sc->tools = c.tools; sc->wavefront = c.wavefront;
+  if (ctx->slices.mode == 1) return;      // the context's grid is the slices': the stream has no tiles, the writer derives the sub-streams from ctx->slices
+  sc->tile_columns = c.tile_columns; sc->tile_rows = c.tile_rows; sc->tile_uniform_spacing = c.tile_uniform_spacing;
   memcpy(sc->tile_column_width, c.tile_column_width, sizeof sc->tile_column_width); memcpy(sc->tile_row_height, c.tile_row_height, sizeof sc->tile_row_height);
-  sc->lf_across_tiles = c.lf_across_tiles; sc->tools = c.tools; sc->wavefront = c.wavefront;
+  sc->lf_across_tiles = ctx->stream_lf_across_tiles;
+}
+
+extern "C" hevcdl_status hevcdl_get_slice_layout(const hevcdl_ctx *ctx, hevcdl_slice_layout *out)
+{
+  if (!ctx || !out) return HEVCDL_ERR_INVALID_ARG;
+  *out = ctx->slices;
+  return HEVCDL_OK;
 }
 
 static void entropy_release(hevcdl_ctx *ctx)
@@ -1724,7 +1744,7 @@ extern "C" hevcdl_status hevcdl_enable_device_entropy(hevcdl_ctx *ctx, int on)
   if (ctx->ec.entropy_on) return HEVCDL_OK;
   hevcdl_stream_config sc; entropy_stream_config(ctx, 0, &sc);
   EntropyPlan pl;
-  const hevcdl_status st = entropy_plan(&sc, ctx->ec_capacity_per_ctu, pl); if (st) return fail(ctx, st, "device entropy: stream configuration");
+  const hevcdl_status st = entropy_plan(&sc, &ctx->slices, ctx->ec_capacity_per_ctu, pl); if (st) return fail(ctx, st, "device entropy: stream configuration");
   // the workspace holds the regions of at most ENTROPY_WS_BYTES worth of pictures (84 MB a picture at 2160p: 2040 CTUs x 40 KB); larger batches go through it in passes
   const size_t ENTROPY_WS_BYTES = (size_t)512 << 20;
   const int pass = (int)std::max<size_t>(1, std::min<size_t>((size_t)ctx->cfg.max_frames, ENTROPY_WS_BYTES / pl.frame_stride));
@@ -1748,7 +1768,7 @@ static hevcdl_status entropy_pipeline(hevcdl_ctx *ctx, int n_frames, int want_sa
 {
   hevcdl_stream_config sc; entropy_stream_config(ctx, want_sao, &sc);
   EntropyPlan pl;
-  hevcdl_status st = entropy_plan(&sc, ctx->ec_capacity_per_ctu, pl); if (st) return fail(ctx, st, "device entropy: stream configuration");
+  hevcdl_status st = entropy_plan(&sc, &ctx->slices, ctx->ec_capacity_per_ctu, pl); if (st) return fail(ctx, st, "device entropy: stream configuration");
   const int units = ctx->ec.ec_units;
   ctx->ec_ms[0] = ctx->ec_ms[1] = ctx->ec_ms[2] = 0;
   Event ev[5];      // with the profile switch: start, between the two launches, end of the coding, around the pack launch
@@ -1809,9 +1829,9 @@ static hevcdl_status entropy_pipeline(hevcdl_ctx *ctx, int n_frames, int want_sa
         HIPCHK(hipMemcpy(rec.data(), ctx->stage.d_records + rec_b * f, rec_b, hipMemcpyDeviceToHost));
         if (want_sao) HIPCHK(hipMemcpy(sao.data(), ctx->sao.d_sao_params + sao_b * f, sao_b, hipMemcpyDeviceToHost));
         size_t total = 0; uint32_t *sz = ctx->ec.h_slice_sizes.data() + (size_t)f * units;
-        hevcdl_host_writer_slice_data(&sc, rec.data(), want_sao ? sao.data() : nullptr, nullptr, 0, sz, &total);
+        hevcdl_host_writer_slice_data(&sc, &ctx->slices, rec.data(), want_sao ? sao.data() : nullptr, nullptr, 0, sz, &total);
         all.resize(at[(size_t)f] + total);
-        if (hevcdl_host_writer_slice_data(&sc, rec.data(), want_sao ? sao.data() : nullptr, all.data() + at[(size_t)f], total, sz, &total) != 0) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "device entropy: host fallback");
+        if (hevcdl_host_writer_slice_data(&sc, &ctx->slices, rec.data(), want_sao ? sao.data() : nullptr, all.data() + at[(size_t)f], total, sz, &total) != 0) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "device entropy: host fallback");
       } else all.insert(all.end(), ctx->ec.h_slice.begin() + (ptrdiff_t)ctx->ec.h_slice_at[(size_t)f], ctx->ec.h_slice.begin() + (ptrdiff_t)ctx->ec.h_slice_at[(size_t)f + 1]);
     }
     at[(size_t)n_frames] = all.size();
@@ -1878,6 +1898,7 @@ extern "C" hevcdl_status hevcdl_encode_pictures_stream(hevcdl_ctx *ctx, const vo
 extern "C" hevcdl_status hevcdl_begin_frames(hevcdl_ctx *ctx, const uint8_t *yuv, int n_frames, const uint8_t *labels_opt, uint8_t *labels_out_opt)
 {
   TRY(check_frames(ctx, n_frames));
+  if (ctx->slices.mode != 0) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "begin_frames: the per-CTU session does not code slices; use hevcdl_compress_frames");
   if (n_frames == 0 || !yuv) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "begin_frames: no frames");
   TRY(ensure_staging(ctx));
   TRY(lazy_alloc(ctx, ctx->ses.d_cabac, sizeof(hevcdl_cabac_state) * (size_t)ctx->cfg.max_frames, "coder states of the per-CTU session (cfg.max_frames)"));

@@ -57,19 +57,19 @@ const Key KEYS[] = {
   { "IntraPeriod", 0, PATH, "1" }, { "GOPSize", 0, PATH, "1" }, { "MaxDeltaQP", 0, PATH, "0" }, { "DeltaQpRD", 0, PATH, "0" },
   { "RDOQ", 0, USED, 0 }, { "RDOQTS", 0, USED, 0 }, { "TransformSkip", 0, USED, 0 }, { "TransformSkipFast", 0, USED, 0 },
   { "SignHideFlag", "SBH", USED, 0 }, { "StrongIntraSmoothing", 0, USED, 0 }, { "FastUDIUseMPMEnabled", 0, USED, 0 },      // tool switches (hevcdl_config.tools): 0 or 1
-  { "SliceMode", 0, PATH, "0" }, { "PCMEnabledFlag", 0, PATH, "0" }, { "NumTileColumnsMinus1", 0, USED, 0 },
+  { "SliceMode", 0, USED, 0 }, { "SliceArgument", 0, USED, 0 }, { "PCMEnabledFlag", 0, PATH, "0" }, { "NumTileColumnsMinus1", 0, USED, 0 },
   { "NumTileRowsMinus1", 0, USED, 0 }, { "WaveFrontSynchro", 0, USED, 0 }, { "ScalingList", 0, PATH, "0" },
   { "TransquantBypassEnable", 0, PATH, "0" }, { "CUTransquantBypassFlagForce", 0, PATH, "0" },
   // stream / in-loop filter keys
   { "Level", 0, USED, 0 }, { "DecodingRefreshType", 0, PATH, "1" }, { "ReWriteParamSetsFlag", 0, USED, 0 }, { "LoopFilterOffsetInPPS", 0, USED, 0 },
   { "LoopFilterBetaOffset_div2", 0, USED, 0 }, { "LoopFilterTcOffset_div2", 0, USED, 0 },
-  { "DeblockingFilterMetric", 0, USED, 0 }, { "SAO", 0, USED, 0 }, { "SAOLcuBoundary", 0, PATH, "0" }, { "LFCrossSliceBoundaryFlag", 0, NOEFFECT, 0 },      // (without slices the reference sets it to 1 whatever the cfg says: TAppEncTop.cpp:278-281)
+  { "DeblockingFilterMetric", 0, USED, 0 }, { "SAO", 0, USED, 0 }, { "SAOLcuBoundary", 0, PATH, "0" }, { "LFCrossSliceBoundaryFlag", 0, USED, 0 },      // (used with SliceMode 1 / 3; without slices the reference sets it to 1 whatever the cfg says: TAppEncTop.cpp:278-281)
   { "LFCrossTileBoundaryFlag", 0, USED, 0 }, { "SEIDecodedPictureHash", 0, USED, 0 },
   // quality report (TAppEncCfg.cpp:759-762): MS-SSIM per picture and in the summary, MSE per picture, MSE in the summary; default 0
   { "PrintMSSSIM", 0, USED, 0 }, { "PrintFrameMSE", 0, USED, 0 }, { "PrintSequenceMSE", 0, USED, 0 },
   // no effect on an all-intra slice with the settings above
   { "QuadtreeTUMaxDepthInter", 0, NOEFFECT, 0 }, { "FastSearch", 0, NOEFFECT, 0 }, { "SearchRange", 0, NOEFFECT, 0 }, { "HadamardME", 0, NOEFFECT, 0 },
-  { "FEN", 0, NOEFFECT, 0 }, { "FDM", 0, NOEFFECT, 0 }, { "AMP", 0, NOEFFECT, 0 }, { "MaxCuDQPDepth", 0, NOEFFECT, 0 }, { "SliceArgument", 0, NOEFFECT, 0 },
+  { "FEN", 0, NOEFFECT, 0 }, { "FDM", 0, NOEFFECT, 0 }, { "AMP", 0, NOEFFECT, 0 }, { "MaxCuDQPDepth", 0, NOEFFECT, 0 },
   { "PCMLog2MaxSize", 0, NOEFFECT, 0 }, { "PCMLog2MinSize", 0, NOEFFECT, 0 }, { "PCMInputBitDepthFlag", 0, NOEFFECT, 0 },
   { "PCMFilterDisableFlag", 0, NOEFFECT, 0 }, { "TileUniformSpacing", 0, USED, 0 }, { "TileColumnWidthArray", 0, USED, 0 },
   { "TileRowHeightArray", 0, USED, 0 }, { "ScalingListFile", 0, NOEFFECT, 0 },
@@ -329,8 +329,21 @@ int main(int argc, char **argv)
         opt.errors.push_back("TileUniformSpacing = 0 needs TileColumnWidthArray / TileRowHeightArray with a size for every tile column / row but the last");
     }
   }
+  // Slices (TAppEncCfg.cpp:1008-1017): SliceMode 1 = SliceArgument CTUs a slice (whole CTU rows only on this path), 3 = SliceArgument tiles a slice; SliceArgument and
+  // LFCrossSliceBoundaryFlag are read only then (the default cfg carries SliceArgument 1500 beside SliceMode 0).  What hevcdl_create refuses arrives with its reason.
+  const long slice_mode = opt.geti("SliceMode", 0), slice_arg = slice_mode ? opt.geti("SliceArgument", 0) : 0, lf_slices = slice_mode ? opt.geti("LFCrossSliceBoundaryFlag", 1) != 0 : 1;
+  if (slice_mode < 0 || slice_mode > 3) opt.errors.push_back("SliceMode = " + std::to_string(slice_mode) + " is not a value of the key (0, 1 or 3; 2 is not implemented by this path)");
+  else if (slice_mode == 2) opt.errors.push_back("SliceMode = 2 (slices by bytes) is not implemented by this path: the slice borders would depend on the coded bytes");
+  else if (slice_mode == 1 && (tile_cols * tile_rows > 1 || wavefront)) opt.errors.push_back("SliceMode = 1 together with tiles or WaveFrontSynchro is not implemented by this path");
+  else if (slice_mode == 1 && width > 0 && height > 0 && (slice_arg < 1 || slice_arg % ((width + 63) / 64) != 0 || (((height + 63) / 64) + slice_arg / ((width + 63) / 64) - 1) / (slice_arg / ((width + 63) / 64)) > 22))
+    opt.errors.push_back("SliceMode = 1 needs a SliceArgument that is a positive multiple of the picture's width in CTUs (" + std::to_string((width + 63) / 64) + ") and gives at most 22 slices a picture: only slices of whole CTU rows are implemented");
+  else if (slice_mode == 3 && (tile_cols * tile_rows == 1 || slice_arg < 1)) opt.errors.push_back("SliceMode = 3 (slices of whole tiles) needs tiles and a SliceArgument of at least 1");
+  else if (slice_mode == 3 && slice_arg > 1 && opt.geti("LFCrossTileBoundaryFlag", 1) != 0 && !lf_slices)
+    opt.errors.push_back("SliceMode = 3 with more than one tile a slice, LFCrossTileBoundaryFlag = 1 and LFCrossSliceBoundaryFlag = 0 is not implemented by this path (the in-loop filters have one flag for all tile borders)");
+  else if (slice_mode != 0 && dbk_metric != 0) opt.errors.push_back("slices together with DeblockingFilterMetric are not implemented by this path");
   if (opt.v.count("PrintConfig")) {
-    printf("{\"InputFile\": \"%s\", \"ReconFile\": \"%s\", \"SourceWidth\": %d, \"SourceHeight\": %d, \"QP\": %d, \"FrameSkip\": %ld, \"FramesToBeEncoded\": %ld, "
+    printf("{\"SliceMode\": %ld, \"SliceArgument\": %ld, \"LFCrossSliceBoundaryFlag\": %ld, ", slice_mode, slice_arg, lf_slices);
+    printf("\"InputFile\": \"%s\", \"ReconFile\": \"%s\", \"SourceWidth\": %d, \"SourceHeight\": %d, \"QP\": %d, \"FrameSkip\": %ld, \"FramesToBeEncoded\": %ld, "
            "\"FrameRate\": %g, \"LabelDir\": \"%s\", \"CnnInput\": \"%s\", \"BitstreamFile\": \"%s\", \"level_idc\": %d, \"tiles\": [%d, %d], \"bit_depth\": %d, "
            "\"ConformanceWindowMode\": %d, \"HorizontalPadding\": %d, \"VerticalPadding\": %d, \"InputBitDepth\": %d, \"InternalBitDepth\": %d, \"OutputBitDepth\": %d, \"coded_size\": [%d, %d], "
            "\"InputChromaFormat\": %d, \"ChromaFormatIDC\": %d, \"Input ChromaFormatIDC\": \"4:%c:%c\", \"Output (internal) ChromaFormatIDC\": \"4:2:0\", \"InputColourSpaceConvert\": \"%s\", "
@@ -398,7 +411,8 @@ int main(int argc, char **argv)
     if (free_b > 0) { double mine = (double)free_b * 0.8 / (shared_device ? (double)devices.size() : 1.0);       // (contexts that share a device share its memory)
       if (mine > 2.0 * (double)workspace) mine -= (double)workspace;
       dev_cap = std::max<long>(1, (long)mine / per_picture_dev); } }
-  const long auto_batch = std::max<long>(1, std::min<long>(std::min<long>(2048 / (tile_cols * tile_rows), dev_cap), (24L << 30) / (long)frame_bytes));
+  const long units_per_picture = slice_mode == 1 ? (((height + 63) / 64) * (long)((width + 63) / 64) + slice_arg - 1) / slice_arg : (long)tile_cols * tile_rows;      // independent units of the decision launch: tiles, or row slices
+  const long auto_batch = std::max<long>(1, std::min<long>(std::min<long>(2048 / units_per_picture, dev_cap), (24L << 30) / (long)frame_bytes));
   const long even_batch = (per_shard + ((per_shard + auto_batch - 1) / auto_batch) - 1) / ((per_shard + auto_batch - 1) / auto_batch);
   int batch = (int)std::min<long>(per_shard, std::max<long>(1, opt.geti("BatchFrames", even_batch)));
 
@@ -422,6 +436,7 @@ int main(int argc, char **argv)
   cfg.tools = tools;
   cfg.lf_beta_offset_div2 = (int)opt.geti("LoopFilterBetaOffset_div2", 0); cfg.lf_tc_offset_div2 = (int)opt.geti("LoopFilterTcOffset_div2", 0);      // -6 .. 6 (hevcdl_create checks)
   cfg.deblocking_metric = (int)dbk_metric; cfg.lf_offset_in_pps = (int)lf_in_pps;
+  cfg.slice_mode = (int)slice_mode; cfg.slice_argument = (int)slice_arg; cfg.lf_across_slices = (int)lf_slices;
   cfg.cnn_input = cnn_input == "luma" ? HEVCDL_CNN_INPUT_LUMA : HEVCDL_CNN_INPUT_RGB601;
   cfg.bn_mode = bn_mode == "eval" ? HEVCDL_BN_EVAL : HEVCDL_BN_REFERENCE;
   if (shared_device) cfg.exec_flags |= HEVCDL_EXEC_NO_UNIT_HANDOVER;
@@ -516,6 +531,7 @@ int main(int argc, char **argv)
   scfg.tools = cfg.tools; scfg.lf_beta_offset_div2 = cfg.lf_beta_offset_div2; scfg.lf_tc_offset_div2 = cfg.lf_tc_offset_div2; scfg.loop_filter_disable = deblock ? 0 : 1;
   scfg.lf_across_tiles = cfg.lf_across_tiles; scfg.tile_uniform_spacing = cfg.tile_uniform_spacing; memcpy(scfg.tile_column_width, cfg.tile_column_width, sizeof scfg.tile_column_width); memcpy(scfg.tile_row_height, cfg.tile_row_height, sizeof scfg.tile_row_height);
   scfg.conf_win_right = width - src_w; scfg.conf_win_bottom = height - src_h;
+  const hevcdl_slice_layout slices = { (int)slice_mode, (int)slice_arg, (int)lf_slices };      // NAL units, slice headers and the PPS's across-slices flag (mode 0: one slice, as ever)
   if (conf_mode == 3) { scfg.conf_win_left = win_l; scfg.conf_win_right = win_r; scfg.conf_win_top = win_t; scfg.conf_win_bottom = win_b; }      // PSNR, the hash and the digests stay over the whole coded picture (no padding: m_aiPad is 0)
   const double ny = (double)src_w * src_h, nc = ny / 4;      // PSNR, MSE and MS-SSIM are taken over the picture without the padding (TEncGOP.cpp:2302-2303, 2375-2376)
   double sum_bits = 0, sum_psnr[3] = { 0, 0, 0 }, sum_mse[3] = { 0, 0, 0 }, sum_msssim[3] = { 0, 0, 0 }; long done = 0;
@@ -580,7 +596,7 @@ int main(int argc, char **argv)
       {
         std::atomic<int> next(0);
         auto work = [&]() {
-          std::vector<uint8_t> buf(hevcdl_access_unit_bound(width, height));
+          std::vector<uint8_t> buf(hevcdl_access_unit_bound_slices(width, height, &slices));
           for (int i = next++; i < count; i = next++) {
             if (slice_data && buf.size() < slice_at[(size_t)i + 1] - slice_at[(size_t)i] + 4096) buf.resize(2 * (slice_at[(size_t)i + 1] - slice_at[(size_t)i]) + 4096);
             PicOut &po = pics[i]; po.md5_text[0] = 0;
@@ -620,8 +636,8 @@ int main(int argc, char **argv)
             }
             if (file_order && coded_order) std::swap(po.sse[1], po.sse[2]);
             // the access unit: VPS+SPS+PPS+slice, written to -b; its size is the picture's bit count (TEncGOP.cpp:2420-2447)
-            if (slice_data) po.st = hevcdl_write_access_unit_from_slice_data_dbk(&scfg, (int)(cc.f0 + first + i), slice_data + slice_at[(size_t)i], slice_sizes + (size_t)i * n_sub, n_sub, &choices[i], buf.data(), buf.size(), &po.au_len);
-            else po.st = hevcdl_write_access_unit_dbk(&scfg, (int)(cc.f0 + first + i), recs + (size_t)ctus * i, sao ? sao_params + (size_t)ctus * i : nullptr, &choices[i], buf.data(), buf.size(), &po.au_len);
+            if (slice_data) po.st = hevcdl_write_access_unit_from_slice_data_slices(&scfg, &slices, (int)(cc.f0 + first + i), slice_data + slice_at[(size_t)i], slice_sizes + (size_t)i * n_sub, n_sub, &choices[i], buf.data(), buf.size(), &po.au_len);
+            else po.st = hevcdl_write_access_unit_slices(&scfg, &slices, (int)(cc.f0 + first + i), recs + (size_t)ctus * i, sao ? sao_params + (size_t)ctus * i : nullptr, &choices[i], buf.data(), buf.size(), &po.au_len);
             if (po.st != HEVCDL_OK) continue;
             po.bytes.assign(buf.begin(), buf.begin() + po.au_len);
             if (hash_sei) { // suffix SEI after the slice; not part of the picture's bit count (as in the reference)

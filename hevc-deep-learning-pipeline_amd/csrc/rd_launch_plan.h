@@ -22,6 +22,17 @@ struct RdPlanContext {
   int remote_groups() const { return (bit_depth == 8 && !(exec_flags & HEVCDL_EXEC_NO_UNIT_HANDOVER) && n_cus >= 8 && n_cus <= 1024) ? n_cus : 0; }
 };
 
+// The plan's view of a context: `grid` is the configuration the context RUNS (with SliceMode 1 a column of row slices in the tile fields: slice_grid.h), so a slice
+// context plans exactly like the tile context with the same grid.  waves: wavefronts per workgroup of each build.
+static inline RdPlanContext rd_plan_context_of(const hevcdl_config &grid, int n_cus, const int *waves)
+{
+  RdPlanContext pc;
+  pc.n_cus = n_cus; pc.max_frames = grid.max_frames; pc.bit_depth = grid.bit_depth; pc.tools = grid.tools; pc.exec_flags = grid.exec_flags; pc.wavefront = grid.wavefront;
+  pc.tile_columns = grid.tile_columns; pc.tile_rows = grid.tile_rows; pc.ctus_x = (grid.width + 63) >> 6; pc.ctus_y = (grid.height + 63) >> 6;
+  for (int b = 0; b < RD_BUILDS; b++) pc.waves[b] = waves[b];
+  return pc;
+}
+
 // the arguments of one launch.  ctu_end / tile_count < 0: all of them; session_frame >= 0: the per-CTU session's frame (hevcdl_compress_ctu)
 struct RdLaunchArgs { int n_frames = 0, ctu_begin = 0, ctu_end = -1; bool cabac_in = false, cabac_out = false; int tile_begin = 0, tile_count = -1, session_frame = -1; };
 

@@ -121,6 +121,16 @@ typedef struct hevcdl_config {
    * itself runs as before.  A non-zero metric needs lf_offset_in_pps 0 and the filter on, as in the reference (TAppEncCfg.cpp:2143), and metric 1 a picture of at least
    * 64 luma samples either way (the reference divides by the number of 32-sample columns and rows minus one).  hevcdl_create_error names what was refused. */
   int32_t  deblocking_metric, lf_offset_in_pps;
+  /* Slices (cfg keys SliceMode, SliceArgument, LFCrossSliceBoundaryFlag).  slice_mode 0 (the default; a zeroed tail means it): one slice a picture, and the
+   * other two fields are not looked at (the reference sets LFCrossSliceBoundaryFlag to 1 then, TAppEncTop.cpp:278-281).  1: slices of slice_argument CTUs in raster order; only
+   * whole CTU rows -- slice_argument a positive multiple of the picture's width in CTUs -- at most 22 slices a picture, not together with tiles or wavefront.  Such slices are the
+   * reference's tile rows of full width in everything but the syntax (same decisions, same filters): the context runs them as a unit grid of one column, which may be narrower
+   * than the four CTUs a tile column needs.  3: slices of slice_argument tiles in raster order of the tile grid (the last one takes the rest); needs tiles; changes nothing
+   * but the stream.  2 (slices by bytes) is refused.  lf_across_slices = LFCrossSliceBoundaryFlag: 0 = deblocking and SAO stop at slice borders.  In mode 3 every slice border is
+   * a tile border and the in-loop filters cross it only when BOTH lf_across_tiles and lf_across_slices are set (tests/golden/slices_t512_a1_lf0.npz), while a tile border inside
+   * a slice follows lf_across_tiles alone: more than one tile a slice with lf_across_tiles 1 and lf_across_slices 0 is refused (the filters have one flag).  Not together
+   * with deblocking_metric, and the per-CTU session refuses such a context.  hevcdl_create_error names what was refused. */
+  int32_t  slice_mode, slice_argument, lf_across_slices;
 } hevcdl_config;
 
 /* One CTU of decisions: what compressCtu leaves in the picture's CTU record (TEncCu.cpp:1091 copyToPic).
@@ -159,7 +169,7 @@ hevcdl_status hevcdl_config_default_bd(hevcdl_config *cfg, int width, int height
 /* weights: flat fp32 blob, HEVCDL_WEIGHT_FLOATS values (replaces torch.load at use_model.py:62). */
 hevcdl_status hevcdl_create(const hevcdl_config *cfg, const float *weights, size_t n_floats, hevcdl_ctx **out);
 /* Why the calling thread's last hevcdl_create refused its configuration: there is no context to ask yet.  ONLY the refusals of the deblocking keys (deblocking_metric,
- * lf_offset_in_pps) leave a message so far; every other failure of hevcdl_create, and a success, leave "" -- the status is then all there is. */
+ * lf_offset_in_pps) and of the slice keys (slice_mode, slice_argument, lf_across_slices) leave a message so far; every other failure of hevcdl_create, and a success, leave "" -- the status is then all there is. */
 const char   *hevcdl_create_error(void);
 void          hevcdl_destroy(hevcdl_ctx *ctx);
 const char   *hevcdl_last_error(const hevcdl_ctx *ctx);
@@ -474,8 +484,8 @@ typedef struct hevcdl_stream_config {
                                     (TEncCavlc.cpp:526-535); a decoder then outputs width - right by height - bottom */
   int32_t  conf_win_left, conf_win_top;       /* the other two offsets (default 0; ConformanceWindowMode 3, hevcdl_source_format.conf_win_*): even, and something must be left
                                     of the picture */
-                                 /* (LFCrossSliceBoundaryFlag has no field: without slices -- SliceMode 0, the only mode of this path -- the reference sets it to 1 whatever the cfg
-                                    says, TAppEncTop.cpp:278-281; tests/golden/stream_c192_q32.npz pins that) */
+                                 /* (LFCrossSliceBoundaryFlag has no field here: without slices -- SliceMode 0, a NULL hevcdl_slice_layout -- the reference sets it to 1 whatever the cfg
+                                    says, TAppEncTop.cpp:278-281; tests/golden/stream_c192_q32.npz pins that.  With slices it is hevcdl_slice_layout.lf_across_slices) */
 } hevcdl_stream_config;
 hevcdl_status hevcdl_stream_config_default(hevcdl_stream_config *cfg, int width, int height, int qp);
 size_t        hevcdl_access_unit_bound(int width, int height);
@@ -519,6 +529,37 @@ hevcdl_status hevcdl_code_slice_data_host(const hevcdl_stream_config *cfg, const
                                           int capacity_per_ctu, uint8_t *out, size_t out_capacity, uint32_t *sizes, uint32_t *overflow);
 hevcdl_status hevcdl_code_slice_data(int device, const hevcdl_stream_config *cfg, const hevcdl_ctu_record *records, const hevcdl_sao_blk *sao_opt, int n_frames,
                                      int capacity_per_ctu, uint8_t *out, size_t out_capacity, uint32_t *sizes, uint32_t *overflow);
+
+/* ---- slices (cfg keys SliceMode, SliceArgument, LFCrossSliceBoundaryFlag) -----------------------------------------------------------------------------
+ * hevcdl_stream_config does not grow (recorded digests hash its bytes): what slices change in a stream is this small block, taken by siblings of the writer's entry points.
+ * A NULL layout, or mode 0, is the function without the suffix.  mode 1: slices of `argument` CTUs, whole CTU rows only (a positive multiple of the width in CTUs, at most
+ * 22 slices), cfg without tiles and wavefront -- the slice data is then one sub-stream per SLICE (n_substreams = the number of slices), no entry points, and nothing in the
+ * stream speaks of tiles.  mode 3: slices of `argument` tiles of cfg's tile grid; sub-streams are the tiles as ever, a slice header carries the entry points of its own tiles.
+ * Every slice is a NAL unit of its own with first_slice_segment_in_pic_flag / slice_segment_address and the whole header repeated (TEncCavlc.cpp:755-1109, TEncGOP's slice
+ * loop); pps_loop_filter_across_slices_enabled_flag and slice_loop_filter_across_slices_enabled_flag are lf_across_slices.  Anything else is HEVCDL_ERR_INVALID_ARG,
+ * mode 2 HEVCDL_ERR_UNSUPPORTED. */
+typedef struct hevcdl_slice_layout {
+  int32_t mode;                  /* SliceMode 0, 1, 3 */
+  int32_t argument;              /* SliceArgument: CTUs (mode 1) or tiles (mode 3) a slice */
+  int32_t lf_across_slices;      /* LFCrossSliceBoundaryFlag */
+} hevcdl_slice_layout;
+/* hevcdl_write_access_unit_dbk / hevcdl_write_access_unit_from_slice_data_dbk (choice may be NULL as there) */
+hevcdl_status hevcdl_write_access_unit_slices(const hevcdl_stream_config *cfg, const hevcdl_slice_layout *layout, int poc, const hevcdl_ctu_record *records,
+                                              const hevcdl_sao_blk *sao, const hevcdl_dbk_choice *choice, uint8_t *out, size_t capacity, size_t *out_len);
+hevcdl_status hevcdl_write_access_unit_from_slice_data_slices(const hevcdl_stream_config *cfg, const hevcdl_slice_layout *layout, int poc, const uint8_t *data,
+                                                              const uint32_t *sizes, int n_substreams, const hevcdl_dbk_choice *choice, uint8_t *out, size_t capacity, size_t *out_len);
+/* hevcdl_slice_data_layout / hevcdl_code_slice_data_host / hevcdl_code_slice_data: in mode 1 the sub-streams are the slices; in every mode a sub-stream that ends a slice
+ * ends with the terminating bin alone, without end_of_slice_segment_flag 0 in front of it */
+hevcdl_status hevcdl_slice_data_layout_slices(const hevcdl_stream_config *cfg, const hevcdl_slice_layout *layout, int capacity_per_ctu, int *n_substreams, size_t *picture_bytes,
+                                              uint32_t *offsets_opt, uint32_t *capacities_opt);
+hevcdl_status hevcdl_code_slice_data_host_slices(const hevcdl_stream_config *cfg, const hevcdl_slice_layout *layout, const hevcdl_ctu_record *records, const hevcdl_sao_blk *sao_opt,
+                                                 int n_frames, int capacity_per_ctu, uint8_t *out, size_t out_capacity, uint32_t *sizes, uint32_t *overflow);
+hevcdl_status hevcdl_code_slice_data_slices(int device, const hevcdl_stream_config *cfg, const hevcdl_slice_layout *layout, const hevcdl_ctu_record *records,
+                                            const hevcdl_sao_blk *sao_opt, int n_frames, int capacity_per_ctu, uint8_t *out, size_t out_capacity, uint32_t *sizes, uint32_t *overflow);
+/* hevcdl_access_unit_bound plus the headers of the slice NAL units (at most 22 in mode 1, 440 in mode 3) */
+size_t        hevcdl_access_unit_bound_slices(int width, int height, const hevcdl_slice_layout *layout);
+/* The layout a context's pictures are written with (mode 0 for a context without slices). */
+hevcdl_status hevcdl_get_slice_layout(const hevcdl_ctx *ctx, hevcdl_slice_layout *out);
 
 /* Decoded picture hash (cfg key SEIDecodedPictureHash 1 = MD5): the suffix SEI NAL the reference appends to the access unit
  * (TEncGOP.cpp:1938-1960), computed from `picture` = the final reconstruction (planar 4:2:0; uint16 samples at 10 bits).  At most
