@@ -65,12 +65,27 @@ class Config(ctypes.Structure):
                 ("tile_uniform_spacing", ctypes.c_int32), ("tile_column_width", ctypes.c_int32 * 19), ("tile_row_height", ctypes.c_int32 * 21),
                 ("lf_across_tiles", ctypes.c_int32), ("lf_beta_offset_div2", ctypes.c_int32), ("lf_tc_offset_div2", ctypes.c_int32), ("wavefront", ctypes.c_int32),
                 ("deblocking_metric", ctypes.c_int32), ("lf_offset_in_pps", ctypes.c_int32),
-                ("slice_mode", ctypes.c_int32), ("slice_argument", ctypes.c_int32), ("lf_across_slices", ctypes.c_int32)]
+                ("slice_mode", ctypes.c_int32), ("slice_argument", ctypes.c_int32), ("lf_across_slices", ctypes.c_int32),
+                ("slice_segment_mode", ctypes.c_int32), ("slice_segment_argument", ctypes.c_int32)]
 
 
 class SliceLayout(ctypes.Structure):
     """hevcdl_slice_layout of include/hevcdl.h: SliceMode (0, 1, 3), SliceArgument, LFCrossSliceBoundaryFlag -- what slices change in a stream."""
     _fields_ = [("mode", ctypes.c_int32), ("argument", ctypes.c_int32), ("lf_across_slices", ctypes.c_int32)]
+
+
+class SegmentLayout(ctypes.Structure):
+    """hevcdl_segment_layout of include/hevcdl.h: SliceSegmentMode (0, 1, 3), SliceSegmentArgument -- the dependent slice segments of a stream."""
+    _fields_ = [("mode", ctypes.c_int32), ("argument", ctypes.c_int32)]
+
+
+def segment_layout(segments=None):
+    """segments = (SliceSegmentMode, SliceSegmentArgument) or None -> a SegmentLayout, or None for a stream without dependent slice segments."""
+    if segments is None or isinstance(segments, SegmentLayout):
+        return segments
+    if int(segments[0]) == 0:
+        return None
+    return SegmentLayout(int(segments[0]), int(segments[1]))
 
 
 def slice_layout(slices=None, lf_across_slices=True):
@@ -356,6 +371,15 @@ def load_library():
     lib.hevcdl_access_unit_bound_slices.argtypes = [ci, ci, slp]
     lib.hevcdl_access_unit_bound_slices.restype = ctypes.c_size_t
     lib.hevcdl_get_slice_layout.argtypes = [vp, slp]
+    sgp = ctypes.POINTER(SegmentLayout)
+    lib.hevcdl_write_access_unit_segments.argtypes = [ctypes.POINTER(StreamConfig), slp, sgp, ci, vp, vp, vp, vp, ctypes.c_size_t, szp]
+    lib.hevcdl_write_access_unit_from_slice_data_segments.argtypes = [ctypes.POINTER(StreamConfig), slp, sgp, ci, vp, vp, ci, vp, vp, ctypes.c_size_t, szp]
+    lib.hevcdl_slice_data_layout_segments.argtypes = [ctypes.POINTER(StreamConfig), slp, sgp, ci, ctypes.POINTER(ci), szp, vp, vp]
+    lib.hevcdl_code_slice_data_host_segments.argtypes = [ctypes.POINTER(StreamConfig), slp, sgp, vp, vp, ci, ci, vp, ctypes.c_size_t, vp, vp]
+    lib.hevcdl_code_slice_data_segments.argtypes = [ci, ctypes.POINTER(StreamConfig), slp, sgp, vp, vp, ci, ci, vp, ctypes.c_size_t, vp, vp]
+    lib.hevcdl_access_unit_bound_segments.argtypes = [ci, ci, slp, sgp]
+    lib.hevcdl_access_unit_bound_segments.restype = ctypes.c_size_t
+    lib.hevcdl_get_segment_layout.argtypes = [vp, sgp]
     _lib = lib
     return lib
 
@@ -375,7 +399,9 @@ EXPORTS = ["hevcdl_config_default", "hevcdl_create", "hevcdl_destroy", "hevcdl_l
            "hevcdl_create_error", "hevcdl_dbk_metric_frames", "hevcdl_dbk_metric_frames_dev", "hevcdl_dbk_metric_choice", "hevcdl_deblock_frames_choice", "hevcdl_deblock_frames_choice_dev",
            "hevcdl_get_dbk_choice", "hevcdl_dbk_trial_frames", "hevcdl_dbk_trial_frames_dev", "hevcdl_dbk_walk_table", "hevcdl_dbk_select_reset", "hevcdl_write_access_unit_dbk", "hevcdl_write_access_unit_from_slice_data_dbk",
            "hevcdl_write_access_unit_slices", "hevcdl_write_access_unit_from_slice_data_slices", "hevcdl_slice_data_layout_slices", "hevcdl_code_slice_data_host_slices", "hevcdl_code_slice_data_slices",
-           "hevcdl_access_unit_bound_slices", "hevcdl_get_slice_layout"]
+           "hevcdl_access_unit_bound_slices", "hevcdl_get_slice_layout",
+           "hevcdl_write_access_unit_segments", "hevcdl_write_access_unit_from_slice_data_segments", "hevcdl_slice_data_layout_segments", "hevcdl_code_slice_data_host_segments",
+           "hevcdl_code_slice_data_segments", "hevcdl_access_unit_bound_segments", "hevcdl_get_segment_layout"]
 
 
 def picture_hash_sei(width, height, picture, bit_depth=8, method=1):
@@ -505,7 +531,7 @@ TOOL_RDOQ, TOOL_RDOQTS, TOOL_TSKIP, TOOL_TSKIP_FAST, TOOL_SIGN_HIDE, TOOL_STRONG
 
 
 def default_config(width, height, qp, max_frames=1, device=0, cnn_input=0, tiles=(1, 1), bit_depth=8, lf_across_tiles=True, bn_mode=0, tools=TOOLS_REFERENCE, lf_offsets=(0, 0), wavefront=False,
-                   deblocking_metric=0, lf_offset_in_pps=True, slices=None, lf_across_slices=True):
+                   deblocking_metric=0, lf_offset_in_pps=True, slices=None, lf_across_slices=True, segments=None):
     lib = load_library()
     cfg = Config()
     st = lib.hevcdl_config_default_bd(ctypes.byref(cfg), width, height, qp, bit_depth)
@@ -521,6 +547,8 @@ def default_config(width, height, qp, max_frames=1, device=0, cnn_input=0, tiles
     cfg.deblocking_metric, cfg.lf_offset_in_pps = int(deblocking_metric), 1 if lf_offset_in_pps else 0      # DeblockingFilterMetric, LoopFilterOffsetInPPS
     if slices is not None:                     # (SliceMode, SliceArgument), LFCrossSliceBoundaryFlag
         cfg.slice_mode, cfg.slice_argument, cfg.lf_across_slices = int(slices[0]), int(slices[1]), 1 if lf_across_slices else 0
+    if segments is not None:                   # (SliceSegmentMode, SliceSegmentArgument)
+        cfg.slice_segment_mode, cfg.slice_segment_argument = int(segments[0]), int(segments[1])
     return cfg
 
 
@@ -553,20 +581,21 @@ def stream_config(width, height, qp, level_idc=186, sao=False, tiles=(1, 1), bit
 CANARY = 0xA5      # what code_slice_data fills its buffer with before the coder runs: the gaps between the sub-stream regions must still hold it afterwards
 
 
-def slice_data_layout(cfg, capacity_per_ctu=0, layout=None):
+def slice_data_layout(cfg, capacity_per_ctu=0, layout=None, segments=None):
     """-> (sub-streams of a picture, bytes of a picture's regions, offsets [n], capacities [n]) of a slice-data buffer (hevcdl_slice_data_layout; layout: a SliceLayout,
-    hevcdl_slice_data_layout_slices)."""
+    hevcdl_slice_data_layout_slices; segments: a SegmentLayout or (mode, argument), hevcdl_slice_data_layout_segments)."""
     lib = load_library()
+    segments = segment_layout(segments)
     n, nbytes = ctypes.c_int(0), ctypes.c_size_t(0)
-    st = lib.hevcdl_slice_data_layout_slices(ctypes.byref(cfg), _layout_ptr(layout), int(capacity_per_ctu), ctypes.byref(n), ctypes.byref(nbytes), None, None)
+    st = lib.hevcdl_slice_data_layout_segments(ctypes.byref(cfg), _layout_ptr(layout), _layout_ptr(segments), int(capacity_per_ctu), ctypes.byref(n), ctypes.byref(nbytes), None, None)
     if st:
         raise HevcdlError(st, "hevcdl_slice_data_layout")
     off, cap = np.zeros(n.value, np.uint32), np.zeros(n.value, np.uint32)
-    lib.hevcdl_slice_data_layout_slices(ctypes.byref(cfg), _layout_ptr(layout), int(capacity_per_ctu), ctypes.byref(n), ctypes.byref(nbytes), off.ctypes.data, cap.ctypes.data)
+    lib.hevcdl_slice_data_layout_segments(ctypes.byref(cfg), _layout_ptr(layout), _layout_ptr(segments), int(capacity_per_ctu), ctypes.byref(n), ctypes.byref(nbytes), off.ctypes.data, cap.ctypes.data)
     return n.value, nbytes.value, off, cap
 
 
-def code_slice_data(cfg, records, sao=None, capacity_per_ctu=0, device=None, layout=None):
+def code_slice_data(cfg, records, sao=None, capacity_per_ctu=0, device=None, layout=None, segments=None):
     """TEST AND DIAGNOSTIC: the slice data of records [n_frames, ctus] by the shared coder -- device None: on the CPU (hevcdl_code_slice_data_host, no GPU needed),
     otherwise by the kernels on that device (hevcdl_code_slice_data).  cfg: stream_config(...) with sao=True when SAO parameters [n_frames, ctus, 3] are passed.
     -> (buffer [n_frames, picture bytes] pre-filled with CANARY, sizes [n_frames, n], overflow [n_frames, n], offsets [n], capacities [n])."""
@@ -574,7 +603,8 @@ def code_slice_data(cfg, records, sao=None, capacity_per_ctu=0, device=None, lay
     records = np.ascontiguousarray(records, REC_DTYPE)
     records = records.reshape(1, -1) if records.ndim == 1 else records
     nf = records.shape[0]
-    n, nbytes, off, cap = slice_data_layout(cfg, capacity_per_ctu, layout)
+    segments = segment_layout(segments)      # dependent slice segments: a sub-stream that ends one ends with end_of_slice_segment_flag 1
+    n, nbytes, off, cap = slice_data_layout(cfg, capacity_per_ctu, layout, segments)
     buf = np.full((nf, nbytes), CANARY, np.uint8)
     sizes, ovf = np.zeros((nf, n), np.uint32), np.zeros((nf, n), np.uint32)
     sao_ptr = None
@@ -582,9 +612,9 @@ def code_slice_data(cfg, records, sao=None, capacity_per_ctu=0, device=None, lay
         sao = np.ascontiguousarray(sao, SAO_DTYPE)
         sao_ptr = sao.ctypes.data
     if device is None:
-        st = lib.hevcdl_code_slice_data_host_slices(ctypes.byref(cfg), _layout_ptr(layout), records.ctypes.data, sao_ptr, nf, int(capacity_per_ctu), buf.ctypes.data, buf.size, sizes.ctypes.data, ovf.ctypes.data)
+        st = lib.hevcdl_code_slice_data_host_segments(ctypes.byref(cfg), _layout_ptr(layout), _layout_ptr(segments), records.ctypes.data, sao_ptr, nf, int(capacity_per_ctu), buf.ctypes.data, buf.size, sizes.ctypes.data, ovf.ctypes.data)
     else:
-        st = lib.hevcdl_code_slice_data_slices(int(device), ctypes.byref(cfg), _layout_ptr(layout), records.ctypes.data, sao_ptr, nf, int(capacity_per_ctu), buf.ctypes.data, buf.size, sizes.ctypes.data, ovf.ctypes.data)
+        st = lib.hevcdl_code_slice_data_segments(int(device), ctypes.byref(cfg), _layout_ptr(layout), _layout_ptr(segments), records.ctypes.data, sao_ptr, nf, int(capacity_per_ctu), buf.ctypes.data, buf.size, sizes.ctypes.data, ovf.ctypes.data)
     if st:
         raise HevcdlError(st, "hevcdl_code_slice_data")
     return buf, sizes, ovf, off, cap
@@ -629,17 +659,20 @@ def dbk_walk_table(table, state, pps_offsets=(0, 0)):
     return np.array([(c.override_enabled, c.override_flag, c.disabled, c.beta_offset_div2, c.tc_offset_div2)], DBK_CHOICE_DTYPE)[0], st.tolist()
 
 
-def write_access_unit_from_slice_data(cfg, poc, data, sizes, choice=None, layout=None):
+def write_access_unit_from_slice_data(cfg, poc, data, sizes, choice=None, layout=None, segments=None):
     """Everything of picture poc's access unit around slice data that exists already (hevcdl_write_access_unit_from_slice_data; with `choice`, the picture's deblocking
-    parameters, hevcdl_write_access_unit_from_slice_data_dbk) -> bytes."""
+    parameters, hevcdl_write_access_unit_from_slice_data_dbk; with `segments`, a NAL unit per dependent slice segment, hevcdl_write_access_unit_from_slice_data_segments) -> bytes."""
     lib = load_library()
+    segments = segment_layout(segments)
     data = np.frombuffer(bytes(data) + b"\0", np.uint8)
     sizes = np.ascontiguousarray(sizes, np.uint32)
-    cap = lib.hevcdl_access_unit_bound_slices(cfg.width, cfg.height, _layout_ptr(layout)) + data.size
+    cap = lib.hevcdl_access_unit_bound_segments(cfg.width, cfg.height, _layout_ptr(layout), _layout_ptr(segments)) + data.size
     buf = np.zeros(cap, np.uint8)
     n = ctypes.c_size_t(0)
     cp, _keep = _choice_ptr(choice)
-    if layout is not None:      # a slice NAL unit per slice (hevcdl_write_access_unit_from_slice_data_slices)
+    if segments is not None:
+        st = lib.hevcdl_write_access_unit_from_slice_data_segments(ctypes.byref(cfg), _layout_ptr(layout), ctypes.byref(segments), int(poc), data.ctypes.data, sizes.ctypes.data, int(sizes.size), cp, buf.ctypes.data, cap, ctypes.byref(n))
+    elif layout is not None:      # a slice NAL unit per slice (hevcdl_write_access_unit_from_slice_data_slices)
         st = lib.hevcdl_write_access_unit_from_slice_data_slices(ctypes.byref(cfg), ctypes.byref(layout), int(poc), data.ctypes.data, sizes.ctypes.data, int(sizes.size), cp, buf.ctypes.data, cap, ctypes.byref(n))
     elif cp is None:
         st = lib.hevcdl_write_access_unit_from_slice_data(ctypes.byref(cfg), int(poc), data.ctypes.data, sizes.ctypes.data, int(sizes.size), buf.ctypes.data, cap, ctypes.byref(n))
@@ -651,10 +684,11 @@ def write_access_unit_from_slice_data(cfg, poc, data, sizes, choice=None, layout
 
 
 def write_access_unit(width, height, qp, poc, records, level_idc=186, sao=None, tiles=(1, 1), bit_depth=8, lf_across_tiles=True, tools=TOOLS_REFERENCE, lf_offsets=(0, 0), lf_disable=False,
-                      rewrite_param_sets=True, wavefront=False, conf_win=(0, 0), choice=None, slices=None, lf_across_slices=True):
+                      rewrite_param_sets=True, wavefront=False, conf_win=(0, 0), choice=None, slices=None, lf_across_slices=True, segments=None):
     """Host-side bitstream writer (no GPU): VPS+SPS+PPS+slice NAL of one picture from its CTU records -> bytes.  choice: the picture's deblocking parameters
     and whether the PPS lets a slice override (hevcdl_write_access_unit_dbk: DeblockingFilterMetric, LoopFilterOffsetInPPS 0).  slices: (SliceMode, SliceArgument) -- a slice
-    NAL unit per slice (hevcdl_write_access_unit_slices), lf_across_slices the two across-slices flags."""
+    NAL unit per slice (hevcdl_write_access_unit_slices), lf_across_slices the two across-slices flags.  segments: (SliceSegmentMode, SliceSegmentArgument) -- a NAL unit per
+    dependent slice segment (hevcdl_write_access_unit_segments)."""
     lib = load_library()
     cfg = stream_config(width, height, qp, level_idc, False, tiles, bit_depth, lf_across_tiles, tools, lf_offsets, lf_disable, rewrite_param_sets, wavefront, conf_win)
     sao_ptr = None
@@ -664,11 +698,14 @@ def write_access_unit(width, height, qp, poc, records, level_idc=186, sao=None, 
         sao_ptr = sao.ctypes.data
     records = np.ascontiguousarray(records)
     layout = slice_layout(slices, lf_across_slices)
-    cap = lib.hevcdl_access_unit_bound_slices(width, height, _layout_ptr(layout))
+    segments = segment_layout(segments)
+    cap = lib.hevcdl_access_unit_bound_segments(width, height, _layout_ptr(layout), _layout_ptr(segments))
     buf = np.zeros(cap, np.uint8)
     n = ctypes.c_size_t(0)
     cp, _keep = _choice_ptr(choice)
-    if layout is not None:
+    if segments is not None:
+        st = lib.hevcdl_write_access_unit_segments(ctypes.byref(cfg), _layout_ptr(layout), ctypes.byref(segments), int(poc), records.ctypes.data, sao_ptr, cp, buf.ctypes.data, cap, ctypes.byref(n))
+    elif layout is not None:
         st = lib.hevcdl_write_access_unit_slices(ctypes.byref(cfg), ctypes.byref(layout), int(poc), records.ctypes.data, sao_ptr, cp, buf.ctypes.data, cap, ctypes.byref(n))
     elif cp is None:
         st = lib.hevcdl_write_access_unit(ctypes.byref(cfg), int(poc), records.ctypes.data, sao_ptr, buf.ctypes.data, cap, ctypes.byref(n))
@@ -743,11 +780,13 @@ class Encoder:
     """One context per device.  Frames are planar 8-bit 4:2:0, numpy [n_frames, w*h*3/2] uint8."""
 
     def __init__(self, width, height, qp, max_frames=1, device=0, cnn_input=0, weights=None, cfg=None, tiles=(1, 1), bit_depth=8, lf_across_tiles=True, bn_mode=0, tools=TOOLS_REFERENCE, lf_offsets=(0, 0), wavefront=False,
-                 deblocking_metric=0, lf_offset_in_pps=True, slices=None, lf_across_slices=True):
-        """bit_depth 10: every yuv / recon array of the decision path holds uint16 samples (frame_bytes counts bytes).  slices: (SliceMode, SliceArgument)."""
+                 deblocking_metric=0, lf_offset_in_pps=True, slices=None, lf_across_slices=True, segments=None):
+        """bit_depth 10: every yuv / recon array of the decision path holds uint16 samples (frame_bytes counts bytes).  slices: (SliceMode, SliceArgument); segments:
+        (SliceSegmentMode, SliceSegmentArgument) -- dependent slice segments, which change the stream alone."""
         self.lib = load_library()
         self.cfg = cfg or default_config(width, height, qp, max_frames, device, cnn_input, tiles, bit_depth, lf_across_tiles, bn_mode, tools, lf_offsets, wavefront,
-                                         deblocking_metric, lf_offset_in_pps, slices, lf_across_slices)
+                                         deblocking_metric, lf_offset_in_pps, slices, lf_across_slices, segments)
+        self.segment_layout = segment_layout((self.cfg.slice_segment_mode, self.cfg.slice_segment_argument))
         self.slice_layout = slice_layout((self.cfg.slice_mode, self.cfg.slice_argument), self.cfg.lf_across_slices != 0)      # what the writer's entry points take for this context's pictures
         self.bit_depth = self.cfg.bit_depth
         self.sample_dtype = np.uint8 if self.bit_depth == 8 else np.dtype("<u2")

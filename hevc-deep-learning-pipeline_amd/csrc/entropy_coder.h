@@ -60,7 +60,7 @@ struct EcPic {
   int W, H, ctus_x, ctus_y, ctus;
   int tx0, ty0;                  // top-left luma sample of the tile being written: nothing left of / above it is a neighbour
   uint32_t tools; int max_sao_offset;
-  int slice_end_ctu = -1;        // raster address of the last CTU of the sub-stream when a slice ends with it; -1: none but the picture's last CTU ends a slice (no slices, or a
+  int slice_end_ctu = -1;        // raster address of the last CTU of the sub-stream when a slice, or a dependent slice segment, ends with it; -1: none but the picture's last CTU ends one (no slices, or a
                                  // sub-stream inside a slice).  The one member with a default: code that fills an EcPic field by field and knows no slices needs no change
 };
 struct EcCu { int x, y, log2, depth, zbase, nparts, part; const hevcdl_ctu_record *r; };
@@ -499,6 +499,16 @@ EC_FN void ec_unit_rect(int wpp, int tcols, const int *col_bd, const int *row_bd
 // Does sub-stream k of `units` end a slice?  slice_units: sub-streams (tiles) per slice -- 0: one slice a picture; SliceMode 1 (a grid of one column, a slice per row
 // of it): 1; SliceMode 3: SliceArgument, the last slice taking what is left (TEncSlice::calculateBoundingCtuTsAddrForSlice, FIXED_NUMBER_OF_TILES).
 EC_FN int ec_ends_slice(int slice_units, int k, int units) { return k == units - 1 || (slice_units > 0 && (k + 1) % slice_units == 0); }
+// Does it end a slice SEGMENT (SliceSegmentMode 1 over WaveFrontSynchro rows, 3 over tiles)?  segment_units: sub-streams (CTU rows, tiles) per segment, counted from the
+// start of the slice -- a segment never runs past the end of its slice (TEncSlice.cpp:1285-1288) -- 0: no dependent segments, and the answer is ec_ends_slice's.  The end of
+// a segment is coded as the end of a slice: end_of_slice_segment_flag 1 alone.
+EC_FN int ec_ends_segment(int slice_units, int segment_units, int k, int units)
+{
+  if (ec_ends_slice(slice_units, k, units)) return 1;
+  if (segment_units <= 0) return 0;
+  const int in_slice = slice_units > 0 ? k % slice_units : k;
+  return (in_slice + 1) % segment_units == 0;
+}
 // ... and p.slice_end_ctu of that sub-stream, the CTUs [cx0, cx1) x [cy0, cy1)
 EC_FN int ec_slice_end_ctu(int ends_slice, int ctus_x, int cx1, int cy1) { return ends_slice ? (cy1 - 1) * ctus_x + cx1 - 1 : -1; }
 

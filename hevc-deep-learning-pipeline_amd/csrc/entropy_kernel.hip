@@ -83,7 +83,7 @@ extern "C" __global__ __launch_bounds__(EC_WAVES * 64) void hevcdl_entropy_kerne
   ec_unit_rect(p.wpp, p.tile_cols, p.col_bd, p.row_bd, p.ctus_x, k, cx0, cx1, cy0, cy1);
   if (cx0 < 0 || cy0 < 0 || cx1 > p.ctus_x || cy1 > p.ctus_y) return;
   if (!p.wpp) { pic.tx0 = cx0 * 64; pic.ty0 = cy0 * 64; }
-  pic.slice_end_ctu = ec_slice_end_ctu(ec_ends_slice(p.wpp ? 0 : p.slice_units, k, p.units), p.ctus_x, cx1, cy1);
+  pic.slice_end_ctu = ec_slice_end_ctu(ec_ends_segment(p.wpp ? 0 : p.slice_units, p.segment_units, k, p.units), p.ctus_x, cx1, cy1);
   if (p.wpp && k > 0 && p.ctus_x > 1 && p.sync) { // every lane copies the whole set: nothing a lane reads from LDS later was written by another lane
     const uint32_t *src = sync + (k - 1) * (EC_SYNC_BYTES / 4);
     for (int i = 0; i < EC_SYNC_BYTES / 4; i++) ((uint32_t *)l.ctx)[i] = src[i];

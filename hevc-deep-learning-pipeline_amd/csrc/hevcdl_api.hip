@@ -144,6 +144,7 @@ struct hevcdl_ctx {
   char last_rd[160] = { 0 };           // which build and launch form the last decision launch took (hevcdl_last_rd_launch)
   hevcdl_config cfg = {};              // as created -- but with slices its tile fields hold the grid the context RUNS (hevcdl_create): a column of row slices for SliceMode 1
   hevcdl_slice_layout slices = { 0, 0, 1 };      // what the caller's slice keys say; the stream is written from this, never from the grid
+  hevcdl_segment_layout segments = { 0, 0 };     // the caller's SliceSegmentMode / SliceSegmentArgument: the stream's alone -- ctx->cfg does not hold them (slice_grid.h)
   int stream_lf_across_tiles = 1;      // the caller's lf_across_tiles (cfg's is the effective one: in SliceMode 3 combined with lf_across_slices)
   int ctus_x = 0, ctus_y = 0, ctus = 0, n_cus = 0; size_t frame_bytes = 0;
   int col_bd[21] = { 0 }, row_bd[23] = { 0 };    // tile boundaries in CTUs
@@ -396,7 +397,7 @@ extern "C" hevcdl_status hevcdl_create(const hevcdl_config *cfg, const float *we
   if (cfg->deblocking_metric != 0 && cfg->lf_offset_in_pps != 0) return refuse(HEVCDL_ERR_INVALID_ARG, "If DeblockingFilterMetric is non-zero then both LoopFilterDisable and LoopFilterOffsetInPPS must be 0");
   if (cfg->deblocking_metric == 1 && (hevcdl_dbk_metric_edges(cfg->width) < 1 || hevcdl_dbk_metric_edges(cfg->height) < 1))
     return refuse(HEVCDL_ERR_INVALID_ARG, "DeblockingFilterMetric 1 needs a coded picture of at least 64 luma samples in either direction (the reference asserts noCol > 1 && noRows > 1)");
-  // Slices: the grid the context runs (slice_grid.h) -- a column of row slices for SliceMode 1, the cfg's tiles otherwise
+  // Slices: the grid the context runs (slice_grid.h) -- a column of row slices for SliceMode 1, the cfg's tiles otherwise; the segment keys are checked there and left out of it
   hevcdl_config grid;
   { const char *why = ""; const hevcdl_status gs = hevcdl_slice_grid(cfg, &grid, &why); if (gs != HEVCDL_OK) return refuse(gs, why); }
   int ndev = 0;
@@ -405,6 +406,7 @@ extern "C" hevcdl_status hevcdl_create(const hevcdl_config *cfg, const float *we
   if (!ctx) return HEVCDL_ERR_OOM;
   ctx->cfg = grid; ctx->stream_lf_across_tiles = cfg->lf_across_tiles;
   ctx->slices.mode = cfg->slice_mode; ctx->slices.argument = cfg->slice_mode ? cfg->slice_argument : 0; ctx->slices.lf_across_slices = cfg->slice_mode ? cfg->lf_across_slices != 0 : 1;
+  ctx->segments.mode = cfg->slice_segment_mode; ctx->segments.argument = cfg->slice_segment_mode ? cfg->slice_segment_argument : 0;
   cfg = &ctx->cfg;      // the one place the grid comes from
   ctx->ctus_x = (cfg->width + 63) >> 6; ctx->ctus_y = (cfg->height + 63) >> 6; ctx->ctus = ctx->ctus_x * ctx->ctus_y;
   ctx->frame_bytes = hevcdl_frame_bytes_bd(cfg->width, cfg->height, cfg->bit_depth);
@@ -1648,18 +1650,18 @@ struct EntropyPlan {
   hevcdl_entropy_params k;             // geometry, QP, tools filled; pointers not
   std::vector<uint32_t> off, cap; size_t frame_stride; int units;
 };
-static hevcdl_status entropy_plan(const hevcdl_stream_config *cfg, const hevcdl_slice_layout *layout, int capacity_per_ctu, EntropyPlan &pl)
+static hevcdl_status entropy_plan(const hevcdl_stream_config *cfg, const hevcdl_slice_layout *layout, const hevcdl_segment_layout *segments, int capacity_per_ctu, EntropyPlan &pl)
 {
   int n = 0; size_t bytes = 0;
-  TRY(hevcdl_slice_data_layout_slices(cfg, layout, capacity_per_ctu, &n, &bytes, nullptr, nullptr));
+  TRY(hevcdl_slice_data_layout_segments(cfg, layout, segments, capacity_per_ctu, &n, &bytes, nullptr, nullptr));
   pl.off.resize((size_t)n); pl.cap.resize((size_t)n);
-  TRY(hevcdl_slice_data_layout_slices(cfg, layout, capacity_per_ctu, &n, &bytes, pl.off.data(), pl.cap.data()));
+  TRY(hevcdl_slice_data_layout_segments(cfg, layout, segments, capacity_per_ctu, &n, &bytes, pl.off.data(), pl.cap.data()));
   pl.units = n; pl.frame_stride = bytes;
   hevcdl_entropy_params &k = pl.k; memset(&k, 0, sizeof k);
   k.width = cfg->width; k.height = cfg->height; k.ctus_x = (cfg->width + 63) >> 6; k.ctus_y = (cfg->height + 63) >> 6; k.qp = cfg->qp; k.tools = (int)cfg->tools;
   k.max_sao_offset = (1 << ((cfg->bit_depth < 10 ? cfg->bit_depth : 10) - 5)) - 1; k.wpp = cfg->wavefront != 0; k.units = n; k.frame_stride = bytes;
   int rows = 0;
-  return (hevcdl_status)hevcdl_substream_grid(cfg, layout, &k.tile_cols, &rows, k.col_bd, k.row_bd, &k.slice_units);    // the writer's own grid: the cfg's tiles, or a column of row slices
+  return (hevcdl_status)hevcdl_substream_grid(cfg, layout, segments, &k.tile_cols, &rows, k.col_bd, k.row_bd, &k.slice_units, &k.segment_units);    // the writer's own grid: the cfg's tiles, or a column of row slices
 }
 
 extern "C" hevcdl_status hevcdl_code_slice_data(int device, const hevcdl_stream_config *cfg, const hevcdl_ctu_record *records, const hevcdl_sao_blk *sao_opt, int n_frames,
@@ -1671,9 +1673,16 @@ extern "C" hevcdl_status hevcdl_code_slice_data(int device, const hevcdl_stream_
 extern "C" hevcdl_status hevcdl_code_slice_data_slices(int device, const hevcdl_stream_config *cfg, const hevcdl_slice_layout *layout, const hevcdl_ctu_record *records,
                                                        const hevcdl_sao_blk *sao_opt, int n_frames, int capacity_per_ctu, uint8_t *out, size_t out_capacity, uint32_t *sizes, uint32_t *overflow)
 {
+  return hevcdl_code_slice_data_segments(device, cfg, layout, nullptr, records, sao_opt, n_frames, capacity_per_ctu, out, out_capacity, sizes, overflow);
+}
+
+extern "C" hevcdl_status hevcdl_code_slice_data_segments(int device, const hevcdl_stream_config *cfg, const hevcdl_slice_layout *layout, const hevcdl_segment_layout *segments,
+                                                         const hevcdl_ctu_record *records, const hevcdl_sao_blk *sao_opt, int n_frames, int capacity_per_ctu, uint8_t *out, size_t out_capacity,
+                                                         uint32_t *sizes, uint32_t *overflow)
+{
   if (!cfg || !records || !out || !sizes || !overflow || n_frames < 0) return HEVCDL_ERR_INVALID_ARG;
   EntropyPlan pl;
-  TRY(entropy_plan(cfg, layout, capacity_per_ctu, pl));
+  TRY(entropy_plan(cfg, layout, segments, capacity_per_ctu, pl));
   if ((cfg->sao_enabled != 0) != (sao_opt != nullptr)) return HEVCDL_ERR_INVALID_ARG;
   if (out_capacity / (pl.frame_stride ? pl.frame_stride : 1) < (size_t)n_frames) return HEVCDL_ERR_INVALID_ARG;
   if (n_frames == 0) return HEVCDL_OK;
@@ -1726,6 +1735,13 @@ extern "C" hevcdl_status hevcdl_get_slice_layout(const hevcdl_ctx *ctx, hevcdl_s
   return HEVCDL_OK;
 }
 
+extern "C" hevcdl_status hevcdl_get_segment_layout(const hevcdl_ctx *ctx, hevcdl_segment_layout *out)
+{
+  if (!ctx || !out) return HEVCDL_ERR_INVALID_ARG;
+  *out = ctx->segments;
+  return HEVCDL_OK;
+}
+
 static void entropy_release(hevcdl_ctx *ctx)
 {
   ctx->ec = Entropy();
@@ -1744,7 +1760,7 @@ extern "C" hevcdl_status hevcdl_enable_device_entropy(hevcdl_ctx *ctx, int on)
   if (ctx->ec.entropy_on) return HEVCDL_OK;
   hevcdl_stream_config sc; entropy_stream_config(ctx, 0, &sc);
   EntropyPlan pl;
-  const hevcdl_status st = entropy_plan(&sc, &ctx->slices, ctx->ec_capacity_per_ctu, pl); if (st) return fail(ctx, st, "device entropy: stream configuration");
+  const hevcdl_status st = entropy_plan(&sc, &ctx->slices, &ctx->segments, ctx->ec_capacity_per_ctu, pl); if (st) return fail(ctx, st, "device entropy: stream configuration");
   // the workspace holds the regions of at most ENTROPY_WS_BYTES worth of pictures (84 MB a picture at 2160p: 2040 CTUs x 40 KB); larger batches go through it in passes
   const size_t ENTROPY_WS_BYTES = (size_t)512 << 20;
   const int pass = (int)std::max<size_t>(1, std::min<size_t>((size_t)ctx->cfg.max_frames, ENTROPY_WS_BYTES / pl.frame_stride));
@@ -1768,7 +1784,7 @@ static hevcdl_status entropy_pipeline(hevcdl_ctx *ctx, int n_frames, int want_sa
 {
   hevcdl_stream_config sc; entropy_stream_config(ctx, want_sao, &sc);
   EntropyPlan pl;
-  hevcdl_status st = entropy_plan(&sc, &ctx->slices, ctx->ec_capacity_per_ctu, pl); if (st) return fail(ctx, st, "device entropy: stream configuration");
+  hevcdl_status st = entropy_plan(&sc, &ctx->slices, &ctx->segments, ctx->ec_capacity_per_ctu, pl); if (st) return fail(ctx, st, "device entropy: stream configuration");
   const int units = ctx->ec.ec_units;
   ctx->ec_ms[0] = ctx->ec_ms[1] = ctx->ec_ms[2] = 0;
   Event ev[5];      // with the profile switch: start, between the two launches, end of the coding, around the pack launch
@@ -1829,9 +1845,9 @@ static hevcdl_status entropy_pipeline(hevcdl_ctx *ctx, int n_frames, int want_sa
         HIPCHK(hipMemcpy(rec.data(), ctx->stage.d_records + rec_b * f, rec_b, hipMemcpyDeviceToHost));
         if (want_sao) HIPCHK(hipMemcpy(sao.data(), ctx->sao.d_sao_params + sao_b * f, sao_b, hipMemcpyDeviceToHost));
         size_t total = 0; uint32_t *sz = ctx->ec.h_slice_sizes.data() + (size_t)f * units;
-        hevcdl_host_writer_slice_data(&sc, &ctx->slices, rec.data(), want_sao ? sao.data() : nullptr, nullptr, 0, sz, &total);
+        hevcdl_host_writer_slice_data(&sc, &ctx->slices, &ctx->segments, rec.data(), want_sao ? sao.data() : nullptr, nullptr, 0, sz, &total);
         all.resize(at[(size_t)f] + total);
-        if (hevcdl_host_writer_slice_data(&sc, &ctx->slices, rec.data(), want_sao ? sao.data() : nullptr, all.data() + at[(size_t)f], total, sz, &total) != 0) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "device entropy: host fallback");
+        if (hevcdl_host_writer_slice_data(&sc, &ctx->slices, &ctx->segments, rec.data(), want_sao ? sao.data() : nullptr, all.data() + at[(size_t)f], total, sz, &total) != 0) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "device entropy: host fallback");
       } else all.insert(all.end(), ctx->ec.h_slice.begin() + (ptrdiff_t)ctx->ec.h_slice_at[(size_t)f], ctx->ec.h_slice.begin() + (ptrdiff_t)ctx->ec.h_slice_at[(size_t)f + 1]);
     }
     at[(size_t)n_frames] = all.size();

@@ -33,6 +33,7 @@
 #include <thread>
 #include <vector>
 #include "hevcdl.h"
+#include "slice_grid.h"      // hevcdl_segment_keys: the segment keys are refused here with the library's own sentences
 
 namespace {
 
@@ -57,7 +58,7 @@ const Key KEYS[] = {
   { "IntraPeriod", 0, PATH, "1" }, { "GOPSize", 0, PATH, "1" }, { "MaxDeltaQP", 0, PATH, "0" }, { "DeltaQpRD", 0, PATH, "0" },
   { "RDOQ", 0, USED, 0 }, { "RDOQTS", 0, USED, 0 }, { "TransformSkip", 0, USED, 0 }, { "TransformSkipFast", 0, USED, 0 },
   { "SignHideFlag", "SBH", USED, 0 }, { "StrongIntraSmoothing", 0, USED, 0 }, { "FastUDIUseMPMEnabled", 0, USED, 0 },      // tool switches (hevcdl_config.tools): 0 or 1
-  { "SliceMode", 0, USED, 0 }, { "SliceArgument", 0, USED, 0 }, { "PCMEnabledFlag", 0, PATH, "0" }, { "NumTileColumnsMinus1", 0, USED, 0 },
+  { "SliceMode", 0, USED, 0 }, { "SliceArgument", 0, USED, 0 }, { "SliceSegmentMode", 0, USED, 0 }, { "SliceSegmentArgument", 0, USED, 0 }, { "PCMEnabledFlag", 0, PATH, "0" }, { "NumTileColumnsMinus1", 0, USED, 0 },
   { "NumTileRowsMinus1", 0, USED, 0 }, { "WaveFrontSynchro", 0, USED, 0 }, { "ScalingList", 0, PATH, "0" },
   { "TransquantBypassEnable", 0, PATH, "0" }, { "CUTransquantBypassFlagForce", 0, PATH, "0" },
   // stream / in-loop filter keys
@@ -341,8 +342,18 @@ int main(int argc, char **argv)
   else if (slice_mode == 3 && slice_arg > 1 && opt.geti("LFCrossTileBoundaryFlag", 1) != 0 && !lf_slices)
     opt.errors.push_back("SliceMode = 3 with more than one tile a slice, LFCrossTileBoundaryFlag = 1 and LFCrossSliceBoundaryFlag = 0 is not implemented by this path (the in-loop filters have one flag for all tile borders)");
   else if (slice_mode != 0 && dbk_metric != 0) opt.errors.push_back("slices together with DeblockingFilterMetric are not implemented by this path");
+  // Dependent slice segments (TAppEncCfg.cpp:942-943): SliceSegmentMode 1 = SliceSegmentArgument CTUs a segment (whole rows of a WaveFrontSynchro picture on this path),
+  // 3 = SliceSegmentArgument tiles a segment; the argument is read only then.  What hevcdl_create refuses is refused here in its words (csrc/slice_grid.h).
+  const long seg_mode = opt.geti("SliceSegmentMode", 0), seg_arg = seg_mode ? opt.geti("SliceSegmentArgument", 0) : 0;
+  if (seg_mode != 0 && width > 0 && height > 0) {
+    hevcdl_config probe; memset(&probe, 0, sizeof probe);
+    probe.width = width; probe.height = height; probe.tile_columns = tile_cols; probe.tile_rows = tile_rows; probe.wavefront = wavefront ? 1 : 0; probe.deblocking_metric = (int)dbk_metric;
+    probe.slice_mode = (int)slice_mode; probe.slice_segment_mode = (int)seg_mode; probe.slice_segment_argument = (int)seg_arg;
+    const char *why = "";
+    if (hevcdl_segment_keys(&probe, &why) != HEVCDL_OK) opt.errors.push_back("SliceSegmentMode = " + std::to_string(seg_mode) + ", SliceSegmentArgument = " + std::to_string(seg_arg) + ": " + why);
+  }
   if (opt.v.count("PrintConfig")) {
-    printf("{\"SliceMode\": %ld, \"SliceArgument\": %ld, \"LFCrossSliceBoundaryFlag\": %ld, ", slice_mode, slice_arg, lf_slices);
+    printf("{\"SliceMode\": %ld, \"SliceArgument\": %ld, \"LFCrossSliceBoundaryFlag\": %ld, \"SliceSegmentMode\": %ld, \"SliceSegmentArgument\": %ld, ", slice_mode, slice_arg, lf_slices, seg_mode, seg_arg);
     printf("\"InputFile\": \"%s\", \"ReconFile\": \"%s\", \"SourceWidth\": %d, \"SourceHeight\": %d, \"QP\": %d, \"FrameSkip\": %ld, \"FramesToBeEncoded\": %ld, "
            "\"FrameRate\": %g, \"LabelDir\": \"%s\", \"CnnInput\": \"%s\", \"BitstreamFile\": \"%s\", \"level_idc\": %d, \"tiles\": [%d, %d], \"bit_depth\": %d, "
            "\"ConformanceWindowMode\": %d, \"HorizontalPadding\": %d, \"VerticalPadding\": %d, \"InputBitDepth\": %d, \"InternalBitDepth\": %d, \"OutputBitDepth\": %d, \"coded_size\": [%d, %d], "
@@ -437,6 +448,7 @@ int main(int argc, char **argv)
   cfg.lf_beta_offset_div2 = (int)opt.geti("LoopFilterBetaOffset_div2", 0); cfg.lf_tc_offset_div2 = (int)opt.geti("LoopFilterTcOffset_div2", 0);      // -6 .. 6 (hevcdl_create checks)
   cfg.deblocking_metric = (int)dbk_metric; cfg.lf_offset_in_pps = (int)lf_in_pps;
   cfg.slice_mode = (int)slice_mode; cfg.slice_argument = (int)slice_arg; cfg.lf_across_slices = (int)lf_slices;
+  cfg.slice_segment_mode = (int)seg_mode; cfg.slice_segment_argument = (int)seg_arg;
   cfg.cnn_input = cnn_input == "luma" ? HEVCDL_CNN_INPUT_LUMA : HEVCDL_CNN_INPUT_RGB601;
   cfg.bn_mode = bn_mode == "eval" ? HEVCDL_BN_EVAL : HEVCDL_BN_REFERENCE;
   if (shared_device) cfg.exec_flags |= HEVCDL_EXEC_NO_UNIT_HANDOVER;
@@ -532,6 +544,7 @@ int main(int argc, char **argv)
   scfg.lf_across_tiles = cfg.lf_across_tiles; scfg.tile_uniform_spacing = cfg.tile_uniform_spacing; memcpy(scfg.tile_column_width, cfg.tile_column_width, sizeof scfg.tile_column_width); memcpy(scfg.tile_row_height, cfg.tile_row_height, sizeof scfg.tile_row_height);
   scfg.conf_win_right = width - src_w; scfg.conf_win_bottom = height - src_h;
   const hevcdl_slice_layout slices = { (int)slice_mode, (int)slice_arg, (int)lf_slices };      // NAL units, slice headers and the PPS's across-slices flag (mode 0: one slice, as ever)
+  const hevcdl_segment_layout segments = { (int)seg_mode, (int)seg_arg };      // a NAL unit per dependent slice segment (mode 0: none)
   if (conf_mode == 3) { scfg.conf_win_left = win_l; scfg.conf_win_right = win_r; scfg.conf_win_top = win_t; scfg.conf_win_bottom = win_b; }      // PSNR, the hash and the digests stay over the whole coded picture (no padding: m_aiPad is 0)
   const double ny = (double)src_w * src_h, nc = ny / 4;      // PSNR, MSE and MS-SSIM are taken over the picture without the padding (TEncGOP.cpp:2302-2303, 2375-2376)
   double sum_bits = 0, sum_psnr[3] = { 0, 0, 0 }, sum_mse[3] = { 0, 0, 0 }, sum_msssim[3] = { 0, 0, 0 }; long done = 0;
@@ -596,7 +609,7 @@ int main(int argc, char **argv)
       {
         std::atomic<int> next(0);
         auto work = [&]() {
-          std::vector<uint8_t> buf(hevcdl_access_unit_bound_slices(width, height, &slices));
+          std::vector<uint8_t> buf(hevcdl_access_unit_bound_segments(width, height, &slices, &segments));
           for (int i = next++; i < count; i = next++) {
             if (slice_data && buf.size() < slice_at[(size_t)i + 1] - slice_at[(size_t)i] + 4096) buf.resize(2 * (slice_at[(size_t)i + 1] - slice_at[(size_t)i]) + 4096);
             PicOut &po = pics[i]; po.md5_text[0] = 0;
@@ -636,8 +649,8 @@ int main(int argc, char **argv)
             }
             if (file_order && coded_order) std::swap(po.sse[1], po.sse[2]);
             // the access unit: VPS+SPS+PPS+slice, written to -b; its size is the picture's bit count (TEncGOP.cpp:2420-2447)
-            if (slice_data) po.st = hevcdl_write_access_unit_from_slice_data_slices(&scfg, &slices, (int)(cc.f0 + first + i), slice_data + slice_at[(size_t)i], slice_sizes + (size_t)i * n_sub, n_sub, &choices[i], buf.data(), buf.size(), &po.au_len);
-            else po.st = hevcdl_write_access_unit_slices(&scfg, &slices, (int)(cc.f0 + first + i), recs + (size_t)ctus * i, sao ? sao_params + (size_t)ctus * i : nullptr, &choices[i], buf.data(), buf.size(), &po.au_len);
+            if (slice_data) po.st = hevcdl_write_access_unit_from_slice_data_segments(&scfg, &slices, &segments, (int)(cc.f0 + first + i), slice_data + slice_at[(size_t)i], slice_sizes + (size_t)i * n_sub, n_sub, &choices[i], buf.data(), buf.size(), &po.au_len);
+            else po.st = hevcdl_write_access_unit_segments(&scfg, &slices, &segments, (int)(cc.f0 + first + i), recs + (size_t)ctus * i, sao ? sao_params + (size_t)ctus * i : nullptr, &choices[i], buf.data(), buf.size(), &po.au_len);
             if (po.st != HEVCDL_OK) continue;
             po.bytes.assign(buf.begin(), buf.begin() + po.au_len);
             if (hash_sei) { // suffix SEI after the slice; not part of the picture's bit count (as in the reference)

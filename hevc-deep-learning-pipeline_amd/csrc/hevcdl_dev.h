@@ -226,6 +226,7 @@ struct hevcdl_entropy_params {
   int width, height, ctus_x, ctus_y, qp, tools, max_sao_offset, wpp, tile_cols;
   int col_bd[21], row_bd[23];
   int slice_units;                 // sub-streams per slice (hevcdl_ec::ec_ends_slice): 0 = the picture is one slice; 1 = SliceMode 1 (the grid is one column of row slices); n = SliceMode 3
+  int segment_units;               // sub-streams per dependent slice segment (hevcdl_ec::ec_ends_segment): 0 = none; SliceSegmentMode 1: CTU rows of a wavefront picture; 3: tiles
 };
 struct hevcdl_entropy_pack_params {
   const unsigned char *src; unsigned char *dst;
@@ -310,10 +311,12 @@ void hevcdl_source_window_size(const struct hevcdl_source_format *fmt, int *ww, 
 // fallback for a picture whose sub-stream overflowed its region on the device; 0, or -1 when `capacity` is too small or `out` is null (sizes and *total are set either way)
 struct hevcdl_slice_layout;
 // hevcdl_bitstream.cpp: the grid of sub-streams the writer derives from a stream configuration and a slice layout (NULL: none) -- the cfg's tiles, or with SliceMode 1 one
-// column of row slices -- and the sub-streams per slice (hevcdl_entropy_params.slice_units); a hevcdl_status
-int hevcdl_substream_grid(const struct hevcdl_stream_config *cfg, const struct hevcdl_slice_layout *layout, int *cols, int *rows, int col_bd[21], int row_bd[23], int *slice_units);
-int hevcdl_host_writer_slice_data(const struct hevcdl_stream_config *cfg, const struct hevcdl_slice_layout *layout, const struct hevcdl_ctu_record *records, const struct hevcdl_sao_blk *sao, uint8_t *out, size_t capacity,
-                                  uint32_t *sizes, size_t *total);
+// column of row slices -- and the sub-streams per slice and per dependent slice segment (hevcdl_entropy_params.slice_units, .segment_units; `segments` NULL: none); a hevcdl_status
+struct hevcdl_segment_layout;
+int hevcdl_substream_grid(const struct hevcdl_stream_config *cfg, const struct hevcdl_slice_layout *layout, const struct hevcdl_segment_layout *segments, int *cols, int *rows, int col_bd[21],
+                          int row_bd[23], int *slice_units, int *segment_units);
+int hevcdl_host_writer_slice_data(const struct hevcdl_stream_config *cfg, const struct hevcdl_slice_layout *layout, const struct hevcdl_segment_layout *segments, const struct hevcdl_ctu_record *records,
+                                  const struct hevcdl_sao_blk *sao, uint8_t *out, size_t capacity, uint32_t *sizes, size_t *total);
 void hevcdl_launch_entropy(const struct hevcdl_entropy_params *p, void *stream, void *mid_event_opt);      // one launch, or the two of the wavefront scheme; mid_event_opt (a hipEvent_t) is recorded between the two
 void hevcdl_launch_entropy_pack(const struct hevcdl_entropy_pack_params *p, void *stream);
 size_t hevcdl_cnn_smem_bytes(void);

@@ -8,10 +8,38 @@
 #define HEVCDL_SLICE_GRID_H
 #include "hevcdl.h"
 
-// cfg (valid but for its slice keys) -> *grid, or the status of the refusal and, in *why, its sentence
+// Dependent slice segments (SliceSegmentMode 1 over WaveFrontSynchro rows, 3 over tiles) change nothing a context computes: they are checked here and
+// then taken OUT of the grid configuration, so that launch plan, workspace and parameter blocks cannot see them; the context keeps them for the stream alone.
+static inline hevcdl_status hevcdl_segment_keys(const hevcdl_config *cfg, const char **why)
+{
+  *why = "";
+  if (cfg->slice_segment_mode == 0) return HEVCDL_OK;
+  const int cx = (cfg->width + 63) >> 6, tiled = cfg->tile_columns * cfg->tile_rows > 1;
+#define SEGMENT_REFUSE(status, text) do { *why = text; return status; } while (0)
+  if (cfg->slice_segment_mode == 2) SEGMENT_REFUSE(HEVCDL_ERR_UNSUPPORTED, "SliceSegmentMode 2 (slice segments by bytes) is not supported: the segment borders would depend on the coded bytes");
+  if (cfg->slice_segment_mode != 1 && cfg->slice_segment_mode != 3) SEGMENT_REFUSE(HEVCDL_ERR_INVALID_ARG, "SliceSegmentMode is 0, 1 or 3");
+  if (cfg->deblocking_metric != 0) SEGMENT_REFUSE(HEVCDL_ERR_UNSUPPORTED, "slice segments together with DeblockingFilterMetric are not supported");
+  if (cfg->slice_segment_mode == 1) {
+    if (tiled) SEGMENT_REFUSE(HEVCDL_ERR_UNSUPPORTED, "SliceSegmentMode 1 together with tiles is not supported (SliceSegmentMode 3 cuts a picture of tiles into segments)");
+    if (cfg->slice_mode != 0) SEGMENT_REFUSE(HEVCDL_ERR_UNSUPPORTED, "SliceSegmentMode 1 together with slices is not supported (row slices are refused with WaveFrontSynchro, which these segments need)");
+    if (!cfg->wavefront)
+      SEGMENT_REFUSE(HEVCDL_ERR_UNSUPPORTED, "SliceSegmentMode 1 needs WaveFrontSynchro: without it a segment starts in the middle of a coder chain and the reference's decisions change from its first CTU on");
+    if (cfg->slice_segment_argument < 1 || cfg->slice_segment_argument % cx != 0)
+      SEGMENT_REFUSE(HEVCDL_ERR_UNSUPPORTED, "SliceSegmentMode 1 needs a SliceSegmentArgument that is a positive multiple of the picture's width in CTUs: a segment that starts inside a CTU row changes the reference's decisions");
+    return HEVCDL_OK;
+  }
+  if (!tiled) SEGMENT_REFUSE(HEVCDL_ERR_INVALID_ARG, "SliceSegmentMode 3 (segments of whole tiles) needs tiles");
+  if (cfg->slice_segment_argument < 1) SEGMENT_REFUSE(HEVCDL_ERR_INVALID_ARG, "SliceSegmentMode 3 needs a SliceSegmentArgument of at least 1 tile");
+#undef SEGMENT_REFUSE
+  return HEVCDL_OK;
+}
+
+// cfg (valid but for its slice and segment keys) -> *grid, or the status of the refusal and, in *why, its sentence
 static inline hevcdl_status hevcdl_slice_grid(const hevcdl_config *cfg, hevcdl_config *grid, const char **why)
 {
-  *grid = *cfg; *why = "";
+  *grid = *cfg;
+  { const hevcdl_status ss = hevcdl_segment_keys(cfg, why); if (ss != HEVCDL_OK) return ss; }
+  grid->slice_segment_mode = grid->slice_segment_argument = 0;
   if (cfg->slice_mode == 0) return HEVCDL_OK;
   const int cx = (cfg->width + 63) >> 6, cy = (cfg->height + 63) >> 6, tiled = cfg->tile_columns * cfg->tile_rows > 1;
 #define SLICE_REFUSE(status, text) do { *why = text; return status; } while (0)

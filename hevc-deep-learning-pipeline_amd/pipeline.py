@@ -43,7 +43,7 @@ def read_frames(path, width, height, first, count, bit_depth=8, frame_samples=No
 
 def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None, recon_path=None, frame_skip=0, batch=256, tiles=(1, 1),
                     lf_across_tiles=True, bit_depth=8, level_idc=186, frame_rate=30.0, hash_sei=False, labels_fn=None, device=None, log=print, tools=0x7f, wavefront=False, device_entropy=False, device_report=False, source_format=None,
-                    deblocking_metric=0, lf_offset_in_pps=True, slices=None, lf_across_slices=True):
+                    deblocking_metric=0, lf_offset_in_pps=True, slices=None, lf_across_slices=True, segments=None):
     """Encode frames [frame_skip, frame_skip + n_frames) of a planar YUV file.  Works stand-alone and under torch.distributed
     (initialised by the caller): rank r takes a contiguous share of the frames.  Returns, on rank 0, the summary (metrics.Summary)
     and the list of per-picture rows [poc, bits, sseY, sseU, sseV]; other ranks return (None, None).
@@ -64,7 +64,9 @@ def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None
     with more than one rank.
     slices = (SliceMode, SliceArgument), lf_across_slices = LFCrossSliceBoundaryFlag: mode 1 cuts a picture into slices of whole CTU rows (SliceArgument a multiple of the
     width in CTUs; independent units of the decision launch, like tiles), mode 3 a picture of tiles into slices of SliceArgument tiles.  Every slice is a NAL unit of its own;
-    what the library refuses (hevcdl.h, hevcdl_config.slice_mode) is raised with its reason."""
+    what the library refuses (hevcdl.h, hevcdl_config.slice_mode) is raised with its reason.
+    segments = (SliceSegmentMode, SliceSegmentArgument): dependent slice segments -- mode 1 makes every SliceSegmentArgument / width-in-CTUs rows of a wavefront picture a NAL
+    unit of its own, mode 3 every SliceSegmentArgument tiles.  Nothing but the stream changes (hevcdl.h, hevcdl_config.slice_segment_mode)."""
     if deblocking_metric not in (0, 1, 2):
         raise ValueError("DeblockingFilterMetric %r is not a value of the key (0, 1 or 2)" % (deblocking_metric,))
     if deblocking_metric and lf_offset_in_pps:
@@ -86,7 +88,7 @@ def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None
     part_rec = (recon_path + ".part%d" % rank) if recon_path else None
     fb, fr = open(part_bits, "wb") if part_bits else None, open(part_rec, "wb") if part_rec else None
     if len(mine):
-        enc = Encoder(width, height, qp, max_frames=min(batch, len(mine)), device=device, tiles=tiles, bit_depth=bit_depth, lf_across_tiles=lf_across_tiles, tools=tools, wavefront=wavefront, slices=slices, lf_across_slices=lf_across_slices, **dbk)      # tools: HEVCDL_TOOL_*; wavefront: WaveFrontSynchro mask (the cfg's tool switches)
+        enc = Encoder(width, height, qp, max_frames=min(batch, len(mine)), device=device, tiles=tiles, bit_depth=bit_depth, lf_across_tiles=lf_across_tiles, tools=tools, wavefront=wavefront, slices=slices, lf_across_slices=lf_across_slices, segments=segments, **dbk)      # tools: HEVCDL_TOOL_*; wavefront: WaveFrontSynchro mask (the cfg's tool switches)
         sf = source_format
         sw, sh = (sf.source_width, sf.source_height) if sf is not None else (width, height)
         conf_win = (width - sw, height - sh)
@@ -123,9 +125,9 @@ def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None
             choices = enc.get_dbk_choice(0, nb)      # what every picture's slice header says about its deblocking filter
             def one_picture(i):          # host work of a picture (arithmetic coder, hash, SSE): independent -> thread pool (ctypes drops the GIL)
                 if device_entropy:
-                    au = write_access_unit_from_slice_data(scfg, b0 + i, slice_data[i], slice_sizes[i], choices[i], layout=enc.slice_layout)
+                    au = write_access_unit_from_slice_data(scfg, b0 + i, slice_data[i], slice_sizes[i], choices[i], layout=enc.slice_layout, segments=enc.segment_layout)
                 else:
-                    au = write_access_unit(width, height, qp, b0 + i, recs[i], level_idc=level_idc, sao=sao[i], tiles=tiles, bit_depth=bit_depth, lf_across_tiles=lf_across_tiles, tools=tools, wavefront=wavefront, conf_win=conf_win, choice=choices[i], slices=slices, lf_across_slices=lf_across_slices)
+                    au = write_access_unit(width, height, qp, b0 + i, recs[i], level_idc=level_idc, sao=sao[i], tiles=tiles, bit_depth=bit_depth, lf_across_tiles=lf_across_tiles, tools=tools, wavefront=wavefront, conf_win=conf_win, choice=choices[i], slices=slices, lf_across_slices=lf_across_slices, segments=enc.segment_layout)
                 if device_report:
                     return au, digest_sei(1, report_digest(reports[i])) if hash_sei else b"", [int(v) for v in reports[i]["sse"]]
                 sei = picture_hash_sei(width, height, final[i], bit_depth) if hash_sei else b""
@@ -176,14 +178,16 @@ def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None
 
 
 def encode_sequence_tile_sharded(input_path, width, height, qp, n_frames, tiles, bitstream_path=None, recon_path=None, frame_skip=0, batch=None, lf_across_tiles=True,
-                                 bit_depth=8, level_idc=186, frame_rate=30.0, hash_sei=False, device=None, log=print, tools=0x7f, slices=None):
+                                 bit_depth=8, level_idc=186, frame_rate=30.0, hash_sei=False, device=None, log=print, tools=0x7f, slices=None, segments=None):
     """The within-picture partition: every rank decides its share of the TILES of every picture of a batch
     (`hevcdl_compress_tiles_dev`), one all-to-all moves the tile payloads to the picture's owner (`sharding.exchange_tiles_to_owners`:
     picture i of the batch -> rank i mod world), the owner runs the in-loop filters on the assembled picture and writes its access unit.
-    Needs torch.distributed initialised; batch (default: world size) is a multiple of the world size.  Output == encode_sequence().  Slices are refused: the owner writes
-    one slice a picture."""
+    Needs torch.distributed initialised; batch (default: world size) is a multiple of the world size.  Output == encode_sequence().  Slices and dependent slice segments
+    are refused: the owner writes one slice NAL unit a picture."""
     if slices is not None and int(slices[0]) != 0:
         raise ValueError("the tile-sharded path does not code slices (SliceMode %d): use encode_sequence" % int(slices[0]))
+    if segments is not None and int(segments[0]) != 0:
+        raise ValueError("the tile-sharded path does not code slice segments (SliceSegmentMode %d): use encode_sequence" % int(segments[0]))
     import torch
     import torch.distributed as dist
     from . import REC_DTYPE, SAO_DTYPE

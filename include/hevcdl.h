@@ -131,6 +131,15 @@ typedef struct hevcdl_config {
    * a slice follows lf_across_tiles alone: more than one tile a slice with lf_across_tiles 1 and lf_across_slices 0 is refused (the filters have one flag).  Not together
    * with deblocking_metric, and the per-CTU session refuses such a context.  hevcdl_create_error names what was refused. */
   int32_t  slice_mode, slice_argument, lf_across_slices;
+  /* Dependent slice segments (cfg keys SliceSegmentMode, SliceSegmentArgument).  slice_segment_mode 0 (the default; a zeroed tail means it): none, and
+   * the argument is not looked at.  1: segments of slice_segment_argument CTUs; needs wavefront 1, no tiles, slice_mode 0 and an argument that is a positive multiple of the
+   * picture's width in CTUs -- segments of argument / width whole CTU rows, the last one shorter; a picture one CTU wide makes every CTU a segment.  3: segments of
+   * slice_segment_argument tiles in raster order of the tile grid, the last one taking the rest; needs tiles and an argument of at least 1; may be combined with slice_mode 3,
+   * and a segment never runs past the end of its slice.  Both change nothing but the stream -- every segment is a NAL unit of its own with a short header, and a sub-stream
+   * that ends a segment ends with end_of_slice_segment_flag 1: launch plan, workspace, decisions, filters and the per-CTU session are those of the context without the keys.
+   * Refused: 2 (segments by bytes); mode 1 without wavefront or with segments that are not whole CTU rows (the reference's decisions change where a segment starts in the
+   * middle of a coder chain), mode 1 with tiles or slices, mode 3 without tiles, either mode with deblocking_metric.  hevcdl_create_error names what was refused. */
+  int32_t  slice_segment_mode, slice_segment_argument;
 } hevcdl_config;
 
 /* One CTU of decisions: what compressCtu leaves in the picture's CTU record (TEncCu.cpp:1091 copyToPic).
@@ -169,7 +178,7 @@ hevcdl_status hevcdl_config_default_bd(hevcdl_config *cfg, int width, int height
 /* weights: flat fp32 blob, HEVCDL_WEIGHT_FLOATS values (replaces torch.load at use_model.py:62). */
 hevcdl_status hevcdl_create(const hevcdl_config *cfg, const float *weights, size_t n_floats, hevcdl_ctx **out);
 /* Why the calling thread's last hevcdl_create refused its configuration: there is no context to ask yet.  ONLY the refusals of the deblocking keys (deblocking_metric,
- * lf_offset_in_pps) and of the slice keys (slice_mode, slice_argument, lf_across_slices) leave a message so far; every other failure of hevcdl_create, and a success, leave "" -- the status is then all there is. */
+ * lf_offset_in_pps), of the slice keys (slice_mode, slice_argument, lf_across_slices) and of the segment keys (slice_segment_mode, slice_segment_argument) leave a message so far; every other failure of hevcdl_create, and a success, leave "" -- the status is then all there is. */
 const char   *hevcdl_create_error(void);
 void          hevcdl_destroy(hevcdl_ctx *ctx);
 const char   *hevcdl_last_error(const hevcdl_ctx *ctx);
@@ -560,6 +569,37 @@ hevcdl_status hevcdl_code_slice_data_slices(int device, const hevcdl_stream_conf
 size_t        hevcdl_access_unit_bound_slices(int width, int height, const hevcdl_slice_layout *layout);
 /* The layout a context's pictures are written with (mode 0 for a context without slices). */
 hevcdl_status hevcdl_get_slice_layout(const hevcdl_ctx *ctx, hevcdl_slice_layout *out);
+
+/* ---- dependent slice segments (cfg keys SliceSegmentMode, SliceSegmentArgument) -----------------------------------------------------------------------------------------
+ * Neither hevcdl_stream_config nor hevcdl_slice_layout grows (recorded digests hash the first; callers pass the second without a size): the segments of a stream are this
+ * block, taken beside the slice layout by siblings of the _slices entry points.  A NULL block, or mode 0, is the _slices function.  mode 1: segments of `argument` CTUs --
+ * cfg with wavefront and without tiles, no slices, `argument` a positive multiple of the width in CTUs: argument / width CTU rows a segment.  mode 3: segments of `argument`
+ * tiles of cfg's tile grid, counted from the start of each slice of a mode-3 slice layout (a segment ends where its slice ends).  The sub-streams are those of the stream
+ * without segments (CTU rows, tiles).  Every segment is a NAL unit of its own: the PPS says dependent_slice_segments_enabled_flag 1; a header that does not start a slice is
+ * dependent_slice_segment_flag 1, slice_segment_address, the entry points of the segment's own rows or tiles, and the alignment (TEncCavlc.cpp:755-1109); a sub-stream that
+ * ends a segment ends with end_of_slice_segment_flag 1 alone.  Anything else is HEVCDL_ERR_INVALID_ARG, mode 2 HEVCDL_ERR_UNSUPPORTED. */
+typedef struct hevcdl_segment_layout {
+  int32_t mode;                  /* SliceSegmentMode 0, 1, 3 */
+  int32_t argument;              /* SliceSegmentArgument: CTUs (mode 1) or tiles (mode 3) a segment */
+} hevcdl_segment_layout;
+hevcdl_status hevcdl_write_access_unit_segments(const hevcdl_stream_config *cfg, const hevcdl_slice_layout *layout, const hevcdl_segment_layout *segments, int poc,
+                                                const hevcdl_ctu_record *records, const hevcdl_sao_blk *sao, const hevcdl_dbk_choice *choice, uint8_t *out, size_t capacity, size_t *out_len);
+hevcdl_status hevcdl_write_access_unit_from_slice_data_segments(const hevcdl_stream_config *cfg, const hevcdl_slice_layout *layout, const hevcdl_segment_layout *segments, int poc,
+                                                                const uint8_t *data, const uint32_t *sizes, int n_substreams, const hevcdl_dbk_choice *choice, uint8_t *out,
+                                                                size_t capacity, size_t *out_len);
+/* (the regions of a slice-data buffer do not depend on the segments; the function is there so that a caller passes one set of arguments everywhere) */
+hevcdl_status hevcdl_slice_data_layout_segments(const hevcdl_stream_config *cfg, const hevcdl_slice_layout *layout, const hevcdl_segment_layout *segments, int capacity_per_ctu,
+                                                int *n_substreams, size_t *picture_bytes, uint32_t *offsets_opt, uint32_t *capacities_opt);
+hevcdl_status hevcdl_code_slice_data_host_segments(const hevcdl_stream_config *cfg, const hevcdl_slice_layout *layout, const hevcdl_segment_layout *segments,
+                                                   const hevcdl_ctu_record *records, const hevcdl_sao_blk *sao_opt, int n_frames, int capacity_per_ctu, uint8_t *out, size_t out_capacity,
+                                                   uint32_t *sizes, uint32_t *overflow);
+hevcdl_status hevcdl_code_slice_data_segments(int device, const hevcdl_stream_config *cfg, const hevcdl_slice_layout *layout, const hevcdl_segment_layout *segments,
+                                              const hevcdl_ctu_record *records, const hevcdl_sao_blk *sao_opt, int n_frames, int capacity_per_ctu, uint8_t *out, size_t out_capacity,
+                                              uint32_t *sizes, uint32_t *overflow);
+/* hevcdl_access_unit_bound_slices plus the headers of the segment NAL units (one per CTU row or tile at the most) */
+size_t        hevcdl_access_unit_bound_segments(int width, int height, const hevcdl_slice_layout *layout, const hevcdl_segment_layout *segments);
+/* The segments a context's pictures are written with (mode 0 for a context without them). */
+hevcdl_status hevcdl_get_segment_layout(const hevcdl_ctx *ctx, hevcdl_segment_layout *out);
 
 /* Decoded picture hash (cfg key SEIDecodedPictureHash 1 = MD5): the suffix SEI NAL the reference appends to the access unit
  * (TEncGOP.cpp:1938-1960), computed from `picture` = the final reconstruction (planar 4:2:0; uint16 samples at 10 bits).  At most
