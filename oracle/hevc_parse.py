@@ -114,34 +114,69 @@ def parse_pps(n):
 
 
 def parse_slice_header(n, sps, pps):
-    """I slices of the reference's all-intra configuration only."""
+    """slice_segment_header() of 7.3.6.1 for the I slices the reference's all-intra configuration and the product write: the picture's first segment or a later one
+    (slice_segment_address in Ceil(Log2(PicSizeInCtbsY)) bits), independent or dependent.  A dependent header stops behind the address and goes on with its own
+    entry points; "dependent" and "address" are always in the result (0 for the picture's first segment)."""
     nt = (n[0] >> 1) & 63
     r = Bits(unescape(n)[2:]); f = {"nal_type": nt}
     f["first_slice"] = r.u(1)
     if 16 <= nt <= 23:
         f["no_output_prior"] = r.u(1)
     f["pps_id"] = r.ue()
-    assert f["first_slice"] == 1
-    f["slice_type"] = r.ue()
-    if nt not in (19, 20):
-        f["poc_lsb"] = r.u(sps["log2_poc_m4"] + 4)
-        f["st_rps_sps_flag"] = r.u(1)
-        if not f["st_rps_sps_flag"]:
-            f["rps"] = (r.ue(), r.ue())      # num_negative, num_positive (inter_ref_pic_set_prediction_flag absent for idx 0)
-    if sps["sao"]:
-        f["sao_luma"] = r.u(1); f["sao_chroma"] = r.u(1)
-    f["qp_delta"] = r.se()
-    if pps.get("dbk_override"):
-        f["dbk_override_flag"] = r.u(1)
-    f["header_bits"] = r.p
-    if pps["lf_across_slices"]:             # deblocking on (and / or SAO): slice_loop_filter_across_slices_enabled_flag
-        f["slice_lf_across_slices"] = r.u(1)
+    f["dependent"], f["address"] = 0, 0
+    if not f["first_slice"]:
+        if pps["dep_slices"]:
+            f["dependent"] = r.u(1)
+        ctb_log2 = sps["log2_min_cb_m3"] + 3 + sps["log2_diff_cb"]
+        ctbs = ((sps["width"] + (1 << ctb_log2) - 1) >> ctb_log2) * ((sps["height"] + (1 << ctb_log2) - 1) >> ctb_log2)
+        f["address_bits"] = (ctbs - 1).bit_length()                # Ceil(Log2(PicSizeInCtbsY))
+        f["address_bit_pos"] = 16 + r.p                            # of the first address bit in the unescaped NAL unit
+        f["address"] = r.u(f["address_bits"])
+    if not f["dependent"]:
+        r.u(pps["extra_bits"])                                     # slice_reserved_flag[]
+        f["slice_type"] = r.ue()
+        assert f["slice_type"] == 2
+        if pps["output_flag_present"]:
+            f["pic_output"] = r.u(1)
+        if nt not in (19, 20):
+            f["poc_lsb"] = r.u(sps["log2_poc_m4"] + 4)
+            f["st_rps_sps_flag"] = r.u(1)
+            if not f["st_rps_sps_flag"]:                           # st_ref_pic_set(num_short_term_ref_pic_sets), 7.3.7
+                inter = r.u(1) if sps["num_st_rps"] > 0 else 0
+                assert not inter
+                f["rps"] = (r.ue(), r.ue())                        # num_negative_pics, num_positive_pics
+                f["rps_pics"] = [(r.ue(), r.u(1)) for _ in range(sum(f["rps"]))]
+            elif sps["num_st_rps"] > 1:
+                f["st_rps_idx"] = r.u((sps["num_st_rps"] - 1).bit_length())
+            assert not sps["long_term"]
+            if sps["temporal_mvp"]:
+                f["temporal_mvp"] = r.u(1)
+        if sps["sao"]:
+            f["sao_luma"] = r.u(1); f["sao_chroma"] = r.u(1)
+        f["qp_delta"] = r.se()
+        assert not pps["slice_chroma_off"]
+        if pps.get("dbk_override"):
+            f["dbk_override_flag"] = r.u(1)
+        f["dbk_disabled"] = pps.get("dbk_disabled", 0)             # inferred from the PPS unless the slice overrides
+        f["beta_div2"], f["tc_div2"] = pps.get("beta_div2", 0), pps.get("tc_div2", 0)
+        if f.get("dbk_override_flag"):
+            f["dbk_disabled"] = r.u(1)
+            f["beta_div2"] = f["tc_div2"] = 0
+            if not f["dbk_disabled"]:
+                f["beta_div2"] = r.se(); f["tc_div2"] = r.se()
+        f["header_bits"] = r.p
+        # pps_loop_filter_across_slices_enabled_flag and an in-loop filter of the slice that is on (7.3.6.1)
+        if pps["lf_across_slices"] and (f.get("sao_luma") or f.get("sao_chroma") or not f["dbk_disabled"]):
+            f["slice_lf_across_slices"] = r.u(1)
     f["entry_points"] = []
     if pps.get("tiles_enabled") or pps.get("wpp"):
         n_entry = r.ue()
         if n_entry:
-            bits = r.ue() + 1
+            f["offset_len_minus1"] = r.ue()
+            bits = f["offset_len_minus1"] + 1
+            f["entry_point_bit_pos"] = 16 + r.p                    # of the first entry_point_offset_minus1 in the unescaped NAL unit
             f["entry_points"] = [r.u(bits) + 1 for _ in range(n_entry)]
+    assert not pps["sh_ext"]
     assert r.u(1) == 1                      # byte_alignment()
     while r.p % 8:
         assert r.u(1) == 0

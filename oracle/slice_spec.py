@@ -1,16 +1,26 @@
 """oracle/slice_spec.py -- TEST INFRASTRUCTURE, not product code.
 
-An independent DECODER of the slice data of an I slice, written from the text of ITU-T H.265 for the configuration the product writes: one slice
-per picture, 4:2:0, CTB 64, minimum CB 8, transform blocks 4 .. 32, no PCM / transquant bypass / scaling lists / cu_qp_delta, tiles or
-entropy_coding_sync (wavefront rows), SAO on or off, 8 and 10 bits.  Clauses restated:
+An independent DECODER of the slice data of an I slice, written from the text of ITU-T H.265 for the configuration the product writes: pictures of
+one or several slices and dependent slice segments (a NAL unit each), 4:2:0, CTB 64, minimum CB 8, transform blocks 4 .. 32, no PCM / transquant
+bypass / scaling lists / cu_qp_delta, tiles or entropy_coding_sync (wavefront rows), SAO on or off, 8 and 10 bits.  Clauses restated:
 
-  7.3.8.1-7.3.8.5, 7.3.8.8, 7.3.8.10, 7.3.8.11   slice_segment_data, coding_tree_unit, sao, coding_quadtree, coding_unit, transform_tree,
+  7.3.6.1 (in oracle/hevc_parse.py), 7.4.7.1     slice_segment_header: first_slice_segment_in_pic_flag, dependent_slice_segment_flag, slice_segment_address,
+                                                 the dependent header, the deblocking override fields, the entry points; SliceAddrRs
+  7.3.8.1-7.3.8.5, 7.3.8.8, 7.3.8.10, 7.3.8.11   slice_segment_data (per segment), coding_tree_unit, sao, coding_quadtree, coding_unit, transform_tree,
                                                  transform_unit, residual_coding, with the semantics of 7.4.9 (inferred values, scanIdx, hidden signs)
-  9.3.1-9.3.4                                    initialisation, storage and synchronisation of the context variables, the binarisations, the ctxInc
+  9.3.1-9.3.4                                    initialisation, storage and synchronisation of the context variables (tile start, wavefront row start,
+                                                 start of a dependent segment, start of a slice: in that order), the binarisations, the ctxInc
                                                  derivations, the arithmetic decoding engine (decision, bypass, terminate)
   6.5.1-6.5.5                                    CTB raster <-> tile scan, TileId, MinTbAddrZs, the up-right diagonal, horizontal and vertical scans
-  6.4.1                                          z-scan order availability (picture, tile, decoding order)
+  6.4.1                                          z-scan order availability (picture, decoding order, tile, slice)
   8.4.2, 8.4.3                                   the candidate list of the luma prediction mode, rem_intra_luma_pred_mode, the chroma mode
+
+SLICES AND SEGMENTS.  decode_access_unit takes every slice NAL unit of the access unit in order and cuts each one's sub-streams at its own entry points
+against its own payload.  SliceAddrRs (the address of the independent segment a CTB's slice began with) is the slice term of availability and of the SAO
+merge candidates.  A picture of row slices (SliceMode 1) has NO tiles in its PPS and is decoded with one tile and slice availability alone -- the product
+computes the same thing as a tile grid of one column (csrc/slice_grid.h); the two stay two derivations, the coder's grid is never passed in.  Not
+covered: slices or segments that start inside a CTU row or inside a tile (the product refuses those layouts, so the restore of 9.3.2.2's TableStateIdxDs
+is implemented and its tally entry stays 0), P and B slices, wavefront together with tiles, SAO for luma or chroma alone.
 
 It is deliberately NOT a restatement of csrc/entropy_coder.h or of the host writer: coding_quadtree and transform_tree are the recursive functions of
 the standard (the product walks both trees iteratively), every scan, the last-position prefix / suffix split and the z-order are GENERATED from the
@@ -21,11 +31,13 @@ CONSTANT TABLES.  The tables of the arithmetic coder that cannot be derived are 
 (9.3.4.2.5) are typed in below from the standard and a CPU test asserts that they equal the product's; transIdxMps is the standard's rule (state + 1,
 62 stays 62).  rangeTabLps (Table 9-40) and the initValue of every context of an I slice (Tables 9-5 .. 9-37, initType 0) are READ OUT OF
 csrc/entropy_tables.h at import by a small parser (LPS_TABLE; CTX_INIT cut per syntax element at the enum offsets found there).  The contents of
-those two tables are therefore pinned by the 56 reference-encoder streams this decoder reproduces the records of (tests/golden/rd_*.npz), NOT by the
+those two tables are therefore pinned by the reference-encoder streams this decoder reproduces the records of (tests/golden/rd_*.npz, slices_*.npz,
+segments_*.npz), NOT by the
 round trip: an arithmetic coder round-trips with any table that the coder and the decoder share.
 
-END CONDITIONS are demanded, not reported: end_of_slice_segment_flag is 1 behind the picture's last CTU and nowhere else, end_of_subset_one_bit (1)
-stands behind the last CTU of every tile / CTU row, byte_alignment() follows (a 1 and zeros up to the byte boundary) and then the sub-stream has no
+END CONDITIONS are demanded, not reported: end_of_slice_segment_flag is 1 behind the last CTU of every slice segment and nowhere else (the last CTU is
+the one before the next segment's slice_segment_address; the last segment ends the picture), end_of_subset_one_bit (1) stands behind the last CTU of
+every tile / CTU row that does not end its segment, byte_alignment() follows (a 1 and zeros up to the byte boundary) and then the sub-stream has no
 byte left.  A violation, a read past the end of a sub-stream, a level outside 16 bits or an ivlOffset of 510 / 511 raises SliceError.
 
 Besides records and SAO parameters the decoder returns a TALLY of the branches taken (as oracle/filter_spec.py does), so that a corpus can be held to
@@ -179,6 +191,8 @@ class Geometry:
             self.rs2ts[rs] = v
             self.ts2rs[v] = rs
             self.tile_id_rs[rs] = ty * (len(self.col_bd) - 1) + tx
+        self.slice_addr_rs = [0] * n                                      # SliceAddrRs of every CTB decoded so far (7.4.7.1); one slice: 0 everywhere
+        self.slice_term = True                                            # False: a test's mutant of 6.4.1 that forgets the slice
         d = ctb_log2 - min_tb_log2
         self.w4, self.h4 = self.wc << d, self.hc << d
         self.zs = [[0] * self.w4 for _ in range(self.h4)]                 # MinTbAddrZs[y][x] (6-10)
@@ -191,7 +205,9 @@ class Geometry:
                 self.zs[y][x] = v
 
     def available(self, xc, yc, xn, yn):
-        """6.4.1 with one slice: 0 unavailable, 1 available; the reason of a refusal is in self.why ('picture', 'order', 'tile')."""
+        """6.4.1: 0 unavailable, 1 available; the reason of a refusal is in self.why ('picture', 'order', 'tile', 'slice'; a neighbour in another tile AND another
+        slice says 'tile'), and self.other_slice says whether the neighbour's SliceAddrRs differs."""
+        self.other_slice = False
         if xn < 0 or yn < 0 or xn >= self.w or yn >= self.h:
             self.why = "picture"
             return False
@@ -200,8 +216,13 @@ class Geometry:
             self.why = "order"
             return False
         c = self.ctb_log2
-        if self.tile_id_rs[(yn >> c) * self.wc + (xn >> c)] != self.tile_id_rs[(yc >> c) * self.wc + (xc >> c)]:
+        rn, rc = (yn >> c) * self.wc + (xn >> c), (yc >> c) * self.wc + (xc >> c)
+        self.other_slice = self.slice_addr_rs[rn] != self.slice_addr_rs[rc]
+        if self.tile_id_rs[rn] != self.tile_id_rs[rc]:
             self.why = "tile"
+            return False
+        if self.other_slice and self.slice_term:
+            self.why = "slice"
             return False
         return True
 
@@ -312,7 +333,12 @@ def new_tally():
          "chroma_mode": [0] * 5, "chroma_34": 0, "split_ctx_tile_edge": 0, "tskip_present": [0, 0], "tskip_set": [0, 0],
          "sao_merge_left": 0, "sao_merge_up": 0, "sao_merge_left_tile_edge": 0, "sao_merge_up_tile_edge": 0, "sao_band": 0, "sao_edge": 0,
          "sao_band_wrap": 0, "sao_band_position_max": -1, "sao_offset_abs_max": 0, "ctx_sync_from_above": 0, "ctx_init_at_row_start": 0,
-         "chroma_4x4_behind_fourth": 0, "substreams": 0, "level_out_of_range": 0}
+         "chroma_4x4_behind_fourth": 0, "substreams": 0, "level_out_of_range": 0,
+         # pictures of several slices / slice segments
+         "slices": 0, "segments_dependent": 0, "segment_ends_mid_slice": 0, "split_ctx_slice_edge": 0, "sao_merge_up_slice_edge": 0, "sao_merge_left_slice_edge": 0,
+         "cand_above_other_slice": 0, "cand_left_other_slice": 0, "ctx_restore_from_previous_segment": 0, "ctx_init_at_segment_start": 0,
+         # counted by decode_access_unit (the picture entries leave them 0)
+         "entry_points_in_dependent_header": 0, "emulation_bytes_in_multi_nal_picture": 0, "emulation_bytes_under_dependent_entry_points": 0}
     return t
 
 
@@ -335,10 +361,12 @@ def add_tally(a, b):
 class _Picture:
     """One picture being decoded: sequence / picture parameters, the arrays the semantics keep (CtDepth, IntraPredModeY), the output."""
 
-    def __init__(self, width, height, qp, tools, bit_depth, col_bd, row_bd, wavefront, sao, strict_levels=True, min_cb_log2=3, ctb_log2=6, min_tb_log2=2, max_tb_log2=5, max_th_depth_intra=2):
+    def __init__(self, width, height, qp, tools, bit_depth, col_bd, row_bd, wavefront, sao, strict_levels=True, min_cb_log2=3, ctb_log2=6, min_tb_log2=2, max_tb_log2=5, max_th_depth_intra=2,
+                 slice_term=True, sao_slice_rule=True, mid_slice_end=True):
         if ctb_log2 != 6 or min_tb_log2 != 2:
             raise SliceError("the record layout is that of 64x64 CTBs and 4x4 minimum transform blocks")
         self.g = Geometry(width, height, col_bd, row_bd, ctb_log2, min_tb_log2)
+        self.g.slice_term, self.sao_slice_rule, self.mid_slice_end = bool(slice_term), bool(sao_slice_rule), bool(mid_slice_end)      # False: a test's mutants
         self.w, self.h, self.qp, self.bit_depth = width, height, qp, bit_depth
         self.tskip_enabled, self.sign_hiding = bool(tools & TOOL_TSKIP), bool(tools & TOOL_SIGN_HIDE)
         self.wavefront, self.sao_on, self.strict_levels = bool(wavefront), bool(sao), bool(strict_levels)
@@ -367,16 +395,21 @@ class _Picture:
     def sao_syntax(self, rx, ry, rs):
         g, t, p = self.g, self.tally, self.sao[rs]
         merge_left = merge_up = 0
-        if rx > 0:
-            if g.tile_id_rs[rs] == g.tile_id_rs[rs - 1]:                  # one slice: the left CTB is in the slice
-                merge_left = self.bin("sao_merge")
-            else:
+        sl = g.slice_addr_rs
+        if rx > 0:                                                        # 7.3.8.3: leftCtbInSliceSeg (SliceAddrRs) and leftCtbInTile
+            other = sl[rs] != sl[rs - 1]
+            t["sao_merge_left_slice_edge"] += other
+            if g.tile_id_rs[rs] != g.tile_id_rs[rs - 1]:
                 t["sao_merge_left_tile_edge"] += 1
+            elif not (other and self.sao_slice_rule):
+                merge_left = self.bin("sao_merge")
         if ry > 0 and not merge_left:
-            if g.tile_id_rs[rs] == g.tile_id_rs[rs - g.wc]:
-                merge_up = self.bin("sao_merge")
-            else:
+            other = sl[rs] != sl[rs - g.wc]
+            t["sao_merge_up_slice_edge"] += other
+            if g.tile_id_rs[rs] != g.tile_id_rs[rs - g.wc]:
                 t["sao_merge_up_tile_edge"] += 1
+            elif not (other and self.sao_slice_rule):
+                merge_up = self.bin("sao_merge")
         if merge_left or merge_up:
             t["sao_merge_left" if merge_left else "sao_merge_up"] += 1
             p[0]["mode"], p[0]["type"] = 2, 0 if merge_left else 1
@@ -423,8 +456,11 @@ class _Picture:
             for xn, yn in ((x0 - 1, y0), (x0, y0 - 1)):                   # 9.3.4.2.2
                 if self.g.available(x0, y0, xn, yn):
                     inc += self.ct_depth[yn >> 2][xn >> 2] > depth
-                elif self.g.why == "tile":
-                    self.tally["split_ctx_tile_edge"] += 1
+                else:
+                    if self.g.why == "tile":
+                        self.tally["split_ctx_tile_edge"] += 1
+                    if self.g.other_slice:
+                        self.tally["split_ctx_slice_edge"] += 1
             split = self.bin("split_cu", inc)
         else:
             split = 1 if log2 > self.min_cb_log2 else 0
@@ -466,7 +502,10 @@ class _Picture:
             for which, (xn, yn) in enumerate(((xp - 1, yp), (xp, yp - 1))):
                 if not self.g.available(xp, yp, xn, yn):
                     cand_nb.append(1)
-                    t[("cand_tile_edge_above" if which else "cand_tile_edge_left") if self.g.why == "tile" else "cand_picture_edge"] += 1
+                    if self.g.why != "slice":
+                        t[("cand_tile_edge_above" if which else "cand_tile_edge_left") if self.g.why == "tile" else "cand_picture_edge"] += 1
+                    if self.g.other_slice:
+                        t["cand_above_other_slice" if which else "cand_left_other_slice"] += 1
                 elif which == 1 and yp - 1 < ((yp >> self.ctb_log2) << self.ctb_log2):
                     cand_nb.append(1)
                     t["cand_above_other_ctu_row"] += 1
@@ -735,50 +774,103 @@ class _Picture:
                 plane[base + ((ys << 2) + py) * size + (xs << 2) + px] = value
 
     # -- 7.3.8.1, 7.3.8.2, 9.3.1, 9.3.2
-    def slice_segment_data(self, substreams):
+    def slice_segment_data(self, segments):
+        """segments: [(slice_segment_address, dependent_slice_segment_flag, [sub-streams])] in the order of their NAL units.  A segment runs from its address, in tile
+        scan, up to the CTB whose end_of_slice_segment_flag is 1; the next segment's address must be the CTB behind that one, and the last one must end the picture."""
         g, t = self.g, self.tally
         n_ctb = g.wc * g.hc
-        stored = None
-        k = -1
-        for ts in range(n_ctb):
-            rs = g.ts2rs[ts]
-            rx, ry = rs % g.wc, rs // g.wc
-            x0, y0 = rx << 6, ry << 6
-            new_tile = ts == 0 or g.tile_id_rs[rs] != g.tile_id_rs[g.ts2rs[ts - 1]]
-            new_row = self.wavefront and rs % g.wc == 0
-            if new_tile or new_row:
-                k += 1
-                if k >= len(substreams):
-                    raise SliceError("%d sub-streams, more are needed" % len(substreams))
-                self.e = Engine(substreams[k])
-                t["substreams"] += 1
+        stored_wpp = stored_ds = None
+        ts = 0
+        slice_addr = None
+        for si, (address, dependent, substreams) in enumerate(segments):
+            if not 0 <= address < n_ctb:
+                raise SliceError("slice_segment_address %d in a picture of %d CTBs" % (address, n_ctb))
+            if ts >= n_ctb:
+                raise SliceError("a slice segment behind the picture's last CTB")
+            if address != g.ts2rs[ts]:
+                raise SliceError("slice_segment_address %d, the CTB behind the segment before it is %d" % (address, g.ts2rs[ts]))
+            if dependent:
+                if slice_addr is None:
+                    raise SliceError("a dependent slice segment opens the picture")
+                t["segments_dependent"] += 1
+            else:
+                slice_addr = address                                      # SliceAddrRs (7.4.7.1)
+                t["slices"] += 1
+            if not substreams:
+                raise SliceError("a slice segment without data")
+            # the segment's last CTB, as its neighbours say: the CTB before the next segment's address, or the picture's last
+            if si + 1 < len(segments):
+                nxt_addr = segments[si + 1][0]
+                if not 0 <= nxt_addr < n_ctb:
+                    raise SliceError("slice_segment_address %d in a picture of %d CTBs" % (nxt_addr, n_ctb))
+                last_ts = g.rs2ts[nxt_addr] - 1
+                ends_mid_slice = bool(segments[si + 1][1])
+            else:
+                last_ts, ends_mid_slice = n_ctb - 1, False
+            if last_ts < ts:
+                raise SliceError("slice_segment_address %d does not lie behind segment %d" % (segments[si + 1][0], si))
+            k = 0
+            first_ts = ts
+            while True:
+                rs = g.ts2rs[ts]
+                rx, ry = rs % g.wc, rs // g.wc
+                x0, y0 = rx << 6, ry << 6
+                g.slice_addr_rs[rs] = slice_addr
+                new_tile = ts == 0 or g.tile_id_rs[rs] != g.tile_id_rs[g.ts2rs[ts - 1]]
+                new_row = self.wavefront and rs % g.wc == 0
+                if ts == first_ts or new_tile or new_row:                 # 9.3.1: the arithmetic decoder starts at the segment's data and behind every byte_alignment()
+                    if ts != first_ts:
+                        k += 1
+                    if k >= len(substreams):
+                        raise SliceError("segment %d: %d sub-streams, more are needed" % (si, len(substreams)))
+                    self.e = Engine(substreams[k])
+                    t["substreams"] += 1
+                # 9.3.1, the context variables at the start of a CTU, in the order of the text
                 if new_tile:
                     self.st, self.mps = init_contexts(self.qp)
-                else:                                                     # 9.3.1: the spatial neighbour T (x0 + CtbSizeY, y0 - CtbSizeY) decides
+                elif new_row:                                             # the spatial neighbour T (x0 + CtbSizeY, y0 - CtbSizeY) decides
                     if g.available(x0, y0, x0 + 64, y0 - 64):
-                        self.st, self.mps = list(stored[0]), list(stored[1])
+                        self.st, self.mps = list(stored_wpp[0]), list(stored_wpp[1])
                         t["ctx_sync_from_above"] += 1
                     else:
                         self.st, self.mps = init_contexts(self.qp)
                         t["ctx_init_at_row_start"] += 1
-            if self.sao_on:
-                self.sao_syntax(rx, ry, rs)
-            self.coding_quadtree(x0, y0, 6, 0)
-            end = self.e.terminate()                                      # end_of_slice_segment_flag
-            if end != (1 if ts == n_ctb - 1 else 0):
-                raise SliceError("end_of_slice_segment_flag %d behind CTU %d of %d" % (end, ts + 1, n_ctb))
-            if self.wavefront and rs % g.wc == 1:                        # 9.3.2.2 storage: behind the second CTB of a row (one tile with wavefront here)
-                stored = (list(self.st), list(self.mps))
-            if end:
-                self.e.finish()                                           # rbsp_slice_segment_trailing_bits()
-            else:
-                nxt = g.ts2rs[ts + 1]
+                elif ts == first_ts and dependent:                        # TableStateIdxDs, stored at the end of the segment before (9.3.2.2)
+                    self.st, self.mps = list(stored_ds[0]), list(stored_ds[1])
+                    t["ctx_restore_from_previous_segment"] += 1
+                elif ts == first_ts:
+                    self.st, self.mps = init_contexts(self.qp)
+                    t["ctx_init_at_segment_start"] += 1
+                if self.sao_on:
+                    self.sao_syntax(rx, ry, rs)
+                self.coding_quadtree(x0, y0, 6, 0)
+                end = self.e.terminate()                                  # end_of_slice_segment_flag
+                want_end = ts == last_ts
+                if want_end and ends_mid_slice and not self.mid_slice_end:
+                    want_end = False                                      # a test's mutant: a border between two segments of a slice is taken for no border
+                if end != (1 if want_end else 0):
+                    raise SliceError("end_of_slice_segment_flag %d behind CTU %d of %d (segment %d ends behind CTU %d)" % (end, ts + 1, n_ctb, si, last_ts + 1))
+                if self.wavefront and rs % g.wc == 1:                     # 9.3.2.2 storage: behind the second CTB of a row (one tile with wavefront here)
+                    stored_wpp = (list(self.st), list(self.mps))
+                ts += 1
+                if end:
+                    stored_ds = (list(self.st), list(self.mps))           # 9.3.2.2: at the end of the slice segment data (dependent_slice_segments_enabled_flag)
+                    self.e.finish()                                       # rbsp_slice_segment_trailing_bits()
+                    t["segment_ends_mid_slice"] += ends_mid_slice
+                    break
+                if ts >= n_ctb:
+                    raise SliceError("no end_of_slice_segment_flag behind the picture's last CTU")
+                nxt = g.ts2rs[ts]
                 if g.tile_id_rs[nxt] != g.tile_id_rs[rs] or (self.wavefront and nxt % g.wc == 0):
                     if self.e.terminate() != 1:                           # end_of_subset_one_bit
                         raise SliceError("end_of_subset_one_bit is 0")
                     self.e.finish()                                       # byte_alignment()
-        if k + 1 != len(substreams):
-            raise SliceError("%d sub-streams, %d were used" % (len(substreams), k + 1))
+                if ts - 1 == last_ts:                                     # (the mutant only) go on in the next segment's data
+                    break
+            if k + 1 != len(substreams):
+                raise SliceError("segment %d: %d sub-streams, %d were used" % (si, len(substreams), k + 1))
+        if ts != n_ctb:
+            raise SliceError("the last slice segment ends behind CTU %d of %d" % (ts, n_ctb))
 
     def records(self):
         n = self.g.wc * self.g.hc
@@ -791,17 +883,28 @@ class _Picture:
 
 
 def decode_picture(substreams, width, height, qp, tools, bit_depth=8, col_bd=None, row_bd=None, wavefront=False, sao=False, strict_levels=True, **sps):
-    """The slice data of one picture from its sub-streams (one per tile in raster order of the tile grid, or one per CTU row with wavefront, otherwise one).
-    col_bd / row_bd: tile boundaries in CTUs including 0 and the picture's size (None: one tile).  tools: HEVCDL_TOOL_* bits (transform skip, sign hiding).
-    -> (records [ctus] in REC_DTYPE layout, SAO parameters [ctus, 3] in SAO_DTYPE layout or None, mask [ctus, 3, 256] of the tskip entries whose flag was in
+    """The slice data of one picture of ONE slice segment from its sub-streams (one per tile in raster order of the tile grid, or one per CTU row with wavefront,
+    otherwise one).  col_bd / row_bd: tile boundaries in CTUs including 0 and the picture's size (None: one tile).  tools: HEVCDL_TOOL_* bits (transform skip, sign
+    hiding).  -> (records [ctus] in REC_DTYPE layout, SAO parameters [ctus, 3] in SAO_DTYPE layout or None, mask [ctus, 3, 256] of the tskip entries whose flag was in
     the stream, tally).  strict_levels False: a level outside 16 bits (a stream no conforming encoder writes) is counted in the tally and kept modulo 2^16."""
+    return decode_picture_segments([(0, 0, substreams)], width, height, qp, tools, bit_depth, col_bd, row_bd, wavefront, sao, strict_levels, **sps)
+
+
+def decode_picture_segments(segments, width, height, qp, tools, bit_depth=8, col_bd=None, row_bd=None, wavefront=False, sao=False, strict_levels=True,
+                            slice_term=True, sao_slice_rule=True, mid_slice_end=True, **sps):
+    """The slice data of one picture of several slices and slice segments.  segments: [(slice_segment_address, dependent_slice_segment_flag, [sub-streams])] in
+    decoding order -- what the headers of the picture's slice NAL units say and what their entry points cut, or the same said about a coder's buffer.  col_bd /
+    row_bd are the PPS's tiles: a picture cut into slices of CTU rows has one tile.  QP, SAO and the tool bits are the picture's (every independent header repeats them).
+    slice_term / sao_slice_rule / mid_slice_end False: TEST-ONLY mutants (the slice term of 6.4.1 forgotten; SAO merge candidates taken across a slice border; a
+    border between two segments of one slice taken for none) that a corpus must catch.  -> what decode_picture returns."""
     wc, hc = (width + 63) >> 6, (height + 63) >> 6
-    pic = _Picture(width, height, qp, tools, bit_depth, col_bd or [0, wc], row_bd or [0, hc], wavefront, sao, strict_levels, **sps)
+    pic = _Picture(width, height, qp, tools, bit_depth, col_bd or [0, wc], row_bd or [0, hc], wavefront, sao, strict_levels,
+                   slice_term=slice_term, sao_slice_rule=sao_slice_rule, mid_slice_end=mid_slice_end, **sps)
     if wavefront and (len(pic.g.col_bd) > 2 or len(pic.g.row_bd) > 2):
         raise SliceError("wavefront together with tiles is outside this decoder")
     try:
-        pic.slice_segment_data([bytes(s) for s in substreams])
-    except (IndexError, KeyError) as e:                                   # a damaged stream may lead outside the picture's arrays: the same refusal
+        pic.slice_segment_data([(int(a), int(d), [bytes(b) for b in subs]) for a, d, subs in segments])
+    except (IndexError, KeyError, TypeError) as e:                        # a damaged stream may lead outside the picture's arrays: the same refusal
         raise SliceError("syntax leads outside the picture: %r" % (e,))
     return pic.records(), (pic.sao if sao else None), pic.mask, pic.tally
 
@@ -820,22 +923,46 @@ def unescape_with_positions(nal):
     return bytes(out), pos
 
 
-def decode_access_unit(au, strict_levels=True, picture_decoder=None):
-    """One access unit (Annex B: VPS, SPS, PPS, one slice NAL) -> what decode_picture returns, plus a dict of what the headers said.  The sub-streams are cut
-    at the slice header's entry points, which count the bytes of the slice segment data WITH its emulation prevention bytes (7.4.7.1): sub-stream k is the
-    bytes [sum of the offsets before k, + offset k) of the NAL's payload behind the header, the last one takes the rest, and no offset may reach past it.
-    picture_decoder: a stand-in for decode_picture with its signature (a test's cache around it)."""
+def cut_substreams(nal, hdr):
+    """One slice NAL unit and its parsed header -> (sub-streams without their emulation prevention bytes, payload bytes, emulation prevention bytes per sub-stream).
+    The entry points count the bytes of the slice segment data WITH its emulation prevention bytes (7.4.7.1): sub-stream k is the bytes [sum of the offsets before
+    k, + offset k) of the NAL's payload behind the header, the last one takes the rest, and no offset may reach past it."""
+    rbsp, pos = unescape_with_positions(nal)
+    if hdr["data_byte_pos"] >= len(pos):
+        raise SliceError("a slice NAL unit without slice segment data")
+    first = pos[hdr["data_byte_pos"]]                                     # the first byte of slice_segment_data() in the NAL
+    payload = len(nal) - first
+    offs = hdr["entry_points"]
+    if sum(offs) >= payload:
+        raise SliceError("entry points add up to %d bytes, the slice data has %d" % (sum(offs), payload))
+    cuts = [first]
+    for o in offs:
+        cuts.append(cuts[-1] + o)
+    cuts.append(len(nal))
+    at = [bisect.bisect_left(pos, c) for c in cuts]                       # an emulation prevention byte belongs to the sub-stream it lies in and is dropped there
+    subs = [rbsp[at[k]:at[k + 1]] for k in range(len(cuts) - 1)]
+    emu = [(cuts[k + 1] - cuts[k]) - len(subs[k]) for k in range(len(subs))]
+    return subs, payload, emu
+
+
+def decode_access_unit(au, strict_levels=True, picture_decoder=None, segments_decoder=None, **mutants):
+    """One access unit (Annex B: VPS, SPS, PPS, the picture's slice NAL units in order) -> what decode_picture returns, plus a dict of what the headers said.  Every
+    NAL unit's sub-streams are cut at its own header's entry points against its own payload (cut_substreams).  Demanded of the headers, by SliceError: the first has
+    first_slice_segment_in_pic_flag 1 and the others 0; every independent header of the picture carries the same QP, SAO flags and deblocking fields; and, by
+    slice_segment_data, that every slice_segment_address is the CTB behind the last CTB of the segment before it and the last segment ends the picture.
+    picture_decoder: a stand-in for decode_picture with its signature, used for a picture of one segment; segments_decoder: one for decode_picture_segments (a test's
+    cache around each).  mutants: decode_picture_segments' test-only switches."""
     import hevc_parse as hp
-    nals = hp.split_annexb(au)
-    by_type = {}
-    for _, n in nals:
-        by_type.setdefault((n[0] >> 1) & 63, []).append(n)
-    sps, pps = hp.parse_sps(by_type[33][0]), hp.parse_pps(by_type[34][0])
-    slices = [n for ty, v in by_type.items() if ty < 32 for n in v]
-    if len(slices) != 1:
-        raise SliceError("%d slice NAL units in the access unit" % len(slices))
-    nal = slices[0]
-    hdr, _ = hp.parse_slice_header(nal, sps, pps)
+    nals = [n for _, n in hp.split_annexb(au)]
+    ps = {}
+    for n in nals:
+        ps.setdefault((n[0] >> 1) & 63, n)
+    if 33 not in ps or 34 not in ps:
+        raise SliceError("no SPS / PPS in the access unit")
+    sps, pps = hp.parse_sps(ps[33]), hp.parse_pps(ps[34])
+    slices = [n for n in nals if ((n[0] >> 1) & 63) < 32]
+    if not slices:
+        raise SliceError("no slice NAL unit in the access unit")
     if pps["cu_qp_delta"] or pps["tq_bypass"] or sps["pcm"] or sps["scaling_list"] or pps["scaling_list"] or sps["chroma_format"] != 1:
         raise SliceError("a syntax switch outside this decoder is on")
     w, h = sps["width"], sps["height"]
@@ -848,26 +975,43 @@ def decode_access_unit(au, strict_levels=True, picture_decoder=None):
         else:
             col_bd = [sum(pps["column_widths"][:i]) for i in range(pps["tile_columns"])] + [wc]
             row_bd = [sum(pps["row_heights"][:i]) for i in range(pps["tile_rows"])] + [hc]
-    rbsp, pos = unescape_with_positions(nal)
-    first = pos[hdr["data_byte_pos"]]                                     # the first byte of slice_segment_data() in the NAL
-    payload = len(nal) - first
-    offs = hdr["entry_points"]
-    if sum(offs) >= payload:
-        raise SliceError("entry points add up to %d bytes, the slice data has %d" % (sum(offs), payload))
-    cuts = [first]
-    for o in offs:
-        cuts.append(cuts[-1] + o)
-    cuts.append(len(nal))
-    at = [bisect.bisect_left(pos, c) for c in cuts]                       # an emulation prevention byte belongs to the sub-stream it lies in and is dropped there
-    subs = [rbsp[at[k]:at[k + 1]] for k in range(len(cuts) - 1)]
-    qp = 26 + pps["init_qp_m26"] + hdr["qp_delta"]
+    segs, segments, first_hdr = [], [], None
+    for i, nal in enumerate(slices):
+        try:
+            hdr, _ = hp.parse_slice_header(nal, sps, pps)
+        except (AssertionError, IndexError) as e:
+            raise SliceError("slice segment header %d: %r" % (i, e))
+        if hdr["first_slice"] != (1 if i == 0 else 0):
+            raise SliceError("first_slice_segment_in_pic_flag %d in slice NAL unit %d of the access unit" % (hdr["first_slice"], i))
+        if not hdr["dependent"]:
+            if sps["sao"] and hdr["sao_luma"] != hdr["sao_chroma"]:
+                raise SliceError("SAO for one of luma / chroma only is outside this decoder")
+            same = ("qp_delta", "sao_luma", "sao_chroma", "dbk_override_flag", "dbk_disabled", "beta_div2", "tc_div2", "slice_lf_across_slices")
+            if first_hdr is None:
+                first_hdr = hdr
+            elif any(hdr.get(k) != first_hdr.get(k) for k in same):
+                raise SliceError("the independent slice segment headers of the picture differ in %s" % [k for k in same if hdr.get(k) != first_hdr.get(k)])
+        subs, payload, emu = cut_substreams(nal, hdr)
+        segs.append({"first_slice": hdr["first_slice"], "dependent": hdr["dependent"], "address": hdr["address"], "entry_points": list(hdr["entry_points"]),
+                     "offset_len_minus1": hdr.get("offset_len_minus1"), "substreams": subs, "payload_bytes": payload, "nal_bytes": len(nal), "emulation": emu, "header": hdr})
+        segments.append((hdr["address"], hdr["dependent"], subs))
+    qp = 26 + pps["init_qp_m26"] + first_hdr["qp_delta"]
     tools = (TOOL_TSKIP if pps["tskip"] else 0) | (TOOL_SIGN_HIDE if pps["sign_hiding"] else 0)
     bd = 8 + sps["bd_luma_m8"]
-    sao = bool(sps["sao"] and (hdr.get("sao_luma") or hdr.get("sao_chroma")))
-    if sao and not (hdr["sao_luma"] and hdr["sao_chroma"]):
-        raise SliceError("SAO for one of luma / chroma only is outside this decoder")
-    out = (picture_decoder or decode_picture)(subs, w, h, qp, tools, bd, col_bd, row_bd, bool(pps["wpp"]), sao, strict_levels=strict_levels, min_cb_log2=sps["log2_min_cb_m3"] + 3, ctb_log2=ctb_log2,
-                         min_tb_log2=sps["log2_min_tb_m2"] + 2, max_tb_log2=sps["log2_min_tb_m2"] + 2 + sps["log2_diff_tb"], max_th_depth_intra=sps["tu_depth_intra"])
+    sao = bool(sps["sao"] and first_hdr.get("sao_luma"))
+    kw = dict(strict_levels=strict_levels, min_cb_log2=sps["log2_min_cb_m3"] + 3, ctb_log2=ctb_log2, min_tb_log2=sps["log2_min_tb_m2"] + 2,
+              max_tb_log2=sps["log2_min_tb_m2"] + 2 + sps["log2_diff_tb"], max_th_depth_intra=sps["tu_depth_intra"])
+    if len(segments) == 1 and not mutants:
+        out = (picture_decoder or decode_picture)(segments[0][2], w, h, qp, tools, bd, col_bd, row_bd, bool(pps["wpp"]), sao, **kw)
+    else:
+        kw.update(mutants)
+        out = (segments_decoder or decode_picture_segments)(segments, w, h, qp, tools, bd, col_bd, row_bd, bool(pps["wpp"]), sao, **kw)
+    tally = dict(out[3])                                                  # (a cached result stays as it is)
+    tally["entry_points_in_dependent_header"] = sum(len(g["entry_points"]) for g in segs if g["dependent"])
+    tally["emulation_bytes_in_multi_nal_picture"] = sum(sum(g["emulation"]) for g in segs) if len(segs) > 1 else 0
+    tally["emulation_bytes_under_dependent_entry_points"] = sum(sum(g["emulation"][:len(g["entry_points"])]) for g in segs if g["dependent"])
     info = {"width": w, "height": h, "qp": qp, "tools": tools, "bit_depth": bd, "col_bd": col_bd, "row_bd": row_bd, "wavefront": bool(pps["wpp"]), "sao": sao,
-            "entry_points": list(offs), "substreams": subs, "payload_bytes": payload}
-    return out + (info,)
+            "entry_points": list(segs[0]["entry_points"]), "substreams": [b for g in segs for b in g["substreams"]], "payload_bytes": segs[0]["payload_bytes"],
+            "segments": segs, "dep_slices": bool(pps["dep_slices"]), "lf_across_slices": bool(pps["lf_across_slices"]),
+            "dbk": (first_hdr.get("dbk_override_flag", 0), first_hdr["dbk_disabled"], first_hdr["beta_div2"], first_hdr["tc_div2"])}
+    return out[:3] + (tally, info)

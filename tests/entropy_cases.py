@@ -1,5 +1,6 @@
 """Inputs of the entropy-coder tests (tests/test_entropy.py on the CPU, tests/test_entropy_gpu.py on the device): the golden fixtures as coder inputs, a seeded corpus of
-synthetic records that no encode produces, garbage records, and the helpers that turn coded slice data into access units."""
+synthetic records that no encode produces, garbage records, the helpers that turn coded slice data into access units, and (last section) the layout corpus: the
+same kinds of pictures under every slice and segment layout the writer accepts (tests/test_entropy_slices_roundtrip.py, tests/test_entropy_slices_gpu.py)."""
 import ctypes
 import functools
 import glob
@@ -466,3 +467,245 @@ def assert_round_trip(name, cfg, recs, sao, decoded, counts=None):
     assert (gsao is None) == (wsao is None)
     if wsao is not None:
         assert np.array_equal(gsao, wsao), "%s: SAO parameters differ at CTU %s" % (name, [a for a in range(len(wsao)) if not np.array_equal(gsao[a], wsao[a])][:4])
+
+
+# ---- pictures of several slices and slice segments ----------------------------------------------------------------------------------------------------------------
+def _lay(tiles=(1, 1), wavefront=False, slices=None, lf_across_slices=True, segments=None, choice=None, lf_offsets=(0, 0)):
+    """A layout: what hevcdl_write_access_unit_segments is told besides the picture.  slices (SliceMode, SliceArgument), segments (SliceSegmentMode, SliceSegmentArgument),
+    choice: a hevcdl_dbk_choice 5-tuple (LoopFilterOffsetInPPS 0: every independent header repeats the deblocking fields behind an override flag)."""
+    return {"tiles": tiles, "wavefront": wavefront, "slices": slices, "lf_across_slices": lf_across_slices, "segments": segments, "choice": choice, "lf_offsets": lf_offsets}
+
+
+def layout_keys(lay):
+    """-> (layout=, segments=) of code_slice_data / write_access_unit_from_slice_data."""
+    import hevcdl_amd
+    return hevcdl_amd.slice_layout(lay["slices"], lay["lf_across_slices"]), lay["segments"]
+
+
+def segment_borders(cfg, lay):
+    """What the layout says about the picture's NAL units, from the keys' definitions (not from the coder's grid): -> ([(slice_segment_address, dependent flag, first
+    sub-stream, sub-streams)] in decoding order, (col_bd, row_bd) of the tiles the PPS declares, wavefront).  A sub-stream is a tile, a wavefront row or -- SliceMode 1,
+    whose PPS has no tiles -- a whole slice of CTU rows."""
+    import hevcdl_amd
+    cx, cy = (cfg.width + 63) // 64, (cfg.height + 63) // 64
+    _, _, _, cb, rb = hevcdl_amd.tile_layout(lay["tiles"], cfg.width, cfg.height)
+    slices, segs = lay["slices"], lay["segments"]
+    if slices and slices[0] == 1:
+        rows = slices[1] // cx
+        return [(r * cx, 0, i, 1) for i, r in enumerate(range(0, cy, rows))], ([0, cx], [0, cy]), False
+    if lay["wavefront"]:
+        addr = [r * cx for r in range(cy)]
+    else:
+        addr = [rb[ty] * cx + cb[tx] for ty in range(len(rb) - 1) for tx in range(len(cb) - 1)]
+    per = slices[1] if slices else len(addr)
+    seg = (segs[1] // cx if segs[0] == 1 else segs[1]) if segs else per
+    out = []
+    for k0 in range(0, len(addr), per):
+        k1 = min(k0 + per, len(addr))
+        for s0 in range(k0, k1, seg):
+            out.append((addr[s0], int(s0 > k0), s0, min(s0 + seg, k1) - s0))
+    return out, (cb, rb), bool(lay["wavefront"])
+
+
+def code_layout(cfg, recs, sao, lay, **kw):
+    import hevcdl_amd
+    layout, segments = layout_keys(lay)
+    return hevcdl_amd.code_slice_data(cfg, recs, sao, layout=layout, segments=segments, **kw)
+
+
+_DECODED_SEGMENTS = {}
+
+
+def cached_decode_picture_segments(segments, width, height, qp, tools, bit_depth, col_bd, row_bd, wavefront, sao, strict_levels=False, **kw):
+    """slice_spec.decode_picture_segments behind a table of its results, as cached_decode_picture is for the one-segment entry."""
+    import slice_spec
+    segments = tuple((int(a), int(d), tuple(bytes(b) for b in subs)) for a, d, subs in segments)
+    key = (segments, width, height, qp, tools & 0x14, bit_depth, tuple(col_bd), tuple(row_bd), bool(wavefront), bool(sao), bool(strict_levels), tuple(sorted(kw.items())))
+    if key not in _DECODED_SEGMENTS:
+        try:
+            _DECODED_SEGMENTS[key] = slice_spec.decode_picture_segments(segments, width, height, qp, tools, bit_depth, col_bd, row_bd, wavefront, sao, strict_levels=strict_levels, **kw)
+        except slice_spec.SliceError as e:
+            _DECODED_SEGMENTS[key] = e
+    if isinstance(_DECODED_SEGMENTS[key], Exception):
+        raise _DECODED_SEGMENTS[key]
+    return _DECODED_SEGMENTS[key]
+
+
+def decode_layout_substreams(cfg, lay, subs, strict_levels=False, **mutants):
+    """The decoder's segment entry on sub-streams coded under cfg and the layout (straight from code_slice_data's buffer) -> (records, SAO parameters, tskip mask, tally)."""
+    borders, (cb, rb), wpp = segment_borders(cfg, lay)
+    assert sum(n for _, _, _, n in borders) == len(subs)
+    segments = [(a, d, subs[k:k + n]) for a, d, k, n in borders]
+    kw = dict(SPS_OF_THE_PRODUCT)
+    kw.update(mutants)
+    return cached_decode_picture_segments(segments, cfg.width, cfg.height, cfg.qp, cfg.tools, cfg.bit_depth, cb, rb, wpp, bool(cfg.sao_enabled), strict_levels=strict_levels, **kw)
+
+
+def write_layout_access_units(cfg, recs, sao, lay, coded=None):
+    """-> (hevcdl_write_access_unit_segments from the records, hevcdl_write_access_unit_from_slice_data_segments around the shared coder's sub-streams) of picture 0."""
+    import hevcdl_amd
+    lib = hevcdl_amd.load_library()
+    wcfg = hevcdl_amd.stream_config(cfg.width, cfg.height, cfg.qp, sao=sao is not None, tiles=lay["tiles"], bit_depth=cfg.bit_depth, tools=cfg.tools, lf_offsets=lay["lf_offsets"],
+                                    wavefront=lay["wavefront"])
+    assert bytes(wcfg) == bytes(cfg)
+    layout, segments = layout_keys(lay)
+    segments = hevcdl_amd.segment_layout(segments)
+    cap = cfg.width * cfg.height * 12 + (1 << 16)                         # as host_writer_stream: room for pictures of maximal levels, which hevcdl_access_unit_bound does not give
+    buf, n = np.zeros(cap, np.uint8), ctypes.c_size_t(0)
+    cp, _keep = hevcdl_amd._choice_ptr(lay["choice"])
+    r, p = np.ascontiguousarray(recs[0]), None if sao is None else np.ascontiguousarray(sao[0])
+    st = lib.hevcdl_write_access_unit_segments(ctypes.byref(cfg), hevcdl_amd._layout_ptr(layout), hevcdl_amd._layout_ptr(segments), 0, r.ctypes.data, None if p is None else p.ctypes.data, cp,
+                                               buf.ctypes.data, cap, ctypes.byref(n))
+    assert st == 0, st
+    a = buf[:n.value].tobytes()
+    coded = coded or code_layout(cfg, recs, sao, lay)
+    buf, sizes, ovf, off, cap = coded
+    assert not ovf.any()
+    b = hevcdl_amd.write_access_unit_from_slice_data(cfg, 0, hevcdl_amd.pack_slice_data(buf[0], sizes[0], off), sizes[0], choice=lay["choice"], layout=layout, segments=segments)
+    return a, b
+
+
+def layouts_of(cx, cy):
+    """The layouts hevcdl_write_access_unit_segments accepts on a picture of cx x cy CTUs (cy >= 2), by what each is there for."""
+    rows_t = (1, cy)                                                      # a tile per CTU row (a tile column needs four CTUs: rows are what small pictures have)
+    out = [("rs1", _lay(slices=(1, cx))),                                                           # row slices of one row
+           ("rs1lf0", _lay(slices=(1, cx), lf_across_slices=False)),
+           ("ts1", _lay(tiles=rows_t, slices=(3, 1))),                                             # slices of one tile
+           ("ws1", _lay(wavefront=True, segments=(1, cx))),                                        # wavefront segments of one row
+           ("tg1", _lay(tiles=rows_t, segments=(3, 1))),                                           # tile segments alone
+           ("rs1dbk", _lay(slices=(1, cx), choice=(1, 1, 0, 2, -1), lf_offsets=(2, -1))),          # LoopFilterOffsetInPPS 0: deblocking fields in every independent header
+           ("ws1dbk", _lay(wavefront=True, segments=(1, cx), choice=(1, 1, 1, 0, 0)))]             # ... with the filter disabled by the slice
+    if cy >= 3:
+        out += [("rs2", _lay(slices=(1, 2 * cx), lf_across_slices=cy == 3)),                        # several rows; 3 rows: a shorter last slice
+                ("ts2", _lay(tiles=rows_t, slices=(3, 2))),                                        # 2 or more tiles a slice; the last takes what is left
+                ("ws2", _lay(wavefront=True, segments=(1, 2 * cx))),                               # several rows a segment (3 rows: a shorter last segment)
+                ("tg2", _lay(tiles=rows_t, segments=(3, 2))),
+                ("ts2g1", _lay(tiles=rows_t, slices=(3, 2), segments=(3, 1))),                     # tile segments inside tile slices
+                ("ts3g2", _lay(tiles=rows_t, slices=(3, 3), segments=(3, 2), choice=(1, 1, 0, -3, 4), lf_offsets=(-3, 4)))]      # a segment cut short at its slice's end
+    return out
+
+
+LAYOUT_SIZES = [s for s in FUZZ_SIZES if s[1] > 64]                       # two CTU rows or more: (8, 72), (72, 72), (136, 200), (200, 136)
+# directed: twelve tiles in slices of five in segments of two (5 + 5 + 2 tiles -> 3 + 3 + 1 segments), tile COLUMNS in slices in segments (a slice border to the LEFT of a
+# CTU), a one-CTU-wide wavefront picture of three rows
+LAYOUT_DIRECTED = [("t12s5g2", 64, 768, _lay(tiles=(1, 12), slices=(3, 5), segments=(3, 2))),
+                   ("c2s1", 456, 64, _lay(tiles=(2, 1), slices=(3, 1), lf_across_slices=False)),
+                   ("c2g1", 520, 64, _lay(tiles=(2, 1), segments=(3, 1))),
+                   ("w1x3", 64, 192, _lay(wavefront=True, segments=(1, 1)))]
+
+
+@functools.lru_cache(maxsize=None)
+def layout_corpus():
+    """Seeded pictures of at most 12 CTUs under every layout of layouts_of and LAYOUT_DIRECTED: [(name, cfg, records [1, ctus], SAO parameters [1, ctus, 3] or None,
+    layout)].  Styles as in fuzz_corpus (all +-32767, last position, mixed), 8 and 10 bits, SAO on and off; the attributes cycle with periods that share no factor with
+    the number of layouts of a size, so that each layout meets each of them."""
+    import hevcdl_amd
+    rng = np.random.default_rng(20241105)
+    out = []
+    i = 0
+    for rnd in range(3):
+        for w, h in LAYOUT_SIZES:
+            for lname, lay in layouts_of((w + 63) // 64, (h + 63) // 64):
+                if rnd >= 1 and lname in ("rs1lf0", "rs1dbk", "ws1dbk"):
+                    continue
+                style = (0 if i % 11 == 3 else (1 if i % 11 == 7 else (2 if i % 4 == 1 or (rnd >= 1 and lname in ("ws2", "tg2")) else None)))      # (flat rows under a dependent header's entry points)
+                if style == 0 and w * h > 136 * 136:                      # an all-+-32767 picture of 12 CTUs is 100 KB of slice data: 4 CTUs carry the same paths
+                    style = None
+                bd = 10 if i % 3 == 1 else 8
+                with_sao = i % 2 == 0
+                tools = 0x7f if i % 5 else 0x7f & ~(0x04 if i % 10 else 0x10)
+                out.append(_layout_picture(rng, "%s%02d_%dx%d_%s" % ("M" if style == 0 else "L", i, w, h, lname), w, h, lay, style, bd, with_sao, tools))
+                i += 1
+    for k, (lname, w, h, lay) in enumerate(LAYOUT_DIRECTED):
+        out.append(_layout_picture(rng, "%s%d_%dx%d_%s" % ("M" if lname == "w1x3" else "D", k, w, h, lname), w, h, lay, 0 if lname == "w1x3" else (2 if k == 0 else None), 10 if k == 1 else 8, k != 2, 0x7f))
+    return out
+
+
+def flatten_ctu(r, x0, y0, w, h):
+    """One CTU record made flat: 8x8 CUs, planar prediction (the first candidate wherever the neighbours are flat or missing), chroma from luma, no coefficient.  Every bin
+    of such a CTU is soon the more probable one and every bypass bin 0, so the arithmetic coder's low stays 0 and it writes zero bytes: the slice data then needs
+    emulation prevention bytes, which natural content of a few KB almost never does."""
+    for k in ("part_size", "luma_dir", "tr_idx", "cbf", "tskip", "coeff_y", "coeff_cb", "coeff_cr", "depth", "chroma_dir"):
+        r[k][...] = 0
+    for y4 in range(min(16, (h - y0) // 4)):
+        for x4 in range(min(16, (w - x0) // 4)):
+            z = _z_of(x4, y4)
+            r["depth"][z], r["chroma_dir"][z] = 3, 36
+
+
+def _layout_picture(rng, name, w, h, lay, style, bd, with_sao, tools):
+    """style 2: mixed records with every even CTU row flat (flatten_ctu)."""
+    import hevcdl_amd
+    cfg = hevcdl_amd.stream_config(w, h, int(rng.integers(0, 52)), sao=with_sao, tiles=lay["tiles"], bit_depth=bd, tools=tools, wavefront=lay["wavefront"], lf_offsets=lay["lf_offsets"])
+    recs = synth_records(rng, w, h, None if style == 2 else style)[None]
+    if style == 2:
+        cx = (w + 63) // 64
+        for a in range(recs.shape[1]):
+            if (a // cx) % 2 == 0:
+                flatten_ctu(recs[0, a], (a % cx) * 64, (a // cx) * 64, w, h)
+    sao = synth_sao(rng, recs.shape[1], bd)[None] if with_sao else None
+    return name, cfg, recs, sao, lay
+
+
+def canonical_layout(cfg, recs, sao, mask, lay):
+    """canonical() for a picture of slices: a SAO merge candidate in another slice does not exist either.  canonical() knows tile borders from the cfg; the borders of
+    slices are added here from segment_borders (the first CTU row / column of every independent segment's rectangle)."""
+    out, s = canonical(cfg, recs, sao, mask)
+    if sao is None:
+        return out, s
+    borders, (cb, rb), _ = segment_borders(cfg, lay)
+    cx = (cfg.width + 63) // 64
+    starts = sorted(a for a, d, _, _ in borders if not d)
+    for a in range(sao.shape[0]):
+        if sao[a][0]["mode"] != 2 or s[a, 0]["mode"] != 2:
+            continue
+        nb = a - 1 if sao[a][0]["type"] == 0 else a - cx
+        if _slice_of(cfg, lay, starts, a) != _slice_of(cfg, lay, starts, nb):
+            s[a] = np.zeros(3, s.dtype)
+    return out, s
+
+
+def _slice_of(cfg, lay, starts, rs):
+    """SliceAddrRs of a CTU: the independent segment whose tiles / rows hold it.  Row slices and wavefront: the last start at or below rs; tiles: the start of the slice
+    that the CTU's tile belongs to."""
+    import hevcdl_amd
+    cx = (cfg.width + 63) // 64
+    _, _, _, cb, rb = hevcdl_amd.tile_layout(lay["tiles"], cfg.width, cfg.height)
+    if len(cb) == 2 and len(rb) == 2:
+        return max(a for a in starts if a <= rs)
+    rx, ry = rs % cx, rs // cx
+    tx, ty = max(i for i in range(len(cb) - 1) if rx >= cb[i]), max(j for j in range(len(rb) - 1) if ry >= rb[j])
+    tile = ty * (len(cb) - 1) + tx
+    per = lay["slices"][1] if lay["slices"] else (len(cb) - 1) * (len(rb) - 1)
+    first = (tile // per) * per
+    return rb[first // (len(cb) - 1)] * cx + cb[first % (len(cb) - 1)]
+
+
+def assert_layout_round_trip(name, cfg, recs, sao, lay, decoded):
+    got, gsao, mask, _ = decoded
+    want, wsao = canonical_layout(cfg, recs, sao, mask, lay)
+    for k in RT_FIELDS:
+        assert np.array_equal(got[k], want[k]), "%s: %s differs at %s" % (name, k, np.argwhere(got[k] != want[k])[:4].tolist())
+    assert (gsao is None) == (wsao is None)
+    if wsao is not None:
+        assert np.array_equal(gsao, wsao), "%s: SAO parameters differ at CTU %s" % (name, [a for a in range(len(wsao)) if not np.array_equal(gsao[a], wsao[a])][:4])
+
+
+# 64x128 pictures (two CTUs, QP 30) whose sub-stream 0 ends a dependent slice segment in mid-slice -- end_of_slice_segment_flag 1 and rbsp_slice_segment_trailing_bits()
+# where the same sub-stream without the segment keys writes flag 0, end_of_subset_one_bit and byte_alignment() -- on the edges of the device coder's output stage, in the
+# wavefront variant (segments (1, 1): the two-launch path) and the tile-rows variant (tiles (1, 2), segments (3, 1)): (seed of synth_records, length of sub-stream 0).
+# Found by a search over the seeds 1, 2, 3, ... with the host coder; the tests assert the residues.
+STAGE_VARIANTS = {"wavefront": {"wavefront": True, "segments": (1, 1)}, "tiles": {"tiles": (1, 2), "segments": (3, 1)}}
+STAGE_SEEDS_SEGMENT = {(v, k): s for v in STAGE_VARIANTS for k, s in
+                       {"on_boundary": (104, 1792), "one_past": (217, 1793), "one_before": (97, 1535), "tail_1": (3, 1041), "tail_2": (2, 898), "tail_3": (1, 1543)}.items()}
+
+
+def stage_segment_picture(variant, kind):
+    """-> (cfg, records [1, 2], layout, the same layout without the segment keys, length of sub-stream 0)."""
+    import hevcdl_amd
+    seed, length = STAGE_SEEDS_SEGMENT[(variant, kind)]
+    lay = _lay(**STAGE_VARIANTS[variant])
+    cfg = hevcdl_amd.stream_config(64, 128, 30, tiles=lay["tiles"], wavefront=lay["wavefront"])
+    plain = dict(lay)
+    plain["segments"] = None
+    return cfg, synth_records(np.random.default_rng(seed), 64, 128)[None], lay, plain, length

@@ -105,18 +105,22 @@ def split_annexb(stream):
 
 def slice_nals(stream):
     """Per access unit (one starts at a VPS: ReWriteParamSetsFlag 1): [(NAL unit type, first_slice_segment_in_pic_flag, dependent_slice_segment_flag)] of its slice NAL
-    units.  In a stream with dependent segments enabled the flag of a NAL unit that is not the picture's first follows no_output_of_prior_pics_flag (IRAP pictures
-    only here) and the one bit of slice_pic_parameter_set_id 0; elsewhere it is reported as 0."""
-    out, dep_enabled = [], False
+    units, read by oracle/hevc_parse.py's slice_segment_header(): the flag exists under the PPS's dependent_slice_segments_enabled_flag in every header but the
+    picture's first; elsewhere it is reported as 0."""
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import hevc_parse
+    out, sps, pps = [], None, None
     for _, n in split_annexb(stream):
         t = (n[0] >> 1) & 63
         if t == 32:
             out.append([])
+        elif t == 33:
+            sps = hevc_parse.parse_sps(n)
         elif t == 34:
-            dep_enabled = bool((n[2] >> 5) & 1)      # pps id 0, sps id 0 (a bit each), dependent_slice_segments_enabled_flag
+            pps = hevc_parse.parse_pps(n)
         elif t <= 21:
-            first = n[2] >> 7
-            out[-1].append((t, first, (n[2] >> 4) & 1 if dep_enabled and not first else 0))
+            hdr, _ = hevc_parse.parse_slice_header(n, sps, pps)
+            out[-1].append((t, hdr["first_slice"], hdr["dependent"]))
     return out
 
 
