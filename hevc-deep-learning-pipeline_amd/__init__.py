@@ -23,7 +23,7 @@ LEAF_LIB_PATH = os.path.join(PKG_DIR, "lib", "libhevcdl_hip_leaf.so")        # -
 WEIGHTS_PATH = os.path.join(PKG_DIR, "weights", "hevc_encoder_model.f32")
 WEIGHT_FLOATS = 637712
 LEAF_SOURCES = ["rd_leaf.hip", "rd_leaf_bd10.hip", "rd_leaf_wide.hip", "rd_leaf_tools.hip"]      # the decision kernel's four builds, each with csrc/rd_leaf_harness.h behind it
-SOURCES = ["cnn_kernel.hip", "fc_kernel.hip", "rd_kernel.hip", "rd_kernel_bd10.hip", "rd_kernel_wide.hip", "rd_kernel_tools.hip", "deblock_kernel.hip", "dbk_select_kernel.hip", "sao_kernel.hip", "quality_kernel.hip", "report_kernel.hip", "entropy_kernel.hip", "source_kernel.hip", "hevcdl_api.hip", "hevcdl_bitstream.cpp"]
+SOURCES = ["cnn_kernel.hip", "fc_kernel.hip", "rd_kernel.hip", "rd_kernel_bd10.hip", "rd_kernel_wide.hip", "rd_kernel_tools.hip", "deblock_kernel.hip", "dbk_select_kernel.hip", "sao_kernel.hip", "quality_kernel.hip", "report_kernel.hip", "entropy_kernel.hip", "source_kernel.hip", "qp_rd_kernel.hip", "hevcdl_api.hip", "hevcdl_bitstream.cpp"]
 
 STATUS = {0: "OK", 1: "INVALID_ARG", 2: "UNSUPPORTED", 3: "NO_DEVICE", 4: "HIP", 5: "OOM"}
 
@@ -66,7 +66,21 @@ class Config(ctypes.Structure):
                 ("lf_across_tiles", ctypes.c_int32), ("lf_beta_offset_div2", ctypes.c_int32), ("lf_tc_offset_div2", ctypes.c_int32), ("wavefront", ctypes.c_int32),
                 ("deblocking_metric", ctypes.c_int32), ("lf_offset_in_pps", ctypes.c_int32),
                 ("slice_mode", ctypes.c_int32), ("slice_argument", ctypes.c_int32), ("lf_across_slices", ctypes.c_int32),
-                ("slice_segment_mode", ctypes.c_int32), ("slice_segment_argument", ctypes.c_int32)]
+                ("slice_segment_mode", ctypes.c_int32), ("slice_segment_argument", ctypes.c_int32), ("delta_qp_rd", ctypes.c_int32)]
+
+
+QP_RD_MAX_N = 6      # HEVCDL_QP_RD_MAX_N (include/hevcdl.h): the largest DeltaQpRD a context takes
+QP_RD_MAX_CANDIDATES = 2 * QP_RD_MAX_N + 1
+
+
+class QpRdCandidate(ctypes.Structure):
+    """hevcdl_qp_rd_candidate of include/hevcdl.h: one candidate of the QP search -- offset, the QP it is coded at, and the decision constants of Config for it."""
+    _fields_ = [("offset", ctypes.c_int32), ("qp", ctypes.c_int32), ("lambda_", ctypes.c_double), ("sqrt_lambda", ctypes.c_double), ("chroma_weight", ctypes.c_double),
+                ("lambda_chroma", ctypes.c_double), ("err_scale", (ctypes.c_double * 4) * 2), ("sbh_rd_factor", ctypes.c_int64 * 2), ("qp_chroma", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
+# hevcdl_qp_rd_row as a numpy record: the picture sums of every candidate, the best cost and index (take: device bookkeeping)
+QP_RD_ROW_DTYPE = np.dtype([("bits", "<u8", (QP_RD_MAX_CANDIDATES,)), ("dist", "<u8", (QP_RD_MAX_CANDIDATES,)), ("best_cost", "<f8"), ("best_idx", "<i4"), ("take", "<i4")])
 
 
 class SliceLayout(ctypes.Structure):
@@ -380,6 +394,15 @@ def load_library():
     lib.hevcdl_access_unit_bound_segments.argtypes = [ci, ci, slp, sgp]
     lib.hevcdl_access_unit_bound_segments.restype = ctypes.c_size_t
     lib.hevcdl_get_segment_layout.argtypes = [vp, sgp]
+    lib.hevcdl_qp_rd_candidates.argtypes = [ctypes.POINTER(Config), ctypes.POINTER(QpRdCandidate), ci, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double)]
+    lib.hevcdl_qp_rd_pick_index.argtypes = [vp, vp, ci, ctypes.c_double]
+    lib.hevcdl_get_qp_rd.argtypes = [vp, ci, ci, vp, vp]
+    lib.hevcdl_get_qp_rd_info.argtypes = [vp, szp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double)]
+    lib.hevcdl_qp_rd_step.argtypes = [ci, ci, ctypes.c_size_t, ci, ci, ctypes.c_double, vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t]
+    lib.hevcdl_deblock_frames_qp.argtypes = [vp, vp, ci, vp, vp, vp, vp]
+    lib.hevcdl_deblock_frames_qp_dev.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp]
+    lib.hevcdl_sao_frames_qp.argtypes = [vp, vp, vp, ci, vp, vp, vp]
+    lib.hevcdl_sao_frames_qp_dev.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -401,7 +424,41 @@ EXPORTS = ["hevcdl_config_default", "hevcdl_create", "hevcdl_destroy", "hevcdl_l
            "hevcdl_write_access_unit_slices", "hevcdl_write_access_unit_from_slice_data_slices", "hevcdl_slice_data_layout_slices", "hevcdl_code_slice_data_host_slices", "hevcdl_code_slice_data_slices",
            "hevcdl_access_unit_bound_slices", "hevcdl_get_slice_layout",
            "hevcdl_write_access_unit_segments", "hevcdl_write_access_unit_from_slice_data_segments", "hevcdl_slice_data_layout_segments", "hevcdl_code_slice_data_host_segments",
-           "hevcdl_code_slice_data_segments", "hevcdl_access_unit_bound_segments", "hevcdl_get_segment_layout"]
+           "hevcdl_code_slice_data_segments", "hevcdl_access_unit_bound_segments", "hevcdl_get_segment_layout",
+           "hevcdl_qp_rd_candidates", "hevcdl_qp_rd_pick_index", "hevcdl_get_qp_rd", "hevcdl_get_qp_rd_info", "hevcdl_qp_rd_step",
+           "hevcdl_deblock_frames_qp", "hevcdl_deblock_frames_qp_dev", "hevcdl_sao_frames_qp", "hevcdl_sao_frames_qp_dev"]
+
+
+def qp_rd_candidates(cfg):
+    """The candidate table of a Config (hevcdl_qp_rd_candidates; no GPU needed) -> (list of QpRdCandidate in candidate order, frame lambda)."""
+    lib = load_library()
+    out = (QpRdCandidate * QP_RD_MAX_CANDIDATES)()
+    n, fl = ctypes.c_int(0), ctypes.c_double(0.0)
+    st = lib.hevcdl_qp_rd_candidates(ctypes.byref(cfg), out, QP_RD_MAX_CANDIDATES, ctypes.byref(n), ctypes.byref(fl))
+    if st:
+        raise HevcdlError(st, "hevcdl_qp_rd_candidates")
+    return [out[i] for i in range(n.value)], fl.value
+
+
+def qp_rd_pick(bits, dist, frame_lambda):
+    """The pick rule of the QP search on picture sums in candidate order (hevcdl_qp_rd_pick_index: the source the device runs) -> the index kept."""
+    lib = load_library()
+    bits, dist = np.ascontiguousarray(bits, np.uint64).reshape(-1), np.ascontiguousarray(dist, np.uint64).reshape(-1)
+    if bits.size != dist.size:
+        raise ValueError("as many bits as dist sums")
+    return int(lib.hevcdl_qp_rd_pick_index(bits.ctypes.data, dist.ctypes.data, int(bits.size), float(frame_lambda)))
+
+
+def qp_rd_step(ctus_per_frame, frame_bytes, idx, frame_lambda, trial_records, trial_recon, trial_stats, rows, records, recon, stats, guard_bytes, device=0):
+    """TEST AND DIAGNOSTIC: the sum and keep kernels alone (hevcdl_qp_rd_step).  rows [n] QP_RD_ROW_DTYPE and the three destinations (byte arrays WITH their guard
+    margins) are updated in place."""
+    lib = load_library()
+    n = int(rows.shape[0])
+    ptr = lambda a: None if a is None else a.ctypes.data
+    st = lib.hevcdl_qp_rd_step(int(device), int(ctus_per_frame), int(frame_bytes), n, int(idx), float(frame_lambda), ptr(trial_records), ptr(trial_recon), ptr(trial_stats),
+                               rows.ctypes.data, ptr(records), ptr(recon), ptr(stats), int(guard_bytes))
+    if st:
+        raise HevcdlError(st, "hevcdl_qp_rd_step")
 
 
 def picture_hash_sei(width, height, picture, bit_depth=8, method=1):
@@ -531,7 +588,7 @@ TOOL_RDOQ, TOOL_RDOQTS, TOOL_TSKIP, TOOL_TSKIP_FAST, TOOL_SIGN_HIDE, TOOL_STRONG
 
 
 def default_config(width, height, qp, max_frames=1, device=0, cnn_input=0, tiles=(1, 1), bit_depth=8, lf_across_tiles=True, bn_mode=0, tools=TOOLS_REFERENCE, lf_offsets=(0, 0), wavefront=False,
-                   deblocking_metric=0, lf_offset_in_pps=True, slices=None, lf_across_slices=True, segments=None):
+                   deblocking_metric=0, lf_offset_in_pps=True, slices=None, lf_across_slices=True, segments=None, delta_qp_rd=0):
     lib = load_library()
     cfg = Config()
     st = lib.hevcdl_config_default_bd(ctypes.byref(cfg), width, height, qp, bit_depth)
@@ -549,6 +606,7 @@ def default_config(width, height, qp, max_frames=1, device=0, cnn_input=0, tiles
         cfg.slice_mode, cfg.slice_argument, cfg.lf_across_slices = int(slices[0]), int(slices[1]), 1 if lf_across_slices else 0
     if segments is not None:                   # (SliceSegmentMode, SliceSegmentArgument)
         cfg.slice_segment_mode, cfg.slice_segment_argument = int(segments[0]), int(segments[1])
+    cfg.delta_qp_rd = int(delta_qp_rd)         # DeltaQpRD: every picture decided at 2N+1 QPs round the cfg's, the cheapest kept
     return cfg
 
 
@@ -780,12 +838,12 @@ class Encoder:
     """One context per device.  Frames are planar 8-bit 4:2:0, numpy [n_frames, w*h*3/2] uint8."""
 
     def __init__(self, width, height, qp, max_frames=1, device=0, cnn_input=0, weights=None, cfg=None, tiles=(1, 1), bit_depth=8, lf_across_tiles=True, bn_mode=0, tools=TOOLS_REFERENCE, lf_offsets=(0, 0), wavefront=False,
-                 deblocking_metric=0, lf_offset_in_pps=True, slices=None, lf_across_slices=True, segments=None):
+                 deblocking_metric=0, lf_offset_in_pps=True, slices=None, lf_across_slices=True, segments=None, delta_qp_rd=0):
         """bit_depth 10: every yuv / recon array of the decision path holds uint16 samples (frame_bytes counts bytes).  slices: (SliceMode, SliceArgument); segments:
         (SliceSegmentMode, SliceSegmentArgument) -- dependent slice segments, which change the stream alone."""
         self.lib = load_library()
         self.cfg = cfg or default_config(width, height, qp, max_frames, device, cnn_input, tiles, bit_depth, lf_across_tiles, bn_mode, tools, lf_offsets, wavefront,
-                                         deblocking_metric, lf_offset_in_pps, slices, lf_across_slices, segments)
+                                         deblocking_metric, lf_offset_in_pps, slices, lf_across_slices, segments, delta_qp_rd)
         self.segment_layout = segment_layout((self.cfg.slice_segment_mode, self.cfg.slice_segment_argument))
         self.slice_layout = slice_layout((self.cfg.slice_mode, self.cfg.slice_argument), self.cfg.lf_across_slices != 0)      # what the writer's entry points take for this context's pictures
         self.bit_depth = self.cfg.bit_depth
@@ -1038,6 +1096,46 @@ class Encoder:
         out = np.zeros(count, DBK_CHOICE_DTYPE)
         self._check(self.lib.hevcdl_get_dbk_choice(self._h, int(first), int(count), out.ctypes.data))
         return out
+
+    # ---- DeltaQpRD: the slice QP picked per picture among 2N+1 candidate encodes ----
+    def get_qp_rd(self, first, count):
+        """(rows [count] QP_RD_ROW_DTYPE, the QP every picture was coded with [count] int32) of pictures [first, first + count) of the last decision call (hevcdl_get_qp_rd)."""
+        rows, qps = np.zeros(count, QP_RD_ROW_DTYPE), np.zeros(count, np.int32)
+        self._check(self.lib.hevcdl_get_qp_rd(self._h, int(first), int(count), rows.ctypes.data, qps.ctypes.data))
+        return rows, qps
+
+    def get_qp_rd_info(self):
+        """TEST AND DIAGNOSTIC: (bytes of the trial set the context holds, sum / keep kernel launches so far)."""
+        b, k = ctypes.c_size_t(0), ctypes.c_uint64(0)
+        self._check(self.lib.hevcdl_get_qp_rd_info(self._h, ctypes.byref(b), ctypes.byref(k), None))
+        return int(b.value), int(k.value)
+
+    def get_qp_rd_kernel_ms(self):
+        """With profile_enable: HIP-event ms of (the sum launches, the keep launches) of the last search, each summed over its candidates."""
+        b, k, ms = ctypes.c_size_t(0), ctypes.c_uint64(0), (ctypes.c_double * 2)()
+        self._check(self.lib.hevcdl_get_qp_rd_info(self._h, ctypes.byref(b), ctypes.byref(k), ms))
+        return float(ms[0]), float(ms[1])
+
+    def deblock_frames_qp(self, recon, records, idx, choices=None):
+        """deblock_frames for pictures coded with candidates idx [n] of the context's table (hevcdl_deblock_frames_qp)."""
+        recon, n = self._frames(recon)
+        records = np.ascontiguousarray(records).reshape(n, self.ctus)
+        idx = np.ascontiguousarray(idx, np.int32).reshape(n)
+        if choices is not None:
+            choices = np.ascontiguousarray(choices, DBK_CHOICE_DTYPE).reshape(n)
+        out = np.zeros_like(recon)
+        self._check(self.lib.hevcdl_deblock_frames_qp(self._h, recon.ctypes.data, n, records.ctypes.data, None if choices is None else choices.ctypes.data, idx.ctypes.data, out.ctypes.data))
+        return out
+
+    def sao_frames_qp(self, org, deblocked, idx):
+        """sao_frames for pictures coded with candidates idx [n] of the context's table (hevcdl_sao_frames_qp)."""
+        org, n = self._frames(org)
+        dbk, _ = self._frames(deblocked)
+        idx = np.ascontiguousarray(idx, np.int32).reshape(n)
+        params = np.zeros((n, self.ctus, 3), SAO_DTYPE)
+        out = np.zeros_like(org)
+        self._check(self.lib.hevcdl_sao_frames_qp(self._h, org.ctypes.data, dbk.ctypes.data, n, idx.ctypes.data, params.ctypes.data, out.ctypes.data))
+        return params, out
 
     def sao_frames(self, org, deblocked):
         """original + deblocked frames -> (SAO parameters [n, ctus, 3] SAO_DTYPE, final reconstruction)."""

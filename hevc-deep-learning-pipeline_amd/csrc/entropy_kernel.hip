@@ -60,6 +60,7 @@ extern "C" __global__ __launch_bounds__(EC_WAVES * 64) void hevcdl_entropy_kerne
   pic.recs = (const hevcdl_ctu_record *)p.records + (size_t)f * pic.ctus;
   pic.sao = p.sao ? (const hevcdl_sao_blk *)p.sao + (size_t)f * pic.ctus : nullptr;
   pic.tools = (uint32_t)p.tools; pic.max_sao_offset = p.max_sao_offset; pic.tx0 = 0; pic.ty0 = 0;
+  const int slice_qp = p.frame_qp ? p.frame_qp[f].qp : p.qp;      // the picture's own slice QP (DeltaQpRD), or the launch's
   EcCoder s;
   s.t = t; s.ctx = l.ctx; s.absb = l.absb; s.stage = l.stage; s.out = nullptr; s.cap = 0; s.dry = 0;
   ec_start(s);
@@ -69,7 +70,7 @@ extern "C" __global__ __launch_bounds__(EC_WAVES * 64) void hevcdl_entropy_kerne
   if (p.phase == 1) { // contexts only, first two CTUs of every row; the slot of row r = the contexts behind CTU 1 of row r
     if (p.ctus_x < 2 || !p.sync) return;
     s.dry = 1;
-    ec_init_contexts(l.ctx, t, p.qp);
+    ec_init_contexts(l.ctx, t, slice_qp);
     for (int row = 0; row < p.ctus_y; row++) {
       ec_code_ctu(s, pic, 0, row);
       ec_code_ctu(s, pic, 1, row);
@@ -87,7 +88,7 @@ extern "C" __global__ __launch_bounds__(EC_WAVES * 64) void hevcdl_entropy_kerne
   if (p.wpp && k > 0 && p.ctus_x > 1 && p.sync) { // every lane copies the whole set: nothing a lane reads from LDS later was written by another lane
     const uint32_t *src = sync + (k - 1) * (EC_SYNC_BYTES / 4);
     for (int i = 0; i < EC_SYNC_BYTES / 4; i++) ((uint32_t *)l.ctx)[i] = src[i];
-  } else ec_init_contexts(l.ctx, t, p.qp);
+  } else ec_init_contexts(l.ctx, t, slice_qp);
   s.out = p.out + (size_t)f * p.frame_stride + p.unit_off[k];
   s.cap = p.unit_cap[k] & ~3u;
   ec_code_substream(s, pic, cx0, cx1, cy0, cy1);

@@ -13,6 +13,7 @@
 #include "source_core.h"
 #include "rd_launch_plan.h"
 #include "slice_grid.h"
+#include "qp_rd.h"
 
 enum { LABELS_PER_CTU = 16, LOGITS_PER_CTU = 64, CTU_RGB_BYTES = 64 * 64 * 3 };      // of a CTU: its 16x16 cells, four logits a cell, the RGB input of hevcdl_predict_depth_rgb
 
@@ -139,6 +140,20 @@ struct RdWorkspace {
   DevBuf<unsigned char> d_wpp;           // WaveFrontSynchro: [max_frames][ctus_y] 256 bytes (the contexts behind a row's second CTU, the row's finished-CTU count: rd_kernel.hip)
   DevBuf<unsigned char> d_sched;         // hand-over of units between workgroups (finished counter, per-workgroup unit counts, mailboxes)
 };
+// DeltaQpRD (qp_rd_kernel.hip, qp_rd.h): the candidate table of the configuration; the trial set -- outputs of the candidates behind the first, for max_frames pictures --
+// and the rows, allocated by the first decision call of a context with the key (or hevcdl_reserve_workspace); the per-picture QP table of the stages behind the
+// decisions.  A context without the key (n == 0) allocates and launches none of it.
+struct QpRd {
+  int n = 0, count = 1;                  // cfg.delta_qp_rd, 2 n + 1
+  hevcdl_qp_rd_candidate cand[HEVCDL_QP_RD_MAX_CANDIDATES]; double frame_lambda = 0;
+  DevBuf<unsigned char> d_records, d_recon, d_stats; DevBuf<hevcdl_qp_rd_row> d_rows;
+  DevBuf<hevcdl_frame_qp> d_frame_qp; std::vector<hevcdl_frame_qp> h_frame_qp;      // what SAO and the entropy coder read per picture (staged like the deblocking rows)
+  size_t trial_bytes = 0; unsigned long long launches = 0;
+  std::vector<Event> ev_sum, ev_keep;    // with hevcdl_profile_enable: start / stop pairs round the sum and keep launches of the last search (hevcdl_get_qp_rd_info)
+  int last_frames = 0;                   // pictures of the last decision call: their rows are in d_rows
+  std::vector<int32_t> h_idx;            // the picture pipeline's last batch: the candidate every picture was coded with
+  std::vector<hevcdl_qp_rd_row> h_rows;  // ... and its rows, fetched once (hevcdl_get_qp_rd then copies from here, also inside a chunk callback); empty behind a *_dev call
+};
 
 struct hevcdl_ctx {
   char last_rd[160] = { 0 };           // which build and launch form the last decision launch took (hevcdl_last_rd_launch)
@@ -150,7 +165,7 @@ struct hevcdl_ctx {
   int col_bd[21] = { 0 }, row_bd[23] = { 0 };    // tile boundaries in CTUs
   DevBuf<float> d_weights, d_a3; size_t a3_ctus = 0;   // d_a3: conv3 outputs of one chunk of CTUs (32 KB per CTU): the hand-over from the conv kernel to the head kernel
   DevBuf<int> d_flag;                  // device-side error flag of the label check
-  Staging stage; SaoWorkspace sao; Quality q; Report rp; Entropy ec; Source src; Session ses; RdWorkspace rd; DbkSelect dbk;
+  Staging stage; SaoWorkspace sao; Quality q; Report rp; Entropy ec; Source src; Session ses; RdWorkspace rd; DbkSelect dbk; QpRd qprd;
   int ec_capacity_per_ctu = 0;         // hevcdl_set_entropy_capacity (tests): 0 = the default; outlives the entropy switch
   bool profile = false;
   std::vector<Event> ev_cnn, ev_rd, ev_conv;       // start/stop pairs (ev_conv: the convolution kernel alone, one pair per chunk of CTUs)
@@ -164,10 +179,7 @@ struct hevcdl_ctx {
   size_t sao_bytes(size_t n) const { return (size_t)ctus * sizeof(hevcdl_sao_blk) * n; }
 };
 
-static const int CHROMA_SCALE_420[58] = { 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29,
-  29, 30, 31, 32, 33, 33, 34, 34, 35, 35, 36, 36, 37, 37, 38, 39, 40, 41, 42, 43, 44, 45, 46, 47, 48, 49, 50, 51 };   // TComRom.cpp:536
-static const int QUANT_SCALES[6] = { 26214, 23302, 20560, 18396, 16384, 14564 };   // TComRom.cpp:354-357
-static const int INV_QUANT_SCALES[6] = { 40, 45, 51, 57, 64, 72 };                  // TComRom.cpp:359-362
+// (CHROMA_SCALE_420 and the quantiser scales of TComRom.cpp: csrc/qp_rd.h, beside the lambda family that reads them)
 
 static hevcdl_status fail(hevcdl_ctx *c, hevcdl_status s, const char *what, hipError_t e = hipSuccess)
 {
@@ -237,25 +249,12 @@ extern "C" hevcdl_status hevcdl_config_default_bd(hevcdl_config *cfg, int width,
   cfg->ctu_size = 64; cfg->max_partition_depth = 4; cfg->tu_log2_min = 2; cfg->tu_log2_max = 5; cfg->tu_max_depth_intra = 3;
   cfg->tools = HEVCDL_TOOLS_REFERENCE; cfg->bn_mode = HEVCDL_BN_REFERENCE; cfg->boundary_policy = HEVCDL_BOUNDARY_CLAMP;
   cfg->cnn_input = HEVCDL_CNN_INPUT_RGB601; cfg->device = 0; cfg->max_frames = 1; cfg->tile_columns = 1; cfg->tile_rows = 1; cfg->tile_uniform_spacing = 1; cfg->lf_across_tiles = 1; cfg->lf_offset_in_pps = 1; cfg->lf_across_slices = 1;
-  // TEncSlice::calculateLambda (TEncSlice.cpp:433-527) for an all-intra GOP of 1, then setUpLambda (:112-140)
-  cfg->lambda = 0.57 * 1.0 * pow(2.0, (qp - 12) / 3.0);
-  cfg->sqrt_lambda = sqrt(cfg->lambda);                         // TComRdCost::setLambda TComRdCost.cpp:109-122
-  cfg->qp_chroma = CHROMA_SCALE_420[qp];
-  cfg->chroma_weight = pow(2.0, (qp - cfg->qp_chroma) / 3.0);
-  cfg->lambda_chroma = cfg->lambda / cfg->chroma_weight;
-  for (int ch = 0; ch < 2; ch++) {
-    // quantiser QP = QP + qpBdOffset (6 per extra bit, TComTrQuant.cpp:71-100); distortion is kept at 8-bit scale (FULL_NBIT 0:
-    // DISTORTION_PRECISION_ADJUSTMENT, TypeDef.h:170), hence the 1 << 2(bd-8) divisors
-    const int q = (ch ? cfg->qp_chroma : qp) + 6 * (bit_depth - 8), rem = q % 6, per = q / 6, dadj = 2 * (bit_depth - 8);
-    for (int l = 0; l < 4; l++) {                               // TComTrQuant::setErrScaleCoeff TComTrQuant.cpp:3096-3126
-      const int tshift = 15 - bit_depth - (l + 2);
-      double s = (double)(1 << 15);
-      s = s * pow(2.0, -2.0 * tshift);
-      cfg->err_scale[ch][l] = s / QUANT_SCALES[rem] / QUANT_SCALES[rem] / (1 << dadj);
-    }
-    const double inv = (double)INV_QUANT_SCALES[rem], lam = ch ? cfg->lambda_chroma : cfg->lambda;
-    cfg->sbh_rd_factor[ch] = (int64_t)(inv * inv * (1 << (2 * per)) / lam / 16 / (1 << dadj) + 0.5);   // TComTrQuant.cpp:2532-2535
-  }
+  // TEncSlice::calculateLambda (TEncSlice.cpp:433-527) for an all-intra GOP of 1, then setUpLambda (:112-140) and the quantiser's tables: csrc/qp_rd.h, the code every
+  // candidate of the QP search (delta_qp_rd) is computed by as well
+  hevcdl_qp_rd_candidate f;
+  hevcdl_lambda_family_of(qp, qp, bit_depth, &f);
+  cfg->lambda = f.lambda; cfg->sqrt_lambda = f.sqrt_lambda; cfg->chroma_weight = f.chroma_weight; cfg->lambda_chroma = f.lambda_chroma; cfg->qp_chroma = f.qp_chroma;
+  memcpy(cfg->err_scale, f.err_scale, sizeof cfg->err_scale); cfg->sbh_rd_factor[0] = f.sbh_rd_factor[0]; cfg->sbh_rd_factor[1] = f.sbh_rd_factor[1];
   return HEVCDL_OK;
 }
 
@@ -400,6 +399,8 @@ extern "C" hevcdl_status hevcdl_create(const hevcdl_config *cfg, const float *we
   // Slices: the grid the context runs (slice_grid.h) -- a column of row slices for SliceMode 1, the cfg's tiles otherwise; the segment keys are checked there and left out of it
   hevcdl_config grid;
   { const char *why = ""; const hevcdl_status gs = hevcdl_slice_grid(cfg, &grid, &why); if (gs != HEVCDL_OK) return refuse(gs, why); }
+  // DeltaQpRD: what the key is refused with (qp_rd.h), in its words
+  { const char *why = ""; const hevcdl_status qs = hevcdl_qp_rd_keys(cfg, &why); if (qs != HEVCDL_OK) return refuse(qs, why); }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device >= ndev) return HEVCDL_ERR_NO_DEVICE;
   hevcdl_ctx *ctx = new (std::nothrow) hevcdl_ctx();
@@ -408,6 +409,11 @@ extern "C" hevcdl_status hevcdl_create(const hevcdl_config *cfg, const float *we
   ctx->slices.mode = cfg->slice_mode; ctx->slices.argument = cfg->slice_mode ? cfg->slice_argument : 0; ctx->slices.lf_across_slices = cfg->slice_mode ? cfg->lf_across_slices != 0 : 1;
   ctx->segments.mode = cfg->slice_segment_mode; ctx->segments.argument = cfg->slice_segment_mode ? cfg->slice_segment_argument : 0;
   cfg = &ctx->cfg;      // the one place the grid comes from
+  { // the candidates' constants (hevcdl_qp_rd_candidates gives the same table; one candidate without the key): with the key the cfg's own lambda fields are not read
+    ctx->qprd.n = cfg->delta_qp_rd;
+    ctx->qprd.count = hevcdl_qp_rd_table(cfg->qp, cfg->delta_qp_rd, cfg->bit_depth, ctx->qprd.cand, &ctx->qprd.frame_lambda);
+    if (ctx->qprd.count < 1) { delete ctx; return refuse(HEVCDL_ERR_INVALID_ARG, "DeltaQpRD: no candidate table for this QP and bit depth"); }
+  }
   ctx->ctus_x = (cfg->width + 63) >> 6; ctx->ctus_y = (cfg->height + 63) >> 6; ctx->ctus = ctx->ctus_x * ctx->ctus_y;
   ctx->frame_bytes = hevcdl_frame_bytes_bd(cfg->width, cfg->height, cfg->bit_depth);
   hevcdl_tile_bounds(ctx->ctus_x, cfg->tile_columns, cfg->tile_uniform_spacing, cfg->tile_column_width, 1, ctx->col_bd);
@@ -564,7 +570,7 @@ static hevcdl_status ensure_scratch(hevcdl_ctx *ctx, size_t need, hipStream_t s,
 // One decision launch: the plan (rd_launch_plan.h: build, form, workgroups), the areas it wants cleared and seeded, the workspace, the launch, the report.
 static hevcdl_status launch_rd(hevcdl_ctx *ctx, const void *d_yuv, int n_frames, const void *d_labels, void *d_records, void *d_recon, void *d_stats, hipStream_t s,
                                int ctu_begin = 0, int ctu_end = -1, const void *d_cabac_in = nullptr, void *d_cabac_out = nullptr,
-                               int tile_begin = 0, int tile_count = -1, int session_frame = -1)
+                               int tile_begin = 0, int tile_count = -1, int session_frame = -1, const hevcdl_qp_rd_candidate *cand = nullptr)
 {
   RdWorkspace &w = ctx->rd;
   const RdLaunchArgs a = { n_frames, ctu_begin, ctu_end, d_cabac_in != nullptr, d_cabac_out != nullptr, tile_begin, tile_count, session_frame };
@@ -592,6 +598,11 @@ static hevcdl_status launch_rd(hevcdl_ctx *ctx, const void *d_yuv, int n_frames,
   memcpy(p.k.err_scale, ctx->cfg.err_scale, sizeof p.k.err_scale);
   p.k.sbh_rd_factor[0] = ctx->cfg.sbh_rd_factor[0]; p.k.sbh_rd_factor[1] = ctx->cfg.sbh_rd_factor[1];
   p.k.qp = ctx->cfg.qp; p.k.qp_chroma = ctx->cfg.qp_chroma; p.k.tools = (int)ctx->cfg.tools;
+  if (cand) { // DeltaQpRD: this launch codes one candidate of the QP search -- its constants in the cfg's place (setUpLambda(lambda[idx], iQP[idx]), TEncSlice.cpp:632)
+    p.k.lambda = cand->lambda; p.k.sqrt_lambda = cand->sqrt_lambda; p.k.chroma_weight = cand->chroma_weight; p.k.lambda_chroma = cand->lambda_chroma;
+    memcpy(p.k.err_scale, cand->err_scale, sizeof p.k.err_scale);
+    p.k.sbh_rd_factor[0] = cand->sbh_rd_factor[0]; p.k.sbh_rd_factor[1] = cand->sbh_rd_factor[1]; p.k.qp = cand->qp; p.k.qp_chroma = cand->qp_chroma;
+  }
 #ifdef HEVCDL_STAGE_TRACE
   // stage-trace build (tests/test_rd_gpu.py, lib/libhevcdl_hip_trace.so): the kernel logs its search events here; hevcdl_stage_trace_fetch reads them
   if (!g_stage_log) HIPCHK(hipMalloc(&g_stage_log, STAGE_LOG_WORDS * 4));
@@ -621,7 +632,7 @@ static hevcdl_status launch_rd(hevcdl_ctx *ctx, const void *d_yuv, int n_frames,
     else {
       (void)hipGetLastError(); p.migrate = pl.migrate = 0; p.remote = pl.remote = 0; pl.grid = pl.groups;
       if (pl.wpp == 1) { prof_end(ctx, ctx->ev_rd, s); ctx->cfg.exec_flags |= HEVCDL_EXEC_NO_UNIT_HANDOVER; w.plan.exec_flags = ctx->cfg.exec_flags;      // rows on waves of their own need co-residency: this context walks a frame's rows on one wave from now on
-                         return launch_rd(ctx, d_yuv, n_frames, d_labels, d_records, d_recon, d_stats, s, ctu_begin, ctu_end, d_cabac_in, d_cabac_out, tile_begin, tile_count); }
+                         return launch_rd(ctx, d_yuv, n_frames, d_labels, d_records, d_recon, d_stats, s, ctu_begin, ctu_end, d_cabac_in, d_cabac_out, tile_begin, tile_count, -1, cand); }
     }
   }
   if (!launched) (void)hipLaunchKernel(rd.kernel, dim3(pl.groups), dim3(threads), args, smem, s);      // (an error is picked up below, as after every launch)
@@ -657,6 +668,46 @@ static hevcdl_status check_frames(hevcdl_ctx *ctx, int n_frames)
 // the opening of an entry that takes n_frames pictures: a bad context or count is its status, no pictures are nothing to do
 #define FRAMES_OR_RETURN(ctx, n) do { TRY(check_frames(ctx, n)); if ((n) == 0) return HEVCDL_OK; } while (0)
 
+// ---- DeltaQpRD: TEncSlice::precompressSlice (TEncSlice.cpp:572-661) for a batch of pictures ----------------------------------------------------------------------------
+// the trial set and the rows, all or nothing, for max_frames pictures
+static hevcdl_status ensure_qp_rd_trial(hevcdl_ctx *ctx)
+{
+  QpRd &g = ctx->qprd;
+  if (g.d_rows) return HEVCDL_OK;
+  const size_t nf = (size_t)ctx->cfg.max_frames, bytes = ctx->records_bytes(nf) + ctx->frame_bytes * nf + sizeof(hevcdl_frame_stats) * nf + sizeof(hevcdl_qp_rd_row) * nf;
+  TRY(alloc_all(ctx, { want(g.d_records, ctx->records_bytes(nf)), want(g.d_recon, ctx->frame_bytes * nf), want(g.d_stats, sizeof(hevcdl_frame_stats) * nf), want(g.d_rows, sizeof(hevcdl_qp_rd_row) * nf) },
+                "DeltaQpRD trial set (records, reconstruction and statistics of cfg.max_frames pictures)"));
+  g.trial_bytes = bytes;
+  return HEVCDL_OK;
+}
+
+// 2N+1 decision launches over the same frames and labels, each followed by the sum launch and (behind the first) the keep launch, all in order on `s`.  Our search is
+// deterministic: the trial that wins is what the reference's final compressSlice at the winning QP (TEncGOP.cpp, behind precompressSlice) would produce again, so it is kept.
+static hevcdl_status qp_rd_search(hevcdl_ctx *ctx, const void *d_yuv, int n_frames, const void *d_labels, void *d_records, void *d_recon, void *d_stats, hipStream_t s)
+{
+  QpRd &g = ctx->qprd;
+  if (((uintptr_t)d_records & 15) || ((uintptr_t)d_recon & 15) || ((uintptr_t)d_stats & 7)) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "DeltaQpRD: records and reconstruction must be 16-byte aligned, statistics 8-byte aligned");
+  TRY(ensure_qp_rd_trial(ctx));
+  g.last_frames = 0; g.h_rows.clear(); g.ev_sum.clear(); g.ev_keep.clear();
+  hevcdl_qp_rd_sum_params sp; memset(&sp, 0, sizeof sp);
+  sp.rows = g.d_rows; sp.ctus_per_frame = ctx->ctus; sp.n_frames = n_frames; sp.frame_lambda = g.frame_lambda;
+  hevcdl_qp_rd_keep_params kp; memset(&kp, 0, sizeof kp);
+  kp.src_records = g.d_records; kp.src_recon = g.d_recon; kp.src_stats = d_stats ? g.d_stats.p : nullptr;
+  kp.dst_records = (unsigned char *)d_records; kp.dst_recon = (unsigned char *)d_recon; kp.dst_stats = (unsigned char *)d_stats;
+  kp.rows = g.d_rows; kp.rec16 = ctx->records_bytes(1) / 16; kp.pic16 = kp.rec16 + ctx->frame_bytes / 16; kp.n_frames = n_frames;
+  for (int idx = 0; idx < g.count; idx++) {
+    const bool own = idx == 0;      // candidate 0 writes into the call's own buffers, the others into the trial set
+    TRY(launch_rd(ctx, d_yuv, n_frames, d_labels, own ? d_records : (void *)g.d_records.p, own ? d_recon : (void *)g.d_recon.p, d_stats ? (own ? d_stats : (void *)g.d_stats.p) : nullptr, s,
+                  0, -1, nullptr, nullptr, 0, -1, -1, &g.cand[idx]));
+    sp.records = own ? (const unsigned char *)d_records : g.d_records.p; sp.idx = idx;
+    prof_begin(ctx, g.ev_sum, s); hevcdl_launch_qp_rd_sum(&sp, s); prof_end(ctx, g.ev_sum, s); g.launches++;
+    if (!own) { prof_begin(ctx, g.ev_keep, s); hevcdl_launch_qp_rd_keep(&kp, s); prof_end(ctx, g.ev_keep, s); g.launches++; }
+    HIPCHK(hipGetLastError());
+  }
+  g.last_frames = n_frames;
+  return HEVCDL_OK;
+}
+
 // caller-supplied labels (device copy): boundary clamp + quadtree consistency in place; labels above 3 -> HEVCDL_ERR_INVALID_ARG
 extern "C" hevcdl_status hevcdl_clamp_labels_dev(hevcdl_ctx *ctx, void *d_labels, int n_frames, void *stream)
 {
@@ -691,6 +742,7 @@ extern "C" hevcdl_status hevcdl_compress_frames_dev(hevcdl_ctx *ctx, const void 
 {
   FRAMES_OR_RETURN(ctx, n_frames);
   if (!d_yuv || !d_labels || !d_records || !d_recon) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null device pointer");
+  if (ctx->qprd.n) return qp_rd_search(ctx, d_yuv, n_frames, d_labels, d_records, d_recon, d_stats, (hipStream_t)stream);
   return launch_rd(ctx, d_yuv, n_frames, d_labels, d_records, d_recon, d_stats, (hipStream_t)stream);
 }
 
@@ -698,6 +750,7 @@ extern "C" hevcdl_status hevcdl_compress_tiles_dev(hevcdl_ctx *ctx, const void *
                                                    int tile_begin, int tile_count, void *stream)
 {
   TRY(check_frames(ctx, n_frames));
+  if (ctx->qprd.n) return fail(ctx, HEVCDL_ERR_UNSUPPORTED, "compress_tiles: DeltaQpRD picks a QP per picture from the sums of ALL its tiles; a range of tiles cannot (use hevcdl_compress_frames_dev)");
   if (tile_begin < 0 || tile_count < 0 || tile_begin + tile_count > ctx->cfg.tile_columns * ctx->cfg.tile_rows) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "tile range outside the tile grid");
   if (n_frames == 0 || tile_count == 0) return HEVCDL_OK;
   if (!d_yuv || !d_labels || !d_records || !d_recon) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null device pointer");
@@ -791,6 +844,7 @@ extern "C" hevcdl_status hevcdl_reserve_workspace(hevcdl_ctx *ctx)
 {
   if (!ctx) return HEVCDL_ERR_INVALID_ARG;
   HIPCHK(hipSetDevice(ctx->cfg.device));
+  if (ctx->qprd.n) TRY(ensure_qp_rd_trial(ctx));      // DeltaQpRD: the trial set is part of what the decisions need
   const size_t need = ctx->rd.scratch_per_wave * rd_largest_scratch_blocks(ctx->rd.plan);
   if (need <= ctx->rd.scratch_bytes) return HEVCDL_OK;
   HIPCHK(hipDeviceSynchronize());
@@ -858,34 +912,52 @@ static hevcdl_status compress_frames_staged(hevcdl_ctx *ctx, int n_frames, const
 
 // ---- deblocking (row f-2, first half): TComLoopFilter::loopFilterPic, TComLoopFilter.cpp:130, called at TEncGOP.cpp:1742 ----
 // tc / beta / chroma tc of a picture filtered with (beta_offset_div2, tc_offset_div2): TComLoopFilter.cpp:59-67 (the tables: csrc/dbk_select.h), :623-624, 782-804, Bs 2
-static void dbk_triple(const hevcdl_ctx *ctx, int beta_offset_div2, int tc_offset_div2, int *tc, int *beta, int *tc_c)
+// qp: the picture's slice QP (the cfg's, or with DeltaQpRD the one the picture was coded with)
+static void dbk_triple(const hevcdl_ctx *ctx, int qp, int beta_offset_div2, int tc_offset_div2, int *tc, int *beta, int *tc_c)
 {
-  const int qp = ctx->cfg.qp, qpc = CHROMA_SCALE_420[qp < 0 ? 0 : (qp > 57 ? 57 : qp)];      // TComLoopFilter.cpp:782-797, cQpOffset 0
+  const int qpc = HEVCDL_CHROMA_SCALE_420[qp < 0 ? 0 : (qp > 57 ? 57 : qp)];      // TComLoopFilter.cpp:782-797, cQpOffset 0
   const int bd_scale = 1 << (ctx->cfg.bit_depth - 8);                                       // iBitdepthScale, TComLoopFilter.cpp:596, 770
   const int tco = 2 * tc_offset_div2, bo = 2 * beta_offset_div2;   // slice_tc_offset_div2 / slice_beta_offset_div2 << 1 (TComLoopFilter.cpp:623-624, 804), Bs 2
   auto clipi = [](int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); };
   *tc = HEVCDL_DBK_TC[clipi(qp + 2 + tco, 53)] * bd_scale; *beta = HEVCDL_DBK_BETA[clipi(qp + bo, 51)] * bd_scale; *tc_c = HEVCDL_DBK_TC[clipi(qpc + 2 + tco, 53)] * bd_scale;
 }
 
+// idx: NULL, or the candidate of the QP search every picture was coded with (DeltaQpRD)
+static hevcdl_status check_qp_rd_idx(hevcdl_ctx *ctx, const int32_t *idx, int n_frames)
+{
+  for (int i = 0; idx && i < n_frames; i++) if (idx[i] < 0 || idx[i] >= ctx->qprd.count) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "a picture's candidate index lies outside the context's table (0 .. 2 DeltaQpRD)");
+  return HEVCDL_OK;
+}
+
 extern "C" hevcdl_status hevcdl_deblock_frames_choice_dev(hevcdl_ctx *ctx, const void *d_recon, int n_frames, const void *d_records, const hevcdl_dbk_choice *choices, void *d_out, void *stream)
 {
+  return hevcdl_deblock_frames_qp_dev(ctx, d_recon, n_frames, d_records, choices, nullptr, d_out, stream);
+}
+
+extern "C" hevcdl_status hevcdl_deblock_frames_qp_dev(hevcdl_ctx *ctx, const void *d_recon, int n_frames, const void *d_records, const hevcdl_dbk_choice *choices, const int32_t *idx, void *d_out, void *stream)
+{
   FRAMES_OR_RETURN(ctx, n_frames);
+  TRY(check_qp_rd_idx(ctx, idx, n_frames));
   if (!d_recon || !d_records || !d_out) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null device pointer");
   hevcdl_dbk_params p;
   p.in = (const uint8_t *)d_recon; p.out = (uint8_t *)d_out; p.records = (const unsigned char *)d_records;
   p.width = ctx->cfg.width; p.height = ctx->cfg.height; p.ctus_x = ctx->ctus_x; p.ctus_per_frame = ctx->ctus; p.n_frames = n_frames;
-  dbk_triple(ctx, ctx->cfg.lf_beta_offset_div2, ctx->cfg.lf_tc_offset_div2, &p.tc, &p.beta, &p.tc_c);
+  dbk_triple(ctx, ctx->cfg.qp, ctx->cfg.lf_beta_offset_div2, ctx->cfg.lf_tc_offset_div2, &p.tc, &p.beta, &p.tc_c);
   p.pel_max = (1 << ctx->cfg.bit_depth) - 1;
   p.lf_across_tiles = ctx->cfg.lf_across_tiles != 0; p.tile_cols = ctx->cfg.tile_columns; p.tile_rows = ctx->cfg.tile_rows;
   memcpy(p.col_bd, ctx->col_bd, sizeof p.col_bd); memcpy(p.row_bd, ctx->row_bd, sizeof p.row_bd);
   p.frame_params = nullptr;
-  if (choices) { // a row of (tc, beta, tc_c, disabled) per picture, uploaded in front of the launch on its stream (the host copy lives in the context until the next call)
-    for (int i = 0; i < n_frames; i++)
+  if (choices || idx) { // a row of (tc, beta, tc_c, disabled) per picture, uploaded in front of the launch on its stream (the host copy lives in the context until the next call)
+    for (int i = 0; choices && i < n_frames; i++)
       if (choices[i].beta_offset_div2 < -6 || choices[i].beta_offset_div2 > 6 || choices[i].tc_offset_div2 < -6 || choices[i].tc_offset_div2 > 6) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "a picture's deblocking offsets are out of range (-6 .. 6)");
     TRY(lazy_alloc(ctx, ctx->dbk.d_frame_params, sizeof(int) * 4 * (size_t)ctx->cfg.max_frames, "per-picture deblocking parameters (cfg.max_frames)"));
     std::vector<int> &h = ctx->dbk.h_frame_params;
     h.assign((size_t)4 * n_frames, 0);
-    for (int i = 0; i < n_frames; i++) { dbk_triple(ctx, choices[i].beta_offset_div2, choices[i].tc_offset_div2, &h[4 * i], &h[4 * i + 1], &h[4 * i + 2]); h[4 * i + 3] = choices[i].disabled != 0; }
+    for (int i = 0; i < n_frames; i++) {
+      const int qp = idx ? ctx->qprd.cand[idx[i]].qp : ctx->cfg.qp;
+      dbk_triple(ctx, qp, choices ? choices[i].beta_offset_div2 : ctx->cfg.lf_beta_offset_div2, choices ? choices[i].tc_offset_div2 : ctx->cfg.lf_tc_offset_div2, &h[4 * i], &h[4 * i + 1], &h[4 * i + 2]);
+      h[4 * i + 3] = choices && choices[i].disabled != 0;
+    }
     HIPCHK(hipMemcpyAsync(ctx->dbk.d_frame_params, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice, (hipStream_t)stream));
     p.frame_params = ctx->dbk.d_frame_params;
   }
@@ -905,12 +977,17 @@ extern "C" hevcdl_status hevcdl_deblock_frames(hevcdl_ctx *ctx, const uint8_t *r
 
 extern "C" hevcdl_status hevcdl_deblock_frames_choice(hevcdl_ctx *ctx, const uint8_t *recon, int n_frames, const hevcdl_ctu_record *records, const hevcdl_dbk_choice *choices, uint8_t *out)
 {
+  return hevcdl_deblock_frames_qp(ctx, recon, n_frames, records, choices, nullptr, out);
+}
+
+extern "C" hevcdl_status hevcdl_deblock_frames_qp(hevcdl_ctx *ctx, const uint8_t *recon, int n_frames, const hevcdl_ctu_record *records, const hevcdl_dbk_choice *choices, const int32_t *idx, uint8_t *out)
+{
   FRAMES_OR_RETURN(ctx, n_frames);
   if (!recon || !records || !out) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null pointer");
   TRY(ensure_staging(ctx));
   HIPCHK(hipMemcpy(ctx->stage.d_recon, recon, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(ctx->stage.d_records, records, ctx->records_bytes(n_frames), hipMemcpyHostToDevice));
-  TRY(hevcdl_deblock_frames_choice_dev(ctx, ctx->stage.d_recon, n_frames, ctx->stage.d_records, choices, ctx->stage.d_yuv, nullptr));   // d_yuv: free staging plane set
+  TRY(hevcdl_deblock_frames_qp_dev(ctx, ctx->stage.d_recon, n_frames, ctx->stage.d_records, choices, idx, ctx->stage.d_yuv, nullptr));   // d_yuv: free staging plane set
   TRY(sync_or_fail(ctx, "deblock kernels"));
   HIPCHK(hipMemcpy(out, ctx->stage.d_yuv, ctx->frame_bytes * n_frames, hipMemcpyDeviceToHost));
   return HEVCDL_OK;
@@ -971,7 +1048,7 @@ extern "C" hevcdl_status hevcdl_dbk_trial_frames_dev(hevcdl_ctx *ctx, const void
   q.org = (const uint8_t *)d_org; q.table = d_tables; q.shift = 2 * (ctx->cfg.bit_depth - 8);
   for (int b = -3; b <= 3; b++) for (int t = -3; t <= 3; t++) { // the distinct (tc, beta) pairs of luma and the distinct chroma tc values (a function of t alone)
     int tc, beta, tc_c;
-    dbk_triple(ctx, b, t, &tc, &beta, &tc_c);
+    dbk_triple(ctx, ctx->cfg.qp, b, t, &tc, &beta, &tc_c);
     const int e = 7 * (b + 3) + (t + 3);
     int j = 0; while (j < q.n_luma && (q.tc[j] != tc || q.beta[j] != beta)) j++;
     if (j == q.n_luma) { q.tc[j] = tc; q.beta[j] = beta; q.n_luma++; }
@@ -1026,7 +1103,25 @@ extern "C" hevcdl_status hevcdl_get_dbk_choice(hevcdl_ctx *ctx, int first, int c
 // ---- SAO (row f-2, second half): TEncSampleAdaptiveOffset::SAOProcess, TEncSampleAdaptiveOffset.cpp:244, called at TEncGOP.cpp:1797 ----
 extern "C" hevcdl_status hevcdl_sao_frames_dev(hevcdl_ctx *ctx, const void *d_org, const void *d_deblocked, int n_frames, void *d_params, void *d_out, void *stream)
 {
+  return hevcdl_sao_frames_qp_dev(ctx, d_org, d_deblocked, n_frames, nullptr, d_params, d_out, stream);
+}
+
+// the per-picture QP table of a batch (hevcdl_frame_qp) from the pictures' candidate indices, uploaded in front of the launches that read it on their stream (the host
+// copy lives in the context until the next call, like the deblocking rows)
+static hevcdl_status upload_frame_qp(hevcdl_ctx *ctx, const int32_t *idx, int n_frames, hipStream_t s)
+{
+  TRY(lazy_alloc(ctx, ctx->qprd.d_frame_qp, sizeof(hevcdl_frame_qp) * (size_t)ctx->cfg.max_frames, "per-picture QP table (cfg.max_frames)"));
+  std::vector<hevcdl_frame_qp> &h = ctx->qprd.h_frame_qp;
+  h.resize((size_t)n_frames);
+  for (int i = 0; i < n_frames; i++) { const hevcdl_qp_rd_candidate &c = ctx->qprd.cand[idx[i]]; h[(size_t)i] = hevcdl_frame_qp{ c.lambda, c.lambda_chroma, c.qp, 0 }; }      // slice lambdas per component, TEncSlice.cpp:112-140, 656-660
+  HIPCHK(hipMemcpyAsync(ctx->qprd.d_frame_qp, h.data(), sizeof(hevcdl_frame_qp) * h.size(), hipMemcpyHostToDevice, s));
+  return HEVCDL_OK;
+}
+
+extern "C" hevcdl_status hevcdl_sao_frames_qp_dev(hevcdl_ctx *ctx, const void *d_org, const void *d_deblocked, int n_frames, const int32_t *idx, void *d_params, void *d_out, void *stream)
+{
   FRAMES_OR_RETURN(ctx, n_frames);
+  TRY(check_qp_rd_idx(ctx, idx, n_frames));
   if (!d_org || !d_deblocked || !d_params || !d_out) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null device pointer");
   const size_t nf = (size_t)ctx->cfg.max_frames;
   TRY(lazy_alloc(ctx, ctx->sao.d_sao_stats, (size_t)ctx->ctus * 3 * 5 * 256 * nf, "SAO statistics (cfg.max_frames)"));
@@ -1039,11 +1134,18 @@ extern "C" hevcdl_status hevcdl_sao_frames_dev(hevcdl_ctx *ctx, const void *d_or
   p.lambda = ctx->cfg.lambda; p.lambda_chroma = ctx->cfg.lambda_chroma;          // slice lambdas per component, TEncSlice.cpp:112-140
   p.tile_cols = ctx->cfg.tile_columns; p.tile_rows = ctx->cfg.tile_rows; p.bit_depth = ctx->cfg.bit_depth; p.lf_across_tiles = ctx->cfg.lf_across_tiles != 0;
   memcpy(p.col_bd, ctx->col_bd, sizeof p.col_bd); memcpy(p.row_bd, ctx->row_bd, sizeof p.row_bd);
+  p.frame_qp = nullptr;
+  if (idx) { TRY(upload_frame_qp(ctx, idx, n_frames, (hipStream_t)stream)); p.frame_qp = ctx->qprd.d_frame_qp; }
   hevcdl_launch_sao(&p, stream);
   return launch_status(ctx);
 }
 
 extern "C" hevcdl_status hevcdl_sao_frames(hevcdl_ctx *ctx, const uint8_t *org, const uint8_t *deblocked, int n_frames, hevcdl_sao_blk *params, uint8_t *out)
+{
+  return hevcdl_sao_frames_qp(ctx, org, deblocked, n_frames, nullptr, params, out);
+}
+
+extern "C" hevcdl_status hevcdl_sao_frames_qp(hevcdl_ctx *ctx, const uint8_t *org, const uint8_t *deblocked, int n_frames, const int32_t *idx, hevcdl_sao_blk *params, uint8_t *out)
 {
   FRAMES_OR_RETURN(ctx, n_frames);
   if (!org || !deblocked || !params || !out) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null pointer");
@@ -1052,7 +1154,7 @@ extern "C" hevcdl_status hevcdl_sao_frames(hevcdl_ctx *ctx, const uint8_t *org, 
   HIPCHK(hipMemcpy(ctx->stage.d_yuv, org, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(ctx->stage.d_recon, deblocked, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
   // the records staging area is free here and large enough for one more picture set (15120 B per CTU >= 6144)
-  TRY(hevcdl_sao_frames_dev(ctx, ctx->stage.d_yuv, ctx->stage.d_recon, n_frames, ctx->sao.d_sao_params, ctx->stage.d_records, nullptr));
+  TRY(hevcdl_sao_frames_qp_dev(ctx, ctx->stage.d_yuv, ctx->stage.d_recon, n_frames, idx, ctx->sao.d_sao_params, ctx->stage.d_records, nullptr));
   TRY(sync_or_fail(ctx, "sao kernels"));
   HIPCHK(hipMemcpy(params, ctx->sao.d_sao_params, ctx->sao_bytes(n_frames), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(out, ctx->stage.d_records, ctx->frame_bytes * n_frames, hipMemcpyDeviceToHost));
@@ -1511,6 +1613,16 @@ static hevcdl_status encode_pictures_device(hevcdl_ctx *ctx, const void *yuv, in
   HIPCHK(hipMemcpy(ctx->stage.d_yuv, yuv, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
   TRY(stage_labels(ctx, labels_opt, n_frames));
   TRY(hevcdl_compress_frames_dev(ctx, ctx->stage.d_yuv, n_frames, ctx->stage.d_labels, ctx->stage.d_records, ctx->stage.d_recon, ctx->stage.d_stats, nullptr));
+  const int32_t *pic_idx = nullptr;      // DeltaQpRD: the candidate every picture ended with -- a few words a picture to the host, then every later stage runs with the picture's own QP
+  ctx->qprd.h_idx.clear();
+  if (ctx->qprd.n) {
+    std::vector<hevcdl_qp_rd_row> &rows = ctx->qprd.h_rows;
+    rows.resize((size_t)n_frames);
+    HIPCHK(hipMemcpy(rows.data(), ctx->qprd.d_rows, sizeof(hevcdl_qp_rd_row) * (size_t)n_frames, hipMemcpyDeviceToHost));      // (behind the launches of the null stream)
+    for (const hevcdl_qp_rd_row &r : rows) ctx->qprd.h_idx.push_back(r.best_idx);
+    TRY(check_qp_rd_idx(ctx, ctx->qprd.h_idx.data(), n_frames));
+    pic_idx = ctx->qprd.h_idx.data();
+  }
   if (windowed) { // the statistics' SSE (the reconstruction before the in-loop filters) over the window: the decision kernel summed over the padding too
     TRY(crop_window_dev(ctx, ctx->stage.d_recon, n_frames, ctx->src.d_win_pic, nullptr));
     hevcdl_quality_params q; quality_sized_params(ctx, &q, ww, wh);
@@ -1546,9 +1658,9 @@ static hevcdl_status encode_pictures_device(hevcdl_ctx *ctx, const void *yuv, in
       }
       TRY(hevcdl_deblock_frames_choice_dev(ctx, ctx->stage.d_recon, n_frames, ctx->stage.d_records, ch.data(), ctx->stage.d_recon, nullptr));      // in place
     } else
-    if (deblock) { TRY(hevcdl_deblock_frames_dev(ctx, ctx->stage.d_recon, n_frames, ctx->stage.d_records, ctx->stage.d_recon, nullptr)); }      // in place
+    if (deblock) { TRY(hevcdl_deblock_frames_qp_dev(ctx, ctx->stage.d_recon, n_frames, ctx->stage.d_records, nullptr, pic_idx, ctx->stage.d_recon, nullptr)); }      // in place (pic_idx NULL: hevcdl_deblock_frames_dev)
   }
-  if (want_sao) { TRY(hevcdl_sao_frames_dev(ctx, ctx->stage.d_yuv, ctx->stage.d_recon, n_frames, ctx->sao.d_sao_params, ctx->stage.d_picture, nullptr)); *d_final = ctx->stage.d_picture; }
+  if (want_sao) { TRY(hevcdl_sao_frames_qp_dev(ctx, ctx->stage.d_yuv, ctx->stage.d_recon, n_frames, pic_idx, ctx->sao.d_sao_params, ctx->stage.d_picture, nullptr)); *d_final = ctx->stage.d_picture; }
   ctx->q.h_quality.clear();
   ctx->rp.h_report.clear();
   if (windowed && (ctx->q.quality_on || ctx->rp.report_on)) { TRY(crop_window_dev(ctx, *d_final, n_frames, ctx->src.d_win_pic, nullptr)); }      // the output pictures' window (TEncGOP.cpp:2302-2303, 2375-2376, 2413-2414)
@@ -1792,11 +1904,14 @@ static hevcdl_status entropy_pipeline(hevcdl_ctx *ctx, int n_frames, int want_sa
   const size_t rec_b = ctx->records_bytes(1), sao_b = ctx->sao_bytes(1);
   ctx->ec.h_slice.clear(); ctx->ec.h_slice_sizes.assign((size_t)n_frames * units, 0); ctx->ec.h_slice_at.assign((size_t)n_frames + 1, 0); ctx->ec.ec_fallbacks = 0;
   std::vector<uint32_t> ovf; std::vector<unsigned long long> dst; std::vector<int> fallback;
+  const bool per_picture_qp = ctx->qprd.n != 0 && (int)ctx->qprd.h_idx.size() == n_frames;      // DeltaQpRD: the contexts of every picture start from its own QP
+  if (per_picture_qp) TRY(upload_frame_qp(ctx, ctx->qprd.h_idx.data(), n_frames, nullptr));
   for (int first = 0; first < n_frames; first += ctx->ec.ec_pass_frames) {
     const int cnt = std::min(ctx->ec.ec_pass_frames, n_frames - first); const size_t n_sub = (size_t)cnt * units;
     hevcdl_entropy_params k = pl.k;
     k.records = ctx->stage.d_records + rec_b * first; k.sao = want_sao ? ctx->sao.d_sao_params + sao_b * first : (unsigned char *)nullptr; k.tables = ctx->ec.d_ec_tables; k.out = ctx->ec.d_ec_ws;
     k.unit_off = ctx->ec.d_ec_off; k.unit_cap = ctx->ec.d_ec_cap; k.sizes = ctx->ec.d_ec_sizes; k.overflow = ctx->ec.d_ec_ovf; k.sync = ctx->ec.d_ec_sync; k.n_frames = cnt;
+    if (per_picture_qp) k.frame_qp = ctx->qprd.d_frame_qp.p + first;
     if (ev[0]) HIPCHK(hipEventRecord(ev[0], nullptr));
     hevcdl_launch_entropy(&k, nullptr, ev[1]);
     if (ev[2]) HIPCHK(hipEventRecord(ev[2], nullptr));
@@ -1845,6 +1960,7 @@ static hevcdl_status entropy_pipeline(hevcdl_ctx *ctx, int n_frames, int want_sa
         HIPCHK(hipMemcpy(rec.data(), ctx->stage.d_records + rec_b * f, rec_b, hipMemcpyDeviceToHost));
         if (want_sao) HIPCHK(hipMemcpy(sao.data(), ctx->sao.d_sao_params + sao_b * f, sao_b, hipMemcpyDeviceToHost));
         size_t total = 0; uint32_t *sz = ctx->ec.h_slice_sizes.data() + (size_t)f * units;
+        if (per_picture_qp) sc.qp = ctx->qprd.cand[ctx->qprd.h_idx[(size_t)f]].qp;
         hevcdl_host_writer_slice_data(&sc, &ctx->slices, &ctx->segments, rec.data(), want_sao ? sao.data() : nullptr, nullptr, 0, sz, &total);
         all.resize(at[(size_t)f] + total);
         if (hevcdl_host_writer_slice_data(&sc, &ctx->slices, &ctx->segments, rec.data(), want_sao ? sao.data() : nullptr, all.data() + at[(size_t)f], total, sz, &total) != 0) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "device entropy: host fallback");
@@ -1915,6 +2031,7 @@ extern "C" hevcdl_status hevcdl_begin_frames(hevcdl_ctx *ctx, const uint8_t *yuv
 {
   TRY(check_frames(ctx, n_frames));
   if (ctx->slices.mode != 0) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "begin_frames: the per-CTU session does not code slices; use hevcdl_compress_frames");
+  if (ctx->qprd.n) return fail(ctx, HEVCDL_ERR_UNSUPPORTED, "begin_frames: the per-CTU session does not search the slice QP (DeltaQpRD codes every picture 2N+1 times); use hevcdl_compress_frames");
   if (n_frames == 0 || !yuv) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "begin_frames: no frames");
   TRY(ensure_staging(ctx));
   TRY(lazy_alloc(ctx, ctx->ses.d_cabac, sizeof(hevcdl_cabac_state) * (size_t)ctx->cfg.max_frames, "coder states of the per-CTU session (cfg.max_frames)"));
@@ -1960,6 +2077,94 @@ extern "C" hevcdl_status hevcdl_get_recon(hevcdl_ctx *ctx, int frame, uint8_t *r
   if (frame < 0 || frame >= ctx->ses.session_frames || !recon) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "get_recon: frame outside the session / null pointer");
   HIPCHK(hipSetDevice(ctx->cfg.device));
   HIPCHK(hipMemcpy(recon, ctx->stage.d_recon + ctx->frame_bytes * frame, ctx->frame_bytes, hipMemcpyDeviceToHost));
+  return HEVCDL_OK;
+}
+
+// ---- DeltaQpRD: the public side (the search itself: qp_rd_search above) ------------------------------------------------------------------------------------------------
+extern "C" hevcdl_status hevcdl_qp_rd_candidates(const hevcdl_config *cfg, hevcdl_qp_rd_candidate *out, int capacity, int *count, double *frame_lambda)
+{
+  if (!cfg || !out || !count || !frame_lambda || cfg->delta_qp_rd < 0 || cfg->delta_qp_rd > HEVCDL_QP_RD_MAX_N || capacity < 2 * cfg->delta_qp_rd + 1 || cfg->qp < 0 || cfg->qp > 51) return HEVCDL_ERR_INVALID_ARG;
+  if ((cfg->bit_depth != 8 && cfg->bit_depth != 10) || (cfg->bit_depth > 8 && cfg->qp - cfg->delta_qp_rd < 0)) return HEVCDL_ERR_UNSUPPORTED;
+  const int n = hevcdl_qp_rd_table(cfg->qp, cfg->delta_qp_rd, cfg->bit_depth, out, frame_lambda);
+  if (n < 1) return HEVCDL_ERR_INVALID_ARG;
+  *count = n;
+  return HEVCDL_OK;
+}
+
+extern "C" int hevcdl_qp_rd_pick_index(const uint64_t *bits, const uint64_t *dist, int n, double frame_lambda)
+{
+  return !bits || !dist || n < 1 ? -1 : hevcdl_qp_rd_pick(bits, dist, n, frame_lambda);
+}
+
+extern "C" hevcdl_status hevcdl_get_qp_rd(hevcdl_ctx *ctx, int first, int count, hevcdl_qp_rd_row *rows, int32_t *qps_opt)
+{
+  if (!ctx) return HEVCDL_ERR_INVALID_ARG;
+  TRY(check_batch_range(ctx, "hevcdl_get_qp_rd", rows != nullptr, ctx->qprd.n != 0, "hevcdl_create with cfg.delta_qp_rd", first, count, (long long)ctx->qprd.last_frames));
+  if (count == 0) return HEVCDL_OK;
+  if ((int)ctx->qprd.h_rows.size() == ctx->qprd.last_frames) memcpy(rows, ctx->qprd.h_rows.data() + first, sizeof(hevcdl_qp_rd_row) * (size_t)count);      // a picture pipeline fetched them
+  else {
+    TRY(sync_or_fail(ctx, "hevcdl_get_qp_rd"));
+    HIPCHK(hipMemcpy(rows, ctx->qprd.d_rows.p + first, sizeof(hevcdl_qp_rd_row) * (size_t)count, hipMemcpyDeviceToHost));
+  }
+  for (int i = 0; i < count; i++) {
+    if (rows[i].best_idx < 0 || rows[i].best_idx >= ctx->qprd.count) return fail(ctx, HEVCDL_ERR_HIP, "hevcdl_get_qp_rd: a row's index lies outside the candidate table");
+    if (qps_opt) qps_opt[i] = ctx->qprd.cand[rows[i].best_idx].qp;
+  }
+  return HEVCDL_OK;
+}
+
+static double sum_event_pairs(std::vector<Event> &v, unsigned *pairs_opt);
+extern "C" hevcdl_status hevcdl_get_qp_rd_info(hevcdl_ctx *ctx, size_t *trial_bytes, uint64_t *kernel_launches, double *kernel_ms_opt)
+{
+  if (!ctx || !trial_bytes || !kernel_launches) return HEVCDL_ERR_INVALID_ARG;
+  *trial_bytes = ctx->qprd.d_rows ? ctx->qprd.trial_bytes : 0; *kernel_launches = ctx->qprd.launches;
+  if (kernel_ms_opt) { // HIP-event times of the sum and the keep launches of the last search, each summed over its candidates; zeros without hevcdl_profile_enable
+    TRY(sync_or_fail(ctx, "hevcdl_get_qp_rd_info"));
+    kernel_ms_opt[0] = sum_event_pairs(ctx->qprd.ev_sum, nullptr); kernel_ms_opt[1] = sum_event_pairs(ctx->qprd.ev_keep, nullptr);
+  }
+  return HEVCDL_OK;
+}
+
+// the two kernels alone (host buffers, no context): the destinations travel with their guard margins, so that a write outside a payload shows in what comes back
+extern "C" hevcdl_status hevcdl_qp_rd_step(int device, int ctus_per_frame, size_t frame_bytes, int n_frames, int idx, double frame_lambda, const hevcdl_ctu_record *trial_records,
+                                           const void *trial_recon, const hevcdl_frame_stats *trial_stats, hevcdl_qp_rd_row *rows, void *records, void *recon, void *stats, size_t guard_bytes)
+{
+  if (ctus_per_frame < 1 || n_frames < 1 || n_frames > 65535 || idx < 0 || idx >= HEVCDL_QP_RD_MAX_CANDIDATES || (frame_bytes & 15) || (guard_bytes & 15) || !trial_records || !rows) return HEVCDL_ERR_INVALID_ARG;
+  if (idx > 0 && (!trial_recon || !trial_stats || !records || !recon || !stats)) return HEVCDL_ERR_INVALID_ARG;
+  TRY(select_device(device));
+  const size_t nf = (size_t)n_frames, rec_b = sizeof(hevcdl_ctu_record) * (size_t)ctus_per_frame * nf, pic_b = frame_bytes * nf, stat_b = sizeof(hevcdl_frame_stats) * nf, row_b = sizeof(hevcdl_qp_rd_row) * nf;
+  const size_t g = guard_bytes;
+  DevBuf<unsigned char> t_rec, t_pic, t_stat, d_rec, d_pic, d_stat; DevBuf<hevcdl_qp_rd_row> d_rows;
+  TRY(alloc_all(nullptr, { want(t_rec, rec_b), want(t_pic, pic_b + 16), want(t_stat, stat_b), want(d_rec, rec_b + 2 * g), want(d_pic, pic_b + 2 * g + 16), want(d_stat, stat_b + 2 * g), want(d_rows, row_b) }, ""));
+  hipError_t e = hipMemcpy(t_rec, trial_records, rec_b, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_rows, rows, row_b, hipMemcpyHostToDevice);
+  if (e == hipSuccess && idx > 0) {
+    if (pic_b) e = hipMemcpy(t_pic, trial_recon, pic_b, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(t_stat, trial_stats, stat_b, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_rec, records, rec_b + 2 * g, hipMemcpyHostToDevice);
+    if (e == hipSuccess && pic_b + 2 * g) e = hipMemcpy(d_pic, recon, pic_b + 2 * g, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_stat, stats, stat_b + 2 * g, hipMemcpyHostToDevice);
+  }
+  if (e == hipSuccess) {
+    hevcdl_qp_rd_sum_params sp; memset(&sp, 0, sizeof sp);
+    sp.records = t_rec; sp.rows = d_rows; sp.ctus_per_frame = ctus_per_frame; sp.n_frames = n_frames; sp.idx = idx; sp.frame_lambda = frame_lambda;
+    hevcdl_launch_qp_rd_sum(&sp, nullptr);
+    if (idx > 0) {
+      hevcdl_qp_rd_keep_params kp; memset(&kp, 0, sizeof kp);
+      kp.src_records = t_rec; kp.src_recon = t_pic; kp.src_stats = t_stat; kp.dst_records = d_rec + g; kp.dst_recon = d_pic + g; kp.dst_stats = d_stat + g;
+      kp.rows = d_rows; kp.rec16 = sizeof(hevcdl_ctu_record) * (size_t)ctus_per_frame / 16; kp.pic16 = kp.rec16 + frame_bytes / 16; kp.n_frames = n_frames;
+      hevcdl_launch_qp_rd_keep(&kp, nullptr);
+    }
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(rows, d_rows, row_b, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && idx > 0) {
+      e = hipMemcpy(records, d_rec, rec_b + 2 * g, hipMemcpyDeviceToHost);
+      if (e == hipSuccess && pic_b + 2 * g) e = hipMemcpy(recon, d_pic, pic_b + 2 * g, hipMemcpyDeviceToHost);
+      if (e == hipSuccess) e = hipMemcpy(stats, d_stat, stat_b + 2 * g, hipMemcpyDeviceToHost);
+    }
+  }
+  if (e != hipSuccess) return hip_fail(nullptr, "", e);
   return HEVCDL_OK;
 }
 

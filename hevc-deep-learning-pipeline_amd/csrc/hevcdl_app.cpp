@@ -34,6 +34,7 @@
 #include <vector>
 #include "hevcdl.h"
 #include "slice_grid.h"      // hevcdl_segment_keys: the segment keys are refused here with the library's own sentences
+#include "qp_rd.h"           // hevcdl_qp_rd_keys: likewise DeltaQpRD
 
 namespace {
 
@@ -55,7 +56,7 @@ const Key KEYS[] = {
   { "InputColourSpaceConvert", 0, USED, 0 }, { "OutputInternalColourSpace", 0, USED, 0 }, { "SNRInternalColourSpace", 0, USED, 0 }, { "TemporalSubsampleRatio", "ts", USED, 0 },
   { "MaxCUWidth", 0, PATH, "64" }, { "MaxCUHeight", 0, PATH, "64" }, { "MaxPartitionDepth", 0, PATH, "4" },
   { "QuadtreeTULog2MaxSize", 0, PATH, "5" }, { "QuadtreeTULog2MinSize", 0, PATH, "2" }, { "QuadtreeTUMaxDepthIntra", 0, PATH, "3" },
-  { "IntraPeriod", 0, PATH, "1" }, { "GOPSize", 0, PATH, "1" }, { "MaxDeltaQP", 0, PATH, "0" }, { "DeltaQpRD", 0, PATH, "0" },
+  { "IntraPeriod", 0, PATH, "1" }, { "GOPSize", 0, PATH, "1" }, { "MaxDeltaQP", 0, PATH, "0" }, { "DeltaQpRD", "dqr", USED, 0 },      // (DeltaQpRD: 0 .. 6, the slice QP of every picture picked among 2N+1 candidate encodes)
   { "RDOQ", 0, USED, 0 }, { "RDOQTS", 0, USED, 0 }, { "TransformSkip", 0, USED, 0 }, { "TransformSkipFast", 0, USED, 0 },
   { "SignHideFlag", "SBH", USED, 0 }, { "StrongIntraSmoothing", 0, USED, 0 }, { "FastUDIUseMPMEnabled", 0, USED, 0 },      // tool switches (hevcdl_config.tools): 0 or 1
   { "SliceMode", 0, USED, 0 }, { "SliceArgument", 0, USED, 0 }, { "SliceSegmentMode", 0, USED, 0 }, { "SliceSegmentArgument", 0, USED, 0 }, { "PCMEnabledFlag", 0, PATH, "0" }, { "NumTileColumnsMinus1", 0, USED, 0 },
@@ -352,8 +353,19 @@ int main(int argc, char **argv)
     const char *why = "";
     if (hevcdl_segment_keys(&probe, &why) != HEVCDL_OK) opt.errors.push_back("SliceSegmentMode = " + std::to_string(seg_mode) + ", SliceSegmentArgument = " + std::to_string(seg_arg) + ": " + why);
   }
+  // DeltaQpRD (TAppEncCfg.cpp:897, "-dqr"): every picture is decided at QP, QP - 1, QP + 1, ... QP + N and the cheapest candidate is kept (TEncSlice::precompressSlice).
+  // What hevcdl_create refuses is refused here in its words (csrc/qp_rd.h).
+  const long delta_qp_rd = opt.geti("DeltaQpRD", 0);
+  if (delta_qp_rd != 0) {
+    hevcdl_config probe; memset(&probe, 0, sizeof probe);
+    probe.qp = qp; probe.bit_depth = bit_depth; probe.deblocking_metric = (int)dbk_metric; probe.slice_mode = (int)slice_mode; probe.slice_segment_mode = (int)seg_mode; probe.delta_qp_rd = (int)delta_qp_rd;
+    const char *why = "";
+    if (delta_qp_rd < -1000 || delta_qp_rd > 1000) probe.delta_qp_rd = -1;
+    if (hevcdl_qp_rd_keys(&probe, &why) != HEVCDL_OK) opt.errors.push_back("DeltaQpRD = " + std::to_string(delta_qp_rd) + ": " + why);
+  }
   if (opt.v.count("PrintConfig")) {
-    printf("{\"SliceMode\": %ld, \"SliceArgument\": %ld, \"LFCrossSliceBoundaryFlag\": %ld, \"SliceSegmentMode\": %ld, \"SliceSegmentArgument\": %ld, ", slice_mode, slice_arg, lf_slices, seg_mode, seg_arg);
+    printf("{\"DeltaQpRD\": %ld, ", delta_qp_rd);
+    printf("\"SliceMode\": %ld, \"SliceArgument\": %ld, \"LFCrossSliceBoundaryFlag\": %ld, \"SliceSegmentMode\": %ld, \"SliceSegmentArgument\": %ld, ", slice_mode, slice_arg, lf_slices, seg_mode, seg_arg);
     printf("\"InputFile\": \"%s\", \"ReconFile\": \"%s\", \"SourceWidth\": %d, \"SourceHeight\": %d, \"QP\": %d, \"FrameSkip\": %ld, \"FramesToBeEncoded\": %ld, "
            "\"FrameRate\": %g, \"LabelDir\": \"%s\", \"CnnInput\": \"%s\", \"BitstreamFile\": \"%s\", \"level_idc\": %d, \"tiles\": [%d, %d], \"bit_depth\": %d, "
            "\"ConformanceWindowMode\": %d, \"HorizontalPadding\": %d, \"VerticalPadding\": %d, \"InputBitDepth\": %d, \"InternalBitDepth\": %d, \"OutputBitDepth\": %d, \"coded_size\": [%d, %d], "
@@ -449,6 +461,7 @@ int main(int argc, char **argv)
   cfg.deblocking_metric = (int)dbk_metric; cfg.lf_offset_in_pps = (int)lf_in_pps;
   cfg.slice_mode = (int)slice_mode; cfg.slice_argument = (int)slice_arg; cfg.lf_across_slices = (int)lf_slices;
   cfg.slice_segment_mode = (int)seg_mode; cfg.slice_segment_argument = (int)seg_arg;
+  cfg.delta_qp_rd = (int)delta_qp_rd;
   cfg.cnn_input = cnn_input == "luma" ? HEVCDL_CNN_INPUT_LUMA : HEVCDL_CNN_INPUT_RGB601;
   cfg.bn_mode = bn_mode == "eval" ? HEVCDL_BN_EVAL : HEVCDL_BN_REFERENCE;
   if (shared_device) cfg.exec_flags |= HEVCDL_EXEC_NO_UNIT_HANDOVER;
@@ -467,11 +480,11 @@ int main(int argc, char **argv)
   struct Shard {
     int dev = 0; long f_lo = 0, f_hi = 0; hevcdl_ctx *ctx = nullptr; int batch = 1; int rc = 0;
     double t_read = 0, t_dev = 0, t_host = 0, t_write = 0;
-    std::vector<unsigned long long> rows;       // per coded picture: { poc, bits, sse Y, sse U, sse V, ctus, encode ns, device }  (what the devices gather); PrintMSSSIM: + the three MS-SSIM doubles' bit patterns
+    std::vector<unsigned long long> rows;       // per coded picture: { poc, bits, sse Y, sse U, sse V, ctus, encode ns, device, slice QP }  (what the devices gather); PrintMSSSIM: + the three MS-SSIM doubles' bit patterns
     std::vector<std::vector<uint8_t>> aus;      // multi-device runs: the access units (+ hash SEI) of the block, written out in POC order at the end
     std::vector<std::string> md5;
   };
-  const int ROW = print_msssim ? 11 : 8;
+  const int ROW = print_msssim ? 12 : 9;
   std::vector<Shard> shards(n_shards);
   for (int i = 0; i < n_shards; i++) { shards[i].dev = devices[i]; shards[i].f_lo = (long)i * n_frames / n_shards; shards[i].f_hi = (long)(i + 1) * n_frames / n_shards; }
   for (int i = 0; i < n_shards; i++) { // contexts: created one after the other (a refused allocation halves the batch of every shard)
@@ -558,12 +571,13 @@ int main(int argc, char **argv)
   const double maxval = (double)(255 << (bit_depth - 8));
   // one picture's log line and its share of the summary (TEncGOP.cpp:2500-2541; PSNR from the squared error as TEncGOP.cpp:2391-2394)
   // msssim_bits: the picture's three MS-SSIM values as bit patterns (PrintMSSSIM), or null
-  auto log_picture = [&](long poc, unsigned long long bits, const unsigned long long *sse, double et, const char *md5_text, const unsigned long long *msssim_bits) {
+  // pic_qp: the slice QP the picture was coded with (the cfg's, or with DeltaQpRD the candidate kept for it)
+  auto log_picture = [&](long poc, int pic_qp, unsigned long long bits, const unsigned long long *sse, double et, const char *md5_text, const unsigned long long *msssim_bits) {
     const double p[3] = { psnr_of(sse[0], ny, maxval), psnr_of(sse[1], nc, maxval), psnr_of(sse[2], nc, maxval) };
     if (!print_msssim && !print_frame_mse)
-      printf("POC %4ld TId: %1d ( %c-SLICE, QP %d ) %10llu bits [Y %6.4lf dB    U %6.4lf dB    V %6.4lf dB] [ET %5.0f ]%s\n", poc, 0, 'I', qp, bits, p[0], p[1], p[2], et, md5_text);
+      printf("POC %4ld TId: %1d ( %c-SLICE, QP %d ) %10llu bits [Y %6.4lf dB    U %6.4lf dB    V %6.4lf dB] [ET %5.0f ]%s\n", poc, 0, 'I', pic_qp, bits, p[0], p[1], p[2], et, md5_text);
     else { // the groups of TEncGOP.cpp:2522-2537 between the PSNR group and [ET
-      printf("POC %4ld TId: %1d ( %c-SLICE, QP %d ) %10llu bits [Y %6.4lf dB    U %6.4lf dB    V %6.4lf dB]", poc, 0, 'I', qp, bits, p[0], p[1], p[2]);
+      printf("POC %4ld TId: %1d ( %c-SLICE, QP %d ) %10llu bits [Y %6.4lf dB    U %6.4lf dB    V %6.4lf dB]", poc, 0, 'I', pic_qp, bits, p[0], p[1], p[2]);
       if (print_msssim) {
         double m[3]; memcpy(m, msssim_bits, sizeof m);
         printf(" [MS-SSIM Y %1.6lf    U %1.6lf    V %1.6lf]", m[0], m[1], m[2]);
@@ -606,10 +620,17 @@ int main(int argc, char **argv)
       if (device_report) { const hevcdl_status rst = hevcdl_get_picture_report(S.ctx, first, count, reports.data()); if (rst != HEVCDL_OK) { fprintf(stderr, "Error: %s (status %d)\n", hevcdl_last_error(S.ctx), (int)rst); S.rc = 3; return 1; } }
       std::vector<hevcdl_dbk_choice> choices(count);          // what every picture's slice header says about its deblocking filter (the cfg's values, or the metric's)
       { const hevcdl_status cst = hevcdl_get_dbk_choice(S.ctx, first, count, choices.data()); if (cst != HEVCDL_OK) { fprintf(stderr, "Error: %s (status %d)\n", hevcdl_last_error(S.ctx), (int)cst); S.rc = 3; return 1; } }
+      std::vector<int32_t> pic_qps((size_t)count, qp);      // DeltaQpRD: the QP every picture of the chunk was coded with -- its slice_qp_delta and its log line
+      if (delta_qp_rd) {
+        std::vector<hevcdl_qp_rd_row> qrows((size_t)count);
+        const hevcdl_status qst = hevcdl_get_qp_rd(S.ctx, first, count, qrows.data(), pic_qps.data());
+        if (qst != HEVCDL_OK) { fprintf(stderr, "Error: %s (status %d)\n", hevcdl_last_error(S.ctx), (int)qst); S.rc = 3; return 1; }
+      }
       {
         std::atomic<int> next(0);
         auto work = [&]() {
           std::vector<uint8_t> buf(hevcdl_access_unit_bound_segments(width, height, &slices, &segments));
+          hevcdl_stream_config pcfg = scfg;      // the access unit's own copy: its qp is the picture's
           for (int i = next++; i < count; i = next++) {
             if (slice_data && buf.size() < slice_at[(size_t)i + 1] - slice_at[(size_t)i] + 4096) buf.resize(2 * (slice_at[(size_t)i + 1] - slice_at[(size_t)i]) + 4096);
             PicOut &po = pics[i]; po.md5_text[0] = 0;
@@ -649,8 +670,9 @@ int main(int argc, char **argv)
             }
             if (file_order && coded_order) std::swap(po.sse[1], po.sse[2]);
             // the access unit: VPS+SPS+PPS+slice, written to -b; its size is the picture's bit count (TEncGOP.cpp:2420-2447)
-            if (slice_data) po.st = hevcdl_write_access_unit_from_slice_data_segments(&scfg, &slices, &segments, (int)(cc.f0 + first + i), slice_data + slice_at[(size_t)i], slice_sizes + (size_t)i * n_sub, n_sub, &choices[i], buf.data(), buf.size(), &po.au_len);
-            else po.st = hevcdl_write_access_unit_segments(&scfg, &slices, &segments, (int)(cc.f0 + first + i), recs + (size_t)ctus * i, sao ? sao_params + (size_t)ctus * i : nullptr, &choices[i], buf.data(), buf.size(), &po.au_len);
+            pcfg.qp = pic_qps[(size_t)i];
+            if (slice_data) po.st = hevcdl_write_access_unit_from_slice_data_segments(&pcfg, &slices, &segments, (int)(cc.f0 + first + i), slice_data + slice_at[(size_t)i], slice_sizes + (size_t)i * n_sub, n_sub, &choices[i], buf.data(), buf.size(), &po.au_len);
+            else po.st = hevcdl_write_access_unit_segments(&pcfg, &slices, &segments, (int)(cc.f0 + first + i), recs + (size_t)ctus * i, sao ? sao_params + (size_t)ctus * i : nullptr, &choices[i], buf.data(), buf.size(), &po.au_len);
             if (po.st != HEVCDL_OK) continue;
             po.bytes.assign(buf.begin(), buf.begin() + po.au_len);
             if (hash_sei) { // suffix SEI after the slice; not part of the picture's bit count (as in the reference)
@@ -678,13 +700,14 @@ int main(int argc, char **argv)
         PicOut &po = pics[i];
         if (po.st != HEVCDL_OK) { fprintf(stderr, "Error: bitstream writer failed (status %d)\n", (int)po.st); S.rc = 3; return 1; }
         const long poc = cc.f0 + first + i;
-        unsigned long long row[11] = { (unsigned long long)poc, (unsigned long long)po.au_len * 8, po.sse[0], po.sse[1], po.sse[2], (unsigned long long)ctus, (unsigned long long)(cc.et * 1e9), (unsigned long long)S.dev, 0, 0, 0 };
-        if (print_msssim) memcpy(row + 8, quality[i].msssim, 3 * sizeof(double));
+        unsigned long long row[12] = { (unsigned long long)poc, (unsigned long long)po.au_len * 8, po.sse[0], po.sse[1], po.sse[2], (unsigned long long)ctus, (unsigned long long)(cc.et * 1e9), (unsigned long long)S.dev,
+                                       (unsigned long long)pic_qps[(size_t)i], 0, 0, 0 };
+        if (print_msssim) memcpy(row + 9, quality[i].msssim, 3 * sizeof(double));
         S.rows.insert(S.rows.end(), row, row + ROW);
         if (multi) { S.aus.push_back(std::move(po.bytes)); S.md5.push_back(po.md5_text); }
         else {
           if (fbits) fwrite(po.bytes.data(), 1, po.bytes.size(), fbits);
-          log_picture(poc, (unsigned long long)po.au_len * 8, po.sse, cc.et, po.md5_text, print_msssim ? row + 8 : nullptr);
+          log_picture(poc, pic_qps[(size_t)i], (unsigned long long)po.au_len * 8, po.sse, cc.et, po.md5_text, print_msssim ? row + 9 : nullptr);
         }
       }
       if (frec || frecords) {
@@ -767,7 +790,7 @@ int main(int argc, char **argv)
         const Shard &S = shards[si];
         const size_t li = (size_t)(poc - S.f_lo);
         if (fbits) fwrite(S.aus[li].data(), 1, S.aus[li].size(), fbits);
-        log_picture(poc, rows[r][1], rows[r] + 2, (double)rows[r][6] * 1e-9, S.md5[li].c_str(), print_msssim ? rows[r] + 8 : nullptr);
+        log_picture(poc, (int)rows[r][8], rows[r][1], rows[r] + 2, (double)rows[r][6] * 1e-9, S.md5[li].c_str(), print_msssim ? rows[r] + 9 : nullptr);
       }
     }
   }

@@ -149,6 +149,10 @@ struct hevcdl_dbk_trial_params {
   int n_chroma, tc_c[7], chroma_of[7];            // the distinct chroma tc values, and for every t the value it uses
 };
 
+// The slice QP of every picture of a batch and the lambdas that go with it (cfg key DeltaQpRD: pictures of one batch end at different QPs), for the stages behind the
+// decisions that read them: the SAO decision and the entropy coder's context initialisation.  The deblocking filter has its own rows (hevcdl_dbk_params.frame_params).
+struct hevcdl_frame_qp { double lambda, lambda_chroma; int qp, pad; };
+
 // sample adaptive offset (sao_kernel.hip)
 struct hevcdl_sao_params {
   const uint8_t *org, *deblocked;  // [frame] planar 4:2:0
@@ -164,6 +168,7 @@ struct hevcdl_sao_params {
   int bit_depth;                   // 8: planes of uint8; 10: planes of uint16 (offset range 31, band = sample >> 5, distortion >> 4)
   int lf_across_tiles;             // 0: a neighbouring CTU of another tile counts as missing (like the picture border)
   double lambda, lambda_chroma;
+  const struct hevcdl_frame_qp *frame_qp;      // NULL, or [frame] in HBM: qp, lambda and lambda_chroma per picture (the three launch-wide values are then not read)
 };
 
 // picture quality metrics (quality_kernel.hip): exact SSE and the reference's MS-SSIM for n_pics pictures of up to three planes
@@ -227,6 +232,26 @@ struct hevcdl_entropy_params {
   int col_bd[21], row_bd[23];
   int slice_units;                 // sub-streams per slice (hevcdl_ec::ec_ends_slice): 0 = the picture is one slice; 1 = SliceMode 1 (the grid is one column of row slices); n = SliceMode 3
   int segment_units;               // sub-streams per dependent slice segment (hevcdl_ec::ec_ends_segment): 0 = none; SliceSegmentMode 1: CTU rows of a wavefront picture; 3: tiles
+  const struct hevcdl_frame_qp *frame_qp;      // NULL, or [frame] in HBM: the slice QP of every picture (qp above is then not read)
+};
+
+// DeltaQpRD (qp_rd_kernel.hip).  Sum: one workgroup per picture adds up bits and dist of the picture's CTU records -- the candidate `idx` just coded -- and compares
+// (csrc/qp_rd.h); keep: pictures whose row says `take` get records, reconstruction and statistics of the trial set copied over the call's own.
+struct hevcdl_qp_rd_sum_params {
+  const unsigned char *records;    // [frame][ctu] hevcdl_ctu_record of candidate idx
+  struct hevcdl_qp_rd_row *rows;   // [frame]
+  int ctus_per_frame, n_frames, idx;
+  int ctu_iters;                   // CTUs a lane visits at the most: ceil(ctus_per_frame / 256)
+  double frame_lambda;
+};
+struct hevcdl_qp_rd_keep_params {
+  const unsigned char *src_records, *src_recon, *src_stats;      // the trial set; all but the statistics 16-byte aligned, picture by picture
+  unsigned char *dst_records, *dst_recon, *dst_stats;            // the call's buffers; *_stats may both be NULL
+  const struct hevcdl_qp_rd_row *rows;                           // [frame]
+  unsigned long long rec16, pic16;                               // 16-byte units of a picture's records and of a picture's records + reconstruction
+  unsigned long long chunk16;                                    // units a workgroup copies: a multiple of 1024 (256 lanes x 4 units in flight)
+  int chunk_iters;                                               // chunk16 / 1024
+  int n_frames;
 };
 struct hevcdl_entropy_pack_params {
   const unsigned char *src; unsigned char *dst;
@@ -319,6 +344,8 @@ int hevcdl_host_writer_slice_data(const struct hevcdl_stream_config *cfg, const 
                                   const struct hevcdl_sao_blk *sao, uint8_t *out, size_t capacity, uint32_t *sizes, size_t *total);
 void hevcdl_launch_entropy(const struct hevcdl_entropy_params *p, void *stream, void *mid_event_opt);      // one launch, or the two of the wavefront scheme; mid_event_opt (a hipEvent_t) is recorded between the two
 void hevcdl_launch_entropy_pack(const struct hevcdl_entropy_pack_params *p, void *stream);
+void hevcdl_launch_qp_rd_sum(const struct hevcdl_qp_rd_sum_params *p, void *stream);          // qp_rd_kernel.hip; fills ctu_iters
+void hevcdl_launch_qp_rd_keep(const struct hevcdl_qp_rd_keep_params *p, void *stream);        // fills chunk16 / chunk_iters
 size_t hevcdl_cnn_smem_bytes(void);
 size_t hevcdl_fc_smem_bytes(void);
 size_t hevcdl_rd_smem_bytes(void);

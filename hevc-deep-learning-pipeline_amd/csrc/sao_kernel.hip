@@ -334,7 +334,9 @@ __global__ __launch_bounds__(256) void hevcdl_sao_offsets_kernel(hevcdl_sao_para
   const Bd bd = { (1 << ((p.bit_depth < 10 ? p.bit_depth : 10) - 5)) - 1, 2 * (p.bit_depth - 8), p.bit_depth - 8 };
   const Stat GLB &st = ((const Stat GLB *)p.stats)[idx];
   int32_t q[32], aux;
-  derive_offsets(type, comp ? p.lambda_chroma : p.lambda, st, q, aux, bd);
+  double lam = comp ? p.lambda_chroma : p.lambda;
+  if (p.frame_qp) { const hevcdl_frame_qp GLB &fq = ((const hevcdl_frame_qp GLB *)p.frame_qp)[idx / ((size_t)p.ctus_per_frame * 3 * NTYPES)]; lam = comp ? fq.lambda_chroma : fq.lambda; }      // the picture's own slice lambdas
+  derive_offsets(type, lam, st, q, aux, bd);
   Cand GLB &c = ((Cand GLB *)p.cand)[idx];
   for (int i = 0; i < 4; i++) c.off[i] = (int8_t)(type == BO ? q[(aux + i) & 31] : q[i < 2 ? i : i + 1]);
   c.aux = aux; c.dist = get_dist(type, aux, q, st, bd);
@@ -381,7 +383,9 @@ __global__ __launch_bounds__(64) void hevcdl_sao_decide_kernel(hevcdl_sao_params
   const int frame = blockIdx.x * 64 + threadIdx.x;
   if (frame >= p.n_frames) return;
   const int cx = p.ctus_x, nctu = p.ctus_per_frame;
-  const double lambda[3] = { p.lambda, p.lambda_chroma, p.lambda_chroma };
+  double lambda[3] = { p.lambda, p.lambda_chroma, p.lambda_chroma };
+  int slice_qp = p.qp;
+  if (p.frame_qp) { const hevcdl_frame_qp GLB &fq = ((const hevcdl_frame_qp GLB *)p.frame_qp)[frame]; lambda[0] = fq.lambda; lambda[1] = lambda[2] = fq.lambda_chroma; slice_qp = fq.qp; }      // the picture's own slice QP and lambdas
   const Bd bd = { (1 << ((p.bit_depth < 10 ? p.bit_depth : 10) - 5)) - 1, 2 * (p.bit_depth - 8), p.bit_depth - 8 };
   const Stat GLB *stats = (const Stat GLB *)p.stats + (size_t)frame * nctu * 3 * NTYPES;
   CRec GLB *crec = (CRec GLB *)p.crec + (size_t)frame * nctu;
@@ -390,7 +394,7 @@ __global__ __launch_bounds__(64) void hevcdl_sao_decide_kernel(hevcdl_sao_params
     const int init[2] = { 153, 200 };
     for (int i = 0; i < 2; i++) {
       const int v = init[i], slope = (v >> 4) * 5 - 45, offset = ((v & 15) << 3) - 16;
-      int s = ((slope * p.qp) >> 4) + offset; s = s < 1 ? 1 : (s > 126 ? 126 : s);
+      int s = ((slope * slice_qp) >> 4) + offset; s = s < 1 ? 1 : (s > 126 ? 126 : s);
       const int mps = s >= 64; const uint8_t st = (uint8_t)(((mps ? s - 64 : 63 - s) << 1) + mps);
       if (i == 0) go.merge_ctx = st; else go.type_ctx = st;
     }

@@ -43,7 +43,7 @@ def read_frames(path, width, height, first, count, bit_depth=8, frame_samples=No
 
 def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None, recon_path=None, frame_skip=0, batch=256, tiles=(1, 1),
                     lf_across_tiles=True, bit_depth=8, level_idc=186, frame_rate=30.0, hash_sei=False, labels_fn=None, device=None, log=print, tools=0x7f, wavefront=False, device_entropy=False, device_report=False, source_format=None,
-                    deblocking_metric=0, lf_offset_in_pps=True, slices=None, lf_across_slices=True, segments=None):
+                    deblocking_metric=0, lf_offset_in_pps=True, slices=None, lf_across_slices=True, segments=None, delta_qp_rd=0):
     """Encode frames [frame_skip, frame_skip + n_frames) of a planar YUV file.  Works stand-alone and under torch.distributed
     (initialised by the caller): rank r takes a contiguous share of the frames.  Returns, on rank 0, the summary (metrics.Summary)
     and the list of per-picture rows [poc, bits, sseY, sseU, sseV]; other ranks return (None, None).
@@ -66,7 +66,9 @@ def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None
     width in CTUs; independent units of the decision launch, like tiles), mode 3 a picture of tiles into slices of SliceArgument tiles.  Every slice is a NAL unit of its own;
     what the library refuses (hevcdl.h, hevcdl_config.slice_mode) is raised with its reason.
     segments = (SliceSegmentMode, SliceSegmentArgument): dependent slice segments -- mode 1 makes every SliceSegmentArgument / width-in-CTUs rows of a wavefront picture a NAL
-    unit of its own, mode 3 every SliceSegmentArgument tiles.  Nothing but the stream changes (hevcdl.h, hevcdl_config.slice_segment_mode)."""
+    unit of its own, mode 3 every SliceSegmentArgument tiles.  Nothing but the stream changes (hevcdl.h, hevcdl_config.slice_segment_mode).
+    delta_qp_rd = N (the cfg key DeltaQpRD): every picture is decided at 2N+1 QPs round `qp` and coded with the cheapest (hevcdl.h, hevcdl_config.delta_qp_rd).  Pictures are
+    independent, so it shards like everything else; the rows then carry a sixth column, the QP the picture was coded with, and the log lines print it."""
     if deblocking_metric not in (0, 1, 2):
         raise ValueError("DeblockingFilterMetric %r is not a value of the key (0, 1 or 2)" % (deblocking_metric,))
     if deblocking_metric and lf_offset_in_pps:
@@ -83,12 +85,12 @@ def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None
                          "chain and cannot be dealt to ranks; run it on one rank" % world)
     mine = sharding.shard_frames(n_frames, world, rank)
     per_rank = sharding.max_shard(n_frames, world)
-    rows = np.full((per_rank + 1, 5), -1, np.int64)
+    rows = np.full((per_rank + 1, 6 if delta_qp_rd else 5), -1, np.int64)
     part_bits = (bitstream_path + ".part%d" % rank) if bitstream_path else None
     part_rec = (recon_path + ".part%d" % rank) if recon_path else None
     fb, fr = open(part_bits, "wb") if part_bits else None, open(part_rec, "wb") if part_rec else None
     if len(mine):
-        enc = Encoder(width, height, qp, max_frames=min(batch, len(mine)), device=device, tiles=tiles, bit_depth=bit_depth, lf_across_tiles=lf_across_tiles, tools=tools, wavefront=wavefront, slices=slices, lf_across_slices=lf_across_slices, segments=segments, **dbk)      # tools: HEVCDL_TOOL_*; wavefront: WaveFrontSynchro mask (the cfg's tool switches)
+        enc = Encoder(width, height, qp, max_frames=min(batch, len(mine)), device=device, tiles=tiles, bit_depth=bit_depth, lf_across_tiles=lf_across_tiles, tools=tools, wavefront=wavefront, slices=slices, lf_across_slices=lf_across_slices, segments=segments, delta_qp_rd=delta_qp_rd, **dbk)      # tools: HEVCDL_TOOL_*; wavefront: WaveFrontSynchro mask (the cfg's tool switches)
         sf = source_format
         sw, sh = (sf.source_width, sf.source_height) if sf is not None else (width, height)
         conf_win = (width - sw, height - sh)
@@ -123,11 +125,16 @@ def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None
             slice_data, slice_sizes = enc.get_slice_data(0, nb) if device_entropy else (None, None)
             reports = enc.get_picture_report(0, nb) if device_report else None
             choices = enc.get_dbk_choice(0, nb)      # what every picture's slice header says about its deblocking filter
+            pic_qp = [int(v) for v in enc.get_qp_rd(0, nb)[1]] if delta_qp_rd else [qp] * nb      # the QP every picture was coded with: its slice_qp_delta
             def one_picture(i):          # host work of a picture (arithmetic coder, hash, SSE): independent -> thread pool (ctypes drops the GIL)
                 if device_entropy:
-                    au = write_access_unit_from_slice_data(scfg, b0 + i, slice_data[i], slice_sizes[i], choices[i], layout=enc.slice_layout, segments=enc.segment_layout)
+                    pcfg = scfg
+                    if pic_qp[i] != qp:          # the access unit's own copy of the stream configuration
+                        pcfg = type(scfg).from_buffer_copy(scfg)
+                        pcfg.qp = pic_qp[i]
+                    au = write_access_unit_from_slice_data(pcfg, b0 + i, slice_data[i], slice_sizes[i], choices[i], layout=enc.slice_layout, segments=enc.segment_layout)
                 else:
-                    au = write_access_unit(width, height, qp, b0 + i, recs[i], level_idc=level_idc, sao=sao[i], tiles=tiles, bit_depth=bit_depth, lf_across_tiles=lf_across_tiles, tools=tools, wavefront=wavefront, conf_win=conf_win, choice=choices[i], slices=slices, lf_across_slices=lf_across_slices, segments=enc.segment_layout)
+                    au = write_access_unit(width, height, pic_qp[i], b0 + i, recs[i], level_idc=level_idc, sao=sao[i], tiles=tiles, bit_depth=bit_depth, lf_across_tiles=lf_across_tiles, tools=tools, wavefront=wavefront, conf_win=conf_win, choice=choices[i], slices=slices, lf_across_slices=lf_across_slices, segments=enc.segment_layout)
                 if device_report:
                     return au, digest_sei(1, report_digest(reports[i])) if hash_sei else b"", [int(v) for v in reports[i]["sse"]]
                 sei = picture_hash_sei(width, height, final[i], bit_depth) if hash_sei else b""
@@ -141,7 +148,7 @@ def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None
                 poc = b0 + i
                 if fb:
                     fb.write(au + sei)
-                rows[poc - mine.start] = [poc, len(au) * 8] + sse
+                rows[poc - mine.start] = [poc, len(au) * 8] + sse + ([pic_qp[i]] if delta_qp_rd else [])
             if fr:
                 (final if sf is None else store_output_host(sf, width, height, bit_depth, final)).tofile(fr)
             log("rank %d: pictures %d..%d encoded (%.2f s per picture)" % (rank, b0, b0 + nb - 1, et))
@@ -169,16 +176,17 @@ def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None
                             out.write(chunk)
                     os.remove(path + ".part%d" % r)
     summ = metrics.Summary(*((source_format.source_width, source_format.source_height) if source_format is not None else (width, height)), frame_rate, bit_depth)
-    for poc, bits, sy, su, sv in allrows:
-        p = summ.add(int(bits), (int(sy), int(su), int(sv)))
-        log(metrics.frame_line(int(poc), qp, int(bits), p))
+    for row in allrows:
+        poc, bits, sy, su, sv = (int(v) for v in row[:5])
+        p = summ.add(bits, (sy, su, sv))
+        log(metrics.frame_line(poc, int(row[5]) if delta_qp_rd else qp, bits, p))
     log("\n\nSUMMARY --------------------------------------------------------")
     log(summ.text())
     return summ, allrows
 
 
 def encode_sequence_tile_sharded(input_path, width, height, qp, n_frames, tiles, bitstream_path=None, recon_path=None, frame_skip=0, batch=None, lf_across_tiles=True,
-                                 bit_depth=8, level_idc=186, frame_rate=30.0, hash_sei=False, device=None, log=print, tools=0x7f, slices=None, segments=None):
+                                 bit_depth=8, level_idc=186, frame_rate=30.0, hash_sei=False, device=None, log=print, tools=0x7f, slices=None, segments=None, delta_qp_rd=0):
     """The within-picture partition: every rank decides its share of the TILES of every picture of a batch
     (`hevcdl_compress_tiles_dev`), one all-to-all moves the tile payloads to the picture's owner (`sharding.exchange_tiles_to_owners`:
     picture i of the batch -> rank i mod world), the owner runs the in-loop filters on the assembled picture and writes its access unit.
@@ -188,6 +196,8 @@ def encode_sequence_tile_sharded(input_path, width, height, qp, n_frames, tiles,
         raise ValueError("the tile-sharded path does not code slices (SliceMode %d): use encode_sequence" % int(slices[0]))
     if segments is not None and int(segments[0]) != 0:
         raise ValueError("the tile-sharded path does not code slice segments (SliceSegmentMode %d): use encode_sequence" % int(segments[0]))
+    if delta_qp_rd:      # a picture's QP is picked from the sums of ALL its tiles, which no rank has
+        raise ValueError("the tile-sharded path does not search the slice QP (DeltaQpRD %d): use encode_sequence" % int(delta_qp_rd))
     import torch
     import torch.distributed as dist
     from . import REC_DTYPE, SAO_DTYPE

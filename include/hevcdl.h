@@ -140,7 +140,37 @@ typedef struct hevcdl_config {
    * Refused: 2 (segments by bytes); mode 1 without wavefront or with segments that are not whole CTU rows (the reference's decisions change where a segment starts in the
    * middle of a coder chain), mode 1 with tiles or slices, mode 3 without tiles, either mode with deblocking_metric.  hevcdl_create_error names what was refused. */
   int32_t  slice_segment_mode, slice_segment_argument;
+  /* DeltaQpRD (cfg key of that name, "slice-based multi-QP optimization").  0 (the default; a zeroed tail means it): none -- everything behaves as
+   * without the field.  N = 1 .. HEVCDL_QP_RD_MAX_N: every picture is decided 2N+1 times, at qp, qp - 1, qp + 1, ... qp + N with the same labels (the CNN runs once), and
+   * the candidate with the least picture cost dist + bits * frameLambda is kept (TEncSlice::precompressSlice, TEncSlice.cpp:572-661): its records, reconstruction and
+   * statistics are what the call returns, its QP and lambdas what deblocking, SAO, the slice header (slice_qp_delta; init_qp_minus26 stays 0) and the entropy coder's
+   * contexts use.  Pictures of one batch may end at different QPs: hevcdl_get_qp_rd.  A candidate outside 0 .. 51 is coded at the clipped QP with the lambda of the
+   * unclipped one, as in the reference.  Tiles and wavefront are allowed (a picture is still one slice).  Refused: with slice_mode or slice_segment_mode (the reference
+   * optimises per slice), with deblocking_metric, N above the bound, at 10 bits qp - N < 0 (the reference would code at a negative QP); the per-CTU session
+   * (hevcdl_begin_frames) and hevcdl_compress_tiles_dev refuse such a context.  hevcdl_create_error names what was refused. */
+  int32_t  delta_qp_rd;
 } hevcdl_config;
+
+/* ---- DeltaQpRD: the slice QP of a picture picked among 2N+1 candidate encodes (csrc/qp_rd.h, csrc/qp_rd_kernel.hip) -----------------------------------------------
+ * The largest N a context takes: 13 candidates, offsets -6 .. +6 -- one doubling of the quantiser step either way.  Every candidate is a whole decision launch, so a
+ * picture costs 2N+1 times its decisions. */
+#define HEVCDL_QP_RD_MAX_N 6
+#define HEVCDL_QP_RD_MAX_CANDIDATES (2 * HEVCDL_QP_RD_MAX_N + 1)
+/* One candidate: its offset (0, -1, +1, -2, +2, ...: TEncSlice.cpp:294), the QP it is coded at (:523) and the decision constants of hevcdl_config for it, field for field. */
+typedef struct hevcdl_qp_rd_candidate {
+  int32_t  offset, qp;
+  double   lambda, sqrt_lambda, chroma_weight, lambda_chroma;
+  double   err_scale[2][4];
+  int64_t  sbh_rd_factor[2];
+  int32_t  qp_chroma, pad;
+} hevcdl_qp_rd_candidate;
+/* One picture's row of the trial table: what the device keeps per picture while the candidates run, and what hevcdl_get_qp_rd hands out. */
+typedef struct hevcdl_qp_rd_row {
+  uint64_t bits[HEVCDL_QP_RD_MAX_CANDIDATES], dist[HEVCDL_QP_RD_MAX_CANDIDATES];      /* m_uiPicTotalBits / m_uiPicDist of every candidate (TEncSlice.cpp:959-961): the sums of hevcdl_ctu_record.bits / .dist */
+  double   best_cost;            /* dPicRdCostBest */
+  int32_t  best_idx;             /* uiQpIdxBest: the candidate the picture was coded with */
+  int32_t  take;                 /* (device bookkeeping: the last candidate summed was a new best) */
+} hevcdl_qp_rd_row;
 
 /* One CTU of decisions: what compressCtu leaves in the picture's CTU record (TEncCu.cpp:1091 copyToPic).
  * 256 entries = 4x4 luma partitions in z-scan order (TComRom.cpp:284-352).  Coefficients use the
@@ -174,6 +204,15 @@ hevcdl_status hevcdl_config_default(hevcdl_config *cfg, int width, int height, i
 /* The same for a given sample bit depth (8 or 10): quantiser QP offset 6 per extra bit, distortion kept at 8-bit scale
  * (the reference's FULL_NBIT 0 build, TypeDef.h:162-172), lambda unchanged (TEncSlice.cpp:433-527). */
 hevcdl_status hevcdl_config_default_bd(hevcdl_config *cfg, int width, int height, int qp, int bit_depth);
+/* DeltaQpRD, host only (no GPU needed; csrc/qp_rd.h): the candidate table of a configuration -- cfg->qp, cfg->delta_qp_rd and cfg->bit_depth are read.  out[idx], idx = 0 ..
+ * 2N: the candidate's offset, the QP it is coded at and its constants, computed by the code hevcdl_config_default* fills a configuration with; *count = 2N+1;
+ * *frame_lambda = 0.68 * 2^((qp - 12) / 3), the lambda of the picture cost (TEncSlice.cpp:615-623).  delta_qp_rd 0 gives the one candidate a plain context runs.
+ * HEVCDL_ERR_INVALID_ARG: null pointers, capacity below 2N+1, N outside 0 .. HEVCDL_QP_RD_MAX_N, qp outside 0 .. 51; HEVCDL_ERR_UNSUPPORTED: a bit depth other
+ * than 8 or 10, or 10 bits with qp - N < 0. */
+hevcdl_status hevcdl_qp_rd_candidates(const hevcdl_config *cfg, hevcdl_qp_rd_candidate *out, int capacity, int *count, double *frame_lambda);
+/* ... and the pick rule (TEncSlice.cpp:646-652): the index of the candidate kept, from the n pairs of picture sums in candidate order -- cost = dist + bits * frame_lambda in
+ * IEEE double, multiply and add separate, strict `<`: a tie keeps the earlier index.  -1 for null pointers or n < 1.  The device runs the same source. */
+int           hevcdl_qp_rd_pick_index(const uint64_t *bits, const uint64_t *dist, int n, double frame_lambda);
 
 /* weights: flat fp32 blob, HEVCDL_WEIGHT_FLOATS values (replaces torch.load at use_model.py:62). */
 hevcdl_status hevcdl_create(const hevcdl_config *cfg, const float *weights, size_t n_floats, hevcdl_ctx **out);
@@ -675,6 +714,38 @@ const char   *hevcdl_last_rd_launch(const hevcdl_ctx *ctx);
  * allocates the largest workspace any launch of the context (1 .. max_frames frames) can ask for, so that a lack of memory shows up here -- the CLI calls it right
  * behind hevcdl_create and retries with a smaller batch -- and no later launch allocates or synchronises. */
 hevcdl_status hevcdl_reserve_workspace(hevcdl_ctx *ctx);
+
+/* ---- DeltaQpRD on a context (cfg.delta_qp_rd = N > 0) ----------------------------------------------------------------------------------------------------------------------
+ * Every decision call for whole frames -- hevcdl_compress_frames*, hevcdl_encode_frames_dev and the picture pipelines -- runs the label CNN once (where it runs it at all)
+ * and then the decision launch 2N+1 times on the caller's stream, each with that candidate's constants and each with the launch plan of the same call without the key.
+ * Candidate 0 writes into the call's own records / reconstruction / statistics; later candidates write into one trial set the context owns (records, reconstruction and
+ * statistics of max_frames pictures, allocated by the first such call or by hevcdl_reserve_workspace; a refusal is HEVCDL_ERR_OOM).  Behind every launch
+ * hevcdl_qp_rd_sum_kernel adds up the picture's bits and dist and compares, and hevcdl_qp_rd_keep_kernel copies the trial set's outputs over the call's own for the
+ * pictures whose candidate is the best so far.  The search is deterministic, so the winning trial IS the reference's final compress at the winning QP: it is kept, not
+ * run again.  The device entry points need d_records and d_recon 16-byte aligned and d_stats 8-byte aligned (HEVCDL_ERR_INVALID_ARG otherwise).
+ * The picture pipelines then fetch the rows (a few words a picture) and run deblocking, the SAO decision and the device entropy coder with every picture's own QP and
+ * lambdas.  The host writer takes the picture's QP in hevcdl_stream_config.qp of the call that writes its access unit: slice_qp_delta = qp - 26, and no parameter set
+ * depends on it.
+ * hevcdl_get_qp_rd: rows [first, first + count) of the LAST decision call of the context (it waits for the device first) and, in qps_opt, the QP every picture was coded
+ * with.  On a context without the key: HEVCDL_ERR_INVALID_ARG. */
+hevcdl_status hevcdl_get_qp_rd(hevcdl_ctx *ctx, int first, int count, hevcdl_qp_rd_row *rows, int32_t *qps_opt);
+/* The stages behind the decisions for pictures with QPs of their own: idx[i] = the candidate (0 .. 2N of the context's table, hevcdl_qp_rd_candidates) picture i was coded
+ * with.  idx == NULL is the function without the suffix; an index outside the table is HEVCDL_ERR_INVALID_ARG.  choices_opt: as hevcdl_deblock_frames_choice. */
+hevcdl_status hevcdl_deblock_frames_qp(hevcdl_ctx *ctx, const uint8_t *recon, int n_frames, const hevcdl_ctu_record *records, const hevcdl_dbk_choice *choices_opt, const int32_t *idx, uint8_t *out);
+hevcdl_status hevcdl_deblock_frames_qp_dev(hevcdl_ctx *ctx, const void *d_recon, int n_frames, const void *d_records, const hevcdl_dbk_choice *choices_opt, const int32_t *idx, void *d_out, void *stream);
+hevcdl_status hevcdl_sao_frames_qp(hevcdl_ctx *ctx, const uint8_t *org, const uint8_t *deblocked, int n_frames, const int32_t *idx, hevcdl_sao_blk *params, uint8_t *out);
+hevcdl_status hevcdl_sao_frames_qp_dev(hevcdl_ctx *ctx, const void *d_org, const void *d_deblocked, int n_frames, const int32_t *idx, void *d_params, void *d_out, void *stream);
+/* TEST AND DIAGNOSTIC entry points.
+ * hevcdl_get_qp_rd_info: bytes of the trial set the context holds (0: none allocated) and how many sum / keep kernel launches it has made so far; kernel_ms_opt[2] (may be
+ * NULL): HIP-event times of the sum launches and of the keep launches of the LAST search, each summed over its candidates -- measured only with
+ * hevcdl_profile_enable(ctx, 1) (the call then synchronises and the events are released), zeros otherwise.
+ * hevcdl_qp_rd_step: the two kernels alone, without a context, for candidate `idx` of n_frames pictures of ctus_per_frame CTUs and frame_bytes bytes of reconstruction
+ * (a multiple of 16): the sum launch over trial_records and, for idx > 0, the keep launch from the trial set into records / recon / stats.  Host buffers in and out; rows is
+ * read (idx > 0: the state the candidates before left) and written.  The three destinations are passed WITH a margin of guard_bytes (a multiple of 16) in front of and
+ * behind the payload, uploaded and downloaded whole: what the kernels leave untouched comes back as it went. */
+hevcdl_status hevcdl_get_qp_rd_info(hevcdl_ctx *ctx, size_t *trial_bytes, uint64_t *kernel_launches, double *kernel_ms_opt);
+hevcdl_status hevcdl_qp_rd_step(int device, int ctus_per_frame, size_t frame_bytes, int n_frames, int idx, double frame_lambda, const hevcdl_ctu_record *trial_records,
+                                const void *trial_recon, const hevcdl_frame_stats *trial_stats, hevcdl_qp_rd_row *rows, void *records, void *recon, void *stats, size_t guard_bytes);
 /* kernel timing with HIP events recorded on the launch stream */
 hevcdl_status hevcdl_profile_enable(hevcdl_ctx *ctx, int enable);
 hevcdl_status hevcdl_profile_get(hevcdl_ctx *ctx, hevcdl_profile *out);   /* synchronises, returns and resets */
