@@ -23,7 +23,7 @@ LEAF_LIB_PATH = os.path.join(PKG_DIR, "lib", "libhevcdl_hip_leaf.so")        # -
 WEIGHTS_PATH = os.path.join(PKG_DIR, "weights", "hevc_encoder_model.f32")
 WEIGHT_FLOATS = 637712
 LEAF_SOURCES = ["rd_leaf.hip", "rd_leaf_bd10.hip", "rd_leaf_wide.hip", "rd_leaf_tools.hip"]      # the decision kernel's four builds, each with csrc/rd_leaf_harness.h behind it
-SOURCES = ["cnn_kernel.hip", "fc_kernel.hip", "rd_kernel.hip", "rd_kernel_bd10.hip", "rd_kernel_wide.hip", "rd_kernel_tools.hip", "deblock_kernel.hip", "dbk_select_kernel.hip", "sao_kernel.hip", "quality_kernel.hip", "report_kernel.hip", "entropy_kernel.hip", "source_kernel.hip", "qp_rd_kernel.hip", "hevcdl_api.hip", "hevcdl_bitstream.cpp"]
+SOURCES = ["cnn_kernel.hip", "fc_kernel.hip", "rd_kernel.hip", "rd_kernel_bd10.hip", "rd_kernel_wide.hip", "rd_kernel_tools.hip", "deblock_kernel.hip", "dbk_select_kernel.hip", "sao_kernel.hip", "quality_kernel.hip", "report_kernel.hip", "entropy_kernel.hip", "source_kernel.hip", "qp_rd_kernel.hip", "frame_permute_kernel.hip", "hevcdl_api.hip", "hevcdl_bitstream.cpp"]
 
 STATUS = {0: "OK", 1: "INVALID_ARG", 2: "UNSUPPORTED", 3: "NO_DEVICE", 4: "HIP", 5: "OOM"}
 
@@ -403,6 +403,17 @@ def load_library():
     lib.hevcdl_deblock_frames_qp_dev.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp]
     lib.hevcdl_sao_frames_qp.argtypes = [vp, vp, vp, ci, vp, vp, vp]
     lib.hevcdl_sao_frames_qp_dev.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp]
+    cpp = ctypes.POINTER(ctypes.c_char_p)
+    lib.hevcdl_set_frame_qps.argtypes = [vp, vp, ci]
+    lib.hevcdl_set_lambda_modifier.argtypes = [vp, ctypes.c_double]
+    lib.hevcdl_get_frame_qps.argtypes = [vp, ci, ci, vp]
+    lib.hevcdl_frame_qp_check.argtypes = [ctypes.POINTER(Config), vp, ci, ctypes.c_double, cpp]
+    lib.hevcdl_frame_qp_list.argtypes = [ci, vp, ci, ci, ci, vp]
+    lib.hevcdl_frame_qp_offsets.argtypes = [ci, ci, ci, ci, ctypes.c_char_p, vp, ctypes.POINTER(ci)]
+    lib.hevcdl_frame_qp_families.argtypes = [ci, ci, ctypes.c_double, ctypes.POINTER(QpRdCandidate)]
+    lib.hevcdl_frame_qp_grouping.argtypes = [vp, ci, vp, vp, vp, vp, ctypes.POINTER(ci)]
+    lib.hevcdl_get_frame_qp_info.argtypes = [vp, szp, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double)]
+    lib.hevcdl_frame_permute_step.argtypes = [ci, ci, szp, ci, vp, ci, vp, vp, ctypes.c_size_t]
     _lib = lib
     return lib
 
@@ -426,7 +437,85 @@ EXPORTS = ["hevcdl_config_default", "hevcdl_create", "hevcdl_destroy", "hevcdl_l
            "hevcdl_write_access_unit_segments", "hevcdl_write_access_unit_from_slice_data_segments", "hevcdl_slice_data_layout_segments", "hevcdl_code_slice_data_host_segments",
            "hevcdl_code_slice_data_segments", "hevcdl_access_unit_bound_segments", "hevcdl_get_segment_layout",
            "hevcdl_qp_rd_candidates", "hevcdl_qp_rd_pick_index", "hevcdl_get_qp_rd", "hevcdl_get_qp_rd_info", "hevcdl_qp_rd_step",
-           "hevcdl_deblock_frames_qp", "hevcdl_deblock_frames_qp_dev", "hevcdl_sao_frames_qp", "hevcdl_sao_frames_qp_dev"]
+           "hevcdl_deblock_frames_qp", "hevcdl_deblock_frames_qp_dev", "hevcdl_sao_frames_qp", "hevcdl_sao_frames_qp_dev",
+           "hevcdl_set_frame_qps", "hevcdl_set_lambda_modifier", "hevcdl_get_frame_qps", "hevcdl_frame_qp_check", "hevcdl_frame_qp_list", "hevcdl_frame_qp_offsets",
+           "hevcdl_frame_qp_families", "hevcdl_frame_qp_grouping", "hevcdl_get_frame_qp_info", "hevcdl_frame_permute_step"]
+
+
+# ---- a QP per picture (include/hevcdl.h "A QP per picture"; csrc/frame_qp.h): the host-only rule, no GPU needed ----
+def frame_qp_offsets(n, qp_increment_frame=None, frame_skip=0, temporal_subsample_ratio=1, dqp_file=None):
+    """The per-POC offsets of a sequence of n pictures (hevcdl_frame_qp_offsets): zeros, ones from the switching POC of QPIncrementFrame on, then the integers of dQPFile,
+    which overwrite -> (offsets [n] int32, how many the file set)."""
+    lib = load_library()
+    out, got = np.zeros(max(int(n), 1), np.int32), ctypes.c_int(0)
+    st = lib.hevcdl_frame_qp_offsets(int(n), -1 if qp_increment_frame is None else int(qp_increment_frame), int(frame_skip), int(temporal_subsample_ratio),
+                                     os.fsencode(dqp_file) if dqp_file else None, out.ctypes.data, ctypes.byref(got))
+    if st:
+        raise HevcdlError(st, "hevcdl_frame_qp_offsets: dQPFile %s cannot be read as integers of -64 .. 64" % (dqp_file,))
+    return out[:int(n)], got.value
+
+
+def frame_qp_list(base_qp, dqp, intra_qp_offset=0, bit_depth=8, n=None):
+    """The QP of every picture (hevcdl_frame_qp_list): Clip3(-QpBDOffset, 51, base + dqp[poc] + IntraQPOffset) -> [n] int32; a QP below 0 raises."""
+    lib = load_library()
+    dqp = None if dqp is None else np.ascontiguousarray(dqp, np.int32).reshape(-1)
+    n = int(dqp.size if n is None else n)
+    out = np.zeros(max(n, 1), np.int32)
+    st = lib.hevcdl_frame_qp_list(int(base_qp), None if dqp is None else dqp.ctypes.data, n, int(intra_qp_offset), int(bit_depth), out.ctypes.data)
+    if st:
+        raise HevcdlError(st, "hevcdl_frame_qp_list: " + FRAME_QP_REFUSE_NEGATIVE)
+    return out[:n]
+
+
+FRAME_QP_REFUSE_NEGATIVE = "a picture's QP is below 0: at 10 bits the reference would code it at a negative QP, which this path does not have"
+
+
+def frame_qp_family(qp, bit_depth=8, lambda_modifier=1.0):
+    """The decision constants of a picture coded at qp with the lambda modifier (hevcdl_frame_qp_families) -> QpRdCandidate."""
+    lib = load_library()
+    out = QpRdCandidate()
+    st = lib.hevcdl_frame_qp_families(int(qp), int(bit_depth), float(lambda_modifier), ctypes.byref(out))
+    if st:
+        raise HevcdlError(st, "hevcdl_frame_qp_families")
+    return out
+
+
+def frame_qp_grouping(qps):
+    """The grouping of a batch by QP (hevcdl_frame_qp_grouping) -> (perm [n]: sorted place -> picture, runs [(qp, first, count)], contiguous: nothing would be copied)."""
+    lib = load_library()
+    qps = np.ascontiguousarray(qps, np.int32).reshape(-1)
+    n = int(qps.size)
+    perm, rq, rf, rc, cont = np.zeros(max(n, 1), np.int32), np.zeros(52, np.int32), np.zeros(52, np.int32), np.zeros(52, np.int32), ctypes.c_int(0)
+    nr = lib.hevcdl_frame_qp_grouping(qps.ctypes.data, n, perm.ctypes.data, rq.ctypes.data, rf.ctypes.data, rc.ctypes.data, ctypes.byref(cont))
+    if nr < 0:
+        raise HevcdlError(1, "hevcdl_frame_qp_grouping: a picture's QP lies outside 0 .. 51")
+    return perm[:n], [(int(rq[i]), int(rf[i]), int(rc[i])) for i in range(nr)], bool(cont.value)
+
+
+def frame_qp_check(cfg, qps=None, lambda_modifier=1.0):
+    """What hevcdl_set_frame_qps / hevcdl_set_lambda_modifier would answer on a context of cfg (hevcdl_frame_qp_check; no GPU needed) -> (status, sentence)."""
+    lib = load_library()
+    qps = None if qps is None else np.ascontiguousarray(qps, np.int32).reshape(-1)
+    why = ctypes.c_char_p()
+    st = lib.hevcdl_frame_qp_check(ctypes.byref(cfg), None if qps is None else qps.ctypes.data, 0 if qps is None else int(qps.size), float(lambda_modifier), ctypes.byref(why))
+    return int(st), (why.value or b"").decode()
+
+
+def frame_permute_step(ranges, perm, scatter, guard_bytes, device=0):
+    """TEST AND DIAGNOSTIC: the permute kernel alone (hevcdl_frame_permute_step).  ranges: [(src [n * bytes] uint8, dst [guard + n * bytes + guard] uint8)], at most four;
+    the destinations are updated in place."""
+    lib = load_library()
+    perm = np.ascontiguousarray(perm, np.int32).reshape(-1)
+    n, k = int(perm.size), len(ranges)
+    bytes_ = (ctypes.c_size_t * k)(*[int(s.size) // n for s, _ in ranges])
+    srcs = (ctypes.c_void_p * k)(*[s.ctypes.data for s, _ in ranges])
+    dsts = (ctypes.c_void_p * k)(*[d.ctypes.data for _, d in ranges])
+    for (s, d), b in zip(ranges, bytes_):
+        if s.dtype != np.uint8 or d.dtype != np.uint8 or s.size != n * b or d.size != n * b + 2 * int(guard_bytes):
+            raise ValueError("a range is n pictures of bytes, its destination the same with a margin either side")
+    st = lib.hevcdl_frame_permute_step(int(device), k, bytes_, n, perm.ctypes.data, int(bool(scatter)), srcs, dsts, int(guard_bytes))
+    if st:
+        raise HevcdlError(st, "hevcdl_frame_permute_step")
 
 
 def qp_rd_candidates(cfg):
@@ -875,6 +964,33 @@ class Encoder:
     def _frames(self, yuv):
         yuv = np.ascontiguousarray(yuv, self.sample_dtype).reshape(-1, self.frame_samples)
         return yuv, yuv.shape[0]
+
+    # ---- a QP per picture (hevcdl_set_frame_qps) ----
+    def set_frame_qps(self, qps):
+        """Picture i of every following decision, filter or picture-pipeline call is coded at qps[i]; pictures past the list take the context's QP.  None or an empty
+        list returns to the context's one QP."""
+        if qps is None or len(qps) == 0:
+            self._check(self.lib.hevcdl_set_frame_qps(self._h, None, 0))
+            return
+        q = np.ascontiguousarray(qps, np.int32).reshape(-1)
+        self._check(self.lib.hevcdl_set_frame_qps(self._h, q.ctypes.data, int(q.size)))
+
+    def set_lambda_modifier(self, lambda_modifier):
+        """The factor every picture's lambda is multiplied by before anything is derived from it (LambdaModifierI, else LambdaModifier0); 1.0 changes no bit."""
+        self._check(self.lib.hevcdl_set_lambda_modifier(self._h, float(lambda_modifier)))
+
+    def get_frame_qps(self, first, count):
+        """The QP of pictures [first, first + count) of the last decision call -> [count] int32."""
+        out = np.zeros(max(int(count), 1), np.int32)
+        self._check(self.lib.hevcdl_get_frame_qps(self._h, int(first), int(count), out.ctypes.data))
+        return out[:int(count)]
+
+    def get_frame_qp_info(self, want_ms=False):
+        """TEST AND DIAGNOSTIC: (bytes of the sorted sets, decision launches, permute launches[, (gather ms, scatter ms)]) of the last decision call."""
+        b, r, k = ctypes.c_size_t(0), ctypes.c_int(0), ctypes.c_int(0)
+        ms = (ctypes.c_double * 2)() if want_ms else None
+        self._check(self.lib.hevcdl_get_frame_qp_info(self._h, ctypes.byref(b), ctypes.byref(r), ctypes.byref(k), ms))
+        return (int(b.value), int(r.value), int(k.value)) + (((float(ms[0]), float(ms[1])),) if want_ms else ())
 
     # ---- source pictures that are not in the context's own format (hevcdl_set_source_format) ----
     def set_source_format(self, fmt):

@@ -14,6 +14,7 @@
 #include "rd_launch_plan.h"
 #include "slice_grid.h"
 #include "qp_rd.h"
+#include "frame_qp.h"
 
 enum { LABELS_PER_CTU = 16, LOGITS_PER_CTU = 64, CTU_RGB_BYTES = 64 * 64 * 3 };      // of a CTU: its 16x16 cells, four logits a cell, the RGB input of hevcdl_predict_depth_rgb
 
@@ -155,6 +156,20 @@ struct QpRd {
   std::vector<hevcdl_qp_rd_row> h_rows;  // ... and its rows, fetched once (hevcdl_get_qp_rd then copies from here, also inside a chunk callback); empty behind a *_dev call
 };
 
+// A QP per picture (hevcdl_set_frame_qps, hevcdl_set_lambda_modifier; frame_qp.h, frame_permute_kernel.hip): the list and the modifier as set; the QPs of the last decision
+// call; the two sorted sets -- originals and labels the gather fills, records / reconstruction / statistics the decision launches fill and the scatter empties -- for
+// max_frames pictures, all or nothing, by the first call whose list is not contiguous runs (or hevcdl_reserve_workspace).  A context that never sets a list or a modifier
+// allocates and launches none of it.  Not DeltaQpRD's trial set: the two keys exclude each other.
+struct FrameQp {
+  std::vector<int> list; double lambda_modifier = 1.0;
+  bool active() const { return !list.empty() || lambda_modifier != 1.0; }
+  std::vector<int> used;                 // the QP of every picture of the last decision call
+  std::vector<int> perm;                 // of the last permuted call: sorted place -> picture; the host copy the upload reads (it lives until the next call)
+  DevBuf<uint8_t> d_yuv, d_labels, d_recon; DevBuf<unsigned char> d_records, d_stats; DevBuf<int> d_perm;      // d_perm: [max_frames], read by the gather and (as its inverse) by the scatter
+  size_t set_bytes = 0; int rd_launches = 0, permute_launches = 0;
+  std::vector<Event> ev_permute;         // with hevcdl_profile_enable: start / stop pairs round the gather and the scatter launch of the last call
+};
+
 struct hevcdl_ctx {
   char last_rd[160] = { 0 };           // which build and launch form the last decision launch took (hevcdl_last_rd_launch)
   hevcdl_config cfg = {};              // as created -- but with slices its tile fields hold the grid the context RUNS (hevcdl_create): a column of row slices for SliceMode 1
@@ -165,7 +180,7 @@ struct hevcdl_ctx {
   int col_bd[21] = { 0 }, row_bd[23] = { 0 };    // tile boundaries in CTUs
   DevBuf<float> d_weights, d_a3; size_t a3_ctus = 0;   // d_a3: conv3 outputs of one chunk of CTUs (32 KB per CTU): the hand-over from the conv kernel to the head kernel
   DevBuf<int> d_flag;                  // device-side error flag of the label check
-  Staging stage; SaoWorkspace sao; Quality q; Report rp; Entropy ec; Source src; Session ses; RdWorkspace rd; DbkSelect dbk; QpRd qprd;
+  Staging stage; SaoWorkspace sao; Quality q; Report rp; Entropy ec; Source src; Session ses; RdWorkspace rd; DbkSelect dbk; QpRd qprd; FrameQp fqp;
   int ec_capacity_per_ctu = 0;         // hevcdl_set_entropy_capacity (tests): 0 = the default; outlives the entropy switch
   bool profile = false;
   std::vector<Event> ev_cnn, ev_rd, ev_conv;       // start/stop pairs (ev_conv: the convolution kernel alone, one pair per chunk of CTUs)
@@ -708,6 +723,67 @@ static hevcdl_status qp_rd_search(hevcdl_ctx *ctx, const void *d_yuv, int n_fram
   return HEVCDL_OK;
 }
 
+// ---- a QP per picture: one decision launch per run of equal QP (frame_qp.h) ----------------------------------------------------------------------------------------------
+// the two sorted sets and the permutations, all or nothing, for max_frames pictures
+static hevcdl_status ensure_frame_qp_sets(hevcdl_ctx *ctx)
+{
+  FrameQp &g = ctx->fqp;
+  if (g.d_perm) return HEVCDL_OK;
+  const size_t nf = (size_t)ctx->cfg.max_frames;
+  TRY(alloc_all(ctx, { want(g.d_records, ctx->records_bytes(nf)), want(g.d_yuv, ctx->frame_bytes * nf), want(g.d_recon, ctx->frame_bytes * nf), want(g.d_labels, ctx->labels_bytes(nf)),
+                       want(g.d_stats, sizeof(hevcdl_frame_stats) * nf), want(g.d_perm, sizeof(int) * nf) },
+                "sorted picture sets of a QP per picture (originals, labels, records, reconstruction and statistics of cfg.max_frames pictures)"));
+  g.set_bytes = ctx->records_bytes(nf) + 2 * ctx->frame_bytes * nf + ctx->labels_bytes(nf) + sizeof(hevcdl_frame_stats) * nf + sizeof(int) * nf;
+  return HEVCDL_OK;
+}
+
+// the QP of picture i of a call: the list's, past its end the context's
+static int frame_qp_at(const hevcdl_ctx *ctx, int i) { return i < (int)ctx->fqp.list.size() ? ctx->fqp.list[(size_t)i] : ctx->cfg.qp; }
+
+static hevcdl_status frame_qp_decide(hevcdl_ctx *ctx, const void *d_yuv, int n_frames, const void *d_labels, void *d_records, void *d_recon, void *d_stats, hipStream_t s)
+{
+  FrameQp &g = ctx->fqp;
+  g.used.resize((size_t)n_frames);
+  for (int i = 0; i < n_frames; i++) g.used[(size_t)i] = frame_qp_at(ctx, i);
+  g.rd_launches = 0; g.permute_launches = 0; g.ev_permute.clear();
+  std::vector<hevcdl_qp_run> runs((size_t)std::min(n_frames, 52));
+  int n_runs = hevcdl_frame_qp_contiguous_runs(g.used.data(), n_frames, runs.data());
+  if (n_runs < 0) return fail(ctx, HEVCDL_ERR_INVALID_ARG, HEVCDL_FRAME_QP_REFUSE_RANGE);
+  const bool permuted = n_runs == 0;
+  const unsigned char *yuv = (const unsigned char *)d_yuv, *labels = (const unsigned char *)d_labels;
+  unsigned char *records = (unsigned char *)d_records, *recon = (unsigned char *)d_recon, *stats = (unsigned char *)d_stats;
+  hevcdl_frame_permute_params pp; memset(&pp, 0, sizeof pp);
+  if (permuted) { // bring the pictures together by QP: the runs are those of the sorted order, the launches read and write the sorted sets
+    TRY(ensure_frame_qp_sets(ctx));
+    g.perm.resize((size_t)n_frames);
+    n_runs = hevcdl_frame_qp_group(g.used.data(), n_frames, g.perm.data(), runs.data(), nullptr);
+    HIPCHK(hipMemcpyAsync(g.d_perm, g.perm.data(), sizeof(int) * (size_t)n_frames, hipMemcpyHostToDevice, s));
+    pp.perm = g.d_perm; pp.n_frames = n_frames; pp.scatter = 0; pp.n_ranges = 2;
+    pp.r[0].src = yuv; pp.r[0].dst = g.d_yuv; pp.r[0].bytes = ctx->frame_bytes;
+    pp.r[1].src = labels; pp.r[1].dst = g.d_labels; pp.r[1].bytes = ctx->labels_bytes(1);
+    prof_begin(ctx, g.ev_permute, s); hevcdl_launch_frame_permute(&pp, s); prof_end(ctx, g.ev_permute, s); g.permute_launches++;
+    HIPCHK(hipGetLastError());
+    yuv = g.d_yuv; labels = g.d_labels; records = g.d_records; recon = g.d_recon; stats = d_stats ? g.d_stats.p : nullptr;
+  }
+  for (int r = 0; r < n_runs; r++) { // the plan of every launch is rd_launch_plan's for the run's frame count; its constants are the run's lambda family
+    hevcdl_qp_rd_candidate fam;
+    hevcdl_frame_qp_family(runs[(size_t)r].qp, ctx->cfg.bit_depth, g.lambda_modifier, &fam);
+    const size_t f0 = (size_t)runs[(size_t)r].first;
+    TRY(launch_rd(ctx, yuv + ctx->frame_bytes * f0, runs[(size_t)r].count, labels + ctx->labels_bytes(f0), records + ctx->records_bytes(f0), recon + ctx->frame_bytes * f0,
+                  stats ? stats + sizeof(hevcdl_frame_stats) * f0 : nullptr, s, 0, -1, nullptr, nullptr, 0, -1, -1, &fam));
+    g.rd_launches++;
+  }
+  if (permuted) { // back to picture order: sorted place i goes to picture perm[i]
+    pp.scatter = 1; pp.n_ranges = d_stats ? 3 : 2;
+    pp.r[0].src = g.d_records; pp.r[0].dst = (unsigned char *)d_records; pp.r[0].bytes = ctx->records_bytes(1);
+    pp.r[1].src = g.d_recon; pp.r[1].dst = (unsigned char *)d_recon; pp.r[1].bytes = ctx->frame_bytes;
+    pp.r[2].src = g.d_stats; pp.r[2].dst = (unsigned char *)d_stats; pp.r[2].bytes = sizeof(hevcdl_frame_stats);
+    prof_begin(ctx, g.ev_permute, s); hevcdl_launch_frame_permute(&pp, s); prof_end(ctx, g.ev_permute, s); g.permute_launches++;
+    HIPCHK(hipGetLastError());
+  }
+  return HEVCDL_OK;
+}
+
 // caller-supplied labels (device copy): boundary clamp + quadtree consistency in place; labels above 3 -> HEVCDL_ERR_INVALID_ARG
 extern "C" hevcdl_status hevcdl_clamp_labels_dev(hevcdl_ctx *ctx, void *d_labels, int n_frames, void *stream)
 {
@@ -743,6 +819,8 @@ extern "C" hevcdl_status hevcdl_compress_frames_dev(hevcdl_ctx *ctx, const void 
   FRAMES_OR_RETURN(ctx, n_frames);
   if (!d_yuv || !d_labels || !d_records || !d_recon) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null device pointer");
   if (ctx->qprd.n) return qp_rd_search(ctx, d_yuv, n_frames, d_labels, d_records, d_recon, d_stats, (hipStream_t)stream);
+  if (ctx->fqp.active()) return frame_qp_decide(ctx, d_yuv, n_frames, d_labels, d_records, d_recon, d_stats, (hipStream_t)stream);
+  ctx->fqp.used.assign((size_t)n_frames, ctx->cfg.qp); ctx->fqp.rd_launches = 1; ctx->fqp.permute_launches = 0;
   return launch_rd(ctx, d_yuv, n_frames, d_labels, d_records, d_recon, d_stats, (hipStream_t)stream);
 }
 
@@ -751,6 +829,7 @@ extern "C" hevcdl_status hevcdl_compress_tiles_dev(hevcdl_ctx *ctx, const void *
 {
   TRY(check_frames(ctx, n_frames));
   if (ctx->qprd.n) return fail(ctx, HEVCDL_ERR_UNSUPPORTED, "compress_tiles: DeltaQpRD picks a QP per picture from the sums of ALL its tiles; a range of tiles cannot (use hevcdl_compress_frames_dev)");
+  if (ctx->fqp.active()) return fail(ctx, HEVCDL_ERR_UNSUPPORTED, HEVCDL_FRAME_QP_REFUSE_TILES);
   if (tile_begin < 0 || tile_count < 0 || tile_begin + tile_count > ctx->cfg.tile_columns * ctx->cfg.tile_rows) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "tile range outside the tile grid");
   if (n_frames == 0 || tile_count == 0) return HEVCDL_OK;
   if (!d_yuv || !d_labels || !d_records || !d_recon) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null device pointer");
@@ -845,6 +924,7 @@ extern "C" hevcdl_status hevcdl_reserve_workspace(hevcdl_ctx *ctx)
   if (!ctx) return HEVCDL_ERR_INVALID_ARG;
   HIPCHK(hipSetDevice(ctx->cfg.device));
   if (ctx->qprd.n) TRY(ensure_qp_rd_trial(ctx));      // DeltaQpRD: the trial set is part of what the decisions need
+  if (!ctx->fqp.list.empty()) TRY(ensure_frame_qp_sets(ctx));      // a QP per picture: so are the sorted sets (a list that is contiguous runs never touches them)
   const size_t need = ctx->rd.scratch_per_wave * rd_largest_scratch_blocks(ctx->rd.plan);
   if (need <= ctx->rd.scratch_bytes) return HEVCDL_OK;
   HIPCHK(hipDeviceSynchronize());
@@ -947,14 +1027,14 @@ extern "C" hevcdl_status hevcdl_deblock_frames_qp_dev(hevcdl_ctx *ctx, const voi
   p.lf_across_tiles = ctx->cfg.lf_across_tiles != 0; p.tile_cols = ctx->cfg.tile_columns; p.tile_rows = ctx->cfg.tile_rows;
   memcpy(p.col_bd, ctx->col_bd, sizeof p.col_bd); memcpy(p.row_bd, ctx->row_bd, sizeof p.row_bd);
   p.frame_params = nullptr;
-  if (choices || idx) { // a row of (tc, beta, tc_c, disabled) per picture, uploaded in front of the launch on its stream (the host copy lives in the context until the next call)
+  if (choices || idx || !ctx->fqp.list.empty()) { // a row of (tc, beta, tc_c, disabled) per picture, uploaded in front of the launch on its stream (the host copy lives in the context until the next call)
     for (int i = 0; choices && i < n_frames; i++)
       if (choices[i].beta_offset_div2 < -6 || choices[i].beta_offset_div2 > 6 || choices[i].tc_offset_div2 < -6 || choices[i].tc_offset_div2 > 6) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "a picture's deblocking offsets are out of range (-6 .. 6)");
     TRY(lazy_alloc(ctx, ctx->dbk.d_frame_params, sizeof(int) * 4 * (size_t)ctx->cfg.max_frames, "per-picture deblocking parameters (cfg.max_frames)"));
     std::vector<int> &h = ctx->dbk.h_frame_params;
     h.assign((size_t)4 * n_frames, 0);
     for (int i = 0; i < n_frames; i++) {
-      const int qp = idx ? ctx->qprd.cand[idx[i]].qp : ctx->cfg.qp;
+      const int qp = idx ? ctx->qprd.cand[idx[i]].qp : frame_qp_at(ctx, i);      // a candidate's (DeltaQpRD), the list's (hevcdl_set_frame_qps) or the context's
       dbk_triple(ctx, qp, choices ? choices[i].beta_offset_div2 : ctx->cfg.lf_beta_offset_div2, choices ? choices[i].tc_offset_div2 : ctx->cfg.lf_tc_offset_div2, &h[4 * i], &h[4 * i + 1], &h[4 * i + 2]);
       h[4 * i + 3] = choices && choices[i].disabled != 0;
     }
@@ -1106,14 +1186,18 @@ extern "C" hevcdl_status hevcdl_sao_frames_dev(hevcdl_ctx *ctx, const void *d_or
   return hevcdl_sao_frames_qp_dev(ctx, d_org, d_deblocked, n_frames, nullptr, d_params, d_out, stream);
 }
 
-// the per-picture QP table of a batch (hevcdl_frame_qp) from the pictures' candidate indices, uploaded in front of the launches that read it on their stream (the host
+// the per-picture QP table of a batch (hevcdl_frame_qp) from the pictures' candidate indices -- or, idx NULL, from the list and the modifier of hevcdl_set_frame_qps --, uploaded in front of the launches that read it on their stream (the host
 // copy lives in the context until the next call, like the deblocking rows)
 static hevcdl_status upload_frame_qp(hevcdl_ctx *ctx, const int32_t *idx, int n_frames, hipStream_t s)
 {
   TRY(lazy_alloc(ctx, ctx->qprd.d_frame_qp, sizeof(hevcdl_frame_qp) * (size_t)ctx->cfg.max_frames, "per-picture QP table (cfg.max_frames)"));
   std::vector<hevcdl_frame_qp> &h = ctx->qprd.h_frame_qp;
   h.resize((size_t)n_frames);
-  for (int i = 0; i < n_frames; i++) { const hevcdl_qp_rd_candidate &c = ctx->qprd.cand[idx[i]]; h[(size_t)i] = hevcdl_frame_qp{ c.lambda, c.lambda_chroma, c.qp, 0 }; }      // slice lambdas per component, TEncSlice.cpp:112-140, 656-660
+  for (int i = 0; i < n_frames; i++) {
+    hevcdl_qp_rd_candidate fam;
+    if (!idx) hevcdl_frame_qp_family(frame_qp_at(ctx, i), ctx->cfg.bit_depth, ctx->fqp.lambda_modifier, &fam);
+    const hevcdl_qp_rd_candidate &c = idx ? ctx->qprd.cand[idx[i]] : fam; h[(size_t)i] = hevcdl_frame_qp{ c.lambda, c.lambda_chroma, c.qp, 0 };
+  }      // slice lambdas per component, TEncSlice.cpp:112-140, 656-660
   HIPCHK(hipMemcpyAsync(ctx->qprd.d_frame_qp, h.data(), sizeof(hevcdl_frame_qp) * h.size(), hipMemcpyHostToDevice, s));
   return HEVCDL_OK;
 }
@@ -1135,7 +1219,7 @@ extern "C" hevcdl_status hevcdl_sao_frames_qp_dev(hevcdl_ctx *ctx, const void *d
   p.tile_cols = ctx->cfg.tile_columns; p.tile_rows = ctx->cfg.tile_rows; p.bit_depth = ctx->cfg.bit_depth; p.lf_across_tiles = ctx->cfg.lf_across_tiles != 0;
   memcpy(p.col_bd, ctx->col_bd, sizeof p.col_bd); memcpy(p.row_bd, ctx->row_bd, sizeof p.row_bd);
   p.frame_qp = nullptr;
-  if (idx) { TRY(upload_frame_qp(ctx, idx, n_frames, (hipStream_t)stream)); p.frame_qp = ctx->qprd.d_frame_qp; }
+  if (idx || ctx->fqp.active()) { TRY(upload_frame_qp(ctx, idx, n_frames, (hipStream_t)stream)); p.frame_qp = ctx->qprd.d_frame_qp; }
   hevcdl_launch_sao(&p, stream);
   return launch_status(ctx);
 }
@@ -1904,8 +1988,9 @@ static hevcdl_status entropy_pipeline(hevcdl_ctx *ctx, int n_frames, int want_sa
   const size_t rec_b = ctx->records_bytes(1), sao_b = ctx->sao_bytes(1);
   ctx->ec.h_slice.clear(); ctx->ec.h_slice_sizes.assign((size_t)n_frames * units, 0); ctx->ec.h_slice_at.assign((size_t)n_frames + 1, 0); ctx->ec.ec_fallbacks = 0;
   std::vector<uint32_t> ovf; std::vector<unsigned long long> dst; std::vector<int> fallback;
-  const bool per_picture_qp = ctx->qprd.n != 0 && (int)ctx->qprd.h_idx.size() == n_frames;      // DeltaQpRD: the contexts of every picture start from its own QP
-  if (per_picture_qp) TRY(upload_frame_qp(ctx, ctx->qprd.h_idx.data(), n_frames, nullptr));
+  const bool searched = ctx->qprd.n != 0 && (int)ctx->qprd.h_idx.size() == n_frames;      // DeltaQpRD: the contexts of every picture start from its own QP
+  const bool per_picture_qp = searched || !ctx->fqp.list.empty();                          // ... as with a list of hevcdl_set_frame_qps
+  if (per_picture_qp) TRY(upload_frame_qp(ctx, searched ? ctx->qprd.h_idx.data() : nullptr, n_frames, nullptr));
   for (int first = 0; first < n_frames; first += ctx->ec.ec_pass_frames) {
     const int cnt = std::min(ctx->ec.ec_pass_frames, n_frames - first); const size_t n_sub = (size_t)cnt * units;
     hevcdl_entropy_params k = pl.k;
@@ -1960,7 +2045,7 @@ static hevcdl_status entropy_pipeline(hevcdl_ctx *ctx, int n_frames, int want_sa
         HIPCHK(hipMemcpy(rec.data(), ctx->stage.d_records + rec_b * f, rec_b, hipMemcpyDeviceToHost));
         if (want_sao) HIPCHK(hipMemcpy(sao.data(), ctx->sao.d_sao_params + sao_b * f, sao_b, hipMemcpyDeviceToHost));
         size_t total = 0; uint32_t *sz = ctx->ec.h_slice_sizes.data() + (size_t)f * units;
-        if (per_picture_qp) sc.qp = ctx->qprd.cand[ctx->qprd.h_idx[(size_t)f]].qp;
+        if (per_picture_qp) sc.qp = searched ? ctx->qprd.cand[ctx->qprd.h_idx[(size_t)f]].qp : frame_qp_at(ctx, f);
         hevcdl_host_writer_slice_data(&sc, &ctx->slices, &ctx->segments, rec.data(), want_sao ? sao.data() : nullptr, nullptr, 0, sz, &total);
         all.resize(at[(size_t)f] + total);
         if (hevcdl_host_writer_slice_data(&sc, &ctx->slices, &ctx->segments, rec.data(), want_sao ? sao.data() : nullptr, all.data() + at[(size_t)f], total, sz, &total) != 0) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "device entropy: host fallback");
@@ -2032,6 +2117,7 @@ extern "C" hevcdl_status hevcdl_begin_frames(hevcdl_ctx *ctx, const uint8_t *yuv
   TRY(check_frames(ctx, n_frames));
   if (ctx->slices.mode != 0) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "begin_frames: the per-CTU session does not code slices; use hevcdl_compress_frames");
   if (ctx->qprd.n) return fail(ctx, HEVCDL_ERR_UNSUPPORTED, "begin_frames: the per-CTU session does not search the slice QP (DeltaQpRD codes every picture 2N+1 times); use hevcdl_compress_frames");
+  if (ctx->fqp.active()) return fail(ctx, HEVCDL_ERR_UNSUPPORTED, HEVCDL_FRAME_QP_REFUSE_SESSION);
   if (n_frames == 0 || !yuv) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "begin_frames: no frames");
   TRY(ensure_staging(ctx));
   TRY(lazy_alloc(ctx, ctx->ses.d_cabac, sizeof(hevcdl_cabac_state) * (size_t)ctx->cfg.max_frames, "coder states of the per-CTU session (cfg.max_frames)"));
@@ -2163,6 +2249,132 @@ extern "C" hevcdl_status hevcdl_qp_rd_step(int device, int ctus_per_frame, size_
       if (e == hipSuccess && pic_b + 2 * g) e = hipMemcpy(recon, d_pic, pic_b + 2 * g, hipMemcpyDeviceToHost);
       if (e == hipSuccess) e = hipMemcpy(stats, d_stat, stat_b + 2 * g, hipMemcpyDeviceToHost);
     }
+  }
+  if (e != hipSuccess) return hip_fail(nullptr, "", e);
+  return HEVCDL_OK;
+}
+
+// ---- a QP per picture: the public side (the grouped decisions: frame_qp_decide above) ----------------------------------------------------------------------------------
+extern "C" hevcdl_status hevcdl_frame_qp_check(const hevcdl_config *cfg, const int *qp, int n, double lambda_modifier, const char **why)
+{
+  static const char *none = "";
+  if (!cfg || n < 0) { if (why) *why = none; return HEVCDL_ERR_INVALID_ARG; }
+  const char *w = none;
+  const hevcdl_status st = hevcdl_frame_qp_keys(cfg, qp, n, lambda_modifier, &w);
+  if (why) *why = w;
+  return st;
+}
+
+extern "C" hevcdl_status hevcdl_set_frame_qps(hevcdl_ctx *ctx, const int *qp, int n)
+{
+  if (!ctx) return HEVCDL_ERR_INVALID_ARG;
+  if (n < 0) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "hevcdl_set_frame_qps: n < 0");
+  if (!qp || n == 0) { ctx->fqp.list.clear(); return HEVCDL_OK; }
+  const char *why = "";
+  const hevcdl_status st = hevcdl_frame_qp_keys(&ctx->cfg, qp, n, ctx->fqp.lambda_modifier, &why);
+  if (st != HEVCDL_OK) return fail(ctx, st, why);
+  ctx->fqp.list.assign(qp, qp + n);
+  return HEVCDL_OK;
+}
+
+extern "C" hevcdl_status hevcdl_set_lambda_modifier(hevcdl_ctx *ctx, double lambda_modifier)
+{
+  if (!ctx) return HEVCDL_ERR_INVALID_ARG;
+  const char *why = "";
+  const hevcdl_status st = hevcdl_frame_qp_keys(&ctx->cfg, ctx->fqp.list.data(), (int)ctx->fqp.list.size(), lambda_modifier, &why);
+  if (st != HEVCDL_OK) return fail(ctx, st, why);
+  ctx->fqp.lambda_modifier = lambda_modifier;
+  return HEVCDL_OK;
+}
+
+extern "C" hevcdl_status hevcdl_get_frame_qps(hevcdl_ctx *ctx, int first, int count, int32_t *qp)
+{
+  if (!ctx) return HEVCDL_ERR_INVALID_ARG;
+  TRY(check_batch_range(ctx, "hevcdl_get_frame_qps", qp != nullptr, true, "", first, count, (long long)ctx->fqp.used.size()));
+  for (int i = 0; i < count; i++) qp[i] = ctx->fqp.used[(size_t)first + i];
+  return HEVCDL_OK;
+}
+
+extern "C" hevcdl_status hevcdl_frame_qp_list(int base_qp, const int *dqp, int n, int intra_qp_offset, int bit_depth, int *out)
+{
+  if (n < 0 || (n && !out) || (bit_depth != 8 && bit_depth != 10) || base_qp < 0 || base_qp > 51) return HEVCDL_ERR_INVALID_ARG;
+  for (int i = 0; i < n; i++) {
+    out[i] = hevcdl_frame_qp_of(base_qp, dqp ? dqp[i] : 0, intra_qp_offset, bit_depth);
+    if (out[i] < 0) return HEVCDL_ERR_INVALID_ARG;
+  }
+  return HEVCDL_OK;
+}
+
+extern "C" hevcdl_status hevcdl_frame_qp_offsets(int n, int qpif, int frame_skip, int temporal_subsample_ratio, const char *dqp_file, int *dqp, int *file_values)
+{
+  if (n < 0 || (n && !dqp) || frame_skip < 0 || temporal_subsample_ratio < 1) return HEVCDL_ERR_INVALID_ARG;
+  if (file_values) *file_values = 0;
+  hevcdl_dqp_increment(dqp, n, qpif >= 0, (unsigned)(qpif >= 0 ? qpif : 0), (unsigned)frame_skip, (unsigned)temporal_subsample_ratio);
+  if (dqp_file && dqp_file[0]) {
+    const int got = hevcdl_dqp_read_file(dqp_file, dqp, n);
+    if (got < 0) return HEVCDL_ERR_INVALID_ARG;
+    if (file_values) *file_values = got;
+  }
+  return HEVCDL_OK;
+}
+
+extern "C" hevcdl_status hevcdl_frame_qp_families(int qp, int bit_depth, double lambda_modifier, hevcdl_qp_rd_candidate *out)
+{
+  if (!out || qp < 0 || qp > 51 || (bit_depth != 8 && bit_depth != 10) || !(lambda_modifier > 0.0) || !(lambda_modifier < 1.0e30)) return HEVCDL_ERR_INVALID_ARG;
+  hevcdl_frame_qp_family(qp, bit_depth, lambda_modifier, out);
+  return HEVCDL_OK;
+}
+
+extern "C" int hevcdl_frame_qp_grouping(const int *qp, int n, int *perm, int *run_qp, int *run_first, int *run_count, int *contiguous)
+{
+  if (n < 0 || (n && (!qp || !perm)) || !run_qp || !run_first || !run_count) return -1;
+  std::vector<hevcdl_qp_run> runs(52);
+  const int n_runs = hevcdl_frame_qp_group(qp, n, perm, runs.data(), nullptr);
+  if (n_runs < 0) return -1;
+  for (int r = 0; r < n_runs; r++) { run_qp[r] = runs[(size_t)r].qp; run_first[r] = runs[(size_t)r].first; run_count[r] = runs[(size_t)r].count; }
+  if (contiguous) *contiguous = n == 0 || hevcdl_frame_qp_contiguous_runs(qp, n, runs.data()) > 0;
+  return n_runs;
+}
+
+extern "C" hevcdl_status hevcdl_get_frame_qp_info(hevcdl_ctx *ctx, size_t *set_bytes, int *rd_launches, int *permute_launches, double *kernel_ms_opt)
+{
+  if (!ctx || !set_bytes || !rd_launches || !permute_launches) return HEVCDL_ERR_INVALID_ARG;
+  *set_bytes = ctx->fqp.d_perm ? ctx->fqp.set_bytes : 0; *rd_launches = ctx->fqp.rd_launches; *permute_launches = ctx->fqp.permute_launches;
+  if (kernel_ms_opt) { // the gather pair first, then the scatter pair; zeros without hevcdl_profile_enable or when nothing was copied
+    TRY(sync_or_fail(ctx, "hevcdl_get_frame_qp_info"));
+    std::vector<Event> &v = ctx->fqp.ev_permute;
+    for (int i = 0; i < 2; i++) { float t = 0; kernel_ms_opt[i] = (v.size() == 4 && hipEventElapsedTime(&t, v[(size_t)2 * i], v[(size_t)2 * i + 1]) == hipSuccess) ? t : 0.0; }
+    v.clear();
+  }
+  return HEVCDL_OK;
+}
+
+// the kernel alone (host buffers, no context): the destinations travel with their guard margins, so that a write outside a payload shows in what comes back
+extern "C" hevcdl_status hevcdl_frame_permute_step(int device, int n_ranges, const size_t *bytes, int n_frames, const int *perm, int scatter, const void *const *src, void *const *dst, size_t guard_bytes)
+{
+  if (n_ranges < 1 || n_ranges > 4 || n_frames < 1 || n_frames > 65535 || !bytes || !perm || !src || !dst) return HEVCDL_ERR_INVALID_ARG;
+  { std::vector<char> seen((size_t)n_frames, 0);
+    for (int i = 0; i < n_frames; i++) { if (perm[i] < 0 || perm[i] >= n_frames || seen[(size_t)perm[i]]) return HEVCDL_ERR_INVALID_ARG; seen[(size_t)perm[i]] = 1; } }
+  for (int k = 0; k < n_ranges; k++) if (!bytes[k] || !src[k] || !dst[k]) return HEVCDL_ERR_INVALID_ARG;
+  TRY(select_device(device));
+  const size_t nf = (size_t)n_frames, g = guard_bytes;
+  DevBuf<unsigned char> d_src[4], d_dst[4]; DevBuf<int> d_perm;
+  hipError_t e = hipMalloc(&d_perm.p, sizeof(int) * nf);
+  for (int k = 0; k < n_ranges && e == hipSuccess; k++) {
+    e = hipMalloc(&d_src[k].p, bytes[k] * nf);
+    if (e == hipSuccess) e = hipMalloc(&d_dst[k].p, bytes[k] * nf + 2 * g);
+    if (e == hipSuccess) e = hipMemcpy(d_src[k], src[k], bytes[k] * nf, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_dst[k], dst[k], bytes[k] * nf + 2 * g, hipMemcpyHostToDevice);
+  }
+  if (e == hipSuccess) e = hipMemcpy(d_perm, perm, sizeof(int) * nf, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hevcdl_frame_permute_params p; memset(&p, 0, sizeof p);
+    p.perm = d_perm; p.n_frames = n_frames; p.n_ranges = n_ranges; p.scatter = scatter != 0;
+    for (int k = 0; k < n_ranges; k++) { p.r[k].src = d_src[k]; p.r[k].dst = d_dst[k] + g; p.r[k].bytes = bytes[k]; }
+    hevcdl_launch_frame_permute(&p, nullptr);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    for (int k = 0; k < n_ranges && e == hipSuccess; k++) e = hipMemcpy(dst[k], d_dst[k], bytes[k] * nf + 2 * g, hipMemcpyDeviceToHost);
   }
   if (e != hipSuccess) return hip_fail(nullptr, "", e);
   return HEVCDL_OK;

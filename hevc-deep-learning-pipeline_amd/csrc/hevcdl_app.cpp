@@ -35,6 +35,7 @@
 #include "hevcdl.h"
 #include "slice_grid.h"      // hevcdl_segment_keys: the segment keys are refused here with the library's own sentences
 #include "qp_rd.h"           // hevcdl_qp_rd_keys: likewise DeltaQpRD
+#include "frame_qp.h"        // the rule of a QP per picture (dQPFile, QPIncrementFrame, IntraQPOffset, LambdaModifierI / 0) and its refusals
 
 namespace {
 
@@ -46,6 +47,8 @@ const Key KEYS[] = {
   { "InputFile", "i", USED, 0 }, { "BitstreamFile", "b", USED, 0 }, { "ReconFile", "o", USED, 0 }, { "SourceWidth", "wdt", USED, 0 },
   { "SourceHeight", "hgt", USED, 0 }, { "FrameRate", "fr", USED, 0 }, { "FrameSkip", "fs", USED, 0 }, { "FramesToBeEncoded", "f", USED, 0 },
   { "QP", "q", USED, 0 },
+  // a QP per picture (TAppEncCfg.cpp:866, 871, 899, 853, 860; csrc/frame_qp.h): the offsets are computed once for the sequence, every batch sets its slice (hevcdl_set_frame_qps)
+  { "dQPFile", "m", USED, 0 }, { "QPIncrementFrame", "qpif", USED, 0 }, { "IntraQPOffset", 0, USED, 0 }, { "LambdaModifierI", "LMI", USED, 0 }, { "LambdaModifier0", "LM0", USED, 0 },
   // extensions of this front end
   { "LabelDir", 0, USED, 0 }, { "BatchFrames", 0, USED, 0 }, { "ChunkFrames", 0, USED, 0 }, { "Device", 0, USED, 0 }, { "Devices", 0, USED, 0 }, { "NumDevices", 0, USED, 0 }, { "Weights", 0, USED, 0 }, { "RecordFile", 0, USED, 0 }, { "DeviceEntropy", 0, USED, 0 }, { "DeviceReport", 0, USED, 0 },
   { "CnnInput", 0, USED, 0 }, { "BnMode", 0, USED, 0 }, { "PrintConfig", 0, USED, 0 }, { "LoopFilterDisable", 0, USED, 0 },
@@ -75,6 +78,10 @@ const Key KEYS[] = {
   { "PCMLog2MaxSize", 0, NOEFFECT, 0 }, { "PCMLog2MinSize", 0, NOEFFECT, 0 }, { "PCMInputBitDepthFlag", 0, NOEFFECT, 0 },
   { "PCMFilterDisableFlag", 0, NOEFFECT, 0 }, { "TileUniformSpacing", 0, USED, 0 }, { "TileColumnWidthArray", 0, USED, 0 },
   { "TileRowHeightArray", 0, USED, 0 }, { "ScalingListFile", 0, NOEFFECT, 0 },
+  // lambda keys that an all-intra GOP of 1 never reads (TEncSlice.cpp:459-474: temporal layers above 0 do not exist, an I slice of an I GOP entry takes 0.57 whatever
+  // IQPFactor says, and LambdaFromQpEnable picks the same 0.57 with no B pictures)
+  { "LambdaModifier1", "LM1", NOEFFECT, 0 }, { "LambdaModifier2", "LM2", NOEFFECT, 0 }, { "LambdaModifier3", "LM3", NOEFFECT, 0 }, { "LambdaModifier4", "LM4", NOEFFECT, 0 },
+  { "LambdaModifier5", "LM5", NOEFFECT, 0 }, { "LambdaModifier6", "LM6", NOEFFECT, 0 }, { "IQPFactor", "IQF", NOEFFECT, 0 }, { "LambdaFromQpEnable", 0, NOEFFECT, 0 },
 };
 
 const Key *find_key(const std::string &name, bool shortform)
@@ -363,8 +370,49 @@ int main(int argc, char **argv)
     if (delta_qp_rd < -1000 || delta_qp_rd > 1000) probe.delta_qp_rd = -1;
     if (hevcdl_qp_rd_keys(&probe, &why) != HEVCDL_OK) opt.errors.push_back("DeltaQpRD = " + std::to_string(delta_qp_rd) + ": " + why);
   }
+  // A QP per picture.  dQPFile ("-m"), QPIncrementFrame ("-qpif"), IntraQPOffset: qp[poc] = Clip3(-QpBDOffset, 51, QP + dqp[poc] + IntraQPOffset); LambdaModifierI
+  // (its first value: there is one temporal layer), else LambdaModifier0: the factor on every picture's lambda.  The rule and what is refused: csrc/frame_qp.h.
+  const std::string dqp_file = native_path(opt.get("dQPFile"));
+  const bool qpif_present = opt.v.count("QPIncrementFrame") && !opt.get("QPIncrementFrame").empty();
+  const long qpif = qpif_present ? opt.geti("QPIncrementFrame", 0) : -1, intra_qp_offset = opt.geti("IntraQPOffset", 0);
+  double lambda_modifier = 1.0;
+  if (opt.v.count("LambdaModifierI") && !opt.get("LambdaModifierI").empty()) lambda_modifier = atof(opt.get("LambdaModifierI").c_str());
+  else if (opt.v.count("LambdaModifier0")) lambda_modifier = atof(opt.get("LambdaModifier0").c_str());
+  if (qpif_present && qpif < 0) opt.errors.push_back("QPIncrementFrame = " + std::to_string(qpif) + " is not a source frame number");
+  const bool frame_qp_keys = !dqp_file.empty() || qpif_present || intra_qp_offset != 0;
+  // the QPs of pictures 0 .. n - 1 of the sequence; false with the sentence in `why`
+  auto sequence_qps = [&](long n, std::vector<int> &qps, std::string &why) -> bool {
+    std::vector<int> dqp((size_t)std::max<long>(n, 0));
+    hevcdl_dqp_increment(dqp.data(), (int)dqp.size(), qpif_present && qpif >= 0, (unsigned)std::max<long>(qpif, 0), (unsigned)std::max<long>(frame_skip, 0), (unsigned)std::max<long>(ts_ratio, 1));
+    if (!dqp_file.empty()) {
+      const int got = hevcdl_dqp_read_file(dqp_file.c_str(), dqp.data(), (int)dqp.size());
+      if (got == -1) { why = "dQPFile '" + dqp_file + "' cannot be opened"; return false; }
+      if (got < 0) { why = "dQPFile '" + dqp_file + "' must hold whitespace-separated integers of -64 .. 64, one a POC"; return false; }
+    }
+    qps.resize(dqp.size());
+    for (size_t i = 0; i < dqp.size(); i++) qps[i] = hevcdl_frame_qp_of(qp, dqp[i], (int)intra_qp_offset, bit_depth);
+    return true;
+  };
+  std::vector<int> seq_qps;
+  if (frame_qp_keys || lambda_modifier != 1.0) {
+    hevcdl_config probe; memset(&probe, 0, sizeof probe);
+    probe.qp = qp; probe.bit_depth = bit_depth; probe.deblocking_metric = (int)dbk_metric; probe.delta_qp_rd = (int)delta_qp_rd;
+    std::string why;
+    const long n_known = std::max<long>(1, (n_frames + std::max<long>(ts_ratio, 1) - 1) / std::max<long>(ts_ratio, 1));      // (FramesToBeEncoded 0: the file's length decides below; one picture shows every refusal but a value's)
+    if (frame_qp_keys && !sequence_qps(n_known, seq_qps, why)) opt.errors.push_back(why);
+    else {
+      const char *w = "";
+      if (hevcdl_frame_qp_keys(&probe, frame_qp_keys ? seq_qps.data() : nullptr, frame_qp_keys ? (int)seq_qps.size() : 0, lambda_modifier, &w) != HEVCDL_OK) opt.errors.push_back(w);
+    }
+  }
+  char qp_line[160];      // TAppEncCfg.cpp:2927-2933
+  if (qpif_present) snprintf(qp_line, sizeof qp_line, "QP                                     : %d (incrementing internal QP at source frame %ld)", qp, qpif);
+  else snprintf(qp_line, sizeof qp_line, "QP                                     : %d", qp);
   if (opt.v.count("PrintConfig")) {
     printf("{\"DeltaQpRD\": %ld, ", delta_qp_rd);
+    printf("\"QPLine\": \"%s\", \"dQPFile\": \"%s\", \"QPIncrementFrame\": %ld, \"IntraQPOffset\": %ld, \"LambdaModifier\": %.17g, \"FrameQPs\": [", qp_line, json_escape(dqp_file).c_str(), qpif, intra_qp_offset, lambda_modifier);
+    for (size_t i = 0; i < seq_qps.size(); i++) printf("%s%d", i ? ", " : "", seq_qps[i]);
+    printf("], ");
     printf("\"SliceMode\": %ld, \"SliceArgument\": %ld, \"LFCrossSliceBoundaryFlag\": %ld, \"SliceSegmentMode\": %ld, \"SliceSegmentArgument\": %ld, ", slice_mode, slice_arg, lf_slices, seg_mode, seg_arg);
     printf("\"InputFile\": \"%s\", \"ReconFile\": \"%s\", \"SourceWidth\": %d, \"SourceHeight\": %d, \"QP\": %d, \"FrameSkip\": %ld, \"FramesToBeEncoded\": %ld, "
            "\"FrameRate\": %g, \"LabelDir\": \"%s\", \"CnnInput\": \"%s\", \"BitstreamFile\": \"%s\", \"level_idc\": %d, \"tiles\": [%d, %d], \"bit_depth\": %d, "
@@ -403,6 +451,12 @@ int main(int argc, char **argv)
   if (avail <= 0) { fprintf(stderr, "Error: input holds no frame after FrameSkip\n"); return 2; }
   if (n_frames <= 0 || n_frames > avail) n_frames = avail;                    // TAppEncTop: stops at end of file
   n_frames = (n_frames + ts_ratio - 1) / ts_ratio;                            // source frames -> pictures: picture k is source frame FrameSkip + k * ratio; POCs are consecutive
+  if (frame_qp_keys) { // the QP of every picture of the sequence, once; every shard and batch takes its slice
+    std::string why; const char *w = "";
+    hevcdl_config probe; memset(&probe, 0, sizeof probe); probe.bit_depth = bit_depth;
+    if (!sequence_qps(n_frames, seq_qps, why)) { fprintf(stderr, "Error: %s\n", why.c_str()); return 2; }
+    if (hevcdl_frame_qp_keys(&probe, seq_qps.data(), (int)seq_qps.size(), lambda_modifier, &w) != HEVCDL_OK) { fprintf(stderr, "Error: %s\n", w); return 2; }
+  }
   // Devices.  --Device d (default 0): one device.  --Devices 0-7 | 0,2,5 | --NumDevices N: the frames of the job in contiguous blocks, one block, one host thread and
   // one context per entry (the app loop of TAppEncTop.cpp:568-691 once per block; -fs / -f of TAppEncCfg.cpp:786,788 are what a block is); an entry may repeat a
   // device (two contexts share it: the contexts then never wait on each other, HEVCDL_EXEC_NO_UNIT_HANDOVER).
@@ -502,6 +556,13 @@ int main(int argc, char **argv)
       if (st == HEVCDL_OK && device_report && (st = hevcdl_enable_picture_report(shards[i].ctx, 1, hash_sei)) != HEVCDL_OK) { hevcdl_destroy(shards[i].ctx); shards[i].ctx = nullptr; }
       // a file that is not in the codec's format: the upload buffer of source-format frames and the window crops of a padded picture
       if (st == HEVCDL_OK && use_fmt && (st = hevcdl_set_source_format(shards[i].ctx, &fmt)) != HEVCDL_OK) { hevcdl_destroy(shards[i].ctx); shards[i].ctx = nullptr; }
+      // a QP per picture: the modifier once, the first batch's slice of the list in front of the reservation so that the sorted sets are part of it (every batch sets its own below)
+      if (st == HEVCDL_OK && lambda_modifier != 1.0 && (st = hevcdl_set_lambda_modifier(shards[i].ctx, lambda_modifier)) != HEVCDL_OK) { fprintf(stderr, "Error: %s\n", hevcdl_last_error(shards[i].ctx)); return 2; }
+      if (st == HEVCDL_OK && frame_qp_keys) {
+        const long lo = shards[i].f_lo, cnt = std::min<long>(batch, shards[i].f_hi - lo);
+        if ((st = hevcdl_set_frame_qps(shards[i].ctx, seq_qps.data() + lo, (int)cnt)) != HEVCDL_OK) { fprintf(stderr, "Error: %s\n", hevcdl_last_error(shards[i].ctx)); return 2; }
+        if ((st = hevcdl_reserve_workspace(shards[i].ctx)) != HEVCDL_OK) { hevcdl_destroy(shards[i].ctx); shards[i].ctx = nullptr; }
+      }
       if (st == HEVCDL_ERR_OOM && ws_oom) {
         // the workspace is sized by the device's CUs, not by the batch: a smaller batch does not shrink it.  What does: the independent launch form (a block per wave of
         // the context's own frames instead of every CU's workgroup), then the eight-wave build
@@ -533,6 +594,7 @@ int main(int argc, char **argv)
     printf("%43s  4:%c:%c\n%43s  4:2:0\n\n", "Input ChromaFormatIDC = ", in_cf == 400 ? '0' : (in_cf == 444 ? '4' : '2'), in_cf == 400 ? '0' : (in_cf == 420 ? '0' : (in_cf == 422 ? '2' : '4')), "Output (internal) ChromaFormatIDC = ");
     printf("File layout: colour space %s, window left %d right %d top %d bottom %d, every %ld. source frame\n", colour_space ? "YCbCrtoYCrCb" : "UNCHANGED", win_l, win_r, win_t, win_b, ts_ratio);
   }
+  if (qpif_present) printf("%s\n", qp_line);
   printf("HEVC-DL MI355X path: %dx%d  QP %d  frames %ld (skip %ld)  batch %d  labels: %s\n", width, height, qp, n_frames, frame_skip, batch,
          label_dir.empty() ? (cnn_input == "luma" ? "on-device CNN (luma input)" : "on-device CNN (BT.601 RGB input)") : ("files under " + label_dir).c_str());
   if (multi) {
@@ -621,6 +683,7 @@ int main(int argc, char **argv)
       std::vector<hevcdl_dbk_choice> choices(count);          // what every picture's slice header says about its deblocking filter (the cfg's values, or the metric's)
       { const hevcdl_status cst = hevcdl_get_dbk_choice(S.ctx, first, count, choices.data()); if (cst != HEVCDL_OK) { fprintf(stderr, "Error: %s (status %d)\n", hevcdl_last_error(S.ctx), (int)cst); S.rc = 3; return 1; } }
       std::vector<int32_t> pic_qps((size_t)count, qp);      // DeltaQpRD: the QP every picture of the chunk was coded with -- its slice_qp_delta and its log line
+      if (frame_qp_keys) for (int i = 0; i < count; i++) pic_qps[(size_t)i] = seq_qps[(size_t)(cc.f0 + first + i)];      // a QP per picture: the rule's
       if (delta_qp_rd) {
         std::vector<hevcdl_qp_rd_row> qrows((size_t)count);
         const hevcdl_status qst = hevcdl_get_qp_rd(S.ctx, first, count, qrows.data(), pic_qps.data());
@@ -753,6 +816,10 @@ int main(int argc, char **argv)
       const auto t0 = now();
       S.t_read += secs(tr0, t0);
       cc.f0 = f0; cc.yuv = yuv_mem.data(); cc.et = 0.0; cc.t0 = t0; cc.nb = nb;
+      if (frame_qp_keys) { // this batch's slice of the sequence's QPs
+        const hevcdl_status qst = hevcdl_set_frame_qps(S.ctx, seq_qps.data() + f0, nb);
+        if (qst != HEVCDL_OK) { fprintf(stderr, "Error: %s (status %d)\n", hevcdl_last_error(S.ctx), (int)qst); S.rc = 3; break; }
+      }
       const double host_before = S.t_host + S.t_write;
       const hevcdl_status est = device_entropy ? hevcdl_encode_pictures_stream(S.ctx, yuv_mem.data(), nb, lab, deblock ? 1 : 0, sao ? 1 : 0, want_pictures ? 1 : 0, want_records ? 1 : 0, chunk, &Tramp::stream, &on_chunk)
                                                : hevcdl_encode_pictures_chunked(S.ctx, yuv_mem.data(), nb, lab, deblock ? 1 : 0, sao ? 1 : 0, chunk, &Tramp::call, &on_chunk);

@@ -253,6 +253,26 @@ struct hevcdl_qp_rd_keep_params {
   int chunk_iters;                                               // chunk16 / 1024
   int n_frames;
 };
+// A QP per picture (frame_permute_kernel.hip): picture perm[i] of every source range becomes picture i of its destination (gather), or picture i becomes picture perm[i]
+// (scatter: the inverse).  A range is `bytes` bytes a picture, picture after picture, in source and destination alike.
+struct hevcdl_frame_permute_range {
+  const unsigned char *src; unsigned char *dst;
+  unsigned long long bytes;                  // of one picture
+  // set by the launcher: the width of the range's accesses -- 16 when bytes, src and dst are all multiples of 16 (dwordx4, the chunked path), else the largest of 8, 4, 1
+  // that divides all three (the 40 bytes of statistics a picture: plain narrower loads and stores by workgroup (0, picture)) -- and its units of that width a picture
+  int unit_bytes, pad;
+  unsigned long long units;
+};
+struct hevcdl_frame_permute_params {
+  struct hevcdl_frame_permute_range r[4];
+  const int *perm;                           // [n_frames] in HBM, a permutation of 0 .. n_frames - 1
+  int n_ranges, n_frames, scatter;
+  // set by the launcher: a workgroup copies chunk_iters rounds of 1024 16-byte units (256 lanes x 4 in flight) of ONE range; the chunks of range k are
+  // [chunk_first[k], chunk_first[k + 1]) of the grid's x (a narrow range has none)
+  int chunk_iters;
+  unsigned int chunk_first[5];
+  int narrow_iters;                          // units of the longest narrow range a lane visits at the most: ceil(units / 256)
+};
 struct hevcdl_entropy_pack_params {
   const unsigned char *src; unsigned char *dst;
   const uint32_t *unit_off, *unit_cap, *sizes;
@@ -346,6 +366,7 @@ void hevcdl_launch_entropy(const struct hevcdl_entropy_params *p, void *stream, 
 void hevcdl_launch_entropy_pack(const struct hevcdl_entropy_pack_params *p, void *stream);
 void hevcdl_launch_qp_rd_sum(const struct hevcdl_qp_rd_sum_params *p, void *stream);          // qp_rd_kernel.hip; fills ctu_iters
 void hevcdl_launch_qp_rd_keep(const struct hevcdl_qp_rd_keep_params *p, void *stream);        // fills chunk16 / chunk_iters
+void hevcdl_launch_frame_permute(const struct hevcdl_frame_permute_params *p, void *stream);  // frame_permute_kernel.hip; fills the fields marked so
 size_t hevcdl_cnn_smem_bytes(void);
 size_t hevcdl_fc_smem_bytes(void);
 size_t hevcdl_rd_smem_bytes(void);

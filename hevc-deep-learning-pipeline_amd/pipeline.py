@@ -43,7 +43,7 @@ def read_frames(path, width, height, first, count, bit_depth=8, frame_samples=No
 
 def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None, recon_path=None, frame_skip=0, batch=256, tiles=(1, 1),
                     lf_across_tiles=True, bit_depth=8, level_idc=186, frame_rate=30.0, hash_sei=False, labels_fn=None, device=None, log=print, tools=0x7f, wavefront=False, device_entropy=False, device_report=False, source_format=None,
-                    deblocking_metric=0, lf_offset_in_pps=True, slices=None, lf_across_slices=True, segments=None, delta_qp_rd=0):
+                    deblocking_metric=0, lf_offset_in_pps=True, slices=None, lf_across_slices=True, segments=None, delta_qp_rd=0, frame_qps=None, lambda_modifier=1.0):
     """Encode frames [frame_skip, frame_skip + n_frames) of a planar YUV file.  Works stand-alone and under torch.distributed
     (initialised by the caller): rank r takes a contiguous share of the frames.  Returns, on rank 0, the summary (metrics.Summary)
     and the list of per-picture rows [poc, bits, sseY, sseU, sseV]; other ranks return (None, None).
@@ -68,7 +68,15 @@ def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None
     segments = (SliceSegmentMode, SliceSegmentArgument): dependent slice segments -- mode 1 makes every SliceSegmentArgument / width-in-CTUs rows of a wavefront picture a NAL
     unit of its own, mode 3 every SliceSegmentArgument tiles.  Nothing but the stream changes (hevcdl.h, hevcdl_config.slice_segment_mode).
     delta_qp_rd = N (the cfg key DeltaQpRD): every picture is decided at 2N+1 QPs round `qp` and coded with the cheapest (hevcdl.h, hevcdl_config.delta_qp_rd).  Pictures are
-    independent, so it shards like everything else; the rows then carry a sixth column, the QP the picture was coded with, and the log lines print it."""
+    independent, so it shards like everything else; the rows then carry a sixth column, the QP the picture was coded with, and the log lines print it.
+    frame_qps: the QP of every picture of the sequence ([n_frames], POC order; hevcdl_amd.frame_qp_offsets / frame_qp_list make it from the cfg keys dQPFile, QPIncrementFrame
+    and IntraQPOffset) -- every batch sets its slice (Encoder.set_frame_qps), pictures of one QP are decided in one launch; lambda_modifier: LambdaModifierI, else
+    LambdaModifier0.  Rows and log lines carry the QP as with delta_qp_rd, which excludes both (hevcdl.h, "A QP per picture")."""
+    if frame_qps is not None:
+        frame_qps = [int(q) for q in frame_qps]
+        if len(frame_qps) != n_frames:
+            raise ValueError("frame_qps holds %d QPs for %d pictures" % (len(frame_qps), n_frames))
+    own_qp = bool(delta_qp_rd) or frame_qps is not None      # the rows carry the QP every picture was coded with
     if deblocking_metric not in (0, 1, 2):
         raise ValueError("DeblockingFilterMetric %r is not a value of the key (0, 1 or 2)" % (deblocking_metric,))
     if deblocking_metric and lf_offset_in_pps:
@@ -85,12 +93,14 @@ def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None
                          "chain and cannot be dealt to ranks; run it on one rank" % world)
     mine = sharding.shard_frames(n_frames, world, rank)
     per_rank = sharding.max_shard(n_frames, world)
-    rows = np.full((per_rank + 1, 6 if delta_qp_rd else 5), -1, np.int64)
+    rows = np.full((per_rank + 1, 6 if own_qp else 5), -1, np.int64)
     part_bits = (bitstream_path + ".part%d" % rank) if bitstream_path else None
     part_rec = (recon_path + ".part%d" % rank) if recon_path else None
     fb, fr = open(part_bits, "wb") if part_bits else None, open(part_rec, "wb") if part_rec else None
     if len(mine):
         enc = Encoder(width, height, qp, max_frames=min(batch, len(mine)), device=device, tiles=tiles, bit_depth=bit_depth, lf_across_tiles=lf_across_tiles, tools=tools, wavefront=wavefront, slices=slices, lf_across_slices=lf_across_slices, segments=segments, delta_qp_rd=delta_qp_rd, **dbk)      # tools: HEVCDL_TOOL_*; wavefront: WaveFrontSynchro mask (the cfg's tool switches)
+        if lambda_modifier != 1.0:
+            enc.set_lambda_modifier(lambda_modifier)
         sf = source_format
         sw, sh = (sf.source_width, sf.source_height) if sf is not None else (width, height)
         conf_win = (width - sw, height - sh)
@@ -116,6 +126,8 @@ def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None
             yuv = read_frames(input_path, sw, sh, frame_skip + b0, nb, sf.input_bit_depth if sf is not None else bit_depth, sf.source_samples if sf is not None else None)
             t0 = time.time()
             labels = labels_fn(b0, nb) if labels_fn else None
+            if frame_qps is not None:
+                enc.set_frame_qps(frame_qps[b0:b0 + nb])
             if stream_only:
                 recs = final = sao = None
                 enc.encode_pictures_stream(yuv, labels, want_pictures=False, want_records=False)
@@ -125,7 +137,7 @@ def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None
             slice_data, slice_sizes = enc.get_slice_data(0, nb) if device_entropy else (None, None)
             reports = enc.get_picture_report(0, nb) if device_report else None
             choices = enc.get_dbk_choice(0, nb)      # what every picture's slice header says about its deblocking filter
-            pic_qp = [int(v) for v in enc.get_qp_rd(0, nb)[1]] if delta_qp_rd else [qp] * nb      # the QP every picture was coded with: its slice_qp_delta
+            pic_qp = [int(v) for v in enc.get_qp_rd(0, nb)[1]] if delta_qp_rd else [int(v) for v in enc.get_frame_qps(0, nb)]      # the QP every picture was coded with: its slice_qp_delta
             def one_picture(i):          # host work of a picture (arithmetic coder, hash, SSE): independent -> thread pool (ctypes drops the GIL)
                 if device_entropy:
                     pcfg = scfg
@@ -148,7 +160,7 @@ def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None
                 poc = b0 + i
                 if fb:
                     fb.write(au + sei)
-                rows[poc - mine.start] = [poc, len(au) * 8] + sse + ([pic_qp[i]] if delta_qp_rd else [])
+                rows[poc - mine.start] = [poc, len(au) * 8] + sse + ([pic_qp[i]] if own_qp else [])
             if fr:
                 (final if sf is None else store_output_host(sf, width, height, bit_depth, final)).tofile(fr)
             log("rank %d: pictures %d..%d encoded (%.2f s per picture)" % (rank, b0, b0 + nb - 1, et))
@@ -179,14 +191,14 @@ def encode_sequence(input_path, width, height, qp, n_frames, bitstream_path=None
     for row in allrows:
         poc, bits, sy, su, sv = (int(v) for v in row[:5])
         p = summ.add(bits, (sy, su, sv))
-        log(metrics.frame_line(poc, int(row[5]) if delta_qp_rd else qp, bits, p))
+        log(metrics.frame_line(poc, int(row[5]) if own_qp else qp, bits, p))
     log("\n\nSUMMARY --------------------------------------------------------")
     log(summ.text())
     return summ, allrows
 
 
 def encode_sequence_tile_sharded(input_path, width, height, qp, n_frames, tiles, bitstream_path=None, recon_path=None, frame_skip=0, batch=None, lf_across_tiles=True,
-                                 bit_depth=8, level_idc=186, frame_rate=30.0, hash_sei=False, device=None, log=print, tools=0x7f, slices=None, segments=None, delta_qp_rd=0):
+                                 bit_depth=8, level_idc=186, frame_rate=30.0, hash_sei=False, device=None, log=print, tools=0x7f, slices=None, segments=None, delta_qp_rd=0, frame_qps=None, lambda_modifier=1.0):
     """The within-picture partition: every rank decides its share of the TILES of every picture of a batch
     (`hevcdl_compress_tiles_dev`), one all-to-all moves the tile payloads to the picture's owner (`sharding.exchange_tiles_to_owners`:
     picture i of the batch -> rank i mod world), the owner runs the in-loop filters on the assembled picture and writes its access unit.
@@ -198,6 +210,8 @@ def encode_sequence_tile_sharded(input_path, width, height, qp, n_frames, tiles,
         raise ValueError("the tile-sharded path does not code slice segments (SliceSegmentMode %d): use encode_sequence" % int(segments[0]))
     if delta_qp_rd:      # a picture's QP is picked from the sums of ALL its tiles, which no rank has
         raise ValueError("the tile-sharded path does not search the slice QP (DeltaQpRD %d): use encode_sequence" % int(delta_qp_rd))
+    if frame_qps is not None or lambda_modifier != 1.0:      # hevcdl_compress_tiles_dev refuses it: every rank would have to group the same pictures
+        raise ValueError("the tile-sharded path does not code a QP per picture (frame_qps, lambda_modifier): use encode_sequence")
     import torch
     import torch.distributed as dist
     from . import REC_DTYPE, SAO_DTYPE

@@ -746,6 +746,48 @@ hevcdl_status hevcdl_sao_frames_qp_dev(hevcdl_ctx *ctx, const void *d_org, const
 hevcdl_status hevcdl_get_qp_rd_info(hevcdl_ctx *ctx, size_t *trial_bytes, uint64_t *kernel_launches, double *kernel_ms_opt);
 hevcdl_status hevcdl_qp_rd_step(int device, int ctus_per_frame, size_t frame_bytes, int n_frames, int idx, double frame_lambda, const hevcdl_ctu_record *trial_records,
                                 const void *trial_recon, const hevcdl_frame_stats *trial_stats, hevcdl_qp_rd_row *rows, void *records, void *recon, void *stats, size_t guard_bytes);
+/* ---- A QP per picture (cfg keys dQPFile, QPIncrementFrame, IntraQPOffset, LambdaModifierI / LambdaModifier0; csrc/frame_qp.h) -------------------------
+ * hevcdl_set_frame_qps: picture i of every following decision, in-loop filter or picture-pipeline call of the context is coded at qp[i], for i < n; pictures past n take the
+ * context's QP (the list is copied).  qp == NULL or n == 0 returns to the context's one QP exactly.  A value outside 0 .. 51 is HEVCDL_ERR_INVALID_ARG and leaves the list
+ * as it was.  The front ends compute the list from the keys with the rule of csrc/frame_qp.h (TEncCfg::getQPForPicture, TEncTop.cpp:1396-1451) and set the slice of every
+ * batch; a sweep sets e.g. 22 27 32 37 on four copies of a picture.
+ * hevcdl_set_lambda_modifier: the factor the lambda of every picture is multiplied by before anything is derived from it (LambdaModifierI, else LambdaModifier0:
+ * TEncSlice.cpp:512-520).  1.0 (the default) changes no bit.
+ * The decisions of a call then run as ONE decision launch per run of equal QP, each with the lambda family of its QP (hevcdl_frame_qp_families) and with the launch plan
+ * of a plain call of that many frames.  Where every QP is one contiguous run of the list (32 32 30 30) nothing is copied: the launches take offsets into the caller's
+ * buffers.  Otherwise (32 30 32) hevcdl_frame_permute_kernel gathers source pictures and labels into a set sorted by QP, the launches write into a second sorted set, and
+ * the kernel scatters records, reconstruction and statistics back in picture order, all on the caller's stream.  Both sets (originals, labels, records, reconstruction
+ * and statistics of max_frames pictures) are allocated, all or nothing, by the first call that needs them or by hevcdl_reserve_workspace while a list is set; a refusal is
+ * HEVCDL_ERR_OOM.  Deblocking, the SAO decision, the device entropy coder and its host fallback run with every picture's own QP and lambdas; the host writer takes the
+ * picture's QP in hevcdl_stream_config.qp of the call that writes its access unit (slice_qp_delta = qp - 26; no parameter set depends on it).
+ * Tiles, WaveFrontSynchro, slices and slice segments are allowed (a picture's slices share its QP).  Refused, with a sentence in hevcdl_last_error: a list or a modifier
+ * other than 1.0 on a context with delta_qp_rd or deblocking_metric (HEVCDL_ERR_UNSUPPORTED, by the setters); hevcdl_begin_frames and hevcdl_compress_tiles_dev while either is set.
+ * hevcdl_get_frame_qps: the QPs of pictures [first, first + count) of the LAST decision call (every picture's, also without a list). */
+hevcdl_status hevcdl_set_frame_qps(hevcdl_ctx *ctx, const int *qp, int n);
+hevcdl_status hevcdl_set_lambda_modifier(hevcdl_ctx *ctx, double lambda_modifier);
+hevcdl_status hevcdl_get_frame_qps(hevcdl_ctx *ctx, int first, int count, int32_t *qp);
+/* Host only (no GPU needed): what the two setters would answer on a context of cfg -- HEVCDL_OK, or the status with *why the sentence (a string constant). */
+hevcdl_status hevcdl_frame_qp_check(const hevcdl_config *cfg, const int *qp, int n, double lambda_modifier, const char **why);
+/* Host only: the rule.  hevcdl_frame_qp_list: out[poc] = Clip3(-6 (bit_depth - 8), 51, base_qp + dqp[poc] + intra_qp_offset) for poc < n (dqp NULL: zeros); a result
+ * below 0 is HEVCDL_ERR_INVALID_ARG (10 bits: this path has no negative QP).  hevcdl_frame_qp_offsets: dqp[0 .. n) of a sequence -- zeros, ones from the switching POC of
+ * QPIncrementFrame on (qpif < 0: absent; frame_skip, temporal_subsample_ratio as the cfg's), then the integers of the file dqp_file (NULL or "": none), which overwrite;
+ * *file_values (may be NULL): how many the file set.  A file that cannot be opened or holds anything but integers of -64 .. 64 is HEVCDL_ERR_INVALID_ARG.
+ * hevcdl_frame_qp_families: the decision constants of a picture coded at qp with the modifier.  hevcdl_frame_qp_grouping: perm[n] (sorted place -> picture, stable),
+ * run_qp / run_first / run_count (room for 52 each) and *contiguous (1: every QP is one contiguous run of the list as given, nothing would be copied); returns the number
+ * of runs, -1 for a QP outside 0 .. 51. */
+hevcdl_status hevcdl_frame_qp_list(int base_qp, const int *dqp, int n, int intra_qp_offset, int bit_depth, int *out);
+hevcdl_status hevcdl_frame_qp_offsets(int n, int qpif, int frame_skip, int temporal_subsample_ratio, const char *dqp_file, int *dqp, int *file_values);
+hevcdl_status hevcdl_frame_qp_families(int qp, int bit_depth, double lambda_modifier, hevcdl_qp_rd_candidate *out);
+int hevcdl_frame_qp_grouping(const int *qp, int n, int *perm, int *run_qp, int *run_first, int *run_count, int *contiguous);
+/* TEST AND DIAGNOSTIC entry points.
+ * hevcdl_get_frame_qp_info: bytes of the two sorted sets the context holds (0: none allocated), decision launches and permute-kernel launches of the LAST decision call;
+ * kernel_ms_opt[2] (may be NULL): HIP-event times of its gather and scatter launches -- measured only with hevcdl_profile_enable(ctx, 1), zeros otherwise.
+ * hevcdl_frame_permute_step: the kernel alone, without a context, on host buffers: n_ranges (1 .. 4) ranges of bytes[k] bytes a picture, n_frames pictures, picture
+ * perm[i] of src[k] to picture i of dst[k] (scatter 0) or picture i to picture perm[i] (scatter 1).  Every destination is passed WITH a margin of guard_bytes in front of and
+ * behind the payload, uploaded and downloaded whole: what the kernel leaves untouched comes back as it went.  perm must be a permutation of 0 .. n_frames - 1
+ * (HEVCDL_ERR_INVALID_ARG otherwise). */
+hevcdl_status hevcdl_get_frame_qp_info(hevcdl_ctx *ctx, size_t *set_bytes, int *rd_launches, int *permute_launches, double *kernel_ms_opt);
+hevcdl_status hevcdl_frame_permute_step(int device, int n_ranges, const size_t *bytes, int n_frames, const int *perm, int scatter, const void *const *src, void *const *dst, size_t guard_bytes);
 /* kernel timing with HIP events recorded on the launch stream */
 hevcdl_status hevcdl_profile_enable(hevcdl_ctx *ctx, int enable);
 hevcdl_status hevcdl_profile_get(hevcdl_ctx *ctx, hevcdl_profile *out);   /* synchronises, returns and resets */
