@@ -23,7 +23,7 @@ LEAF_LIB_PATH = os.path.join(PKG_DIR, "lib", "libhevcdl_hip_leaf.so")        # -
 WEIGHTS_PATH = os.path.join(PKG_DIR, "weights", "hevc_encoder_model.f32")
 WEIGHT_FLOATS = 637712
 LEAF_SOURCES = ["rd_leaf.hip", "rd_leaf_bd10.hip", "rd_leaf_wide.hip", "rd_leaf_tools.hip"]      # the decision kernel's four builds, each with csrc/rd_leaf_harness.h behind it
-SOURCES = ["cnn_kernel.hip", "fc_kernel.hip", "rd_kernel.hip", "rd_kernel_bd10.hip", "rd_kernel_wide.hip", "rd_kernel_tools.hip", "deblock_kernel.hip", "dbk_select_kernel.hip", "sao_kernel.hip", "quality_kernel.hip", "report_kernel.hip", "entropy_kernel.hip", "source_kernel.hip", "qp_rd_kernel.hip", "frame_permute_kernel.hip", "hevcdl_api.hip", "hevcdl_bitstream.cpp"]
+SOURCES = ["cnn_kernel.hip", "fc_kernel.hip", "rd_kernel.hip", "rd_kernel_bd10.hip", "rd_kernel_wide.hip", "rd_kernel_tools.hip", "deblock_kernel.hip", "dbk_select_kernel.hip", "sao_kernel.hip", "quality_kernel.hip", "report_kernel.hip", "entropy_kernel.hip", "source_kernel.hip", "qp_rd_kernel.hip", "frame_permute_kernel.hip", "hevcdl_api.hip", "hevcdl_bitstream.cpp", "hevcdl_parse.cpp", "recon_kernel.hip"]
 
 STATUS = {0: "OK", 1: "INVALID_ARG", 2: "UNSUPPORTED", 3: "NO_DEVICE", 4: "HIP", 5: "OOM"}
 
@@ -177,6 +177,12 @@ class SourceFormat(ctypes.Structure):
         return w * h * 3 // 2
 
 
+class ParsedPicture(ctypes.Structure):
+    """hevcdl_parsed_picture of include/hevcdl.h: what the headers of one picture of a parsed stream say."""
+    _fields_ = [("poc", ctypes.c_int32), ("nal_type", ctypes.c_int32), ("qp", ctypes.c_int32), ("sao", ctypes.c_int32), ("dbk", DbkChoice), ("lf_across_slices", ctypes.c_int32),
+                ("n_segments", ctypes.c_int32), ("hash_method", ctypes.c_int32), ("hash_plane_bytes", ctypes.c_int32), ("digest", ctypes.c_uint8 * 48)]
+
+
 class Profile(ctypes.Structure):
     _fields_ = [("cnn_ms", ctypes.c_double), ("rd_ms", ctypes.c_double), ("cnn_launches", ctypes.c_uint32), ("rd_launches", ctypes.c_uint32), ("cnn_conv_ms", ctypes.c_double)]
 
@@ -268,6 +274,22 @@ def build_app(force=False):
     subprocess.run([hipcc, "-O2", "-std=c++17", "-x", "c++", src, "-x", "none", "-I" + os.path.join(ROOT, "include"), "-L" + os.path.dirname(lib), "-lhevcdl_hip",
                     "-Wl,-rpath,$ORIGIN/../lib", "-pthread", "-ldl", "-o", APP_PATH], check=True)
     return APP_PATH
+
+
+DECODER_APP_PATH = os.path.join(PKG_DIR, "bin", "TAppDecoderHevcdl")
+
+
+def build_decoder_app(force=False):
+    """Compile the command-line decoder (csrc/hevcdl_decoder_app.cpp, host C++ over the C ABI) into bin/TAppDecoderHevcdl."""
+    src = os.path.join(PKG_DIR, "csrc", "hevcdl_decoder_app.cpp")
+    lib = build_ext()
+    if not force and os.path.exists(DECODER_APP_PATH) and os.path.getmtime(DECODER_APP_PATH) >= max(os.path.getmtime(src), os.path.getmtime(lib)):
+        return DECODER_APP_PATH
+    os.makedirs(os.path.dirname(DECODER_APP_PATH), exist_ok=True)
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    subprocess.run([hipcc, "-O2", "-std=c++17", "-x", "c++", src, "-x", "none", "-I" + os.path.join(ROOT, "include"), "-L" + os.path.dirname(lib), "-lhevcdl_hip",
+                    "-Wl,-rpath,$ORIGIN/../lib", "-pthread", "-ldl", "-o", DECODER_APP_PATH], check=True)
+    return DECODER_APP_PATH
 
 
 _lib = None
@@ -414,6 +436,19 @@ def load_library():
     lib.hevcdl_frame_qp_grouping.argtypes = [vp, ci, vp, vp, vp, vp, ctypes.POINTER(ci)]
     lib.hevcdl_get_frame_qp_info.argtypes = [vp, szp, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double)]
     lib.hevcdl_frame_permute_step.argtypes = [ci, ci, szp, ci, vp, ci, vp, vp, ctypes.c_size_t]
+    lib.hevcdl_parse_stream.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(StreamConfig), slp, sgp, ctypes.POINTER(ParsedPicture), ci, ctypes.POINTER(ci), vp, vp, ctypes.c_size_t]
+    lib.hevcdl_parse_error.argtypes = []
+    lib.hevcdl_parse_error.restype = ctypes.c_char_p
+    lib.hevcdl_validate_records.argtypes = [ctypes.POINTER(StreamConfig), vp, ci]
+    lib.hevcdl_sao_apply_frames.argtypes = [vp, vp, ci, vp, vp]
+    lib.hevcdl_reconstruct_frames.argtypes = [ci, ctypes.POINTER(StreamConfig), slp, vp, vp, ci, vp]
+    lib.hevcdl_reconstruct_frames_dev.argtypes = [ci, ctypes.POINTER(StreamConfig), slp, vp, vp, ci, vp, vp]
+    lib.hevcdl_reconstruct_frames_host.argtypes = [ctypes.POINTER(StreamConfig), slp, vp, vp, ci, vp]
+    lib.hevcdl_recon_launches.argtypes = []
+    lib.hevcdl_config_from_stream.argtypes = [ctypes.POINTER(StreamConfig), slp, ci, ci, ctypes.POINTER(Config)]
+    lib.hevcdl_decode_stream.argtypes = [vp, vp, ctypes.c_size_t, vp, ci, ctypes.POINTER(ci), ctypes.POINTER(ParsedPicture), vp]
+    lib.hevcdl_recon_launches.restype = ctypes.c_uint64
+    lib.hevcdl_sao_apply_frames_dev.argtypes = [vp, vp, ci, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -439,7 +474,106 @@ EXPORTS = ["hevcdl_config_default", "hevcdl_create", "hevcdl_destroy", "hevcdl_l
            "hevcdl_qp_rd_candidates", "hevcdl_qp_rd_pick_index", "hevcdl_get_qp_rd", "hevcdl_get_qp_rd_info", "hevcdl_qp_rd_step",
            "hevcdl_deblock_frames_qp", "hevcdl_deblock_frames_qp_dev", "hevcdl_sao_frames_qp", "hevcdl_sao_frames_qp_dev",
            "hevcdl_set_frame_qps", "hevcdl_set_lambda_modifier", "hevcdl_get_frame_qps", "hevcdl_frame_qp_check", "hevcdl_frame_qp_list", "hevcdl_frame_qp_offsets",
-           "hevcdl_frame_qp_families", "hevcdl_frame_qp_grouping", "hevcdl_get_frame_qp_info", "hevcdl_frame_permute_step"]
+           "hevcdl_frame_qp_families", "hevcdl_frame_qp_grouping", "hevcdl_get_frame_qp_info", "hevcdl_frame_permute_step",
+           "hevcdl_parse_stream", "hevcdl_parse_error", "hevcdl_validate_records", "hevcdl_sao_apply_frames", "hevcdl_sao_apply_frames_dev",
+           "hevcdl_reconstruct_frames", "hevcdl_reconstruct_frames_dev", "hevcdl_reconstruct_frames_host", "hevcdl_recon_launches",
+           "hevcdl_config_from_stream", "hevcdl_decode_stream"]
+
+
+class ParsedStream:
+    """What parse_stream gives back: cfg (StreamConfig), slices / segments (SliceLayout / SegmentLayout or None, as write_access_unit_from_slice_data takes them),
+    pictures (a list of ParsedPicture), records [pictures, ctus] (REC_DTYPE) and sao [pictures, ctus, 3] (SAO_DTYPE; zeros for a picture without SAO)."""
+
+    def __init__(self, cfg, slices, segments, pictures, records, sao):
+        self.cfg, self.slices, self.segments, self.pictures, self.records, self.sao = cfg, slices, segments, pictures, records, sao
+
+    @property
+    def qps(self):
+        return [p.qp for p in self.pictures]
+
+    def digest(self, i):
+        """(method, plane digests) of the decoded picture hash SEI behind picture i, or (0, b"")."""
+        p = self.pictures[i]
+        return p.hash_method, bytes(p.digest[:3 * p.hash_plane_bytes])
+
+
+def parse_stream(stream, headers_only=False):
+    """hevcdl_parse_stream (host only, no GPU): an Annex-B stream of this library's writer, or of the reference encoder in the same configuration -> a ParsedStream.
+    HevcdlError carries the status (1: a damaged stream, 2: a feature outside the decoder) and the parser's sentence."""
+    lib = load_library()
+    buf = np.frombuffer(bytes(stream), np.uint8)
+    cfg = StreamConfig()
+    cfg.struct_size = ctypes.sizeof(StreamConfig)
+    sl, sg, n = SliceLayout(), SegmentLayout(), ctypes.c_int(0)
+
+    def check(st):
+        if st != 0:
+            raise HevcdlError(st, "hevcdl_parse_stream: " + lib.hevcdl_parse_error().decode())
+    check(lib.hevcdl_parse_stream(buf.ctypes.data, buf.size, ctypes.byref(cfg), ctypes.byref(sl), ctypes.byref(sg), None, 0, ctypes.byref(n), None, None, 0))
+    ctus = ((cfg.width + 63) // 64) * ((cfg.height + 63) // 64)
+    pics = (ParsedPicture * n.value)()
+    records = None if headers_only else np.zeros((n.value, ctus), REC_DTYPE)
+    sao = None if headers_only else np.zeros((n.value, ctus, 3), SAO_DTYPE)
+    check(lib.hevcdl_parse_stream(buf.ctypes.data, buf.size, ctypes.byref(cfg), ctypes.byref(sl), ctypes.byref(sg), pics, n.value, ctypes.byref(n),
+                                  None if headers_only else records.ctypes.data, None if headers_only else sao.ctypes.data, 0 if headers_only else n.value * ctus))
+    return ParsedStream(cfg, sl if sl.mode else None, sg if sg.mode else None, list(pics), records, sao)
+
+
+def decode_stream(stream, device=0, batch=64):
+    """hevcdl_decode_stream on a context made for the stream (hevcdl_config_from_stream): parsed on the host; reconstruction, deblocking, SAO and the digests on the
+    device, `batch` pictures at a time in HBM.  -> (pictures [n, w * h * 3 / 2] in coded format, uint16 at 10 bits; the stream's StreamConfig, whose conf_win_* say what
+    to show; the pictures' ParsedPicture list; verdicts [n]: True / False where the device's digest was compared with a hash SEI, None where the stream carries none).
+    HevcdlError carries the status and the decoder's sentence."""
+    lib = load_library()
+    head = parse_stream(stream, headers_only=True)
+    n = len(head.pictures)
+    cfg = Config()
+    st = lib.hevcdl_config_from_stream(ctypes.byref(head.cfg), _layout_ptr(head.slices), max(1, min(int(batch), n)), int(device), ctypes.byref(cfg))
+    if st:
+        raise HevcdlError(st, "hevcdl_config_from_stream")
+    w = np.zeros(WEIGHT_FLOATS, np.float32)      # the label CNN does not run in a decoder: a context wants a blob of the right size
+    h = ctypes.c_void_p()
+    st = lib.hevcdl_create(ctypes.byref(cfg), w.ctypes.data, w.size, ctypes.byref(h))
+    if st:
+        raise HevcdlError(st, "hevcdl_create: " + (lib.hevcdl_create_error() or b"").decode())
+    try:
+        buf = np.frombuffer(bytes(stream), np.uint8)
+        pictures = np.zeros((n, head.cfg.width * head.cfg.height * 3 // 2), np.uint8 if head.cfg.bit_depth == 8 else np.dtype("<u2"))
+        info, ok, count = (ParsedPicture * n)(), np.zeros(n, np.int32), ctypes.c_int(0)
+        st = lib.hevcdl_decode_stream(h, buf.ctypes.data, buf.size, pictures.ctypes.data, n, ctypes.byref(count), info, ok.ctypes.data)
+        if st:
+            raise HevcdlError(st, "hevcdl_decode_stream: " + (lib.hevcdl_last_error(h) or b"").decode())
+    finally:
+        lib.hevcdl_destroy(h)
+    return pictures, head.cfg, list(info), [None if v < 0 else bool(v) for v in ok]
+
+
+def reconstruct_frames(cfg, records, slices=None, qps=None, device=None):
+    """The unfiltered reconstruction of records [pictures, ctus] under cfg (a StreamConfig: size, bit depth, QP, tiles, the strong-intra tool bit) and the slice layout:
+    device None: csrc/recon_core.h on the CPU (hevcdl_reconstruct_frames_host, no GPU needed), otherwise hevcdl_recon_kernel on that device.  qps: a QP per picture.
+    -> [pictures, w * h * 3 / 2] samples (uint8, or uint16 at 10 bits).  HevcdlError carries the status and the sentence."""
+    lib = load_library()
+    r = np.ascontiguousarray(records, REC_DTYPE)
+    r = r.reshape(1, -1) if r.ndim == 1 else r
+    n = r.shape[0]
+    out = np.zeros((n, cfg.width * cfg.height * 3 // 2), np.uint8 if cfg.bit_depth == 8 else np.dtype("<u2"))
+    q = None if qps is None else np.ascontiguousarray(qps, np.int32).reshape(n)
+    qp = None if q is None else q.ctypes.data
+    if device is None:
+        st = lib.hevcdl_reconstruct_frames_host(ctypes.byref(cfg), _layout_ptr(slices), qp, r.ctypes.data, n, out.ctypes.data)
+    else:
+        st = lib.hevcdl_reconstruct_frames(int(device), ctypes.byref(cfg), _layout_ptr(slices), qp, r.ctypes.data, n, out.ctypes.data)
+    if st:
+        raise HevcdlError(st, "hevcdl_reconstruct_frames: " + lib.hevcdl_parse_error().decode())
+    return out
+
+
+def validate_records(cfg, records):
+    """hevcdl_validate_records: records [pictures, ctus] of cfg's size -> None, or the sentence saying what is wrong with them."""
+    lib = load_library()
+    r = np.ascontiguousarray(records)
+    st = lib.hevcdl_validate_records(ctypes.byref(cfg), r.ctypes.data, r.shape[0] if r.ndim > 1 else 1)
+    return None if st == 0 else lib.hevcdl_parse_error().decode()
 
 
 # ---- a QP per picture (include/hevcdl.h "A QP per picture"; csrc/frame_qp.h): the host-only rule, no GPU needed ----
@@ -1261,6 +1395,14 @@ class Encoder:
         out = np.zeros_like(org)
         self._check(self.lib.hevcdl_sao_frames(self._h, org.ctypes.data, dbk.ctypes.data, n, params.ctypes.data, out.ctypes.data))
         return params, out
+
+    def sao_apply_frames(self, deblocked, params):
+        """deblocked frames + given SAO parameters [n, ctus, 3] (a parsed stream's: parse_stream(...).sao) -> the output pictures (hevcdl_sao_apply_frames)."""
+        dbk, n = self._frames(deblocked)
+        params = np.ascontiguousarray(params, SAO_DTYPE).reshape(n, self.ctus, 3)
+        out = np.zeros_like(dbk)
+        self._check(self.lib.hevcdl_sao_apply_frames(self._h, dbk.ctypes.data, n, params.ctypes.data, out.ctypes.data))
+        return out
 
     def sao_frames_dev(self, d_org, d_deblocked, n, d_params, d_out, stream=None):
         self._check(self.lib.hevcdl_sao_frames_dev(self._h, d_org, d_deblocked, n, d_params, d_out, stream))

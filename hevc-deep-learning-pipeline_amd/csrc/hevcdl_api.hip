@@ -7,6 +7,7 @@
 #include <vector>
 #include "hevcdl.h"
 #include "hevcdl_dev.h"
+#include "recon_launch.h"
 #include "dbk_select.h"
 #include "entropy_coder.h"
 #include "picture_hash_core.h"
@@ -89,7 +90,8 @@ struct Staging {      // staging buffers for the host-pointer entry points: the 
   DevBuf<uint8_t> d_picture;            // final pictures of hevcdl_encode_pictures (SAO output)
   HostBuf h_chunk[2]; size_t h_chunk_bytes = 0; Stream copy_stream; Event copy_ev[2];   // hevcdl_encode_pictures_chunked: two page-locked chunk buffers
 };
-struct SaoWorkspace { DevBuf<unsigned char> d_sao_stats, d_sao_recon, d_sao_params, d_sao_cand; };      // SAO workspace: by the first call that needs each
+struct SaoWorkspace { DevBuf<unsigned char> d_sao_stats, d_sao_recon, d_sao_params, d_sao_cand; std::vector<hevcdl_sao_blk> given; };
+struct Decoder { DevBuf<unsigned char> d_work; std::vector<uint32_t> keep; };      // hevcdl_decode_stream: the reconstruction's units, QPs and row counts (cfg.max_frames), by the first call      // SAO workspace: by the first call that needs each
 // picture quality (quality_kernel.hip): the workspace is allocated by hevcdl_enable_quality(ctx, 1), or by the first hevcdl_picture_quality* call of a context
 // with the switch off, and freed by hevcdl_enable_quality(ctx, 0); d_q_out by the switch or by hevcdl_picture_quality (host buffers).  A context that uses neither allocates none of it
 struct Quality {
@@ -180,7 +182,7 @@ struct hevcdl_ctx {
   int col_bd[21] = { 0 }, row_bd[23] = { 0 };    // tile boundaries in CTUs
   DevBuf<float> d_weights, d_a3; size_t a3_ctus = 0;   // d_a3: conv3 outputs of one chunk of CTUs (32 KB per CTU): the hand-over from the conv kernel to the head kernel
   DevBuf<int> d_flag;                  // device-side error flag of the label check
-  Staging stage; SaoWorkspace sao; Quality q; Report rp; Entropy ec; Source src; Session ses; RdWorkspace rd; DbkSelect dbk; QpRd qprd; FrameQp fqp;
+  Staging stage; SaoWorkspace sao; Decoder dec; Quality q; Report rp; Entropy ec; Source src; Session ses; RdWorkspace rd; DbkSelect dbk; QpRd qprd; FrameQp fqp;
   int ec_capacity_per_ctu = 0;         // hevcdl_set_entropy_capacity (tests): 0 = the default; outlives the entropy switch
   bool profile = false;
   std::vector<Event> ev_cnn, ev_rd, ev_conv;       // start/stop pairs (ev_conv: the convolution kernel alone, one pair per chunk of CTUs)
@@ -1242,6 +1244,157 @@ extern "C" hevcdl_status hevcdl_sao_frames_qp(hevcdl_ctx *ctx, const uint8_t *or
   TRY(sync_or_fail(ctx, "sao kernels"));
   HIPCHK(hipMemcpy(params, ctx->sao.d_sao_params, ctx->sao_bytes(n_frames), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(out, ctx->stage.d_records, ctx->frame_bytes * n_frames, hipMemcpyDeviceToHost));
+  return HEVCDL_OK;
+}
+
+// ---- SAO with GIVEN parameters: what a decoder runs behind the deblocking filter (the parameters of a parsed stream, hevcdl_parse_stream) ----
+// params: HOST memory, [n_frames][ctus] as the writer takes them (a merged CTU: mode 2 and the direction in component 0).  They are checked and resolved on the host --
+// a merge takes the resolved parameters of its candidate, which must exist inside the picture and inside the CTU's tile / row slice of the context; modes 0 / 1, types 0 .. 4, band positions 0 .. 31, offsets within +-31 --
+// and staged in the context (one host copy, one device buffer: one such call at a time, like hevcdl_deblock_frames_choice_dev).
+extern "C" hevcdl_status hevcdl_sao_apply_frames_dev(hevcdl_ctx *ctx, const void *d_deblocked, int n_frames, const hevcdl_sao_blk *params, void *d_out, void *stream)
+{
+  FRAMES_OR_RETURN(ctx, n_frames);
+  if (!d_deblocked || !params || !d_out) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null pointer");
+  if (d_deblocked == d_out) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "SAO reads the neighbours of every sample: the output must not be the input");
+  std::vector<hevcdl_sao_blk> &h = ctx->sao.given;
+  h.assign((size_t)n_frames * ctx->ctus, hevcdl_sao_blk{});
+  for (int f = 0; f < n_frames; f++) for (int a = 0; a < ctx->ctus; a++) {
+    const hevcdl_sao_blk &in = params[(size_t)f * ctx->ctus + a];
+    hevcdl_sao_blk &out = h[(size_t)f * ctx->ctus + a];
+    if (in.c[0].mode == 2) {
+      const int dir = in.c[0].type;
+      if (!(dir == 0 ? a % ctx->ctus_x > 0 : (dir == 1 && a >= ctx->ctus_x))) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "an SAO merge without its candidate inside the picture");
+      // ... and inside the CTU's unit of the context's grid (tiles; the rows of SliceMode 1 slices): sao() has no merge flag across such a border
+      bool border = false;
+      if (dir == 0) { for (int t = 1; t < ctx->cfg.tile_columns; t++) border |= ctx->col_bd[t] == a % ctx->ctus_x; }
+      else { for (int t = 1; t < ctx->cfg.tile_rows; t++) border |= ctx->row_bd[t] == a / ctx->ctus_x; }
+      if (border) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "an SAO merge across a tile or slice border of the context");
+      out = h[(size_t)f * ctx->ctus + (dir == 0 ? a - 1 : a - ctx->ctus_x)];
+      continue;
+    }
+    for (int c = 0; c < 3; c++) {
+      const hevcdl_sao_offset &o = in.c[c];
+      if (o.mode == 0) continue;
+      if (o.mode != 1 || o.type < 0 || o.type > 4 || o.aux < 0 || o.aux > 31) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "SAO parameters out of range (mode 0 .. 2, type 0 .. 4, band position 0 .. 31)");
+      out.c[c].mode = 1; out.c[c].type = o.type; out.c[c].aux = o.type == 4 ? o.aux : 0;
+      for (int k = 0; k < 4; k++) {
+        const int i = o.type == 4 ? (o.aux + k) & 31 : (k < 2 ? k : k + 1);
+        if (o.offset[i] < -31 || o.offset[i] > 31) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "an SAO offset outside +-31");
+        out.c[c].offset[i] = o.offset[i];
+      }
+    }
+  }
+  TRY(lazy_alloc(ctx, ctx->sao.d_sao_recon, ctx->sao_bytes((size_t)ctx->cfg.max_frames), "SAO reconstruction parameters (cfg.max_frames)"));
+  HIPCHK(hipMemcpyAsync(ctx->sao.d_sao_recon, h.data(), ctx->sao_bytes((size_t)n_frames), hipMemcpyHostToDevice, (hipStream_t)stream));
+  hevcdl_sao_params p;
+  memset(&p, 0, sizeof p);
+  p.deblocked = (const uint8_t *)d_deblocked; p.out = (uint8_t *)d_out; p.recon_params = ctx->sao.d_sao_recon;
+  p.width = ctx->cfg.width; p.height = ctx->cfg.height; p.ctus_x = ctx->ctus_x; p.ctus_per_frame = ctx->ctus; p.n_frames = n_frames; p.qp = ctx->cfg.qp;
+  p.tile_cols = ctx->cfg.tile_columns; p.tile_rows = ctx->cfg.tile_rows; p.bit_depth = ctx->cfg.bit_depth; p.lf_across_tiles = ctx->cfg.lf_across_tiles != 0;
+  memcpy(p.col_bd, ctx->col_bd, sizeof p.col_bd); memcpy(p.row_bd, ctx->row_bd, sizeof p.row_bd);
+  hevcdl_launch_sao_apply(&p, stream);
+  return launch_status(ctx);
+}
+
+extern "C" hevcdl_status hevcdl_sao_apply_frames(hevcdl_ctx *ctx, const void *deblocked, int n_frames, const hevcdl_sao_blk *params, void *out)
+{
+  FRAMES_OR_RETURN(ctx, n_frames);
+  if (!deblocked || !params || !out) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null pointer");
+  TRY(ensure_staging(ctx));
+  HIPCHK(hipMemcpy(ctx->stage.d_recon, deblocked, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
+  // (the records staging area is free here and large enough for one more picture set, as in hevcdl_sao_frames_qp)
+  TRY(hevcdl_sao_apply_frames_dev(ctx, ctx->stage.d_recon, n_frames, params, ctx->stage.d_records, nullptr));
+  TRY(sync_or_fail(ctx, "sao apply kernels"));
+  HIPCHK(hipMemcpy(out, ctx->stage.d_records, ctx->frame_bytes * n_frames, hipMemcpyDeviceToHost));
+  return HEVCDL_OK;
+}
+
+// ---- the decoder: hevcdl_parse_stream -> hevcdl_recon_kernel -> deblocking -> SAO with the stream's parameters -> digests by the report kernels ----
+extern "C" hevcdl_status hevcdl_config_from_stream(const hevcdl_stream_config *sc, const hevcdl_slice_layout *slices_opt, int max_frames, int device, hevcdl_config *out)
+{
+  if (!sc || sc->struct_size != sizeof *sc || !out || max_frames < 1) return HEVCDL_ERR_INVALID_ARG;
+  TRY(hevcdl_config_default_bd(out, sc->width, sc->height, sc->qp, sc->bit_depth));
+  out->max_frames = max_frames; out->device = device; out->tools = sc->tools;
+  out->tile_columns = sc->tile_columns; out->tile_rows = sc->tile_rows; out->tile_uniform_spacing = sc->tile_uniform_spacing;
+  memcpy(out->tile_column_width, sc->tile_column_width, sizeof out->tile_column_width); memcpy(out->tile_row_height, sc->tile_row_height, sizeof out->tile_row_height);
+  out->lf_across_tiles = sc->lf_across_tiles; out->lf_beta_offset_div2 = sc->lf_beta_offset_div2; out->lf_tc_offset_div2 = sc->lf_tc_offset_div2;
+  if (slices_opt && slices_opt->mode) { out->slice_mode = slices_opt->mode; out->slice_argument = slices_opt->argument; out->lf_across_slices = slices_opt->lf_across_slices; }
+  return HEVCDL_OK;      // (wavefront and the segment keys change the stream alone: a decoding context does not need them)
+}
+
+static hevcdl_status ensure_report_workspace(hevcdl_ctx *ctx);      // (with the report entry points below)
+namespace { struct FrameQpGuard { hevcdl_ctx *c; ~FrameQpGuard() { c->fqp.list.clear(); } }; }
+
+extern "C" hevcdl_status hevcdl_decode_stream(hevcdl_ctx *ctx, const uint8_t *stream, size_t bytes, void *pictures_opt, int picture_capacity, int *n_pictures,
+                                             hevcdl_parsed_picture *info_opt, int32_t *hash_ok_opt)
+{
+  if (!ctx) return HEVCDL_ERR_INVALID_ARG;
+  if (n_pictures) *n_pictures = 0;
+  if (!stream || !n_pictures || picture_capacity < 0) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null stream or picture count");
+  hevcdl_stream_config sc; memset(&sc, 0, sizeof sc); sc.struct_size = sizeof sc;
+  hevcdl_slice_layout sl = { 0, 0, 1 }; hevcdl_segment_layout sg = { 0, 0 };
+  int n = 0;
+  hevcdl_status st = hevcdl_parse_stream(stream, bytes, &sc, &sl, &sg, nullptr, 0, &n, nullptr, nullptr, 0);
+  if (st != HEVCDL_OK) return fail(ctx, st, hevcdl_parse_error());
+  *n_pictures = n;
+  { // the context must describe the stream: size, depth and the grid the in-loop filters stop at (tiles, row slices) with its flag
+    hevcdl_config want, grid; const char *why = "";
+    if (hevcdl_config_from_stream(&sc, &sl, ctx->cfg.max_frames, ctx->cfg.device, &want) != HEVCDL_OK || hevcdl_slice_grid(&want, &grid, &why) != HEVCDL_OK)
+      return fail(ctx, HEVCDL_ERR_UNSUPPORTED, why[0] ? why : "the stream's configuration cannot be run by a context");
+    int cb[21], rb[23];
+    const bool same = grid.width == ctx->cfg.width && grid.height == ctx->cfg.height && grid.bit_depth == ctx->cfg.bit_depth && grid.tile_columns == ctx->cfg.tile_columns &&
+                      grid.tile_rows == ctx->cfg.tile_rows && (grid.lf_across_tiles != 0) == (ctx->cfg.lf_across_tiles != 0) &&
+                      !hevcdl_tile_bounds(ctx->ctus_x, grid.tile_columns, grid.tile_uniform_spacing, grid.tile_column_width, 1, cb) &&
+                      !hevcdl_tile_bounds(ctx->ctus_y, grid.tile_rows, grid.tile_uniform_spacing, grid.tile_row_height, 1, rb) &&
+                      !memcmp(cb, ctx->col_bd, sizeof(int) * (size_t)(grid.tile_columns + 1)) && !memcmp(rb, ctx->row_bd, sizeof(int) * (size_t)(grid.tile_rows + 1));
+    if (!same) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "the context does not describe the stream (size, bit depth, tiles, slices or the loop-filter flags differ): create it from hevcdl_config_from_stream");
+  }
+  if (ctx->cfg.delta_qp_rd || ctx->cfg.deblocking_metric) return fail(ctx, HEVCDL_ERR_UNSUPPORTED, "a context with delta_qp_rd or deblocking_metric does not decode");
+  if (n > picture_capacity) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "the stream holds more pictures than there is room for (*n_pictures says how many)");
+  std::vector<hevcdl_parsed_picture> pics; std::vector<hevcdl_ctu_record> recs; std::vector<hevcdl_sao_blk> sao;
+  try { pics.resize((size_t)n); recs.resize((size_t)n * ctx->ctus); sao.resize((size_t)n * ctx->ctus); } catch (...) { return fail(ctx, HEVCDL_ERR_OOM, "host memory for the stream's records"); }
+  st = hevcdl_parse_stream(stream, bytes, &sc, &sl, &sg, pics.data(), n, &n, recs.data(), sao.data(), recs.size());
+  if (st != HEVCDL_OK) return fail(ctx, st, hevcdl_parse_error());
+  TRY(ensure_staging(ctx));
+  TRY(lazy_alloc(ctx, ctx->stage.d_picture, ctx->frame_bytes * (size_t)ctx->cfg.max_frames, "output pictures (cfg.max_frames)"));
+  TRY(ensure_report_workspace(ctx));
+  const size_t work = hevcdl_recon_work_bytes(ctx->cfg.width, ctx->cfg.height, ctx->cfg.max_frames);
+  TRY(lazy_alloc(ctx, ctx->dec.d_work, work, "reconstruction row counts (cfg.max_frames)"));
+  HIPCHK(hipSetDevice(ctx->cfg.device));
+  FrameQpGuard guard{ ctx };
+  std::vector<int> qps; std::vector<hevcdl_dbk_choice> choices; std::vector<hevcdl_picture_report_t> rep;
+  for (int first = 0; first < n; first += ctx->cfg.max_frames) {
+    const int cnt = std::min(ctx->cfg.max_frames, n - first);
+    qps.resize((size_t)cnt); choices.resize((size_t)cnt); rep.resize((size_t)cnt);
+    bool any_sao = false, own_qp = false;
+    for (int i = 0; i < cnt; i++) { qps[i] = pics[first + i].qp; choices[i] = pics[first + i].dbk; any_sao |= pics[first + i].sao != 0; own_qp |= qps[i] != ctx->cfg.qp; }
+    HIPCHK(hipMemcpyAsync(ctx->stage.d_records, recs.data() + (size_t)first * ctx->ctus, ctx->records_bytes((size_t)cnt), hipMemcpyHostToDevice, nullptr));
+    const uint32_t *d_err = nullptr;
+    st = hevcdl_recon_enqueue(&sc, &sl, qps.data(), ctx->stage.d_records, cnt, ctx->stage.d_recon, ctx->dec.d_work, work, nullptr, ctx->dec.keep, &d_err);
+    if (st != HEVCDL_OK) return fail(ctx, st, hevcdl_parse_error());
+    if (own_qp) TRY(hevcdl_set_frame_qps(ctx, qps.data(), cnt)); else ctx->fqp.list.clear();
+    TRY(hevcdl_deblock_frames_choice_dev(ctx, ctx->stage.d_recon, cnt, ctx->stage.d_records, choices.data(), ctx->stage.d_recon, nullptr));
+    const void *d_final = ctx->stage.d_recon;
+    if (any_sao) { TRY(hevcdl_sao_apply_frames_dev(ctx, ctx->stage.d_recon, cnt, sao.data() + (size_t)first * ctx->ctus, ctx->stage.d_picture, nullptr)); d_final = ctx->stage.d_picture; }
+    for (int i = 0; i < cnt; i++) if (hash_ok_opt) hash_ok_opt[first + i] = -1;
+    for (int method = 1; method <= 3; method++) { // the digests of the pictures still in HBM, by the report kernels, against the stream's SEI
+      bool any = false;
+      for (int i = 0; i < cnt; i++) any |= pics[first + i].hash_method == method;
+      if (!any) continue;
+      TRY(hevcdl_picture_report_dev(ctx, nullptr, d_final, cnt, method, ctx->rp.d_rp_out, nullptr));
+      HIPCHK(hipMemcpy(rep.data(), ctx->rp.d_rp_out, sizeof(hevcdl_picture_report_t) * (size_t)cnt, hipMemcpyDeviceToHost));
+      for (int i = 0; i < cnt; i++) {
+        const hevcdl_parsed_picture &pc = pics[first + i];
+        if (pc.hash_method == method && hash_ok_opt) hash_ok_opt[first + i] = rep[i].plane_bytes == pc.hash_plane_bytes && !memcmp(rep[i].digest, pc.digest, (size_t)(3 * pc.hash_plane_bytes));
+      }
+    }
+    uint32_t err = 0;
+    HIPCHK(hipMemcpy(&err, d_err, 4, hipMemcpyDeviceToHost));
+    if (err) return fail(ctx, HEVCDL_ERR_HIP, "reconstruction: a CTU row waited for the row above longer than the limit");
+    if (pictures_opt) HIPCHK(hipMemcpy((unsigned char *)pictures_opt + (size_t)first * ctx->frame_bytes, d_final, ctx->frame_bytes * (size_t)cnt, hipMemcpyDeviceToHost));
+    TRY(sync_or_fail(ctx, "decoder"));
+  }
+  if (info_opt) memcpy(info_opt, pics.data(), sizeof(hevcdl_parsed_picture) * (size_t)n);
   return HEVCDL_OK;
 }
 

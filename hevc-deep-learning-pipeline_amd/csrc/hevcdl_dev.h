@@ -332,6 +332,7 @@ static inline void hevcdl_clamp_ctu_labels(uint8_t *lab, int x0, int y0, int wid
 extern "C" {
 #endif
 void hevcdl_launch_sao(const struct hevcdl_sao_params *p, void *stream);
+void hevcdl_launch_sao_apply(const struct hevcdl_sao_params *p, void *stream);      // the reconstruction alone, from given resolved parameters
 void hevcdl_launch_deblock(const struct hevcdl_dbk_params *p, void *stream);
 void hevcdl_launch_dbk_metric(const struct hevcdl_dbk_metric_params *p, void *stream);
 void hevcdl_launch_dbk_trial(const struct hevcdl_dbk_trial_params *p, void *stream);

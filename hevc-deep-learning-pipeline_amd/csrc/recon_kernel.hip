@@ -1,0 +1,216 @@
+// recon_kernel.hip -- hevcdl_recon_kernel: the unfiltered reconstruction of intra pictures from CTU records on gfx950, and its host entry points.
+//
+// The arithmetic and the walk over a CTU are csrc/recon_core.h, one source for this kernel and for hevcdl_reconstruct_frames_host (one "lane" on the CPU: what the
+// kernel's index logic is checked with where there is no GPU).  Here: how the rows of a batch are dealt and how a row waits for the one above.
+//   * A workgroup is ONE wave (64 lanes over the samples of a transform block); it rebuilds whole CTU rows.
+//   * Rows are claimed in increasing (picture, row) order from one atomic ticket.  A CTU reads reconstructed samples of its left neighbour (its own wave) and of the three
+//     CTUs above it, so CTU x of a row waits until the row above has finished min(x + 2, width) CTUs: a per-row finished count in HBM, written with a release store behind
+//     the row's samples and read with agent-scope acquire loads, s_sleep between them.  The row waited for has a smaller ticket, so it was claimed by a wave that is
+//     already running (or done): no launch can deadlock, whatever its residency.  The wait is bounded all the same (SPIN_LIMIT): past it the wave sets the error word and
+//     goes on, the host returns HEVCDL_ERR_HIP -- a shared device is never left with a wave that spins for ever.
+//   * 8- and 10-bit samples are the two instantiations of one template.
+// The kernel is launched only on records that passed hevcdl_validate_records (the host-buffer entry points check; the device form takes the caller's word, and
+// recon_core.h clamps and masks every index all the same).
+#include <hip/hip_runtime.h>
+#include <atomic>
+#include <cstring>
+#include <vector>
+#include "hevcdl.h"
+#include "hevcdl_dev.h"
+#include "recon_launch.h"
+#include "hevcdl_parse.h"
+#include "recon_core.h"
+
+using namespace hevcdl_rc;
+
+namespace {
+enum { SPIN_LIMIT = 1 << 22, RC_MAX_GROUPS = 2048 };
+struct RcLaunch {
+  RcPic pic;                     // picture 0: recs, out; the kernel steps both per picture
+  const int32_t *qps;            // [n_frames] in HBM, or null: pic.qp for every picture
+  uint32_t *sync;                // [0] ticket, [1] error word, [2 + picture * ctus_y + row] finished CTUs of the row; zeroed before the launch
+  size_t frame_bytes;
+  int n_frames, ctus;
+};
+
+template <typename PEL>
+__global__ __launch_bounds__(64) void hevcdl_recon_kernel(RcLaunch L)
+{
+  __shared__ RcWork w;
+  __shared__ int ticket;
+  const int lane = (int)threadIdx.x, rows = L.pic.ctus_y, total = L.n_frames * rows;
+  for (int it = 0; it <= total; it++) {
+    if (lane == 0) ticket = (int)atomicAdd(L.sync, 1u);
+    __syncthreads();
+    const int t = ticket;
+    __syncthreads();
+    if (t >= total) return;
+    const int f = t / rows, cy = t - f * rows;
+    RcPic p = L.pic;
+    p.recs = L.pic.recs + (size_t)f * L.ctus; p.out = (unsigned char *)L.pic.out + (size_t)f * L.frame_bytes;
+    if (L.qps) p.qp = L.qps[f];
+    uint32_t *fin = L.sync + 2 + (size_t)f * rows;
+    for (int cx = 0; cx < p.ctus_x; cx++) {
+      if (cy > 0) {
+        const uint32_t need = (uint32_t)(cx + 2 < p.ctus_x ? cx + 2 : p.ctus_x);
+        if (lane == 0) {
+          int spins = 0;
+          if (__hip_atomic_load(L.sync + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) spins = SPIN_LIMIT;      // a wait has run out already: nobody waits again
+          while (__hip_atomic_load(fin + cy - 1, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < need && spins < SPIN_LIMIT) { __builtin_amdgcn_s_sleep(16); spins++; }
+          if (spins >= SPIN_LIMIT) __hip_atomic_store(L.sync + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        __syncthreads();
+      }
+      rc_ctu<PEL>(p, w, lane, 64, cx, cy);
+      __threadfence();
+      __syncthreads();
+      if (lane == 0) __hip_atomic_store(fin + cy, (uint32_t)(cx + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
+std::atomic<unsigned long long> g_launches{0};
+
+#define RC_REFUSE(st, ...) do { hevcdl_parse::set_error(__VA_ARGS__); return st; } while (0)
+
+// cfg and layout -> the picture's geometry and the unit (slice, tile) of every CTU
+hevcdl_status rc_setup(const hevcdl_stream_config *cfg, const hevcdl_slice_layout *sl, RcPic &p, std::vector<uint32_t> &unit)
+{
+  if (!cfg || cfg->struct_size != sizeof *cfg) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "null configuration, or one of another size");
+  if (cfg->width < 8 || cfg->height < 8 || (cfg->width & 7) || (cfg->height & 7) || cfg->width > 16384 || cfg->height > 16384) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "picture size %d x %d", cfg->width, cfg->height);
+  if (cfg->bit_depth != 8 && cfg->bit_depth != 10) RC_REFUSE(HEVCDL_ERR_UNSUPPORTED, "bit depth %d: 8 and 10 are reconstructed", cfg->bit_depth);
+  if (cfg->qp < 0 || cfg->qp > 51) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "QP %d", cfg->qp);
+  p.W = cfg->width; p.H = cfg->height; p.ctus_x = (p.W + 63) >> 6; p.ctus_y = (p.H + 63) >> 6; p.bit_depth = cfg->bit_depth; p.qp = cfg->qp;
+  p.strong = (cfg->tools & HEVCDL_TOOL_STRONG_INTRA) != 0;
+  int col_bd[21], row_bd[23];
+  const int tc = cfg->tile_columns, tr = cfg->tile_rows;
+  if (tc < 1 || tr < 1 || tc > 20 || tr > 22 || hevcdl_tile_bounds(p.ctus_x, tc, cfg->tile_uniform_spacing != 0, cfg->tile_column_width, 1, col_bd) ||
+      hevcdl_tile_bounds(p.ctus_y, tr, cfg->tile_uniform_spacing != 0, cfg->tile_row_height, 1, row_bd)) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "the tile grid does not fit the picture");
+  const int mode = sl ? sl->mode : 0;
+  if (mode != 0 && mode != 1 && mode != 3) RC_REFUSE(HEVCDL_ERR_UNSUPPORTED, "SliceMode %d", mode);
+  if (mode == 1 && (sl->argument < 1 || sl->argument % p.ctus_x != 0 || tc * tr > 1)) RC_REFUSE(HEVCDL_ERR_UNSUPPORTED, "SliceMode 1 needs whole CTU rows and no tiles");
+  if (mode == 3 && sl->argument < 1) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "SliceMode 3 needs at least one tile a slice");
+  unit.assign((size_t)p.ctus_x * p.ctus_y, 0);
+  for (int y = 0; y < p.ctus_y; y++) for (int x = 0; x < p.ctus_x; x++) {
+    int tx = 0, ty = 0;
+    while (tx + 1 < tc && x >= col_bd[tx + 1]) tx++;
+    while (ty + 1 < tr && y >= row_bd[ty + 1]) ty++;
+    const int tile = ty * tc + tx, slice = mode == 1 ? y / (sl->argument / p.ctus_x) : (mode == 3 ? tile / sl->argument : 0);
+    unit[(size_t)y * p.ctus_x + x] = (uint32_t)slice * 1024u + (uint32_t)tile;
+  }
+  return HEVCDL_OK;
+}
+hevcdl_status rc_check_qps(const int32_t *qps, int n)
+{
+  if (qps) for (int i = 0; i < n; i++) if (qps[i] < 0 || qps[i] > 51) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "QP %d of picture %d", qps[i], i);
+  return HEVCDL_OK;
+}
+#define HIPOK(call) do { if ((call) != hipSuccess) { (void)hipGetLastError(); RC_REFUSE(HEVCDL_ERR_HIP, "%s failed", #call); } } while (0)
+} // namespace
+
+extern "C" unsigned long long hevcdl_recon_launches(void) { return g_launches.load(); }
+
+extern "C" hevcdl_status hevcdl_reconstruct_frames_host(const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const int32_t *qps_opt,
+                                                       const hevcdl_ctu_record *records, int n_frames, void *recon)
+{
+  RcPic p; std::vector<uint32_t> unit;
+  hevcdl_status st = rc_setup(cfg, slices_opt, p, unit);
+  if (st != HEVCDL_OK) return st;
+  if (!records || !recon || n_frames < 0) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "null records or pictures");
+  if ((st = rc_check_qps(qps_opt, n_frames)) != HEVCDL_OK) return st;
+  if ((st = hevcdl_validate_records(cfg, records, n_frames)) != HEVCDL_OK) return st;
+  const size_t ctus = unit.size(), fb = hevcdl_frame_bytes_bd(p.W, p.H, p.bit_depth);
+  std::vector<RcWork> w(1);
+  p.unit = unit.data();
+  for (int f = 0; f < n_frames; f++) {
+    p.recs = records + (size_t)f * ctus; p.out = (unsigned char *)recon + (size_t)f * fb; p.qp = qps_opt ? qps_opt[f] : cfg->qp;
+    for (int cy = 0; cy < p.ctus_y; cy++) for (int cx = 0; cx < p.ctus_x; cx++) {
+      if (p.bit_depth == 8) rc_ctu<uint8_t>(p, w[0], 0, 1, cx, cy); else rc_ctu<uint16_t>(p, w[0], 0, 1, cx, cy);
+    }
+  }
+  return HEVCDL_OK;
+}
+
+// The launch alone, on work memory the caller owns (hevcdl_decode_stream: a buffer of the context, sized once by hevcdl_recon_work_bytes): nothing is allocated, freed or
+// waited for.  `keep` receives the host copy of what is uploaded (units, QPs) and must live until the stream has passed the copies; *d_error is the error word in the
+// work memory, to be fetched with the batch's other results: non-zero = a row waited past the limit.  The device is the caller's current one.
+extern "C" size_t hevcdl_recon_work_bytes(int width, int height, int n_frames)
+{
+  const size_t cx = (size_t)((width + 63) >> 6), cy = (size_t)((height + 63) >> 6), n = (size_t)(n_frames > 0 ? n_frames : 0);
+  return cx * cy * 4 + n * 4 + (2 + n * cy) * 4;
+}
+hevcdl_status hevcdl_recon_enqueue(const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const int32_t *qps_opt, const void *d_records, int n_frames,
+                                   void *d_recon, void *d_work, size_t work_bytes, void *stream, std::vector<uint32_t> &keep, const uint32_t **d_error)
+{
+  RcLaunch L;
+  memset(&L, 0, sizeof L);
+  hevcdl_status st = rc_setup(cfg, slices_opt, L.pic, keep);
+  if (st != HEVCDL_OK) return st;
+  if (!d_records || !d_recon || !d_work || !d_error || n_frames < 1 || n_frames > (1 << 16)) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "null device pointer, or a picture count outside 1 .. 65536");
+  if ((st = rc_check_qps(qps_opt, n_frames)) != HEVCDL_OK) return st;
+  if (work_bytes < hevcdl_recon_work_bytes(cfg->width, cfg->height, n_frames)) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "work memory smaller than hevcdl_recon_work_bytes");
+  hipStream_t s = (hipStream_t)stream;
+  const size_t ctus = keep.size(), rows = (size_t)n_frames * L.pic.ctus_y;
+  const size_t b_unit = ctus * 4, b_qp = (size_t)n_frames * 4, b_sync = (2 + rows) * 4;
+  if (qps_opt) keep.insert(keep.end(), (const uint32_t *)qps_opt, (const uint32_t *)qps_opt + n_frames);
+  unsigned char *d = (unsigned char *)d_work;
+  HIPOK(hipMemcpyAsync(d, keep.data(), keep.size() * 4, hipMemcpyHostToDevice, s));
+  HIPOK(hipMemsetAsync(d + b_unit + b_qp, 0, b_sync, s));
+  L.pic.unit = (const uint32_t *)d; L.pic.recs = (const hevcdl_ctu_record *)d_records; L.pic.out = d_recon;
+  L.qps = qps_opt ? (const int32_t *)(d + b_unit) : nullptr; L.sync = (uint32_t *)(d + b_unit + b_qp);
+  L.frame_bytes = hevcdl_frame_bytes_bd(L.pic.W, L.pic.H, L.pic.bit_depth); L.n_frames = n_frames; L.ctus = (int)ctus;
+  const unsigned groups = (unsigned)(rows < RC_MAX_GROUPS ? rows : RC_MAX_GROUPS);
+  g_launches.fetch_add(1);
+  if (L.pic.bit_depth == 8) hipLaunchKernelGGL(hevcdl_recon_kernel<uint8_t>, dim3(groups), dim3(64), 0, s, L);
+  else hipLaunchKernelGGL(hevcdl_recon_kernel<uint16_t>, dim3(groups), dim3(64), 0, s, L);
+  HIPOK(hipGetLastError());
+  *d_error = L.sync + 1;
+  return HEVCDL_OK;
+}
+
+// The stand-alone device form: its own work memory, allocated and freed by the call, which therefore waits for the stream (a pipeline uses the form above).
+extern "C" hevcdl_status hevcdl_reconstruct_frames_dev(int device, const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const int32_t *qps_opt,
+                                                      const void *d_records, int n_frames, void *d_recon, void *stream)
+{
+  if (n_frames == 0 && cfg) { RcPic p; std::vector<uint32_t> u; return rc_setup(cfg, slices_opt, p, u); }
+  if (!cfg || n_frames < 0) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "null configuration or a negative picture count");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { (void)hipGetLastError(); RC_REFUSE(HEVCDL_ERR_NO_DEVICE, "no such device"); }
+  HIPOK(hipSetDevice(device));
+  const size_t total = hevcdl_recon_work_bytes(cfg->width, cfg->height, n_frames);
+  unsigned char *d = nullptr;
+  if (hipMalloc(&d, total) != hipSuccess) { (void)hipGetLastError(); RC_REFUSE(HEVCDL_ERR_OOM, "no device memory for the row counts"); }
+  std::vector<uint32_t> keep; const uint32_t *d_err = nullptr; uint32_t err = 0;
+  hevcdl_status out = hevcdl_recon_enqueue(cfg, slices_opt, qps_opt, d_records, n_frames, d_recon, d, total, stream, keep, &d_err);
+  if (out == HEVCDL_OK && (hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess || hipStreamSynchronize((hipStream_t)stream) != hipSuccess)) {
+    (void)hipGetLastError(); hevcdl_parse::set_error("a HIP call of the reconstruction failed"); out = HEVCDL_ERR_HIP;
+  }
+  if (out == HEVCDL_OK && err) { hevcdl_parse::set_error("a CTU row waited for the row above longer than the limit"); out = HEVCDL_ERR_HIP; }
+  if (out != HEVCDL_OK) (void)hipStreamSynchronize((hipStream_t)stream);      // nothing may still read the work memory when it is freed
+  (void)hipFree(d);
+  return out;
+}
+
+extern "C" hevcdl_status hevcdl_reconstruct_frames(int device, const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const int32_t *qps_opt,
+                                                  const hevcdl_ctu_record *records, int n_frames, void *recon)
+{
+  RcPic p; std::vector<uint32_t> unit;
+  hevcdl_status st = rc_setup(cfg, slices_opt, p, unit);
+  if (st != HEVCDL_OK) return st;
+  if (!records || !recon || n_frames < 0) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "null records or pictures");
+  if ((st = rc_check_qps(qps_opt, n_frames)) != HEVCDL_OK) return st;
+  if ((st = hevcdl_validate_records(cfg, records, n_frames)) != HEVCDL_OK) return st;      // nothing is allocated, copied or launched on QPs or records that are refused
+  if (n_frames == 0) return HEVCDL_OK;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { (void)hipGetLastError(); RC_REFUSE(HEVCDL_ERR_NO_DEVICE, "no such device"); }
+  HIPOK(hipSetDevice(device));
+  const size_t b_rec = sizeof(hevcdl_ctu_record) * unit.size() * (size_t)n_frames, b_pic = hevcdl_frame_bytes_bd(p.W, p.H, p.bit_depth) * (size_t)n_frames;
+  unsigned char *d = nullptr;
+  if (hipMalloc(&d, b_rec + b_pic) != hipSuccess) { (void)hipGetLastError(); RC_REFUSE(HEVCDL_ERR_OOM, "no device memory for %d pictures", n_frames); }
+  st = HEVCDL_OK;
+  if (hipMemcpy(d, records, b_rec, hipMemcpyHostToDevice) != hipSuccess || hipMemset(d + b_rec, 0, b_pic) != hipSuccess) { (void)hipGetLastError(); hevcdl_parse::set_error("upload failed"); st = HEVCDL_ERR_HIP; }
+  if (st == HEVCDL_OK) st = hevcdl_reconstruct_frames_dev(device, cfg, slices_opt, qps_opt, d, n_frames, d + b_rec, nullptr);
+  if (st == HEVCDL_OK && hipMemcpy(recon, d + b_rec, b_pic, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); hevcdl_parse::set_error("download failed"); st = HEVCDL_ERR_HIP; }
+  (void)hipFree(d);
+  return st;
+}

@@ -593,6 +593,17 @@ __global__ __launch_bounds__(256) void hevcdl_sao_apply8_kernel(hevcdl_sao_param
   }
 }
 
+// The offset reconstruction alone, from resolved parameters that are GIVEN (p.recon_params: a merged CTU holds its candidate's parameters): what a decoder runs behind
+// the deblocking filter, and the last step of hevcdl_launch_sao below (the choice between the 8-bit and the 16-bit kernel lives here).  The host checks the parameters before they are uploaded (hevcdl_sao_apply_frames): modes, types and band positions in range.
+extern "C" void hevcdl_launch_sao_apply(const hevcdl_sao_params *pp, void *stream)
+{
+  const hevcdl_sao_params p = *pp;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 per_ctu(p.ctus_per_frame, 3, p.n_frames);
+  if (p.bit_depth == 8) hipLaunchKernelGGL(hevcdl_sao_apply8_kernel, per_ctu, dim3(256), 0, s, p);
+  else hipLaunchKernelGGL(hevcdl_sao_apply_kernel<uint16_t>, per_ctu, dim3(256), 0, s, p);
+}
+
 extern "C" void hevcdl_launch_sao(const hevcdl_sao_params *pp, void *stream)
 {
   const hevcdl_sao_params p = *pp;
@@ -605,6 +616,5 @@ extern "C" void hevcdl_launch_sao(const hevcdl_sao_params *pp, void *stream)
   hipLaunchKernelGGL(hevcdl_sao_decide_kernel, dim3((p.n_frames + 63) / 64), dim3(64), 0, s, p);
   const size_t n_ctu = (size_t)p.n_frames * p.ctus_per_frame;
   hipLaunchKernelGGL(hevcdl_sao_expand_kernel, dim3((unsigned)((n_ctu + 255) / 256)), dim3(256), 0, s, p);
-  if (p.bit_depth == 8) hipLaunchKernelGGL(hevcdl_sao_apply8_kernel, per_ctu, dim3(256), 0, s, p);
-  else hipLaunchKernelGGL(hevcdl_sao_apply_kernel<uint16_t>, per_ctu, dim3(256), 0, s, p);
+  hevcdl_launch_sao_apply(pp, stream);
 }

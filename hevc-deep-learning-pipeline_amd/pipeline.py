@@ -306,3 +306,85 @@ def encode_sequence_tile_sharded(input_path, width, height, qp, n_frames, tiles,
     log("\n\nSUMMARY --------------------------------------------------------")
     log(summ.text())
     return summ, allrows
+
+
+def parse_sequence(bitstream_path, headers_only=False):
+    """A stream file of this pipeline (or of the reference encoder in the same configuration) read back on the host, no GPU: -> a ParsedStream -- the stream's
+    configuration and slice / segment layouts, per picture POC, QP, deblocking choice and the hash SEI's digests, and (unless headers_only) the CTU records and SAO
+    parameters of every picture, as encode_sequence's writers took them.  HevcdlError says what a stream outside the parser's surface, or a damaged one, was refused for."""
+    from . import parse_stream
+    with open(bitstream_path, "rb") as f:
+        return parse_stream(f.read(), headers_only=headers_only)
+
+
+def decode_stream_by_stages(stream, device=0, batch=64):
+    """TEST AND DIAGNOSTIC: decode_stream with the stages called one by one through host buffers and the digests computed on the host.  A stream of this pipeline (or of the reference encoder in the same configuration) decoded on the device, stage by stage: hevcdl_parse_stream on the host ->
+    hevcdl_recon_kernel (the unfiltered reconstruction from the parsed records) -> deblocking with every picture's own QP and slice-header parameters -> SAO with the
+    stream's parameters -> the decoded picture hash of every picture against its SEI.  -> (pictures [n, w * h * 3 / 2] in coded format -- the conformance window is NOT
+    cut --, the ParsedStream, verdicts [n]: True / False where the stream carries a hash, None where it does not).  Pictures go through the device `batch` at a time."""
+    from . import parse_stream, reconstruct_frames, picture_hash, DBK_CHOICE_DTYPE
+    p = parse_stream(stream)
+    cfg, n = p.cfg, len(p.pictures)
+    tiles = (cfg.tile_columns, cfg.tile_rows)
+    if not cfg.tile_uniform_spacing:
+        cx, cy = (cfg.width + 63) // 64, (cfg.height + 63) // 64
+        cw, rh = [cfg.tile_column_width[i] for i in range(cfg.tile_columns - 1)], [cfg.tile_row_height[i] for i in range(cfg.tile_rows - 1)]
+        tiles = (cw + [cx - sum(cw)], rh + [cy - sum(rh)])
+    slices = (p.slices.mode, p.slices.argument) if p.slices else None
+    batch = max(1, min(batch, n))
+    enc = Encoder(cfg.width, cfg.height, p.qps[0], max_frames=batch, device=device, tiles=tiles, bit_depth=cfg.bit_depth, lf_across_tiles=bool(cfg.lf_across_tiles),
+                  lf_offsets=(cfg.lf_beta_offset_div2, cfg.lf_tc_offset_div2), slices=slices, lf_across_slices=bool(p.slices.lf_across_slices) if p.slices else True)
+    out, verdicts = [], []
+    try:
+        for first in range(0, n, batch):
+            pics = p.pictures[first:first + batch]
+            recs, qps = p.records[first:first + len(pics)], p.qps[first:first + len(pics)]
+            cur = reconstruct_frames(cfg, recs, slices=p.slices, qps=qps, device=device)
+            enc.set_frame_qps(qps if any(q != p.qps[0] for q in qps) else None)
+            # a picture whose filter is off (in the PPS or in its slice headers) is copied by the stage: the choice says so
+            choices = np.zeros(len(pics), DBK_CHOICE_DTYPE)
+            for i, pic in enumerate(pics):
+                choices[i] = (pic.dbk.override_enabled, pic.dbk.override_flag, pic.dbk.disabled, pic.dbk.beta_offset_div2, pic.dbk.tc_offset_div2)
+            cur = enc.deblock_frames_choice(cur, recs, choices)
+            if any(pic.sao for pic in pics):
+                cur = enc.sao_apply_frames(cur, p.sao[first:first + len(pics)])      # (a picture without SAO holds mode 0 everywhere: copied)
+            out.append(cur)
+            for i, pic in enumerate(pics):
+                method, digest = p.digest(first + i)
+                verdicts.append(None if not method else bytes(picture_hash(cfg.width, cfg.height, cur[i], cfg.bit_depth, method)) == digest)
+    finally:
+        enc.close()
+    return np.concatenate(out), p, verdicts
+
+
+def decode_stream(stream, device=0, batch=64):
+    """A stream of this pipeline (or of the reference encoder in the same configuration) decoded by hevcdl_decode_stream: parsed on the host; reconstruction from the
+    records, deblocking, SAO with the stream's parameters and the digests of the decoded picture hash on the device, `batch` pictures at a time in HBM.
+    -> (pictures [n, w * h * 3 / 2] in coded format -- the conformance window is NOT cut --, the ParsedStream of the headers, verdicts [n]: True / False where the stream
+    carries a hash, None where it does not)."""
+    from . import decode_stream as decode, parse_stream
+    pictures, _, _, verdicts = decode(stream, device=device, batch=batch)
+    return pictures, parse_stream(stream, headers_only=True), verdicts
+
+
+def decode_sequence(bitstream_path, recon_path=None, device=0, batch=64, log=None):
+    """decode_stream over a stream file; with recon_path the output pictures are written as the reference decoder writes them: the conformance window, at the coded bit
+    depth.  One line per picture (POC, QP, hash verdict) goes to `log` (a callable, e.g. print).  -> (pictures, ParsedStream, verdicts); a hash mismatch raises
+    ValueError behind the file."""
+    with open(bitstream_path, "rb") as f:
+        pictures, p, verdicts = decode_stream(f.read(), device=device, batch=batch)
+    cfg = p.cfg
+    w, h = cfg.width, cfg.height
+    if recon_path is not None:
+        l, r, t, b = cfg.conf_win_left, cfg.conf_win_right, cfg.conf_win_top, cfg.conf_win_bottom
+        with open(recon_path, "wb") as f:
+            for pic in pictures:
+                y, u, v = pic[:w * h].reshape(h, w), pic[w * h:w * h * 5 // 4].reshape(h // 2, w // 2), pic[w * h * 5 // 4:].reshape(h // 2, w // 2)
+                for plane, s in ((y, 1), (u, 2), (v, 2)):
+                    f.write(np.ascontiguousarray(plane[t // s:(h - b) // s, l // s:(w - r) // s]).tobytes())
+    for i, pic in enumerate(p.pictures):
+        if log:
+            log("POC %4d  QP %2d  [%s]" % (pic.poc if pic.nal_type == 21 else 0, pic.qp, {None: "no hash", True: "hash OK", False: "hash MISMATCH"}[verdicts[i]]))
+    if any(v is False for v in verdicts):
+        raise ValueError("decoded picture hash mismatch in picture(s) %s" % [i for i, v in enumerate(verdicts) if v is False])
+    return pictures, p, verdicts

@@ -326,6 +326,18 @@ typedef struct hevcdl_sao_blk { hevcdl_sao_offset c[3]; } hevcdl_sao_blk;      /
 hevcdl_status hevcdl_sao_frames(hevcdl_ctx *ctx, const uint8_t *org, const uint8_t *deblocked, int n_frames, hevcdl_sao_blk *params, uint8_t *out);
 hevcdl_status hevcdl_sao_frames_dev(hevcdl_ctx *ctx, const void *d_org, const void *d_deblocked, int n_frames, void *d_params, void *d_out, void *stream);
 
+/* SAO with GIVEN parameters -- what a decoder runs behind the deblocking filter: deblocked pictures + the [n_frames][ctus] parameters of a stream (hevcdl_parse_stream;
+ * the layout hevcdl_sao_frames returns and hevcdl_write_access_unit takes: a merged CTU is mode 2 with the direction in component 0) -> the output pictures.  No original and
+ * no decision: hevcdl_sao_apply*_kernel alone.  params is HOST memory in both forms: the call checks it (HEVCDL_ERR_INVALID_ARG: a mode outside 0 .. 2, a type outside
+ * 0 .. 4, a band position outside 0 .. 31, an offset outside +-31, a merge whose candidate lies outside the picture or across a tile / row-slice border of the context),
+ * resolves the merges and stages the result in the context -- one such call at a time.
+ * THE CONTEXT MUST DESCRIBE THE STREAM: picture size, bit depth, tiles, lf_across_tiles and the slice keys (slice_mode, slice_argument, lf_across_slices) decide where the
+ * filter stops, and the call takes them from the context -- it is not given the stream's configuration and cannot compare.  A context created from the parsed
+ * hevcdl_stream_config and hevcdl_slice_layout field by field filters as the stream's encoder did; parameters of a SliceMode 1 stream with lf_across_slices 0 run through a
+ * context without the slice keys are filtered across the slice borders, and no error is reported.  The device form is asynchronous on `stream`; d_out must not be d_deblocked.  A CTU of mode 0 is copied. */
+hevcdl_status hevcdl_sao_apply_frames(hevcdl_ctx *ctx, const void *deblocked, int n_frames, const hevcdl_sao_blk *params, void *out);
+hevcdl_status hevcdl_sao_apply_frames_dev(hevcdl_ctx *ctx, const void *d_deblocked, int n_frames, const hevcdl_sao_blk *params, void *d_out, void *stream);
+
 /* ---- the whole picture pipeline in one call (host buffers): CNN labels (labels_opt == NULL) -> decisions -> deblocking (deblock != 0) -> SAO
  * (sao_opt != NULL; with deblock == 0 -- LoopFilterDisable 1 -- it works on the unfiltered reconstruction, as the reference does) with the pictures staying in HBM between the stages.  records + picture_out (the output picture: after the
  * enabled filters; uint16 samples at 10 bits) + sao_opt feed hevcdl_write_access_unit / hevcdl_write_picture_hash_sei.  stats_opt: SSE before
@@ -788,6 +800,79 @@ int hevcdl_frame_qp_grouping(const int *qp, int n, int *perm, int *run_qp, int *
  * (HEVCDL_ERR_INVALID_ARG otherwise). */
 hevcdl_status hevcdl_get_frame_qp_info(hevcdl_ctx *ctx, size_t *set_bytes, int *rd_launches, int *permute_launches, double *kernel_ms_opt);
 hevcdl_status hevcdl_frame_permute_step(int device, int n_ranges, const size_t *bytes, int n_frames, const int *perm, int scatter, const void *const *src, void *const *dst, size_t guard_bytes);
+/* ---- stream parser (host side; no GPU needed; csrc/hevcdl_parse.cpp, csrc/hevcdl_parse.h) ----------------------------------------------------------------------------------
+ * The inverse of the bitstream writer: an Annex-B stream of the kind hevcdl_write_access_unit_segments produces -- and the reference encoder's streams of the same
+ * configurations -- back into what the writer took.  Parsed: start codes and emulation prevention, VPS / SPS / PPS, every slice_segment_header() (entry points, dependent
+ * segments, deblocking override and offsets, slice_qp_delta, SAO flags), the decoded picture hash of a suffix SEI (MD5, CRC, checksum), and the slice data of I slices by
+ * an arithmetic decoder over csrc/entropy_tables.h: SAO syntax, coding quadtree, part mode, luma and chroma modes, transform tree, cbf, residual_coding with transform skip
+ * and sign data hiding, end_of_slice_segment_flag / end_of_subset_one_bit and the byte alignment of every sub-stream (tiles, wavefront rows).
+ * One picture of the stream: */
+typedef struct hevcdl_parsed_picture {
+  int32_t poc;                   /* slice_pic_order_cnt_lsb (0 for an IDR picture) */
+  int32_t nal_type;              /* of its slice NAL units: 19 IDR_W_RADL, 20 IDR_N_LP, 21 CRA */
+  int32_t qp;                    /* 26 + init_qp_minus26 + slice_qp_delta */
+  int32_t sao;                   /* slice_sao_luma_flag (= slice_sao_chroma_flag): the picture's CTUs carry SAO parameters */
+  hevcdl_dbk_choice dbk;         /* what its slice headers say about the deblocking filter, as hevcdl_get_dbk_choice gives it */
+  int32_t lf_across_slices;      /* slice_loop_filter_across_slices_enabled_flag (the PPS's flag where the header has none) */
+  int32_t n_segments;            /* slice segments (NAL units) of the picture */
+  int32_t hash_method;           /* decoded picture hash SEI behind the picture: 0 none, 1 MD5, 2 CRC, 3 checksum */
+  int32_t hash_plane_bytes;      /* 16 / 2 / 4 */
+  uint8_t digest[48];            /* the plane digests side by side, as hevcdl_picture_hash leaves them */
+} hevcdl_parsed_picture;
+/* cfg (struct_size set by the caller), slices_opt, segments_opt: what hevcdl_write_access_unit_segments would be told to write this stream (cfg->qp: the first picture's;
+ * of cfg->tools only the three bits a stream carries -- transform skip, sign hiding, strong intra smoothing -- are the stream's, the others are set).  *n_pictures: pictures
+ * in the stream.  pictures_opt[picture_capacity], records_opt / sao_opt [ctu_capacity]: picture i's CTUs at i x hevcdl_ctus_per_frame(cfg->width, cfg->height).  With
+ * records_opt NULL only the headers are parsed: call once for the counts, once more with the buffers.  Of a record every field the stream determines is filled (named in
+ * csrc/hevcdl_parse.h), bits / dist / cost are 0; sao_opt is needed when a picture has SAO on and holds zeros for the others.
+ * Accepted is exactly what this library's writer can produce: I slices, main or main10, 4:2:0, CTU 64, minimum CB 8, TU 4 .. 32, any picture size (multiples of 8) with a
+ * conformance window, tiles or wavefront rows, slices of CTU rows or tiles, dependent segments, every tool switch, the deblocking filter on or off.  Anything else is
+ * HEVCDL_ERR_UNSUPPORTED -- P and B slices, PCM, scaling lists, cu_qp_delta_enabled_flag, transquant bypass, other chroma formats or bit depths, slices that do not start at
+ * a CTU row or a tile, ... -- and a damaged stream is HEVCDL_ERR_INVALID_ARG, never a crash: every value that addresses memory is checked where it is read.  Either way
+ * hevcdl_parse_error() is a sentence saying what (per thread; "" after a success). */
+hevcdl_status hevcdl_parse_stream(const uint8_t *stream, size_t bytes, hevcdl_stream_config *cfg, hevcdl_slice_layout *slices_opt, hevcdl_segment_layout *segments_opt,
+                                  hevcdl_parsed_picture *pictures_opt, int picture_capacity, int *n_pictures, hevcdl_ctu_record *records_opt, hevcdl_sao_blk *sao_opt,
+                                  size_t ctu_capacity);
+const char   *hevcdl_parse_error(void);
+/* Records a caller brings itself (n_frames pictures of cfg's size), checked as the parser's own are by construction: depths that form a quadtree with the forced splits
+ * at the picture's edge, NxN only in 8x8 CUs, prediction modes in range and constant over their block, tr_idx a transform tree within TU 4 .. 32 and depth 3, no cbf
+ * bit below the depth of the partition's transform unit, transform-skip flags 0 / 1.  HEVCDL_ERR_INVALID_ARG with a sentence in hevcdl_parse_error() otherwise.  NOT
+ * looked at: levels (any 16-bit value is one), and whether the cbf bits of a unit agree with its levels or with the bits of the depths above it. */
+hevcdl_status hevcdl_validate_records(const hevcdl_stream_config *cfg, const hevcdl_ctu_record *records, int n_frames);
+
+/* ---- reconstruction from records (csrc/recon_kernel.hip, csrc/recon_core.h): the unfiltered reconstruction of intra pictures -- what hevcdl_compress_frames returns
+ * beside its records -- from records alone: per transform unit in coding order the reference samples with availability and substitution (bounded by picture, slice and
+ * tile), the [1 2 1] filter and strong smoothing, all 35 prediction modes with the DC and edge filters, dequantisation at the picture's QP, inverse DST / DCT / transform
+ * skip, clipping.  The standard's integer arithmetic: no tolerance.  Context-free, like hevcdl_code_slice_data: cfg (width, height, bit_depth 8 / 10, qp, the tile grid,
+ * the strong-intra bit of tools) and slices_opt (NULL: one slice a picture) say where a neighbour stops being available; qps_opt (HOST memory, NULL: cfg->qp) a QP per
+ * picture.  records [n_frames][ctus], recon: n_frames planar 4:2:0 pictures (uint16 samples at 10 bits).  The sentence of a refusal is in hevcdl_parse_error().
+ * hevcdl_reconstruct_frames: host buffers -- records that fail hevcdl_validate_records return its status and nothing is launched -- upload, the kernel hevcdl_recon_kernel, download; a wave
+ * rebuilds a CTU row, rows are claimed in order from one ticket, a row stays two CTUs behind the one above.  _dev: device buffers (d_records 16-byte aligned); the records are the
+ * caller's word, having passed hevcdl_validate_records before they were uploaded (the kernel clamps every index all the same); launches on `stream` and WAITS for it (the
+ * row counts are allocated and freed by the call; hevcdl_decode_stream runs the same launch on a buffer the context owns and fetches the error word with the batch).  _host: the same source on the CPU, no GPU needed (TEST AND DIAGNOSTIC: one sample at a time).
+ * hevcdl_recon_launches: launches of the kernel this process has made (TEST AND DIAGNOSTIC). */
+hevcdl_status hevcdl_reconstruct_frames(int device, const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const int32_t *qps_opt,
+                                        const hevcdl_ctu_record *records, int n_frames, void *recon);
+hevcdl_status hevcdl_reconstruct_frames_dev(int device, const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const int32_t *qps_opt,
+                                            const void *d_records, int n_frames, void *d_recon, void *stream);
+hevcdl_status hevcdl_reconstruct_frames_host(const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const int32_t *qps_opt,
+                                             const hevcdl_ctu_record *records, int n_frames, void *recon);
+unsigned long long hevcdl_recon_launches(void);
+
+/* ---- the decoder: a stream of this library's writer, or of the reference encoder in the same configuration, to pictures ------------------------
+ * hevcdl_config_from_stream: the configuration of a context that can decode a parsed stream (hevcdl_parse_stream with records_opt NULL gives cfg, the slice layout and
+ * the picture count): size, bit depth, QP of the first picture, tiles, loop-filter flags and offsets, the slice keys; max_frames = pictures a batch, device as given.
+ * hevcdl_decode_stream: parses on the host, then per batch of cfg.max_frames pictures, in HBM on the context's own buffers: the records are uploaded,
+ * the reconstruction kernel rebuilds the pictures, the deblocking filter runs with every picture's own QP and slice-header parameters, SAO with the stream's parameters,
+ * and the report kernels compute the digests of the pictures where the stream carries a decoded picture hash SEI (MD5, CRC or checksum).  pictures_opt: picture_capacity
+ * pictures in CODED format (the conformance window is not cut: cfg.conf_win_* of the parsed stream say what to show; uint16 samples at 10 bits); info_opt
+ * [picture_capacity]: what the headers said; hash_ok_opt [picture_capacity]: 1 the device's digest equals the SEI's, 0 it does not, -1 the picture has no SEI.
+ * *n_pictures is set as soon as the headers are parsed, also when there is too little room (HEVCDL_ERR_INVALID_ARG).  The context must describe the stream
+ * (HEVCDL_ERR_INVALID_ARG otherwise: size, depth, tiles, slices, loop-filter flags are compared).  A refusal of the parser comes back with its status and its sentence
+ * in hevcdl_last_error(ctx).  The host holds the whole stream's records while it runs (15 120 bytes a CTU). */
+hevcdl_status hevcdl_config_from_stream(const hevcdl_stream_config *stream_cfg, const hevcdl_slice_layout *slices_opt, int max_frames, int device, hevcdl_config *out);
+hevcdl_status hevcdl_decode_stream(hevcdl_ctx *ctx, const uint8_t *stream, size_t bytes, void *pictures_opt, int picture_capacity, int *n_pictures,
+                                   hevcdl_parsed_picture *info_opt, int32_t *hash_ok_opt);
+
 /* kernel timing with HIP events recorded on the launch stream */
 hevcdl_status hevcdl_profile_enable(hevcdl_ctx *ctx, int enable);
 hevcdl_status hevcdl_profile_get(hevcdl_ctx *ctx, hevcdl_profile *out);   /* synchronises, returns and resets */
