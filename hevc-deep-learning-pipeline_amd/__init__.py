@@ -23,7 +23,7 @@ LEAF_LIB_PATH = os.path.join(PKG_DIR, "lib", "libhevcdl_hip_leaf.so")        # -
 WEIGHTS_PATH = os.path.join(PKG_DIR, "weights", "hevc_encoder_model.f32")
 WEIGHT_FLOATS = 637712
 LEAF_SOURCES = ["rd_leaf.hip", "rd_leaf_bd10.hip", "rd_leaf_wide.hip", "rd_leaf_tools.hip"]      # the decision kernel's four builds, each with csrc/rd_leaf_harness.h behind it
-SOURCES = ["cnn_kernel.hip", "fc_kernel.hip", "rd_kernel.hip", "rd_kernel_bd10.hip", "rd_kernel_wide.hip", "rd_kernel_tools.hip", "deblock_kernel.hip", "dbk_select_kernel.hip", "sao_kernel.hip", "quality_kernel.hip", "report_kernel.hip", "entropy_kernel.hip", "source_kernel.hip", "qp_rd_kernel.hip", "frame_permute_kernel.hip", "hevcdl_api.hip", "hevcdl_bitstream.cpp", "hevcdl_parse.cpp", "recon_kernel.hip"]
+SOURCES = ["cnn_kernel.hip", "fc_kernel.hip", "rd_kernel.hip", "rd_kernel_bd10.hip", "rd_kernel_wide.hip", "rd_kernel_tools.hip", "deblock_kernel.hip", "dbk_select_kernel.hip", "sao_kernel.hip", "quality_kernel.hip", "report_kernel.hip", "entropy_kernel.hip", "source_kernel.hip", "qp_rd_kernel.hip", "frame_permute_kernel.hip", "hevcdl_api.hip", "hevcdl_bitstream.cpp", "hevcdl_parse.cpp", "recon_kernel.hip", "slice_decode_kernel.hip"]
 
 STATUS = {0: "OK", 1: "INVALID_ARG", 2: "UNSUPPORTED", 3: "NO_DEVICE", 4: "HIP", 5: "OOM"}
 
@@ -437,6 +437,11 @@ def load_library():
     lib.hevcdl_get_frame_qp_info.argtypes = [vp, szp, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double)]
     lib.hevcdl_frame_permute_step.argtypes = [ci, ci, szp, ci, vp, ci, vp, vp, ctypes.c_size_t]
     lib.hevcdl_parse_stream.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(StreamConfig), slp, sgp, ctypes.POINTER(ParsedPicture), ci, ctypes.POINTER(ci), vp, vp, ctypes.c_size_t]
+    lib.hevcdl_parse_stream_core.argtypes = lib.hevcdl_parse_stream.argtypes
+    lib.hevcdl_parse_stream_dev.argtypes = [ci] + lib.hevcdl_parse_stream.argtypes
+    lib.hevcdl_slice_decode_launches.argtypes = []
+    lib.hevcdl_slice_decode_launches.restype = ctypes.c_uint64
+    lib.hevcdl_enable_device_parse.argtypes = [vp, ci]
     lib.hevcdl_parse_error.argtypes = []
     lib.hevcdl_parse_error.restype = ctypes.c_char_p
     lib.hevcdl_validate_records.argtypes = [ctypes.POINTER(StreamConfig), vp, ci]
@@ -477,7 +482,8 @@ EXPORTS = ["hevcdl_config_default", "hevcdl_create", "hevcdl_destroy", "hevcdl_l
            "hevcdl_frame_qp_families", "hevcdl_frame_qp_grouping", "hevcdl_get_frame_qp_info", "hevcdl_frame_permute_step",
            "hevcdl_parse_stream", "hevcdl_parse_error", "hevcdl_validate_records", "hevcdl_sao_apply_frames", "hevcdl_sao_apply_frames_dev",
            "hevcdl_reconstruct_frames", "hevcdl_reconstruct_frames_dev", "hevcdl_reconstruct_frames_host", "hevcdl_recon_launches",
-           "hevcdl_config_from_stream", "hevcdl_decode_stream"]
+           "hevcdl_config_from_stream", "hevcdl_decode_stream",
+           "hevcdl_parse_stream_core", "hevcdl_parse_stream_dev", "hevcdl_slice_decode_launches", "hevcdl_enable_device_parse"]
 
 
 class ParsedStream:
@@ -497,10 +503,21 @@ class ParsedStream:
         return p.hash_method, bytes(p.digest[:3 * p.hash_plane_bytes])
 
 
-def parse_stream(stream, headers_only=False):
+def parse_stream(stream, headers_only=False, engine="host", device=0):
     """hevcdl_parse_stream (host only, no GPU): an Annex-B stream of this library's writer, or of the reference encoder in the same configuration -> a ParsedStream.
+    engine: who decodes the slice data -- "host" the parser's own decoder, "core" the shared decoder csrc/slice_decode_core.h on the CPU (hevcdl_parse_stream_core),
+    "device" the same source in hevcdl_slice_decode_kernel on `device` (hevcdl_parse_stream_dev).  The headers are the parser's in all three.
     HevcdlError carries the status (1: a damaged stream, 2: a feature outside the decoder) and the parser's sentence."""
     lib = load_library()
+    if engine not in ("host", "core", "device"):
+        raise ValueError("engine is \"host\", \"core\" or \"device\"")
+    if engine == "core":
+        parse = lib.hevcdl_parse_stream_core
+    elif engine == "device":
+        def parse(*a):
+            return lib.hevcdl_parse_stream_dev(int(device), *a)
+    else:
+        parse = lib.hevcdl_parse_stream
     buf = np.frombuffer(bytes(stream), np.uint8)
     cfg = StreamConfig()
     cfg.struct_size = ctypes.sizeof(StreamConfig)
@@ -508,19 +525,20 @@ def parse_stream(stream, headers_only=False):
 
     def check(st):
         if st != 0:
-            raise HevcdlError(st, "hevcdl_parse_stream: " + lib.hevcdl_parse_error().decode())
+            raise HevcdlError(st, {"host": "hevcdl_parse_stream: ", "core": "hevcdl_parse_stream_core: ", "device": "hevcdl_parse_stream_dev: "}[engine] + lib.hevcdl_parse_error().decode())
     check(lib.hevcdl_parse_stream(buf.ctypes.data, buf.size, ctypes.byref(cfg), ctypes.byref(sl), ctypes.byref(sg), None, 0, ctypes.byref(n), None, None, 0))
     ctus = ((cfg.width + 63) // 64) * ((cfg.height + 63) // 64)
     pics = (ParsedPicture * n.value)()
     records = None if headers_only else np.zeros((n.value, ctus), REC_DTYPE)
     sao = None if headers_only else np.zeros((n.value, ctus, 3), SAO_DTYPE)
-    check(lib.hevcdl_parse_stream(buf.ctypes.data, buf.size, ctypes.byref(cfg), ctypes.byref(sl), ctypes.byref(sg), pics, n.value, ctypes.byref(n),
+    check(parse(buf.ctypes.data, buf.size, ctypes.byref(cfg), ctypes.byref(sl), ctypes.byref(sg), pics, n.value, ctypes.byref(n),
                                   None if headers_only else records.ctypes.data, None if headers_only else sao.ctypes.data, 0 if headers_only else n.value * ctus))
     return ParsedStream(cfg, sl if sl.mode else None, sg if sg.mode else None, list(pics), records, sao)
 
 
-def decode_stream(stream, device=0, batch=64):
-    """hevcdl_decode_stream on a context made for the stream (hevcdl_config_from_stream): parsed on the host; reconstruction, deblocking, SAO and the digests on the
+def decode_stream(stream, device=0, batch=64, device_parse=False):
+    """hevcdl_decode_stream on a context made for the stream (hevcdl_config_from_stream): parsed on the host -- with device_parse the headers only, the slice data by
+    hevcdl_slice_decode_kernel (hevcdl_enable_device_parse) --; reconstruction, deblocking, SAO and the digests on the
     device, `batch` pictures at a time in HBM.  -> (pictures [n, w * h * 3 / 2] in coded format, uint16 at 10 bits; the stream's StreamConfig, whose conf_win_* say what
     to show; the pictures' ParsedPicture list; verdicts [n]: True / False where the device's digest was compared with a hash SEI, None where the stream carries none).
     HevcdlError carries the status and the decoder's sentence."""
@@ -537,6 +555,10 @@ def decode_stream(stream, device=0, batch=64):
     if st:
         raise HevcdlError(st, "hevcdl_create: " + (lib.hevcdl_create_error() or b"").decode())
     try:
+        if device_parse:
+            st = lib.hevcdl_enable_device_parse(h, 1)
+            if st:
+                raise HevcdlError(st, "hevcdl_enable_device_parse: " + (lib.hevcdl_last_error(h) or b"").decode())
         buf = np.frombuffer(bytes(stream), np.uint8)
         pictures = np.zeros((n, head.cfg.width * head.cfg.height * 3 // 2), np.uint8 if head.cfg.bit_depth == 8 else np.dtype("<u2"))
         info, ok, count = (ParsedPicture * n)(), np.zeros(n, np.int32), ctypes.c_int(0)
@@ -1514,6 +1536,10 @@ class Encoder:
     def enable_device_entropy(self, on=True):
         """encode_pictures* also code the slice data of their pictures on the device; read it with get_slice_data or take it from encode_pictures_stream."""
         self._check(self.lib.hevcdl_enable_device_entropy(self._h, int(bool(on))))
+
+    def enable_device_parse(self, on=True):
+        """hevcdl_decode_stream on this context decodes the slice data on the device (hevcdl_enable_device_parse); off gives the buffers back."""
+        self._check(self.lib.hevcdl_enable_device_parse(self._h, int(bool(on))))
 
     def set_entropy_capacity(self, capacity_per_ctu):
         """Test entry point (hevcdl_set_entropy_capacity): the capacity per CTU of the next enable_device_entropy(True); a small value makes the host code the pictures."""

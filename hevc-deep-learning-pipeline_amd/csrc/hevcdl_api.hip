@@ -16,6 +16,7 @@
 #include "slice_grid.h"
 #include "qp_rd.h"
 #include "frame_qp.h"
+#include "slice_decode_units.h"
 
 enum { LABELS_PER_CTU = 16, LOGITS_PER_CTU = 64, CTU_RGB_BYTES = 64 * 64 * 3 };      // of a CTU: its 16x16 cells, four logits a cell, the RGB input of hevcdl_predict_depth_rgb
 
@@ -92,6 +93,15 @@ struct Staging {      // staging buffers for the host-pointer entry points: the 
 };
 struct SaoWorkspace { DevBuf<unsigned char> d_sao_stats, d_sao_recon, d_sao_params, d_sao_cand; std::vector<hevcdl_sao_blk> given; };
 struct Decoder { DevBuf<unsigned char> d_work; std::vector<uint32_t> keep; };      // hevcdl_decode_stream: the reconstruction's units, QPs and row counts (cfg.max_frames), by the first call      // SAO workspace: by the first call that needs each
+// slice data DECODED on the device (slice_decode_kernel.hip): everything below is allocated by hevcdl_enable_device_parse(ctx, 1), sized for cfg.max_frames pictures, and
+// freed by (ctx, 0); the three that hold a batch's bytes and tables are given back and allocated larger when a batch needs more.  A context that never turns the switch
+// on allocates and launches none of it
+struct DeviceParse {
+  bool on = false;
+  DevBuf<unsigned char> d_tables, d_rbsp, d_sao; DevBuf<hevcdl_sd::SdSub> d_subs; DevBuf<hevcdl_sd::SdUnit> d_units; DevBuf<hevcdl_sd::SdResult> d_results;
+  size_t rbsp_bytes = 0, n_subs = 0, n_units = 0;      // what the three hold
+  std::vector<hevcdl_sao_blk> h_sao; std::vector<hevcdl_sd::SdResult> h_results; std::vector<hevcdl_sd::SdUnit> h_units;      // the batch in work
+};
 // picture quality (quality_kernel.hip): the workspace is allocated by hevcdl_enable_quality(ctx, 1), or by the first hevcdl_picture_quality* call of a context
 // with the switch off, and freed by hevcdl_enable_quality(ctx, 0); d_q_out by the switch or by hevcdl_picture_quality (host buffers).  A context that uses neither allocates none of it
 struct Quality {
@@ -182,7 +192,7 @@ struct hevcdl_ctx {
   int col_bd[21] = { 0 }, row_bd[23] = { 0 };    // tile boundaries in CTUs
   DevBuf<float> d_weights, d_a3; size_t a3_ctus = 0;   // d_a3: conv3 outputs of one chunk of CTUs (32 KB per CTU): the hand-over from the conv kernel to the head kernel
   DevBuf<int> d_flag;                  // device-side error flag of the label check
-  Staging stage; SaoWorkspace sao; Decoder dec; Quality q; Report rp; Entropy ec; Source src; Session ses; RdWorkspace rd; DbkSelect dbk; QpRd qprd; FrameQp fqp;
+  Staging stage; SaoWorkspace sao; Decoder dec; DeviceParse dp; Quality q; Report rp; Entropy ec; Source src; Session ses; RdWorkspace rd; DbkSelect dbk; QpRd qprd; FrameQp fqp;
   int ec_capacity_per_ctu = 0;         // hevcdl_set_entropy_capacity (tests): 0 = the default; outlives the entropy switch
   bool profile = false;
   std::vector<Event> ev_cnn, ev_rd, ev_conv;       // start/stop pairs (ev_conv: the convolution kernel alone, one pair per chunk of CTUs)
@@ -1323,6 +1333,67 @@ extern "C" hevcdl_status hevcdl_config_from_stream(const hevcdl_stream_config *s
 }
 
 static hevcdl_status ensure_report_workspace(hevcdl_ctx *ctx);      // (with the report entry points below)
+
+// ---- slice data decoded on the device (hevcdl_enable_device_parse) ----
+extern "C" hevcdl_status hevcdl_enable_device_parse(hevcdl_ctx *ctx, int on)
+{
+  if (!ctx) return HEVCDL_ERR_INVALID_ARG;
+  TRY(check_frames(ctx, 0));
+  if (!on) {
+    if (!ctx->dp.on) return HEVCDL_OK;
+    TRY(sync_or_fail(ctx, "hevcdl_enable_device_parse"));
+    ctx->dp = DeviceParse();
+    return HEVCDL_OK;
+  }
+  if (ctx->dp.on) return HEVCDL_OK;
+  DeviceParse &g = ctx->dp;
+  // a picture's units: its tiles (the context's grid: row slices are a column of them) or one; its sub-streams: those, or its CTU rows.  Bytes: 256 a CTU to begin with
+  const size_t per = (size_t)std::max(ctx->cfg.tile_columns * ctx->cfg.tile_rows, 1) + (size_t)ctx->ctus_y, n = per * (size_t)ctx->cfg.max_frames;
+  const size_t rbsp = (size_t)256 * ctx->ctus * ctx->cfg.max_frames;
+  TRY(alloc_all(ctx, { want(g.d_tables, sizeof(hevcdl_ec::EcTables)), want(g.d_rbsp, rbsp), want(g.d_sao, ctx->sao_bytes((size_t)ctx->cfg.max_frames)), want(g.d_subs, n * sizeof(hevcdl_sd::SdSub)),
+                       want(g.d_units, n * sizeof(hevcdl_sd::SdUnit)), want(g.d_results, n * sizeof(hevcdl_sd::SdResult)) }, "device parse buffers (cfg.max_frames)"));
+  const hipError_t e = hipMemcpy(g.d_tables, &hevcdl_ec::ec_tables(), sizeof(hevcdl_ec::EcTables), hipMemcpyHostToDevice);
+  if (e != hipSuccess) { ctx->dp = DeviceParse(); return hip_fail(ctx, "device parse tables", e); }
+  g.rbsp_bytes = rbsp; g.n_subs = g.n_units = n; g.on = true;
+  return HEVCDL_OK;
+}
+
+// pictures [first, first + cnt) of su: bytes and tables up, the kernel into stage.d_records and dp.d_sao, the error slots back -- an error is HEVCDL_ERR_INVALID_ARG with
+// picture, CTU and sentence -- and with want_sao the SAO blocks into dp.h_sao
+static hevcdl_status device_parse_batch(hevcdl_ctx *ctx, const hevcdl_parse::StreamUnits &su, int first, int cnt, bool want_sao)
+{
+  DeviceParse &g = ctx->dp;
+  size_t sub0, n_subs, byte0, n_bytes;
+  const hevcdl_status st = hevcdl_parse::batch_tables(su, first, cnt, g.h_units, sub0, n_subs, byte0, n_bytes);
+  if (st != HEVCDL_OK) return fail(ctx, st, hevcdl_parse_error());
+  TRY(ensure_staging(ctx));
+  if (n_bytes > g.rbsp_bytes || n_subs > g.n_subs || g.h_units.size() > g.n_units) { // a batch that needs more: nothing of the last one is in flight (every batch ends with a wait)
+    TRY(sync_or_fail(ctx, "device parse buffers"));
+    if (n_bytes > g.rbsp_bytes) { g.d_rbsp.reset(); g.rbsp_bytes = 0; TRY(lazy_alloc(ctx, g.d_rbsp, n_bytes, "device parse: the RBSP bytes of a batch")); g.rbsp_bytes = n_bytes; }
+    if (n_subs > g.n_subs) { g.d_subs.reset(); g.n_subs = 0; TRY(lazy_alloc(ctx, g.d_subs, n_subs * sizeof(hevcdl_sd::SdSub), "device parse: the sub-stream table of a batch")); g.n_subs = n_subs; }
+    if (g.h_units.size() > g.n_units) {
+      g.d_units.reset(); g.d_results.reset(); g.n_units = 0;
+      TRY(lazy_alloc(ctx, g.d_units, g.h_units.size() * sizeof(hevcdl_sd::SdUnit), "device parse: the unit table of a batch"));
+      TRY(lazy_alloc(ctx, g.d_results, g.h_units.size() * sizeof(hevcdl_sd::SdResult), "device parse: the error slots of a batch"));
+      g.n_units = g.h_units.size();
+    }
+  }
+  if (n_bytes) HIPCHK(hipMemcpy(g.d_rbsp, su.rbsp.data() + byte0, n_bytes, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(g.d_subs, su.subs.data() + sub0, n_subs * sizeof(hevcdl_sd::SdSub), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(g.d_units, g.h_units.data(), g.h_units.size() * sizeof(hevcdl_sd::SdUnit), hipMemcpyHostToDevice));
+  hevcdl_slice_decode_params k;
+  k.sd = su.sd; k.blob = g.d_rbsp; k.blob_bytes = n_bytes; k.subs = g.d_subs; k.units = g.d_units; k.n_subs = (int)n_subs; k.n_units = (int)g.h_units.size();
+  k.records = ctx->stage.d_records; k.sao = g.d_sao; k.ctus = ctx->ctus; k.n_pics = cnt; k.results = g.d_results; k.tables = g.d_tables;
+  if (!hevcdl_launch_slice_decode(&k, nullptr)) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "device parse: the unit tables of a batch do not fit a launch");
+  TRY(launch_status(ctx));
+  g.h_results.resize(g.h_units.size());
+  HIPCHK(hipMemcpy(g.h_results.data(), g.d_results, g.h_units.size() * sizeof(hevcdl_sd::SdResult), hipMemcpyDeviceToHost));
+  hevcdl_sd::SdResult res = { 0, -1 };
+  const int bad = hevcdl_slice_decode_first_error(g.h_units, g.h_results.data(), &res);
+  if (bad >= 0) { hevcdl_parse::set_slice_error(first + bad, res); return fail(ctx, HEVCDL_ERR_INVALID_ARG, hevcdl_parse_error()); }
+  if (want_sao) { g.h_sao.resize((size_t)cnt * ctx->ctus); HIPCHK(hipMemcpy(g.h_sao.data(), g.d_sao, ctx->sao_bytes((size_t)cnt), hipMemcpyDeviceToHost)); }
+  return HEVCDL_OK;
+}
 namespace { struct FrameQpGuard { hevcdl_ctx *c; ~FrameQpGuard() { c->fqp.list.clear(); } }; }
 
 extern "C" hevcdl_status hevcdl_decode_stream(hevcdl_ctx *ctx, const uint8_t *stream, size_t bytes, void *pictures_opt, int picture_capacity, int *n_pictures,
@@ -1352,9 +1423,22 @@ extern "C" hevcdl_status hevcdl_decode_stream(hevcdl_ctx *ctx, const uint8_t *st
   if (ctx->cfg.delta_qp_rd || ctx->cfg.deblocking_metric) return fail(ctx, HEVCDL_ERR_UNSUPPORTED, "a context with delta_qp_rd or deblocking_metric does not decode");
   if (n > picture_capacity) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "the stream holds more pictures than there is room for (*n_pictures says how many)");
   std::vector<hevcdl_parsed_picture> pics; std::vector<hevcdl_ctu_record> recs; std::vector<hevcdl_sao_blk> sao;
-  try { pics.resize((size_t)n); recs.resize((size_t)n * ctx->ctus); sao.resize((size_t)n * ctx->ctus); } catch (...) { return fail(ctx, HEVCDL_ERR_OOM, "host memory for the stream's records"); }
-  st = hevcdl_parse_stream(stream, bytes, &sc, &sl, &sg, pics.data(), n, &n, recs.data(), sao.data(), recs.size());
-  if (st != HEVCDL_OK) return fail(ctx, st, hevcdl_parse_error());
+  hevcdl_parse::StreamUnits su;                      // device parse: the slice data of the stream, cut into units
+  const bool dev_parse = ctx->dp.on;
+  if (dev_parse) {
+    try { st = hevcdl_parse::collect_units(stream, bytes, 1, 1, (size_t)-1, su); } catch (...) { return fail(ctx, HEVCDL_ERR_OOM, "host memory for the stream's slice data"); }
+    if (st != HEVCDL_OK) return fail(ctx, st, hevcdl_parse_error());
+    if (su.ctus != ctx->ctus) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "the context does not describe the stream");
+    pics = su.pictures;
+    if (su.pending != HEVCDL_OK) { // the headers refuse a later picture: as the host parser would, an error in the slice data of a picture in front of it comes first
+      for (int first = 0; first < (int)pics.size(); first += ctx->cfg.max_frames) TRY(device_parse_batch(ctx, su, first, std::min(ctx->cfg.max_frames, (int)pics.size() - first), false));
+      return fail(ctx, su.pending, su.pending_sentence);
+    }
+  } else {
+    try { pics.resize((size_t)n); recs.resize((size_t)n * ctx->ctus); sao.resize((size_t)n * ctx->ctus); } catch (...) { return fail(ctx, HEVCDL_ERR_OOM, "host memory for the stream's records"); }
+    st = hevcdl_parse_stream(stream, bytes, &sc, &sl, &sg, pics.data(), n, &n, recs.data(), sao.data(), recs.size());
+    if (st != HEVCDL_OK) return fail(ctx, st, hevcdl_parse_error());
+  }
   TRY(ensure_staging(ctx));
   TRY(lazy_alloc(ctx, ctx->stage.d_picture, ctx->frame_bytes * (size_t)ctx->cfg.max_frames, "output pictures (cfg.max_frames)"));
   TRY(ensure_report_workspace(ctx));
@@ -1368,14 +1452,15 @@ extern "C" hevcdl_status hevcdl_decode_stream(hevcdl_ctx *ctx, const uint8_t *st
     qps.resize((size_t)cnt); choices.resize((size_t)cnt); rep.resize((size_t)cnt);
     bool any_sao = false, own_qp = false;
     for (int i = 0; i < cnt; i++) { qps[i] = pics[first + i].qp; choices[i] = pics[first + i].dbk; any_sao |= pics[first + i].sao != 0; own_qp |= qps[i] != ctx->cfg.qp; }
-    HIPCHK(hipMemcpyAsync(ctx->stage.d_records, recs.data() + (size_t)first * ctx->ctus, ctx->records_bytes((size_t)cnt), hipMemcpyHostToDevice, nullptr));
+    if (dev_parse) TRY(device_parse_batch(ctx, su, first, cnt, any_sao));      // the records into stage.d_records, the SAO blocks into dp.h_sao; an error before anything else is launched
+    else HIPCHK(hipMemcpyAsync(ctx->stage.d_records, recs.data() + (size_t)first * ctx->ctus, ctx->records_bytes((size_t)cnt), hipMemcpyHostToDevice, nullptr));
     const uint32_t *d_err = nullptr;
     st = hevcdl_recon_enqueue(&sc, &sl, qps.data(), ctx->stage.d_records, cnt, ctx->stage.d_recon, ctx->dec.d_work, work, nullptr, ctx->dec.keep, &d_err);
     if (st != HEVCDL_OK) return fail(ctx, st, hevcdl_parse_error());
     if (own_qp) TRY(hevcdl_set_frame_qps(ctx, qps.data(), cnt)); else ctx->fqp.list.clear();
     TRY(hevcdl_deblock_frames_choice_dev(ctx, ctx->stage.d_recon, cnt, ctx->stage.d_records, choices.data(), ctx->stage.d_recon, nullptr));
     const void *d_final = ctx->stage.d_recon;
-    if (any_sao) { TRY(hevcdl_sao_apply_frames_dev(ctx, ctx->stage.d_recon, cnt, sao.data() + (size_t)first * ctx->ctus, ctx->stage.d_picture, nullptr)); d_final = ctx->stage.d_picture; }
+    if (any_sao) { TRY(hevcdl_sao_apply_frames_dev(ctx, ctx->stage.d_recon, cnt, dev_parse ? ctx->dp.h_sao.data() : sao.data() + (size_t)first * ctx->ctus, ctx->stage.d_picture, nullptr)); d_final = ctx->stage.d_picture; }
     for (int i = 0; i < cnt; i++) if (hash_ok_opt) hash_ok_opt[first + i] = -1;
     for (int method = 1; method <= 3; method++) { // the digests of the pictures still in HBM, by the report kernels, against the stream's SEI
       bool any = false;

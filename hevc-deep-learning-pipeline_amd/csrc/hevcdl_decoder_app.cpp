@@ -1,9 +1,10 @@
 // hevcdl_decoder_app.cpp -- bin/TAppDecoderHevcdl: the command-line decoder over the C ABI, with the reference decoder's option names.
-//   TAppDecoderHevcdl -b str.bin [-o rec.yuv] [-d depth] [--device n] [--batch n]
+//   TAppDecoderHevcdl -b str.bin [-o rec.yuv] [-d depth] [--device n] [--batch n] [--DeviceParse 0|1]
 // -b the stream, -o the reconstruction file (the conformance window of every picture, planar 4:2:0), -d the file's bit depth (0, the default: the stream's own; samples
 // above 8 bits are two bytes, little endian; converted as the reference's file writer does: up by a left shift, down by a rounding right shift and a clip).  One line per
 // picture: POC, QP and the verdict of the decoded picture hash -- the device's digest against the stream's SEI.  Exit status: 0; 1 when a digest does not match; 2 for
-// anything else (options, the file, a stream the decoder refuses: its sentence is printed).
+// anything else (options, the file, a stream the decoder refuses: its sentence is printed).  --DeviceParse 1: the slice data is decoded on the device
+// (hevcdl_enable_device_parse); the pictures, the lines and the exit status are the same.
 // Host C++: the stream is parsed and the pictures are rebuilt by hevcdl_decode_stream; nothing here touches a sample but the window and the depth of the file.
 #include <cstdint>
 #include <cstdio>
@@ -31,7 +32,7 @@ static void write_plane(FILE *f, const unsigned char *pic, size_t plane_off, int
 int main(int argc, char **argv)
 {
   std::string in, out;
-  int depth = 0, device = 0, batch = 64;
+  int depth = 0, device = 0, batch = 64, device_parse = 0;
   for (int i = 1; i < argc; i++) {
     const std::string a = argv[i];
     auto value = [&](const char *name) -> const char * { if (i + 1 >= argc) { fprintf(stderr, "Error: %s needs a value\n", name); exit(2); } return argv[++i]; };
@@ -40,7 +41,8 @@ int main(int argc, char **argv)
     else if (a == "-d" || a == "--OutputBitDepth") depth = atoi(value("-d"));
     else if (a == "--device") device = atoi(value("--device"));
     else if (a == "--batch") batch = atoi(value("--batch"));
-    else { fprintf(stderr, "Error: unknown option '%s'\nusage: TAppDecoderHevcdl -b str.bin [-o rec.yuv] [-d depth] [--device n] [--batch n]\n", a.c_str()); return 2; }
+    else if (a == "--DeviceParse") device_parse = atoi(value("--DeviceParse"));
+    else { fprintf(stderr, "Error: unknown option '%s'\nusage: TAppDecoderHevcdl -b str.bin [-o rec.yuv] [-d depth] [--device n] [--batch n] [--DeviceParse 0|1]\n", a.c_str()); return 2; }
   }
   if (in.empty()) { fprintf(stderr, "Error: no bitstream file (-b)\n"); return 2; }
   if (depth != 0 && (depth < 8 || depth > 16)) { fprintf(stderr, "Error: -d is 0 or 8 .. 16\n"); return 2; }
@@ -64,6 +66,7 @@ int main(int argc, char **argv)
   hevcdl_ctx *ctx = nullptr;
   st = hevcdl_create(&cfg, weights.data(), weights.size(), &ctx);
   if (st != HEVCDL_OK) { fprintf(stderr, "Error: hevcdl_create: status %d %s\n", (int)st, hevcdl_create_error()); return 2; }
+  if (device_parse && (st = hevcdl_enable_device_parse(ctx, 1)) != HEVCDL_OK) { fprintf(stderr, "Error: %s (status %d)\n", hevcdl_last_error(ctx), (int)st); hevcdl_destroy(ctx); return 2; }
   const size_t fb = hevcdl_frame_bytes_bd(sc.width, sc.height, sc.bit_depth);
   std::vector<unsigned char> pictures(fb * (size_t)n);
   std::vector<hevcdl_parsed_picture> info((size_t)n); std::vector<int32_t> ok((size_t)n);

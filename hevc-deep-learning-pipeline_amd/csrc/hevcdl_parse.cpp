@@ -22,6 +22,8 @@
 #define EC_FN static inline
 #include "entropy_coder.h"
 #include "hevcdl_parse.h"
+#define SD_FN static inline
+#include "slice_decode_units.h"
 
 namespace hevcdl_parse {
 static thread_local char g_error[256] = "";
@@ -907,4 +909,252 @@ extern "C" hevcdl_status hevcdl_validate_records(const hevcdl_stream_config *cfg
     if (v.why) INVALID("picture %d, CTU %d: %s", f, a, v.why);
   }
   return HEVCDL_OK;
+}
+
+// ---- the same stream through the shared slice-data decoder (slice_decode_core.h) ---------------------------------------------------------------------------------
+// Everything in front of the slice data is the code above: split_annexb, unescape, the parameter-set, slice-header and SEI parsers, cut_substreams, derive_layouts and
+// check_layouts, called in hevcdl_parse_stream's order -- a header refusal is the parser's, sentence included.  Where the parser decodes a picture, collect_units cuts
+// it into units (slice_decode_units.h); who walks them is the caller's choice: the CPU (hevcdl_parse_stream_core) or hevcdl_slice_decode_kernel.
+namespace {
+using namespace hevcdl_sd;
+
+// the units of one picture behind check_layouts: sub-streams start at a segment, a tile and a wavefront row; units at a tile, at a row slice, or at the picture
+hevcdl_status picture_units(const ParamSets &ps, const Grid &g, const hevcdl_slice_layout &sl, const std::vector<SegmentData> &segs, const hevcdl_parsed_picture &cur, StreamUnits &out)
+{
+  const int pic = (int)out.pictures.size();
+  const size_t byte0 = out.rbsp.size(), sub0 = out.subs.size();
+  const bool tiled = ps.tcols * ps.trows > 1;
+  auto new_tile = [&](int ts) { return ts == 0 || g.tile_id[(size_t)g.ts2rs[(size_t)ts]] != g.tile_id[(size_t)g.ts2rs[(size_t)ts - 1]]; };
+  std::vector<int> sub_ts;                          // first CTU (tile scan) of every sub-stream of the picture
+  for (size_t i = 0; i < segs.size(); i++) {
+    const int a = g.rs2ts[(size_t)segs[i].h.address], b = i + 1 < segs.size() ? g.rs2ts[(size_t)segs[i + 1].h.address] : g.n;
+    size_t k = 0;
+    for (int ts = a; ts < b; ts++) {
+      if (!(ts == a || new_tile(ts) || (ps.wpp && g.ts2rs[(size_t)ts] % g.cx == 0))) continue;
+      if (k < segs[i].subs.size()) {
+        const auto &sb = segs[i].subs[k];
+        if (out.rbsp.size() - byte0 + sb.second > 0xffffffffull) UNSUPPORTED("a picture of more than 4 GB of slice data is outside this decoder");
+        out.subs.push_back({ (uint32_t)(out.rbsp.size() - byte0), (uint32_t)sb.second, 0u, 0u });
+        out.rbsp.insert(out.rbsp.end(), sb.first, sb.first + sb.second);
+        sub_ts.push_back(ts);
+      }
+      k++;
+    }
+    if (k != segs[i].subs.size()) INVALID("slice segment %d has %d sub-streams, %d are needed", (int)i, (int)segs[i].subs.size(), (int)k);
+    out.subs.back().ends_segment = 1;
+  }
+  int slice_addr = 0;
+  size_t si = 0, k = 0;
+  for (int ts = 0; ts < g.n; ) {
+    while (si < segs.size() && g.rs2ts[(size_t)segs[si].h.address] <= ts) { if (!segs[si].h.dependent) slice_addr = segs[si].h.address; si++; }
+    int end = g.n;                                  // the unit [ts, end)
+    if (tiled) { end = ts + 1; while (end < g.n && !new_tile(end)) end++; }
+    else if (sl.mode == 1) { for (size_t j = 0; j < segs.size(); j++) { const int a = g.rs2ts[(size_t)segs[j].h.address]; if (a > ts && a < end) end = a; } }
+    SdUnit u; memset(&u, 0, sizeof u);
+    u.pic = pic; u.first_ts = ts; u.n_ctus = end - ts; u.slice_addr = slice_addr; u.qp = cur.qp; u.sao_on = cur.sao;
+    u.sub0 = (int)(sub0 + k);
+    while (k < sub_ts.size() && sub_ts[k] < end) { k++; u.n_subs++; }
+    const int a = g.ts2rs[(size_t)ts], b = g.ts2rs[(size_t)end - 1];
+    u.cx0 = a % g.cx; u.cy0 = a / g.cx; u.cx1 = b % g.cx + 1; u.cy1 = b / g.cx + 1;
+    out.units.push_back(u);
+    ts = end;
+  }
+  for (size_t j = out.pic_unit.back(); j < out.units.size(); j++) out.units[j].rbsp_bytes = (uint32_t)(out.rbsp.size() - byte0);
+  out.pictures.push_back(cur);
+  out.pic_byte.push_back(out.rbsp.size()); out.pic_sub.push_back(out.subs.size()); out.pic_unit.push_back(out.units.size());
+  return HEVCDL_OK;
+}
+
+// hevcdl_parse_stream's loop over the NAL units, its checks in its order; a picture that closes is cut into units where the parser decodes it
+hevcdl_status collect_loop(const uint8_t *stream, size_t bytes, int want_slice_data, int have_sao, size_t ctu_capacity, StreamUnits &out)
+{
+  std::vector<std::pair<size_t, size_t>> units;
+  split_annexb(stream, bytes, units);
+  if (units.empty()) INVALID("no start code in the stream");
+  ParamSets ps; memset(&ps, 0, sizeof ps);
+  ParamSets active; memset(&active, 0, sizeof active);
+  Grid g; bool have_grid = false;
+  hevcdl_slice_layout sl = { 0, 0, 1 }; hevcdl_segment_layout sg = { 0, 0 };
+  std::vector<SegmentData> segs; std::vector<Nal> seg_nals;
+  hevcdl_parsed_picture cur; memset(&cur, 0, sizeof cur);
+  int count = 0, level_idc = 0, first_qp = 0, ps_before_second = 0;
+  bool open = false;
+
+  auto close_picture = [&]() -> hevcdl_status {
+    if (!open) return HEVCDL_OK;
+    open = false;
+    hevcdl_status st;
+    if (count == 0) { st = derive_layouts(active, g, segs, sl, sg); if (st != HEVCDL_OK) return st; }
+    st = check_layouts(active, g, segs, sl, sg);
+    if (st != HEVCDL_OK) return st;
+    cur.n_segments = (int)segs.size();
+    if (want_slice_data) {
+      if ((size_t)(count + 1) * (size_t)g.n > ctu_capacity) INVALID("room for %llu CTUs, picture %d needs %llu", (unsigned long long)ctu_capacity, count, (unsigned long long)(count + 1) * g.n);
+      if (cur.sao && !have_sao) INVALID("the stream carries SAO parameters and there is no room for them");
+      if (count == 0) {
+        SdStream &d = out.sd;
+        d.W = active.width; d.H = active.height; d.ctus_x = g.cx; d.ctus_y = g.cy; d.wpp = active.wpp; d.tskip = active.tskip; d.sign_hiding = active.sign_hiding;
+        d.max_sao = (1 << (std::min(active.bit_depth, 10) - 5)) - 1; d.row_slices = sl.mode == 1;
+      }
+      for (const SegmentData &s : segs) if (s.subs.empty()) INVALID("a slice segment without data");
+      st = picture_units(active, g, sl, segs, cur, out);
+      if (st != HEVCDL_OK) return st;
+    } else out.pictures.push_back(cur);
+    if (count == 0) first_qp = cur.qp;
+    count++;
+    segs.clear(); seg_nals.clear();
+    return HEVCDL_OK;
+  };
+
+  seg_nals.reserve(units.size());
+  for (const auto &u : units) {
+    Nal nal;
+    if (!unescape(stream + u.first, u.second - u.first, nal)) INVALID("a NAL unit of %llu bytes, or one with forbidden_zero_bit set", (unsigned long long)(u.second - u.first));
+    hevcdl_status st = HEVCDL_OK;
+    if (nal.type == 32) { st = close_picture(); if (st != HEVCDL_OK) return st; continue; }
+    if (nal.type == 33 || nal.type == 34) {
+      st = close_picture(); if (st != HEVCDL_OK) return st;
+      st = nal.type == 33 ? parse_sps(nal, ps) : parse_pps(nal, ps);
+      if (st != HEVCDL_OK) return st;
+      if (nal.type == 33) level_idc = ps.level_idc;
+      if (count == 1) ps_before_second = 1;
+      continue;
+    }
+    if (nal.type == 40 || nal.type == 39) {
+      if (nal.type == 40 && open) { st = parse_hash_sei(nal, cur); if (st != HEVCDL_OK) return st; }
+      continue;
+    }
+    if (nal.type == 35 || nal.type == 36 || nal.type == 37 || nal.type == 38) { if (nal.type != 38) { st = close_picture(); if (st != HEVCDL_OK) return st; } continue; }
+    if (nal.type >= 32) UNSUPPORTED("NAL unit type %d is outside this decoder", nal.type);
+    if (nal.type != 19 && nal.type != 20 && nal.type != 21) UNSUPPORTED("NAL unit type %d: only intra random access pictures (IDR, CRA) are decoded", nal.type);
+    if (!ps.have_sps || !ps.have_pps) INVALID("a slice NAL unit in front of the SPS and the PPS");
+    if (nal.rbsp.empty()) INVALID("an empty slice NAL unit");
+    if (nal.rbsp[0] & 0x80) {
+      st = close_picture(); if (st != HEVCDL_OK) return st;
+      if (count > 0 && memcmp(&ps, &active, sizeof ps) != 0) UNSUPPORTED("parameter sets that change inside the stream are outside this decoder");
+      if (count == 0) { active = ps; st = make_grid(active, g); if (st != HEVCDL_OK) return st; have_grid = true; out.ctus = g.n; }
+      memset(&cur, 0, sizeof cur);
+      open = true;
+    } else if (!open) INVALID("a slice segment without the first segment of its picture");
+    if (segs.size() >= (size_t)MAX_SEGMENTS) INVALID("more than %d slice segments a picture", (int)MAX_SEGMENTS);
+    seg_nals.push_back(std::move(nal));
+    const Nal &kept = seg_nals.back();
+    SegmentData sd;
+    st = parse_slice_header(kept, active, g.n, sd.h);
+    if (st != HEVCDL_OK) return st;
+    if (sd.h.first != (segs.empty() ? 1 : 0)) INVALID("first_slice_segment_in_pic_flag of a slice segment");
+    if (!sd.h.dependent) {
+      if (sd.h.sao_luma != sd.h.sao_chroma) UNSUPPORTED("SAO for one of luma / chroma only is outside this decoder");
+      const int qp = active.init_qp + sd.h.qp_delta;
+      if (qp < 0 || qp > 51) INVALID("slice QP %d", qp);
+      if (segs.empty()) { cur.poc = sd.h.poc; cur.nal_type = sd.h.nal_type; cur.qp = qp; cur.sao = sd.h.sao_luma; cur.dbk = sd.h.dbk; cur.lf_across_slices = sd.h.lf_across_slices; }
+      else if (cur.qp != qp || cur.sao != sd.h.sao_luma || memcmp(&cur.dbk, &sd.h.dbk, sizeof cur.dbk) != 0 || cur.lf_across_slices != sd.h.lf_across_slices || cur.poc != sd.h.poc)
+        UNSUPPORTED("slices of one picture that differ in QP, SAO or deblocking parameters are outside this decoder");
+    } else if (segs.empty()) INVALID("a dependent slice segment opens the picture");
+    if (kept.type != (segs.empty() ? kept.type : cur.nal_type)) INVALID("the slice NAL units of a picture differ in their type");
+    st = cut_substreams(kept, sd);
+    if (st != HEVCDL_OK) return st;
+    segs.push_back(std::move(sd));
+  }
+  { const hevcdl_status st = close_picture(); if (st != HEVCDL_OK) return st; }
+  if (count == 0 || !have_grid) INVALID("no picture in the stream");
+
+  hevcdl_stream_config c;
+  hevcdl_stream_config_default(&c, active.width, active.height, 26);
+  c.qp = 0; c.level_idc = level_idc; c.sao_enabled = active.sao; c.loop_filter_disable = active.dbk_disabled;
+  c.tile_columns = active.tcols; c.tile_rows = active.trows; c.bit_depth = active.bit_depth; c.tile_uniform_spacing = active.uniform;
+  if (!active.uniform) { for (int i = 0; i < active.tcols - 1 && i < 19; i++) c.tile_column_width[i] = active.col_width[i]; for (int i = 0; i < active.trows - 1 && i < 21; i++) c.tile_row_height[i] = active.row_height[i]; }
+  c.lf_across_tiles = active.lf_across_tiles;
+  c.tools = (HEVCDL_TOOLS_REFERENCE & ~(uint32_t)(HEVCDL_TOOL_TSKIP | HEVCDL_TOOL_SIGN_HIDE | HEVCDL_TOOL_STRONG_INTRA)) | (active.tskip ? HEVCDL_TOOL_TSKIP : 0) |
+            (active.sign_hiding ? HEVCDL_TOOL_SIGN_HIDE : 0) | (active.strong_intra ? HEVCDL_TOOL_STRONG_INTRA : 0);
+  c.lf_beta_offset_div2 = active.beta_div2; c.lf_tc_offset_div2 = active.tc_div2;
+  c.rewrite_param_sets = (count == 1 || ps_before_second) ? 1 : 0;
+  c.wavefront = active.wpp;
+  c.conf_win_left = active.conf_left; c.conf_win_right = active.conf_right; c.conf_win_top = active.conf_top; c.conf_win_bottom = active.conf_bottom;
+  c.qp = first_qp;
+  out.cfg = c; out.slices = sl; out.segments = sg;
+  return HEVCDL_OK;
+}
+
+// the units of pictures [0, n) on the CPU, in the parser's order: the first error met is the lowest picture's first
+hevcdl_status walk_units_host(void *, const StreamUnits &su, int n, hevcdl_ctu_record *records, hevcdl_sao_blk *sao, int *bad_pic, SdResult *res)
+{
+  uint8_t ctx[EC_SYNC_BYTES], sync[EC_SYNC_BYTES], dry_depth[512], dry_dir[512]; uint16_t cg_pos[16]; int16_t cg_val[16];
+  SdState s; memset(&s, 0, sizeof s);
+  s.t = &ec_tables(); s.s = &su.sd; s.ctx = ctx; s.sync = sync; s.cg_pos = cg_pos; s.cg_val = cg_val; s.dry_depth = dry_depth; s.dry_dir = dry_dir;
+  *bad_pic = -1;
+  for (size_t i = 0; i < su.pic_unit[(size_t)n]; i++) {
+    SdUnit u = su.units[i];
+    u.rbsp0 = 0;
+    s.recs = records + (size_t)u.pic * su.ctus; s.sao = sao ? sao + (size_t)u.pic * su.ctus : nullptr;
+    const SdResult r = sd_decode_unit(s, u, su.subs.data(), (int)su.subs.size(), su.rbsp.data() + su.pic_byte[(size_t)u.pic], su.pic_byte[(size_t)u.pic + 1] - su.pic_byte[(size_t)u.pic]);
+    if (r.code != SD_OK) { *bad_pic = u.pic; *res = r; return HEVCDL_OK; }
+  }
+  return HEVCDL_OK;
+}
+} // namespace
+
+namespace hevcdl_parse {
+void set_slice_error(int pic, const SdResult &res)
+{
+  if (res.ctu >= 0) set_error("picture %d, CTU %d: %s", pic, res.ctu, sd_error_sentence(res.code));
+  else set_error("picture %d: %s", pic, sd_error_sentence(res.code));
+}
+
+hevcdl_status collect_units(const uint8_t *stream, size_t bytes, int want_slice_data, int have_sao, size_t ctu_capacity, StreamUnits &out)
+{
+  out.pic_byte.assign(1, 0); out.pic_sub.assign(1, 0); out.pic_unit.assign(1, 0);
+  const hevcdl_status st = collect_loop(stream, bytes, want_slice_data, have_sao, ctu_capacity, out);
+  if (st == HEVCDL_OK) return st;
+  // (a picture that was refused half way through its units leaves nothing behind)
+  out.rbsp.resize(out.pic_byte.back()); out.subs.resize(out.pic_sub.back()); out.units.resize(out.pic_unit.back());
+  if (!want_slice_data || out.pictures.empty()) return st;
+  out.pending = st; snprintf(out.pending_sentence, sizeof out.pending_sentence, "%s", g_error);
+  return HEVCDL_OK;
+}
+
+hevcdl_status batch_tables(const StreamUnits &su, int first, int count, std::vector<SdUnit> &units, size_t &sub0, size_t &n_subs, size_t &byte0, size_t &n_bytes)
+{
+  if (first < 0 || count < 1 || (size_t)first + (size_t)count > su.pictures.size()) INVALID("a batch outside the stream's pictures");
+  sub0 = su.pic_sub[(size_t)first]; n_subs = su.pic_sub[(size_t)first + count] - sub0;
+  byte0 = su.pic_byte[(size_t)first]; n_bytes = su.pic_byte[(size_t)first + count] - byte0;
+  if (n_bytes > 0xffffffffull) UNSUPPORTED("a batch of more than 4 GB of slice data: decode fewer pictures a batch");
+  units.assign(su.units.begin() + (ptrdiff_t)su.pic_unit[(size_t)first], su.units.begin() + (ptrdiff_t)su.pic_unit[(size_t)first + count]);
+  for (SdUnit &u : units) { u.rbsp0 = (uint32_t)(su.pic_byte[(size_t)u.pic] - byte0); u.sub0 -= (int)sub0; u.pic -= first; }
+  return HEVCDL_OK;
+}
+
+hevcdl_status parse_stream_with(UnitWalker walk, void *user, const uint8_t *stream, size_t bytes, hevcdl_stream_config *cfg, hevcdl_slice_layout *slices, hevcdl_segment_layout *segments,
+                                hevcdl_parsed_picture *pictures, int picture_capacity, int *n_pictures, hevcdl_ctu_record *records, hevcdl_sao_blk *sao, size_t ctu_capacity)
+{
+  set_error("%s", "");
+  if (n_pictures) *n_pictures = 0;
+  if (!stream || !cfg || !n_pictures || picture_capacity < 0) INVALID("null stream, configuration or picture count");
+  if (cfg->struct_size != sizeof *cfg) INVALID("hevcdl_stream_config.struct_size is not that of this library");
+  StreamUnits su;
+  hevcdl_status st = collect_units(stream, bytes, records != nullptr, sao != nullptr, ctu_capacity, su);
+  if (st != HEVCDL_OK) return st;
+  const int count = (int)su.pictures.size();
+  for (int i = 0; i < count && pictures && i < picture_capacity; i++) pictures[i] = su.pictures[(size_t)i];
+  if (records) {
+    int bad_pic = -1; SdResult res = { SD_OK, -1 };
+    st = walk(user, su, count, records, sao, &bad_pic, &res);
+    if (st != HEVCDL_OK) return st;
+    if (bad_pic >= 0) { set_slice_error(bad_pic, res); return HEVCDL_ERR_INVALID_ARG; }
+  }
+  if (su.pending != HEVCDL_OK) { set_error("%s", su.pending_sentence); return su.pending; }
+  *n_pictures = count;
+  *cfg = su.cfg;
+  if (slices) *slices = su.slices;
+  if (segments) *segments = su.segments;
+  if (pictures && count > picture_capacity) INVALID("room for %d pictures, the stream holds %d", picture_capacity, count);
+  return HEVCDL_OK;
+}
+} // namespace hevcdl_parse
+
+extern "C" hevcdl_status hevcdl_parse_stream_core(const uint8_t *stream, size_t bytes, hevcdl_stream_config *cfg, hevcdl_slice_layout *slices, hevcdl_segment_layout *segments,
+                                                 hevcdl_parsed_picture *pictures, int picture_capacity, int *n_pictures, hevcdl_ctu_record *records, hevcdl_sao_blk *sao,
+                                                 size_t ctu_capacity)
+{
+  return parse_stream_with(walk_units_host, nullptr, stream, bytes, cfg, slices, segments, pictures, picture_capacity, n_pictures, records, sao, ctu_capacity);
 }

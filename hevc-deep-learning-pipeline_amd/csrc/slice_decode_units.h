@@ -1,0 +1,61 @@
+// slice_decode_units.h -- what the host builds for the shared slice-data decoder (slice_decode_core.h) and who runs it: hevcdl_parse.cpp builds the tables with the
+// parser's own header code, hevcdl_parse_stream_core walks them on the CPU, slice_decode_kernel.hip and hevcdl_decode_stream (hevcdl_api.hip) on the device.
+#ifndef HEVCDL_SLICE_DECODE_UNITS_H
+#define HEVCDL_SLICE_DECODE_UNITS_H
+#include <stddef.h>
+#include <stdint.h>
+#include <vector>
+#include "hevcdl.h"
+#include "hevcdl_parse.h"
+#include "slice_decode_core.h"
+
+namespace hevcdl_parse {
+
+// The pictures of a stream with their headers parsed and their slice data cut into units.  A refusal of the headers does not end the collection with nothing: the
+// pictures in front of it stay, and the refusal waits in `pending` -- hevcdl_parse_stream decodes a picture before it reads the next one's headers, so an error in the
+// slice data of an earlier picture is the one it reports, and so do the walkers of these tables.
+struct StreamUnits {
+  hevcdl_stream_config cfg; hevcdl_slice_layout slices; hevcdl_segment_layout segments;      // as hevcdl_parse_stream gives them (cfg only without a pending refusal)
+  hevcdl_sd::SdStream sd;
+  int ctus = 0;
+  std::vector<hevcdl_parsed_picture> pictures;
+  std::vector<uint8_t> rbsp;                     // the slice data of every picture, emulation prevention removed, sub-stream behind sub-stream
+  std::vector<hevcdl_sd::SdSub> subs;            // offsets count from the first byte of their picture
+  std::vector<hevcdl_sd::SdUnit> units;          // pic: index into pictures; sub0: index into subs; rbsp0: 0 (a batch sets it when it is cut out: batch_tables)
+  std::vector<size_t> pic_byte, pic_sub, pic_unit;      // [pictures + 1]: where picture i's bytes, sub-streams and units start
+  hevcdl_status pending = HEVCDL_OK; char pending_sentence[256] = "";
+};
+// want_slice_data 0: headers only (no tables).  have_sao / ctu_capacity: the caller's room, checked per picture as hevcdl_parse_stream does.  Returns HEVCDL_OK also with a
+// pending refusal; anything else is a refusal in front of the first picture's end (the sentence is in hevcdl_parse_error()).
+hevcdl_status collect_units(const uint8_t *stream, size_t bytes, int want_slice_data, int have_sao, size_t ctu_capacity, StreamUnits &out);
+// the tables of pictures [first, first + count) as one launch takes them: units and sub-streams renumbered from 0, rbsp0 from the first byte of picture `first`
+hevcdl_status batch_tables(const StreamUnits &su, int first, int count, std::vector<hevcdl_sd::SdUnit> &units, size_t &sub0, size_t &n_subs, size_t &byte0, size_t &n_bytes);
+
+// Walks the units of pictures [0, n) into records / sao ([n][ctus]; sao may be null when no picture has SAO on).  HEVCDL_OK: *bad_pic < 0, or the lowest picture with an error and its
+// first error in *res; anything else: the walker itself failed (a HIP error; the sentence set).
+typedef hevcdl_status (*UnitWalker)(void *user, const StreamUnits &su, int n, hevcdl_ctu_record *records, hevcdl_sao_blk *sao, int *bad_pic, hevcdl_sd::SdResult *res);
+// hevcdl_parse_stream's contract with the slice data decoded by `walk`
+hevcdl_status parse_stream_with(UnitWalker walk, void *user, const uint8_t *stream, size_t bytes, hevcdl_stream_config *cfg, hevcdl_slice_layout *slices, hevcdl_segment_layout *segments,
+                                hevcdl_parsed_picture *pictures, int picture_capacity, int *n_pictures, hevcdl_ctu_record *records, hevcdl_sao_blk *sao, size_t ctu_capacity);
+// "picture 3, CTU 17: <sentence of the code>" into hevcdl_parse_error()
+void set_slice_error(int pic, const hevcdl_sd::SdResult &res);
+
+} // namespace hevcdl_parse
+
+// ---- the launch (slice_decode_kernel.hip) ------------------------------------------------------------------------------------------------------------------
+// One wave per unit.  All pointers are device memory: blob [blob_bytes] RBSP bytes of the batch, subs [n_subs], units [n_units] (batch_tables), tables an EcTables block,
+// records [n_pics][ctus] (16-byte aligned) and sao [n_pics][ctus] (may be null when no unit has SAO on) are written -- every CTU of every unit is cleared, then decoded --
+// and results [n_units] receives a code and a CTU per unit.
+struct hevcdl_slice_decode_params {
+  hevcdl_sd::SdStream sd;
+  const uint8_t *blob; unsigned long long blob_bytes;
+  const hevcdl_sd::SdSub *subs; const hevcdl_sd::SdUnit *units; int n_subs, n_units;
+  void *records; void *sao; int ctus, n_pics;
+  hevcdl_sd::SdResult *results;
+  const void *tables;
+};
+// launches nothing and returns 0 when the parameters do not fit each other (no units, a grid that is not `ctus` CTUs, null pointers); 1 behind a launch
+int hevcdl_launch_slice_decode(const hevcdl_slice_decode_params *p, void *stream);
+// the first unit with an error in results [n_units] of a batch -> its picture in the batch (units[].pic) and *res; -1: none
+int hevcdl_slice_decode_first_error(const std::vector<hevcdl_sd::SdUnit> &units, const hevcdl_sd::SdResult *results, hevcdl_sd::SdResult *res);
+#endif

@@ -833,6 +833,22 @@ hevcdl_status hevcdl_parse_stream(const uint8_t *stream, size_t bytes, hevcdl_st
                                   hevcdl_parsed_picture *pictures_opt, int picture_capacity, int *n_pictures, hevcdl_ctu_record *records_opt, hevcdl_sao_blk *sao_opt,
                                   size_t ctu_capacity);
 const char   *hevcdl_parse_error(void);
+/* The same contract with the slice data decoded by the shared decoder csrc/slice_decode_core.h -- one source for the host and for gfx950, the mirror image of
+ * csrc/entropy_coder.h -- instead of the parser's own.  Parameter sets, slice headers, SEI, emulation prevention and the sub-streams are read by the parser's code, so
+ * a refusal of the headers is the parser's, sentence included; the slice data of every picture is cut into units (a tile, a row slice, or a picture: the longest run of
+ * CTUs one decoder must walk serially) and a unit is decoded by one walker.  Arguments, outputs and statuses are hevcdl_parse_stream's; records and SAO blocks are the
+ * same bytes.  An error inside slice data is HEVCDL_ERR_INVALID_ARG with "picture P, CTU A: ..." in hevcdl_parse_error() -- the CTU the parser names.
+ * hevcdl_parse_stream_core: the units on the CPU; no GPU needed (TEST AND DIAGNOSTIC).  hevcdl_parse_stream_dev: the units by hevcdl_slice_decode_kernel
+ * (csrc/slice_decode_kernel.hip) on `device`, one wave a unit, the pictures of up to a GB of records a launch; records and SAO blocks are downloaded into the caller's
+ * buffers (TEST AND DIAGNOSTIC: the decoder's form is hevcdl_enable_device_parse below).  Nothing is launched for a stream the headers refuse.
+ * hevcdl_slice_decode_launches: launches of the kernel this process has made (TEST AND DIAGNOSTIC). */
+hevcdl_status hevcdl_parse_stream_core(const uint8_t *stream, size_t bytes, hevcdl_stream_config *cfg, hevcdl_slice_layout *slices_opt, hevcdl_segment_layout *segments_opt,
+                                       hevcdl_parsed_picture *pictures_opt, int picture_capacity, int *n_pictures, hevcdl_ctu_record *records_opt, hevcdl_sao_blk *sao_opt,
+                                       size_t ctu_capacity);
+hevcdl_status hevcdl_parse_stream_dev(int device, const uint8_t *stream, size_t bytes, hevcdl_stream_config *cfg, hevcdl_slice_layout *slices_opt,
+                                      hevcdl_segment_layout *segments_opt, hevcdl_parsed_picture *pictures_opt, int picture_capacity, int *n_pictures,
+                                      hevcdl_ctu_record *records_opt, hevcdl_sao_blk *sao_opt, size_t ctu_capacity);
+unsigned long long hevcdl_slice_decode_launches(void);
 /* Records a caller brings itself (n_frames pictures of cfg's size), checked as the parser's own are by construction: depths that form a quadtree with the forced splits
  * at the picture's edge, NxN only in 8x8 CUs, prediction modes in range and constant over their block, tr_idx a transform tree within TU 4 .. 32 and depth 3, no cbf
  * bit below the depth of the partition's transform unit, transform-skip flags 0 / 1.  HEVCDL_ERR_INVALID_ARG with a sentence in hevcdl_parse_error() otherwise.  NOT
@@ -868,10 +884,17 @@ unsigned long long hevcdl_recon_launches(void);
  * [picture_capacity]: what the headers said; hash_ok_opt [picture_capacity]: 1 the device's digest equals the SEI's, 0 it does not, -1 the picture has no SEI.
  * *n_pictures is set as soon as the headers are parsed, also when there is too little room (HEVCDL_ERR_INVALID_ARG).  The context must describe the stream
  * (HEVCDL_ERR_INVALID_ARG otherwise: size, depth, tiles, slices, loop-filter flags are compared).  A refusal of the parser comes back with its status and its sentence
- * in hevcdl_last_error(ctx).  The host holds the whole stream's records while it runs (15 120 bytes a CTU). */
+ * in hevcdl_last_error(ctx).  Parsed on the host, the host holds the whole stream's records while it runs (15 120 bytes a CTU); with hevcdl_enable_device_parse it
+ * holds the stream's bytes, its headers and the unit tables, whatever the picture count.
+ * hevcdl_enable_device_parse(ctx, 1): hevcdl_decode_stream reads only the headers on the host and cuts the sub-streams; per batch the RBSP bytes and the unit tables go
+ * up, hevcdl_slice_decode_kernel writes the records where the reconstruction reads them and the SAO blocks beside them, the error slots come back -- an error is
+ * HEVCDL_ERR_INVALID_ARG with picture, CTU and sentence in hevcdl_last_error(ctx), before any reconstruction of the batch is launched -- and of the kernel's output only
+ * the SAO blocks (420 bytes a CTU) are downloaded, for the merge resolution of hevcdl_sao_apply_frames_dev.  The buffers (RBSP bytes, tables, error slots, SAO blocks)
+ * are sized for cfg.max_frames pictures, grown when a batch needs more, and freed by (ctx, 0).  Off by default: without the call nothing changes. */
 hevcdl_status hevcdl_config_from_stream(const hevcdl_stream_config *stream_cfg, const hevcdl_slice_layout *slices_opt, int max_frames, int device, hevcdl_config *out);
 hevcdl_status hevcdl_decode_stream(hevcdl_ctx *ctx, const uint8_t *stream, size_t bytes, void *pictures_opt, int picture_capacity, int *n_pictures,
                                    hevcdl_parsed_picture *info_opt, int32_t *hash_ok_opt);
+hevcdl_status hevcdl_enable_device_parse(hevcdl_ctx *ctx, int on);
 
 /* kernel timing with HIP events recorded on the launch stream */
 hevcdl_status hevcdl_profile_enable(hevcdl_ctx *ctx, int enable);
