@@ -440,6 +440,19 @@ def load_library():
     lib.hevcdl_parse_stream_core.argtypes = lib.hevcdl_parse_stream.argtypes
     lib.hevcdl_parse_stream_dev.argtypes = [ci] + lib.hevcdl_parse_stream.argtypes
     lib.hevcdl_slice_decode_launches.argtypes = []
+    _qp_tail = [ctypes.POINTER(QpInfo), vp]
+    lib.hevcdl_parse_qp_tally.argtypes = [ctypes.POINTER(QpTally)]
+    lib.hevcdl_parse_qp_tally.restype = None
+    lib.hevcdl_enable_cu_qp.argtypes = [vp, ci]
+    for fn in (lib.hevcdl_recon_qp_launches, lib.hevcdl_deblock_qp_launches):
+        fn.argtypes, fn.restype = [], ctypes.c_uint64
+    lib.hevcdl_deblock_frames_map.argtypes = [vp, vp, ci, vp, vp, ctypes.POINTER(QpInfo), vp, vp]
+    lib.hevcdl_parse_stream_qp.argtypes = lib.hevcdl_parse_stream.argtypes[:2] + [ctypes.c_uint] + lib.hevcdl_parse_stream.argtypes[2:] + _qp_tail
+    lib.hevcdl_parse_stream_core_qp.argtypes = lib.hevcdl_parse_stream_qp.argtypes
+    lib.hevcdl_parse_stream_dev_qp.argtypes = [ci] + lib.hevcdl_parse_stream_qp.argtypes
+    lib.hevcdl_reconstruct_frames_qp.argtypes = [ci, ctypes.POINTER(StreamConfig), slp, ctypes.POINTER(QpInfo), vp, vp, ci, vp]
+    lib.hevcdl_reconstruct_frames_qp_dev.argtypes = [ci, ctypes.POINTER(StreamConfig), slp, ctypes.POINTER(QpInfo), vp, vp, ci, vp, vp]
+    lib.hevcdl_reconstruct_frames_qp_host.argtypes = [ctypes.POINTER(StreamConfig), slp, ctypes.POINTER(QpInfo), vp, vp, ci, vp]
     lib.hevcdl_slice_decode_launches.restype = ctypes.c_uint64
     lib.hevcdl_enable_device_parse.argtypes = [vp, ci]
     lib.hevcdl_parse_error.argtypes = []
@@ -483,15 +496,44 @@ EXPORTS = ["hevcdl_config_default", "hevcdl_create", "hevcdl_destroy", "hevcdl_l
            "hevcdl_parse_stream", "hevcdl_parse_error", "hevcdl_validate_records", "hevcdl_sao_apply_frames", "hevcdl_sao_apply_frames_dev",
            "hevcdl_reconstruct_frames", "hevcdl_reconstruct_frames_dev", "hevcdl_reconstruct_frames_host", "hevcdl_recon_launches",
            "hevcdl_config_from_stream", "hevcdl_decode_stream",
-           "hevcdl_parse_stream_core", "hevcdl_parse_stream_dev", "hevcdl_slice_decode_launches", "hevcdl_enable_device_parse"]
+           "hevcdl_parse_stream_core", "hevcdl_parse_stream_dev", "hevcdl_slice_decode_launches", "hevcdl_enable_device_parse",
+           "hevcdl_parse_stream_qp", "hevcdl_parse_stream_core_qp", "hevcdl_parse_stream_dev_qp", "hevcdl_parse_qp_tally", "hevcdl_enable_cu_qp", "hevcdl_deblock_frames_map", "hevcdl_recon_qp_launches", "hevcdl_deblock_qp_launches",
+           "hevcdl_reconstruct_frames_qp", "hevcdl_reconstruct_frames_qp_dev", "hevcdl_reconstruct_frames_qp_host"]
+
+ACCEPT_CU_QP = 1      # HEVCDL_ACCEPT_CU_QP
+
+
+QP_TALLY_FIELDS = ["groups_with_delta", "groups_without_delta", "deltas_positive", "deltas_negative", "deltas_zero", "max_abs_delta", "deltas_with_suffix",
+                   "suffixes_of_several_bins", "deltas_by_parent_chroma_cbf", "groups_left_from_prev", "groups_up_from_prev", "groups_opening_tile", "groups_opening_slice",
+                   "groups_opening_wpp_row", "coded_behind_uncoded_in_ctu"]
+
+
+class QpTally(ctypes.Structure):
+    """hevcdl_qp_tally: what the slice data of the last hevcdl_parse_stream_qp met."""
+    _fields_ = [(k, ctypes.c_uint32) for k in QP_TALLY_FIELDS]
+
+
+def parse_qp_tally():
+    """hevcdl_parse_qp_tally of the calling thread's last parse_stream(cu_qp=True, engine="host") -> {counter: value}."""
+    t = QpTally()
+    load_library().hevcdl_parse_qp_tally(ctypes.byref(t))
+    return {k: int(getattr(t, k)) for k in QP_TALLY_FIELDS}
+
+
+class QpInfo(ctypes.Structure):
+    """hevcdl_qp_info: the PPS fields a QP map goes with."""
+    _fields_ = [("cu_qp_delta_enabled", ctypes.c_int32), ("diff_cu_qp_delta_depth", ctypes.c_int32), ("cb_qp_offset", ctypes.c_int32), ("cr_qp_offset", ctypes.c_int32)]
 
 
 class ParsedStream:
     """What parse_stream gives back: cfg (StreamConfig), slices / segments (SliceLayout / SegmentLayout or None, as write_access_unit_from_slice_data takes them),
-    pictures (a list of ParsedPicture), records [pictures, ctus] (REC_DTYPE) and sao [pictures, ctus, 3] (SAO_DTYPE; zeros for a picture without SAO)."""
+    pictures (a list of ParsedPicture), records [pictures, ctus] (REC_DTYPE) and sao [pictures, ctus, 3] (SAO_DTYPE; zeros for a picture without SAO).
+    With parse_stream(cu_qp=True) also qp_map, int8 [pictures, ctus, 256]: QpY of every 4x4 partition in z-order (0 outside the picture), and qp_info (QpInfo: the PPS's
+    cu_qp_delta_enabled_flag, diff_cu_qp_delta_depth and chroma QP offsets); None otherwise."""
 
-    def __init__(self, cfg, slices, segments, pictures, records, sao):
+    def __init__(self, cfg, slices, segments, pictures, records, sao, qp_map=None, qp_info=None):
         self.cfg, self.slices, self.segments, self.pictures, self.records, self.sao = cfg, slices, segments, pictures, records, sao
+        self.qp_map, self.qp_info = qp_map, qp_info
 
     @property
     def qps(self):
@@ -503,14 +545,18 @@ class ParsedStream:
         return p.hash_method, bytes(p.digest[:3 * p.hash_plane_bytes])
 
 
-def parse_stream(stream, headers_only=False, engine="host", device=0):
+def parse_stream(stream, headers_only=False, engine="host", device=0, cu_qp=False):
     """hevcdl_parse_stream (host only, no GPU): an Annex-B stream of this library's writer, or of the reference encoder in the same configuration -> a ParsedStream.
     engine: who decodes the slice data -- "host" the parser's own decoder, "core" the shared decoder csrc/slice_decode_core.h on the CPU (hevcdl_parse_stream_core),
     "device" the same source in hevcdl_slice_decode_kernel on `device` (hevcdl_parse_stream_dev).  The headers are the parser's in all three.
+    cu_qp: accept cu_qp_delta_enabled_flag and PPS chroma QP offsets (the hevcdl_parse_stream*_qp entry points with HEVCDL_ACCEPT_CU_QP) and return the QP map and
+    the PPS fields with the rest; without it such a stream is refused as ever.
     HevcdlError carries the status (1: a damaged stream, 2: a feature outside the decoder) and the parser's sentence."""
     lib = load_library()
     if engine not in ("host", "core", "device"):
         raise ValueError("engine is \"host\", \"core\" or \"device\"")
+    if cu_qp:
+        return _parse_stream_qp(lib, stream, headers_only, engine, device)
     if engine == "core":
         parse = lib.hevcdl_parse_stream_core
     elif engine == "device":
@@ -536,14 +582,40 @@ def parse_stream(stream, headers_only=False, engine="host", device=0):
     return ParsedStream(cfg, sl if sl.mode else None, sg if sg.mode else None, list(pics), records, sao)
 
 
-def decode_stream(stream, device=0, batch=64, device_parse=False):
+def _parse_stream_qp(lib, stream, headers_only, engine, device):
+    fn = {"host": lib.hevcdl_parse_stream_qp, "core": lib.hevcdl_parse_stream_core_qp, "device": lambda *a: lib.hevcdl_parse_stream_dev_qp(int(device), *a)}[engine]
+    name = {"host": "hevcdl_parse_stream_qp: ", "core": "hevcdl_parse_stream_core_qp: ", "device": "hevcdl_parse_stream_dev_qp: "}[engine]
+    buf = np.frombuffer(bytes(stream), np.uint8)
+    cfg = StreamConfig()
+    cfg.struct_size = ctypes.sizeof(StreamConfig)
+    sl, sg, n, info = SliceLayout(), SegmentLayout(), ctypes.c_int(0), QpInfo()
+
+    def check(st, who):
+        if st != 0:
+            raise HevcdlError(st, who + lib.hevcdl_parse_error().decode())
+    check(lib.hevcdl_parse_stream_qp(buf.ctypes.data, buf.size, ACCEPT_CU_QP, ctypes.byref(cfg), ctypes.byref(sl), ctypes.byref(sg), None, 0, ctypes.byref(n), None, None, 0, ctypes.byref(info), None),
+          "hevcdl_parse_stream_qp: ")
+    ctus = ((cfg.width + 63) // 64) * ((cfg.height + 63) // 64)
+    pics = (ParsedPicture * n.value)()
+    records = None if headers_only else np.zeros((n.value, ctus), REC_DTYPE)
+    sao = None if headers_only else np.zeros((n.value, ctus, 3), SAO_DTYPE)
+    qp_map = None if headers_only else np.zeros((n.value, ctus, 256), np.int8)
+    check(fn(buf.ctypes.data, buf.size, ACCEPT_CU_QP, ctypes.byref(cfg), ctypes.byref(sl), ctypes.byref(sg), pics, n.value, ctypes.byref(n),
+             None if headers_only else records.ctypes.data, None if headers_only else sao.ctypes.data, 0 if headers_only else n.value * ctus, ctypes.byref(info),
+             None if headers_only else qp_map.ctypes.data), name)
+    return ParsedStream(cfg, sl if sl.mode else None, sg if sg.mode else None, list(pics), records, sao, qp_map, info)
+
+
+def decode_stream(stream, device=0, batch=64, device_parse=False, cu_qp=False):
     """hevcdl_decode_stream on a context made for the stream (hevcdl_config_from_stream): parsed on the host -- with device_parse the headers only, the slice data by
     hevcdl_slice_decode_kernel (hevcdl_enable_device_parse) --; reconstruction, deblocking, SAO and the digests on the
     device, `batch` pictures at a time in HBM.  -> (pictures [n, w * h * 3 / 2] in coded format, uint16 at 10 bits; the stream's StreamConfig, whose conf_win_* say what
     to show; the pictures' ParsedPicture list; verdicts [n]: True / False where the device's digest was compared with a hash SEI, None where the stream carries none).
+    cu_qp: hevcdl_enable_cu_qp on the context -- streams with cu_qp_delta_enabled_flag or PPS chroma QP offsets are decoded (the QP map in HBM beside the records, the QP-map
+    instantiations of the reconstruction and the deblocking kernel); off, they are refused as ever.
     HevcdlError carries the status and the decoder's sentence."""
     lib = load_library()
-    head = parse_stream(stream, headers_only=True)
+    head = parse_stream(stream, headers_only=True, cu_qp=cu_qp)
     n = len(head.pictures)
     cfg = Config()
     st = lib.hevcdl_config_from_stream(ctypes.byref(head.cfg), _layout_ptr(head.slices), max(1, min(int(batch), n)), int(device), ctypes.byref(cfg))
@@ -555,6 +627,10 @@ def decode_stream(stream, device=0, batch=64, device_parse=False):
     if st:
         raise HevcdlError(st, "hevcdl_create: " + (lib.hevcdl_create_error() or b"").decode())
     try:
+        if cu_qp:
+            st = lib.hevcdl_enable_cu_qp(h, 1)
+            if st:
+                raise HevcdlError(st, "hevcdl_enable_cu_qp: " + (lib.hevcdl_last_error(h) or b"").decode())
         if device_parse:
             st = lib.hevcdl_enable_device_parse(h, 1)
             if st:
@@ -570,15 +646,90 @@ def decode_stream(stream, device=0, batch=64, device_parse=False):
     return pictures, head.cfg, list(info), [None if v < 0 else bool(v) for v in ok]
 
 
-def reconstruct_frames(cfg, records, slices=None, qps=None, device=None):
+class StreamDecoder:
+    """A decoder context made for a stream (hevcdl_config_from_stream of its headers) that stays open over several hevcdl_decode_stream calls: the switches
+    (hevcdl_enable_cu_qp, hevcdl_enable_device_parse) can be turned between them.  `like`: a stream whose headers describe the streams to come."""
+
+    def __init__(self, like, device=0, batch=64):
+        self.lib = load_library()
+        head = parse_stream(like, headers_only=True, cu_qp=True)
+        self.head, self.h = head, ctypes.c_void_p()
+        cfg = Config()
+        st = self.lib.hevcdl_config_from_stream(ctypes.byref(head.cfg), _layout_ptr(head.slices), max(1, int(batch)), int(device), ctypes.byref(cfg))
+        if st:
+            raise HevcdlError(st, "hevcdl_config_from_stream")
+        w = np.zeros(WEIGHT_FLOATS, np.float32)
+        st = self.lib.hevcdl_create(ctypes.byref(cfg), w.ctypes.data, w.size, ctypes.byref(self.h))
+        if st:
+            raise HevcdlError(st, "hevcdl_create: " + (self.lib.hevcdl_create_error() or b"").decode())
+
+    def _check(self, st, who):
+        if st:
+            raise HevcdlError(st, who + ": " + (self.lib.hevcdl_last_error(self.h) or b"").decode())
+
+    def enable_cu_qp(self, on=True):
+        self._check(self.lib.hevcdl_enable_cu_qp(self.h, int(bool(on))), "hevcdl_enable_cu_qp")
+
+    def enable_device_parse(self, on=True):
+        self._check(self.lib.hevcdl_enable_device_parse(self.h, int(bool(on))), "hevcdl_enable_device_parse")
+
+    def decode(self, stream, n=None):
+        """-> (pictures [n, w * h * 3 / 2], the pictures' ParsedPicture list, verdicts) as decode_stream gives them; n: room in pictures (the stream's count when None)."""
+        c = self.head.cfg
+        buf = np.frombuffer(bytes(stream), np.uint8)
+        n = len(parse_stream(stream, headers_only=True, cu_qp=True).pictures) if n is None else int(n)
+        pictures = np.zeros((n, c.width * c.height * 3 // 2), np.uint8 if c.bit_depth == 8 else np.dtype("<u2"))
+        info, ok, count = (ParsedPicture * n)(), np.zeros(n, np.int32), ctypes.c_int(0)
+        self._check(self.lib.hevcdl_decode_stream(self.h, buf.ctypes.data, buf.size, pictures.ctypes.data, n, ctypes.byref(count), info, ok.ctypes.data), "hevcdl_decode_stream")
+        return pictures, list(info), [None if v < 0 else bool(v) for v in ok]
+
+    def deblock_map(self, recon, parsed):
+        """hevcdl_deblock_frames_map: unfiltered pictures [n, w * h * 3 / 2] + a parse_stream(cu_qp=True) result (records, QP map, PPS offsets, the pictures' deblocking
+        parameters) -> the deblocked pictures, by the QP-map instantiation of the deblocking kernel."""
+        r = np.ascontiguousarray(recon)
+        n = r.shape[0]
+        out = np.zeros_like(r)
+        ch = (DbkChoice * n)(*[p.dbk for p in parsed.pictures])
+        recs, m = np.ascontiguousarray(parsed.records), np.ascontiguousarray(parsed.qp_map)
+        self._check(self.lib.hevcdl_deblock_frames_map(self.h, r.ctypes.data, n, recs.ctypes.data, ch, ctypes.byref(parsed.qp_info), m.ctypes.data, out.ctypes.data), "hevcdl_deblock_frames_map")
+        return out
+
+    def close(self):
+        if self.h:
+            self.lib.hevcdl_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def reconstruct_frames(cfg, records, slices=None, qps=None, device=None, qp_map=None, qp_info=None):
     """The unfiltered reconstruction of records [pictures, ctus] under cfg (a StreamConfig: size, bit depth, QP, tiles, the strong-intra tool bit) and the slice layout:
     device None: csrc/recon_core.h on the CPU (hevcdl_reconstruct_frames_host, no GPU needed), otherwise hevcdl_recon_kernel on that device.  qps: a QP per picture.
+    qp_map [pictures, ctus, 256] int8 with qp_info (a QpInfo; parse_stream(cu_qp=True) gives both): a QP per CU and the PPS chroma offsets -- the
+    hevcdl_reconstruct_frames_qp* entry points, the QP-map instantiation of hevcdl_recon_kernel on a device.
     -> [pictures, w * h * 3 / 2] samples (uint8, or uint16 at 10 bits).  HevcdlError carries the status and the sentence."""
     lib = load_library()
     r = np.ascontiguousarray(records, REC_DTYPE)
     r = r.reshape(1, -1) if r.ndim == 1 else r
     n = r.shape[0]
     out = np.zeros((n, cfg.width * cfg.height * 3 // 2), np.uint8 if cfg.bit_depth == 8 else np.dtype("<u2"))
+    if qp_map is not None:
+        if qps is not None or qp_info is None:
+            raise ValueError("a QP map goes with qp_info and without qps")
+        m = np.ascontiguousarray(qp_map, np.int8)
+        if m.size != r.size * 256:
+            raise ValueError("the QP map holds %d values, the records need %d" % (m.size, r.size * 256))
+        if device is None:
+            st = lib.hevcdl_reconstruct_frames_qp_host(ctypes.byref(cfg), _layout_ptr(slices), ctypes.byref(qp_info), m.ctypes.data, r.ctypes.data, n, out.ctypes.data)
+        else:
+            st = lib.hevcdl_reconstruct_frames_qp(int(device), ctypes.byref(cfg), _layout_ptr(slices), ctypes.byref(qp_info), m.ctypes.data, r.ctypes.data, n, out.ctypes.data)
+        if st:
+            raise HevcdlError(st, "hevcdl_reconstruct_frames_qp: " + lib.hevcdl_parse_error().decode())
+        return out
     q = None if qps is None else np.ascontiguousarray(qps, np.int32).reshape(n)
     qp = None if q is None else q.ctypes.data
     if device is None:

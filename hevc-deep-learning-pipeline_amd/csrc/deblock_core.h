@@ -43,6 +43,30 @@ __device__ __forceinline__ bool edge_flag(const hevcdl_dbk_params &p, const unsi
   return pos > 0 && (pos & (tu - 1)) == 0;
 }
 
+// ---- a QP per edge (the QPMAP instantiations of hevcdl_deblock_fused_kernel) ----
+// Table 8-12 (tC, beta; the host's copy: dbk_select.h) in the code object: on the device once, with the module.  Every index is clamped where it is used.
+__device__ const unsigned char DBK_TC_DEV[54] = { 0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,1,1,1,1,1,1,1,1,1,2,2,2,2,3,3,3,3,4,4,4,5,5,6,6,7,8,9,10,11,13,14,16,18,20,22,24 };
+__device__ const unsigned char DBK_BETA_DEV[52] = { 0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,6,7,8,9,10,11,12,13,14,15,16,17,18,20,22,24,26,28,30,32,34,36,38,40,42,44,46,48,50,52,54,56,58,60,62,64 };
+__device__ __forceinline__ int dbk_tc_of(int idx) { return DBK_TC_DEV[clip3i(0, 53, idx)]; }
+__device__ __forceinline__ int dbk_beta_of(int idx) { return DBK_BETA_DEV[clip3i(0, 51, idx)]; }
+// QpY of the 4x4 partition at luma (x, y) of this frame's map (x, y inside the picture), clamped to what a stream can carry
+__device__ __forceinline__ int map_qp(const signed char GLB *map, int ctus_x, int x, int y)
+{
+  const int x4 = (x & 63) >> 2, y4 = (y & 63) >> 2;
+  int z = 0;
+#pragma unroll
+  for (int b = 0; b < 4; b++) z |= (((x4 >> b) & 1) << (2 * b)) | (((y4 >> b) & 1) << (2 * b + 1));
+  return clip3i(-48, 51, map[(size_t)((y >> 6) * ctus_x + (x >> 6)) * 256 + z]);
+}
+// (QpQ + QpP + 1) >> 1 of the edge at the left (dir 0) / top (dir 1) border of the partition at luma (x, y); x > 0 resp. y > 0 (an edge that edge_flag found)
+__device__ __forceinline__ int edge_qpl(const signed char GLB *map, int ctus_x, int x, int y, int dir)
+{
+  return (map_qp(map, ctus_x, x, y) + map_qp(map, ctus_x, dir ? x : x - 1, dir ? y - 1 : y) + 1) >> 1;
+}
+// QpC of a chroma edge: Table 8-10 (ChromaArrayType 1) of qPL + cQpPicOffset
+__device__ const unsigned char DBK_QPC_DEV[14] = { 29, 30, 31, 32, 33, 33, 34, 34, 35, 35, 36, 36, 37, 37 };      // qPi 30 .. 42
+__device__ __forceinline__ int chroma_qp_of(int qpi) { return qpi < 30 ? qpi : (qpi >= 43 ? qpi - 6 : (int)DBK_QPC_DEV[qpi - 30]); }
+
 // Luma decision + filter of one 4-line segment (xEdgeFilterLuma / xPelFilterLuma, TComLoopFilter.cpp:557-700, 830-920), two lines at a time in
 // packed 16-bit arithmetic (v_pk_*_i16): every intermediate fits 16 bits at 8 and at 10 bits (largest: 9 * 1023 + 3 * 1023 + 8).  Lines are
 // paired (0, 3) and (1, 2): the decisions are taken from lines 0 and 3, so one packed evaluation gives both; the per-line condition of the

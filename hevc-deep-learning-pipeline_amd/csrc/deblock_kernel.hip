@@ -34,7 +34,9 @@
 #ifndef DBK_WAVES
 #define DBK_WAVES 8
 #endif
-template <int CHROMA, typename PEL>
+// QPMAP == 1 (p.qp_map non-null): tc and beta are looked up per edge segment from the QpY of the two partitions it separates, the chroma tc per plane (hevcdl_dev.h).  The
+// flags' QPs are fetched where the flags are; everything else is the code of QPMAP == 0, which compiles to what it was.
+template <int CHROMA, typename PEL, int QPMAP = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DBK_WAVES, DBK_WAVES))) void hevcdl_deblock_fused_kernel(hevcdl_dbk_params p)
 {
   constexpr int TW = DBK_TW, TH = DBK_TH, DW = TW * (int)sizeof(PEL) / 4, QD = (int)sizeof(PEL);      // dwords per tile row; dwords per 4 samples
@@ -55,6 +57,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DBK_WAVES, 
   // the picture's own parameters, read once per workgroup (a scalar load: the address is uniform).  A disabled picture runs with (0, 0, 0): beta 0 stops every luma edge
   // at its first test and a chroma delta clipped to 0 changes nothing, so the picture passes through as it is
   int tc = p.tc, beta = p.beta, tc_c = p.tc_c;
+  [[maybe_unused]] int tc_off = 0, beta_off = 0; [[maybe_unused]] bool pic_off = false;
+  [[maybe_unused]] const signed char GLB *qmap = nullptr;
+  [[maybe_unused]] const int bd_scale = (p.pel_max + 1) >> 8;
+  [[maybe_unused]] int qv0 = 0, qv1 = 0, qh0 = 0, qh1 = 0;      // qPL of the edges behind v0, v1, h0, h1
+  if constexpr (QPMAP) {
+    const int GLB *fp = (const int GLB *)p.frame_params + 4 * frame;
+    tc_off = fp[0]; beta_off = fp[1]; pic_off = fp[3] != 0;
+    qmap = (const signed char GLB *)p.qp_map + (size_t)frame * p.ctus_per_frame * 256;
+  } else
   if (p.frame_params) { const int GLB *fp = (const int GLB *)p.frame_params + 4 * frame; const bool off = fp[3] != 0; tc = off ? 0 : fp[0]; beta = off ? 0 : fp[1]; tc_c = off ? 0 : fp[2]; }
   // stage 1 role: edge column x, rows y .. y + 3
   const int ex = tid % EXN, sy = tid / EXN;
@@ -82,6 +93,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DBK_WAVES, 
         }
         if constexpr (!CHROMA) {
           if (has_l && has_r) v0 = edge_flag(p, recs, p.ctus_x, x, y, 0);
+          if constexpr (QPMAP) { v0 = v0 && !pic_off; if (v0) { const int q = edge_qpl(qmap, p.ctus_x, x, y, 0); tc = dbk_tc_of(q + 2 + tc_off) * bd_scale; beta = dbk_beta_of(q + beta_off) * bd_scale; } }
           if (v0) {
             s2 a[8], b[8];
             rows_to_pairs(l[0], l[3], a, 0); rows_to_pairs(r[0], r[3], a, 4); rows_to_pairs(l[1], l[2], b, 0); rows_to_pairs(r[1], r[2], b, 4);
@@ -90,11 +102,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DBK_WAVES, 
           }
         } else {
           if (c == 0 && has_l && has_r) { v0 = edge_flag(p, recs, p.ctus_x, 2 * x, 2 * y, 0); v1 = edge_flag(p, recs, p.ctus_x, 2 * x, 2 * y + 4, 0); }
+          if constexpr (QPMAP) if (c == 0) { v0 = v0 && !pic_off; v1 = v1 && !pic_off; if (v0) qv0 = edge_qpl(qmap, p.ctus_x, 2 * x, 2 * y, 0); if (v1) qv1 = edge_qpl(qmap, p.ctus_x, 2 * x, 2 * y + 4, 0); }
 #pragma unroll
           for (int h = 0; h < 2; h++) if (h ? v1 : v0) { // rows (0, 1) under the first flag, (2, 3) under the second: p1 p0 = bytes 2, 3 of the left dwords, q0 q1 = bytes 0, 1 of the right ones
             uint32_t &la = l[2 * h], &lb = l[2 * h + 1], &ra = r[2 * h], &rb = r[2 * h + 1];
             const s2 p1 = perm_s2(lb, la, 0x0c060c02u), q1 = perm_s2(rb, ra, 0x0c050c01u);
             s2 p0 = perm_s2(lb, la, 0x0c070c03u), q0 = perm_s2(rb, ra, 0x0c040c00u);
+            if constexpr (QPMAP) tc_c = dbk_tc_of(chroma_qp_of((h ? qv1 : qv0) + (c ? p.cr_qp_offset : p.cb_qp_offset)) + 2 + tc_off) * bd_scale;
             filter_chroma_pairs(p1, p0, q0, q1, tc_c, p.pel_max);
             la = __builtin_amdgcn_perm(u32(p0), la, 0x04020100u); lb = __builtin_amdgcn_perm(u32(p0), lb, 0x06020100u);
             ra = __builtin_amdgcn_perm(u32(q0), ra, 0x03020104u); rb = __builtin_amdgcn_perm(u32(q0), rb, 0x03020106u);
@@ -120,11 +134,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DBK_WAVES, 
           if (CHROMA) { v0 = edge_flag(p, recs, p.ctus_x, 2 * x, 2 * y, 0); v1 = edge_flag(p, recs, p.ctus_x, 2 * x, 2 * y + 4, 0); }
           else v0 = edge_flag(p, recs, p.ctus_x, x, y, 0);
         }
+        if constexpr (QPMAP) {
+          v0 = v0 && !pic_off; v1 = v1 && !pic_off;
+          if (v0) qv0 = CHROMA ? edge_qpl(qmap, p.ctus_x, 2 * x, 2 * y, 0) : edge_qpl(qmap, p.ctus_x, x, y, 0);
+          if (v1) qv1 = edge_qpl(qmap, p.ctus_x, 2 * x, 2 * y + 4, 0);
+        }
       }
-      if (!CHROMA) { if (v0) filter_luma_pk(m, tc, beta, p.pel_max); }
-      else {
+      if (!CHROMA) {
+        if constexpr (QPMAP) { tc = dbk_tc_of(qv0 + 2 + tc_off) * bd_scale; beta = dbk_beta_of(qv0 + beta_off) * bd_scale; }
+        if (v0) filter_luma_pk(m, tc, beta, p.pel_max);
+      } else {
 #pragma unroll
-        for (int i = 0; i < 4; i++) if (i < 2 ? v0 : v1) filter_chroma(m[i][2], m[i][3], m[i][4], m[i][5], tc_c, p.pel_max);
+        for (int i = 0; i < 4; i++) if (i < 2 ? v0 : v1) {
+          if constexpr (QPMAP) tc_c = dbk_tc_of(chroma_qp_of((i < 2 ? qv0 : qv1) + (c ? p.cr_qp_offset : p.cb_qp_offset)) + 2 + tc_off) * bd_scale;
+          filter_chroma(m[i][2], m[i][3], m[i][4], m[i][5], tc_c, p.pel_max);
+        }
       }
 #pragma unroll
       for (int i = 0; i < 4; i++) {
@@ -141,6 +165,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DBK_WAVES, 
     if (c == 0 && cols_ok && has_u && has_d) { // (issued before the barrier: back by the time stage 2 needs it)
       if (CHROMA) { h0 = edge_flag(p, recs, p.ctus_x, 2 * xh, 2 * yh, 1); h1 = edge_flag(p, recs, p.ctus_x, 2 * xh + 4, 2 * yh, 1); }
       else h0 = edge_flag(p, recs, p.ctus_x, xh, yh, 1);
+      if constexpr (QPMAP) {
+        h0 = h0 && !pic_off; h1 = h1 && !pic_off;
+        if (h0) qh0 = CHROMA ? edge_qpl(qmap, p.ctus_x, 2 * xh, 2 * yh, 1) : edge_qpl(qmap, p.ctus_x, xh, yh, 1);
+        if (h1) qh1 = edge_qpl(qmap, p.ctus_x, 2 * xh + 4, 2 * yh, 1);
+      }
     }
     __syncthreads();
     if constexpr (RAW) {
@@ -150,6 +179,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DBK_WAVES, 
         for (int k = 0; k < 8; k++) w[k] = tile[8 * eb + k][xg];
         if constexpr (!CHROMA) {
           if (h0) {
+            if constexpr (QPMAP) { tc = dbk_tc_of(qh0 + 2 + tc_off) * bd_scale; beta = dbk_beta_of(qh0 + beta_off) * bd_scale; }
             s2 a[8], b[8];
 #pragma unroll
             for (int k = 0; k < 8; k++) { a[k] = perm_s2(w[k], w[k], 0x0c030c00u); b[k] = perm_s2(w[k], w[k], 0x0c020c01u); }
@@ -161,7 +191,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DBK_WAVES, 
           s2 a[4], b[4];
 #pragma unroll
           for (int k = 0; k < 4; k++) { a[k] = perm_s2(w[2 + k], w[2 + k], 0x0c010c00u); b[k] = perm_s2(w[2 + k], w[2 + k], 0x0c030c02u); }
+          [[maybe_unused]] const int coff = c ? p.cr_qp_offset : p.cb_qp_offset;
+          if constexpr (QPMAP) tc_c = dbk_tc_of(chroma_qp_of(qh0 + coff) + 2 + tc_off) * bd_scale;
           if (h0) filter_chroma_pairs(a[0], a[1], a[2], a[3], tc_c, p.pel_max);
+          if constexpr (QPMAP) tc_c = dbk_tc_of(chroma_qp_of(qh1 + coff) + 2 + tc_off) * bd_scale;
           if (h1) filter_chroma_pairs(b[0], b[1], b[2], b[3], tc_c, p.pel_max);
           w[3] = __builtin_amdgcn_perm(u32(b[1]), u32(a[1]), 0x06040200u); w[4] = __builtin_amdgcn_perm(u32(b[2]), u32(a[2]), 0x06040200u);
         }
@@ -177,16 +210,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DBK_WAVES, 
         if constexpr (sizeof(PEL) == 1) { const uint32_t w = row[0]; m[0][k] = w & 255; m[1][k] = (w >> 8) & 255; m[2][k] = (w >> 16) & 255; m[3][k] = w >> 24; }
         else { const uint32_t w0 = row[0], w1 = row[1]; m[0][k] = w0 & 0xffff; m[1][k] = w0 >> 16; m[2][k] = w1 & 0xffff; m[3][k] = w1 >> 16; }
       }
-      if (!CHROMA) { if (h0) filter_luma_pk(m, tc, beta, p.pel_max); }
-      else {
+      if (!CHROMA) {
+        if constexpr (QPMAP) { tc = dbk_tc_of(qh0 + 2 + tc_off) * bd_scale; beta = dbk_beta_of(qh0 + beta_off) * bd_scale; }
+        if (h0) filter_luma_pk(m, tc, beta, p.pel_max);
+      } else {
 #pragma unroll
-        for (int i = 0; i < 4; i++) if (i < 2 ? h0 : h1) filter_chroma(m[i][2], m[i][3], m[i][4], m[i][5], tc_c, p.pel_max);
+        for (int i = 0; i < 4; i++) if (i < 2 ? h0 : h1) {
+          if constexpr (QPMAP) tc_c = dbk_tc_of(chroma_qp_of((i < 2 ? qh0 : qh1) + (c ? p.cr_qp_offset : p.cb_qp_offset)) + 2 + tc_off) * bd_scale;
+          filter_chroma(m[i][2], m[i][3], m[i][4], m[i][5], tc_c, p.pel_max);
+        }
       }
 #pragma unroll
       for (int k = 0; k < 8; k++) if (k < 4 ? has_u : has_d) store4<PEL>(dst + (size_t)(yh - 4 + k) * W + xh, m[0][k], m[1][k], m[2][k], m[3][k]);
     }
   }
 }
+
+static unsigned long long g_dbk_qp_launches = 0;      // launches of the QPMAP instantiations (a luma and a chroma kernel count as one)
+extern "C" unsigned long long hevcdl_deblock_qp_launches(void) { return g_dbk_qp_launches; }
 
 extern "C" void hevcdl_launch_deblock(const hevcdl_dbk_params *pp, void *stream)
 {
@@ -195,6 +236,18 @@ extern "C" void hevcdl_launch_deblock(const hevcdl_dbk_params *pp, void *stream)
   const int W = p.width, H = p.height, cw = W >> 1, chh = H >> 1;
   auto grid = [&](int w, int h) { const int n = ((w + 4 + DBK_TW - 1) / DBK_TW) * ((h + 4 + DBK_TH - 1) / DBK_TH); return dim3((unsigned)(((n + 7) / 8) * 8), 1, p.n_frames); };
   const dim3 g0 = grid(W, H), g1 = grid(cw, chh);
+  if (p.qp_map) { // a QP per edge: needs the per-picture rows (offsets, disabled)
+    if (!p.frame_params) return;
+    g_dbk_qp_launches++;
+    if (p.pel_max == 255) {
+      hipLaunchKernelGGL((hevcdl_deblock_fused_kernel<0, uint8_t, 1>), g0, dim3(256), 0, s, p);
+      hipLaunchKernelGGL((hevcdl_deblock_fused_kernel<1, uint8_t, 1>), g1, dim3(256), 0, s, p);
+    } else {
+      hipLaunchKernelGGL((hevcdl_deblock_fused_kernel<0, uint16_t, 1>), g0, dim3(256), 0, s, p);
+      hipLaunchKernelGGL((hevcdl_deblock_fused_kernel<1, uint16_t, 1>), g1, dim3(256), 0, s, p);
+    }
+    return;
+  }
   if (p.pel_max == 255) {
     hipLaunchKernelGGL((hevcdl_deblock_fused_kernel<0, uint8_t>), g0, dim3(256), 0, s, p);
     hipLaunchKernelGGL((hevcdl_deblock_fused_kernel<1, uint8_t>), g1, dim3(256), 0, s, p);

@@ -96,6 +96,9 @@ struct Decoder { DevBuf<unsigned char> d_work; std::vector<uint32_t> keep; };   
 // slice data DECODED on the device (slice_decode_kernel.hip): everything below is allocated by hevcdl_enable_device_parse(ctx, 1), sized for cfg.max_frames pictures, and
 // freed by (ctx, 0); the three that hold a batch's bytes and tables are given back and allocated larger when a batch needs more.  A context that never turns the switch
 // on allocates and launches none of it
+// a QP per CU (hevcdl_enable_cu_qp): the map of a batch in HBM beside the records -- uploaded behind a host parse, written by the kernel with device parse --, allocated
+// by the first stream that needs it.  active / info: the batch in work, read by the deblocking launch (null outside hevcdl_decode_stream and hevcdl_deblock_frames_map)
+struct CuQp { bool on = false; DevBuf<signed char> d_map; const signed char *active = nullptr; hevcdl_qp_info info = { 0, 0, 0, 0 }; };
 struct DeviceParse {
   bool on = false;
   DevBuf<unsigned char> d_tables, d_rbsp, d_sao; DevBuf<hevcdl_sd::SdSub> d_subs; DevBuf<hevcdl_sd::SdUnit> d_units; DevBuf<hevcdl_sd::SdResult> d_results;
@@ -192,7 +195,7 @@ struct hevcdl_ctx {
   int col_bd[21] = { 0 }, row_bd[23] = { 0 };    // tile boundaries in CTUs
   DevBuf<float> d_weights, d_a3; size_t a3_ctus = 0;   // d_a3: conv3 outputs of one chunk of CTUs (32 KB per CTU): the hand-over from the conv kernel to the head kernel
   DevBuf<int> d_flag;                  // device-side error flag of the label check
-  Staging stage; SaoWorkspace sao; Decoder dec; DeviceParse dp; Quality q; Report rp; Entropy ec; Source src; Session ses; RdWorkspace rd; DbkSelect dbk; QpRd qprd; FrameQp fqp;
+  Staging stage; SaoWorkspace sao; Decoder dec; DeviceParse dp; CuQp cuqp; Quality q; Report rp; Entropy ec; Source src; Session ses; RdWorkspace rd; DbkSelect dbk; QpRd qprd; FrameQp fqp;
   int ec_capacity_per_ctu = 0;         // hevcdl_set_entropy_capacity (tests): 0 = the default; outlives the entropy switch
   bool profile = false;
   std::vector<Event> ev_cnn, ev_rd, ev_conv;       // start/stop pairs (ev_conv: the convolution kernel alone, one pair per chunk of CTUs)
@@ -1038,7 +1041,21 @@ extern "C" hevcdl_status hevcdl_deblock_frames_qp_dev(hevcdl_ctx *ctx, const voi
   p.pel_max = (1 << ctx->cfg.bit_depth) - 1;
   p.lf_across_tiles = ctx->cfg.lf_across_tiles != 0; p.tile_cols = ctx->cfg.tile_columns; p.tile_rows = ctx->cfg.tile_rows;
   memcpy(p.col_bd, ctx->col_bd, sizeof p.col_bd); memcpy(p.row_bd, ctx->row_bd, sizeof p.row_bd);
-  p.frame_params = nullptr;
+  p.frame_params = nullptr; p.qp_map = nullptr; p.cb_qp_offset = p.cr_qp_offset = 0;
+  if (ctx->cuqp.active) { // a QP per edge: the rows are (2 tc_offset_div2, 2 beta_offset_div2, -, disabled), the map and the PPS chroma offsets go with them
+    if (idx) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "a QP map does not go with candidate indices");
+    for (int i = 0; choices && i < n_frames; i++)
+      if (choices[i].beta_offset_div2 < -6 || choices[i].beta_offset_div2 > 6 || choices[i].tc_offset_div2 < -6 || choices[i].tc_offset_div2 > 6) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "a picture's deblocking offsets are out of range (-6 .. 6)");
+    TRY(lazy_alloc(ctx, ctx->dbk.d_frame_params, sizeof(int) * 4 * (size_t)ctx->cfg.max_frames, "per-picture deblocking parameters (cfg.max_frames)"));
+    std::vector<int> &h = ctx->dbk.h_frame_params;
+    h.assign((size_t)4 * n_frames, 0);
+    for (int i = 0; i < n_frames; i++) {
+      h[4 * i] = 2 * (choices ? choices[i].tc_offset_div2 : ctx->cfg.lf_tc_offset_div2); h[4 * i + 1] = 2 * (choices ? choices[i].beta_offset_div2 : ctx->cfg.lf_beta_offset_div2);
+      h[4 * i + 3] = choices && choices[i].disabled != 0;
+    }
+    HIPCHK(hipMemcpyAsync(ctx->dbk.d_frame_params, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice, (hipStream_t)stream));
+    p.frame_params = ctx->dbk.d_frame_params; p.qp_map = ctx->cuqp.active; p.cb_qp_offset = ctx->cuqp.info.cb_qp_offset; p.cr_qp_offset = ctx->cuqp.info.cr_qp_offset;
+  } else
   if (choices || idx || !ctx->fqp.list.empty()) { // a row of (tc, beta, tc_c, disabled) per picture, uploaded in front of the launch on its stream (the host copy lives in the context until the next call)
     for (int i = 0; choices && i < n_frames; i++)
       if (choices[i].beta_offset_div2 < -6 || choices[i].beta_offset_div2 > 6 || choices[i].tc_offset_div2 < -6 || choices[i].tc_offset_div2 > 6) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "a picture's deblocking offsets are out of range (-6 .. 6)");
@@ -1082,6 +1099,36 @@ extern "C" hevcdl_status hevcdl_deblock_frames_qp(hevcdl_ctx *ctx, const uint8_t
   TRY(hevcdl_deblock_frames_qp_dev(ctx, ctx->stage.d_recon, n_frames, ctx->stage.d_records, choices, idx, ctx->stage.d_yuv, nullptr));   // d_yuv: free staging plane set
   TRY(sync_or_fail(ctx, "deblock kernels"));
   HIPCHK(hipMemcpy(out, ctx->stage.d_yuv, ctx->frame_bytes * n_frames, hipMemcpyDeviceToHost));
+  return HEVCDL_OK;
+}
+
+// the filter with a QP per edge on host buffers (TEST AND DIAGNOSTIC: the decoder keeps the map in HBM): qp_map [n_frames][ctus][256]
+namespace { struct CuQpActive { hevcdl_ctx *c; ~CuQpActive() { c->cuqp.active = nullptr; } }; }
+static hevcdl_status ensure_qp_map(hevcdl_ctx *ctx) { return lazy_alloc(ctx, ctx->cuqp.d_map, (size_t)256 * ctx->ctus * (size_t)ctx->cfg.max_frames, "QP map (cfg.max_frames)"); }
+extern "C" hevcdl_status hevcdl_deblock_frames_map(hevcdl_ctx *ctx, const void *recon, int n_frames, const hevcdl_ctu_record *records, const hevcdl_dbk_choice *choices_opt,
+                                                  const hevcdl_qp_info *qp_info, const int8_t *qp_map, void *out)
+{
+  FRAMES_OR_RETURN(ctx, n_frames);
+  if (!recon || !records || !out || !qp_info || !qp_map) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "null pointer");
+  if (qp_info->cb_qp_offset < -12 || qp_info->cb_qp_offset > 12 || qp_info->cr_qp_offset < -12 || qp_info->cr_qp_offset > 12) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "chroma QP offsets out of range (-12 .. 12)");
+  TRY(ensure_staging(ctx));
+  TRY(ensure_qp_map(ctx));
+  HIPCHK(hipMemcpy(ctx->stage.d_recon, recon, ctx->frame_bytes * n_frames, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(ctx->stage.d_records, records, ctx->records_bytes(n_frames), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(ctx->cuqp.d_map, qp_map, (size_t)256 * ctx->ctus * (size_t)n_frames, hipMemcpyHostToDevice));
+  CuQpActive guard{ ctx };
+  ctx->cuqp.active = ctx->cuqp.d_map; ctx->cuqp.info = *qp_info;
+  TRY(hevcdl_deblock_frames_qp_dev(ctx, ctx->stage.d_recon, n_frames, ctx->stage.d_records, choices_opt, nullptr, ctx->stage.d_yuv, nullptr));
+  TRY(sync_or_fail(ctx, "deblock kernels"));
+  HIPCHK(hipMemcpy(out, ctx->stage.d_yuv, ctx->frame_bytes * n_frames, hipMemcpyDeviceToHost));
+  return HEVCDL_OK;
+}
+
+extern "C" hevcdl_status hevcdl_enable_cu_qp(hevcdl_ctx *ctx, int on)
+{
+  if (!ctx) return HEVCDL_ERR_INVALID_ARG;
+  if (!on && ctx->cuqp.on) { TRY(sync_or_fail(ctx, "hevcdl_enable_cu_qp")); ctx->cuqp = CuQp(); }
+  ctx->cuqp.on = on != 0;
   return HEVCDL_OK;
 }
 
@@ -1132,6 +1179,7 @@ extern "C" hevcdl_status hevcdl_dbk_trial_frames_dev(hevcdl_ctx *ctx, const void
   hevcdl_dbk_trial_params q;
   memset(&q, 0, sizeof q);
   hevcdl_dbk_params &p = q.d;
+  p.qp_map = nullptr; p.cb_qp_offset = p.cr_qp_offset = 0;
   p.in = (const uint8_t *)d_recon; p.records = (const unsigned char *)d_records;
   p.width = ctx->cfg.width; p.height = ctx->cfg.height; p.ctus_x = ctx->ctus_x; p.ctus_per_frame = ctx->ctus; p.n_frames = n_frames;
   p.pel_max = (1 << ctx->cfg.bit_depth) - 1;
@@ -1360,7 +1408,7 @@ extern "C" hevcdl_status hevcdl_enable_device_parse(hevcdl_ctx *ctx, int on)
 
 // pictures [first, first + cnt) of su: bytes and tables up, the kernel into stage.d_records and dp.d_sao, the error slots back -- an error is HEVCDL_ERR_INVALID_ARG with
 // picture, CTU and sentence -- and with want_sao the SAO blocks into dp.h_sao
-static hevcdl_status device_parse_batch(hevcdl_ctx *ctx, const hevcdl_parse::StreamUnits &su, int first, int cnt, bool want_sao)
+static hevcdl_status device_parse_batch(hevcdl_ctx *ctx, const hevcdl_parse::StreamUnits &su, int first, int cnt, bool want_sao, signed char *d_qp_map = nullptr)
 {
   DeviceParse &g = ctx->dp;
   size_t sub0, n_subs, byte0, n_bytes;
@@ -1383,7 +1431,7 @@ static hevcdl_status device_parse_batch(hevcdl_ctx *ctx, const hevcdl_parse::Str
   HIPCHK(hipMemcpy(g.d_units, g.h_units.data(), g.h_units.size() * sizeof(hevcdl_sd::SdUnit), hipMemcpyHostToDevice));
   hevcdl_slice_decode_params k;
   k.sd = su.sd; k.blob = g.d_rbsp; k.blob_bytes = n_bytes; k.subs = g.d_subs; k.units = g.d_units; k.n_subs = (int)n_subs; k.n_units = (int)g.h_units.size();
-  k.records = ctx->stage.d_records; k.sao = g.d_sao; k.ctus = ctx->ctus; k.n_pics = cnt; k.results = g.d_results; k.tables = g.d_tables;
+  k.records = ctx->stage.d_records; k.sao = g.d_sao; k.ctus = ctx->ctus; k.n_pics = cnt; k.results = g.d_results; k.tables = g.d_tables; k.qp_map = (int8_t *)d_qp_map;
   if (!hevcdl_launch_slice_decode(&k, nullptr)) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "device parse: the unit tables of a batch do not fit a launch");
   TRY(launch_status(ctx));
   g.h_results.resize(g.h_units.size());
@@ -1405,8 +1453,11 @@ extern "C" hevcdl_status hevcdl_decode_stream(hevcdl_ctx *ctx, const uint8_t *st
   hevcdl_stream_config sc; memset(&sc, 0, sizeof sc); sc.struct_size = sizeof sc;
   hevcdl_slice_layout sl = { 0, 0, 1 }; hevcdl_segment_layout sg = { 0, 0 };
   int n = 0;
-  hevcdl_status st = hevcdl_parse_stream(stream, bytes, &sc, &sl, &sg, nullptr, 0, &n, nullptr, nullptr, 0);
+  const unsigned accept = ctx->cuqp.on ? HEVCDL_ACCEPT_CU_QP : 0u;      // off: every stream is answered as ever
+  hevcdl_qp_info qi = { 0, 0, 0, 0 };
+  hevcdl_status st = hevcdl_parse_stream_qp(stream, bytes, accept, &sc, &sl, &sg, nullptr, 0, &n, nullptr, nullptr, 0, &qi, nullptr);
   if (st != HEVCDL_OK) return fail(ctx, st, hevcdl_parse_error());
+  const bool use_map = qi.cu_qp_delta_enabled || qi.cb_qp_offset || qi.cr_qp_offset;      // a stream without either takes the constant-QP launches, also when enabled
   *n_pictures = n;
   { // the context must describe the stream: size, depth and the grid the in-loop filters stop at (tiles, row slices) with its flag
     hevcdl_config want, grid; const char *why = "";
@@ -1422,11 +1473,11 @@ extern "C" hevcdl_status hevcdl_decode_stream(hevcdl_ctx *ctx, const uint8_t *st
   }
   if (ctx->cfg.delta_qp_rd || ctx->cfg.deblocking_metric) return fail(ctx, HEVCDL_ERR_UNSUPPORTED, "a context with delta_qp_rd or deblocking_metric does not decode");
   if (n > picture_capacity) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "the stream holds more pictures than there is room for (*n_pictures says how many)");
-  std::vector<hevcdl_parsed_picture> pics; std::vector<hevcdl_ctu_record> recs; std::vector<hevcdl_sao_blk> sao;
+  std::vector<hevcdl_parsed_picture> pics; std::vector<hevcdl_ctu_record> recs; std::vector<hevcdl_sao_blk> sao; std::vector<int8_t> qmap;
   hevcdl_parse::StreamUnits su;                      // device parse: the slice data of the stream, cut into units
   const bool dev_parse = ctx->dp.on;
   if (dev_parse) {
-    try { st = hevcdl_parse::collect_units(stream, bytes, 1, 1, (size_t)-1, su); } catch (...) { return fail(ctx, HEVCDL_ERR_OOM, "host memory for the stream's slice data"); }
+    try { st = hevcdl_parse::collect_units(stream, bytes, 1, 1, (size_t)-1, su, accept); } catch (...) { return fail(ctx, HEVCDL_ERR_OOM, "host memory for the stream's slice data"); }
     if (st != HEVCDL_OK) return fail(ctx, st, hevcdl_parse_error());
     if (su.ctus != ctx->ctus) return fail(ctx, HEVCDL_ERR_INVALID_ARG, "the context does not describe the stream");
     pics = su.pictures;
@@ -1435,8 +1486,8 @@ extern "C" hevcdl_status hevcdl_decode_stream(hevcdl_ctx *ctx, const uint8_t *st
       return fail(ctx, su.pending, su.pending_sentence);
     }
   } else {
-    try { pics.resize((size_t)n); recs.resize((size_t)n * ctx->ctus); sao.resize((size_t)n * ctx->ctus); } catch (...) { return fail(ctx, HEVCDL_ERR_OOM, "host memory for the stream's records"); }
-    st = hevcdl_parse_stream(stream, bytes, &sc, &sl, &sg, pics.data(), n, &n, recs.data(), sao.data(), recs.size());
+    try { pics.resize((size_t)n); recs.resize((size_t)n * ctx->ctus); sao.resize((size_t)n * ctx->ctus); if (use_map) qmap.resize((size_t)n * ctx->ctus * 256); } catch (...) { return fail(ctx, HEVCDL_ERR_OOM, "host memory for the stream's records"); }
+    st = hevcdl_parse_stream_qp(stream, bytes, accept, &sc, &sl, &sg, pics.data(), n, &n, recs.data(), sao.data(), recs.size(), nullptr, use_map ? qmap.data() : nullptr);
     if (st != HEVCDL_OK) return fail(ctx, st, hevcdl_parse_error());
   }
   TRY(ensure_staging(ctx));
@@ -1446,15 +1497,22 @@ extern "C" hevcdl_status hevcdl_decode_stream(hevcdl_ctx *ctx, const uint8_t *st
   TRY(lazy_alloc(ctx, ctx->dec.d_work, work, "reconstruction row counts (cfg.max_frames)"));
   HIPCHK(hipSetDevice(ctx->cfg.device));
   FrameQpGuard guard{ ctx };
+  CuQpActive map_guard{ ctx };
+  if (use_map) TRY(ensure_qp_map(ctx));
   std::vector<int> qps; std::vector<hevcdl_dbk_choice> choices; std::vector<hevcdl_picture_report_t> rep;
   for (int first = 0; first < n; first += ctx->cfg.max_frames) {
     const int cnt = std::min(ctx->cfg.max_frames, n - first);
     qps.resize((size_t)cnt); choices.resize((size_t)cnt); rep.resize((size_t)cnt);
     bool any_sao = false, own_qp = false;
     for (int i = 0; i < cnt; i++) { qps[i] = pics[first + i].qp; choices[i] = pics[first + i].dbk; any_sao |= pics[first + i].sao != 0; own_qp |= qps[i] != ctx->cfg.qp; }
-    if (dev_parse) TRY(device_parse_batch(ctx, su, first, cnt, any_sao));      // the records into stage.d_records, the SAO blocks into dp.h_sao; an error before anything else is launched
+    if (dev_parse) TRY(device_parse_batch(ctx, su, first, cnt, any_sao, use_map ? ctx->cuqp.d_map.p : nullptr));      // the records into stage.d_records, the SAO blocks into dp.h_sao; an error before anything else is launched
     else HIPCHK(hipMemcpyAsync(ctx->stage.d_records, recs.data() + (size_t)first * ctx->ctus, ctx->records_bytes((size_t)cnt), hipMemcpyHostToDevice, nullptr));
     const uint32_t *d_err = nullptr;
+    if (use_map) { // the map beside the records: uploaded behind a host parse, written there by the kernel with device parse; the two QP-map instantiations read it
+      if (!dev_parse) HIPCHK(hipMemcpyAsync(ctx->cuqp.d_map, qmap.data() + (size_t)first * ctx->ctus * 256, (size_t)cnt * ctx->ctus * 256, hipMemcpyHostToDevice, nullptr));
+      st = hevcdl_recon_enqueue_qp(&sc, &sl, &qi, ctx->cuqp.d_map, ctx->stage.d_records, cnt, ctx->stage.d_recon, ctx->dec.d_work, work, nullptr, ctx->dec.keep, &d_err);
+      ctx->cuqp.active = ctx->cuqp.d_map; ctx->cuqp.info = qi;
+    } else
     st = hevcdl_recon_enqueue(&sc, &sl, qps.data(), ctx->stage.d_records, cnt, ctx->stage.d_recon, ctx->dec.d_work, work, nullptr, ctx->dec.keep, &d_err);
     if (st != HEVCDL_OK) return fail(ctx, st, hevcdl_parse_error());
     if (own_qp) TRY(hevcdl_set_frame_qps(ctx, qps.data(), cnt)); else ctx->fqp.list.clear();

@@ -128,6 +128,12 @@ struct hevcdl_dbk_params {
   int pel_max;                     // (1 << bit depth) - 1; 255: planes of uint8, otherwise planes of uint16
   int lf_across_tiles, tile_cols, tile_rows, col_bd[21], row_bd[23];   // LFCrossTileBoundaryFlag 0: no edge on a tile border is filtered
   const int *frame_params;         // NULL, or [frame][4] in HBM: tc, beta, tc_c (scaled like the three above, which are then not read) and disabled (non-zero: the picture passes unfiltered)
+  // A QP per CU (hevcdl_parse_stream_qp).  qp_map NULL: everything above, the launches as ever.  Otherwise the QPMAP instantiations run: qp_map [frame][ctu][256] int8 in HBM,
+  // QpY per 4x4 partition in z-order; per 4-sample edge segment qPL = (QpQ + QpP + 1) >> 1, beta from Clip3(0, 51, qPL + beta offset), tC from Clip3(0, 53, qPL + 2 + tc offset),
+  // and per chroma plane QpC = Table 8-10 of qPL + cb_qp_offset / cr_qp_offset, tC from QpC + 2 + tc offset.  frame_params is then REQUIRED and its rows mean
+  // (2 tc_offset_div2, 2 beta_offset_div2, unused, disabled); tc / beta / tc_c above are not read.
+  const signed char *qp_map;
+  int cb_qp_offset, cr_qp_offset;
 };
 
 // DeblockingFilterMetric 1 (dbk_select_kernel.hip): the two sums of TEncGOP::applyDeblockingFilterMetric per picture

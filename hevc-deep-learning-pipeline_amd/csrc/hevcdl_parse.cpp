@@ -37,6 +37,8 @@ namespace {
 using namespace hevcdl_ec;
 using namespace hevcdl_parse;
 
+thread_local hevcdl_qp_tally g_tally;      // what the last hevcdl_parse_stream_qp of this thread met (hevcdl_parse_qp_tally)
+
 #define UNSUPPORTED(...) do { set_error(__VA_ARGS__); return HEVCDL_ERR_UNSUPPORTED; } while (0)
 #define INVALID(...) do { set_error(__VA_ARGS__); return HEVCDL_ERR_INVALID_ARG; } while (0)
 
@@ -155,7 +157,7 @@ hevcdl_status parse_sps(const Nal &n, ParamSets &ps)
   return HEVCDL_OK;
 }
 
-hevcdl_status parse_pps(const Nal &n, ParamSets &ps)
+hevcdl_status parse_pps(const Nal &n, ParamSets &ps, unsigned accept)
 {
   BitIn r(n.rbsp.data(), n.rbsp.size());
   r.ue(); r.ue();
@@ -165,9 +167,17 @@ hevcdl_status parse_pps(const Nal &n, ParamSets &ps)
   if (r.bad || ps.init_qp < 0 || ps.init_qp > 51) INVALID("init_qp_minus26 of the PPS");
   if (r.u(1)) UNSUPPORTED("constrained intra prediction is outside this decoder");
   ps.tskip = (int)r.u(1);
-  if (r.u(1)) UNSUPPORTED("cu_qp_delta_enabled_flag is outside this decoder");
+  ps.cu_qp_delta = (int)r.u(1); ps.diff_cu_qp_depth = 0;
+  if (ps.cu_qp_delta && !(accept & HEVCDL_ACCEPT_CU_QP)) UNSUPPORTED("cu_qp_delta_enabled_flag is outside this decoder");
+  if (ps.cu_qp_delta) {
+    const uint32_t d = r.ue();
+    if (r.bad || d > 3) INVALID("diff_cu_qp_delta_depth %u", d);
+    ps.diff_cu_qp_depth = (int)d;
+  }
   const int cb = r.se(), cr = r.se();
-  if (cb != 0 || cr != 0) UNSUPPORTED("chroma QP offsets are outside this decoder");
+  if ((cb != 0 || cr != 0) && !(accept & HEVCDL_ACCEPT_CU_QP)) UNSUPPORTED("chroma QP offsets are outside this decoder");
+  if (cb < -12 || cb > 12 || cr < -12 || cr > 12) INVALID("chroma QP offsets %d / %d in the PPS", cb, cr);
+  ps.cb_qp_offset = cb; ps.cr_qp_offset = cr;
   if (r.u(1)) UNSUPPORTED("slice-level chroma QP offsets are outside this decoder");
   r.u(1); r.u(1);                                    // weighted prediction: nothing in an I slice
   if (r.u(1)) UNSUPPORTED("transquant bypass is outside this decoder");
@@ -314,7 +324,7 @@ struct Engine {
   }
   int bin(uint8_t *ctx, int c)
   {
-    if ((unsigned)c >= (unsigned)NUM_CTX) { bad = 1; return 0; }
+    if ((unsigned)c >= (unsigned)hevcdl_sd::SD_NUM_CTX) { bad = 1; return 0; }
     const uint32_t cv = ctx[c] & 127u, st = cv >> 1; int v = (int)(cv & 1);
     const uint32_t lps = t->lps[st][(range >> 6) & 3];
     range -= lps;
@@ -350,7 +360,69 @@ struct Picture {
   std::vector<int> slice_addr;                       // SliceAddrRs of every CTU decoded so far, -1: not yet
   Engine e; uint8_t ctx[EC_SYNC_BYTES], sync[EC_SYNC_BYTES];
   const char *why;                                   // the first syntax error
-  Picture(const ParamSets &p, const Grid &grid) : ps(p), g(grid), t(&ec_tables()), recs(nullptr), sao(nullptr), why(nullptr) { e.t = t; }
+  // 8.6.1 (only with ps.cu_qp_delta, or with a map to fill): QpY per 4x4 partition of the picture [g.n][256] (null: none wanted) and of the CTU in work; qPY_PREV, qPY_PRED,
+  // IsCuQpDeltaCoded and CuQpDeltaVal of the quantisation group in work
+  int8_t *qp_map; int8_t qp_cur[256]; int qp_prev, qp_pred, dqp_coded, dqp_val;
+  // the tally's view of the group in work: has a CU, where its prediction came from, what opened behind a reset of qPY_PREV (1 slice, 2 tile, 3 wavefront row), and the
+  // CTU of the last group that closed without a delta (-1: the last one had one, or none closed yet)
+  int grp_cu = 0, grp_prev_left = 0, grp_prev_up = 0, grp_reset = 0, grp_ctu = -1, none_ctu = -1;
+  void close_group()
+  {
+    if (!grp_cu) return;
+    if (dqp_coded) { g_tally.groups_with_delta++; if (none_ctu == grp_ctu) g_tally.coded_behind_uncoded_in_ctu++; none_ctu = -1; }
+    else { g_tally.groups_without_delta++; none_ctu = grp_ctu; }
+    grp_cu = 0;
+  }
+  Picture(const ParamSets &p, const Grid &grid) : ps(p), g(grid), t(&ec_tables()), recs(nullptr), sao(nullptr), why(nullptr), qp_map(nullptr), qp_prev(0), qp_pred(0), dqp_coded(0), dqp_val(0) { e.t = t; memset(qp_cur, 0, sizeof qp_cur); }
+
+  void init_contexts()
+  { // the coder's, and behind them the two of cu_qp_delta_abs (initValue 154, Table 9-24: state 0 with MPS 1 at every QP)
+    ec_init_contexts(ctx, t, qp);
+    const int v = hevcdl_sd::SD_DQP_INIT, slope = (v >> 4) * 5 - 45, offset = ((v & 15) << 3) - 16;
+    const int st = std::min(std::max(((slope * qp) >> 4) + offset, 1), 126), mps = st >= 64;
+    ctx[hevcdl_sd::SD_CTX_DQP] = ctx[hevcdl_sd::SD_CTX_DQP + 1] = (uint8_t)(((mps ? st - 64 : 63 - st) << 1) + mps);
+  }
+  // a quantisation group opens at the quadtree node (x0, y0)
+  void start_qg(int x0, int y0)
+  {
+    close_group();
+    dqp_coded = 0; dqp_val = 0;
+    grp_prev_left = !(x0 & 63); grp_prev_up = !(y0 & 63);
+    const int a = (x0 & 63) ? qp_cur[z_of(x0 - 1, y0)] : qp_prev, b = (y0 & 63) ? qp_cur[z_of(x0, y0 - 1)] : qp_prev;
+    qp_pred = (a + b + 1) >> 1;
+  }
+  void cu_qp_delta(int in_4x4_without_luma)
+  { // cu_qp_delta_abs: TU prefix (cMax 5), EG0 suffix; cu_qp_delta_sign_flag
+    int v = 0;
+    while (v < 5 && e.bin(ctx, hevcdl_sd::SD_CTX_DQP + (v ? 1 : 0))) v++;
+    if (v == 5) {
+      int k = 0;
+      while (k < 32 && e.ep()) k++;
+      if (k >= 8) { fail("CuQpDeltaVal outside its range"); return; }
+      v += (1 << k) - 1 + (int)e.eps(k);
+      g_tally.deltas_with_suffix++; if (k > 0) g_tally.suffixes_of_several_bins++;
+    }
+    if (v && e.ep()) v = -v;
+    if (v > 0) g_tally.deltas_positive++; else if (v < 0) g_tally.deltas_negative++; else g_tally.deltas_zero++;
+    if ((uint32_t)(v < 0 ? -v : v) > g_tally.max_abs_delta) g_tally.max_abs_delta = (uint32_t)(v < 0 ? -v : v);
+    if (in_4x4_without_luma) g_tally.deltas_by_parent_chroma_cbf++;
+    const int half = 3 * (ps.bit_depth - 8);
+    if (v < -(26 + half) || v > 25 + half) { fail("CuQpDeltaVal outside its range"); return; }
+    dqp_coded = 1; dqp_val = v;
+  }
+  void finish_cu_qp(int rs, int z, int nparts)
+  {
+    int q = qp;
+    if (ps.cu_qp_delta && !grp_cu) {
+      grp_cu = 1; grp_ctu = rs;
+      if (grp_prev_left) g_tally.groups_left_from_prev++;
+      if (grp_prev_up) g_tally.groups_up_from_prev++;
+      if (grp_reset == 1) g_tally.groups_opening_slice++; else if (grp_reset == 2) g_tally.groups_opening_tile++; else if (grp_reset == 3) g_tally.groups_opening_wpp_row++;
+      grp_reset = 0;
+    }
+    if (ps.cu_qp_delta) { const int off = 6 * (ps.bit_depth - 8); q = ((qp_pred + dqp_val + 52 + 2 * off) % (52 + off)) - off; qp_prev = q; }
+    for (int i = 0; i < nparts; i++) { qp_cur[(z + i) & 255] = (int8_t)q; if (qp_map) qp_map[(size_t)rs * 256 + ((z + i) & 255)] = (int8_t)q; }
+  }
 
   void fail(const char *s) { if (!why) why = s; }
   int z_of(int x, int y) const { return t->r2z[(((y >> 2) & 15) << 4) | ((x >> 2) & 15)]; }
@@ -508,6 +580,7 @@ struct Picture {
       return;
     }
     const int cbf_y = e.bin(ctx, CTX_QT_CBF + (trd == 0 ? 1 : 0));
+    if (ps.cu_qp_delta && !dqp_coded && (cbf_y || cbf_c[1] || cbf_c[2])) { cu_qp_delta(log2 == 2 && !cbf_y); if (why) return; }      // (a 4x4 luma block: cbf_c[] are its parent's)
     for (int i = 0; i < np; i++) r.tr_idx[(z + i) & 255] = (uint8_t)trd;
     if (cbf_y) {
       for (int d = 0; d <= trd; d++) {
@@ -567,6 +640,7 @@ struct Picture {
     }
     for (int i = 0; i < cu.nparts; i++) r.chroma_dir[cu.z + i] = (uint8_t)rec_c;
     transform_tree(cu, 0, log2, 0, 0, 0, 0);
+    if ((ps.cu_qp_delta || qp_map) && !why) finish_cu_qp(rs, cu.z, cu.nparts);
   }
 
   // coding_quadtree() 7.3.8.4
@@ -574,6 +648,7 @@ struct Picture {
   {
     if (e.bad || why) return;
     const int size = 1 << log2;
+    if (ps.cu_qp_delta && log2 >= 6 - ps.diff_cu_qp_depth) start_qg(x0, y0);
     int split;
     if (x0 + size <= W && y0 + size <= H && log2 > 3) {
       int inc = 0;
@@ -618,20 +693,21 @@ hevcdl_status decode_picture_data(Picture &p, const std::vector<SegmentData> &se
         p.e.start(segs[si].subs[k].first, segs[si].subs[k].second);
         if (p.e.bad) INVALID("a sub-stream too short for the arithmetic decoder, or one that starts with an offset of 510 / 511");
       }
-      if (new_tile) ec_init_contexts(p.ctx, p.t, p.qp);
+      if (new_tile) p.init_contexts();
       else if (new_row) {
-        if (have_sync && p.available(rs, (rx + 1) << 6, (ry - 1) << 6)) memcpy(p.ctx, p.sync, NUM_CTX);
-        else ec_init_contexts(p.ctx, p.t, p.qp);
+        if (have_sync && p.available(rs, (rx + 1) << 6, (ry - 1) << 6)) memcpy(p.ctx, p.sync, hevcdl_sd::SD_NUM_CTX);
+        else p.init_contexts();
       } else if (ts == first_ts) {
         if (h.dependent) UNSUPPORTED("a dependent slice segment that starts inside a CTU row or a tile is outside this decoder");
-        ec_init_contexts(p.ctx, p.t, p.qp);
+        p.init_contexts();
       }
+      if (new_tile || new_row || (ts == first_ts && !h.dependent)) { p.qp_prev = p.qp; p.grp_reset = (ts == first_ts && !h.dependent && ts != 0 && !new_tile) ? 1 : (new_tile ? 2 : 3); }      // 8.6.1: the first quantisation group of a slice, a tile, a wavefront row
       if (p.sao_on) p.sao_syntax(rs);
       p.coding_quadtree(rs, rx << 6, ry << 6, 6, 0);
       if (p.why) INVALID("CTU %d: %s", rs, p.why);
       const int end = p.e.terminate();
       if (p.e.bad) INVALID("CTU %d: the slice data ends inside the CTU", rs);
-      if (p.ps.wpp && rx == 1) { memcpy(p.sync, p.ctx, NUM_CTX); have_sync = 1; }
+      if (p.ps.wpp && rx == 1) { memcpy(p.sync, p.ctx, hevcdl_sd::SD_NUM_CTX); have_sync = 1; }
       ts++;
       if (end) {
         if (!p.e.finish()) INVALID("rbsp_slice_segment_trailing_bits() behind CTU %d are damaged, or bytes follow them", rs);
@@ -729,10 +805,17 @@ hevcdl_status check_layouts(const ParamSets &ps, const Grid &g, const std::vecto
 
 extern "C" const char *hevcdl_parse_error(void) { return hevcdl_parse::g_error; }
 
-extern "C" hevcdl_status hevcdl_parse_stream(const uint8_t *stream, size_t bytes, hevcdl_stream_config *cfg, hevcdl_slice_layout *slices, hevcdl_segment_layout *segments,
-                                            hevcdl_parsed_picture *pictures, int picture_capacity, int *n_pictures, hevcdl_ctu_record *records, hevcdl_sao_blk *sao,
-                                            size_t ctu_capacity)
+static void fill_qp_info(const ParamSets &ps, hevcdl_qp_info *q)
 {
+  if (!q) return;
+  q->cu_qp_delta_enabled = ps.cu_qp_delta; q->diff_cu_qp_delta_depth = ps.diff_cu_qp_depth; q->cb_qp_offset = ps.cb_qp_offset; q->cr_qp_offset = ps.cr_qp_offset;
+}
+
+extern "C" hevcdl_status hevcdl_parse_stream_qp(const uint8_t *stream, size_t bytes, unsigned accept, hevcdl_stream_config *cfg, hevcdl_slice_layout *slices, hevcdl_segment_layout *segments,
+                                               hevcdl_parsed_picture *pictures, int picture_capacity, int *n_pictures, hevcdl_ctu_record *records, hevcdl_sao_blk *sao,
+                                               size_t ctu_capacity, hevcdl_qp_info *qp_info, int8_t *qp_map)
+{
+  memset(&g_tally, 0, sizeof g_tally);
   set_error("%s", "");
   if (n_pictures) *n_pictures = 0;
   if (!stream || !cfg || !n_pictures || picture_capacity < 0) INVALID("null stream, configuration or picture count");
@@ -766,8 +849,10 @@ extern "C" hevcdl_status hevcdl_parse_stream(const uint8_t *stream, size_t bytes
       memset(p.recs, 0, sizeof(hevcdl_ctu_record) * (size_t)g.n);
       if (p.sao) memset(p.sao, 0, sizeof(hevcdl_sao_blk) * (size_t)g.n);
       p.W = active.width; p.H = active.height; p.qp = cur.qp; p.sao_on = cur.sao; p.max_sao = (1 << (std::min(active.bit_depth, 10) - 5)) - 1;
+      if (qp_map) { p.qp_map = qp_map + (size_t)count * g.n * 256; memset(p.qp_map, 0, (size_t)g.n * 256); }
       if (cur.sao && !p.sao) INVALID("the stream carries SAO parameters and there is no room for them");
       st = decode_picture_data(p, segs);
+      p.close_group();
       if (st != HEVCDL_OK) return st;
     }
     if (pictures && count < picture_capacity) pictures[count] = cur;
@@ -785,7 +870,7 @@ extern "C" hevcdl_status hevcdl_parse_stream(const uint8_t *stream, size_t bytes
     if (nal.type == 32) { st = close_picture(); if (st != HEVCDL_OK) return st; continue; }      // VPS: nothing a picture depends on
     if (nal.type == 33 || nal.type == 34) {
       st = close_picture(); if (st != HEVCDL_OK) return st;
-      st = nal.type == 33 ? parse_sps(nal, ps) : parse_pps(nal, ps);
+      st = nal.type == 33 ? parse_sps(nal, ps) : parse_pps(nal, ps, accept);
       if (st != HEVCDL_OK) return st;
       if (nal.type == 33) level_idc = ps.level_idc;
       if (count == 1) ps_before_second = 1;
@@ -845,10 +930,20 @@ extern "C" hevcdl_status hevcdl_parse_stream(const uint8_t *stream, size_t bytes
   c.conf_win_left = active.conf_left; c.conf_win_right = active.conf_right; c.conf_win_top = active.conf_top; c.conf_win_bottom = active.conf_bottom;
   c.qp = first_qp;                                   // the first picture's: a stream of one QP is then described by the configuration alone
   *cfg = c;
+  fill_qp_info(active, qp_info);
   if (slices) *slices = sl;
   if (segments) *segments = sg;
   if (pictures && count > picture_capacity) INVALID("room for %d pictures, the stream holds %d", picture_capacity, count);
   return HEVCDL_OK;
+}
+
+extern "C" void hevcdl_parse_qp_tally(hevcdl_qp_tally *out) { if (out) *out = g_tally; }
+
+extern "C" hevcdl_status hevcdl_parse_stream(const uint8_t *stream, size_t bytes, hevcdl_stream_config *cfg, hevcdl_slice_layout *slices, hevcdl_segment_layout *segments,
+                                            hevcdl_parsed_picture *pictures, int picture_capacity, int *n_pictures, hevcdl_ctu_record *records, hevcdl_sao_blk *sao,
+                                            size_t ctu_capacity)
+{
+  return hevcdl_parse_stream_qp(stream, bytes, 0, cfg, slices, segments, pictures, picture_capacity, n_pictures, records, sao, ctu_capacity, nullptr, nullptr);
 }
 
 // ---- records a caller brings itself ----------------------------------------------------------------------------------------------
@@ -966,7 +1061,7 @@ hevcdl_status picture_units(const ParamSets &ps, const Grid &g, const hevcdl_sli
 }
 
 // hevcdl_parse_stream's loop over the NAL units, its checks in its order; a picture that closes is cut into units where the parser decodes it
-hevcdl_status collect_loop(const uint8_t *stream, size_t bytes, int want_slice_data, int have_sao, size_t ctu_capacity, StreamUnits &out)
+hevcdl_status collect_loop(const uint8_t *stream, size_t bytes, int want_slice_data, int have_sao, size_t ctu_capacity, StreamUnits &out, unsigned accept)
 {
   std::vector<std::pair<size_t, size_t>> units;
   split_annexb(stream, bytes, units);
@@ -995,6 +1090,7 @@ hevcdl_status collect_loop(const uint8_t *stream, size_t bytes, int want_slice_d
         SdStream &d = out.sd;
         d.W = active.width; d.H = active.height; d.ctus_x = g.cx; d.ctus_y = g.cy; d.wpp = active.wpp; d.tskip = active.tskip; d.sign_hiding = active.sign_hiding;
         d.max_sao = (1 << (std::min(active.bit_depth, 10) - 5)) - 1; d.row_slices = sl.mode == 1;
+        d.cu_qp = active.cu_qp_delta; d.log2_qg = 6 - active.diff_cu_qp_depth; d.qp_bd_offset = 6 * (active.bit_depth - 8);
       }
       for (const SegmentData &s : segs) if (s.subs.empty()) INVALID("a slice segment without data");
       st = picture_units(active, g, sl, segs, cur, out);
@@ -1014,7 +1110,7 @@ hevcdl_status collect_loop(const uint8_t *stream, size_t bytes, int want_slice_d
     if (nal.type == 32) { st = close_picture(); if (st != HEVCDL_OK) return st; continue; }
     if (nal.type == 33 || nal.type == 34) {
       st = close_picture(); if (st != HEVCDL_OK) return st;
-      st = nal.type == 33 ? parse_sps(nal, ps) : parse_pps(nal, ps);
+      st = nal.type == 33 ? parse_sps(nal, ps) : parse_pps(nal, ps, accept);
       if (st != HEVCDL_OK) return st;
       if (nal.type == 33) level_idc = ps.level_idc;
       if (count == 1) ps_before_second = 1;
@@ -1072,21 +1168,21 @@ hevcdl_status collect_loop(const uint8_t *stream, size_t bytes, int want_slice_d
   c.wavefront = active.wpp;
   c.conf_win_left = active.conf_left; c.conf_win_right = active.conf_right; c.conf_win_top = active.conf_top; c.conf_win_bottom = active.conf_bottom;
   c.qp = first_qp;
-  out.cfg = c; out.slices = sl; out.segments = sg;
+  out.cfg = c; out.slices = sl; out.segments = sg; fill_qp_info(active, &out.qp);
   return HEVCDL_OK;
 }
 
 // the units of pictures [0, n) on the CPU, in the parser's order: the first error met is the lowest picture's first
-hevcdl_status walk_units_host(void *, const StreamUnits &su, int n, hevcdl_ctu_record *records, hevcdl_sao_blk *sao, int *bad_pic, SdResult *res)
+hevcdl_status walk_units_host(void *, const StreamUnits &su, int n, hevcdl_ctu_record *records, hevcdl_sao_blk *sao, int8_t *qp_map, int *bad_pic, SdResult *res)
 {
-  uint8_t ctx[EC_SYNC_BYTES], sync[EC_SYNC_BYTES], dry_depth[512], dry_dir[512]; uint16_t cg_pos[16]; int16_t cg_val[16];
+  uint8_t ctx[EC_SYNC_BYTES], sync[EC_SYNC_BYTES], dry_depth[512], dry_dir[512]; uint16_t cg_pos[16]; int16_t cg_val[16]; int8_t qp_cur[256] = { 0 };
   SdState s; memset(&s, 0, sizeof s);
-  s.t = &ec_tables(); s.s = &su.sd; s.ctx = ctx; s.sync = sync; s.cg_pos = cg_pos; s.cg_val = cg_val; s.dry_depth = dry_depth; s.dry_dir = dry_dir;
+  s.t = &ec_tables(); s.s = &su.sd; s.ctx = ctx; s.sync = sync; s.cg_pos = cg_pos; s.cg_val = cg_val; s.dry_depth = dry_depth; s.dry_dir = dry_dir; s.qp_cur = qp_cur;
   *bad_pic = -1;
   for (size_t i = 0; i < su.pic_unit[(size_t)n]; i++) {
     SdUnit u = su.units[i];
     u.rbsp0 = 0;
-    s.recs = records + (size_t)u.pic * su.ctus; s.sao = sao ? sao + (size_t)u.pic * su.ctus : nullptr;
+    s.recs = records + (size_t)u.pic * su.ctus; s.sao = sao ? sao + (size_t)u.pic * su.ctus : nullptr; s.qp_map = qp_map ? qp_map + (size_t)u.pic * su.ctus * 256 : nullptr;
     const SdResult r = sd_decode_unit(s, u, su.subs.data(), (int)su.subs.size(), su.rbsp.data() + su.pic_byte[(size_t)u.pic], su.pic_byte[(size_t)u.pic + 1] - su.pic_byte[(size_t)u.pic]);
     if (r.code != SD_OK) { *bad_pic = u.pic; *res = r; return HEVCDL_OK; }
   }
@@ -1101,10 +1197,10 @@ void set_slice_error(int pic, const SdResult &res)
   else set_error("picture %d: %s", pic, sd_error_sentence(res.code));
 }
 
-hevcdl_status collect_units(const uint8_t *stream, size_t bytes, int want_slice_data, int have_sao, size_t ctu_capacity, StreamUnits &out)
+hevcdl_status collect_units(const uint8_t *stream, size_t bytes, int want_slice_data, int have_sao, size_t ctu_capacity, StreamUnits &out, unsigned accept)
 {
   out.pic_byte.assign(1, 0); out.pic_sub.assign(1, 0); out.pic_unit.assign(1, 0);
-  const hevcdl_status st = collect_loop(stream, bytes, want_slice_data, have_sao, ctu_capacity, out);
+  const hevcdl_status st = collect_loop(stream, bytes, want_slice_data, have_sao, ctu_capacity, out, accept);
   if (st == HEVCDL_OK) return st;
   // (a picture that was refused half way through its units leaves nothing behind)
   out.rbsp.resize(out.pic_byte.back()); out.subs.resize(out.pic_sub.back()); out.units.resize(out.pic_unit.back());
@@ -1125,26 +1221,28 @@ hevcdl_status batch_tables(const StreamUnits &su, int first, int count, std::vec
 }
 
 hevcdl_status parse_stream_with(UnitWalker walk, void *user, const uint8_t *stream, size_t bytes, hevcdl_stream_config *cfg, hevcdl_slice_layout *slices, hevcdl_segment_layout *segments,
-                                hevcdl_parsed_picture *pictures, int picture_capacity, int *n_pictures, hevcdl_ctu_record *records, hevcdl_sao_blk *sao, size_t ctu_capacity)
+                                hevcdl_parsed_picture *pictures, int picture_capacity, int *n_pictures, hevcdl_ctu_record *records, hevcdl_sao_blk *sao, size_t ctu_capacity,
+                                unsigned accept, hevcdl_qp_info *qp_info, int8_t *qp_map)
 {
   set_error("%s", "");
   if (n_pictures) *n_pictures = 0;
   if (!stream || !cfg || !n_pictures || picture_capacity < 0) INVALID("null stream, configuration or picture count");
   if (cfg->struct_size != sizeof *cfg) INVALID("hevcdl_stream_config.struct_size is not that of this library");
   StreamUnits su;
-  hevcdl_status st = collect_units(stream, bytes, records != nullptr, sao != nullptr, ctu_capacity, su);
+  hevcdl_status st = collect_units(stream, bytes, records != nullptr, sao != nullptr, ctu_capacity, su, accept);
   if (st != HEVCDL_OK) return st;
   const int count = (int)su.pictures.size();
   for (int i = 0; i < count && pictures && i < picture_capacity; i++) pictures[i] = su.pictures[(size_t)i];
   if (records) {
     int bad_pic = -1; SdResult res = { SD_OK, -1 };
-    st = walk(user, su, count, records, sao, &bad_pic, &res);
+    st = walk(user, su, count, records, sao, qp_map, &bad_pic, &res);
     if (st != HEVCDL_OK) return st;
     if (bad_pic >= 0) { set_slice_error(bad_pic, res); return HEVCDL_ERR_INVALID_ARG; }
   }
   if (su.pending != HEVCDL_OK) { set_error("%s", su.pending_sentence); return su.pending; }
   *n_pictures = count;
   *cfg = su.cfg;
+  if (qp_info) *qp_info = su.qp;
   if (slices) *slices = su.slices;
   if (segments) *segments = su.segments;
   if (pictures && count > picture_capacity) INVALID("room for %d pictures, the stream holds %d", picture_capacity, count);
@@ -1157,4 +1255,11 @@ extern "C" hevcdl_status hevcdl_parse_stream_core(const uint8_t *stream, size_t 
                                                  size_t ctu_capacity)
 {
   return parse_stream_with(walk_units_host, nullptr, stream, bytes, cfg, slices, segments, pictures, picture_capacity, n_pictures, records, sao, ctu_capacity);
+}
+
+extern "C" hevcdl_status hevcdl_parse_stream_core_qp(const uint8_t *stream, size_t bytes, unsigned accept, hevcdl_stream_config *cfg, hevcdl_slice_layout *slices, hevcdl_segment_layout *segments,
+                                                    hevcdl_parsed_picture *pictures, int picture_capacity, int *n_pictures, hevcdl_ctu_record *records, hevcdl_sao_blk *sao,
+                                                    size_t ctu_capacity, hevcdl_qp_info *qp_info, int8_t *qp_map)
+{
+  return parse_stream_with(walk_units_host, nullptr, stream, bytes, cfg, slices, segments, pictures, picture_capacity, n_pictures, records, sao, ctu_capacity, accept, qp_info, qp_map);
 }

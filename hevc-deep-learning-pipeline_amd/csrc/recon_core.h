@@ -33,6 +33,12 @@ struct RcPic {
   const hevcdl_ctu_record *recs; // [ctus]
   void *out;                     // planar 4:2:0, uint8 or (bit_depth > 8) uint16 samples
 };
+// The same picture with a QP per CU (hevcdl_parse_stream_qp): the second instantiation of rc_ctu / rc_block.  8.6.1: a transform unit is dequantised with its CU's QpY;
+// chroma with qPi = Clip3(-QpBdOffset, 57, QpY + pps_cb_qp_offset) (Cr: pps_cr_qp_offset) through Table 8-10.  RcPic and everything instantiated with it stay as they are.
+struct RcPicQp : RcPic {
+  const int8_t *qp_map;          // [ctus][256] QpY of every 4x4 partition in z-order
+  int cb_off, cr_off;            // pps_cb_qp_offset, pps_cr_qp_offset
+};
 // the working set of one wave (LDS on the device)
 struct RcWork {
   int16_t ref[132], fref[132];   // 4 n + 1 reference samples from the lowest left one up to the corner and along the top; filtered
@@ -100,10 +106,25 @@ RC_FN int rc_chroma_qp(int qp)
   return qp < 30 ? qp : (qp >= 43 ? qp - 6 : t[qp - 30]);
 }
 
+// QpY of the CU that partition z of CTU a lies in; the QP a block of component comp is dequantised with (QpBdOffset added)
+RC_FN int rc_cu_qpy(const RcPic &, int, int) { return 0; }
+RC_FN int rc_cu_qpy(const RcPicQp &p, int a, int z) { return rc_clip(p.qp_map[(size_t)a * 256 + (z & 255)], -6 * (p.bit_depth - 8), 51); }      // clamped before it indexes levelScale
+RC_FN int rc_block_qp(const RcPic &p, int comp, int)
+{
+  const int bd = p.bit_depth;
+  return comp ? rc_chroma_qp(p.qp) + 6 * (bd - 8) : p.qp + 6 * (bd - 8);
+}
+RC_FN int rc_block_qp(const RcPicQp &p, int comp, int qpy)
+{
+  const int off = 6 * (p.bit_depth - 8);
+  if (!comp) return qpy + off;
+  return rc_chroma_qp(rc_clip(qpy + (comp == 1 ? p.cb_off : p.cr_off), -off, 57)) + off;
+}
+
 // One transform block: prediction from the reconstructed neighbours in the picture, residual from the levels, sum, clip, store.  (x, y): the block's position in samples
 // of its component; lx, ly: the same in luma samples; n = 1 << log2n.
-template <typename PEL>
-RC_FN void rc_block(const RcPic &p, RcWork &w, int lane, int nl, int comp, int lx, int ly, int log2n, int mode, int cbf, int tskip, const int16_t *lvl)
+template <typename PEL, typename PIC>
+RC_FN void rc_block(const PIC &p, RcWork &w, int lane, int nl, int comp, int lx, int ly, int log2n, int mode, int cbf, int tskip, const int16_t *lvl, int qpy)
 {
   log2n = rc_clip(log2n, 2, 5); mode = rc_clip(mode, 0, 34);
   const int n = 1 << log2n, nn = n * n, sh = comp ? 1 : 0, x = lx >> sh, y = ly >> sh, bd = p.bit_depth, pmax = (1 << bd) - 1;
@@ -203,7 +224,7 @@ RC_FN void rc_block(const RcPic &p, RcWork &w, int lane, int nl, int comp, int l
   RC_SYNC();
   // ---- 8.6: the residual
   if (cbf) {
-    const int qp = comp ? rc_chroma_qp(p.qp) + 6 * (bd - 8) : p.qp + 6 * (bd - 8);
+    const int qp = rc_block_qp(p, comp, qpy);
     const int ls[6] = { 40, 45, 51, 57, 64, 72 };
     const int64_t scale = (int64_t)(16 * ls[qp % 6]) << (qp / 6);
     const int bds = bd + log2n - 5, sh2 = 20 - bd;
@@ -213,7 +234,7 @@ RC_FN void rc_block(const RcPic &p, RcWork &w, int lane, int nl, int comp, int l
     }
     RC_SYNC();
     if (tskip && n == 4) {
-      for (int i = lane; i < nn; i += nl) w.res[i] = (int16_t)(((w.tmp[i] << 7) + (1 << (sh2 - 1))) >> sh2);
+      for (int i = lane; i < nn; i += nl) w.res[i] = (int16_t)((w.tmp[i] * 128 + (1 << (sh2 - 1))) >> sh2);      // (x 128, not << 7: a negative value is not shifted left)
     } else {
       const int dst = !comp && n == 4, step = 32 >> log2n;
       // first stage down the columns: e[y][x] = sum_k M[k][y] d[k][x], clipped to 16 bits behind a shift of 7; kept in res
@@ -246,8 +267,8 @@ RC_FN void rc_block(const RcPic &p, RcWork &w, int lane, int nl, int comp, int l
 
 // One CTU: its transform units in z-order -- the coding order -- each luma block followed by its chroma blocks (the 4x4 chroma blocks of four 4x4 luma blocks behind the
 // fourth).
-template <typename PEL>
-RC_FN void rc_ctu(const RcPic &p, RcWork &w, int lane, int nl, int cx, int cy)
+template <typename PEL, typename PIC>
+RC_FN void rc_ctu(const PIC &p, RcWork &w, int lane, int nl, int cx, int cy)
 {
   const int a = cy * p.ctus_x + cx;
   if (cx < 0 || cy < 0 || cx >= p.ctus_x || cy >= p.ctus_y) return;
@@ -260,8 +281,8 @@ RC_FN void rc_ctu(const RcPic &p, RcWork &w, int lane, int nl, int cx, int cy)
     if (x >= p.W || y >= p.H) { z++; continue; }
     const int depth = r.depth[z] & 3, trd = r.tr_idx[z] & 7, log2n = rc_clip(6 - depth - trd, 2, 5), np = 1 << (2 * (log2n - 2));
     if (z & (np - 1)) { z++; continue; }                                                         // (not the first partition of its unit: garbage records only)
-    const int luma = r.luma_dir[z], cd = r.chroma_dir[z];
-    rc_block<PEL>(p, w, lane, nl, 0, x, y, log2n, luma, (r.cbf[0][z] >> trd) & 1, r.tskip[0][z], r.coeff_y + 16 * z);
+    const int luma = r.luma_dir[z], cd = r.chroma_dir[z], qpy = rc_cu_qpy(p, a, z);
+    rc_block<PEL>(p, w, lane, nl, 0, x, y, log2n, luma, (r.cbf[0][z] >> trd) & 1, r.tskip[0][z], r.coeff_y + 16 * z, qpy);
     int zc = -1, l2c = 0;
     if (log2n > 2) { zc = z; l2c = log2n - 1; } else if ((z & 3) == 3) { zc = z & ~3; l2c = 2; }
     if (zc >= 0) {
@@ -270,7 +291,7 @@ RC_FN void rc_ctu(const RcPic &p, RcWork &w, int lane, int nl, int cx, int cy)
       int zx2 = 0, zy2 = 0;
       for (int b = 0; b < 4; b++) { zx2 |= ((zc >> (2 * b)) & 1) << b; zy2 |= ((zc >> (2 * b + 1)) & 1) << b; }
       for (int c = 1; c < 3; c++)
-        rc_block<PEL>(p, w, lane, nl, c, x0 + 4 * zx2, y0 + 4 * zy2, l2c, mode_c, (r.cbf[c][zc] >> trd) & 1, r.tskip[c][zc], (c == 1 ? r.coeff_cb : r.coeff_cr) + 4 * zc);
+        rc_block<PEL>(p, w, lane, nl, c, x0 + 4 * zx2, y0 + 4 * zy2, l2c, mode_c, (r.cbf[c][zc] >> trd) & 1, r.tskip[c][zc], (c == 1 ? r.coeff_cb : r.coeff_cr) + 4 * zc, qpy);
     }
     z += np;
   }

@@ -44,6 +44,7 @@ enum SdError {
   SD_E_TB_SIZE, SD_E_TB_LEAVES, SD_E_LAST_POS, SD_E_LAST_SCAN, SD_E_LEVEL, SD_E_LUMA_MODE,
   SD_E_DATA_ENDS,
   SD_E_TRAILING_BITS, SD_E_NO_END, SD_E_EARLY_END, SD_E_SUBSET_BIT, SD_E_ALIGNMENT,
+  SD_E_QP_DELTA,
   SD_E_COUNT
 };
 // the sentence of a code (host side: the kernel reports the code)
@@ -65,6 +66,7 @@ inline const char *sd_error_sentence(int code)
     "end_of_slice_segment_flag inside its slice segment",
     "end_of_subset_one_bit behind the CTU is 0",
     "byte_alignment() behind the CTU is damaged, or its entry point is wrong",
+    "CuQpDeltaVal outside its range",
   };
   return (unsigned)code < (unsigned)SD_E_COUNT ? s[code] : "an unknown error code";
 }
@@ -74,7 +76,11 @@ struct SdStream {
   int32_t W, H, ctus_x, ctus_y;
   int32_t wpp, tskip, sign_hiding, max_sao;      // entropy_coding_sync_enabled_flag, transform_skip_enabled_flag, sign_data_hiding_enabled_flag, (1 << (min(bitDepth, 10) - 5)) - 1
   int32_t row_slices;                            // SliceMode 1: the one layout in which the CTU behind a slice is neither a new tile nor a new wavefront row (sd_decode_unit)
+  int32_t cu_qp, log2_qg, qp_bd_offset;          // cu_qp_delta_enabled_flag (0 unless the caller accepts it), Log2MinCuQpDeltaSize = 6 - diff_cu_qp_delta_depth, QpBdOffset = 6 * (bitDepth - 8)
 };
+// The two contexts of cu_qp_delta_abs stand BEHIND the coder's NUM_CTX, which keep their numbers: the encoder's coder never sees them.  Initialisation value 154 for both
+// (ITU-T H.265 Table 9-4 names Table 9-24 for cu_qp_delta_abs: ctxIdx 0 .. 1 of initType 0 are 154, 154): slope 0, offset 64 -- state 0, MPS 1 at every slice QP.
+enum { SD_CTX_DQP = NUM_CTX, SD_NUM_CTX = NUM_CTX + 2, SD_DQP_INIT = 154 };
 struct SdSub { uint32_t off, size, ends_segment, pad; };      // off: from the first byte of its picture in the blob
 struct SdUnit {
   int32_t pic, first_ts, n_ctus, slice_addr, qp, sub0, n_subs, sao_on;      // slice_addr: SliceAddrRs of its CTUs (one slice a unit: availability inside the unit does not ask for it)
@@ -88,6 +94,9 @@ struct SdState {
   uint8_t *ctx, *sync;                           // EC_SYNC_BYTES each
   uint16_t *cg_pos; int16_t *cg_val;             // 16 + 16: the coefficient group in work
   uint8_t *dry_depth, *dry_dir;                  // 2 x 256 each: the CTUs walked behind the end of a row slice (sd_decode_unit), current and previous
+  int8_t *qp_cur;                                // 256: QpY of the partitions of the CTU in work (qPY_A / qPY_B come from inside the CTB only, 8.6.1); used with qp_map or s->cu_qp
+  int8_t *qp_map;                                // [ctus][256] of the unit's picture, or null: QpY of every 4x4 partition of a coded CU in z-order, 0 outside the picture
+  int slice_qp, last_qp, qg_pred, is_coded, delta_val;      // SliceQpY; QpY of the last CU in decoding order (qPY_PREV of the next group); qPY_PRED, IsCuQpDeltaCoded, CuQpDeltaVal of the group
   hevcdl_ctu_record *recs; hevcdl_sao_blk *sao;  // of the unit's picture.  NOT const, NOT restrict: depth and luma_dir are read back behind the unit's own stores
   int cx0, cx1, cy0, cy1, cur_cx, cur_cy, dry;
   // bit reader and arithmetic decoder
@@ -139,7 +148,7 @@ SD_FN void sd_start(SdState &s, const uint8_t *data, uint32_t n)
 }
 SD_FN int sd_bin(SdState &s, int c)
 {
-  if ((unsigned)c >= (unsigned)NUM_CTX) { s.bad = 1; return 0; }
+  if ((unsigned)c >= (unsigned)SD_NUM_CTX) { s.bad = 1; return 0; }
   const uint32_t cv = s.ctx[c] & 127u, st = cv >> 1; int v = (int)(cv & 1);
   const uint32_t lps = s.t->lps[st][(s.range >> 6) & 3];
   s.range -= lps;
@@ -178,6 +187,55 @@ SD_FN bool sd_finish(SdState &s)
   if (s.bad || c == 0 || c > (uint64_t)s.size * 8 || !s.last) return false;
   if (sd_bits(s, (int)((8 - (c & 7)) & 7)) != 0) return false;
   return sd_consumed(s) == (uint64_t)s.size * 8 && !s.bad;
+}
+
+// the coder's contexts and, behind them, the two of cu_qp_delta_abs
+SD_FN void sd_init_contexts(SdState &s, int qp)
+{
+  ec_init_contexts(s.ctx, s.t, qp);
+  const int v = SD_DQP_INIT, slope = (v >> 4) * 5 - 45, offset = ((v & 15) << 3) - 16;
+  int st = ((slope * qp) >> 4) + offset; st = st < 1 ? 1 : (st > 126 ? 126 : st);
+  const int mps = st >= 64;
+  for (int i = SD_CTX_DQP; i < SD_NUM_CTX; i++) s.ctx[i] = (uint8_t)(((mps ? st - 64 : 63 - st) << 1) + mps);
+}
+
+// ---- 8.6.1: the luma QP of a quantisation group and of a CU -----------------------------------------------------------------------------------------------
+// a quantisation group starts at the coding-quadtree node (x, y): IsCuQpDeltaCoded and CuQpDeltaVal are reset, qPY_PRED is taken from the left and the upper partition
+// where they lie in the same CTB, else from qPY_PREV -- the QpY of the last CU decoded, SliceQpY behind the start of a slice, a tile or a wavefront row
+SD_FN void sd_start_qg(SdState &s, int x, int y)
+{
+  s.is_coded = 0; s.delta_val = 0;
+  const int xl = ((x - 1) >> 2) & 15, yl = (y >> 2) & 15, xu = (x >> 2) & 15, yu = ((y - 1) >> 2) & 15;
+  const int a = (x & 63) ? s.qp_cur[s.t->r2z[(yl << 4) | xl]] : s.last_qp, b = (y & 63) ? s.qp_cur[s.t->r2z[(yu << 4) | xu]] : s.last_qp;
+  s.qg_pred = (a + b + 1) >> 1;
+}
+// cu_qp_delta_abs (prefix: truncated unary, cMax 5, context 0 for the first bin and 1 for the others; suffix: EG0 in bypass bins) and cu_qp_delta_sign_flag, 7.3.8.14 / 9.3.3.10
+SD_FN void sd_cu_qp_delta(SdState &s)
+{
+  int v = 0;
+  for (int k = 0; k < 5; k++) { if (!sd_bin(s, SD_CTX_DQP + (k ? 1 : 0))) break; v++; }
+  if (v == 5) {
+    int k = 0;
+    for (int i = 0; i < 32; i++) { if (!sd_ep(s)) break; if (k < 8) v += 1 << k; k++; }
+    if (k >= 8) { s.err = SD_E_QP_DELTA; return; }                      // (>= 260: far outside any range; the suffix bits are not read)
+    v += (int)sd_eps(s, k);
+  }
+  if (v && sd_ep(s)) v = -v;
+  const int half = s.s->qp_bd_offset >> 1;
+  if (v < -(26 + half) || v > 25 + half) { s.err = SD_E_QP_DELTA; return; }
+  s.is_coded = 1; s.delta_val = v;
+}
+// QpY of the CU whose syntax has just been read: every partition of it in the CTU's map and, where there is one, in the picture's
+SD_FN void sd_finish_cu_qp(SdState &s, int rs, int z, int nparts)
+{
+  int qp = s.slice_qp;
+  if (s.s->cu_qp) {
+    const int off = s.s->qp_bd_offset < 0 ? 0 : (s.s->qp_bd_offset > 48 ? 48 : s.s->qp_bd_offset);
+    qp = ((s.qg_pred + s.delta_val + 52 + 2 * off) % (52 + off)) - off;
+    s.last_qp = qp;
+  }
+  sd_fill8((uint8_t *)s.qp_cur + (z & 255), nparts, qp);
+  if (s.qp_map && !s.dry) sd_fill8((uint8_t *)s.qp_map + (size_t)rs * 256 + (z & 255), nparts, qp);
 }
 
 // ---- the unit's records ----------------------------------------------------------------------------------------------------------------------------------
@@ -371,6 +429,8 @@ SD_FN void sd_transform_tree(SdState &s, const SdCu &cu)
       }
       if (split) { cb[trd + 1] = cbf_c[1]; cr[trd + 1] = cbf_c[2]; continue; }      // the first child starts at the same partition
       const int cbf_y = sd_bin(s, CTX_QT_CBF + (trd == 0 ? 1 : 0));
+      // transform_unit(): cbfChroma of a 4x4 luma block is its parent's -- cbf_c[] was inherited and not read again
+      if (s.s->cu_qp && !s.is_coded && (cbf_y || cbf_c[1] || cbf_c[2])) { sd_cu_qp_delta(s); if (s.err) return; }
       if (r) sd_fill8(&r->tr_idx[z & 255], np, trd);
       const int luma_mode = s.dry ? s.dry_dir[z & 255] : r->luma_dir[z & 255];
       if (cbf_y) {
@@ -437,6 +497,7 @@ SD_FN void sd_coding_unit(SdState &s, hevcdl_ctu_record *r, int x0, int y0, int 
   }
   if (r) sd_fill8(&r->chroma_dir[cu.z], cu.nparts, rec_c);
   sd_transform_tree(s, cu);
+  if ((s.s->cu_qp || s.qp_map) && !s.err) sd_finish_cu_qp(s, s.cur_cy * s.s->ctus_x + s.cur_cx, cu.z, cu.nparts);
 }
 
 // coding_quadtree() 7.3.8.4 of the CTU at (cur_cx, cur_cy): its 8x8 blocks in z-order; a block covered by a coded CU, or outside the picture, is passed over
@@ -454,6 +515,7 @@ SD_FN void sd_coding_quadtree(SdState &s, hevcdl_ctu_record *r)
     for (int k = 0; k < 3 && (z & ((256 >> (2 * depth)) - 1)) != 0; k++) depth++;
     for (int lvl = 0; lvl < 4 && depth < 4; lvl++, depth++) {
       const int size = 64 >> depth, log2 = 6 - depth;
+      if (s.s->cu_qp && log2 >= s.s->log2_qg) sd_start_qg(s, x, y);
       int split;
       if (x + size <= W && y + size <= H && log2 > 3) {
         int inc = 0;
@@ -480,6 +542,8 @@ SD_FN SdResult sd_decode_unit(SdState &s, const SdUnit &u, const SdSub *subs, in
   if (u.cx0 < 0 || u.cy0 < 0 || uw < 1 || uh < 1 || u.cx1 > g.ctus_x || u.cy1 > g.ctus_y || (long long)uw * uh != u.n_ctus || u.sub0 < 0 || u.n_subs < 1 || u.n_subs > n_subs_all ||
       u.sub0 > n_subs_all - u.n_subs || u.n_subs != (g.wpp ? uh : 1) || (uint64_t)u.rbsp0 + u.rbsp_bytes > blob_bytes || (u.sao_on && !s.sao)) { res.code = SD_E_UNIT; return res; }
   s.cx0 = u.cx0; s.cx1 = u.cx1; s.cy0 = u.cy0; s.cy1 = u.cy1; s.dry = 0; s.err = 0; s.bad = 0;
+  if (g.cu_qp && (g.log2_qg < 3 || g.log2_qg > 6 || !s.qp_cur)) { res.code = SD_E_UNIT; return res; }
+  s.slice_qp = s.last_qp = s.qg_pred = u.qp; s.is_coded = 0; s.delta_val = 0;
   int have_sync = 0, k = 0;
   bool walk_on = false;
   for (int cy = u.cy0; cy < u.cy1; cy++) for (int cx = u.cx0; cx < u.cx1; cx++) {
@@ -492,19 +556,21 @@ SD_FN SdResult sd_decode_unit(SdState &s, const SdUnit &u, const SdSub *subs, in
       if ((uint64_t)sb.off + sb.size > u.rbsp_bytes) { res.code = SD_E_UNIT; return res; }
       sd_start(s, blob + u.rbsp0 + sb.off, sb.size);
       if (s.bad) { res.code = SD_E_SUBSTREAM_START; return res; }
-      if (!first && have_sync && sd_available(s, (cx + 1) << 6, (cy - 1) << 6)) { for (int i = 0; i < NUM_CTX; i++) s.ctx[i] = s.sync[i]; }
-      else ec_init_contexts(s.ctx, s.t, u.qp);
+      if (!first && have_sync && sd_available(s, (cx + 1) << 6, (cy - 1) << 6)) { for (int i = 0; i < SD_NUM_CTX; i++) s.ctx[i] = s.sync[i]; }
+      else sd_init_contexts(s, u.qp);
+      s.last_qp = u.qp;                                                 // qPY_PREV of the first quantisation group of a slice, a tile, a wavefront row: SliceQpY
     }
     hevcdl_ctu_record *r = s.recs + rs;
     sd_clear32(r, (int)(sizeof(hevcdl_ctu_record) / 4));
     if (s.sao) sd_clear32(s.sao + rs, (int)(sizeof(hevcdl_sao_blk) / 4));
+    if (s.qp_map) sd_clear32(s.qp_map + (size_t)rs * 256, 64);
     if (u.sao_on) sd_sao(s, rs);
     sd_coding_quadtree(s, r);
     res.ctu = rs;
     if (s.err) { res.code = s.err; return res; }
     const int end = sd_terminate(s);
     if (s.bad) { res.code = SD_E_DATA_ENDS; return res; }
-    if (g.wpp && cx == u.cx0 + 1) { for (int i = 0; i < NUM_CTX; i++) s.sync[i] = s.ctx[i]; have_sync = 1; }
+    if (g.wpp && cx == u.cx0 + 1) { for (int i = 0; i < SD_NUM_CTX; i++) s.sync[i] = s.ctx[i]; have_sync = 1; }
     const bool sub_ends = g.wpp ? cx == u.cx1 - 1 : (cx == u.cx1 - 1 && cy == u.cy1 - 1);
     const bool seg_ends = sub_ends && subs[u.sub0 + k].ends_segment;
     if (end) {

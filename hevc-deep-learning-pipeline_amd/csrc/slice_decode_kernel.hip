@@ -31,7 +31,7 @@ using namespace hevcdl_sd;
 
 namespace {
 constexpr int SD_WAVES = 4;                  // waves (= units) per workgroup
-struct WaveLds { uint8_t ctx[EC_SYNC_BYTES], sync[EC_SYNC_BYTES]; uint16_t cg_pos[16]; int16_t cg_val[16]; uint8_t dry_depth[512], dry_dir[512]; SdStream sd; };
+struct WaveLds { uint8_t ctx[EC_SYNC_BYTES], sync[EC_SYNC_BYTES]; uint16_t cg_pos[16]; int16_t cg_val[16]; uint8_t dry_depth[512], dry_dir[512]; int8_t qp_cur[256]; SdStream sd; };
 std::atomic<unsigned long long> g_launches{ 0 };
 __device__ inline int sd_lane() { return (int)(threadIdx.x & 63u); }
 }
@@ -62,6 +62,8 @@ extern "C" __global__ __launch_bounds__(SD_WAVES * 64) void hevcdl_slice_decode_
     s.t = (const EcTables *)p.tables; s.s = &l.sd; s.ctx = l.ctx; s.sync = l.sync; s.cg_pos = l.cg_pos; s.cg_val = l.cg_val; s.dry_depth = l.dry_depth; s.dry_dir = l.dry_dir;
     s.recs = (hevcdl_ctu_record *)p.records + (size_t)u.pic * p.ctus;
     s.sao = p.sao ? (hevcdl_sao_blk *)p.sao + (size_t)u.pic * p.ctus : nullptr;
+    s.qp_cur = l.qp_cur; s.qp_map = p.qp_map ? p.qp_map + (size_t)u.pic * p.ctus * 256 : nullptr;      // the map: written across the lanes like depth (sd_fill8)
+    s.slice_qp = s.last_qp = s.qg_pred = s.is_coded = s.delta_val = 0;
     s.cx0 = s.cx1 = s.cy0 = s.cy1 = s.cur_cx = s.cur_cy = s.dry = 0; s.d = p.blob; s.size = s.pos = 0; s.win = 0; s.nwin = 0; s.last = 0; s.range = 510; s.offset = 0; s.bad = s.err = 0;
     res = sd_decode_unit(s, u, p.subs, p.n_subs, p.blob, p.blob_bytes);
   }
@@ -72,6 +74,7 @@ int hevcdl_launch_slice_decode(const hevcdl_slice_decode_params *p, void *stream
 {
   if (!p || p->n_units <= 0 || p->n_subs <= 0 || p->n_pics <= 0 || !p->blob || !p->subs || !p->units || !p->records || !p->results || !p->tables) return 0;
   if (p->sd.ctus_x < 1 || p->sd.ctus_y < 1 || (long long)p->sd.ctus_x * p->sd.ctus_y != p->ctus || ((uintptr_t)p->records & 15)) return 0;
+  if ((p->sd.cu_qp && (!p->qp_map || p->sd.log2_qg < 3 || p->sd.log2_qg > 6)) || ((uintptr_t)p->qp_map & 3)) return 0;
   hipLaunchKernelGGL(hevcdl_slice_decode_kernel, dim3((unsigned)((p->n_units + SD_WAVES - 1) / SD_WAVES)), dim3(SD_WAVES * 64), 0, (hipStream_t)stream, *p);
   g_launches++;
   return 1;
@@ -90,7 +93,7 @@ namespace {
 struct DevMem { void *p = nullptr; ~DevMem() { if (p) (void)hipFree(p); } hipError_t get(size_t n) { return hipMalloc(&p, n ? n : 4); } };
 #define SD_HIP(call) do { if ((call) != hipSuccess) { (void)hipGetLastError(); hevcdl_parse::set_error("hevcdl_parse_stream_dev: %s failed", #call); return HEVCDL_ERR_HIP; } } while (0)
 
-hevcdl_status walk_units_dev(void *user, const hevcdl_parse::StreamUnits &su, int n, hevcdl_ctu_record *records, hevcdl_sao_blk *sao, int *bad_pic, SdResult *res)
+hevcdl_status walk_units_dev(void *user, const hevcdl_parse::StreamUnits &su, int n, hevcdl_ctu_record *records, hevcdl_sao_blk *sao, int8_t *qp_map, int *bad_pic, SdResult *res)
 {
   const int device = *(const int *)user;
   int n_dev = 0;
@@ -107,7 +110,9 @@ hevcdl_status walk_units_dev(void *user, const hevcdl_parse::StreamUnits &su, in
     std::vector<SdUnit> units; size_t sub0, n_subs, byte0, n_bytes;
     const hevcdl_status st = hevcdl_parse::batch_tables(su, first, cnt, units, sub0, n_subs, byte0, n_bytes);
     if (st != HEVCDL_OK) return st;
-    DevMem d_blob, d_subs, d_units, d_res, d_rec, d_sao;
+    DevMem d_blob, d_subs, d_units, d_res, d_rec, d_sao, d_map;
+    const size_t map_b = (size_t)su.ctus * 256;
+    if (qp_map) SD_HIP(d_map.get(map_b * cnt));
     SD_HIP(d_blob.get(n_bytes)); SD_HIP(d_subs.get(n_subs * sizeof(SdSub))); SD_HIP(d_units.get(units.size() * sizeof(SdUnit))); SD_HIP(d_res.get(units.size() * sizeof(SdResult)));
     SD_HIP(d_rec.get(rec_b * cnt));
     if (sao) SD_HIP(d_sao.get(sao_b * cnt));
@@ -116,7 +121,7 @@ hevcdl_status walk_units_dev(void *user, const hevcdl_parse::StreamUnits &su, in
     SD_HIP(hipMemcpy(d_units.p, units.data(), units.size() * sizeof(SdUnit), hipMemcpyHostToDevice));
     hevcdl_slice_decode_params k;
     k.sd = su.sd; k.blob = (const uint8_t *)d_blob.p; k.blob_bytes = n_bytes; k.subs = (const SdSub *)d_subs.p; k.units = (const SdUnit *)d_units.p; k.n_subs = (int)n_subs; k.n_units = (int)units.size();
-    k.records = d_rec.p; k.sao = d_sao.p; k.ctus = su.ctus; k.n_pics = cnt; k.results = (SdResult *)d_res.p; k.tables = d_tables.p;
+    k.records = d_rec.p; k.sao = d_sao.p; k.ctus = su.ctus; k.n_pics = cnt; k.results = (SdResult *)d_res.p; k.tables = d_tables.p; k.qp_map = (int8_t *)d_map.p;
     if (!hevcdl_launch_slice_decode(&k, nullptr)) { hevcdl_parse::set_error("hevcdl_parse_stream_dev: the unit tables of pictures %d .. %d do not fit a launch", first, first + cnt - 1); return HEVCDL_ERR_INVALID_ARG; }
     SD_HIP(hipGetLastError());
     std::vector<SdResult> results(units.size());
@@ -125,6 +130,7 @@ hevcdl_status walk_units_dev(void *user, const hevcdl_parse::StreamUnits &su, in
     if (bad >= 0) { *bad_pic = first + bad; return HEVCDL_OK; }
     SD_HIP(hipMemcpy(records + (size_t)first * su.ctus, d_rec.p, rec_b * cnt, hipMemcpyDeviceToHost));
     if (sao) SD_HIP(hipMemcpy(sao + (size_t)first * su.ctus, d_sao.p, sao_b * cnt, hipMemcpyDeviceToHost));
+    if (qp_map) SD_HIP(hipMemcpy(qp_map + (size_t)first * map_b, d_map.p, map_b * cnt, hipMemcpyDeviceToHost));
   }
   return HEVCDL_OK;
 }
@@ -135,4 +141,11 @@ extern "C" hevcdl_status hevcdl_parse_stream_dev(int device, const uint8_t *stre
                                                 size_t ctu_capacity)
 {
   return hevcdl_parse::parse_stream_with(walk_units_dev, &device, stream, bytes, cfg, slices, segments, pictures, picture_capacity, n_pictures, records, sao, ctu_capacity);
+}
+
+extern "C" hevcdl_status hevcdl_parse_stream_dev_qp(int device, const uint8_t *stream, size_t bytes, unsigned accept, hevcdl_stream_config *cfg, hevcdl_slice_layout *slices,
+                                                   hevcdl_segment_layout *segments, hevcdl_parsed_picture *pictures, int picture_capacity, int *n_pictures, hevcdl_ctu_record *records,
+                                                   hevcdl_sao_blk *sao, size_t ctu_capacity, hevcdl_qp_info *qp_info, int8_t *qp_map)
+{
+  return hevcdl_parse::parse_stream_with(walk_units_dev, &device, stream, bytes, cfg, slices, segments, pictures, picture_capacity, n_pictures, records, sao, ctu_capacity, accept, qp_info, qp_map);
 }

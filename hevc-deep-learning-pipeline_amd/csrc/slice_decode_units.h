@@ -17,6 +17,7 @@ namespace hevcdl_parse {
 struct StreamUnits {
   hevcdl_stream_config cfg; hevcdl_slice_layout slices; hevcdl_segment_layout segments;      // as hevcdl_parse_stream gives them (cfg only without a pending refusal)
   hevcdl_sd::SdStream sd;
+  hevcdl_qp_info qp = { 0, 0, 0, 0 };            // the PPS fields a QP map goes with (all 0 unless accepted)
   int ctus = 0;
   std::vector<hevcdl_parsed_picture> pictures;
   std::vector<uint8_t> rbsp;                     // the slice data of every picture, emulation prevention removed, sub-stream behind sub-stream
@@ -27,16 +28,18 @@ struct StreamUnits {
 };
 // want_slice_data 0: headers only (no tables).  have_sao / ctu_capacity: the caller's room, checked per picture as hevcdl_parse_stream does.  Returns HEVCDL_OK also with a
 // pending refusal; anything else is a refusal in front of the first picture's end (the sentence is in hevcdl_parse_error()).
-hevcdl_status collect_units(const uint8_t *stream, size_t bytes, int want_slice_data, int have_sao, size_t ctu_capacity, StreamUnits &out);
+// accept: HEVCDL_ACCEPT_* bits (hevcdl.h) -- 0: cu_qp_delta_enabled_flag and chroma QP offsets are refused as ever; su.qp says what the PPS carries.
+hevcdl_status collect_units(const uint8_t *stream, size_t bytes, int want_slice_data, int have_sao, size_t ctu_capacity, StreamUnits &out, unsigned accept = 0);
 // the tables of pictures [first, first + count) as one launch takes them: units and sub-streams renumbered from 0, rbsp0 from the first byte of picture `first`
 hevcdl_status batch_tables(const StreamUnits &su, int first, int count, std::vector<hevcdl_sd::SdUnit> &units, size_t &sub0, size_t &n_subs, size_t &byte0, size_t &n_bytes);
 
 // Walks the units of pictures [0, n) into records / sao ([n][ctus]; sao may be null when no picture has SAO on).  HEVCDL_OK: *bad_pic < 0, or the lowest picture with an error and its
-// first error in *res; anything else: the walker itself failed (a HIP error; the sentence set).
-typedef hevcdl_status (*UnitWalker)(void *user, const StreamUnits &su, int n, hevcdl_ctu_record *records, hevcdl_sao_blk *sao, int *bad_pic, hevcdl_sd::SdResult *res);
+// first error in *res; anything else: the walker itself failed (a HIP error; the sentence set).  qp_map: [n][ctus][256] or null (hevcdl_parse_stream_qp).
+typedef hevcdl_status (*UnitWalker)(void *user, const StreamUnits &su, int n, hevcdl_ctu_record *records, hevcdl_sao_blk *sao, int8_t *qp_map, int *bad_pic, hevcdl_sd::SdResult *res);
 // hevcdl_parse_stream's contract with the slice data decoded by `walk`
 hevcdl_status parse_stream_with(UnitWalker walk, void *user, const uint8_t *stream, size_t bytes, hevcdl_stream_config *cfg, hevcdl_slice_layout *slices, hevcdl_segment_layout *segments,
-                                hevcdl_parsed_picture *pictures, int picture_capacity, int *n_pictures, hevcdl_ctu_record *records, hevcdl_sao_blk *sao, size_t ctu_capacity);
+                                hevcdl_parsed_picture *pictures, int picture_capacity, int *n_pictures, hevcdl_ctu_record *records, hevcdl_sao_blk *sao, size_t ctu_capacity,
+                                unsigned accept = 0, hevcdl_qp_info *qp_info = nullptr, int8_t *qp_map = nullptr);
 // "picture 3, CTU 17: <sentence of the code>" into hevcdl_parse_error()
 void set_slice_error(int pic, const hevcdl_sd::SdResult &res);
 
@@ -53,6 +56,7 @@ struct hevcdl_slice_decode_params {
   void *records; void *sao; int ctus, n_pics;
   hevcdl_sd::SdResult *results;
   const void *tables;
+  int8_t *qp_map;                                // [n_pics][ctus][256] QpY per 4x4 partition, or null: not wanted (must not be null when sd.cu_qp is set)
 };
 // launches nothing and returns 0 when the parameters do not fit each other (no units, a grid that is not `ctus` CTUs, null pointers); 1 behind a launch
 int hevcdl_launch_slice_decode(const hevcdl_slice_decode_params *p, void *stream);

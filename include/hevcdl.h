@@ -826,7 +826,7 @@ typedef struct hevcdl_parsed_picture {
  * csrc/hevcdl_parse.h), bits / dist / cost are 0; sao_opt is needed when a picture has SAO on and holds zeros for the others.
  * Accepted is exactly what this library's writer can produce: I slices, main or main10, 4:2:0, CTU 64, minimum CB 8, TU 4 .. 32, any picture size (multiples of 8) with a
  * conformance window, tiles or wavefront rows, slices of CTU rows or tiles, dependent segments, every tool switch, the deblocking filter on or off.  Anything else is
- * HEVCDL_ERR_UNSUPPORTED -- P and B slices, PCM, scaling lists, cu_qp_delta_enabled_flag, transquant bypass, other chroma formats or bit depths, slices that do not start at
+ * HEVCDL_ERR_UNSUPPORTED -- P and B slices, PCM, scaling lists, cu_qp_delta_enabled_flag and PPS chroma QP offsets (unless accepted: hevcdl_parse_stream_qp below), transquant bypass, other chroma formats or bit depths, slices that do not start at
  * a CTU row or a tile, ... -- and a damaged stream is HEVCDL_ERR_INVALID_ARG, never a crash: every value that addresses memory is checked where it is read.  Either way
  * hevcdl_parse_error() is a sentence saying what (per thread; "" after a success). */
 hevcdl_status hevcdl_parse_stream(const uint8_t *stream, size_t bytes, hevcdl_stream_config *cfg, hevcdl_slice_layout *slices_opt, hevcdl_segment_layout *segments_opt,
@@ -849,6 +849,35 @@ hevcdl_status hevcdl_parse_stream_dev(int device, const uint8_t *stream, size_t 
                                       hevcdl_segment_layout *segments_opt, hevcdl_parsed_picture *pictures_opt, int picture_capacity, int *n_pictures,
                                       hevcdl_ctu_record *records_opt, hevcdl_sao_blk *sao_opt, size_t ctu_capacity);
 unsigned long long hevcdl_slice_decode_launches(void);
+/* ---- a QP per CU: OFF unless the call accepts it ----------------------------------------------------------------------------------------
+ * The entry points above refuse a PPS with cu_qp_delta_enabled_flag or with pps_cb_qp_offset / pps_cr_qp_offset other than 0, sentence for sentence as ever.  The _qp
+ * forms take `accept`: with HEVCDL_ACCEPT_CU_QP they read cu_qp_delta_enabled_flag, diff_cu_qp_delta_depth (0 .. 3) and the two offsets (-12 .. 12) into *qp_info_opt,
+ * the slice data with cu_qp_delta_abs / cu_qp_delta_sign_flag (7.3.8.14; the two contexts of the prefix stand behind the coder's 161), and derive QpY per 8.6.1: qPY_PREV
+ * is SliceQpY at the first quantisation group of a slice, a tile and a wavefront row, else the QpY of the last CU decoded; qPY_A / qPY_B come from inside the CTB only.
+ * A CuQpDeltaVal outside -(26 + QpBdOffset / 2) .. 25 + QpBdOffset / 2 is HEVCDL_ERR_INVALID_ARG with its CTU.  pps_slice_chroma_qp_offsets_present_flag stays refused.
+ * qp_map_opt: int8 [pictures][ctus][256] BESIDE the records (hevcdl_ctu_record keeps its size): QpY of every 4x4 partition in z-order, every partition of a coded CU
+ * filled -- a CU without a cbf has the predicted value -- and 0 outside the picture; a stream without the flag gives its slice QP everywhere.  Room for ctu_capacity CTUs.
+ * With accept 0 and no map the three are the entry points above.  _core_qp: the shared decoder on the CPU; _dev_qp: the kernel, which writes the map across its lanes. */
+#define HEVCDL_ACCEPT_CU_QP 1u
+typedef struct hevcdl_qp_info { int32_t cu_qp_delta_enabled, diff_cu_qp_delta_depth, cb_qp_offset, cr_qp_offset; } hevcdl_qp_info;
+hevcdl_status hevcdl_parse_stream_qp(const uint8_t *stream, size_t bytes, unsigned accept, hevcdl_stream_config *cfg, hevcdl_slice_layout *slices_opt,
+                                     hevcdl_segment_layout *segments_opt, hevcdl_parsed_picture *pictures_opt, int picture_capacity, int *n_pictures,
+                                     hevcdl_ctu_record *records_opt, hevcdl_sao_blk *sao_opt, size_t ctu_capacity, hevcdl_qp_info *qp_info_opt, int8_t *qp_map_opt);
+/* What the slice data of the last hevcdl_parse_stream_qp of this thread met (TEST AND DIAGNOSTIC: tools/gen_cu_qp_fixtures.py prints it per fixture).  A group is a
+ * quantisation group with at least one CU.  deltas_by_parent_chroma_cbf: read in a 4x4 luma block with cbf_luma 0, i.e. for its parent's chroma cbf;
+ * groups_left_from_prev / groups_up_from_prev: qPY_A / qPY_B replaced by qPY_PREV (the group touches its CTB's edge); groups_opening_*: the first group behind a reset of
+ * qPY_PREV to SliceQpY (picture start counts as a tile's); coded_behind_uncoded_in_ctu: a group with a delta behind one without in the same CTU. */
+typedef struct hevcdl_qp_tally {
+  uint32_t groups_with_delta, groups_without_delta, deltas_positive, deltas_negative, deltas_zero, max_abs_delta, deltas_with_suffix, suffixes_of_several_bins,
+           deltas_by_parent_chroma_cbf, groups_left_from_prev, groups_up_from_prev, groups_opening_tile, groups_opening_slice, groups_opening_wpp_row, coded_behind_uncoded_in_ctu;
+} hevcdl_qp_tally;
+void hevcdl_parse_qp_tally(hevcdl_qp_tally *out);
+hevcdl_status hevcdl_parse_stream_core_qp(const uint8_t *stream, size_t bytes, unsigned accept, hevcdl_stream_config *cfg, hevcdl_slice_layout *slices_opt,
+                                          hevcdl_segment_layout *segments_opt, hevcdl_parsed_picture *pictures_opt, int picture_capacity, int *n_pictures,
+                                          hevcdl_ctu_record *records_opt, hevcdl_sao_blk *sao_opt, size_t ctu_capacity, hevcdl_qp_info *qp_info_opt, int8_t *qp_map_opt);
+hevcdl_status hevcdl_parse_stream_dev_qp(int device, const uint8_t *stream, size_t bytes, unsigned accept, hevcdl_stream_config *cfg, hevcdl_slice_layout *slices_opt,
+                                         hevcdl_segment_layout *segments_opt, hevcdl_parsed_picture *pictures_opt, int picture_capacity, int *n_pictures,
+                                         hevcdl_ctu_record *records_opt, hevcdl_sao_blk *sao_opt, size_t ctu_capacity, hevcdl_qp_info *qp_info_opt, int8_t *qp_map_opt);
 /* Records a caller brings itself (n_frames pictures of cfg's size), checked as the parser's own are by construction: depths that form a quadtree with the forced splits
  * at the picture's edge, NxN only in 8x8 CUs, prediction modes in range and constant over their block, tr_idx a transform tree within TU 4 .. 32 and depth 3, no cbf
  * bit below the depth of the partition's transform unit, transform-skip flags 0 / 1.  HEVCDL_ERR_INVALID_ARG with a sentence in hevcdl_parse_error() otherwise.  NOT
@@ -873,6 +902,15 @@ hevcdl_status hevcdl_reconstruct_frames_dev(int device, const hevcdl_stream_conf
 hevcdl_status hevcdl_reconstruct_frames_host(const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const int32_t *qps_opt,
                                              const hevcdl_ctu_record *records, int n_frames, void *recon);
 unsigned long long hevcdl_recon_launches(void);
+/* The same three with a QP map (hevcdl_parse_stream_qp: int8 [n_frames][ctus][256], HOST memory for the first and the third, DEVICE memory for _dev) and the PPS chroma
+ * offsets of *qp_info: a transform unit is dequantised with its CU's QpY; Cb with qPi = Clip3(-QpBdOffset, 57, QpY + pps_cb_qp_offset) through Table 8-10, Cr with
+ * pps_cr_qp_offset.  Map values are clamped to -QpBdOffset .. 51 before they are used.  A second instantiation of the kernel: the launch above is the one it was. */
+hevcdl_status hevcdl_reconstruct_frames_qp(int device, const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const hevcdl_qp_info *qp_info,
+                                           const int8_t *qp_map, const hevcdl_ctu_record *records, int n_frames, void *recon);
+hevcdl_status hevcdl_reconstruct_frames_qp_dev(int device, const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const hevcdl_qp_info *qp_info,
+                                               const void *d_qp_map, const void *d_records, int n_frames, void *d_recon, void *stream);
+hevcdl_status hevcdl_reconstruct_frames_qp_host(const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const hevcdl_qp_info *qp_info,
+                                                const int8_t *qp_map, const hevcdl_ctu_record *records, int n_frames, void *recon);
 
 /* ---- the decoder: a stream of this library's writer, or of the reference encoder in the same configuration, to pictures ------------------------
  * hevcdl_config_from_stream: the configuration of a context that can decode a parsed stream (hevcdl_parse_stream with records_opt NULL gives cfg, the slice layout and
@@ -895,6 +933,18 @@ hevcdl_status hevcdl_config_from_stream(const hevcdl_stream_config *stream_cfg, 
 hevcdl_status hevcdl_decode_stream(hevcdl_ctx *ctx, const uint8_t *stream, size_t bytes, void *pictures_opt, int picture_capacity, int *n_pictures,
                                    hevcdl_parsed_picture *info_opt, int32_t *hash_ok_opt);
 hevcdl_status hevcdl_enable_device_parse(hevcdl_ctx *ctx, int on);
+/* hevcdl_enable_cu_qp(ctx, 1): hevcdl_decode_stream accepts streams with cu_qp_delta_enabled_flag or PPS chroma QP offsets (HEVCDL_ACCEPT_CU_QP above).  The QP map of
+ * a batch lies in HBM beside the records -- uploaded behind a host parse, written there by hevcdl_slice_decode_kernel with device parse -- and the QP-map instantiations of
+ * hevcdl_recon_kernel and hevcdl_deblock_fused_kernel read it; SAO and the report kernels are what they were.  A stream without the flag and with zero offsets takes the
+ * constant-QP launches, also when enabled.  Off by default: such a stream is refused with the parser's sentence; (ctx, 0) turns it off again and frees the map.
+ * hevcdl_deblock_frames_map: the deblocking filter with a QP per edge on host buffers (TEST AND DIAGNOSTIC) -- per 4-sample edge segment qPL = (QpQ + QpP + 1) >> 1, beta and
+ * tC from qPL and the picture's offsets (choices_opt, NULL: the context's), per chroma plane QpC from qPL + the plane's PPS offset; qp_map [n_frames][ctus][256]. */
+hevcdl_status hevcdl_enable_cu_qp(hevcdl_ctx *ctx, int on);
+/* launches of the QP-map instantiations this process has made: of the reconstruction kernel's -- they count in hevcdl_recon_launches too -- and of the deblocking pair (TEST AND DIAGNOSTIC) */
+unsigned long long hevcdl_recon_qp_launches(void);
+unsigned long long hevcdl_deblock_qp_launches(void);
+hevcdl_status hevcdl_deblock_frames_map(hevcdl_ctx *ctx, const void *recon, int n_frames, const hevcdl_ctu_record *records, const hevcdl_dbk_choice *choices_opt,
+                                        const hevcdl_qp_info *qp_info, const int8_t *qp_map, void *out);
 
 /* kernel timing with HIP events recorded on the launch stream */
 hevcdl_status hevcdl_profile_enable(hevcdl_ctx *ctx, int enable);

@@ -11,8 +11,13 @@ of three runs with the device idle before and after (wall clock around a synchro
   decode_stream   hevcdl_decode_stream: everything, the pictures staying in HBM between the stages, digests by the report kernels; a second row with
                   hevcdl_enable_device_parse, where the records never leave HBM either
 and, where oracle/_ref/TAppDecoder_ref is present, the reference decoder's wall time on the same stream.
+A second leg times a stream with a QP per CU: one picture of the same size coded by the reference encoder with AdaptiveQP 1, MaxCuDQPDepth 2
+(--cu-qp-stream FILE: such a stream made beforehand; otherwise oracle/_ref/TAppEncoder_ref makes it, and without either the leg is written as "not measured") -- parse on
+the host and on the device with the QP map, and reconstruction and deblocking of the SAME records with the map (the QP-map instantiations) and without it (the constant-QP
+kernels at the slice QP: another picture, the same work), then hevcdl_decode_stream with the switch on.
+--keep-lines N keeps the last N lines of the file that is there (results another tool appended, e.g. a comparison against the parent commit).
 
-    python tools/time_decode.py [--batch 8] [--width 3840 --height 2160] [--qp 32]
+    python tools/time_decode.py [--batch 8] [--width 3840 --height 2160] [--qp 32] [--cu-qp-stream FILE]
 """
 import argparse
 import os
@@ -37,6 +42,35 @@ def best(fn, runs=3):
     return min(t) * 1000.0, out
 
 
+def cu_qp_leg(hevcdl_amd, ref_tools, a, d):
+    """The lines of the QP-map leg: a stream of one picture with cu_qp_delta_enabled_flag, its stages with and without the map."""
+    w, h, qp = a.width, a.height, a.qp
+    head = "QP per CU, %dx%d 8-bit QP %d, AdaptiveQP 1 MaxCuDQPDepth 2, 1 picture: " % (w, h, qp)
+    if a.cu_qp_stream:
+        stream = open(a.cu_qp_stream, "rb").read()
+    elif os.path.exists(ref_tools.REF_ENC):
+        yuv = ref_tools.synth_yuv(w, h, 1, seed=78)
+        stream = ref_tools.run_reference(yuv, w, h, qp, ref_tools.make_labels(w, h, 1, "rand", seed=78), extra_args=["--AdaptiveQP=1", "--MaxQPAdaptationRange=6", "--MaxCuDQPDepth=2"])[2]
+    else:
+        return [head + "not measured (no stream given and no reference encoder to make one)"]
+    t_parse, p = best(lambda: hevcdl_amd.parse_stream(stream, cu_qp=True))
+    t_parse_dev, pd = best(lambda: hevcdl_amd.parse_stream(stream, cu_qp=True, engine="device"))
+    assert pd.records.tobytes() == p.records.tobytes() and pd.qp_map.tobytes() == p.qp_map.tobytes() and p.qp_info.cu_qp_delta_enabled
+    t_rec_map, recon = best(lambda: hevcdl_amd.reconstruct_frames(p.cfg, p.records, slices=p.slices, qp_map=p.qp_map, qp_info=p.qp_info, device=0))
+    t_rec, _ = best(lambda: hevcdl_amd.reconstruct_frames(p.cfg, p.records, slices=p.slices, qps=p.qps, device=0))
+    with hevcdl_amd.StreamDecoder(stream, batch=1) as dec:
+        t_dbk_map, _ = best(lambda: dec.deblock_map(recon, p))
+    e = hevcdl_amd.Encoder(w, h, p.qps[0], max_frames=1)
+    t_dbk, _ = best(lambda: e.deblock_frames(recon, p.records))
+    e.close()
+    t_all, out = best(lambda: hevcdl_amd.decode_stream(stream, batch=1, cu_qp=True))
+    t_dp, out_dp = best(lambda: hevcdl_amd.decode_stream(stream, batch=1, cu_qp=True, device_parse=True))
+    assert all(v is True for v in out[3]) and all(v is True for v in out_dp[3]) and np.array_equal(out[0], out_dp[0])
+    return [head + "measured",
+            "  stream %8d bytes  QpY %d .. %d  parse with map %8.1f  parse (device) with map %8.1f" % (len(stream), p.qp_map[p.qp_map != 0].min(), p.qp_map.max(), t_parse, t_parse_dev),
+            "  reconstruct with map %8.1f  without %8.1f   deblock with map %8.1f  without %8.1f   decode_stream %8.1f  with device parse %8.1f" % (t_rec_map, t_rec, t_dbk_map, t_dbk, t_all, t_dp)]
+
+
 def main():
     import hevcdl_amd
     from hevcdl_amd import pipeline
@@ -46,6 +80,8 @@ def main():
     ap.add_argument("--width", type=int, default=3840)
     ap.add_argument("--height", type=int, default=2160)
     ap.add_argument("--qp", type=int, default=32)
+    ap.add_argument("--cu-qp-stream", default=None)
+    ap.add_argument("--keep-lines", type=int, default=0)
     a = ap.parse_args()
     w, h, qp = a.width, a.height, a.qp
     lines = ["decoder times, %dx%d 8-bit QP %d, ms (best of 3; wall clock around synchronous calls)" % (w, h, qp)]
@@ -75,12 +111,15 @@ def main():
                 t0 = time.perf_counter()
                 r = subprocess.run([ref, "-b", "s.bin", "-o", "ref.yuv"], cwd=d, capture_output=True, text=True)
                 lines.append("pictures %3d  reference decoder %8.1f  (exit %d)" % (n, (time.perf_counter() - t0) * 1000.0, r.returncode))
+        lines += cu_qp_leg(hevcdl_amd, ref_tools, a, d)
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
     lines.append("(tools/time_decode.py on one MI355X.  decode_stream is the Python entry hevcdl_amd.decode_stream: it creates and destroys a context per call, which is in its time; the\n"
                  "stage columns include their host <-> device copies.  One 2160p picture is a chain of 34 CTU rows two CTUs apart, so a single picture is bound by that chain's latency and a\n"
                  "batch amortises it.  A record, not a bound.)")
-    with open(os.path.join(ROOT, "profiles", "decode_time.txt"), "w") as f:
-        f.write("\n".join(lines) + "\n")
+    path = os.path.join(ROOT, "profiles", "decode_time.txt")
+    kept = open(path).read().splitlines()[-a.keep_lines:] if a.keep_lines > 0 and os.path.exists(path) else []
+    with open(path, "w") as f:
+        f.write("\n".join(lines + kept) + "\n")
     print("\n".join(lines))
 
 
