@@ -453,6 +453,15 @@ def load_library():
     lib.hevcdl_reconstruct_frames_qp.argtypes = [ci, ctypes.POINTER(StreamConfig), slp, ctypes.POINTER(QpInfo), vp, vp, ci, vp]
     lib.hevcdl_reconstruct_frames_qp_dev.argtypes = [ci, ctypes.POINTER(StreamConfig), slp, ctypes.POINTER(QpInfo), vp, vp, ci, vp, vp]
     lib.hevcdl_reconstruct_frames_qp_host.argtypes = [ctypes.POINTER(StreamConfig), slp, ctypes.POINTER(QpInfo), vp, vp, ci, vp]
+    _sl_tail = [ctypes.POINTER(ScalingInfo)]
+    lib.hevcdl_parse_stream_sl.argtypes = lib.hevcdl_parse_stream_qp.argtypes + _sl_tail
+    lib.hevcdl_parse_stream_core_sl.argtypes = lib.hevcdl_parse_stream_sl.argtypes
+    lib.hevcdl_parse_stream_dev_sl.argtypes = [ci] + lib.hevcdl_parse_stream_sl.argtypes
+    lib.hevcdl_enable_scaling_lists.argtypes = [vp, ci]
+    lib.hevcdl_recon_sl_launches.argtypes, lib.hevcdl_recon_sl_launches.restype = [], ctypes.c_uint64
+    lib.hevcdl_reconstruct_frames_sl.argtypes = [ci, ctypes.POINTER(StreamConfig), slp, ctypes.POINTER(QpInfo), vp, ctypes.POINTER(ScalingInfo), vp, ci, vp]
+    lib.hevcdl_reconstruct_frames_sl_dev.argtypes = [ci, ctypes.POINTER(StreamConfig), slp, ctypes.POINTER(QpInfo), vp, ctypes.POINTER(ScalingInfo), vp, ci, vp, vp]
+    lib.hevcdl_reconstruct_frames_sl_host.argtypes = [ctypes.POINTER(StreamConfig), slp, ctypes.POINTER(QpInfo), vp, ctypes.POINTER(ScalingInfo), vp, ci, vp]
     lib.hevcdl_slice_decode_launches.restype = ctypes.c_uint64
     lib.hevcdl_enable_device_parse.argtypes = [vp, ci]
     lib.hevcdl_parse_error.argtypes = []
@@ -498,9 +507,15 @@ EXPORTS = ["hevcdl_config_default", "hevcdl_create", "hevcdl_destroy", "hevcdl_l
            "hevcdl_config_from_stream", "hevcdl_decode_stream",
            "hevcdl_parse_stream_core", "hevcdl_parse_stream_dev", "hevcdl_slice_decode_launches", "hevcdl_enable_device_parse",
            "hevcdl_parse_stream_qp", "hevcdl_parse_stream_core_qp", "hevcdl_parse_stream_dev_qp", "hevcdl_parse_qp_tally", "hevcdl_enable_cu_qp", "hevcdl_deblock_frames_map", "hevcdl_recon_qp_launches", "hevcdl_deblock_qp_launches",
-           "hevcdl_reconstruct_frames_qp", "hevcdl_reconstruct_frames_qp_dev", "hevcdl_reconstruct_frames_qp_host"]
+           "hevcdl_reconstruct_frames_qp", "hevcdl_reconstruct_frames_qp_dev", "hevcdl_reconstruct_frames_qp_host",
+           "hevcdl_parse_stream_sl", "hevcdl_parse_stream_core_sl", "hevcdl_parse_stream_dev_sl", "hevcdl_enable_scaling_lists", "hevcdl_recon_sl_launches",
+           "hevcdl_reconstruct_frames_sl", "hevcdl_reconstruct_frames_sl_dev", "hevcdl_reconstruct_frames_sl_host"]
 
 ACCEPT_CU_QP = 1      # HEVCDL_ACCEPT_CU_QP
+ACCEPT_SCALING_LISTS = 2      # HEVCDL_ACCEPT_SCALING_LISTS
+SCALING_FACTOR_BYTES = 2032      # HEVCDL_SCALING_FACTOR_BYTES
+# where the plane of (component, log2 of the TU size) starts in the factor block: Y 4 8 16 32, Cb 4 8 16, Cr 4 8 16, each in raster order
+SCALING_PLANE_OFFSET = {(0, 2): 0, (0, 3): 16, (0, 4): 80, (0, 5): 336, (1, 2): 1360, (1, 3): 1376, (1, 4): 1440, (2, 2): 1696, (2, 3): 1712, (2, 4): 1776}
 
 
 QP_TALLY_FIELDS = ["groups_with_delta", "groups_without_delta", "deltas_positive", "deltas_negative", "deltas_zero", "max_abs_delta", "deltas_with_suffix",
@@ -525,15 +540,33 @@ class QpInfo(ctypes.Structure):
     _fields_ = [("cu_qp_delta_enabled", ctypes.c_int32), ("diff_cu_qp_delta_depth", ctypes.c_int32), ("cb_qp_offset", ctypes.c_int32), ("cr_qp_offset", ctypes.c_int32)]
 
 
+class ScalingInfo(ctypes.Structure):
+    """hevcdl_scaling_info: the SPS's scaling-list flags and ScalingFactor of H.265 7.4.5 as bytes (SCALING_PLANE_OFFSET says where a plane starts)."""
+    _fields_ = [("enabled", ctypes.c_int32), ("data_present", ctypes.c_int32), ("factor", ctypes.c_uint8 * SCALING_FACTOR_BYTES)]
+
+
+def scaling_info(factors, enabled=1, data_present=1):
+    """A ScalingInfo from SCALING_FACTOR_BYTES factors (any array of that many values 1 .. 255)."""
+    f = np.ascontiguousarray(factors, np.uint8).reshape(-1)
+    if f.size != SCALING_FACTOR_BYTES:
+        raise ValueError("a factor block holds %d bytes" % SCALING_FACTOR_BYTES)
+    s = ScalingInfo(int(enabled), int(data_present))
+    ctypes.memmove(s.factor, f.ctypes.data, SCALING_FACTOR_BYTES)
+    return s
+
+
 class ParsedStream:
     """What parse_stream gives back: cfg (StreamConfig), slices / segments (SliceLayout / SegmentLayout or None, as write_access_unit_from_slice_data takes them),
     pictures (a list of ParsedPicture), records [pictures, ctus] (REC_DTYPE) and sao [pictures, ctus, 3] (SAO_DTYPE; zeros for a picture without SAO).
     With parse_stream(cu_qp=True) also qp_map, int8 [pictures, ctus, 256]: QpY of every 4x4 partition in z-order (0 outside the picture), and qp_info (QpInfo: the PPS's
-    cu_qp_delta_enabled_flag, diff_cu_qp_delta_depth and chroma QP offsets); None otherwise."""
+    cu_qp_delta_enabled_flag, diff_cu_qp_delta_depth and chroma QP offsets); None otherwise.
+    With parse_stream(scaling_lists=True) also the QP map and qp_info, and scaling (ScalingInfo) with scaling_factors, its factor block as a uint8 array
+    [SCALING_FACTOR_BYTES]; None otherwise."""
 
-    def __init__(self, cfg, slices, segments, pictures, records, sao, qp_map=None, qp_info=None):
+    def __init__(self, cfg, slices, segments, pictures, records, sao, qp_map=None, qp_info=None, scaling=None):
         self.cfg, self.slices, self.segments, self.pictures, self.records, self.sao = cfg, slices, segments, pictures, records, sao
-        self.qp_map, self.qp_info = qp_map, qp_info
+        self.qp_map, self.qp_info, self.scaling = qp_map, qp_info, scaling
+        self.scaling_factors = None if scaling is None else np.frombuffer(bytes(scaling.factor), np.uint8).copy()
 
     @property
     def qps(self):
@@ -545,16 +578,20 @@ class ParsedStream:
         return p.hash_method, bytes(p.digest[:3 * p.hash_plane_bytes])
 
 
-def parse_stream(stream, headers_only=False, engine="host", device=0, cu_qp=False):
+def parse_stream(stream, headers_only=False, engine="host", device=0, cu_qp=False, scaling_lists=False):
     """hevcdl_parse_stream (host only, no GPU): an Annex-B stream of this library's writer, or of the reference encoder in the same configuration -> a ParsedStream.
     engine: who decodes the slice data -- "host" the parser's own decoder, "core" the shared decoder csrc/slice_decode_core.h on the CPU (hevcdl_parse_stream_core),
     "device" the same source in hevcdl_slice_decode_kernel on `device` (hevcdl_parse_stream_dev).  The headers are the parser's in all three.
     cu_qp: accept cu_qp_delta_enabled_flag and PPS chroma QP offsets (the hevcdl_parse_stream*_qp entry points with HEVCDL_ACCEPT_CU_QP) and return the QP map and
     the PPS fields with the rest; without it such a stream is refused as ever.
+    scaling_lists: accept scaling_list_enabled_flag in the SPS (the hevcdl_parse_stream*_sl entry points with HEVCDL_ACCEPT_SCALING_LISTS) and return the flags and the
+    factor block (ParsedStream.scaling, .scaling_factors) with the QP map; without it such a stream is refused as ever.
     HevcdlError carries the status (1: a damaged stream, 2: a feature outside the decoder) and the parser's sentence."""
     lib = load_library()
     if engine not in ("host", "core", "device"):
         raise ValueError("engine is \"host\", \"core\" or \"device\"")
+    if scaling_lists:
+        return _parse_stream_sl(lib, stream, headers_only, engine, device, (ACCEPT_CU_QP if cu_qp else 0) | ACCEPT_SCALING_LISTS)
     if cu_qp:
         return _parse_stream_qp(lib, stream, headers_only, engine, device)
     if engine == "core":
@@ -606,16 +643,42 @@ def _parse_stream_qp(lib, stream, headers_only, engine, device):
     return ParsedStream(cfg, sl if sl.mode else None, sg if sg.mode else None, list(pics), records, sao, qp_map, info)
 
 
-def decode_stream(stream, device=0, batch=64, device_parse=False, cu_qp=False):
+def _parse_stream_sl(lib, stream, headers_only, engine, device, accept):
+    fn = {"host": lib.hevcdl_parse_stream_sl, "core": lib.hevcdl_parse_stream_core_sl, "device": lambda *a: lib.hevcdl_parse_stream_dev_sl(int(device), *a)}[engine]
+    name = {"host": "hevcdl_parse_stream_sl: ", "core": "hevcdl_parse_stream_core_sl: ", "device": "hevcdl_parse_stream_dev_sl: "}[engine]
+    buf = np.frombuffer(bytes(stream), np.uint8)
+    cfg = StreamConfig()
+    cfg.struct_size = ctypes.sizeof(StreamConfig)
+    sl, sg, n, info, sc = SliceLayout(), SegmentLayout(), ctypes.c_int(0), QpInfo(), ScalingInfo()
+
+    def check(st, who):
+        if st != 0:
+            raise HevcdlError(st, who + lib.hevcdl_parse_error().decode())
+    check(lib.hevcdl_parse_stream_sl(buf.ctypes.data, buf.size, accept, ctypes.byref(cfg), ctypes.byref(sl), ctypes.byref(sg), None, 0, ctypes.byref(n), None, None, 0, ctypes.byref(info), None,
+                                     ctypes.byref(sc)), "hevcdl_parse_stream_sl: ")
+    ctus = ((cfg.width + 63) // 64) * ((cfg.height + 63) // 64)
+    pics = (ParsedPicture * n.value)()
+    records = None if headers_only else np.zeros((n.value, ctus), REC_DTYPE)
+    sao = None if headers_only else np.zeros((n.value, ctus, 3), SAO_DTYPE)
+    qp_map = None if headers_only else np.zeros((n.value, ctus, 256), np.int8)
+    check(fn(buf.ctypes.data, buf.size, accept, ctypes.byref(cfg), ctypes.byref(sl), ctypes.byref(sg), pics, n.value, ctypes.byref(n),
+             None if headers_only else records.ctypes.data, None if headers_only else sao.ctypes.data, 0 if headers_only else n.value * ctus, ctypes.byref(info),
+             None if headers_only else qp_map.ctypes.data, ctypes.byref(sc)), name)
+    return ParsedStream(cfg, sl if sl.mode else None, sg if sg.mode else None, list(pics), records, sao, qp_map, info, sc)
+
+
+def decode_stream(stream, device=0, batch=64, device_parse=False, cu_qp=False, scaling_lists=False):
     """hevcdl_decode_stream on a context made for the stream (hevcdl_config_from_stream): parsed on the host -- with device_parse the headers only, the slice data by
     hevcdl_slice_decode_kernel (hevcdl_enable_device_parse) --; reconstruction, deblocking, SAO and the digests on the
     device, `batch` pictures at a time in HBM.  -> (pictures [n, w * h * 3 / 2] in coded format, uint16 at 10 bits; the stream's StreamConfig, whose conf_win_* say what
     to show; the pictures' ParsedPicture list; verdicts [n]: True / False where the device's digest was compared with a hash SEI, None where the stream carries none).
     cu_qp: hevcdl_enable_cu_qp on the context -- streams with cu_qp_delta_enabled_flag or PPS chroma QP offsets are decoded (the QP map in HBM beside the records, the QP-map
     instantiations of the reconstruction and the deblocking kernel); off, they are refused as ever.
+    scaling_lists: hevcdl_enable_scaling_lists on the context -- streams whose SPS enables scaling lists are decoded (the factor block in HBM, the scaling-list instantiation
+    of the reconstruction kernel); off, they are refused as ever.
     HevcdlError carries the status and the decoder's sentence."""
     lib = load_library()
-    head = parse_stream(stream, headers_only=True, cu_qp=cu_qp)
+    head = parse_stream(stream, headers_only=True, cu_qp=cu_qp, scaling_lists=scaling_lists)
     n = len(head.pictures)
     cfg = Config()
     st = lib.hevcdl_config_from_stream(ctypes.byref(head.cfg), _layout_ptr(head.slices), max(1, min(int(batch), n)), int(device), ctypes.byref(cfg))
@@ -631,6 +694,10 @@ def decode_stream(stream, device=0, batch=64, device_parse=False, cu_qp=False):
             st = lib.hevcdl_enable_cu_qp(h, 1)
             if st:
                 raise HevcdlError(st, "hevcdl_enable_cu_qp: " + (lib.hevcdl_last_error(h) or b"").decode())
+        if scaling_lists:
+            st = lib.hevcdl_enable_scaling_lists(h, 1)
+            if st:
+                raise HevcdlError(st, "hevcdl_enable_scaling_lists: " + (lib.hevcdl_last_error(h) or b"").decode())
         if device_parse:
             st = lib.hevcdl_enable_device_parse(h, 1)
             if st:
@@ -648,11 +715,11 @@ def decode_stream(stream, device=0, batch=64, device_parse=False, cu_qp=False):
 
 class StreamDecoder:
     """A decoder context made for a stream (hevcdl_config_from_stream of its headers) that stays open over several hevcdl_decode_stream calls: the switches
-    (hevcdl_enable_cu_qp, hevcdl_enable_device_parse) can be turned between them.  `like`: a stream whose headers describe the streams to come."""
+    (hevcdl_enable_cu_qp, hevcdl_enable_scaling_lists, hevcdl_enable_device_parse) can be turned between them.  `like`: a stream whose headers describe the streams to come."""
 
     def __init__(self, like, device=0, batch=64):
         self.lib = load_library()
-        head = parse_stream(like, headers_only=True, cu_qp=True)
+        head = parse_stream(like, headers_only=True, cu_qp=True, scaling_lists=True)
         self.head, self.h = head, ctypes.c_void_p()
         cfg = Config()
         st = self.lib.hevcdl_config_from_stream(ctypes.byref(head.cfg), _layout_ptr(head.slices), max(1, int(batch)), int(device), ctypes.byref(cfg))
@@ -670,6 +737,9 @@ class StreamDecoder:
     def enable_cu_qp(self, on=True):
         self._check(self.lib.hevcdl_enable_cu_qp(self.h, int(bool(on))), "hevcdl_enable_cu_qp")
 
+    def enable_scaling_lists(self, on=True):
+        self._check(self.lib.hevcdl_enable_scaling_lists(self.h, int(bool(on))), "hevcdl_enable_scaling_lists")
+
     def enable_device_parse(self, on=True):
         self._check(self.lib.hevcdl_enable_device_parse(self.h, int(bool(on))), "hevcdl_enable_device_parse")
 
@@ -677,7 +747,7 @@ class StreamDecoder:
         """-> (pictures [n, w * h * 3 / 2], the pictures' ParsedPicture list, verdicts) as decode_stream gives them; n: room in pictures (the stream's count when None)."""
         c = self.head.cfg
         buf = np.frombuffer(bytes(stream), np.uint8)
-        n = len(parse_stream(stream, headers_only=True, cu_qp=True).pictures) if n is None else int(n)
+        n = len(parse_stream(stream, headers_only=True, cu_qp=True, scaling_lists=True).pictures) if n is None else int(n)
         pictures = np.zeros((n, c.width * c.height * 3 // 2), np.uint8 if c.bit_depth == 8 else np.dtype("<u2"))
         info, ok, count = (ParsedPicture * n)(), np.zeros(n, np.int32), ctypes.c_int(0)
         self._check(self.lib.hevcdl_decode_stream(self.h, buf.ctypes.data, buf.size, pictures.ctypes.data, n, ctypes.byref(count), info, ok.ctypes.data), "hevcdl_decode_stream")
@@ -706,23 +776,35 @@ class StreamDecoder:
         self.close()
 
 
-def reconstruct_frames(cfg, records, slices=None, qps=None, device=None, qp_map=None, qp_info=None):
+def reconstruct_frames(cfg, records, slices=None, qps=None, device=None, qp_map=None, qp_info=None, scaling=None):
     """The unfiltered reconstruction of records [pictures, ctus] under cfg (a StreamConfig: size, bit depth, QP, tiles, the strong-intra tool bit) and the slice layout:
     device None: csrc/recon_core.h on the CPU (hevcdl_reconstruct_frames_host, no GPU needed), otherwise hevcdl_recon_kernel on that device.  qps: a QP per picture.
     qp_map [pictures, ctus, 256] int8 with qp_info (a QpInfo; parse_stream(cu_qp=True) gives both): a QP per CU and the PPS chroma offsets -- the
     hevcdl_reconstruct_frames_qp* entry points, the QP-map instantiation of hevcdl_recon_kernel on a device.
+    scaling (a ScalingInfo; parse_stream(scaling_lists=True) gives it with the map and qp_info, which it needs): the factors of H.265 7.4.5 per coefficient -- the
+    hevcdl_reconstruct_frames_sl* entry points, the scaling-list instantiation of the kernel on a device.
     -> [pictures, w * h * 3 / 2] samples (uint8, or uint16 at 10 bits).  HevcdlError carries the status and the sentence."""
     lib = load_library()
     r = np.ascontiguousarray(records, REC_DTYPE)
     r = r.reshape(1, -1) if r.ndim == 1 else r
     n = r.shape[0]
     out = np.zeros((n, cfg.width * cfg.height * 3 // 2), np.uint8 if cfg.bit_depth == 8 else np.dtype("<u2"))
+    if scaling is not None and qp_map is None:
+        raise ValueError("scaling factors go with a QP map and qp_info")
     if qp_map is not None:
         if qps is not None or qp_info is None:
             raise ValueError("a QP map goes with qp_info and without qps")
         m = np.ascontiguousarray(qp_map, np.int8)
         if m.size != r.size * 256:
             raise ValueError("the QP map holds %d values, the records need %d" % (m.size, r.size * 256))
+        if scaling is not None:
+            if device is None:
+                st = lib.hevcdl_reconstruct_frames_sl_host(ctypes.byref(cfg), _layout_ptr(slices), ctypes.byref(qp_info), m.ctypes.data, ctypes.byref(scaling), r.ctypes.data, n, out.ctypes.data)
+            else:
+                st = lib.hevcdl_reconstruct_frames_sl(int(device), ctypes.byref(cfg), _layout_ptr(slices), ctypes.byref(qp_info), m.ctypes.data, ctypes.byref(scaling), r.ctypes.data, n, out.ctypes.data)
+            if st:
+                raise HevcdlError(st, "hevcdl_reconstruct_frames_sl: " + lib.hevcdl_parse_error().decode())
+            return out
         if device is None:
             st = lib.hevcdl_reconstruct_frames_qp_host(ctypes.byref(cfg), _layout_ptr(slices), ctypes.byref(qp_info), m.ctypes.data, r.ctypes.data, n, out.ctypes.data)
         else:

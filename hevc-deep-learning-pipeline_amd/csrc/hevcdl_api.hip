@@ -99,6 +99,8 @@ struct Decoder { DevBuf<unsigned char> d_work; std::vector<uint32_t> keep; };   
 // a QP per CU (hevcdl_enable_cu_qp): the map of a batch in HBM beside the records -- uploaded behind a host parse, written by the kernel with device parse --, allocated
 // by the first stream that needs it.  active / info: the batch in work, read by the deblocking launch (null outside hevcdl_decode_stream and hevcdl_deblock_frames_map)
 struct CuQp { bool on = false; DevBuf<signed char> d_map; const signed char *active = nullptr; hevcdl_qp_info info = { 0, 0, 0, 0 }; };
+// scaling lists (hevcdl_enable_scaling_lists): the factor block of the stream in work in HBM, allocated by the first stream that has lists; such a stream also uses cuqp.d_map
+struct ScalingLists { bool on = false; DevBuf<unsigned char> d_factor; };
 struct DeviceParse {
   bool on = false;
   DevBuf<unsigned char> d_tables, d_rbsp, d_sao; DevBuf<hevcdl_sd::SdSub> d_subs; DevBuf<hevcdl_sd::SdUnit> d_units; DevBuf<hevcdl_sd::SdResult> d_results;
@@ -195,7 +197,7 @@ struct hevcdl_ctx {
   int col_bd[21] = { 0 }, row_bd[23] = { 0 };    // tile boundaries in CTUs
   DevBuf<float> d_weights, d_a3; size_t a3_ctus = 0;   // d_a3: conv3 outputs of one chunk of CTUs (32 KB per CTU): the hand-over from the conv kernel to the head kernel
   DevBuf<int> d_flag;                  // device-side error flag of the label check
-  Staging stage; SaoWorkspace sao; Decoder dec; DeviceParse dp; CuQp cuqp; Quality q; Report rp; Entropy ec; Source src; Session ses; RdWorkspace rd; DbkSelect dbk; QpRd qprd; FrameQp fqp;
+  Staging stage; SaoWorkspace sao; Decoder dec; DeviceParse dp; CuQp cuqp; ScalingLists sclist; Quality q; Report rp; Entropy ec; Source src; Session ses; RdWorkspace rd; DbkSelect dbk; QpRd qprd; FrameQp fqp;
   int ec_capacity_per_ctu = 0;         // hevcdl_set_entropy_capacity (tests): 0 = the default; outlives the entropy switch
   bool profile = false;
   std::vector<Event> ev_cnn, ev_rd, ev_conv;       // start/stop pairs (ev_conv: the convolution kernel alone, one pair per chunk of CTUs)
@@ -1132,6 +1134,14 @@ extern "C" hevcdl_status hevcdl_enable_cu_qp(hevcdl_ctx *ctx, int on)
   return HEVCDL_OK;
 }
 
+extern "C" hevcdl_status hevcdl_enable_scaling_lists(hevcdl_ctx *ctx, int on)
+{
+  if (!ctx) return HEVCDL_ERR_INVALID_ARG;
+  if (!on && ctx->sclist.on) { TRY(sync_or_fail(ctx, "hevcdl_enable_scaling_lists")); ctx->sclist = ScalingLists(); }
+  ctx->sclist.on = on != 0;
+  return HEVCDL_OK;
+}
+
 // ---- per-picture deblocking parameters: DeblockingFilterMetric 1 (dbk_select_kernel.hip, dbk_select.h), TEncGOP::applyDeblockingFilterMetric, called at TEncGOP.cpp:1739 ----
 extern "C" hevcdl_status hevcdl_dbk_metric_frames_dev(hevcdl_ctx *ctx, const void *d_recon, int n_frames, void *d_sums, void *stream)
 {
@@ -1453,11 +1463,14 @@ extern "C" hevcdl_status hevcdl_decode_stream(hevcdl_ctx *ctx, const uint8_t *st
   hevcdl_stream_config sc; memset(&sc, 0, sizeof sc); sc.struct_size = sizeof sc;
   hevcdl_slice_layout sl = { 0, 0, 1 }; hevcdl_segment_layout sg = { 0, 0 };
   int n = 0;
-  const unsigned accept = ctx->cuqp.on ? HEVCDL_ACCEPT_CU_QP : 0u;      // off: every stream is answered as ever
+  const unsigned accept = (ctx->cuqp.on ? HEVCDL_ACCEPT_CU_QP : 0u) | (ctx->sclist.on ? HEVCDL_ACCEPT_SCALING_LISTS : 0u);      // off: every stream is answered as ever
   hevcdl_qp_info qi = { 0, 0, 0, 0 };
-  hevcdl_status st = hevcdl_parse_stream_qp(stream, bytes, accept, &sc, &sl, &sg, nullptr, 0, &n, nullptr, nullptr, 0, &qi, nullptr);
+  hevcdl_scaling_info si; si.enabled = 0;
+  hevcdl_status st = hevcdl_parse_stream_sl(stream, bytes, accept, &sc, &sl, &sg, nullptr, 0, &n, nullptr, nullptr, 0, &qi, nullptr, &si);
   if (st != HEVCDL_OK) return fail(ctx, st, hevcdl_parse_error());
   const bool use_map = qi.cu_qp_delta_enabled || qi.cb_qp_offset || qi.cr_qp_offset;      // a stream without either takes the constant-QP launches, also when enabled
+  const bool use_sl = si.enabled != 0;                                                    // likewise a stream without scaling lists
+  const bool want_map = use_map || use_sl;                                                // the scaling-list instantiation always reads the map (a constant one for a stream of one QP)
   *n_pictures = n;
   { // the context must describe the stream: size, depth and the grid the in-loop filters stop at (tiles, row slices) with its flag
     hevcdl_config want, grid; const char *why = "";
@@ -1486,8 +1499,8 @@ extern "C" hevcdl_status hevcdl_decode_stream(hevcdl_ctx *ctx, const uint8_t *st
       return fail(ctx, su.pending, su.pending_sentence);
     }
   } else {
-    try { pics.resize((size_t)n); recs.resize((size_t)n * ctx->ctus); sao.resize((size_t)n * ctx->ctus); if (use_map) qmap.resize((size_t)n * ctx->ctus * 256); } catch (...) { return fail(ctx, HEVCDL_ERR_OOM, "host memory for the stream's records"); }
-    st = hevcdl_parse_stream_qp(stream, bytes, accept, &sc, &sl, &sg, pics.data(), n, &n, recs.data(), sao.data(), recs.size(), nullptr, use_map ? qmap.data() : nullptr);
+    try { pics.resize((size_t)n); recs.resize((size_t)n * ctx->ctus); sao.resize((size_t)n * ctx->ctus); if (want_map) qmap.resize((size_t)n * ctx->ctus * 256); } catch (...) { return fail(ctx, HEVCDL_ERR_OOM, "host memory for the stream's records"); }
+    st = hevcdl_parse_stream_qp(stream, bytes, accept, &sc, &sl, &sg, pics.data(), n, &n, recs.data(), sao.data(), recs.size(), nullptr, want_map ? qmap.data() : nullptr);
     if (st != HEVCDL_OK) return fail(ctx, st, hevcdl_parse_error());
   }
   TRY(ensure_staging(ctx));
@@ -1498,18 +1511,26 @@ extern "C" hevcdl_status hevcdl_decode_stream(hevcdl_ctx *ctx, const uint8_t *st
   HIPCHK(hipSetDevice(ctx->cfg.device));
   FrameQpGuard guard{ ctx };
   CuQpActive map_guard{ ctx };
-  if (use_map) TRY(ensure_qp_map(ctx));
+  if (want_map) TRY(ensure_qp_map(ctx));
+  if (use_sl) { // the stream's factors: 2 KB, uploaded once, read by every launch of the stream
+    TRY(lazy_alloc(ctx, ctx->sclist.d_factor, (size_t)HEVCDL_SCALING_FACTOR_BYTES, "scaling factors"));
+    HIPCHK(hipMemcpy(ctx->sclist.d_factor, si.factor, HEVCDL_SCALING_FACTOR_BYTES, hipMemcpyHostToDevice));
+  }
   std::vector<int> qps; std::vector<hevcdl_dbk_choice> choices; std::vector<hevcdl_picture_report_t> rep;
   for (int first = 0; first < n; first += ctx->cfg.max_frames) {
     const int cnt = std::min(ctx->cfg.max_frames, n - first);
     qps.resize((size_t)cnt); choices.resize((size_t)cnt); rep.resize((size_t)cnt);
     bool any_sao = false, own_qp = false;
     for (int i = 0; i < cnt; i++) { qps[i] = pics[first + i].qp; choices[i] = pics[first + i].dbk; any_sao |= pics[first + i].sao != 0; own_qp |= qps[i] != ctx->cfg.qp; }
-    if (dev_parse) TRY(device_parse_batch(ctx, su, first, cnt, any_sao, use_map ? ctx->cuqp.d_map.p : nullptr));      // the records into stage.d_records, the SAO blocks into dp.h_sao; an error before anything else is launched
+    if (dev_parse) TRY(device_parse_batch(ctx, su, first, cnt, any_sao, want_map ? ctx->cuqp.d_map.p : nullptr));      // the records into stage.d_records, the SAO blocks into dp.h_sao; an error before anything else is launched
     else HIPCHK(hipMemcpyAsync(ctx->stage.d_records, recs.data() + (size_t)first * ctx->ctus, ctx->records_bytes((size_t)cnt), hipMemcpyHostToDevice, nullptr));
     const uint32_t *d_err = nullptr;
+    if (want_map && !dev_parse) HIPCHK(hipMemcpyAsync(ctx->cuqp.d_map, qmap.data() + (size_t)first * ctx->ctus * 256, (size_t)cnt * ctx->ctus * 256, hipMemcpyHostToDevice, nullptr));
+    if (use_sl) { // scaling lists: the third instantiation of the reconstruction; the deblocking filter reads the map only where the stream has a QP per CU or chroma offsets
+      st = hevcdl_recon_enqueue_sl(&sc, &sl, &qi, ctx->cuqp.d_map, ctx->sclist.d_factor, ctx->stage.d_records, cnt, ctx->stage.d_recon, ctx->dec.d_work, work, nullptr, ctx->dec.keep, &d_err);
+      if (use_map) { ctx->cuqp.active = ctx->cuqp.d_map; ctx->cuqp.info = qi; }
+    } else
     if (use_map) { // the map beside the records: uploaded behind a host parse, written there by the kernel with device parse; the two QP-map instantiations read it
-      if (!dev_parse) HIPCHK(hipMemcpyAsync(ctx->cuqp.d_map, qmap.data() + (size_t)first * ctx->ctus * 256, (size_t)cnt * ctx->ctus * 256, hipMemcpyHostToDevice, nullptr));
       st = hevcdl_recon_enqueue_qp(&sc, &sl, &qi, ctx->cuqp.d_map, ctx->stage.d_records, cnt, ctx->stage.d_recon, ctx->dec.d_work, work, nullptr, ctx->dec.keep, &d_err);
       ctx->cuqp.active = ctx->cuqp.d_map; ctx->cuqp.info = qi;
     } else

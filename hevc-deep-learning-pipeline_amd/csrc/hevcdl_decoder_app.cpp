@@ -58,8 +58,8 @@ int main(int argc, char **argv)
   hevcdl_stream_config sc; memset(&sc, 0, sizeof sc); sc.struct_size = sizeof sc;
   hevcdl_slice_layout sl = { 0, 0, 1 }; hevcdl_segment_layout sg = { 0, 0 };
   int n = 0;
-  // a QP per CU and PPS chroma QP offsets are always accepted here (hevcdl_enable_cu_qp below); the picture line shows the slice QP
-  hevcdl_status st = hevcdl_parse_stream_qp(stream.data(), stream.size(), HEVCDL_ACCEPT_CU_QP, &sc, &sl, &sg, nullptr, 0, &n, nullptr, nullptr, 0, nullptr, nullptr);
+  // a QP per CU, PPS chroma QP offsets and scaling lists are always accepted here (hevcdl_enable_cu_qp, hevcdl_enable_scaling_lists below); the picture line shows the slice QP
+  hevcdl_status st = hevcdl_parse_stream_sl(stream.data(), stream.size(), HEVCDL_ACCEPT_CU_QP | HEVCDL_ACCEPT_SCALING_LISTS, &sc, &sl, &sg, nullptr, 0, &n, nullptr, nullptr, 0, nullptr, nullptr, nullptr);
   if (st != HEVCDL_OK) { fprintf(stderr, "Error: %s (status %d)\n", hevcdl_parse_error(), (int)st); return 2; }
   hevcdl_config cfg;
   if (hevcdl_config_from_stream(&sc, &sl, n < batch ? n : batch, device, &cfg) != HEVCDL_OK) { fprintf(stderr, "Error: no context configuration for this stream\n"); return 2; }
@@ -68,6 +68,7 @@ int main(int argc, char **argv)
   st = hevcdl_create(&cfg, weights.data(), weights.size(), &ctx);
   if (st != HEVCDL_OK) { fprintf(stderr, "Error: hevcdl_create: status %d %s\n", (int)st, hevcdl_create_error()); return 2; }
   if ((st = hevcdl_enable_cu_qp(ctx, 1)) != HEVCDL_OK) { fprintf(stderr, "Error: %s (status %d)\n", hevcdl_last_error(ctx), (int)st); hevcdl_destroy(ctx); return 2; }
+  if ((st = hevcdl_enable_scaling_lists(ctx, 1)) != HEVCDL_OK) { fprintf(stderr, "Error: %s (status %d)\n", hevcdl_last_error(ctx), (int)st); hevcdl_destroy(ctx); return 2; }
   if (device_parse && (st = hevcdl_enable_device_parse(ctx, 1)) != HEVCDL_OK) { fprintf(stderr, "Error: %s (status %d)\n", hevcdl_last_error(ctx), (int)st); hevcdl_destroy(ctx); return 2; }
   const size_t fb = hevcdl_frame_bytes_bd(sc.width, sc.height, sc.bit_depth);
   std::vector<unsigned char> pictures(fb * (size_t)n);

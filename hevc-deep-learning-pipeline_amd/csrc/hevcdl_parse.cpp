@@ -100,7 +100,84 @@ void profile_tier_level(BitIn &r, int &level_idc)
   level_idc = (int)r.u(8);
 }
 
-hevcdl_status parse_sps(const Nal &n, ParamSets &ps)
+// ---- scaling lists (7.3.4, 7.4.5) ----------------------------------------------------------------------------------------------
+// Table 7-6 in the order it is coded in (up-right diagonal); Table 7-5 is 16 everywhere
+const uint8_t SL_DEFAULT_INTRA[64] = { 16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 17, 16, 17, 16, 17, 18, 17, 18, 18, 17, 18, 21, 19, 20, 21, 20, 19, 21, 24, 22, 22, 24,
+                                       24, 22, 22, 24, 25, 25, 27, 30, 27, 25, 25, 29, 31, 35, 35, 31, 29, 36, 41, 44, 41, 36, 47, 54, 54, 47, 65, 70, 65, 88, 88, 115 };
+const uint8_t SL_DEFAULT_INTER[64] = { 16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 17, 17, 17, 17, 17, 18, 18, 18, 18, 18, 18, 20, 20, 20, 20, 20, 20, 20, 24, 24, 24, 24,
+                                       24, 24, 24, 24, 25, 25, 25, 25, 25, 25, 25, 28, 28, 28, 28, 28, 28, 33, 33, 33, 33, 33, 41, 41, 41, 41, 54, 54, 54, 71, 71, 91 };
+struct ScalingLists { uint8_t list[4][6][64]; int dc[4][6]; };      // [sizeId][matrixId] in coded order; dc: the DC entry of sizeId 2 and 3
+
+void sl_default(ScalingLists &s, int size_id, int m)
+{
+  for (int i = 0; i < 64; i++) s.list[size_id][m][i] = size_id == 0 ? 16 : (m < 3 ? SL_DEFAULT_INTRA[i] : SL_DEFAULT_INTER[i]);
+  s.dc[size_id][m] = 16;
+}
+// ScanOrder[log2][0] of 6.5.3: position i of the up-right diagonal scan of a block of n x n -> raster index y * n + x
+void sl_diag(int n, uint8_t *raster)
+{
+  int i = 0, x = 0, y = 0;
+  while (i < n * n) {
+    while (y >= 0) { if (x < n && y < n) raster[i++] = (uint8_t)(y * n + x); y--; x++; }
+    y = x; x = 0;
+  }
+}
+// ScalingFactor of 7.4.5 for the planes 4:2:0 has, raster order: Y 4 8 16 32, Cb 4 8 16, Cr 4 8 16 (hevcdl_scaling_info).  The inter lists (matrixId 3 .. 5) are dropped here
+void sl_expand(const ScalingLists &s, uint8_t *f)
+{
+  uint8_t d4[16], d8[64];
+  sl_diag(4, d4); sl_diag(8, d8);
+  for (int c = 0; c < 3; c++) {
+    uint8_t *o = f + (c == 0 ? 0 : 1360 + (c - 1) * 336);
+    for (int i = 0; i < 16; i++) o[d4[i]] = s.list[0][c][i];
+    for (int i = 0; i < 64; i++) o[16 + d8[i]] = s.list[1][c][i];
+    for (int size_id = 2; size_id < (c == 0 ? 4 : 3); size_id++) {
+      const int m = size_id == 3 ? 0 : c, n = 4 << size_id, rep = n >> 3;
+      uint8_t *b = o + (size_id == 2 ? 80 : 336);
+      for (int i = 0; i < 64; i++) {
+        const int x8 = d8[i] & 7, y8 = d8[i] >> 3;
+        for (int j = 0; j < rep; j++) for (int k = 0; k < rep; k++) b[(y8 * rep + j) * n + x8 * rep + k] = s.list[size_id][m][i];
+      }
+      b[0] = (uint8_t)s.dc[size_id][m];
+    }
+  }
+}
+// scaling_list_data() 7.3.4 as the reference writes it: for sizeId 3 only matrixId 0 and 3, scaling_list_pred_matrix_id_delta counting in steps of 3
+hevcdl_status parse_scaling_list_data(BitIn &r, ScalingLists &s)
+{
+  for (int size_id = 0; size_id < 4; size_id++) {
+    const int step = size_id == 3 ? 3 : 1, num = size_id == 0 ? 16 : 64;
+    for (int m = 0; m < 6; m += step) {
+      if (!r.u(1)) { // scaling_list_pred_mode_flag 0: the default list, or a copy of an earlier one
+        const uint32_t delta = r.ue();
+        if (r.bad) INVALID("the SPS ends inside its scaling lists");
+        if (delta > (uint32_t)(m / step)) INVALID("scaling_list_pred_matrix_id_delta %u of list %d of size %d", delta, m, size_id);
+        if (delta == 0) sl_default(s, size_id, m);
+        else { const int ref = m - (int)delta * step; memcpy(s.list[size_id][m], s.list[size_id][ref], 64); s.dc[size_id][m] = s.dc[size_id][ref]; }
+        continue;
+      }
+      int next = 8;
+      s.dc[size_id][m] = 16;
+      if (size_id > 1) {
+        const int dc = r.se();
+        if (r.bad) INVALID("the SPS ends inside its scaling lists");
+        if (dc < -7 || dc > 247) INVALID("scaling_list_dc_coef_minus8 %d of list %d of size %d", dc, m, size_id);
+        next = dc + 8; s.dc[size_id][m] = next;
+      }
+      for (int i = 0; i < num; i++) {
+        const int d = r.se();
+        if (r.bad) INVALID("the SPS ends inside its scaling lists");
+        if (d < -128 || d > 127) INVALID("scaling_list_delta_coef %d of list %d of size %d", d, m, size_id);
+        next = (next + d + 256) % 256;
+        if (next == 0) INVALID("entry %d of scaling list %d of size %d is 0", i, m, size_id);
+        s.list[size_id][m][i] = (uint8_t)next;
+      }
+    }
+  }
+  return HEVCDL_OK;
+}
+
+hevcdl_status parse_sps(const Nal &n, ParamSets &ps, unsigned accept)
 {
   BitIn r(n.rbsp.data(), n.rbsp.size());
   r.u(4); const int max_sub = (int)r.u(3); r.u(1);
@@ -133,7 +210,15 @@ hevcdl_status parse_sps(const Nal &n, ParamSets &ps)
   if (r.bad) INVALID("the SPS ends inside its block sizes");
   if (min_cb != 0 || diff_cb != 3 || min_tb != 0 || diff_tb != 3 || td_intra != 2)
     UNSUPPORTED("block sizes of the SPS: only CTU 64, minimum CB 8, TU 4..32 and intra TU depth 3 are decoded");
-  if (r.u(1)) UNSUPPORTED("scaling lists are outside this decoder");
+  ps.sl_enabled = ps.sl_data_present = 0; memset(ps.sl_factor, 0, sizeof ps.sl_factor);
+  if (r.u(1)) { // scaling_list_enabled_flag: the default lists, or sps_scaling_list_data_present_flag and scaling_list_data()
+    if (!(accept & HEVCDL_ACCEPT_SCALING_LISTS)) UNSUPPORTED("scaling lists are outside this decoder");
+    ScalingLists s;
+    for (int size_id = 0; size_id < 4; size_id++) for (int m = 0; m < 6; m++) sl_default(s, size_id, m);
+    ps.sl_enabled = 1; ps.sl_data_present = (int)r.u(1);
+    if (ps.sl_data_present) { const hevcdl_status st = parse_scaling_list_data(r, s); if (st != HEVCDL_OK) return st; }
+    sl_expand(s, ps.sl_factor);
+  }
   r.u(1);                                            // amp_enabled_flag: nothing in an I slice
   ps.sao = (int)r.u(1);
   if (r.u(1)) UNSUPPORTED("PCM is outside this decoder");
@@ -811,9 +896,16 @@ static void fill_qp_info(const ParamSets &ps, hevcdl_qp_info *q)
   q->cu_qp_delta_enabled = ps.cu_qp_delta; q->diff_cu_qp_delta_depth = ps.diff_cu_qp_depth; q->cb_qp_offset = ps.cb_qp_offset; q->cr_qp_offset = ps.cr_qp_offset;
 }
 
-extern "C" hevcdl_status hevcdl_parse_stream_qp(const uint8_t *stream, size_t bytes, unsigned accept, hevcdl_stream_config *cfg, hevcdl_slice_layout *slices, hevcdl_segment_layout *segments,
+static void fill_scaling_info(const ParamSets &ps, hevcdl_scaling_info *s)
+{
+  if (!s) return;
+  s->enabled = ps.sl_enabled; s->data_present = ps.sl_data_present;
+  if (ps.sl_enabled) memcpy(s->factor, ps.sl_factor, sizeof s->factor); else memset(s->factor, 16, sizeof s->factor);
+}
+
+extern "C" hevcdl_status hevcdl_parse_stream_sl(const uint8_t *stream, size_t bytes, unsigned accept, hevcdl_stream_config *cfg, hevcdl_slice_layout *slices, hevcdl_segment_layout *segments,
                                                hevcdl_parsed_picture *pictures, int picture_capacity, int *n_pictures, hevcdl_ctu_record *records, hevcdl_sao_blk *sao,
-                                               size_t ctu_capacity, hevcdl_qp_info *qp_info, int8_t *qp_map)
+                                               size_t ctu_capacity, hevcdl_qp_info *qp_info, int8_t *qp_map, hevcdl_scaling_info *scaling)
 {
   memset(&g_tally, 0, sizeof g_tally);
   set_error("%s", "");
@@ -870,7 +962,7 @@ extern "C" hevcdl_status hevcdl_parse_stream_qp(const uint8_t *stream, size_t by
     if (nal.type == 32) { st = close_picture(); if (st != HEVCDL_OK) return st; continue; }      // VPS: nothing a picture depends on
     if (nal.type == 33 || nal.type == 34) {
       st = close_picture(); if (st != HEVCDL_OK) return st;
-      st = nal.type == 33 ? parse_sps(nal, ps) : parse_pps(nal, ps, accept);
+      st = nal.type == 33 ? parse_sps(nal, ps, accept) : parse_pps(nal, ps, accept);
       if (st != HEVCDL_OK) return st;
       if (nal.type == 33) level_idc = ps.level_idc;
       if (count == 1) ps_before_second = 1;
@@ -930,11 +1022,18 @@ extern "C" hevcdl_status hevcdl_parse_stream_qp(const uint8_t *stream, size_t by
   c.conf_win_left = active.conf_left; c.conf_win_right = active.conf_right; c.conf_win_top = active.conf_top; c.conf_win_bottom = active.conf_bottom;
   c.qp = first_qp;                                   // the first picture's: a stream of one QP is then described by the configuration alone
   *cfg = c;
-  fill_qp_info(active, qp_info);
+  fill_qp_info(active, qp_info); fill_scaling_info(active, scaling);
   if (slices) *slices = sl;
   if (segments) *segments = sg;
   if (pictures && count > picture_capacity) INVALID("room for %d pictures, the stream holds %d", picture_capacity, count);
   return HEVCDL_OK;
+}
+
+extern "C" hevcdl_status hevcdl_parse_stream_qp(const uint8_t *stream, size_t bytes, unsigned accept, hevcdl_stream_config *cfg, hevcdl_slice_layout *slices, hevcdl_segment_layout *segments,
+                                               hevcdl_parsed_picture *pictures, int picture_capacity, int *n_pictures, hevcdl_ctu_record *records, hevcdl_sao_blk *sao,
+                                               size_t ctu_capacity, hevcdl_qp_info *qp_info, int8_t *qp_map)
+{
+  return hevcdl_parse_stream_sl(stream, bytes, accept, cfg, slices, segments, pictures, picture_capacity, n_pictures, records, sao, ctu_capacity, qp_info, qp_map, nullptr);
 }
 
 extern "C" void hevcdl_parse_qp_tally(hevcdl_qp_tally *out) { if (out) *out = g_tally; }
@@ -1110,7 +1209,7 @@ hevcdl_status collect_loop(const uint8_t *stream, size_t bytes, int want_slice_d
     if (nal.type == 32) { st = close_picture(); if (st != HEVCDL_OK) return st; continue; }
     if (nal.type == 33 || nal.type == 34) {
       st = close_picture(); if (st != HEVCDL_OK) return st;
-      st = nal.type == 33 ? parse_sps(nal, ps) : parse_pps(nal, ps, accept);
+      st = nal.type == 33 ? parse_sps(nal, ps, accept) : parse_pps(nal, ps, accept);
       if (st != HEVCDL_OK) return st;
       if (nal.type == 33) level_idc = ps.level_idc;
       if (count == 1) ps_before_second = 1;
@@ -1168,7 +1267,7 @@ hevcdl_status collect_loop(const uint8_t *stream, size_t bytes, int want_slice_d
   c.wavefront = active.wpp;
   c.conf_win_left = active.conf_left; c.conf_win_right = active.conf_right; c.conf_win_top = active.conf_top; c.conf_win_bottom = active.conf_bottom;
   c.qp = first_qp;
-  out.cfg = c; out.slices = sl; out.segments = sg; fill_qp_info(active, &out.qp);
+  out.cfg = c; out.slices = sl; out.segments = sg; fill_qp_info(active, &out.qp); fill_scaling_info(active, &out.sl);
   return HEVCDL_OK;
 }
 
@@ -1222,7 +1321,7 @@ hevcdl_status batch_tables(const StreamUnits &su, int first, int count, std::vec
 
 hevcdl_status parse_stream_with(UnitWalker walk, void *user, const uint8_t *stream, size_t bytes, hevcdl_stream_config *cfg, hevcdl_slice_layout *slices, hevcdl_segment_layout *segments,
                                 hevcdl_parsed_picture *pictures, int picture_capacity, int *n_pictures, hevcdl_ctu_record *records, hevcdl_sao_blk *sao, size_t ctu_capacity,
-                                unsigned accept, hevcdl_qp_info *qp_info, int8_t *qp_map)
+                                unsigned accept, hevcdl_qp_info *qp_info, int8_t *qp_map, hevcdl_scaling_info *scaling)
 {
   set_error("%s", "");
   if (n_pictures) *n_pictures = 0;
@@ -1243,6 +1342,7 @@ hevcdl_status parse_stream_with(UnitWalker walk, void *user, const uint8_t *stre
   *n_pictures = count;
   *cfg = su.cfg;
   if (qp_info) *qp_info = su.qp;
+  if (scaling) *scaling = su.sl;
   if (slices) *slices = su.slices;
   if (segments) *segments = su.segments;
   if (pictures && count > picture_capacity) INVALID("room for %d pictures, the stream holds %d", picture_capacity, count);
@@ -1262,4 +1362,11 @@ extern "C" hevcdl_status hevcdl_parse_stream_core_qp(const uint8_t *stream, size
                                                     size_t ctu_capacity, hevcdl_qp_info *qp_info, int8_t *qp_map)
 {
   return parse_stream_with(walk_units_host, nullptr, stream, bytes, cfg, slices, segments, pictures, picture_capacity, n_pictures, records, sao, ctu_capacity, accept, qp_info, qp_map);
+}
+
+extern "C" hevcdl_status hevcdl_parse_stream_core_sl(const uint8_t *stream, size_t bytes, unsigned accept, hevcdl_stream_config *cfg, hevcdl_slice_layout *slices, hevcdl_segment_layout *segments,
+                                                    hevcdl_parsed_picture *pictures, int picture_capacity, int *n_pictures, hevcdl_ctu_record *records, hevcdl_sao_blk *sao,
+                                                    size_t ctu_capacity, hevcdl_qp_info *qp_info, int8_t *qp_map, hevcdl_scaling_info *scaling)
+{
+  return parse_stream_with(walk_units_host, nullptr, stream, bytes, cfg, slices, segments, pictures, picture_capacity, n_pictures, records, sao, ctu_capacity, accept, qp_info, qp_map, scaling);
 }

@@ -11,6 +11,7 @@
 //   tskip[3]                    transform_skip_flag at the first partition of a 4x4 block that has one in the stream (a 4x4 chroma block: at the first of its four partitions)
 //   coeff_y, coeff_cb, coeff_cr the levels, hidden signs resolved
 // bits, dist and cost are 0: a stream does not carry the encoder's statistics.
+// Scaling lists (HEVCDL_ACCEPT_SCALING_LISTS, hevcdl_parse_stream_sl) change no record either: the factors are one block of the stream, hevcdl_scaling_info.
 // QpY is NOT a field of the record: with HEVCDL_ACCEPT_CU_QP (hevcdl_parse_stream_qp) it goes into a map beside the records, int8 [pictures][ctus][256] in z-order.
 #ifndef HEVCDL_PARSE_H
 #define HEVCDL_PARSE_H
@@ -31,6 +32,8 @@ struct ParamSets {
   int col_width[MAX_TILE_COLS], row_height[MAX_TILE_ROWS];
   int dbk_control, dbk_override_enabled, dbk_disabled, beta_div2, tc_div2;
   int cu_qp_delta, diff_cu_qp_depth, cb_qp_offset, cr_qp_offset;      // all 0 unless the caller accepts them (HEVCDL_ACCEPT_CU_QP)
+  // scaling lists of the SPS (HEVCDL_ACCEPT_SCALING_LISTS, else all 0): the flags and, with sl_enabled, ScalingFactor of 7.4.5 in the layout of hevcdl_scaling_info
+  int sl_enabled, sl_data_present; uint8_t sl_factor[HEVCDL_SCALING_FACTOR_BYTES];
 };
 
 // one slice segment header

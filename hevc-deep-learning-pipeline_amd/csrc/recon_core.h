@@ -1,7 +1,7 @@
 // recon_core.h -- the unfiltered reconstruction of an intra picture from CTU records, as ONE source for the device (recon_kernel.hip: a wave per CTU row, lanes over
 // samples) and for the host (the same functions with one "lane": hevcdl_reconstruct_frames_host, the CPU net of the kernel's arithmetic and index logic).
 // Restated from ITU-T H.265: 6.4.1 (availability, for the neighbours a reference line touches), 8.4.4.2.2 (reference samples and their substitution), 8.4.4.2.3 ([1 2 1] and
-// strong smoothing), 8.4.4.2.4-6 (planar, DC, angular with the DC and edge filters), 8.6.2 / 8.6.3 (chroma QP, flat dequantisation), 8.6.4 (transform skip, DST, DCT),
+// strong smoothing), 8.4.4.2.4-6 (planar, DC, angular with the DC and edge filters), 8.6.2 / 8.6.3 (chroma QP, dequantisation: flat, or with the scaling factors of 7.4.5), 8.6.4 (transform skip, DST, DCT),
 // 8.6.7 (clipping).  Integer arithmetic throughout: nothing carries a tolerance.  rd_kernel.hip is not included and not touched.
 //
 // Construction rules, as for the entropy coder: no recursion (the two quadtrees are walked in z-order over the 256 partitions of a CTU), no allocation, every loop
@@ -38,6 +38,11 @@ struct RcPic {
 struct RcPicQp : RcPic {
   const int8_t *qp_map;          // [ctus][256] QpY of every 4x4 partition in z-order
   int cb_off, cr_off;            // pps_cb_qp_offset, pps_cr_qp_offset
+};
+// The same picture with scaling lists on top of the QP map (hevcdl_parse_stream_sl): the third instantiation.  factor: the 2032 bytes of hevcdl_scaling_info -- ScalingFactor
+// of 7.4.5 in raster order, Y 4 8 16 32, Cb 4 8 16, Cr 4 8 16.  It always has the map: a stream of one QP has a constant one.
+struct RcPicSl : RcPicQp {
+  const uint8_t *factor;
 };
 // the working set of one wave (LDS on the device)
 struct RcWork {
@@ -120,6 +125,16 @@ RC_FN int rc_block_qp(const RcPicQp &p, int comp, int qpy)
   if (!comp) return qpy + off;
   return rc_chroma_qp(rc_clip(qpy + (comp == 1 ? p.cb_off : p.cr_off), -off, 57)) + off;
 }
+
+// m[x][y] of 8.6.4.2 for the coefficients of a block: the flat 16 folded into `flat` = 16 * levelScale << (qP / 6) as it ever was, or the block's plane of factors
+RC_FN const uint8_t *rc_factors(const RcPic &, int, int) { return nullptr; }
+RC_FN const uint8_t *rc_factors(const RcPicSl &p, int comp, int log2n)
+{
+  const int at[4] = { 0, 16, 80, 336 };
+  return p.factor + (comp ? 1360 + (comp - 1) * 336 : 0) + at[comp && log2n > 4 ? 2 : log2n - 2];      // (a chroma block of 32 does not exist in 4:2:0)
+}
+RC_FN int64_t rc_coef_scale(const RcPic &, const uint8_t *, int, int64_t flat) { return flat; }
+RC_FN int64_t rc_coef_scale(const RcPicSl &, const uint8_t *m, int i, int64_t flat) { return (flat >> 4) * (int64_t)m[i]; }
 
 // One transform block: prediction from the reconstructed neighbours in the picture, residual from the levels, sum, clip, store.  (x, y): the block's position in samples
 // of its component; lx, ly: the same in luma samples; n = 1 << log2n.
@@ -228,8 +243,9 @@ RC_FN void rc_block(const PIC &p, RcWork &w, int lane, int nl, int comp, int lx,
     const int ls[6] = { 40, 45, 51, 57, 64, 72 };
     const int64_t scale = (int64_t)(16 * ls[qp % 6]) << (qp / 6);
     const int bds = bd + log2n - 5, sh2 = 20 - bd;
+    const uint8_t *m = rc_factors(p, comp, log2n);                                               // (consecutive lanes read consecutive bytes of a 2 KB table)
     for (int i = lane; i < nn; i += nl) {
-      const int64_t d = ((int64_t)lvl[i] * scale + ((int64_t)1 << (bds - 1))) >> bds;
+      const int64_t d = ((int64_t)lvl[i] * rc_coef_scale(p, m, i, scale) + ((int64_t)1 << (bds - 1))) >> bds;
       w.tmp[i] = (int32_t)(d < -32768 ? -32768 : (d > 32767 ? 32767 : d));
     }
     RC_SYNC();

@@ -38,6 +38,11 @@ struct RcLaunchQp {              // RcLaunch with a QP map instead of per-pictur
   RcPicQp pic; uint32_t *sync; size_t frame_bytes; int n_frames, ctus;
 };
 
+struct RcLaunchSl {              // RcLaunchQp with the scaling factors: pic.factor is the stream's block, the same for every picture
+  RcPicSl pic; uint32_t *sync; size_t frame_bytes; int n_frames, ctus;
+};
+
+// LAUNCH RcLaunchSl: the instantiation with scaling lists on top of the QP map (recon_core.h: RcPicSl); the factors are read from HBM where a block is dequantised.
 // LAUNCH RcLaunch: the constant-QP form, as it ever was.  LAUNCH RcLaunchQp: the instantiation with a QP per CU and the PPS chroma offsets (recon_core.h: RcPicQp)
 template <typename PEL, typename LAUNCH = RcLaunch>
 __global__ __launch_bounds__(64) void hevcdl_recon_kernel(LAUNCH L)
@@ -326,6 +331,122 @@ extern "C" hevcdl_status hevcdl_reconstruct_frames_qp(int device, const hevcdl_s
     (void)hipGetLastError(); hevcdl_parse::set_error("upload failed"); st = HEVCDL_ERR_HIP;
   }
   if (st == HEVCDL_OK) st = hevcdl_reconstruct_frames_qp_dev(device, cfg, slices_opt, qp_info, d + b_rec + b_pic, d, n_frames, d + b_rec, nullptr);
+  if (st == HEVCDL_OK && hipMemcpy(recon, d + b_rec, b_pic, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); hevcdl_parse::set_error("download failed"); st = HEVCDL_ERR_HIP; }
+  (void)hipFree(d);
+  return st;
+}
+
+// ---- the same entry points with scaling factors on top of the QP map (hevcdl_parse_stream_sl): the scaling-list instantiation of hevcdl_recon_kernel -------------------------------------------
+namespace {
+std::atomic<unsigned long long> g_sl_launches{0};
+hevcdl_status rc_check_scaling(const hevcdl_scaling_info *s)
+{
+  if (!s) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "null hevcdl_scaling_info");
+  for (int i = 0; i < HEVCDL_SCALING_FACTOR_BYTES; i++) if (!s->factor[i]) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "scaling factor %d is 0", i);
+  return HEVCDL_OK;
+}
+} // namespace
+
+extern "C" unsigned long long hevcdl_recon_sl_launches(void) { return g_sl_launches.load(); }
+
+extern "C" hevcdl_status hevcdl_reconstruct_frames_sl_host(const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const hevcdl_qp_info *qp_info,
+                                                          const int8_t *qp_map, const hevcdl_scaling_info *scaling, const hevcdl_ctu_record *records, int n_frames, void *recon)
+{
+  RcPicSl p; std::vector<uint32_t> unit;
+  hevcdl_status st = rc_setup(cfg, slices_opt, p, unit);
+  if (st != HEVCDL_OK) return st;
+  if (!records || !recon || n_frames < 0) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "null records or pictures");
+  if ((st = rc_check_qp_info(qp_info, qp_map)) != HEVCDL_OK) return st;
+  if ((st = rc_check_scaling(scaling)) != HEVCDL_OK) return st;
+  if ((st = hevcdl_validate_records(cfg, records, n_frames)) != HEVCDL_OK) return st;
+  const size_t ctus = unit.size(), fb = hevcdl_frame_bytes_bd(p.W, p.H, p.bit_depth);
+  std::vector<RcWork> w(1);
+  p.unit = unit.data(); p.cb_off = qp_info->cb_qp_offset; p.cr_off = qp_info->cr_qp_offset; p.factor = scaling->factor;
+  for (int f = 0; f < n_frames; f++) {
+    p.recs = records + (size_t)f * ctus; p.out = (unsigned char *)recon + (size_t)f * fb; p.qp_map = qp_map + (size_t)f * ctus * 256;
+    for (int cy = 0; cy < p.ctus_y; cy++) for (int cx = 0; cx < p.ctus_x; cx++) {
+      if (p.bit_depth == 8) rc_ctu<uint8_t>(p, w[0], 0, 1, cx, cy); else rc_ctu<uint16_t>(p, w[0], 0, 1, cx, cy);
+    }
+  }
+  return HEVCDL_OK;
+}
+
+// d_factor: HEVCDL_SCALING_FACTOR_BYTES in device memory, non-zero bytes (the caller has checked them: hevcdl_parse_stream_sl's are by construction)
+hevcdl_status hevcdl_recon_enqueue_sl(const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const hevcdl_qp_info *qp_info, const void *d_qp_map, const void *d_factor,
+                                      const void *d_records, int n_frames, void *d_recon, void *d_work, size_t work_bytes, void *stream, std::vector<uint32_t> &keep, const uint32_t **d_error)
+{
+  RcLaunchSl L;
+  memset(&L, 0, sizeof L);
+  hevcdl_status st = rc_setup(cfg, slices_opt, L.pic, keep);
+  if (st != HEVCDL_OK) return st;
+  if (!d_records || !d_recon || !d_work || !d_error || !d_factor || n_frames < 1 || n_frames > (1 << 16)) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "null device pointer, or a picture count outside 1 .. 65536");
+  if ((st = rc_check_qp_info(qp_info, d_qp_map)) != HEVCDL_OK) return st;
+  if (work_bytes < hevcdl_recon_work_bytes(cfg->width, cfg->height, n_frames)) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "work memory smaller than hevcdl_recon_work_bytes");
+  hipStream_t s = (hipStream_t)stream;
+  const size_t ctus = keep.size(), rows = (size_t)n_frames * L.pic.ctus_y;
+  const size_t b_unit = ctus * 4, b_qp = (size_t)n_frames * 4, b_sync = (2 + rows) * 4;      // (the layout of hevcdl_recon_enqueue; the per-picture QPs' room stays unused)
+  unsigned char *d = (unsigned char *)d_work;
+  HIPOK(hipMemcpyAsync(d, keep.data(), keep.size() * 4, hipMemcpyHostToDevice, s));
+  HIPOK(hipMemsetAsync(d + b_unit + b_qp, 0, b_sync, s));
+  L.pic.unit = (const uint32_t *)d; L.pic.recs = (const hevcdl_ctu_record *)d_records; L.pic.out = d_recon; L.pic.qp_map = (const int8_t *)d_qp_map; L.pic.factor = (const uint8_t *)d_factor;
+  L.pic.cb_off = qp_info->cb_qp_offset; L.pic.cr_off = qp_info->cr_qp_offset; L.sync = (uint32_t *)(d + b_unit + b_qp);
+  L.frame_bytes = hevcdl_frame_bytes_bd(L.pic.W, L.pic.H, L.pic.bit_depth); L.n_frames = n_frames; L.ctus = (int)ctus;
+  const unsigned groups = (unsigned)(rows < RC_MAX_GROUPS ? rows : RC_MAX_GROUPS);
+  g_launches.fetch_add(1); g_sl_launches.fetch_add(1);
+  if (L.pic.bit_depth == 8) hipLaunchKernelGGL((hevcdl_recon_kernel<uint8_t, RcLaunchSl>), dim3(groups), dim3(64), 0, s, L);
+  else hipLaunchKernelGGL((hevcdl_recon_kernel<uint16_t, RcLaunchSl>), dim3(groups), dim3(64), 0, s, L);
+  HIPOK(hipGetLastError());
+  *d_error = L.sync + 1;
+  return HEVCDL_OK;
+}
+
+// (the factor block is uploaded behind the work memory of the call and freed with it)
+extern "C" hevcdl_status hevcdl_reconstruct_frames_sl_dev(int device, const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const hevcdl_qp_info *qp_info,
+                                                         const void *d_qp_map, const hevcdl_scaling_info *scaling, const void *d_records, int n_frames, void *d_recon, void *stream)
+{
+  if (!cfg || n_frames < 1) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "null configuration or no picture");
+  { const hevcdl_status st = rc_check_scaling(scaling); if (st != HEVCDL_OK) return st; }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { (void)hipGetLastError(); RC_REFUSE(HEVCDL_ERR_NO_DEVICE, "no such device"); }
+  HIPOK(hipSetDevice(device));
+  const size_t work = (hevcdl_recon_work_bytes(cfg->width, cfg->height, n_frames) + 15) & ~(size_t)15, total = work + HEVCDL_SCALING_FACTOR_BYTES;
+  unsigned char *d = nullptr;
+  if (hipMalloc(&d, total) != hipSuccess) { (void)hipGetLastError(); RC_REFUSE(HEVCDL_ERR_OOM, "no device memory for the row counts"); }
+  std::vector<uint32_t> keep; const uint32_t *d_err = nullptr; uint32_t err = 0;
+  hevcdl_status out = HEVCDL_OK;
+  if (hipMemcpyAsync(d + work, scaling->factor, HEVCDL_SCALING_FACTOR_BYTES, hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess) { (void)hipGetLastError(); hevcdl_parse::set_error("upload failed"); out = HEVCDL_ERR_HIP; }
+  if (out == HEVCDL_OK) out = hevcdl_recon_enqueue_sl(cfg, slices_opt, qp_info, d_qp_map, d + work, d_records, n_frames, d_recon, d, work, stream, keep, &d_err);
+  if (out == HEVCDL_OK && (hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess || hipStreamSynchronize((hipStream_t)stream) != hipSuccess)) {
+    (void)hipGetLastError(); hevcdl_parse::set_error("a HIP call of the reconstruction failed"); out = HEVCDL_ERR_HIP;
+  }
+  if (out == HEVCDL_OK && err) { hevcdl_parse::set_error("a CTU row waited for the row above longer than the limit"); out = HEVCDL_ERR_HIP; }
+  if (out != HEVCDL_OK) (void)hipStreamSynchronize((hipStream_t)stream);      // nothing may still read the work memory when it is freed
+  (void)hipFree(d);
+  return out;
+}
+
+extern "C" hevcdl_status hevcdl_reconstruct_frames_sl(int device, const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const hevcdl_qp_info *qp_info,
+                                                     const int8_t *qp_map, const hevcdl_scaling_info *scaling, const hevcdl_ctu_record *records, int n_frames, void *recon)
+{
+  RcPic p; std::vector<uint32_t> unit;
+  hevcdl_status st = rc_setup(cfg, slices_opt, p, unit);
+  if (st != HEVCDL_OK) return st;
+  if (!records || !recon || n_frames < 0) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "null records or pictures");
+  if ((st = rc_check_qp_info(qp_info, qp_map)) != HEVCDL_OK) return st;
+  if ((st = rc_check_scaling(scaling)) != HEVCDL_OK) return st;
+  if ((st = hevcdl_validate_records(cfg, records, n_frames)) != HEVCDL_OK) return st;
+  if (n_frames == 0) return HEVCDL_OK;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { (void)hipGetLastError(); RC_REFUSE(HEVCDL_ERR_NO_DEVICE, "no such device"); }
+  HIPOK(hipSetDevice(device));
+  const size_t b_rec = sizeof(hevcdl_ctu_record) * unit.size() * (size_t)n_frames, b_pic = hevcdl_frame_bytes_bd(p.W, p.H, p.bit_depth) * (size_t)n_frames, b_map = unit.size() * 256 * (size_t)n_frames;
+  unsigned char *d = nullptr;
+  if (hipMalloc(&d, b_rec + b_pic + b_map) != hipSuccess) { (void)hipGetLastError(); RC_REFUSE(HEVCDL_ERR_OOM, "no device memory for %d pictures", n_frames); }
+  st = HEVCDL_OK;
+  if (hipMemcpy(d, records, b_rec, hipMemcpyHostToDevice) != hipSuccess || hipMemset(d + b_rec, 0, b_pic) != hipSuccess || hipMemcpy(d + b_rec + b_pic, qp_map, b_map, hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipGetLastError(); hevcdl_parse::set_error("upload failed"); st = HEVCDL_ERR_HIP;
+  }
+  if (st == HEVCDL_OK) st = hevcdl_reconstruct_frames_sl_dev(device, cfg, slices_opt, qp_info, d + b_rec + b_pic, scaling, d, n_frames, d + b_rec, nullptr);
   if (st == HEVCDL_OK && hipMemcpy(recon, d + b_rec, b_pic, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); hevcdl_parse::set_error("download failed"); st = HEVCDL_ERR_HIP; }
   (void)hipFree(d);
   return st;

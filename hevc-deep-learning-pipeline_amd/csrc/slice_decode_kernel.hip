@@ -149,3 +149,10 @@ extern "C" hevcdl_status hevcdl_parse_stream_dev_qp(int device, const uint8_t *s
 {
   return hevcdl_parse::parse_stream_with(walk_units_dev, &device, stream, bytes, cfg, slices, segments, pictures, picture_capacity, n_pictures, records, sao, ctu_capacity, accept, qp_info, qp_map);
 }
+
+extern "C" hevcdl_status hevcdl_parse_stream_dev_sl(int device, const uint8_t *stream, size_t bytes, unsigned accept, hevcdl_stream_config *cfg, hevcdl_slice_layout *slices,
+                                                   hevcdl_segment_layout *segments, hevcdl_parsed_picture *pictures, int picture_capacity, int *n_pictures, hevcdl_ctu_record *records,
+                                                   hevcdl_sao_blk *sao, size_t ctu_capacity, hevcdl_qp_info *qp_info, int8_t *qp_map, hevcdl_scaling_info *scaling)
+{
+  return hevcdl_parse::parse_stream_with(walk_units_dev, &device, stream, bytes, cfg, slices, segments, pictures, picture_capacity, n_pictures, records, sao, ctu_capacity, accept, qp_info, qp_map, scaling);
+}

@@ -18,6 +18,7 @@ struct StreamUnits {
   hevcdl_stream_config cfg; hevcdl_slice_layout slices; hevcdl_segment_layout segments;      // as hevcdl_parse_stream gives them (cfg only without a pending refusal)
   hevcdl_sd::SdStream sd;
   hevcdl_qp_info qp = { 0, 0, 0, 0 };            // the PPS fields a QP map goes with (all 0 unless accepted)
+  hevcdl_scaling_info sl;                        // the SPS's scaling lists as factors (enabled 0 unless accepted; set with cfg)
   int ctus = 0;
   std::vector<hevcdl_parsed_picture> pictures;
   std::vector<uint8_t> rbsp;                     // the slice data of every picture, emulation prevention removed, sub-stream behind sub-stream
@@ -28,7 +29,7 @@ struct StreamUnits {
 };
 // want_slice_data 0: headers only (no tables).  have_sao / ctu_capacity: the caller's room, checked per picture as hevcdl_parse_stream does.  Returns HEVCDL_OK also with a
 // pending refusal; anything else is a refusal in front of the first picture's end (the sentence is in hevcdl_parse_error()).
-// accept: HEVCDL_ACCEPT_* bits (hevcdl.h) -- 0: cu_qp_delta_enabled_flag and chroma QP offsets are refused as ever; su.qp says what the PPS carries.
+// accept: HEVCDL_ACCEPT_* bits (hevcdl.h) -- 0: cu_qp_delta_enabled_flag, chroma QP offsets and scaling lists are refused as ever; su.qp says what the PPS carries, su.sl what the SPS.
 hevcdl_status collect_units(const uint8_t *stream, size_t bytes, int want_slice_data, int have_sao, size_t ctu_capacity, StreamUnits &out, unsigned accept = 0);
 // the tables of pictures [first, first + count) as one launch takes them: units and sub-streams renumbered from 0, rbsp0 from the first byte of picture `first`
 hevcdl_status batch_tables(const StreamUnits &su, int first, int count, std::vector<hevcdl_sd::SdUnit> &units, size_t &sub0, size_t &n_subs, size_t &byte0, size_t &n_bytes);
@@ -39,7 +40,7 @@ typedef hevcdl_status (*UnitWalker)(void *user, const StreamUnits &su, int n, he
 // hevcdl_parse_stream's contract with the slice data decoded by `walk`
 hevcdl_status parse_stream_with(UnitWalker walk, void *user, const uint8_t *stream, size_t bytes, hevcdl_stream_config *cfg, hevcdl_slice_layout *slices, hevcdl_segment_layout *segments,
                                 hevcdl_parsed_picture *pictures, int picture_capacity, int *n_pictures, hevcdl_ctu_record *records, hevcdl_sao_blk *sao, size_t ctu_capacity,
-                                unsigned accept = 0, hevcdl_qp_info *qp_info = nullptr, int8_t *qp_map = nullptr);
+                                unsigned accept = 0, hevcdl_qp_info *qp_info = nullptr, int8_t *qp_map = nullptr, hevcdl_scaling_info *scaling = nullptr);
 // "picture 3, CTU 17: <sentence of the code>" into hevcdl_parse_error()
 void set_slice_error(int pic, const hevcdl_sd::SdResult &res);
 

@@ -357,23 +357,24 @@ def decode_stream_by_stages(stream, device=0, batch=64):
     return np.concatenate(out), p, verdicts
 
 
-def decode_stream(stream, device=0, batch=64, device_parse=False, cu_qp=False):
+def decode_stream(stream, device=0, batch=64, device_parse=False, cu_qp=False, scaling_lists=False):
     """A stream of this pipeline (or of the reference encoder in the same configuration) decoded by hevcdl_decode_stream: parsed on the host -- with device_parse only its
     headers, the slice data by hevcdl_slice_decode_kernel into the records in HBM (hevcdl_enable_device_parse) --; reconstruction from the
     records, deblocking, SAO with the stream's parameters and the digests of the decoded picture hash on the device, `batch` pictures at a time in HBM.
     -> (pictures [n, w * h * 3 / 2] in coded format -- the conformance window is NOT cut --, the ParsedStream of the headers, verdicts [n]: True / False where the stream
-    carries a hash, None where it does not).  cu_qp: accept streams with cu_qp_delta_enabled_flag or PPS chroma QP offsets (hevcdl_enable_cu_qp); off, they are refused."""
+    carries a hash, None where it does not).  cu_qp: accept streams with cu_qp_delta_enabled_flag or PPS chroma QP offsets (hevcdl_enable_cu_qp); off, they are refused.
+    scaling_lists: accept streams whose SPS enables scaling lists (hevcdl_enable_scaling_lists); off, they are refused."""
     from . import decode_stream as decode, parse_stream
-    pictures, _, _, verdicts = decode(stream, device=device, batch=batch, device_parse=device_parse, cu_qp=cu_qp)
-    return pictures, parse_stream(stream, headers_only=True, cu_qp=cu_qp), verdicts
+    pictures, _, _, verdicts = decode(stream, device=device, batch=batch, device_parse=device_parse, cu_qp=cu_qp, scaling_lists=scaling_lists)
+    return pictures, parse_stream(stream, headers_only=True, cu_qp=cu_qp, scaling_lists=scaling_lists), verdicts
 
 
-def decode_sequence(bitstream_path, recon_path=None, device=0, batch=64, log=None, device_parse=False, cu_qp=False):
+def decode_sequence(bitstream_path, recon_path=None, device=0, batch=64, log=None, device_parse=False, cu_qp=False, scaling_lists=False):
     """decode_stream over a stream file; with recon_path the output pictures are written as the reference decoder writes them: the conformance window, at the coded bit
     depth.  One line per picture (POC, QP, hash verdict) goes to `log` (a callable, e.g. print).  -> (pictures, ParsedStream, verdicts); a hash mismatch raises
     ValueError behind the file."""
     with open(bitstream_path, "rb") as f:
-        pictures, p, verdicts = decode_stream(f.read(), device=device, batch=batch, device_parse=device_parse, cu_qp=cu_qp)
+        pictures, p, verdicts = decode_stream(f.read(), device=device, batch=batch, device_parse=device_parse, cu_qp=cu_qp, scaling_lists=scaling_lists)
     cfg = p.cfg
     w, h = cfg.width, cfg.height
     if recon_path is not None:

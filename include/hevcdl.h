@@ -826,7 +826,7 @@ typedef struct hevcdl_parsed_picture {
  * csrc/hevcdl_parse.h), bits / dist / cost are 0; sao_opt is needed when a picture has SAO on and holds zeros for the others.
  * Accepted is exactly what this library's writer can produce: I slices, main or main10, 4:2:0, CTU 64, minimum CB 8, TU 4 .. 32, any picture size (multiples of 8) with a
  * conformance window, tiles or wavefront rows, slices of CTU rows or tiles, dependent segments, every tool switch, the deblocking filter on or off.  Anything else is
- * HEVCDL_ERR_UNSUPPORTED -- P and B slices, PCM, scaling lists, cu_qp_delta_enabled_flag and PPS chroma QP offsets (unless accepted: hevcdl_parse_stream_qp below), transquant bypass, other chroma formats or bit depths, slices that do not start at
+ * HEVCDL_ERR_UNSUPPORTED -- P and B slices, PCM, scaling lists in the PPS, scaling lists in the SPS, cu_qp_delta_enabled_flag and PPS chroma QP offsets (the last three unless accepted: hevcdl_parse_stream_qp / _sl below), transquant bypass, other chroma formats or bit depths, slices that do not start at
  * a CTU row or a tile, ... -- and a damaged stream is HEVCDL_ERR_INVALID_ARG, never a crash: every value that addresses memory is checked where it is read.  Either way
  * hevcdl_parse_error() is a sentence saying what (per thread; "" after a success). */
 hevcdl_status hevcdl_parse_stream(const uint8_t *stream, size_t bytes, hevcdl_stream_config *cfg, hevcdl_slice_layout *slices_opt, hevcdl_segment_layout *segments_opt,
@@ -878,6 +878,31 @@ hevcdl_status hevcdl_parse_stream_core_qp(const uint8_t *stream, size_t bytes, u
 hevcdl_status hevcdl_parse_stream_dev_qp(int device, const uint8_t *stream, size_t bytes, unsigned accept, hevcdl_stream_config *cfg, hevcdl_slice_layout *slices_opt,
                                          hevcdl_segment_layout *segments_opt, hevcdl_parsed_picture *pictures_opt, int picture_capacity, int *n_pictures,
                                          hevcdl_ctu_record *records_opt, hevcdl_sao_blk *sao_opt, size_t ctu_capacity, hevcdl_qp_info *qp_info_opt, int8_t *qp_map_opt);
+/* ---- scaling lists: OFF unless the call accepts them -----------------------------------------------------------------------------------------
+ * The _sl forms are the _qp forms with one more output; the _qp forms are the _sl forms with scaling_opt NULL.  With HEVCDL_ACCEPT_SCALING_LISTS in `accept` the SPS may set
+ * scaling_list_enabled_flag: without sps_scaling_list_data_present_flag the default lists hold (Table 7-5, the intra list of Table 7-6, DC 16), with it scaling_list_data()
+ * of 7.3.4 is read -- sizeId 0 .. 3, matrixId 0 .. 5 (0 and 3 for sizeId 3, whose scaling_list_pred_matrix_id_delta counts in steps of 3); the inter lists are parsed and
+ * dropped.  HEVCDL_ERR_INVALID_ARG with a sentence: a scaling_list_pred_matrix_id_delta above its matrixId, scaling_list_dc_coef_minus8 outside -7 .. 247, a
+ * scaling_list_delta_coef outside -128 .. 127, a list entry of 0, an SPS that ends inside its lists.  pps_scaling_list_data_present_flag stays refused.  Without the bit
+ * the flag is refused as ever.  The slice data, the records and the QP map are what they are without lists.
+ * hevcdl_scaling_info.factor: ScalingFactor of 7.4.5 as bytes in raster order (y * n + x), plane behind plane: Y 4x4, 8x8, 16x16, 32x32, then Cb 4x4, 8x8, 16x16, then Cr
+ * likewise -- 3 * (16 + 64 + 256) + 1024 bytes.  16x16 and 32x32 repeat their 8x8 list by 2 and by 4 and carry their DC entry at [0].  A stream without the flag gives
+ * enabled 0 and 16 everywhere. */
+#define HEVCDL_ACCEPT_SCALING_LISTS 2u
+#define HEVCDL_SCALING_FACTOR_BYTES 2032
+typedef struct hevcdl_scaling_info { int32_t enabled, data_present; uint8_t factor[HEVCDL_SCALING_FACTOR_BYTES]; } hevcdl_scaling_info;
+hevcdl_status hevcdl_parse_stream_sl(const uint8_t *stream, size_t bytes, unsigned accept, hevcdl_stream_config *cfg, hevcdl_slice_layout *slices_opt,
+                                     hevcdl_segment_layout *segments_opt, hevcdl_parsed_picture *pictures_opt, int picture_capacity, int *n_pictures,
+                                     hevcdl_ctu_record *records_opt, hevcdl_sao_blk *sao_opt, size_t ctu_capacity, hevcdl_qp_info *qp_info_opt, int8_t *qp_map_opt,
+                                     hevcdl_scaling_info *scaling_opt);
+hevcdl_status hevcdl_parse_stream_core_sl(const uint8_t *stream, size_t bytes, unsigned accept, hevcdl_stream_config *cfg, hevcdl_slice_layout *slices_opt,
+                                          hevcdl_segment_layout *segments_opt, hevcdl_parsed_picture *pictures_opt, int picture_capacity, int *n_pictures,
+                                          hevcdl_ctu_record *records_opt, hevcdl_sao_blk *sao_opt, size_t ctu_capacity, hevcdl_qp_info *qp_info_opt, int8_t *qp_map_opt,
+                                          hevcdl_scaling_info *scaling_opt);
+hevcdl_status hevcdl_parse_stream_dev_sl(int device, const uint8_t *stream, size_t bytes, unsigned accept, hevcdl_stream_config *cfg, hevcdl_slice_layout *slices_opt,
+                                         hevcdl_segment_layout *segments_opt, hevcdl_parsed_picture *pictures_opt, int picture_capacity, int *n_pictures,
+                                         hevcdl_ctu_record *records_opt, hevcdl_sao_blk *sao_opt, size_t ctu_capacity, hevcdl_qp_info *qp_info_opt, int8_t *qp_map_opt,
+                                         hevcdl_scaling_info *scaling_opt);
 /* Records a caller brings itself (n_frames pictures of cfg's size), checked as the parser's own are by construction: depths that form a quadtree with the forced splits
  * at the picture's edge, NxN only in 8x8 CUs, prediction modes in range and constant over their block, tr_idx a transform tree within TU 4 .. 32 and depth 3, no cbf
  * bit below the depth of the partition's transform unit, transform-skip flags 0 / 1.  HEVCDL_ERR_INVALID_ARG with a sentence in hevcdl_parse_error() otherwise.  NOT
@@ -911,6 +936,15 @@ hevcdl_status hevcdl_reconstruct_frames_qp_dev(int device, const hevcdl_stream_c
                                                const void *d_qp_map, const void *d_records, int n_frames, void *d_recon, void *stream);
 hevcdl_status hevcdl_reconstruct_frames_qp_host(const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const hevcdl_qp_info *qp_info,
                                                 const int8_t *qp_map, const hevcdl_ctu_record *records, int n_frames, void *recon);
+/* The same three with scaling factors on top of the QP map (hevcdl_parse_stream_sl gives both; a stream of one QP has a constant map): scaling->factor as described above,
+ * HOST memory in all three -- the 2032 bytes are uploaded by the call.  A coefficient is level * factor * levelScale[qP % 6] << (qP / 6), rounded, shifted by bdShift and
+ * clipped to 16 bits (8.6.4.2); a transform-skipped 4x4 block is scaled with its factors too.  A factor of 0 is refused.  A third instantiation of the kernel. */
+hevcdl_status hevcdl_reconstruct_frames_sl(int device, const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const hevcdl_qp_info *qp_info,
+                                           const int8_t *qp_map, const hevcdl_scaling_info *scaling, const hevcdl_ctu_record *records, int n_frames, void *recon);
+hevcdl_status hevcdl_reconstruct_frames_sl_dev(int device, const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const hevcdl_qp_info *qp_info,
+                                               const void *d_qp_map, const hevcdl_scaling_info *scaling, const void *d_records, int n_frames, void *d_recon, void *stream);
+hevcdl_status hevcdl_reconstruct_frames_sl_host(const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const hevcdl_qp_info *qp_info,
+                                                const int8_t *qp_map, const hevcdl_scaling_info *scaling, const hevcdl_ctu_record *records, int n_frames, void *recon);
 
 /* ---- the decoder: a stream of this library's writer, or of the reference encoder in the same configuration, to pictures ------------------------
  * hevcdl_config_from_stream: the configuration of a context that can decode a parsed stream (hevcdl_parse_stream with records_opt NULL gives cfg, the slice layout and
@@ -943,6 +977,14 @@ hevcdl_status hevcdl_enable_cu_qp(hevcdl_ctx *ctx, int on);
 /* launches of the QP-map instantiations this process has made: of the reconstruction kernel's -- they count in hevcdl_recon_launches too -- and of the deblocking pair (TEST AND DIAGNOSTIC) */
 unsigned long long hevcdl_recon_qp_launches(void);
 unsigned long long hevcdl_deblock_qp_launches(void);
+/* hevcdl_enable_scaling_lists(ctx, 1): hevcdl_decode_stream parses with HEVCDL_ACCEPT_SCALING_LISTS, with host parse and with device parse.  For a stream with
+ * scaling_list_enabled_flag the factor block is uploaded once, the QP map of a batch lies in HBM as with hevcdl_enable_cu_qp (a constant one for a stream of one QP), and the
+ * scaling-list instantiation of hevcdl_recon_kernel runs; the deblocking filter, SAO and the report kernels are what they were.  A stream without the flag takes exactly the
+ * launches it takes without the switch.  A stream with lists AND cu_qp_delta / chroma QP offsets needs both switches and is refused with the missing one's sentence.
+ * Off by default; (ctx, 0) turns it off again and frees the block.  hevcdl_recon_sl_launches: launches of that instantiation by this process -- they count in
+ * hevcdl_recon_launches too (TEST AND DIAGNOSTIC). */
+hevcdl_status hevcdl_enable_scaling_lists(hevcdl_ctx *ctx, int on);
+unsigned long long hevcdl_recon_sl_launches(void);
 hevcdl_status hevcdl_deblock_frames_map(hevcdl_ctx *ctx, const void *recon, int n_frames, const hevcdl_ctu_record *records, const hevcdl_dbk_choice *choices_opt,
                                         const hevcdl_qp_info *qp_info, const int8_t *qp_map, void *out);
 

@@ -15,7 +15,11 @@ A second leg times a stream with a QP per CU: one picture
 (--cu-qp-stream FILE: such a stream made beforehand; otherwise oracle/_ref/TAppEncoder_ref makes it, and without either the leg is written as "not measured") -- parse on
 the host and on the device with the QP map, and reconstruction and deblocking of the SAME records with the map (the QP-map instantiations) and without it (the constant-QP
 kernels at the slice QP: another picture, the same work), then hevcdl_decode_stream with the switch on.
---keep-lines N keeps the last N lines of the file that is there (results another tool appended, e.g. a comparison against the parent commit).
+A third leg times the scaling-list instantiation: the batch stream above with its SPS rewritten on the spot to carry the lists of
+tests/golden/sclist_file_rand.npz (tools/scaling_list_cover.py: with_scaling_lists -- test-side SPS syntax; the slice data is untouched, so the records and the work are
+the same and the pictures are not the encoder's: every digest verdict is False, and is not asserted) -- hevcdl_decode_stream with hevcdl_enable_scaling_lists against the
+constant-QP decode of the stream as it was, five calls each in alternation, and the reconstruction stage alone with and without the factors.
+--keep-lines N keeps the last N lines of the file that is there (results another tool appended, e.g. a comparison against the parent commit; 4 keeps the one of section 5m).
 
     python tools/time_decode.py [--batch 8] [--width 3840 --height 2160] [--qp 32] [--cu-qp-stream FILE]
 """
@@ -31,6 +35,11 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
+
+
+def note(text):
+    """Progress on stderr: the table itself is printed at the end."""
+    print("[time_decode] " + text, file=sys.stderr, flush=True)
 
 
 def best(fn, runs=3):
@@ -71,6 +80,31 @@ def cu_qp_leg(hevcdl_amd, ref_tools, a, d):
             "  reconstruct with map %8.1f  without %8.1f   deblock with map %8.1f  without %8.1f   decode_stream %8.1f  with device parse %8.1f" % (t_rec_map, t_rec, t_dbk_map, t_dbk, t_all, t_dp)]
 
 
+def scaling_list_leg(hevcdl_amd, stream, n):
+    """The lines of the scaling-list leg: `stream` (n pictures, constant QP, this pipeline's) as it is and with scaling lists in its SPS."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import scaling_list_cover as slc
+    lists = np.load(os.path.join(ROOT, "tests", "golden", "sclist_file_rand.npz"))
+    sl_stream = slc.with_scaling_lists(stream, lists)
+    lib = hevcdl_amd.load_library()
+    p = hevcdl_amd.parse_stream(sl_stream, scaling_lists=True)
+    assert p.scaling.enabled == 1 and p.records.tobytes() == hevcdl_amd.parse_stream(stream).records.tobytes()
+    t_rec_sl, _ = best(lambda: hevcdl_amd.reconstruct_frames(p.cfg, p.records, slices=p.slices, qp_map=p.qp_map, qp_info=p.qp_info, scaling=p.scaling, device=0))
+    t_rec_qp, _ = best(lambda: hevcdl_amd.reconstruct_frames(p.cfg, p.records, slices=p.slices, qp_map=p.qp_map, qp_info=p.qp_info, device=0))
+    t_rec, _ = best(lambda: hevcdl_amd.reconstruct_frames(p.cfg, p.records, slices=p.slices, qps=p.qps, device=0))
+    flat, with_lists = [], []
+    for _ in range(5):
+        c0 = lib.hevcdl_recon_sl_launches()
+        flat.append(best(lambda: hevcdl_amd.decode_stream(stream, batch=n, scaling_lists=True), runs=1)[0])
+        assert lib.hevcdl_recon_sl_launches() == c0
+        with_lists.append(best(lambda: hevcdl_amd.decode_stream(sl_stream, batch=n, scaling_lists=True), runs=1)[0])
+        assert lib.hevcdl_recon_sl_launches() == c0 + 1
+    return ["scaling lists, the %d-picture stream above with the lists of sclist_file_rand in its SPS (rewritten on the spot; the same records): measured" % n,
+            "  reconstruct with factors %8.1f  with the QP map alone %8.1f  constant QP %8.1f" % (t_rec_sl, t_rec_qp, t_rec),
+            "  decode_stream, 5 calls each in alternation: constant-QP stream " + " ".join("%.1f" % t for t in flat) + "   (spread %.1f .. %.1f)" % (min(flat), max(flat)),
+            "                                              with scaling lists " + " ".join("%.1f" % t for t in with_lists) + "   (spread %.1f .. %.1f)" % (min(with_lists), max(with_lists))]
+
+
 def main():
     import hevcdl_amd
     from hevcdl_amd import pipeline
@@ -87,6 +121,7 @@ def main():
     lines = ["decoder times, %dx%d 8-bit QP %d, ms (best of 3; wall clock around synchronous calls)" % (w, h, qp)]
     with tempfile.TemporaryDirectory() as d:
         for n in (1, a.batch):
+            note("%d picture(s): encode, then the stages" % n)
             yuv = ref_tools.synth_yuv(w, h, n, seed=77)
             yuv.tofile(os.path.join(d, "in.yuv"))
             pipeline.encode_sequence(os.path.join(d, "in.yuv"), w, h, qp, n, bitstream_path=os.path.join(d, "s.bin"), hash_sei=True, log=lambda *x: None)
@@ -111,7 +146,11 @@ def main():
                 t0 = time.perf_counter()
                 r = subprocess.run([ref, "-b", "s.bin", "-o", "ref.yuv"], cwd=d, capture_output=True, text=True)
                 lines.append("pictures %3d  reference decoder %8.1f  (exit %d)" % (n, (time.perf_counter() - t0) * 1000.0, r.returncode))
+        note("scaling-list leg")
+        sl_lines = scaling_list_leg(hevcdl_amd, stream, a.batch)
+        note("QP-per-CU leg")
         lines += cu_qp_leg(hevcdl_amd, ref_tools, a, d)
+        lines += sl_lines
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
     lines.append("(tools/time_decode.py on one MI355X.  decode_stream is the Python entry hevcdl_amd.decode_stream: it creates and destroys a context per call, which is in its time; the\n"
                  "stage columns include their host <-> device copies.  One 2160p picture is a chain of 34 CTU rows two CTUs apart, so a single picture is bound by that chain's latency and a\n"
