@@ -590,80 +590,30 @@ def parse_stream(stream, headers_only=False, engine="host", device=0, cu_qp=Fals
     lib = load_library()
     if engine not in ("host", "core", "device"):
         raise ValueError("engine is \"host\", \"core\" or \"device\"")
-    if scaling_lists:
-        return _parse_stream_sl(lib, stream, headers_only, engine, device, (ACCEPT_CU_QP if cu_qp else 0) | ACCEPT_SCALING_LISTS)
-    if cu_qp:
-        return _parse_stream_qp(lib, stream, headers_only, engine, device)
-    if engine == "core":
-        parse = lib.hevcdl_parse_stream_core
-    elif engine == "device":
-        def parse(*a):
-            return lib.hevcdl_parse_stream_dev(int(device), *a)
-    else:
-        parse = lib.hevcdl_parse_stream
+    # per variant the entry points of the three engines and what they take around the plain form's arguments: `accept` in front of cfg, qp_info, the QP map and (sl) the
+    # scaling info at the end.  Each variant probes the headers with its own host form and parses with its own form of the engine.
+    suffix = "_sl" if scaling_lists else "_qp" if cu_qp else ""
+    names = {"host": "hevcdl_parse_stream" + suffix, "core": "hevcdl_parse_stream_core" + suffix, "device": "hevcdl_parse_stream_dev" + suffix}
+    accept = ((ACCEPT_CU_QP if cu_qp else 0) | ACCEPT_SCALING_LISTS,) if scaling_lists else (ACCEPT_CU_QP,) if cu_qp else ()
+    info, sc = QpInfo() if suffix else None, ScalingInfo() if scaling_lists else None
     buf = np.frombuffer(bytes(stream), np.uint8)
     cfg = StreamConfig()
     cfg.struct_size = ctypes.sizeof(StreamConfig)
     sl, sg, n = SliceLayout(), SegmentLayout(), ctypes.c_int(0)
 
-    def check(st):
+    def call(name, who, lead, pics, capacity, records, sao, ctu_capacity, qp_map):
+        tail = () if not suffix else (ctypes.byref(info), qp_map) + ((ctypes.byref(sc),) if scaling_lists else ())
+        st = getattr(lib, name)(*lead, buf.ctypes.data, buf.size, *accept, ctypes.byref(cfg), ctypes.byref(sl), ctypes.byref(sg), pics, capacity, ctypes.byref(n), records, sao, ctu_capacity, *tail)
         if st != 0:
-            raise HevcdlError(st, {"host": "hevcdl_parse_stream: ", "core": "hevcdl_parse_stream_core: ", "device": "hevcdl_parse_stream_dev: "}[engine] + lib.hevcdl_parse_error().decode())
-    check(lib.hevcdl_parse_stream(buf.ctypes.data, buf.size, ctypes.byref(cfg), ctypes.byref(sl), ctypes.byref(sg), None, 0, ctypes.byref(n), None, None, 0))
+            raise HevcdlError(st, who + ": " + lib.hevcdl_parse_error().decode())
+    call(names["host"], names["host"] if suffix else names[engine], (), None, 0, None, None, 0, None)      # (the plain form has always named its engine here too)
     ctus = ((cfg.width + 63) // 64) * ((cfg.height + 63) // 64)
     pics = (ParsedPicture * n.value)()
     records = None if headers_only else np.zeros((n.value, ctus), REC_DTYPE)
     sao = None if headers_only else np.zeros((n.value, ctus, 3), SAO_DTYPE)
-    check(parse(buf.ctypes.data, buf.size, ctypes.byref(cfg), ctypes.byref(sl), ctypes.byref(sg), pics, n.value, ctypes.byref(n),
-                                  None if headers_only else records.ctypes.data, None if headers_only else sao.ctypes.data, 0 if headers_only else n.value * ctus))
-    return ParsedStream(cfg, sl if sl.mode else None, sg if sg.mode else None, list(pics), records, sao)
-
-
-def _parse_stream_qp(lib, stream, headers_only, engine, device):
-    fn = {"host": lib.hevcdl_parse_stream_qp, "core": lib.hevcdl_parse_stream_core_qp, "device": lambda *a: lib.hevcdl_parse_stream_dev_qp(int(device), *a)}[engine]
-    name = {"host": "hevcdl_parse_stream_qp: ", "core": "hevcdl_parse_stream_core_qp: ", "device": "hevcdl_parse_stream_dev_qp: "}[engine]
-    buf = np.frombuffer(bytes(stream), np.uint8)
-    cfg = StreamConfig()
-    cfg.struct_size = ctypes.sizeof(StreamConfig)
-    sl, sg, n, info = SliceLayout(), SegmentLayout(), ctypes.c_int(0), QpInfo()
-
-    def check(st, who):
-        if st != 0:
-            raise HevcdlError(st, who + lib.hevcdl_parse_error().decode())
-    check(lib.hevcdl_parse_stream_qp(buf.ctypes.data, buf.size, ACCEPT_CU_QP, ctypes.byref(cfg), ctypes.byref(sl), ctypes.byref(sg), None, 0, ctypes.byref(n), None, None, 0, ctypes.byref(info), None),
-          "hevcdl_parse_stream_qp: ")
-    ctus = ((cfg.width + 63) // 64) * ((cfg.height + 63) // 64)
-    pics = (ParsedPicture * n.value)()
-    records = None if headers_only else np.zeros((n.value, ctus), REC_DTYPE)
-    sao = None if headers_only else np.zeros((n.value, ctus, 3), SAO_DTYPE)
-    qp_map = None if headers_only else np.zeros((n.value, ctus, 256), np.int8)
-    check(fn(buf.ctypes.data, buf.size, ACCEPT_CU_QP, ctypes.byref(cfg), ctypes.byref(sl), ctypes.byref(sg), pics, n.value, ctypes.byref(n),
-             None if headers_only else records.ctypes.data, None if headers_only else sao.ctypes.data, 0 if headers_only else n.value * ctus, ctypes.byref(info),
-             None if headers_only else qp_map.ctypes.data), name)
-    return ParsedStream(cfg, sl if sl.mode else None, sg if sg.mode else None, list(pics), records, sao, qp_map, info)
-
-
-def _parse_stream_sl(lib, stream, headers_only, engine, device, accept):
-    fn = {"host": lib.hevcdl_parse_stream_sl, "core": lib.hevcdl_parse_stream_core_sl, "device": lambda *a: lib.hevcdl_parse_stream_dev_sl(int(device), *a)}[engine]
-    name = {"host": "hevcdl_parse_stream_sl: ", "core": "hevcdl_parse_stream_core_sl: ", "device": "hevcdl_parse_stream_dev_sl: "}[engine]
-    buf = np.frombuffer(bytes(stream), np.uint8)
-    cfg = StreamConfig()
-    cfg.struct_size = ctypes.sizeof(StreamConfig)
-    sl, sg, n, info, sc = SliceLayout(), SegmentLayout(), ctypes.c_int(0), QpInfo(), ScalingInfo()
-
-    def check(st, who):
-        if st != 0:
-            raise HevcdlError(st, who + lib.hevcdl_parse_error().decode())
-    check(lib.hevcdl_parse_stream_sl(buf.ctypes.data, buf.size, accept, ctypes.byref(cfg), ctypes.byref(sl), ctypes.byref(sg), None, 0, ctypes.byref(n), None, None, 0, ctypes.byref(info), None,
-                                     ctypes.byref(sc)), "hevcdl_parse_stream_sl: ")
-    ctus = ((cfg.width + 63) // 64) * ((cfg.height + 63) // 64)
-    pics = (ParsedPicture * n.value)()
-    records = None if headers_only else np.zeros((n.value, ctus), REC_DTYPE)
-    sao = None if headers_only else np.zeros((n.value, ctus, 3), SAO_DTYPE)
-    qp_map = None if headers_only else np.zeros((n.value, ctus, 256), np.int8)
-    check(fn(buf.ctypes.data, buf.size, accept, ctypes.byref(cfg), ctypes.byref(sl), ctypes.byref(sg), pics, n.value, ctypes.byref(n),
-             None if headers_only else records.ctypes.data, None if headers_only else sao.ctypes.data, 0 if headers_only else n.value * ctus, ctypes.byref(info),
-             None if headers_only else qp_map.ctypes.data, ctypes.byref(sc)), name)
+    qp_map = None if headers_only or not suffix else np.zeros((n.value, ctus, 256), np.int8)
+    call(names[engine], names[engine], (int(device),) if engine == "device" else (), pics, n.value, None if headers_only else records.ctypes.data,
+         None if headers_only else sao.ctypes.data, 0 if headers_only else n.value * ctus, None if qp_map is None else qp_map.ctypes.data)
     return ParsedStream(cfg, sl if sl.mode else None, sg if sg.mode else None, list(pics), records, sao, qp_map, info, sc)
 
 

@@ -2,6 +2,8 @@
 // Host C++ (no GPU, no HIP header).  Annex B -> NAL units -> VPS / SPS / PPS / slice segment headers / decoded picture hash SEI -> slice data: an arithmetic
 // DECODER over entropy_tables.h (ITU-T H.265 9.3.4.3) and the I-slice syntax of 7.3.8 (sao, coding_quadtree, coding_unit, transform_tree, residual_coding) ->
 // hevcdl_ctu_record and hevcdl_sao_blk per CTU (hevcdl_parse.h names the record fields a stream determines).
+// One function, walk_stream, owns everything in front of the slice data and hands each complete picture to a sink: hevcdl_parse_stream's sink decodes it with the decoder
+// of this file, collect_units' sink cuts it into units for the shared decoder (slice_decode_core.h), which the first is tested against.
 //
 // Accepted: what hevcdl_write_access_unit_segments can produce.  Anything else is HEVCDL_ERR_UNSUPPORTED with a sentence (hevcdl_parse_error); a damaged stream is
 // HEVCDL_ERR_INVALID_ARG.  Construction rules (a stream is untrusted input):
@@ -886,32 +888,35 @@ hevcdl_status check_layouts(const ParamSets &ps, const Grid &g, const std::vecto
   return HEVCDL_OK;
 }
 
-} // namespace
-
-extern "C" const char *hevcdl_parse_error(void) { return hevcdl_parse::g_error; }
-
-static void fill_qp_info(const ParamSets &ps, hevcdl_qp_info *q)
+// ---- one walk over the stream ----------------------------------------------------------------------------------------------------
+// the hevcdl_stream_config a stream's parameter sets amount to, the layouts of its first picture and what its SPS / PPS carry beyond them
+void fill_config(const ParamSets &active, int level_idc, int first_qp, int count, int ps_before_second, const hevcdl_slice_layout &sl, const hevcdl_segment_layout &sg, StreamShape &out)
 {
-  if (!q) return;
-  q->cu_qp_delta_enabled = ps.cu_qp_delta; q->diff_cu_qp_delta_depth = ps.diff_cu_qp_depth; q->cb_qp_offset = ps.cb_qp_offset; q->cr_qp_offset = ps.cr_qp_offset;
+  hevcdl_stream_config c;
+  hevcdl_stream_config_default(&c, active.width, active.height, 26);
+  c.qp = 0; c.level_idc = level_idc; c.sao_enabled = active.sao; c.loop_filter_disable = active.dbk_disabled;
+  c.tile_columns = active.tcols; c.tile_rows = active.trows; c.bit_depth = active.bit_depth; c.tile_uniform_spacing = active.uniform;
+  if (!active.uniform) { for (int i = 0; i < active.tcols - 1 && i < 19; i++) c.tile_column_width[i] = active.col_width[i]; for (int i = 0; i < active.trows - 1 && i < 21; i++) c.tile_row_height[i] = active.row_height[i]; }
+  c.lf_across_tiles = active.lf_across_tiles;
+  c.tools = (HEVCDL_TOOLS_REFERENCE & ~(uint32_t)(HEVCDL_TOOL_TSKIP | HEVCDL_TOOL_SIGN_HIDE | HEVCDL_TOOL_STRONG_INTRA)) | (active.tskip ? HEVCDL_TOOL_TSKIP : 0) |
+            (active.sign_hiding ? HEVCDL_TOOL_SIGN_HIDE : 0) | (active.strong_intra ? HEVCDL_TOOL_STRONG_INTRA : 0);
+  c.lf_beta_offset_div2 = active.beta_div2; c.lf_tc_offset_div2 = active.tc_div2;
+  c.rewrite_param_sets = (count == 1 || ps_before_second) ? 1 : 0;
+  c.wavefront = active.wpp;
+  c.conf_win_left = active.conf_left; c.conf_win_right = active.conf_right; c.conf_win_top = active.conf_top; c.conf_win_bottom = active.conf_bottom;
+  c.qp = first_qp;                                   // the first picture's: a stream of one QP is then described by the configuration alone
+  out.cfg = c; out.slices = sl; out.segments = sg;
+  out.qp.cu_qp_delta_enabled = active.cu_qp_delta; out.qp.diff_cu_qp_delta_depth = active.diff_cu_qp_depth; out.qp.cb_qp_offset = active.cb_qp_offset; out.qp.cr_qp_offset = active.cr_qp_offset;
+  out.sl.enabled = active.sl_enabled; out.sl.data_present = active.sl_data_present;
+  if (active.sl_enabled) memcpy(out.sl.factor, active.sl_factor, sizeof out.sl.factor); else memset(out.sl.factor, 16, sizeof out.sl.factor);
 }
 
-static void fill_scaling_info(const ParamSets &ps, hevcdl_scaling_info *s)
+// Everything in front of the slice data, once: Annex B -> NAL units -> parameter sets, SEI and slice segment headers, every check in its place.  A picture whose segments are
+// complete and are those of the stream's layouts goes to sink(active, grid, slices, segments, segs, picture, index) -> status: the parser decodes it there, collect_units cuts
+// it into units.  `out` is written only behind the last picture (a refusal leaves it alone).
+template <class Sink>
+hevcdl_status walk_stream(const uint8_t *stream, size_t bytes, unsigned accept, Sink sink, StreamShape &out)
 {
-  if (!s) return;
-  s->enabled = ps.sl_enabled; s->data_present = ps.sl_data_present;
-  if (ps.sl_enabled) memcpy(s->factor, ps.sl_factor, sizeof s->factor); else memset(s->factor, 16, sizeof s->factor);
-}
-
-extern "C" hevcdl_status hevcdl_parse_stream_sl(const uint8_t *stream, size_t bytes, unsigned accept, hevcdl_stream_config *cfg, hevcdl_slice_layout *slices, hevcdl_segment_layout *segments,
-                                               hevcdl_parsed_picture *pictures, int picture_capacity, int *n_pictures, hevcdl_ctu_record *records, hevcdl_sao_blk *sao,
-                                               size_t ctu_capacity, hevcdl_qp_info *qp_info, int8_t *qp_map, hevcdl_scaling_info *scaling)
-{
-  memset(&g_tally, 0, sizeof g_tally);
-  set_error("%s", "");
-  if (n_pictures) *n_pictures = 0;
-  if (!stream || !cfg || !n_pictures || picture_capacity < 0) INVALID("null stream, configuration or picture count");
-  if (cfg->struct_size != sizeof *cfg) INVALID("hevcdl_stream_config.struct_size is not that of this library");
   std::vector<std::pair<size_t, size_t>> units;
   split_annexb(stream, bytes, units);
   if (units.empty()) INVALID("no start code in the stream");
@@ -925,7 +930,7 @@ extern "C" hevcdl_status hevcdl_parse_stream_sl(const uint8_t *stream, size_t by
   int count = 0, level_idc = 0, first_qp = 0, ps_before_second = 0;
   bool open = false;
 
-  // the picture whose segments are collected: check them, decode them, hand them out
+  // the picture whose segments are collected: check them, hand them to the sink
   auto close_picture = [&]() -> hevcdl_status {
     if (!open) return HEVCDL_OK;
     open = false;
@@ -934,20 +939,8 @@ extern "C" hevcdl_status hevcdl_parse_stream_sl(const uint8_t *stream, size_t by
     st = check_layouts(active, g, segs, sl, sg);
     if (st != HEVCDL_OK) return st;
     cur.n_segments = (int)segs.size();
-    if (records) {
-      if ((size_t)(count + 1) * (size_t)g.n > ctu_capacity) INVALID("room for %llu CTUs, picture %d needs %llu", (unsigned long long)ctu_capacity, count, (unsigned long long)(count + 1) * g.n);
-      Picture p(active, g);
-      p.recs = records + (size_t)count * g.n; p.sao = sao ? sao + (size_t)count * g.n : nullptr;
-      memset(p.recs, 0, sizeof(hevcdl_ctu_record) * (size_t)g.n);
-      if (p.sao) memset(p.sao, 0, sizeof(hevcdl_sao_blk) * (size_t)g.n);
-      p.W = active.width; p.H = active.height; p.qp = cur.qp; p.sao_on = cur.sao; p.max_sao = (1 << (std::min(active.bit_depth, 10) - 5)) - 1;
-      if (qp_map) { p.qp_map = qp_map + (size_t)count * g.n * 256; memset(p.qp_map, 0, (size_t)g.n * 256); }
-      if (cur.sao && !p.sao) INVALID("the stream carries SAO parameters and there is no room for them");
-      st = decode_picture_data(p, segs);
-      p.close_group();
-      if (st != HEVCDL_OK) return st;
-    }
-    if (pictures && count < picture_capacity) pictures[count] = cur;
+    st = sink(active, g, sl, sg, segs, cur, count);
+    if (st != HEVCDL_OK) return st;
     if (count == 0) first_qp = cur.qp;
     count++;
     segs.clear(); seg_nals.clear();
@@ -1006,25 +999,52 @@ extern "C" hevcdl_status hevcdl_parse_stream_sl(const uint8_t *stream, size_t by
   }
   { const hevcdl_status st = close_picture(); if (st != HEVCDL_OK) return st; }
   if (count == 0 || !have_grid) INVALID("no picture in the stream");
-  *n_pictures = count;
+  fill_config(active, level_idc, first_qp, count, ps_before_second, sl, sg, out);
+  return HEVCDL_OK;
+}
 
-  hevcdl_stream_config c;
-  hevcdl_stream_config_default(&c, active.width, active.height, 26);
-  c.qp = 0; c.level_idc = level_idc; c.sao_enabled = active.sao; c.loop_filter_disable = active.dbk_disabled;
-  c.tile_columns = active.tcols; c.tile_rows = active.trows; c.bit_depth = active.bit_depth; c.tile_uniform_spacing = active.uniform;
-  if (!active.uniform) { for (int i = 0; i < active.tcols - 1 && i < 19; i++) c.tile_column_width[i] = active.col_width[i]; for (int i = 0; i < active.trows - 1 && i < 21; i++) c.tile_row_height[i] = active.row_height[i]; }
-  c.lf_across_tiles = active.lf_across_tiles;
-  c.tools = (HEVCDL_TOOLS_REFERENCE & ~(uint32_t)(HEVCDL_TOOL_TSKIP | HEVCDL_TOOL_SIGN_HIDE | HEVCDL_TOOL_STRONG_INTRA)) | (active.tskip ? HEVCDL_TOOL_TSKIP : 0) |
-            (active.sign_hiding ? HEVCDL_TOOL_SIGN_HIDE : 0) | (active.strong_intra ? HEVCDL_TOOL_STRONG_INTRA : 0);
-  c.lf_beta_offset_div2 = active.beta_div2; c.lf_tc_offset_div2 = active.tc_div2;
-  c.rewrite_param_sets = (count == 1 || ps_before_second) ? 1 : 0;
-  c.wavefront = active.wpp;
-  c.conf_win_left = active.conf_left; c.conf_win_right = active.conf_right; c.conf_win_top = active.conf_top; c.conf_win_bottom = active.conf_bottom;
-  c.qp = first_qp;                                   // the first picture's: a stream of one QP is then described by the configuration alone
-  *cfg = c;
-  fill_qp_info(active, qp_info); fill_scaling_info(active, scaling);
-  if (slices) *slices = sl;
-  if (segments) *segments = sg;
+} // namespace
+
+extern "C" const char *hevcdl_parse_error(void) { return hevcdl_parse::g_error; }
+
+extern "C" hevcdl_status hevcdl_parse_stream_sl(const uint8_t *stream, size_t bytes, unsigned accept, hevcdl_stream_config *cfg, hevcdl_slice_layout *slices, hevcdl_segment_layout *segments,
+                                               hevcdl_parsed_picture *pictures, int picture_capacity, int *n_pictures, hevcdl_ctu_record *records, hevcdl_sao_blk *sao,
+                                               size_t ctu_capacity, hevcdl_qp_info *qp_info, int8_t *qp_map, hevcdl_scaling_info *scaling)
+{
+  memset(&g_tally, 0, sizeof g_tally);
+  set_error("%s", "");
+  if (n_pictures) *n_pictures = 0;
+  if (!stream || !cfg || !n_pictures || picture_capacity < 0) INVALID("null stream, configuration or picture count");
+  if (cfg->struct_size != sizeof *cfg) INVALID("hevcdl_stream_config.struct_size is not that of this library");
+  // the sink of the walk: the picture's slice data decoded by the parser's own decoder, its header handed out
+  int count = 0;
+  auto decode = [&](const ParamSets &active, const Grid &g, const hevcdl_slice_layout &, const hevcdl_segment_layout &, const std::vector<SegmentData> &segs, const hevcdl_parsed_picture &cur, int index) -> hevcdl_status {
+    if (records) {
+      if ((size_t)(index + 1) * (size_t)g.n > ctu_capacity) INVALID("room for %llu CTUs, picture %d needs %llu", (unsigned long long)ctu_capacity, index, (unsigned long long)(index + 1) * g.n);
+      Picture p(active, g);
+      p.recs = records + (size_t)index * g.n; p.sao = sao ? sao + (size_t)index * g.n : nullptr;
+      memset(p.recs, 0, sizeof(hevcdl_ctu_record) * (size_t)g.n);
+      if (p.sao) memset(p.sao, 0, sizeof(hevcdl_sao_blk) * (size_t)g.n);
+      p.W = active.width; p.H = active.height; p.qp = cur.qp; p.sao_on = cur.sao; p.max_sao = (1 << (std::min(active.bit_depth, 10) - 5)) - 1;
+      if (qp_map) { p.qp_map = qp_map + (size_t)index * g.n * 256; memset(p.qp_map, 0, (size_t)g.n * 256); }
+      if (cur.sao && !p.sao) INVALID("the stream carries SAO parameters and there is no room for them");
+      const hevcdl_status st = decode_picture_data(p, segs);
+      p.close_group();
+      if (st != HEVCDL_OK) return st;
+    }
+    if (pictures && index < picture_capacity) pictures[index] = cur;
+    count = index + 1;
+    return HEVCDL_OK;
+  };
+  StreamShape shape;
+  const hevcdl_status st = walk_stream(stream, bytes, accept, decode, shape);
+  if (st != HEVCDL_OK) return st;
+  *n_pictures = count;
+  *cfg = shape.cfg;
+  if (qp_info) *qp_info = shape.qp;
+  if (scaling) *scaling = shape.sl;
+  if (slices) *slices = shape.slices;
+  if (segments) *segments = shape.segments;
   if (pictures && count > picture_capacity) INVALID("room for %d pictures, the stream holds %d", picture_capacity, count);
   return HEVCDL_OK;
 }
@@ -1106,9 +1126,9 @@ extern "C" hevcdl_status hevcdl_validate_records(const hevcdl_stream_config *cfg
 }
 
 // ---- the same stream through the shared slice-data decoder (slice_decode_core.h) ---------------------------------------------------------------------------------
-// Everything in front of the slice data is the code above: split_annexb, unescape, the parameter-set, slice-header and SEI parsers, cut_substreams, derive_layouts and
-// check_layouts, called in hevcdl_parse_stream's order -- a header refusal is the parser's, sentence included.  Where the parser decodes a picture, collect_units cuts
-// it into units (slice_decode_units.h); who walks them is the caller's choice: the CPU (hevcdl_parse_stream_core) or hevcdl_slice_decode_kernel.
+// Everything in front of the slice data is walk_stream above, the walk hevcdl_parse_stream runs -- a header refusal is the parser's, sentence and place included.  Where
+// the parser's sink decodes a picture, collect_units' sink cuts it into units (slice_decode_units.h); who walks them is the caller's choice: the CPU
+// (hevcdl_parse_stream_core) or hevcdl_slice_decode_kernel.
 namespace {
 using namespace hevcdl_sd;
 
@@ -1159,116 +1179,24 @@ hevcdl_status picture_units(const ParamSets &ps, const Grid &g, const hevcdl_sli
   return HEVCDL_OK;
 }
 
-// hevcdl_parse_stream's loop over the NAL units, its checks in its order; a picture that closes is cut into units where the parser decodes it
+// collect_units' sink of the walk: where the parser decodes a picture, it is cut into units (headers only: just kept)
 hevcdl_status collect_loop(const uint8_t *stream, size_t bytes, int want_slice_data, int have_sao, size_t ctu_capacity, StreamUnits &out, unsigned accept)
 {
-  std::vector<std::pair<size_t, size_t>> units;
-  split_annexb(stream, bytes, units);
-  if (units.empty()) INVALID("no start code in the stream");
-  ParamSets ps; memset(&ps, 0, sizeof ps);
-  ParamSets active; memset(&active, 0, sizeof active);
-  Grid g; bool have_grid = false;
-  hevcdl_slice_layout sl = { 0, 0, 1 }; hevcdl_segment_layout sg = { 0, 0 };
-  std::vector<SegmentData> segs; std::vector<Nal> seg_nals;
-  hevcdl_parsed_picture cur; memset(&cur, 0, sizeof cur);
-  int count = 0, level_idc = 0, first_qp = 0, ps_before_second = 0;
-  bool open = false;
-
-  auto close_picture = [&]() -> hevcdl_status {
-    if (!open) return HEVCDL_OK;
-    open = false;
-    hevcdl_status st;
-    if (count == 0) { st = derive_layouts(active, g, segs, sl, sg); if (st != HEVCDL_OK) return st; }
-    st = check_layouts(active, g, segs, sl, sg);
-    if (st != HEVCDL_OK) return st;
-    cur.n_segments = (int)segs.size();
-    if (want_slice_data) {
-      if ((size_t)(count + 1) * (size_t)g.n > ctu_capacity) INVALID("room for %llu CTUs, picture %d needs %llu", (unsigned long long)ctu_capacity, count, (unsigned long long)(count + 1) * g.n);
-      if (cur.sao && !have_sao) INVALID("the stream carries SAO parameters and there is no room for them");
-      if (count == 0) {
-        SdStream &d = out.sd;
-        d.W = active.width; d.H = active.height; d.ctus_x = g.cx; d.ctus_y = g.cy; d.wpp = active.wpp; d.tskip = active.tskip; d.sign_hiding = active.sign_hiding;
-        d.max_sao = (1 << (std::min(active.bit_depth, 10) - 5)) - 1; d.row_slices = sl.mode == 1;
-        d.cu_qp = active.cu_qp_delta; d.log2_qg = 6 - active.diff_cu_qp_depth; d.qp_bd_offset = 6 * (active.bit_depth - 8);
-      }
-      for (const SegmentData &s : segs) if (s.subs.empty()) INVALID("a slice segment without data");
-      st = picture_units(active, g, sl, segs, cur, out);
-      if (st != HEVCDL_OK) return st;
-    } else out.pictures.push_back(cur);
-    if (count == 0) first_qp = cur.qp;
-    count++;
-    segs.clear(); seg_nals.clear();
-    return HEVCDL_OK;
+  auto cut = [&](const ParamSets &active, const Grid &g, const hevcdl_slice_layout &sl, const hevcdl_segment_layout &, const std::vector<SegmentData> &segs, const hevcdl_parsed_picture &cur, int index) -> hevcdl_status {
+    if (index == 0) out.ctus = g.n;
+    if (!want_slice_data) { out.pictures.push_back(cur); return HEVCDL_OK; }
+    if ((size_t)(index + 1) * (size_t)g.n > ctu_capacity) INVALID("room for %llu CTUs, picture %d needs %llu", (unsigned long long)ctu_capacity, index, (unsigned long long)(index + 1) * g.n);
+    if (cur.sao && !have_sao) INVALID("the stream carries SAO parameters and there is no room for them");
+    if (index == 0) {
+      SdStream &d = out.sd;
+      d.W = active.width; d.H = active.height; d.ctus_x = g.cx; d.ctus_y = g.cy; d.wpp = active.wpp; d.tskip = active.tskip; d.sign_hiding = active.sign_hiding;
+      d.max_sao = (1 << (std::min(active.bit_depth, 10) - 5)) - 1; d.row_slices = sl.mode == 1;
+      d.cu_qp = active.cu_qp_delta; d.log2_qg = 6 - active.diff_cu_qp_depth; d.qp_bd_offset = 6 * (active.bit_depth - 8);
+    }
+    for (const SegmentData &s : segs) if (s.subs.empty()) INVALID("a slice segment without data");
+    return picture_units(active, g, sl, segs, cur, out);
   };
-
-  seg_nals.reserve(units.size());
-  for (const auto &u : units) {
-    Nal nal;
-    if (!unescape(stream + u.first, u.second - u.first, nal)) INVALID("a NAL unit of %llu bytes, or one with forbidden_zero_bit set", (unsigned long long)(u.second - u.first));
-    hevcdl_status st = HEVCDL_OK;
-    if (nal.type == 32) { st = close_picture(); if (st != HEVCDL_OK) return st; continue; }
-    if (nal.type == 33 || nal.type == 34) {
-      st = close_picture(); if (st != HEVCDL_OK) return st;
-      st = nal.type == 33 ? parse_sps(nal, ps, accept) : parse_pps(nal, ps, accept);
-      if (st != HEVCDL_OK) return st;
-      if (nal.type == 33) level_idc = ps.level_idc;
-      if (count == 1) ps_before_second = 1;
-      continue;
-    }
-    if (nal.type == 40 || nal.type == 39) {
-      if (nal.type == 40 && open) { st = parse_hash_sei(nal, cur); if (st != HEVCDL_OK) return st; }
-      continue;
-    }
-    if (nal.type == 35 || nal.type == 36 || nal.type == 37 || nal.type == 38) { if (nal.type != 38) { st = close_picture(); if (st != HEVCDL_OK) return st; } continue; }
-    if (nal.type >= 32) UNSUPPORTED("NAL unit type %d is outside this decoder", nal.type);
-    if (nal.type != 19 && nal.type != 20 && nal.type != 21) UNSUPPORTED("NAL unit type %d: only intra random access pictures (IDR, CRA) are decoded", nal.type);
-    if (!ps.have_sps || !ps.have_pps) INVALID("a slice NAL unit in front of the SPS and the PPS");
-    if (nal.rbsp.empty()) INVALID("an empty slice NAL unit");
-    if (nal.rbsp[0] & 0x80) {
-      st = close_picture(); if (st != HEVCDL_OK) return st;
-      if (count > 0 && memcmp(&ps, &active, sizeof ps) != 0) UNSUPPORTED("parameter sets that change inside the stream are outside this decoder");
-      if (count == 0) { active = ps; st = make_grid(active, g); if (st != HEVCDL_OK) return st; have_grid = true; out.ctus = g.n; }
-      memset(&cur, 0, sizeof cur);
-      open = true;
-    } else if (!open) INVALID("a slice segment without the first segment of its picture");
-    if (segs.size() >= (size_t)MAX_SEGMENTS) INVALID("more than %d slice segments a picture", (int)MAX_SEGMENTS);
-    seg_nals.push_back(std::move(nal));
-    const Nal &kept = seg_nals.back();
-    SegmentData sd;
-    st = parse_slice_header(kept, active, g.n, sd.h);
-    if (st != HEVCDL_OK) return st;
-    if (sd.h.first != (segs.empty() ? 1 : 0)) INVALID("first_slice_segment_in_pic_flag of a slice segment");
-    if (!sd.h.dependent) {
-      if (sd.h.sao_luma != sd.h.sao_chroma) UNSUPPORTED("SAO for one of luma / chroma only is outside this decoder");
-      const int qp = active.init_qp + sd.h.qp_delta;
-      if (qp < 0 || qp > 51) INVALID("slice QP %d", qp);
-      if (segs.empty()) { cur.poc = sd.h.poc; cur.nal_type = sd.h.nal_type; cur.qp = qp; cur.sao = sd.h.sao_luma; cur.dbk = sd.h.dbk; cur.lf_across_slices = sd.h.lf_across_slices; }
-      else if (cur.qp != qp || cur.sao != sd.h.sao_luma || memcmp(&cur.dbk, &sd.h.dbk, sizeof cur.dbk) != 0 || cur.lf_across_slices != sd.h.lf_across_slices || cur.poc != sd.h.poc)
-        UNSUPPORTED("slices of one picture that differ in QP, SAO or deblocking parameters are outside this decoder");
-    } else if (segs.empty()) INVALID("a dependent slice segment opens the picture");
-    if (kept.type != (segs.empty() ? kept.type : cur.nal_type)) INVALID("the slice NAL units of a picture differ in their type");
-    st = cut_substreams(kept, sd);
-    if (st != HEVCDL_OK) return st;
-    segs.push_back(std::move(sd));
-  }
-  { const hevcdl_status st = close_picture(); if (st != HEVCDL_OK) return st; }
-  if (count == 0 || !have_grid) INVALID("no picture in the stream");
-
-  hevcdl_stream_config c;
-  hevcdl_stream_config_default(&c, active.width, active.height, 26);
-  c.qp = 0; c.level_idc = level_idc; c.sao_enabled = active.sao; c.loop_filter_disable = active.dbk_disabled;
-  c.tile_columns = active.tcols; c.tile_rows = active.trows; c.bit_depth = active.bit_depth; c.tile_uniform_spacing = active.uniform;
-  if (!active.uniform) { for (int i = 0; i < active.tcols - 1 && i < 19; i++) c.tile_column_width[i] = active.col_width[i]; for (int i = 0; i < active.trows - 1 && i < 21; i++) c.tile_row_height[i] = active.row_height[i]; }
-  c.lf_across_tiles = active.lf_across_tiles;
-  c.tools = (HEVCDL_TOOLS_REFERENCE & ~(uint32_t)(HEVCDL_TOOL_TSKIP | HEVCDL_TOOL_SIGN_HIDE | HEVCDL_TOOL_STRONG_INTRA)) | (active.tskip ? HEVCDL_TOOL_TSKIP : 0) |
-            (active.sign_hiding ? HEVCDL_TOOL_SIGN_HIDE : 0) | (active.strong_intra ? HEVCDL_TOOL_STRONG_INTRA : 0);
-  c.lf_beta_offset_div2 = active.beta_div2; c.lf_tc_offset_div2 = active.tc_div2;
-  c.rewrite_param_sets = (count == 1 || ps_before_second) ? 1 : 0;
-  c.wavefront = active.wpp;
-  c.conf_win_left = active.conf_left; c.conf_win_right = active.conf_right; c.conf_win_top = active.conf_top; c.conf_win_bottom = active.conf_bottom;
-  c.qp = first_qp;
-  out.cfg = c; out.slices = sl; out.segments = sg; fill_qp_info(active, &out.qp); fill_scaling_info(active, &out.sl);
-  return HEVCDL_OK;
+  return walk_stream(stream, bytes, accept, cut, out);
 }
 
 // the units of pictures [0, n) on the CPU, in the parser's order: the first error met is the lowest picture's first

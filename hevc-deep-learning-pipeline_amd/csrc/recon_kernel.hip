@@ -118,24 +118,64 @@ hevcdl_status rc_check_qps(const int32_t *qps, int n)
   return HEVCDL_OK;
 }
 #define HIPOK(call) do { if ((call) != hipSuccess) { (void)hipGetLastError(); RC_REFUSE(HEVCDL_ERR_HIP, "%s failed", #call); } } while (0)
-} // namespace
-
-extern "C" unsigned long long hevcdl_recon_launches(void) { return g_launches.load(); }
-
-extern "C" hevcdl_status hevcdl_reconstruct_frames_host(const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const int32_t *qps_opt,
-                                                       const hevcdl_ctu_record *records, int n_frames, void *recon)
+hevcdl_status rc_check_qp_info(const hevcdl_qp_info *q, const void *map)
 {
-  RcPic p; std::vector<uint32_t> unit;
+  if (!q || !map) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "null QP map or hevcdl_qp_info");
+  if (q->cb_qp_offset < -12 || q->cb_qp_offset > 12 || q->cr_qp_offset < -12 || q->cr_qp_offset > 12) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "chroma QP offsets %d / %d", q->cb_qp_offset, q->cr_qp_offset);
+  return HEVCDL_OK;
+}
+hevcdl_status rc_check_scaling(const hevcdl_scaling_info *s)
+{
+  if (!s) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "null hevcdl_scaling_info");
+  for (int i = 0; i < HEVCDL_SCALING_FACTOR_BYTES; i++) if (!s->factor[i]) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "scaling factor %d is 0", i);
+  return HEVCDL_OK;
+}
+
+// ---- one host path for the three instantiations --------------------------------------------------------------------------------------------------------------------
+// The forms are named by their launch struct: RcLaunch (a QP per picture), RcLaunchQp (hevcdl_parse_stream_qp's QP map and the PPS chroma offsets), RcLaunchSl (the
+// scaling factors of hevcdl_parse_stream_sl on top of the map).  RcQuant is what a form dequantises with, as its entry points are given it: qps (null: cfg->qp for every
+// picture) for RcLaunch; info and map for the other two, map in host or device memory as the records of the same call are; for RcLaunchSl also the factors -- `scaling`
+// on the host, d_factor where a launch reads them.  What differs between the forms is said where it differs, with if constexpr.
+struct RcQuant { const int32_t *qps; const hevcdl_qp_info *info; const void *map; const hevcdl_scaling_info *scaling; const void *d_factor; };
+template <typename LAUNCH> constexpr bool rc_has_map = !std::is_same<LAUNCH, RcLaunch>::value;
+template <typename LAUNCH> constexpr bool rc_has_factor = std::is_same<LAUNCH, RcLaunchSl>::value;
+std::atomic<unsigned long long> g_qp_launches{0}, g_sl_launches{0};      // g_launches counts every launch, these two only their own form's
+
+// the form's check of what it dequantises with, behind the pointers and in front of the sizes: the per-picture QPs, or the PPS offsets and the map
+template <typename LAUNCH>
+hevcdl_status rc_check_quant(const RcQuant &q, int n_frames)
+{
+  if constexpr (rc_has_map<LAUNCH>) return rc_check_qp_info(q.info, q.map); else return rc_check_qps(q.qps, n_frames);
+}
+
+// what the CPU form and the host-buffer form refuse, in this order, before either does anything
+template <typename LAUNCH>
+hevcdl_status rc_check_host(const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const RcQuant &q, const hevcdl_ctu_record *records, int n_frames, const void *recon,
+                            RcPic &p, std::vector<uint32_t> &unit)
+{
   hevcdl_status st = rc_setup(cfg, slices_opt, p, unit);
   if (st != HEVCDL_OK) return st;
   if (!records || !recon || n_frames < 0) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "null records or pictures");
-  if ((st = rc_check_qps(qps_opt, n_frames)) != HEVCDL_OK) return st;
-  if ((st = hevcdl_validate_records(cfg, records, n_frames)) != HEVCDL_OK) return st;
+  if ((st = rc_check_quant<LAUNCH>(q, n_frames)) != HEVCDL_OK) return st;
+  if constexpr (rc_has_factor<LAUNCH>) { if ((st = rc_check_scaling(q.scaling)) != HEVCDL_OK) return st; }
+  return hevcdl_validate_records(cfg, records, n_frames);      // nothing is allocated, copied or launched on QPs or records that are refused
+}
+
+// the *_host forms: rc_ctu as one "lane" over every CTU of every picture
+template <typename LAUNCH>
+hevcdl_status rc_host(const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const RcQuant &q, const hevcdl_ctu_record *records, int n_frames, void *recon)
+{
+  decltype(LAUNCH::pic) p; std::vector<uint32_t> unit;
+  const hevcdl_status st = rc_check_host<LAUNCH>(cfg, slices_opt, q, records, n_frames, recon, p, unit);
+  if (st != HEVCDL_OK) return st;
   const size_t ctus = unit.size(), fb = hevcdl_frame_bytes_bd(p.W, p.H, p.bit_depth);
   std::vector<RcWork> w(1);
   p.unit = unit.data();
+  if constexpr (rc_has_map<LAUNCH>) { p.cb_off = q.info->cb_qp_offset; p.cr_off = q.info->cr_qp_offset; }
+  if constexpr (rc_has_factor<LAUNCH>) p.factor = q.scaling->factor;
   for (int f = 0; f < n_frames; f++) {
-    p.recs = records + (size_t)f * ctus; p.out = (unsigned char *)recon + (size_t)f * fb; p.qp = qps_opt ? qps_opt[f] : cfg->qp;
+    p.recs = records + (size_t)f * ctus; p.out = (unsigned char *)recon + (size_t)f * fb;
+    if constexpr (rc_has_map<LAUNCH>) p.qp_map = (const int8_t *)q.map + (size_t)f * ctus * 256; else p.qp = q.qps ? q.qps[f] : cfg->qp;
     for (int cy = 0; cy < p.ctus_y; cy++) for (int cx = 0; cx < p.ctus_x; cx++) {
       if (p.bit_depth == 8) rc_ctu<uint8_t>(p, w[0], 0, 1, cx, cy); else rc_ctu<uint16_t>(p, w[0], 0, 1, cx, cy);
     }
@@ -145,55 +185,67 @@ extern "C" hevcdl_status hevcdl_reconstruct_frames_host(const hevcdl_stream_conf
 
 // The launch alone, on work memory the caller owns (hevcdl_decode_stream: a buffer of the context, sized once by hevcdl_recon_work_bytes): nothing is allocated, freed or
 // waited for.  `keep` receives the host copy of what is uploaded (units, QPs) and must live until the stream has passed the copies; *d_error is the error word in the
-// work memory, to be fetched with the batch's other results: non-zero = a row waited past the limit.  The device is the caller's current one.
-extern "C" size_t hevcdl_recon_work_bytes(int width, int height, int n_frames)
+// work memory, to be fetched with the batch's other results: non-zero = a row waited past the limit.  The device is the caller's current one.  The work memory is laid
+// out alike for the three forms -- units, a QP per picture, ticket and error word, row counts -- and the forms with a map leave the QPs' room unused.
+template <typename LAUNCH>
+hevcdl_status rc_enqueue(const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const RcQuant &q, const void *d_records, int n_frames,
+                         void *d_recon, void *d_work, size_t work_bytes, void *stream, std::vector<uint32_t> &keep, const uint32_t **d_error)
 {
-  const size_t cx = (size_t)((width + 63) >> 6), cy = (size_t)((height + 63) >> 6), n = (size_t)(n_frames > 0 ? n_frames : 0);
-  return cx * cy * 4 + n * 4 + (2 + n * cy) * 4;
-}
-hevcdl_status hevcdl_recon_enqueue(const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const int32_t *qps_opt, const void *d_records, int n_frames,
-                                   void *d_recon, void *d_work, size_t work_bytes, void *stream, std::vector<uint32_t> &keep, const uint32_t **d_error)
-{
-  RcLaunch L;
+  LAUNCH L;
   memset(&L, 0, sizeof L);
   hevcdl_status st = rc_setup(cfg, slices_opt, L.pic, keep);
   if (st != HEVCDL_OK) return st;
-  if (!d_records || !d_recon || !d_work || !d_error || n_frames < 1 || n_frames > (1 << 16)) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "null device pointer, or a picture count outside 1 .. 65536");
-  if ((st = rc_check_qps(qps_opt, n_frames)) != HEVCDL_OK) return st;
+  if (!d_records || !d_recon || !d_work || !d_error || (rc_has_factor<LAUNCH> && !q.d_factor) || n_frames < 1 || n_frames > (1 << 16)) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "null device pointer, or a picture count outside 1 .. 65536");
+  if ((st = rc_check_quant<LAUNCH>(q, n_frames)) != HEVCDL_OK) return st;
   if (work_bytes < hevcdl_recon_work_bytes(cfg->width, cfg->height, n_frames)) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "work memory smaller than hevcdl_recon_work_bytes");
   hipStream_t s = (hipStream_t)stream;
   const size_t ctus = keep.size(), rows = (size_t)n_frames * L.pic.ctus_y;
   const size_t b_unit = ctus * 4, b_qp = (size_t)n_frames * 4, b_sync = (2 + rows) * 4;
-  if (qps_opt) keep.insert(keep.end(), (const uint32_t *)qps_opt, (const uint32_t *)qps_opt + n_frames);
+  if constexpr (!rc_has_map<LAUNCH>) { if (q.qps) keep.insert(keep.end(), (const uint32_t *)q.qps, (const uint32_t *)q.qps + n_frames); }
   unsigned char *d = (unsigned char *)d_work;
   HIPOK(hipMemcpyAsync(d, keep.data(), keep.size() * 4, hipMemcpyHostToDevice, s));
   HIPOK(hipMemsetAsync(d + b_unit + b_qp, 0, b_sync, s));
   L.pic.unit = (const uint32_t *)d; L.pic.recs = (const hevcdl_ctu_record *)d_records; L.pic.out = d_recon;
-  L.qps = qps_opt ? (const int32_t *)(d + b_unit) : nullptr; L.sync = (uint32_t *)(d + b_unit + b_qp);
+  if constexpr (rc_has_map<LAUNCH>) { L.pic.qp_map = (const int8_t *)q.map; L.pic.cb_off = q.info->cb_qp_offset; L.pic.cr_off = q.info->cr_qp_offset; }
+  else L.qps = q.qps ? (const int32_t *)(d + b_unit) : nullptr;
+  if constexpr (rc_has_factor<LAUNCH>) L.pic.factor = (const uint8_t *)q.d_factor;
+  L.sync = (uint32_t *)(d + b_unit + b_qp);
   L.frame_bytes = hevcdl_frame_bytes_bd(L.pic.W, L.pic.H, L.pic.bit_depth); L.n_frames = n_frames; L.ctus = (int)ctus;
   const unsigned groups = (unsigned)(rows < RC_MAX_GROUPS ? rows : RC_MAX_GROUPS);
   g_launches.fetch_add(1);
-  if (L.pic.bit_depth == 8) hipLaunchKernelGGL(hevcdl_recon_kernel<uint8_t>, dim3(groups), dim3(64), 0, s, L);
-  else hipLaunchKernelGGL(hevcdl_recon_kernel<uint16_t>, dim3(groups), dim3(64), 0, s, L);
+  if (std::is_same<LAUNCH, RcLaunchQp>::value) g_qp_launches.fetch_add(1);
+  if (rc_has_factor<LAUNCH>) g_sl_launches.fetch_add(1);
+  if (L.pic.bit_depth == 8) hipLaunchKernelGGL((hevcdl_recon_kernel<uint8_t, LAUNCH>), dim3(groups), dim3(64), 0, s, L);
+  else hipLaunchKernelGGL((hevcdl_recon_kernel<uint16_t, LAUNCH>), dim3(groups), dim3(64), 0, s, L);
   HIPOK(hipGetLastError());
   *d_error = L.sync + 1;
   return HEVCDL_OK;
 }
 
-// The stand-alone device form: its own work memory, allocated and freed by the call, which therefore waits for the stream (a pipeline uses the form above).
-extern "C" hevcdl_status hevcdl_reconstruct_frames_dev(int device, const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const int32_t *qps_opt,
-                                                      const void *d_records, int n_frames, void *d_recon, void *stream)
+// The stand-alone device forms: their own work memory, allocated and freed by the call, which therefore waits for the stream (a pipeline uses rc_enqueue).  The
+// scaling-list form checks its factors before it asks for the device, and carries them behind the work memory, rounded up to 16 bytes, to be freed with it.
+template <typename LAUNCH>
+hevcdl_status rc_run_dev(int device, const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, RcQuant q, const void *d_records, int n_frames, void *d_recon, void *stream)
 {
-  if (n_frames == 0 && cfg) { RcPic p; std::vector<uint32_t> u; return rc_setup(cfg, slices_opt, p, u); }
-  if (!cfg || n_frames < 0) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "null configuration or a negative picture count");
+  if constexpr (rc_has_map<LAUNCH>) { if (!cfg || n_frames < 1) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "null configuration or no picture"); }
+  else { // the constant-QP form takes no picture for a question about the configuration
+    if (n_frames == 0 && cfg) { RcPic p; std::vector<uint32_t> u; return rc_setup(cfg, slices_opt, p, u); }
+    if (!cfg || n_frames < 0) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "null configuration or a negative picture count");
+  }
+  if constexpr (rc_has_factor<LAUNCH>) { const hevcdl_status st = rc_check_scaling(q.scaling); if (st != HEVCDL_OK) return st; }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { (void)hipGetLastError(); RC_REFUSE(HEVCDL_ERR_NO_DEVICE, "no such device"); }
   HIPOK(hipSetDevice(device));
-  const size_t total = hevcdl_recon_work_bytes(cfg->width, cfg->height, n_frames);
+  const size_t need = hevcdl_recon_work_bytes(cfg->width, cfg->height, n_frames), work = rc_has_factor<LAUNCH> ? (need + 15) & ~(size_t)15 : need;
   unsigned char *d = nullptr;
-  if (hipMalloc(&d, total) != hipSuccess) { (void)hipGetLastError(); RC_REFUSE(HEVCDL_ERR_OOM, "no device memory for the row counts"); }
+  if (hipMalloc(&d, work + (rc_has_factor<LAUNCH> ? HEVCDL_SCALING_FACTOR_BYTES : 0)) != hipSuccess) { (void)hipGetLastError(); RC_REFUSE(HEVCDL_ERR_OOM, "no device memory for the row counts"); }
   std::vector<uint32_t> keep; const uint32_t *d_err = nullptr; uint32_t err = 0;
-  hevcdl_status out = hevcdl_recon_enqueue(cfg, slices_opt, qps_opt, d_records, n_frames, d_recon, d, total, stream, keep, &d_err);
+  hevcdl_status out = HEVCDL_OK;
+  if constexpr (rc_has_factor<LAUNCH>) {
+    q.d_factor = d + work;
+    if (hipMemcpyAsync(d + work, q.scaling->factor, HEVCDL_SCALING_FACTOR_BYTES, hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess) { (void)hipGetLastError(); hevcdl_parse::set_error("upload failed"); out = HEVCDL_ERR_HIP; }
+  }
+  if (out == HEVCDL_OK) out = rc_enqueue<LAUNCH>(cfg, slices_opt, q, d_records, n_frames, d_recon, d, work, stream, keep, &d_err);
   if (out == HEVCDL_OK && (hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess || hipStreamSynchronize((hipStream_t)stream) != hipSuccess)) {
     (void)hipGetLastError(); hevcdl_parse::set_error("a HIP call of the reconstruction failed"); out = HEVCDL_ERR_HIP;
   }
@@ -203,251 +255,103 @@ extern "C" hevcdl_status hevcdl_reconstruct_frames_dev(int device, const hevcdl_
   return out;
 }
 
-extern "C" hevcdl_status hevcdl_reconstruct_frames(int device, const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const int32_t *qps_opt,
-                                                  const hevcdl_ctu_record *records, int n_frames, void *recon)
+// The host-buffer forms: records, pictures and (with a map) the map behind them in one allocation, uploaded, run by the device form, the pictures downloaded.
+template <typename LAUNCH>
+hevcdl_status rc_run_host_buffers(int device, const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, RcQuant q, const hevcdl_ctu_record *records, int n_frames, void *recon)
 {
   RcPic p; std::vector<uint32_t> unit;
-  hevcdl_status st = rc_setup(cfg, slices_opt, p, unit);
+  hevcdl_status st = rc_check_host<LAUNCH>(cfg, slices_opt, q, records, n_frames, recon, p, unit);
   if (st != HEVCDL_OK) return st;
-  if (!records || !recon || n_frames < 0) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "null records or pictures");
-  if ((st = rc_check_qps(qps_opt, n_frames)) != HEVCDL_OK) return st;
-  if ((st = hevcdl_validate_records(cfg, records, n_frames)) != HEVCDL_OK) return st;      // nothing is allocated, copied or launched on QPs or records that are refused
   if (n_frames == 0) return HEVCDL_OK;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { (void)hipGetLastError(); RC_REFUSE(HEVCDL_ERR_NO_DEVICE, "no such device"); }
   HIPOK(hipSetDevice(device));
   const size_t b_rec = sizeof(hevcdl_ctu_record) * unit.size() * (size_t)n_frames, b_pic = hevcdl_frame_bytes_bd(p.W, p.H, p.bit_depth) * (size_t)n_frames;
+  const size_t b_map = rc_has_map<LAUNCH> ? unit.size() * 256 * (size_t)n_frames : 0;
   unsigned char *d = nullptr;
-  if (hipMalloc(&d, b_rec + b_pic) != hipSuccess) { (void)hipGetLastError(); RC_REFUSE(HEVCDL_ERR_OOM, "no device memory for %d pictures", n_frames); }
-  st = HEVCDL_OK;
-  if (hipMemcpy(d, records, b_rec, hipMemcpyHostToDevice) != hipSuccess || hipMemset(d + b_rec, 0, b_pic) != hipSuccess) { (void)hipGetLastError(); hevcdl_parse::set_error("upload failed"); st = HEVCDL_ERR_HIP; }
-  if (st == HEVCDL_OK) st = hevcdl_reconstruct_frames_dev(device, cfg, slices_opt, qps_opt, d, n_frames, d + b_rec, nullptr);
+  if (hipMalloc(&d, b_rec + b_pic + b_map) != hipSuccess) { (void)hipGetLastError(); RC_REFUSE(HEVCDL_ERR_OOM, "no device memory for %d pictures", n_frames); }
+  if (hipMemcpy(d, records, b_rec, hipMemcpyHostToDevice) != hipSuccess || hipMemset(d + b_rec, 0, b_pic) != hipSuccess ||
+      (rc_has_map<LAUNCH> && hipMemcpy(d + b_rec + b_pic, q.map, b_map, hipMemcpyHostToDevice) != hipSuccess)) { (void)hipGetLastError(); hevcdl_parse::set_error("upload failed"); st = HEVCDL_ERR_HIP; }
+  if (rc_has_map<LAUNCH>) q.map = d + b_rec + b_pic;
+  if (st == HEVCDL_OK) st = rc_run_dev<LAUNCH>(device, cfg, slices_opt, q, d, n_frames, d + b_rec, nullptr);
   if (st == HEVCDL_OK && hipMemcpy(recon, d + b_rec, b_pic, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); hevcdl_parse::set_error("download failed"); st = HEVCDL_ERR_HIP; }
   (void)hipFree(d);
   return st;
 }
-
-// ---- the same entry points with a QP map (hevcdl_parse_stream_qp) and the PPS chroma offsets: the QP-map instantiation of hevcdl_recon_kernel --------------------------------------------------
-namespace {
-std::atomic<unsigned long long> g_qp_launches{0};
-hevcdl_status rc_check_qp_info(const hevcdl_qp_info *q, const void *map)
-{
-  if (!q || !map) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "null QP map or hevcdl_qp_info");
-  if (q->cb_qp_offset < -12 || q->cb_qp_offset > 12 || q->cr_qp_offset < -12 || q->cr_qp_offset > 12) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "chroma QP offsets %d / %d", q->cb_qp_offset, q->cr_qp_offset);
-  return HEVCDL_OK;
-}
 } // namespace
 
-extern "C" unsigned long long hevcdl_recon_qp_launches(void) { return g_qp_launches.load(); }
+extern "C" size_t hevcdl_recon_work_bytes(int width, int height, int n_frames)
+{
+  const size_t cx = (size_t)((width + 63) >> 6), cy = (size_t)((height + 63) >> 6), n = (size_t)(n_frames > 0 ? n_frames : 0);
+  return cx * cy * 4 + n * 4 + (2 + n * cy) * 4;
+}
 
+// ---- the entry points: per form the CPU loop, the launch (recon_launch.h), the stand-alone device form, the host-buffer form and a launch counter ------------------------
+extern "C" unsigned long long hevcdl_recon_launches(void) { return g_launches.load(); }
+extern "C" hevcdl_status hevcdl_reconstruct_frames_host(const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const int32_t *qps_opt,
+                                                       const hevcdl_ctu_record *records, int n_frames, void *recon)
+{
+  return rc_host<RcLaunch>(cfg, slices_opt, { qps_opt, nullptr, nullptr, nullptr, nullptr }, records, n_frames, recon);
+}
+hevcdl_status hevcdl_recon_enqueue(const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const int32_t *qps_opt, const void *d_records, int n_frames,
+                                   void *d_recon, void *d_work, size_t work_bytes, void *stream, std::vector<uint32_t> &keep, const uint32_t **d_error)
+{
+  return rc_enqueue<RcLaunch>(cfg, slices_opt, { qps_opt, nullptr, nullptr, nullptr, nullptr }, d_records, n_frames, d_recon, d_work, work_bytes, stream, keep, d_error);
+}
+extern "C" hevcdl_status hevcdl_reconstruct_frames_dev(int device, const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const int32_t *qps_opt,
+                                                      const void *d_records, int n_frames, void *d_recon, void *stream)
+{
+  return rc_run_dev<RcLaunch>(device, cfg, slices_opt, { qps_opt, nullptr, nullptr, nullptr, nullptr }, d_records, n_frames, d_recon, stream);
+}
+extern "C" hevcdl_status hevcdl_reconstruct_frames(int device, const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const int32_t *qps_opt,
+                                                  const hevcdl_ctu_record *records, int n_frames, void *recon)
+{
+  return rc_run_host_buffers<RcLaunch>(device, cfg, slices_opt, { qps_opt, nullptr, nullptr, nullptr, nullptr }, records, n_frames, recon);
+}
+
+// with a QP map (hevcdl_parse_stream_qp) and the PPS chroma offsets: the QP-map instantiation of hevcdl_recon_kernel
+extern "C" unsigned long long hevcdl_recon_qp_launches(void) { return g_qp_launches.load(); }
 extern "C" hevcdl_status hevcdl_reconstruct_frames_qp_host(const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const hevcdl_qp_info *qp_info,
                                                           const int8_t *qp_map, const hevcdl_ctu_record *records, int n_frames, void *recon)
 {
-  RcPicQp p; std::vector<uint32_t> unit;
-  hevcdl_status st = rc_setup(cfg, slices_opt, p, unit);
-  if (st != HEVCDL_OK) return st;
-  if (!records || !recon || n_frames < 0) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "null records or pictures");
-  if ((st = rc_check_qp_info(qp_info, qp_map)) != HEVCDL_OK) return st;
-  if ((st = hevcdl_validate_records(cfg, records, n_frames)) != HEVCDL_OK) return st;
-  const size_t ctus = unit.size(), fb = hevcdl_frame_bytes_bd(p.W, p.H, p.bit_depth);
-  std::vector<RcWork> w(1);
-  p.unit = unit.data(); p.cb_off = qp_info->cb_qp_offset; p.cr_off = qp_info->cr_qp_offset;
-  for (int f = 0; f < n_frames; f++) {
-    p.recs = records + (size_t)f * ctus; p.out = (unsigned char *)recon + (size_t)f * fb; p.qp_map = qp_map + (size_t)f * ctus * 256;
-    for (int cy = 0; cy < p.ctus_y; cy++) for (int cx = 0; cx < p.ctus_x; cx++) {
-      if (p.bit_depth == 8) rc_ctu<uint8_t>(p, w[0], 0, 1, cx, cy); else rc_ctu<uint16_t>(p, w[0], 0, 1, cx, cy);
-    }
-  }
-  return HEVCDL_OK;
+  return rc_host<RcLaunchQp>(cfg, slices_opt, { nullptr, qp_info, qp_map, nullptr, nullptr }, records, n_frames, recon);
 }
-
 hevcdl_status hevcdl_recon_enqueue_qp(const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const hevcdl_qp_info *qp_info, const void *d_qp_map, const void *d_records,
                                       int n_frames, void *d_recon, void *d_work, size_t work_bytes, void *stream, std::vector<uint32_t> &keep, const uint32_t **d_error)
 {
-  RcLaunchQp L;
-  memset(&L, 0, sizeof L);
-  hevcdl_status st = rc_setup(cfg, slices_opt, L.pic, keep);
-  if (st != HEVCDL_OK) return st;
-  if (!d_records || !d_recon || !d_work || !d_error || n_frames < 1 || n_frames > (1 << 16)) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "null device pointer, or a picture count outside 1 .. 65536");
-  if ((st = rc_check_qp_info(qp_info, d_qp_map)) != HEVCDL_OK) return st;
-  if (work_bytes < hevcdl_recon_work_bytes(cfg->width, cfg->height, n_frames)) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "work memory smaller than hevcdl_recon_work_bytes");
-  hipStream_t s = (hipStream_t)stream;
-  const size_t ctus = keep.size(), rows = (size_t)n_frames * L.pic.ctus_y;
-  const size_t b_unit = ctus * 4, b_qp = (size_t)n_frames * 4, b_sync = (2 + rows) * 4;      // (the layout of hevcdl_recon_enqueue; the per-picture QPs' room stays unused)
-  unsigned char *d = (unsigned char *)d_work;
-  HIPOK(hipMemcpyAsync(d, keep.data(), keep.size() * 4, hipMemcpyHostToDevice, s));
-  HIPOK(hipMemsetAsync(d + b_unit + b_qp, 0, b_sync, s));
-  L.pic.unit = (const uint32_t *)d; L.pic.recs = (const hevcdl_ctu_record *)d_records; L.pic.out = d_recon; L.pic.qp_map = (const int8_t *)d_qp_map;
-  L.pic.cb_off = qp_info->cb_qp_offset; L.pic.cr_off = qp_info->cr_qp_offset; L.sync = (uint32_t *)(d + b_unit + b_qp);
-  L.frame_bytes = hevcdl_frame_bytes_bd(L.pic.W, L.pic.H, L.pic.bit_depth); L.n_frames = n_frames; L.ctus = (int)ctus;
-  const unsigned groups = (unsigned)(rows < RC_MAX_GROUPS ? rows : RC_MAX_GROUPS);
-  g_launches.fetch_add(1); g_qp_launches.fetch_add(1);
-  if (L.pic.bit_depth == 8) hipLaunchKernelGGL((hevcdl_recon_kernel<uint8_t, RcLaunchQp>), dim3(groups), dim3(64), 0, s, L);
-  else hipLaunchKernelGGL((hevcdl_recon_kernel<uint16_t, RcLaunchQp>), dim3(groups), dim3(64), 0, s, L);
-  HIPOK(hipGetLastError());
-  *d_error = L.sync + 1;
-  return HEVCDL_OK;
+  return rc_enqueue<RcLaunchQp>(cfg, slices_opt, { nullptr, qp_info, d_qp_map, nullptr, nullptr }, d_records, n_frames, d_recon, d_work, work_bytes, stream, keep, d_error);
 }
-
 extern "C" hevcdl_status hevcdl_reconstruct_frames_qp_dev(int device, const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const hevcdl_qp_info *qp_info,
                                                          const void *d_qp_map, const void *d_records, int n_frames, void *d_recon, void *stream)
 {
-  if (!cfg || n_frames < 1) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "null configuration or no picture");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { (void)hipGetLastError(); RC_REFUSE(HEVCDL_ERR_NO_DEVICE, "no such device"); }
-  HIPOK(hipSetDevice(device));
-  const size_t total = hevcdl_recon_work_bytes(cfg->width, cfg->height, n_frames);
-  unsigned char *d = nullptr;
-  if (hipMalloc(&d, total) != hipSuccess) { (void)hipGetLastError(); RC_REFUSE(HEVCDL_ERR_OOM, "no device memory for the row counts"); }
-  std::vector<uint32_t> keep; const uint32_t *d_err = nullptr; uint32_t err = 0;
-  hevcdl_status out = hevcdl_recon_enqueue_qp(cfg, slices_opt, qp_info, d_qp_map, d_records, n_frames, d_recon, d, total, stream, keep, &d_err);
-  if (out == HEVCDL_OK && (hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess || hipStreamSynchronize((hipStream_t)stream) != hipSuccess)) {
-    (void)hipGetLastError(); hevcdl_parse::set_error("a HIP call of the reconstruction failed"); out = HEVCDL_ERR_HIP;
-  }
-  if (out == HEVCDL_OK && err) { hevcdl_parse::set_error("a CTU row waited for the row above longer than the limit"); out = HEVCDL_ERR_HIP; }
-  if (out != HEVCDL_OK) (void)hipStreamSynchronize((hipStream_t)stream);      // nothing may still read the work memory when it is freed
-  (void)hipFree(d);
-  return out;
+  return rc_run_dev<RcLaunchQp>(device, cfg, slices_opt, { nullptr, qp_info, d_qp_map, nullptr, nullptr }, d_records, n_frames, d_recon, stream);
 }
-
 extern "C" hevcdl_status hevcdl_reconstruct_frames_qp(int device, const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const hevcdl_qp_info *qp_info,
                                                      const int8_t *qp_map, const hevcdl_ctu_record *records, int n_frames, void *recon)
 {
-  RcPic p; std::vector<uint32_t> unit;
-  hevcdl_status st = rc_setup(cfg, slices_opt, p, unit);
-  if (st != HEVCDL_OK) return st;
-  if (!records || !recon || n_frames < 0) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "null records or pictures");
-  if ((st = rc_check_qp_info(qp_info, qp_map)) != HEVCDL_OK) return st;
-  if ((st = hevcdl_validate_records(cfg, records, n_frames)) != HEVCDL_OK) return st;
-  if (n_frames == 0) return HEVCDL_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { (void)hipGetLastError(); RC_REFUSE(HEVCDL_ERR_NO_DEVICE, "no such device"); }
-  HIPOK(hipSetDevice(device));
-  const size_t b_rec = sizeof(hevcdl_ctu_record) * unit.size() * (size_t)n_frames, b_pic = hevcdl_frame_bytes_bd(p.W, p.H, p.bit_depth) * (size_t)n_frames, b_map = unit.size() * 256 * (size_t)n_frames;
-  unsigned char *d = nullptr;
-  if (hipMalloc(&d, b_rec + b_pic + b_map) != hipSuccess) { (void)hipGetLastError(); RC_REFUSE(HEVCDL_ERR_OOM, "no device memory for %d pictures", n_frames); }
-  st = HEVCDL_OK;
-  if (hipMemcpy(d, records, b_rec, hipMemcpyHostToDevice) != hipSuccess || hipMemset(d + b_rec, 0, b_pic) != hipSuccess || hipMemcpy(d + b_rec + b_pic, qp_map, b_map, hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipGetLastError(); hevcdl_parse::set_error("upload failed"); st = HEVCDL_ERR_HIP;
-  }
-  if (st == HEVCDL_OK) st = hevcdl_reconstruct_frames_qp_dev(device, cfg, slices_opt, qp_info, d + b_rec + b_pic, d, n_frames, d + b_rec, nullptr);
-  if (st == HEVCDL_OK && hipMemcpy(recon, d + b_rec, b_pic, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); hevcdl_parse::set_error("download failed"); st = HEVCDL_ERR_HIP; }
-  (void)hipFree(d);
-  return st;
+  return rc_run_host_buffers<RcLaunchQp>(device, cfg, slices_opt, { nullptr, qp_info, qp_map, nullptr, nullptr }, records, n_frames, recon);
 }
 
-// ---- the same entry points with scaling factors on top of the QP map (hevcdl_parse_stream_sl): the scaling-list instantiation of hevcdl_recon_kernel -------------------------------------------
-namespace {
-std::atomic<unsigned long long> g_sl_launches{0};
-hevcdl_status rc_check_scaling(const hevcdl_scaling_info *s)
-{
-  if (!s) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "null hevcdl_scaling_info");
-  for (int i = 0; i < HEVCDL_SCALING_FACTOR_BYTES; i++) if (!s->factor[i]) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "scaling factor %d is 0", i);
-  return HEVCDL_OK;
-}
-} // namespace
-
+// with scaling factors on top of the QP map (hevcdl_parse_stream_sl): the scaling-list instantiation of hevcdl_recon_kernel
 extern "C" unsigned long long hevcdl_recon_sl_launches(void) { return g_sl_launches.load(); }
-
 extern "C" hevcdl_status hevcdl_reconstruct_frames_sl_host(const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const hevcdl_qp_info *qp_info,
                                                           const int8_t *qp_map, const hevcdl_scaling_info *scaling, const hevcdl_ctu_record *records, int n_frames, void *recon)
 {
-  RcPicSl p; std::vector<uint32_t> unit;
-  hevcdl_status st = rc_setup(cfg, slices_opt, p, unit);
-  if (st != HEVCDL_OK) return st;
-  if (!records || !recon || n_frames < 0) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "null records or pictures");
-  if ((st = rc_check_qp_info(qp_info, qp_map)) != HEVCDL_OK) return st;
-  if ((st = rc_check_scaling(scaling)) != HEVCDL_OK) return st;
-  if ((st = hevcdl_validate_records(cfg, records, n_frames)) != HEVCDL_OK) return st;
-  const size_t ctus = unit.size(), fb = hevcdl_frame_bytes_bd(p.W, p.H, p.bit_depth);
-  std::vector<RcWork> w(1);
-  p.unit = unit.data(); p.cb_off = qp_info->cb_qp_offset; p.cr_off = qp_info->cr_qp_offset; p.factor = scaling->factor;
-  for (int f = 0; f < n_frames; f++) {
-    p.recs = records + (size_t)f * ctus; p.out = (unsigned char *)recon + (size_t)f * fb; p.qp_map = qp_map + (size_t)f * ctus * 256;
-    for (int cy = 0; cy < p.ctus_y; cy++) for (int cx = 0; cx < p.ctus_x; cx++) {
-      if (p.bit_depth == 8) rc_ctu<uint8_t>(p, w[0], 0, 1, cx, cy); else rc_ctu<uint16_t>(p, w[0], 0, 1, cx, cy);
-    }
-  }
-  return HEVCDL_OK;
+  return rc_host<RcLaunchSl>(cfg, slices_opt, { nullptr, qp_info, qp_map, scaling, nullptr }, records, n_frames, recon);
 }
-
 // d_factor: HEVCDL_SCALING_FACTOR_BYTES in device memory, non-zero bytes (the caller has checked them: hevcdl_parse_stream_sl's are by construction)
 hevcdl_status hevcdl_recon_enqueue_sl(const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const hevcdl_qp_info *qp_info, const void *d_qp_map, const void *d_factor,
                                       const void *d_records, int n_frames, void *d_recon, void *d_work, size_t work_bytes, void *stream, std::vector<uint32_t> &keep, const uint32_t **d_error)
 {
-  RcLaunchSl L;
-  memset(&L, 0, sizeof L);
-  hevcdl_status st = rc_setup(cfg, slices_opt, L.pic, keep);
-  if (st != HEVCDL_OK) return st;
-  if (!d_records || !d_recon || !d_work || !d_error || !d_factor || n_frames < 1 || n_frames > (1 << 16)) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "null device pointer, or a picture count outside 1 .. 65536");
-  if ((st = rc_check_qp_info(qp_info, d_qp_map)) != HEVCDL_OK) return st;
-  if (work_bytes < hevcdl_recon_work_bytes(cfg->width, cfg->height, n_frames)) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "work memory smaller than hevcdl_recon_work_bytes");
-  hipStream_t s = (hipStream_t)stream;
-  const size_t ctus = keep.size(), rows = (size_t)n_frames * L.pic.ctus_y;
-  const size_t b_unit = ctus * 4, b_qp = (size_t)n_frames * 4, b_sync = (2 + rows) * 4;      // (the layout of hevcdl_recon_enqueue; the per-picture QPs' room stays unused)
-  unsigned char *d = (unsigned char *)d_work;
-  HIPOK(hipMemcpyAsync(d, keep.data(), keep.size() * 4, hipMemcpyHostToDevice, s));
-  HIPOK(hipMemsetAsync(d + b_unit + b_qp, 0, b_sync, s));
-  L.pic.unit = (const uint32_t *)d; L.pic.recs = (const hevcdl_ctu_record *)d_records; L.pic.out = d_recon; L.pic.qp_map = (const int8_t *)d_qp_map; L.pic.factor = (const uint8_t *)d_factor;
-  L.pic.cb_off = qp_info->cb_qp_offset; L.pic.cr_off = qp_info->cr_qp_offset; L.sync = (uint32_t *)(d + b_unit + b_qp);
-  L.frame_bytes = hevcdl_frame_bytes_bd(L.pic.W, L.pic.H, L.pic.bit_depth); L.n_frames = n_frames; L.ctus = (int)ctus;
-  const unsigned groups = (unsigned)(rows < RC_MAX_GROUPS ? rows : RC_MAX_GROUPS);
-  g_launches.fetch_add(1); g_sl_launches.fetch_add(1);
-  if (L.pic.bit_depth == 8) hipLaunchKernelGGL((hevcdl_recon_kernel<uint8_t, RcLaunchSl>), dim3(groups), dim3(64), 0, s, L);
-  else hipLaunchKernelGGL((hevcdl_recon_kernel<uint16_t, RcLaunchSl>), dim3(groups), dim3(64), 0, s, L);
-  HIPOK(hipGetLastError());
-  *d_error = L.sync + 1;
-  return HEVCDL_OK;
+  return rc_enqueue<RcLaunchSl>(cfg, slices_opt, { nullptr, qp_info, d_qp_map, nullptr, d_factor }, d_records, n_frames, d_recon, d_work, work_bytes, stream, keep, d_error);
 }
-
-// (the factor block is uploaded behind the work memory of the call and freed with it)
 extern "C" hevcdl_status hevcdl_reconstruct_frames_sl_dev(int device, const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const hevcdl_qp_info *qp_info,
                                                          const void *d_qp_map, const hevcdl_scaling_info *scaling, const void *d_records, int n_frames, void *d_recon, void *stream)
 {
-  if (!cfg || n_frames < 1) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "null configuration or no picture");
-  { const hevcdl_status st = rc_check_scaling(scaling); if (st != HEVCDL_OK) return st; }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { (void)hipGetLastError(); RC_REFUSE(HEVCDL_ERR_NO_DEVICE, "no such device"); }
-  HIPOK(hipSetDevice(device));
-  const size_t work = (hevcdl_recon_work_bytes(cfg->width, cfg->height, n_frames) + 15) & ~(size_t)15, total = work + HEVCDL_SCALING_FACTOR_BYTES;
-  unsigned char *d = nullptr;
-  if (hipMalloc(&d, total) != hipSuccess) { (void)hipGetLastError(); RC_REFUSE(HEVCDL_ERR_OOM, "no device memory for the row counts"); }
-  std::vector<uint32_t> keep; const uint32_t *d_err = nullptr; uint32_t err = 0;
-  hevcdl_status out = HEVCDL_OK;
-  if (hipMemcpyAsync(d + work, scaling->factor, HEVCDL_SCALING_FACTOR_BYTES, hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess) { (void)hipGetLastError(); hevcdl_parse::set_error("upload failed"); out = HEVCDL_ERR_HIP; }
-  if (out == HEVCDL_OK) out = hevcdl_recon_enqueue_sl(cfg, slices_opt, qp_info, d_qp_map, d + work, d_records, n_frames, d_recon, d, work, stream, keep, &d_err);
-  if (out == HEVCDL_OK && (hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess || hipStreamSynchronize((hipStream_t)stream) != hipSuccess)) {
-    (void)hipGetLastError(); hevcdl_parse::set_error("a HIP call of the reconstruction failed"); out = HEVCDL_ERR_HIP;
-  }
-  if (out == HEVCDL_OK && err) { hevcdl_parse::set_error("a CTU row waited for the row above longer than the limit"); out = HEVCDL_ERR_HIP; }
-  if (out != HEVCDL_OK) (void)hipStreamSynchronize((hipStream_t)stream);      // nothing may still read the work memory when it is freed
-  (void)hipFree(d);
-  return out;
+  return rc_run_dev<RcLaunchSl>(device, cfg, slices_opt, { nullptr, qp_info, d_qp_map, scaling, nullptr }, d_records, n_frames, d_recon, stream);
 }
-
 extern "C" hevcdl_status hevcdl_reconstruct_frames_sl(int device, const hevcdl_stream_config *cfg, const hevcdl_slice_layout *slices_opt, const hevcdl_qp_info *qp_info,
                                                      const int8_t *qp_map, const hevcdl_scaling_info *scaling, const hevcdl_ctu_record *records, int n_frames, void *recon)
 {
-  RcPic p; std::vector<uint32_t> unit;
-  hevcdl_status st = rc_setup(cfg, slices_opt, p, unit);
-  if (st != HEVCDL_OK) return st;
-  if (!records || !recon || n_frames < 0) RC_REFUSE(HEVCDL_ERR_INVALID_ARG, "null records or pictures");
-  if ((st = rc_check_qp_info(qp_info, qp_map)) != HEVCDL_OK) return st;
-  if ((st = rc_check_scaling(scaling)) != HEVCDL_OK) return st;
-  if ((st = hevcdl_validate_records(cfg, records, n_frames)) != HEVCDL_OK) return st;
-  if (n_frames == 0) return HEVCDL_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { (void)hipGetLastError(); RC_REFUSE(HEVCDL_ERR_NO_DEVICE, "no such device"); }
-  HIPOK(hipSetDevice(device));
-  const size_t b_rec = sizeof(hevcdl_ctu_record) * unit.size() * (size_t)n_frames, b_pic = hevcdl_frame_bytes_bd(p.W, p.H, p.bit_depth) * (size_t)n_frames, b_map = unit.size() * 256 * (size_t)n_frames;
-  unsigned char *d = nullptr;
-  if (hipMalloc(&d, b_rec + b_pic + b_map) != hipSuccess) { (void)hipGetLastError(); RC_REFUSE(HEVCDL_ERR_OOM, "no device memory for %d pictures", n_frames); }
-  st = HEVCDL_OK;
-  if (hipMemcpy(d, records, b_rec, hipMemcpyHostToDevice) != hipSuccess || hipMemset(d + b_rec, 0, b_pic) != hipSuccess || hipMemcpy(d + b_rec + b_pic, qp_map, b_map, hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipGetLastError(); hevcdl_parse::set_error("upload failed"); st = HEVCDL_ERR_HIP;
-  }
-  if (st == HEVCDL_OK) st = hevcdl_reconstruct_frames_sl_dev(device, cfg, slices_opt, qp_info, d + b_rec + b_pic, scaling, d, n_frames, d + b_rec, nullptr);
-  if (st == HEVCDL_OK && hipMemcpy(recon, d + b_rec, b_pic, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); hevcdl_parse::set_error("download failed"); st = HEVCDL_ERR_HIP; }
-  (void)hipFree(d);
-  return st;
+  return rc_run_host_buffers<RcLaunchSl>(device, cfg, slices_opt, { nullptr, qp_info, qp_map, scaling, nullptr }, records, n_frames, recon);
 }

@@ -3,7 +3,8 @@
 // A restatement of what struct Engine and struct Picture of hevcdl_parse.cpp do (ITU-T H.265 9.3.4.3 and 7.3.8: sao, coding_quadtree, coding_unit with the candidate
 // modes of 8.4.2, transform_tree, residual_coding with transform skip and sign data hiding, end_of_slice_segment_flag / end_of_subset_one_bit and the alignment of every
 // sub-stream), stated so that a GPU wave can run it.  Two instantiations: hevcdl_slice_decode_kernel (slice_decode_kernel.hip) and hevcdl_parse_stream_core
-// (hevcdl_parse.cpp).  hevcdl_parse_stream is the second implementation this one is held against: same records, same SAO blocks, byte for byte.
+// (hevcdl_parse.cpp).  hevcdl_parse_stream is the second implementation this one is held against: same records, same SAO blocks, byte for byte.  Only the slice data
+// is decoded twice: the code in front of it (NAL units, parameter sets, slice headers, layouts) is one walk over the stream, walk_stream, that both run.
 //
 // What it decodes is a UNIT (SdUnit): the longest run of CTUs one decoder must walk serially -- a tile, a row slice, or a whole picture (WaveFrontSynchro rows included:
 // they are walked one after the other).  A unit is a rectangle of CTUs walked in raster order, fed by sub-streams (SdSub) out of one blob of RBSP bytes.  Neighbours

@@ -1,5 +1,5 @@
-// slice_decode_units.h -- what the host builds for the shared slice-data decoder (slice_decode_core.h) and who runs it: hevcdl_parse.cpp builds the tables with the
-// parser's own header code, hevcdl_parse_stream_core walks them on the CPU, slice_decode_kernel.hip and hevcdl_decode_stream (hevcdl_api.hip) on the device.
+// slice_decode_units.h -- what the host builds for the shared slice-data decoder (slice_decode_core.h) and who runs it: hevcdl_parse.cpp builds the tables in the one
+// walk over the stream that the parser runs too (walk_stream),hevcdl_parse_stream_core walks them on the CPU, slice_decode_kernel.hip and hevcdl_decode_stream (hevcdl_api.hip) on the device.
 #ifndef HEVCDL_SLICE_DECODE_UNITS_H
 #define HEVCDL_SLICE_DECODE_UNITS_H
 #include <stddef.h>
@@ -11,14 +11,18 @@
 
 namespace hevcdl_parse {
 
-// The pictures of a stream with their headers parsed and their slice data cut into units.  A refusal of the headers does not end the collection with nothing: the
-// pictures in front of it stay, and the refusal waits in `pending` -- hevcdl_parse_stream decodes a picture before it reads the next one's headers, so an error in the
-// slice data of an earlier picture is the one it reports, and so do the walkers of these tables.
-struct StreamUnits {
-  hevcdl_stream_config cfg; hevcdl_slice_layout slices; hevcdl_segment_layout segments;      // as hevcdl_parse_stream gives them (cfg only without a pending refusal)
-  hevcdl_sd::SdStream sd;
+// What the walk over a stream (walk_stream, hevcdl_parse.cpp) leaves behind its last picture, as hevcdl_parse_stream gives it; a refused stream leaves it unset.
+struct StreamShape {
+  hevcdl_stream_config cfg; hevcdl_slice_layout slices; hevcdl_segment_layout segments;
   hevcdl_qp_info qp = { 0, 0, 0, 0 };            // the PPS fields a QP map goes with (all 0 unless accepted)
-  hevcdl_scaling_info sl;                        // the SPS's scaling lists as factors (enabled 0 unless accepted; set with cfg)
+  hevcdl_scaling_info sl;                        // the SPS's scaling lists as factors (enabled 0 unless accepted)
+};
+// The pictures of a stream with their headers parsed and their slice data cut into units: what the walk's second sink makes of a picture where hevcdl_parse_stream's
+// decodes it.  A refusal of the headers does not end the collection with nothing: the pictures in front of it stay, and the refusal waits in `pending` --
+// hevcdl_parse_stream decodes a picture before it reads the next one's headers, so an error in the slice data of an earlier picture is the one it reports, and so
+// do the walkers of these tables.  (The StreamShape part only without a pending refusal.)
+struct StreamUnits : StreamShape {
+  hevcdl_sd::SdStream sd;
   int ctus = 0;
   std::vector<hevcdl_parsed_picture> pictures;
   std::vector<uint8_t> rbsp;                     // the slice data of every picture, emulation prevention removed, sub-stream behind sub-stream

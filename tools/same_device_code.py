@@ -1,4 +1,4 @@
-"""Is the compiled device code of the decision kernel's builds the same in two source trees?  For a change that must not change code (retiring preprocessor
+"""Is the compiled device code of the decision kernel's builds, and of the decoder's kernels, the same in two source trees?  For a change that must not change code (retiring preprocessor
 switches, host-side edits): every build below is compiled device-only for gfx950 from both trees, with build_ext's flags and one -cuid on both sides (hipcc
 derives the CUID from the source path otherwise, and it names a symbol), and the two code objects are compared byte for byte.
 usage: tools/same_device_code.py BASE_TREE [NEW_TREE]      (BASE_TREE: e.g. `git worktree add DIR HEAD~1`; NEW_TREE: this tree)
@@ -16,7 +16,8 @@ BUILDS = ([(s, ()) for s in RD] + [(s, ("HEVCDL_STAGE_TRACE",)) for s in RD] + [
                                           ("HEVCDL_KERNEL_PROF", "HEVCDL_PROF_N=64", "HEVCDL_PROF_GLUE"), ("HEVCDL_KERNEL_PROF", "HEVCDL_PROF_MASTER"),
                                           ("HEVCDL_KERNEL_DEBUG", "HEVCDL_TIMELINE"), ("HEVCDL_MICRO",), ("HEVCDL_MICRO", "HEVCDL_MICRO_T"),
                                           ("HEVCDL_MICRO", "HEVCDL_MICRO_SMALL", "HEVCDL_NW=12"))] +
-          [("hevcdl_api.hip", ())])       # the narrow and clamp kernels beside the host code
+          [("hevcdl_api.hip", ()),        # the narrow and clamp kernels beside the host code
+           ("recon_kernel.hip", ()), ("slice_decode_kernel.hip", ())])      # the decoder's kernels, each with its host entry points behind it
 
 
 def compile_one(job):

@@ -19,7 +19,7 @@ A third leg times the scaling-list instantiation: the bat
 tests/golden/sclist_file_rand.npz (tools/scaling_list_cover.py: with_scaling_lists -- test-side SPS syntax; the slice data is untouched, so the records and the work are
 the same and the pictures are not the encoder's: every digest verdict is False, and is not asserted) -- hevcdl_decode_stream with hevcdl_enable_scaling_lists against the
 constant-QP decode of the stream as it was, five calls each in alternation, and the reconstruction stage alone with and without the factors.
---keep-lines N keeps the last N lines of the file that is there (results another tool appended, e.g. a comparison against the parent commit; 4 keeps the one of section 5m).
+--keep-lines N keeps the last N lines of the file that is there (results another tool appended, e.g. a comparison against the parent commit; 8 keeps those of sections 5m and 5o).
 
     python tools/time_decode.py [--batch 8] [--width 3840 --height 2160] [--qp 32] [--cu-qp-stream FILE]
 """
